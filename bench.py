@@ -14,6 +14,12 @@ apps/texrecon/texrecon.cpp:96-127.
 Prints ONE JSON line (rank 0).  `value` = faces of the scene / max-over-ranks seconds per
 step.  N > 1 runs the SAME scene partitioned over the ranks (BASELINE.json config 4):
 "scaling": "strong".
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
+
+also writes what the last timed step computed -- labels, solver statistics, the data-cost table (a
+fixed, seeded sample of its faces when large) -- as DIR/<name>.npy (float32 / float64, at most 64 MB);
+the scene is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -434,6 +440,49 @@ def dropin_timing(cfg, reps=2, timeout_s=900):
     return last
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_FACES = 65536
+
+
+def dump_outputs(out_dir, labels, stats, table=None):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64), for output-for-output
+    comparisons of two builds on the same inputs.  labels = the labeling (all faces); stats = (name, scalar) pairs of the solver / the
+    data costs, one file each; table = the data-cost table the step left on the device -- whole if it fits the budget, else the
+    columns of a fixed, seeded sample of faces (table_faces.npy names them)."""
+    arrays = {"labels": np.asarray(labels, dtype=np.float32)}
+    arrays.update((name, np.asarray([float(v)], dtype=np.float64)) for name, v in stats)
+    if table is not None:
+        F = table.n_faces
+        cnt = np.diff(table.col_ptr.astype(np.int64))
+        if 12 * len(table.view_id) + 8 * F + arrays["labels"].nbytes <= DUMP_LIMIT_BYTES // 2:
+            faces = np.arange(F, dtype=np.int64)
+            sel = slice(None)
+        else:
+            faces = np.sort(np.random.default_rng(0).choice(F, size=min(F, DUMP_SAMPLE_FACES), replace=False))
+            n = cnt[faces]
+            first = np.cumsum(n) - n                                  # where each sampled column starts in the output
+            sel = np.repeat(table.col_ptr[faces].astype(np.int64) - first, n) + np.arange(int(n.sum()))
+        arrays["table_faces"] = faces.astype(np.float64)
+        arrays["table_counts"] = cnt[faces].astype(np.float32)
+        arrays["table_view_id"] = table.view_id[sel].astype(np.float32)
+        arrays["table_cost"] = table.cost[sel].astype(np.float32)
+        arrays["table_quality"] = table.quality[sel].astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step: %s (%s, %.1f MB)" % (out_dir, ", ".join(sorted(arrays)), total / 1e6))
+
+
+def mrf_stats(ms, nnz):
+    """the solver's statistics of one step as (name, value) pairs; the 32.32 fixed-point energy in two exact 32-bit halves"""
+    e = int(ms["energy_fixed"]) & ((1 << 64) - 1)
+    return [("energy", ms["energy"]), ("energy_fixed_hi", e >> 32), ("energy_fixed_lo", e & 0xFFFFFFFF),
+            ("sweeps", ms["sweeps"]), ("icm_iters", ms["icm_iters"]), ("nnz", nnz)]
+
+
 def run_inproc(args, cfg, max_labels):
     """`--gpus N` started WITHOUT a launcher (no WORLD_SIZE in the environment): the single-node route of the sharded path.  ONE process,
     N host threads, thread r drives the context of GPU r through csrc/shard.hip over the in-process communicator
@@ -555,6 +604,11 @@ def run_inproc(args, cfg, max_labels):
            "sharded_driver": "C++ / in-process communicator (csrc/shard.hip)", "cpu_baseline": None,
            "hardware": ("UNMEASURED ON HARDWARE: %d logical ranks time-slice ONE device (every launch of every rank serialises on it); a test of the N > 1 code path, not a scaling number" % N) if one_gpu
                        else "%d devices, one rank each" % N}
+    if args.dump_outputs is not None and args.steps > 0:
+        labels = np.zeros(F, dtype=np.uint32)
+        for o in res:
+            labels[o["own"]] = o["labels"]
+        dump_outputs(args.dump_outputs, labels, mrf_stats(mrf, r0["nnz_global"]))
     rc = 0
     if "single" in r0:
         got = np.zeros(F, dtype=np.uint32)
@@ -598,25 +652,34 @@ def main():
     ap.add_argument("--no-shuffled", action="store_true", help="skip the extra leg that runs the headline scene with faces AND vertices randomly permuted")
     ap.add_argument("--launch", default="inproc", choices=["inproc", "torchrun"],
                     help="--gpus N > 1 started without a launcher: 'inproc' = one process, one host thread per GPU, peer-push transport (the single-node route); "
-                         "'torchrun' = re-execute under torch.distributed.run, one process per GPU, RCCL")
+                         "'torchrun' = start torch.distributed.run as a child process, one process per GPU, RCCL")
     ap.add_argument("--inproc", action="store_true", help="same as --launch inproc (the default for --gpus N > 1 without a launcher)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (labels, solver statistics, the data-cost table or a "
+                         "fixed sample of it) as DIR/<name>.npy")
     args = ap.parse_args()
     args.config = int(args.config) if args.config.isdigit() else args.config
     if args.inproc:
         args.launch = "inproc"
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs is not None and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step (--steps >= 1)")
+    if args.dump_outputs is not None and (args.shard or "WORLD_SIZE" in os.environ or (args.gpus > 1 and args.launch == "torchrun")):
+        raise SystemExit("--dump-outputs: single-process runs only (--gpus 1, or --gpus N with in-process ranks)")
     def exec_torchrun():
-        # one process per GPU over RCCL: the launcher the driver would use, started from here
+        # one process per GPU over RCCL: the launcher the driver would use, started from here as a fresh child process (this
+        # process may already hold a GPU context); its exit status is this run's
         import socket
+        import subprocess
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]
         rest = [a for a in sys.argv[1:]]
         argv = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port),
                 os.path.abspath(__file__)] + rest
-        log("re-executing:", " ".join(argv))
+        log("starting:", " ".join(argv))
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, argv)
+        sys.exit(subprocess.call(argv))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and args.launch == "torchrun":
         exec_torchrun()
 
@@ -782,6 +845,10 @@ def main():
         elapsed = float(t.item())
     if world == 1 and not args.shard and args.steps > 0:   # labels / statistics of the LAST TIMED step (the profiled steps below repeat it)
         info["timed"] = dict(labels=t_lab.cpu().numpy().view(np.uint32), energy_fixed=info["mrf"]["energy_fixed"], sweeps=info["mrf"]["sweeps"], icm_iters=info["mrf"]["icm_iters"])
+        if args.dump_outputs is not None:
+            pct = info["dc"].get("percentile")
+            dump_outputs(args.dump_outputs, info["timed"]["labels"], mrf_stats(info["mrf"], info["nnz_global"]) + ([("percentile", pct)] if pct is not None else []),
+                         ctx.costs_download())
     n_prof = min(max(args.steps, 1), 3)
     ctx.set_option("profile", 1)
     for _ in range(n_prof if (args.steps > 0 and not args.pmc_child) else 0):

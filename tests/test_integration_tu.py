@@ -7,7 +7,8 @@ The SAME containers -- mve::TriangleMesh, std::vector<tex::TextureView>, tex::Da
 once through upstream's tex::calculate_data_costs (libtexref.so: the reference's code on the CPU) and once through the replacement
 translation unit (libtexdrop.so: the GPU): DataCosts columns bit-equal; tex::view_selection of the replacement writes the labels of
 this repository's solver definition (the oracle) into the UniGraph -- mapMAP itself is absent; exceptions carry
-upstream's texts.  Both libraries are built in the development container (the reference is mounted there) and travel prebuilt."""
+upstream's texts.  Both libraries are built by __graft_entry__.build() where the reference's sources are present; the tests skip
+where they were not built."""
 import ctypes as C
 import json
 import os
@@ -18,7 +19,7 @@ import pytest
 import mvs_texturing_amd as M
 import oracle_py as O
 from conftest import ROOT, get_scene
-from test_reference_pins import _ref_data_costs, _p
+from test_reference_pins import RefLib, _ref_data_costs, _p
 
 pytestmark = pytest.mark.gpu
 _REF = os.path.join(ROOT, "oracle", "_ref", "libtexref.so")
@@ -27,14 +28,10 @@ _DROP = os.path.join(ROOT, "oracle", "_ref", "libtexdrop.so")
 
 @pytest.fixture(scope="module")
 def libs():
-    if os.path.isdir("/root/reference/libs/tex"):
-        import subprocess
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "dropin"])
     if not (os.path.exists(_REF) and os.path.exists(_DROP)):
         pytest.skip("oracle/_ref/libtexref.so / libtexdrop.so not built (the reference sources are not on this machine)")
     M.load_library()                     # libmvs_viewsel.so (and the HIP runtime torch ships) first: the drop-in binds to the same one
-    return C.CDLL(_REF), C.CDLL(_DROP)
+    return RefLib(C.CDLL(_REF)), RefLib(C.CDLL(_DROP))      # (live calls only: nothing stored)
 
 
 def _view_selection_through(D, n_views, col_ptr, view_id, cost, adj_ptr, adj):

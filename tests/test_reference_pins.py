@@ -4,9 +4,16 @@ histogram.cpp (row D2) -- and sparse_table.h (row E), uni_graph.cpp (rows G / f3
 from /root/reference where they lie (oracle/Makefile target `ref`, wrappers in oracle/ref_wrap.cpp) against stand-in
 headers for the absent libraries (oracle/ref_stubs: containers + the oracle's definitions of MVE / rayint / Eigen
 arithmetic), and compared with the oracle's restatements and with the product's host-side file writers.  The GPU parity
-tests compare the HIP path with the oracle, so these rows are pinned to upstream transitively.  The library is built in
-the development container (the reference is mounted there) and travels prebuilt; the tests skip where it does not exist."""
+tests compare the HIP path with the oracle, so these rows are pinned to upstream transitively.
+
+The library can only be built where the reference's sources are present.  Every result of it these tests use is stored
+in tests/golden/reference_pins.npz, keyed by the call and its inputs: where the library is built, each call runs live AND
+must reproduce the stored result; elsewhere the stored result stands in for the call.  An output a test states its
+expectation of (the oracle's answer, the product's file) is stored as a SHA-256 digest, and replays only if that expectation
+IS the reference's output, bit for bit; the rest is stored whole (RefLib).  After a deliberate change of a case,
+re-record with the library built:  MVS_RECORD_REFERENCE_PINS=1 python -m pytest tests/test_reference_pins.py"""
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -18,33 +25,284 @@ from conftest import ROOT, get_scene
 from util_cases import random_mrf
 
 _REF = os.path.join(ROOT, "oracle", "_ref", "libtexref.so")
+_GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_pins.npz")
+
+
+class _Arr:
+    """an array argument: passed to C as its data pointer, seen by RefLib as the array (inputs are keyed by content, outputs recorded)"""
+    def __init__(self, a):
+        self.a = a
+        self._as_parameter_ = a.ctypes.data_as(C.c_void_p)
+
+
+class _Opaque:
+    """a pointer argument that is not part of a call's identity (a BVH handle, a struct array the caller keys otherwise)"""
+    def __init__(self, p):
+        self._as_parameter_ = p if isinstance(p, C.c_void_p) else C.c_void_p(p)
+
+
+class _Cb:
+    """a C callback into Python: RefLib calls `fn` itself when it replays the call that would have called it"""
+    def __init__(self, cfunc, fn):
+        self.cfunc, self.fn = cfunc, fn
+        self._as_parameter_ = C.cast(cfunc, C.c_void_p)
+
+
+def _p(a):
+    return _Arr(a)
+
+
+def _path_key(path):
+    """a file / directory argument: its base name and what it holds (a temporary directory's own name varies from run to run)"""
+    path = os.fsdecode(path)
+    h = hashlib.sha1(os.path.basename(path).encode())
+    if os.path.isfile(path):
+        h.update(b"F" + open(path, "rb").read())
+    elif os.path.isdir(path):
+        for top, dirs, files in sorted(os.walk(path)):
+            rel = os.path.relpath(top, path).encode()
+            for d in sorted(dirs):
+                h.update(b"D" + rel + b"/" + d.encode() + b"\0")
+            for f in sorted(files):
+                h.update(b"F" + rel + b"/" + f.encode() + b"\0" + open(os.path.join(top, f), "rb").read() + b"\0")
+    return h.digest()
+
+
+class _RefFn:
+    def __init__(self, owner, name):
+        self.__dict__.update(_owner=owner, _name=name)
+
+    def __setattr__(self, k, v):             # argtypes / restype go to the real function where the library is loaded
+        if self._owner.lib is not None:
+            setattr(getattr(self._owner.lib, self._name), k, v)
+
+    def __call__(self, *args, _key=b"", _expect=None, _ret_text_len=None):
+        return self._owner.call(self._name, args, _key, _expect or {}, _ret_text_len)
+
+
+class RefLib:
+    """the reference's library (oracle/_ref/libtexref.so) behind a store of its results (tests/golden/*.npz).
+    Loaded: every call runs and must reproduce its stored result (or is recorded, record=True).  Not loaded: the stored
+    result of the call with the same inputs is replayed into the caller's output arrays / files.  Calls made from inside a
+    callback are keyed by the enclosing call and their position in it.
+
+    What the caller states it expects of an output (`_expect` = {argument index: array, or bytes for a file}) is stored as
+    ONE SHA-256 digest per call over all such outputs, and is replayed only if the caller's expectation -- the array as it
+    was before the call with the expected values written over its start -- hashes to what the reference produced: the
+    caller's own comparison then holds bit for bit.  Outputs nobody states are stored whole.  The return value is stored;
+    one that is the length of a text written into argument i (`_ret_text_len` = i) depends on the path arguments inside that
+    text, so it is stored as the length of the text with the paths as placeholders and replayed as the length of the text
+    with this run's paths (error codes, < 0, as they are)."""
+
+    def __init__(self, lib, golden=None, record=False):
+        self.lib, self.golden, self.record = lib, golden, record
+        self.store = self._load(golden) if golden and os.path.exists(golden) and not record else {}
+        self.new = {}
+        self.stack = []
+        self.pending = []
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return _RefFn(self, name)
+
+    # ---- the file: one row per call, stored outputs in one byte blob ----
+    @staticmethod
+    def _load(path):
+        z = np.load(path)
+        out = {}
+        for r, k in enumerate(z["keys"]):
+            kind = int(z["ret_kind"][r])
+            ret = None if kind == 0 else int(z["ret_i"][r]) if kind == 1 else float(z["ret_f"][r])
+            out[k.decode()] = {"ret": ret, "digest": z["digest"][r].tobytes(), "full": {}}
+        keys = z["keys"]
+        for j in range(len(z["full_row"])):
+            o, n = int(z["full_off"][j]), int(z["full_len"][j])
+            out[keys[z["full_row"][j]].decode()]["full"][z["full_name"][j].decode()] = z["blob"][o:o + n].tobytes()
+        return out
+
+    def finish(self):
+        if not (self.record and self.new):
+            return
+        keys = sorted(self.new)
+        recs = [self.new[k] for k in keys]
+        kind = np.array([0 if r["ret"] is None else 2 if isinstance(r["ret"], float) else 1 for r in recs], np.int8)
+        full = [(row, name, data) for row, r in enumerate(recs) for name, data in sorted(r["full"].items())]
+        off = np.cumsum([0] + [len(d) for _, _, d in full])
+        np.savez_compressed(self.golden, keys=np.array([k.encode() for k in keys]), ret_kind=kind,
+                            ret_i=np.array([r["ret"] if kd == 1 else 0 for r, kd in zip(recs, kind)], np.int64),
+                            ret_f=np.array([r["ret"] if kd == 2 else 0.0 for r, kd in zip(recs, kind)], np.float64),
+                            digest=np.array([np.frombuffer(r["digest"], np.uint8) for r in recs], np.uint8).reshape(-1, 32),
+                            full_row=np.array([f[0] for f in full], np.int32), full_name=np.array([f[1].encode() for f in full], "S8"),
+                            full_off=off[:-1].astype(np.int64), full_len=np.diff(off).astype(np.int64),
+                            blob=np.frombuffer(b"".join(f[2] for f in full), np.uint8))
+
+    def _key(self, name, args, extra):
+        h = hashlib.sha1(name.encode() + b"\0" + extra)
+        if self.stack:
+            outer = self.stack[-1]
+            outer[1] += 1
+            h.update(outer[0].encode() + b"#%d" % outer[1])
+        for a in args:
+            if isinstance(a, _Arr):
+                h.update(b"A" + a.a.dtype.str.encode() + repr(a.a.shape).encode() + np.ascontiguousarray(a.a).tobytes())
+            elif isinstance(a, bytes):
+                h.update(b"P" + _path_key(a))
+            elif isinstance(a, (bool, int, float)):
+                h.update(b"N" + repr(a).encode())
+            elif isinstance(a, C._SimpleCData) and not isinstance(a, (C.c_void_p, C.c_char_p)):
+                h.update(b"N" + repr(a.value).encode())
+            elif isinstance(a, _Cb):
+                h.update(b"C")
+            else:
+                h.update(b"?")
+            h.update(b"\0")
+        return h.hexdigest()
+
+    @staticmethod
+    def _text(buf, paths, back):
+        """a string result (NUL-terminated in a byte array) with the path arguments of the call written as placeholders"""
+        t = bytes(buf).split(b"\0", 1)[0]
+        for i, p in sorted(paths.items(), key=lambda x: -len(x[1])):
+            t = t.replace(*((b"@@PATH%d@@" % i, p) if back else (p, b"@@PATH%d@@" % i)))
+        return t
+
+    @staticmethod
+    def _digest(parts):
+        h = hashlib.sha256()
+        for name in sorted(parts):
+            h.update(name.encode() + b"\0" + parts[name] + b"\0")
+        return h.digest() if parts else b"\0" * 32
+
+    @staticmethod
+    def _candidate(a, want):
+        """the array as it is now with the expected values written over its start"""
+        c = a.copy()
+        w = np.ascontiguousarray(want, dtype=a.dtype).reshape(-1)
+        c.reshape(-1)[:w.size] = w
+        return c
+
+    def call(self, name, args, extra, expect, ret_text_len=None):
+        if self.golden is None:                   # a plain library: nothing stored, nothing compared
+            return getattr(self.lib, name)(*args)
+        key = self._key(name, args, extra)
+        paths = {i: a for i, a in enumerate(args) if isinstance(a, bytes)}
+        if self.lib is None:
+            return self._replay(name, key, args, paths, expect, ret_text_len)
+        before = {i: a.a.copy() for i, a in enumerate(args) if isinstance(a, _Arr)}
+        files = {i: (open(p, "rb").read() if os.path.isfile(p) else None) for i, p in paths.items()}
+        self.stack.append([key, 0])
+        try:
+            ret = getattr(self.lib, name)(*args)
+        finally:
+            self.stack.pop()
+        if self.pending and not self.stack:        # (a failure inside a C callback cannot propagate through the C frames)
+            msg, self.pending = self.pending[0], []
+            pytest.fail(msg)
+        stated, full = {}, {}
+        for i, a0 in before.items():
+            a = args[i].a
+            if i in expect:
+                stated["out%d" % i] = np.ascontiguousarray(a).tobytes()
+            elif not np.array_equal(a.view(np.uint8), a0.view(np.uint8)):
+                full["out%d" % i] = self._text(a, paths, False) if paths and a.dtype == np.uint8 else np.ascontiguousarray(a).tobytes()
+        for i, p in paths.items():
+            now = open(p, "rb").read() if os.path.isfile(p) else None
+            if i in expect:
+                stated["file%d" % i] = now or b""
+            elif now is not None and now != files[i]:
+                full["file%d" % i] = now
+        kept = ret
+        if ret_text_len is not None and ret >= 0:
+            text = bytes(args[ret_text_len].a).split(b"\0", 1)[0]
+            kept = len(self._text(text, paths, False)) if ret == len(text) else -(1 << 40)     # (a length that is not the text's: never stored)
+        rec = {"ret": None if kept is None else (float(kept) if isinstance(kept, float) else int(kept)), "digest": self._digest(stated), "full": full}
+        if self.record:
+            self.new[key] = rec
+        else:
+            msg = self._check(name, key, rec)
+            if msg and self.stack:
+                self.pending.append(msg)
+            elif msg:
+                pytest.fail(msg)
+        return ret
+
+    def _check(self, name, key, rec):
+        st = self.store.get(key)
+        if st is None:
+            return "%s: no stored result for these inputs in %s (re-record: see this module's docstring)" % (name, os.path.basename(self.golden))
+        same_ret = st["ret"] == rec["ret"] or (isinstance(rec["ret"], float) and np.isnan(rec["ret"]) and np.isnan(st["ret"]))
+        if not (same_ret and st["digest"] == rec["digest"] and st["full"] == rec["full"]):
+            return "%s: the reference's result differs from the stored one (%s)" % (name, os.path.basename(self.golden))
+        return None
+
+    def _replay(self, name, key, args, paths, expect, ret_text_len=None):
+        st = self.store.get(key)
+        if st is None:
+            pytest.fail("%s: no stored result for these inputs in %s, and the reference's library is not built here" % (name, os.path.basename(self.golden)))
+        cbs = [a for a in args if isinstance(a, _Cb)]
+        if cbs:
+            self.stack.append([key, 0])
+            try:
+                for cb in cbs:
+                    cb.fn(None)
+            finally:
+                self.stack.pop()
+        cands, stated = {}, {}
+        for i, want in expect.items():
+            if isinstance(args[i], bytes):
+                cands[i] = stated["file%d" % i] = bytes(want)
+            else:
+                cands[i] = self._candidate(args[i].a, want)
+                stated["out%d" % i] = cands[i].tobytes()
+        if self._digest(stated) != st["digest"]:
+            pytest.fail("%s: the expected outputs are not what the reference produced (stored digest, %s)" % (name, os.path.basename(self.golden)))
+        for i, c in cands.items():
+            if isinstance(args[i], bytes):
+                with open(args[i], "wb") as f:
+                    f.write(c)
+            else:
+                args[i].a[...] = c
+        for k, v in st["full"].items():
+            i = int(k[4:] if k.startswith("file") else k[3:])
+            if k.startswith("file"):
+                with open(args[i], "wb") as f:
+                    f.write(v)
+            else:
+                a = args[i].a
+                if paths and a.dtype == np.uint8:
+                    t = self._text(v + b"\0", paths, True)
+                    a[:] = 0
+                    a[:len(t)] = np.frombuffer(t, np.uint8)
+                else:
+                    a[...] = np.frombuffer(v, a.dtype).reshape(a.shape)
+        if ret_text_len is not None and st["ret"] >= 0:
+            return len(bytes(args[ret_text_len].a).split(b"\0", 1)[0])
+        return st["ret"]
 
 
 @pytest.fixture(scope="module")
 def R():
-    if os.path.isdir("/root/reference/libs/tex"):
-        import subprocess
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
-    if not os.path.exists(_REF):
-        pytest.skip("oracle/_ref/libtexref.so not built (the reference sources are not on this machine)")
-    L = C.CDLL(_REF)
-    vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
-    L.ref_percentile.argtypes = [vp, u64, C.c_float, C.c_float, u32, C.c_float]; L.ref_percentile.restype = C.c_float
-    L.ref_settings_defaults.argtypes = [vp]
-    L.ref_unigraph_lists.argtypes = [u32, vp, vp, vp, vp]; L.ref_unigraph_lists.restype = u64
-    L.ref_get_subgraphs.argtypes = [u32, vp, vp, vp, u32, vp, vp]; L.ref_get_subgraphs.restype = u32
-    L.ref_tri.argtypes = [vp, vp, vp, u32, vp]
-    L.ref_valid_pixel_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u32, vp]
-    L.ref_face_info.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u32, vp, vp]
-    L.ref_vec_write.argtypes = [C.c_char_p, vp, u32]; L.ref_vec_write.restype = C.c_int
-    L.ref_vec_read.argtypes = [C.c_char_p, vp, u32]; L.ref_vec_read.restype = C.c_int64
-    L.ref_spt_write.argtypes = [C.c_char_p, u32, C.c_uint16, vp, vp, vp]; L.ref_spt_write.restype = C.c_int
-    L.ref_spt_read.argtypes = [C.c_char_p, u32, C.c_uint16, vp, vp, vp, u64]; L.ref_spt_read.restype = C.c_int64
-    return L
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    L = C.CDLL(_REF) if os.path.exists(_REF) else None
+    record = os.environ.get("MVS_RECORD_REFERENCE_PINS") == "1"
+    if L is None and (record or not os.path.exists(_GOLDEN)):
+        pytest.fail("oracle/_ref/libtexref.so is not built and tests/golden/reference_pins.npz cannot stand in for it")
+    if L is not None:
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        L.ref_percentile.argtypes = [vp, u64, C.c_float, C.c_float, u32, C.c_float]; L.ref_percentile.restype = C.c_float
+        L.ref_settings_defaults.argtypes = [vp]; L.ref_settings_defaults.restype = None
+        L.ref_unigraph_lists.argtypes = [u32, vp, vp, vp, vp]; L.ref_unigraph_lists.restype = u64
+        L.ref_get_subgraphs.argtypes = [u32, vp, vp, vp, u32, vp, vp]; L.ref_get_subgraphs.restype = u32
+        L.ref_tri.argtypes = [vp, vp, vp, u32, vp]; L.ref_tri.restype = None
+        L.ref_valid_pixel_map.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, u32, vp]; L.ref_valid_pixel_map.restype = None
+        L.ref_face_info.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, u32, vp, vp]; L.ref_face_info.restype = None
+        L.ref_vec_write.argtypes = [C.c_char_p, vp, u32]; L.ref_vec_write.restype = C.c_int
+        L.ref_vec_read.argtypes = [C.c_char_p, vp, u32]; L.ref_vec_read.restype = C.c_int64
+        L.ref_spt_write.argtypes = [C.c_char_p, u32, C.c_uint16, vp, vp, vp]; L.ref_spt_write.restype = C.c_int
+        L.ref_spt_read.argtypes = [C.c_char_p, u32, C.c_uint16, vp, vp, vp, u64]; L.ref_spt_read.restype = C.c_int64
+    lib = RefLib(L, _GOLDEN, record=record)
+    yield lib
+    lib.finish()
 
 
 def test_percentile_equals_the_reference_histogram(R):
@@ -67,7 +325,7 @@ def test_percentile_equals_the_reference_histogram(R):
 
 def test_settings_defaults_equal_the_reference_struct(R):
     out = np.zeros(3, np.int32)
-    R.ref_settings_defaults(_p(out))
+    R.ref_settings_defaults(_p(out), _expect={0: np.int32([1, 0, 1])})
     s = M.Settings()
     assert out.tolist() == [s.data_term, s.outlier_removal, s.geometric_visibility_test] == [1, 0, 1]
     st = O.settings_struct()
@@ -91,7 +349,7 @@ def test_adjacency_lists_are_reachable_unigraph_states(R):
     for name, ap, ad in _meshes():
         F = len(ap) - 1
         op = np.zeros(F + 1, np.uint32); oa = np.zeros(max(len(ad), 1), np.uint32)
-        n_edges = R.ref_unigraph_lists(F, _p(np.ascontiguousarray(ap)), _p(np.ascontiguousarray(ad)), _p(op), _p(oa))
+        n_edges = R.ref_unigraph_lists(F, _p(np.ascontiguousarray(ap)), _p(np.ascontiguousarray(ad)), _p(op), _p(oa), _expect={3: ap, 4: ad})
         assert np.array_equal(op, ap) and np.array_equal(oa[:len(ad)], ad), name
         assert n_edges * 2 == len(ad)
 
@@ -109,10 +367,11 @@ def test_get_subgraphs_equals_the_reference(R):
             lp, cp, cf = O.get_subgraphs(ap, ad, labels, n_labels)
             for lab in range(n_labels):
                 rcp = np.zeros(F + 1, np.uint32); rcf = np.zeros(max(F, 1), np.uint32)
-                nc = R.ref_get_subgraphs(F, _p(np.ascontiguousarray(ap)), _p(np.ascontiguousarray(ad)), _p(labels), lab, _p(rcp), _p(rcf))
                 c0, c1 = int(lp[lab]), int(lp[lab + 1])
-                assert nc == c1 - c0, (name, n_labels, lab)
                 base = int(cp[c0])
+                nc = R.ref_get_subgraphs(F, _p(np.ascontiguousarray(ap)), _p(np.ascontiguousarray(ad)), _p(labels), lab, _p(rcp), _p(rcf),
+                                         _expect={5: cp[c0:c1 + 1].astype(np.int64) - base, 6: cf[base:int(cp[c1])]})
+                assert nc == c1 - c0, (name, n_labels, lab)
                 assert np.array_equal(cp[c0:c1 + 1].astype(np.int64) - base, rcp[:nc + 1].astype(np.int64))
                 assert np.array_equal(cf[base:int(cp[c1])], rcf[:int(rcp[nc])])
 
@@ -127,10 +386,10 @@ def test_spt_files_are_the_reference_format(R, tmp_path):
         dc.save_to_file(ours)
     except M.viewsel.MvsError as e:   # pragma: no cover
         pytest.skip("HIP library not loadable here: %s" % e)
-    assert R.ref_spt_write(theirs.encode(), 300, 40, _p(col_ptr), _p(view_id), _p(cost)) == 0
+    assert R.ref_spt_write(theirs.encode(), 300, 40, _p(col_ptr), _p(view_id), _p(cost), _expect={0: open(ours, "rb").read()}) == 0
     assert open(ours, "rb").read() == open(theirs, "rb").read()
     cp = np.zeros(301, np.uint32); vi = np.zeros(len(view_id), np.uint16); co = np.zeros(len(cost), np.float32)
-    assert R.ref_spt_read(ours.encode(), 300, 40, _p(cp), _p(vi), _p(co), len(cost)) == len(cost)
+    assert R.ref_spt_read(ours.encode(), 300, 40, _p(cp), _p(vi), _p(co), len(cost), _expect={3: col_ptr, 4: view_id, 5: cost}) == len(cost)
     assert np.array_equal(cp, col_ptr) and np.array_equal(vi, view_id) and np.array_equal(co.view(np.uint32), cost.view(np.uint32))
     assert R.ref_spt_read(ours.encode(), 299, 40, _p(cp), _p(vi), _p(co), len(cost)) == -1      # "SparseTable has different dimension!"
 
@@ -162,7 +421,7 @@ def test_tri_equals_the_reference_class(R):
         a, b = np.zeros(5, np.float32), np.zeros(5, np.float32)
         ia, ib = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
         OL.orc_tri(_p(p), _p(a), _p(xy), 64, _p(ia))
-        R.ref_tri(_p(p), _p(b), _p(xy), 64, _p(ib))
+        R.ref_tri(_p(p), _p(b), _p(xy), 64, _p(ib), _expect={1: a, 4: ia})
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (p, a, b)
         assert np.array_equal(ia, ib), (p, xy[ia != ib])
         n_in += int(ia.sum())
@@ -199,7 +458,7 @@ def test_validity_mask_and_valid_pixel_equal_the_reference(R):
         for erode in (0, 1):
             a, b = np.zeros(len(xy), np.uint8), np.zeros(len(xy), np.uint8)
             OL.orc_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(a))
-            R.ref_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(b))
+            R.ref_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(b), _expect={6: a})
             assert np.array_equal(a, b), (w, h, erode, xy[a != b][:5])
             assert 0 < a.sum() < len(a)
         # erosion removes valid positions, the flood fill did invalidate the corner blob but not the island
@@ -214,7 +473,7 @@ def test_validity_mask_and_valid_pixel_equal_the_reference(R):
             for erode in (0, 1):
                 a, b = np.zeros(len(xy), np.uint8), np.zeros(len(xy), np.uint8)
                 OL.orc_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(a))
-                R.ref_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(b))
+                R.ref_valid_pixel_map(_p(img), w, h, erode, _p(xy), len(xy), _p(b), _expect={6: a})
                 assert np.array_equal(a, b), (name, w, h, erode)
             if name == "all_black":
                 assert a.sum() == 0
@@ -250,7 +509,7 @@ def test_get_face_info_equals_the_reference(R):
         qa, qb = np.zeros(n, np.float32), np.zeros(n, np.float32)
         ca, cb = np.zeros(3 * n, np.float32), np.zeros(3 * n, np.float32)
         OL.orc_face_info(_p(img), _p(gmi), w, h, data_term, outlier, _p(verts), n, _p(qa), _p(ca))
-        R.ref_face_info(_p(img), _p(gmi), w, h, data_term, outlier, _p(verts), n, _p(qb), _p(cb))
+        R.ref_face_info(_p(img), _p(gmi), w, h, data_term, outlier, _p(verts), n, _p(qb), _p(cb), _expect={8: qa, 9: ca})
         bad = np.nonzero(qa.view(np.uint32) != qb.view(np.uint32))[0]
         assert len(bad) == 0, (data_term, outlier, bad[:5], qa[bad[:5]], qb[bad[:5]], px[bad[:5]])
         assert np.array_equal(ca.view(np.uint32), cb.view(np.uint32)), (data_term, outlier)
@@ -269,7 +528,9 @@ def test_get_face_info_equals_the_reference(R):
         v.width, v.height, v.rgb, v.gmi, v.mask = w, h, img.ctypes.data, gmi.ctypes.data, None
         for data_term in (1, 0):
             qb = np.zeros(n, np.float32); cb = np.zeros(3 * n, np.float32)
-            R.ref_face_info(_p(img), _p(gmi), w, h, data_term, 0, _p(verts), n, _p(qb), _p(cb))
+            qa, ca = np.zeros(n, np.float32), np.zeros(3 * n, np.float32)
+            OL.orc_face_info(_p(img), _p(gmi), w, h, data_term, 0, _p(verts), n, _p(qa), _p(ca))
+            R.ref_face_info(_p(img), _p(gmi), w, h, data_term, 0, _p(verts), n, _p(qb), _p(cb), _expect={8: qa, 9: ca})
             q = C.c_float(0.0); col = (C.c_float * 3)()
             for k in range(n):
                 D.dmh_face_info(C.byref(v), data_term, 0, C.c_void_p(verts[k, 0:3].ctypes.data), C.c_void_p(verts[k, 3:6].ctypes.data),
@@ -288,20 +549,21 @@ def test_labeling_vec_files_are_the_reference_format(R, tmp_path):
     labels = np.array([0, 3, 1, 200, 65535, 7, 0], dtype=np.uint32)
     ours, theirs = str(tmp_path / "ours_labeling.vec"), str(tmp_path / "theirs_labeling.vec")
     assert L.mvs_write_labeling_vec(labels.ctypes.data, len(labels), ours.encode()) == 0
-    assert R.ref_vec_write(theirs.encode(), _p(labels), len(labels)) == 0
+    assert R.ref_vec_write(theirs.encode(), _p(labels), len(labels), _expect={0: open(ours, "rb").read()}) == 0
     assert open(ours, "rb").read() == open(theirs, "rb").read()
     back = np.zeros(16, np.uint32)
-    assert R.ref_vec_read(ours.encode(), _p(back), 16) == len(labels)
+    assert R.ref_vec_read(ours.encode(), _p(back), 16, _expect={1: labels}) == len(labels)
     assert np.array_equal(back[:len(labels)], labels)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # rows A, B, D: the reference's OWN calculate_data_costs.cpp, whole
 # ---------------------------------------------------------------------------------------------------------------------
-def _ref_data_costs(R, scene, data_term, outlier, geom, brute=False):
-    """tex::calculate_data_costs (calculate_data_costs.cpp:308-323) compiled from /root/reference, with the arithmetic of
+def _ref_data_costs(R, scene, data_term, outlier, geom, brute=False, expect=None):
+    """tex::calculate_data_costs (calculate_data_costs.cpp:308-323) of the reference, with the arithmetic of
     the ABSENT libraries supplied from outside: camera arrays, gradient-magnitude images (oracle's), and each any-hit ray
-    answered by the oracle's orc_ray_hit for the ray exactly as the reference's code set it up."""
+    answered by the oracle's orc_ray_hit for the ray exactly as the reference's code set it up.  The stored result is a digest of
+    the table: where the library is not built, `expect` = (oracle table, rays) is what stands in for it, if it IS the reference's."""
     OL = O.load()
     OL.orc_ray_hit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int]
     OL.orc_ray_hit.restype = C.c_int
@@ -317,21 +579,29 @@ def _ref_data_costs(R, scene, data_term, outlier, geom, brute=False):
     bvh = OL.orc_bvh_build(C.byref(mesh))
     cap = F * V
     col_ptr = np.zeros(F + 1, np.uint32); vid = np.zeros(cap, np.uint16); cost = np.zeros(cap, np.float32)
-    rays = C.c_uint64(0)
+    rays = np.zeros(1, np.uint64)
+    exp = {}
+    if expect is not None:
+        exp = {15: expect[0].col_ptr, 16: expect[0].view_id, 17: expect[0].cost, 19: np.array([expect[1]], np.uint64)}
+    cams = hashlib.sha1()                  # what the views hand over by pointer: cameras and pixels
+    for k in sorted(scene.cams):
+        cams.update(k.encode() + np.ascontiguousarray(scene.cams[k]).tobytes())
+    for img in scene.images:
+        cams.update(np.ascontiguousarray(img).tobytes())
     R.ref_calculate_data_costs.restype = C.c_int64
     R.ref_calculate_data_costs.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     try:
         n = R.ref_calculate_data_costs(scene.verts.shape[0], _p(scene.verts), F, _p(scene.faces), _p(scene.normals),
-                                       C.cast(views, C.c_void_p), C.cast(gptr, C.c_void_p), V,
+                                       _Opaque(C.cast(views, C.c_void_p)), _Opaque(C.cast(gptr, C.c_void_p)), V,
                                        {"area": 0, "gmi": 1}[data_term], {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier], int(geom),
-                                       C.cast(OL.orc_ray_hit, C.c_void_p), bvh, C.cast(C.pointer(mesh), C.c_void_p), int(brute),
-                                       _p(col_ptr), _p(vid), _p(cost), cap, C.cast(C.pointer(rays), C.c_void_p))
+                                       _Opaque(C.cast(OL.orc_ray_hit, C.c_void_p)), _Opaque(bvh), _Opaque(C.cast(C.pointer(mesh), C.c_void_p)), int(brute),
+                                       _p(col_ptr), _p(vid), _p(cost), cap, _p(rays), _key=cams.digest(), _expect=exp)
     finally:
         OL.orc_bvh_free(bvh)
     assert 0 <= n <= cap
-    return col_ptr, vid[:n].copy(), cost[:n].copy(), rays.value
+    return col_ptr, vid[:n].copy(), cost[:n].copy(), int(rays[0])
 
 
 _DC_CASES = [("tiny", dt, orm, gv) for dt in ("gmi", "area") for orm in ("none", "gauss_damping", "gauss_clamping") for gv in (True, False)] + \
@@ -354,8 +624,8 @@ def test_data_costs_equal_the_reference_calculate_data_costs(R, name, data_term,
     same number of rays.  The arithmetic of the absent libraries (MVE vectors / cameras / Sobel / YCbCr, rayint, Eigen)
     is the oracle's definition on both sides (oracle/ref_stubs) -- that part stays an assumption."""
     s = get_scene(name)
-    col_ptr, vid, cost, rays = _ref_data_costs(R, s, data_term, outlier, geom)
     want, stats = O.data_costs(s, data_term=data_term, outlier_removal=outlier, geometric_visibility_test=geom)
+    col_ptr, vid, cost, rays = _ref_data_costs(R, s, data_term, outlier, geom, expect=(want, stats["rays"]))
     assert np.array_equal(col_ptr, want.col_ptr)
     assert np.array_equal(vid, want.view_id)
     assert np.array_equal(cost.view(np.uint32), want.cost.view(np.uint32))
@@ -372,8 +642,8 @@ def test_data_costs_on_a_hostile_soup_equal_the_reference(R, seed, spread):
     s = soup_scene(seed, spread=spread)
     total = 0
     for data_term, outlier, geom in (("gmi", "none", True), ("area", "gauss_clamping", True), ("gmi", "gauss_damping", False), ("area", "none", True)):
-        col_ptr, vid, cost, rays = _ref_data_costs(R, s, data_term, outlier, geom)
         want, stats = O.data_costs(s, data_term=data_term, outlier_removal=outlier, geometric_visibility_test=geom)
+        col_ptr, vid, cost, rays = _ref_data_costs(R, s, data_term, outlier, geom, expect=(want, stats["rays"]))
         assert np.array_equal(col_ptr, want.col_ptr) and np.array_equal(vid, want.view_id)
         assert np.array_equal(cost.view(np.uint32), want.cost.view(np.uint32))
         assert rays == stats["rays"]
@@ -410,8 +680,8 @@ def test_outlier_detection_equals_the_reference_function(R):
         q0 = (rng.random(n).astype(np.float32) + np.float32(0.1))
         for mode in (0, 1, 2):
             qa, qb = q0.copy(), q0.copy()
-            ra = R.ref_outlier_detection(n, _p(col), _p(qa), mode)
             rb = OL.orc_outlier_detection(n, _p(col), _p(qb), mode)
+            ra = R.ref_outlier_detection(n, _p(col), _p(qa), mode, _expect={2: qb})
             assert ra == rb, (n, mode)
             assert np.array_equal(qa.view(np.uint32), qb.view(np.uint32)), (n, mode)
             if mode:
@@ -424,15 +694,32 @@ def test_outlier_detection_equals_the_reference_function(R):
 # ---------------------------------------------------------------------------------------------------------------------
 # row F: the reference's OWN view_selection.cpp (model construction + decode; mapMAP itself is absent)
 # ---------------------------------------------------------------------------------------------------------------------
-def _ref_view_selection(R, n_views, col_ptr, view_id, cost, adj_ptr, adj):
-    """tex::view_selection compiled from /root/reference.  The recording mapMAP stand-in hands the model the reference
+_MODEL_MISC = np.float64([1.0, 5, 0.01, 1, 0, 1, 1, 1, 1, 5, 1, 5, 1, 1, 1, 548923723])
+
+
+def _model_statement(col_ptr, vid, cost, adj_ptr, adj):
+    """an independent numpy statement of the model view_selection.cpp:26-81 builds: an edge i < j only between faces that both
+    have candidate views, in UniGraph list order, weight 1; label set {view_id + 1} with the table's costs, or {0} with cost 1
+    for a face nobody sees"""
+    F = len(col_ptr) - 1
+    empty = np.diff(col_ptr.astype(np.int64)) == 0
+    edges = [(i, int(j)) for i in range(F) if not empty[i] for j in adj[adj_ptr[i]:adj_ptr[i + 1]] if i < j and not empty[j]]
+    lptr = np.zeros(F + 1, np.int64); lptr[1:] = np.cumsum(np.where(empty, 1, np.diff(col_ptr.astype(np.int64))))
+    labels = np.zeros(lptr[-1], np.int32); costs = np.ones(lptr[-1], np.float32)
+    sel = np.repeat(~empty, np.diff(lptr))
+    labels[sel] = vid.astype(np.int32) + 1; costs[sel] = cost
+    return dict(empty=empty, edges=np.array(edges, np.uint32).reshape(-1, 2), lptr=lptr, labels=labels, costs=costs)
+
+
+def _ref_view_selection(R, n_views, col_ptr, view_id, cost, adj_ptr, adj, expect=None):
+    """tex::view_selection of the reference.  The recording mapMAP stand-in hands the model the reference
     built to `solve`, which checks it against an independent numpy statement of view_selection.cpp:26-81, runs the
     ORACLE's solver on that model and answers with label offsets.  Returns (labels the reference wrote into the UniGraph,
-    model facts)."""
+    model facts).  expect = (model statement, labels): what the reference's reads are expected to return (RefLib stores digests)."""
     F = len(col_ptr) - 1
-    R.ref_model_sizes.argtypes = [C.c_void_p]
-    R.ref_model_get.argtypes = [C.c_void_p] * 6
-    R.ref_model_set_offsets.argtypes = [C.c_void_p]
+    R.ref_model_sizes.argtypes = [C.c_void_p]; R.ref_model_sizes.restype = None
+    R.ref_model_get.argtypes = [C.c_void_p] * 6; R.ref_model_get.restype = None
+    R.ref_model_set_offsets.argtypes = [C.c_void_p]; R.ref_model_set_offsets.restype = None
     R.ref_view_selection.argtypes = [C.c_uint32, C.c_uint16, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_char_p, C.c_int]
     R.ref_view_selection.restype = C.c_int
@@ -440,12 +727,15 @@ def _ref_view_selection(R, n_views, col_ptr, view_id, cost, adj_ptr, adj):
 
     def solve(_user):
         try:
-            sz = np.zeros(3, np.uint64); R.ref_model_sizes(_p(sz))
+            st = expect[0] if expect else None
+            sz = np.zeros(3, np.uint64)
+            R.ref_model_sizes(_p(sz), _expect={0: np.uint64([len(st["lptr"]) - 1, len(st["edges"]), len(st["labels"])])} if st else None)
             n, E, T = (int(x) for x in sz)
             edges = np.zeros(2 * max(E, 1), np.uint32); w = np.zeros(max(E, 1), np.float32)
             lptr = np.zeros(n + 1, np.uint32); labels = np.zeros(max(T, 1), np.int32); costs = np.zeros(max(T, 1), np.float32)
             misc = np.zeros(16, np.float64)
-            R.ref_model_get(_p(edges), _p(w), _p(lptr), _p(labels), _p(costs), _p(misc))
+            R.ref_model_get(_p(edges), _p(w), _p(lptr), _p(labels), _p(costs), _p(misc),
+                            _expect={0: st["edges"], 1: np.ones(E, np.float32), 2: st["lptr"], 3: st["labels"], 4: st["costs"], 5: _MODEL_MISC} if st else None)
             edges = edges[:2 * E].reshape(-1, 2); w = w[:E]; labels = labels[:T]; costs = costs[:T]
             seen.update(n=n, edges=edges.copy(), w=w.copy(), lptr=lptr.copy(), labels=labels.copy(), costs=costs.copy(), misc=misc.copy())
             # the oracle's solver on THE MODEL: columns = label - 1 of the nodes that have views, lists = edge insertion order
@@ -476,7 +766,8 @@ def _ref_view_selection(R, n_views, col_ptr, view_id, cost, adj_ptr, adj):
     cb = C.CFUNCTYPE(C.c_int, C.c_void_p)(solve)
     out = np.zeros(F, np.uint32)
     err = C.create_string_buffer(256)
-    rc = R.ref_view_selection(F, n_views, _p(col_ptr), _p(view_id), _p(cost), _p(adj_ptr), _p(adj), C.cast(cb, C.c_void_p), _p(out), err, 256)
+    rc = R.ref_view_selection(F, n_views, _p(col_ptr), _p(view_id), _p(cost), _p(adj_ptr), _p(adj), _Cb(cb, solve), _p(out), err, 256,
+                              _expect={8: expect[1]} if expect else None)
     assert rc == 0, (err.value, seen.get("error"))
     return out, seen
 
@@ -503,23 +794,19 @@ def test_view_selection_equals_the_reference_model_and_decode(R):
     raw inputs; and upstream's decode (:120-131) writes those labels into the UniGraph."""
     for name, n_views, col_ptr, vid, cost, adj_ptr, adj in _vs_cases(R):
         F = len(col_ptr) - 1
-        got, m = _ref_view_selection(R, n_views, col_ptr, vid, cost, adj_ptr, adj)
-        empty = np.diff(col_ptr.astype(np.int64)) == 0
+        ms = _model_statement(col_ptr, vid, cost, adj_ptr, adj)
+        want, st = O.view_selection(O.CsrNp(F, n_views, col_ptr, vid, cost), adj_ptr, adj)
+        got, m = _ref_view_selection(R, n_views, col_ptr, vid, cost, adj_ptr, adj, expect=(ms, want))
+        empty = ms["empty"]
         # model == independent statement
-        want_edges = [(i, int(j)) for i in range(F) if not empty[i] for j in adj[adj_ptr[i]:adj_ptr[i + 1]] if i < j and not empty[j]]
-        assert m["n"] == F and m["edges"].tolist() == [list(e) for e in want_edges], name
+        assert m["n"] == F and m["edges"].tolist() == ms["edges"].tolist(), name
         assert (m["w"] == 1.0).all()
-        want_lptr = np.zeros(F + 1, np.int64); want_lptr[1:] = np.cumsum(np.where(empty, 1, np.diff(col_ptr.astype(np.int64))))
-        assert np.array_equal(m["lptr"], want_lptr)
-        want_labels = np.zeros(want_lptr[-1], np.int32); want_costs = np.ones(want_lptr[-1], np.float32)
-        sel = np.repeat(~empty, np.diff(want_lptr))
-        want_labels[sel] = vid.astype(np.int32) + 1; want_costs[sel] = cost
-        assert np.array_equal(m["labels"], want_labels) and np.array_equal(m["costs"].view(np.uint32), want_costs.view(np.uint32)), name
+        assert np.array_equal(m["lptr"], ms["lptr"])
+        assert np.array_equal(m["labels"], ms["labels"]) and np.array_equal(m["costs"].view(np.uint32), ms["costs"].view(np.uint32)), name
         misc = m["misc"]
         assert misc[0] == 1.0 and misc[1] == 5 and misc[2] == 0.01 and misc[3] == 1 and misc[4] == 0 and misc[5] == 1
         assert misc[6:15].tolist() == [1, 1, 1, 5, 1, 5, 1, 1, 1] and int(misc[15]) == 548923723
         # decode == the oracle's labeling of the raw inputs
-        want, st = O.view_selection(O.CsrNp(F, n_views, col_ptr, vid, cost), adj_ptr, adj)
         assert np.array_equal(got, want), name
         assert (got[empty] == 0).all() and (got[~empty] > 0).all()
         assert m["model_energy"] == st["energy_fixed"]
@@ -547,13 +834,13 @@ def test_prepare_mesh_and_adjacency_equal_the_reference_functions(R):
         verts = np.ascontiguousarray(verts, np.float32); faces = np.ascontiguousarray(faces, np.uint32)
         F = len(faces)
         fo = np.zeros((F, 3), np.uint32); no = np.zeros((F, 3), np.float32)
-        kept = R.ref_prepare_mesh(len(verts), _p(verts), F, _p(faces), _p(fo), _p(no))
         f_o, n_o = O.prepare_mesh(verts, faces)
+        kept = R.ref_prepare_mesh(len(verts), _p(verts), F, _p(faces), _p(fo), _p(no), _expect={4: f_o, 5: n_o})
         assert kept == len(f_o) and np.array_equal(fo[:kept], f_o), name
         assert np.array_equal(no[:kept].view(np.uint32), n_o.view(np.uint32)), name
         ap_o, ad_o = O.build_adjacency(faces)
         optr = np.zeros(F + 1, np.uint32); oadj = np.zeros(max(len(ad_o), 1) + 64, np.uint32)
-        edges = R.ref_build_adjacency(len(verts), F, _p(faces), _p(optr), _p(oadj), len(oadj))
+        edges = R.ref_build_adjacency(len(verts), F, _p(faces), _p(optr), _p(oadj), len(oadj), _expect={3: ap_o, 4: ad_o})
         assert edges * 2 == optr[-1]
         assert np.array_equal(optr, ap_o) and np.array_equal(oadj[:optr[-1]], ad_o), name
     s = get_scene("bumpy")
@@ -589,11 +876,11 @@ def test_scene_folder_ingest_equals_the_reference_generate_texture_views(R, tmp_
     for name, text in files.items():
         (d / name).write_bytes(text.encode())
     (d / "64x48_dir.cam").mkdir()
-    R.ref_scene_folder_views.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]; R.ref_scene_folder_views.restype = C.c_int
-    buf = C.create_string_buffer(1 << 16)
-    n = R.ref_scene_folder_views(str(d).encode(), str(tmp).encode(), buf, len(buf))
+    R.ref_scene_folder_views.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int]; R.ref_scene_folder_views.restype = C.c_int
+    buf = np.zeros(1 << 16, np.uint8)
+    n = R.ref_scene_folder_views(str(d).encode(), str(tmp).encode(), _p(buf), len(buf), _ret_text_len=2)     # (returns the text's length)
     assert n > 0, n
-    ref = json.loads(buf.value.decode())
+    ref = json.loads(bytes(buf).split(b"\0", 1)[0].decode())
     pairs = ingest.list_scene_folder(str(d))
     assert [os.path.basename(c) for c, _ in pairs] == ["64x48_%s.cam" % k for k in "abcdef"]
     assert len(ref["views"]) == len(pairs) == 6
