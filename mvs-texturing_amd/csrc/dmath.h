@@ -413,7 +413,7 @@ MVS_HD bool foot_sums_certified(const FootSetup& s, uint32_t num_samples, double
 // wave_info_kernel does with a lane group, here with one lane.  ROWS scan lines per iteration, so that as many loads are in flight
 // where the serial walk waits for every pixel in turn (its fp64 sum is a dependent chain by definition).  The caller certifies the
 // sums (foot_sums_certified) before using them.  gmi must be readable up to three bytes before / after a span (the context's padded
-// buffer).
+// buffer).  The sums are 32 bits wide: the caller walks only footprints for which foot_words_fit holds.
 MVS_HD uint32_t bytes_sum4(uint32_t v, uint32_t acc) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sad_u8(v, 0u, acc);
@@ -457,6 +457,13 @@ MVS_HD void foot_walk_gmi_words(const ViewParams& view, const FootSetup& s, uint
         }
     }
     *num_samples = n; *gmi_sum = g;
+}
+// True when the u8 sum of any footprint inside the bounding box of `s` fits 32 bits, 255 x pixels <= 2^32 - 1 = 255 x 16843009.
+// A footprint has fewer than (h + 2) scan lines (y from floor(min y) to below ceil(max y)) of fewer than (w + 2) pixels (foot_row:
+// both span ends lie in [min x, max x]), h, w the extents of the box; the fp32 product is compared with 2^24, 0.4 % below the
+// limit, far more than its rounding.  (A triangle in a 45 MP image can cover 22 M pixels.)
+MVS_HD bool foot_words_fit(const FootSetup& s) {
+    return ((s.aabb_max_y - s.aabb_min_y) + 2.0f) * ((s.aabb_max_x - s.aabb_min_x) + 2.0f) < 16777216.0f;
 }
 
 constexpr float FOOT_DEFERRED = -1.0f;   // quality marker: "sampled by the wave-per-footprint kernel" (qualities are >= 0)

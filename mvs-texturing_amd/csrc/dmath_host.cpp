@@ -157,10 +157,11 @@ uint64_t dmh_isqrt_mismatches(uint32_t n_max) {
 // the integer word walk of the footprint samplers (foot_walk_gmi_words, 2 / 3 / 4 scan lines per iteration) against the plain loop over
 // the same spans, on random triangles in random images whose width is NOT a multiple of four (every alignment of a span's first and
 // last word occurs).  out[0] = trials with a sampled `fast` footprint, out[1] = disagreements in (pixel count, sum) -- must be 0,
-// out[2] = pixels walked
+// out[2] = pixels walked, out[3] = footprints with more pixels than the bound foot_words_fit relies on, (box height + 2) x
+// (box width + 2) -- must be 0
 void dmh_word_walk_trials(uint64_t seed, uint32_t trials, uint64_t* out) {
-    uint64_t n_fast = 0, n_bad = 0, n_px = 0;
-#pragma omp parallel for schedule(dynamic, 64) reduction(+ : n_fast, n_bad, n_px)
+    uint64_t n_fast = 0, n_bad = 0, n_px = 0, n_over = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(+ : n_fast, n_bad, n_px, n_over)
     for (uint32_t t = 0; t < trials; ++t) {
         uint64_t x = seed * 0x9E3779B97F4A7C15ull + (uint64_t)t * 0xD1B54A32D192ED03ull + 1ull;
         auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
@@ -190,8 +191,9 @@ void dmh_word_walk_trials(uint64_t seed, uint32_t trials, uint64_t* out) {
         foot_walk_gmi_words<2>(vp, s, &n[0], &g[0]); foot_walk_gmi_words<3>(vp, s, &n[1], &g[1]); foot_walk_gmi_words<4>(vp, s, &n[2], &g[2]);
         ++n_fast; n_px += n0;
         for (int k = 0; k < 3; ++k) n_bad += (n[k] != n0 || g[k] != g0);
+        n_over += (double)n0 > ((double)s.aabb_max_y - s.aabb_min_y + 2.0) * ((double)s.aabb_max_x - s.aabb_min_x + 2.0);
     }
-    out[0] = n_fast; out[1] = n_bad; out[2] = n_px;
+    out[0] = n_fast; out[1] = n_bad; out[2] = n_px; out[3] = n_over;
 }
 
 }  // extern "C"

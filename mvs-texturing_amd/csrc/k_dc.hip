@@ -192,10 +192,12 @@ __global__ void __launch_bounds__(256, WORDS ? 6 : 1) info_kernel(const float* _
                         if (fs.area > defer_area) fi.quality = FOOT_DEFERRED;
                         else {
                             foot_edges(fs);
+                            // (a footprint whose 32-bit sum could wrap goes to the lane group, which totals in 64 bits)
+                            const bool walk = fs.fast && foot_words_fit(fs);
                             uint32_t n = 0, g = 0;
-                            if (fs.fast) foot_walk_gmi_words(view, fs, &n, &g);
+                            if (walk) foot_walk_gmi_words(view, fs, &n, &g);
                             const double CG = (double)g / 255.0;
-                            if (fs.fast && foot_sums_certified<1, false>(fs, n, 0.0, 0.0, 0.0, CG, cert_shift)) foot_finish<1, false>(view, fs, n, 0.0, 0.0, 0.0, CG, &fi);
+                            if (walk && foot_sums_certified<1, false>(fs, n, 0.0, 0.0, 0.0, CG, cert_shift)) foot_finish<1, false>(view, fs, n, 0.0, 0.0, 0.0, CG, &fi);
                             else fi.quality = FOOT_DEFERRED;
                         }
                     } else foot_finish<1, false>(view, fs, 0u, 0.0, 0.0, 0.0, 0.0, &fi);
@@ -258,8 +260,14 @@ __global__ void __launch_bounds__(256) wave_info_kernel(const float* __restrict_
     foot_edges(s);
     const int w = view.width;
     const uint8_t* image = view.rgb; const uint8_t* gimg = view.gmi;
-    uint32_t n = 0, c0 = 0, c1 = 0, c2 = 0, g = 0;             // per-lane integer sums: <= 255 * (pixels / 16) each
-    const int y_begin = (int)floorf(s.aabb_min_y), y_end = act ? (int)ceilf(s.aabb_max_y) : y_begin;   // (float)y < ceilf(max): y < an integer-valued float
+    // Per-lane integer sums, <= 255 x (the lane's pixels).  A lane takes every second scan line of the footprint (2 x 8 arrangement;
+    // a narrow one: every 16th) and of each line at most (span + 3) / 8 + 4 pixels (words of four, 32 bytes apart; narrow: the whole
+    // span, < 98 pixels), span <= box width + 1, lines <= box height + 2.  So they fit 32 bits (255 x pixels < 2^32) where
+    // (height + 4) / 2 x ((width + 4) / 8 + 4) < 2^24, for footprints up to ~ 270 M pixels; a larger one (an image above 500 MP) is
+    // not summed here but re-walked serially in fp64.  The group's totals reach 16 x a lane's: they are formed in 64 bits.
+    const bool lanes_fit = (0.5f * ((s.aabb_max_y - s.aabb_min_y) + 4.0f)) * (0.125f * ((s.aabb_max_x - s.aabb_min_x) + 4.0f) + 4.0f) < 16777216.0f;
+    uint32_t n = 0, c0 = 0, c1 = 0, c2 = 0, g = 0;
+    const int y_begin = (int)floorf(s.aabb_min_y), y_end = (act && lanes_fit) ? (int)ceilf(s.aabb_max_y) : y_begin;   // (float)y < ceilf(max): y < an integer-valued float
     // Blocks of 16 scan lines: lane r of the group evaluates the span of line yb + r ONCE (foot_row: two correctly rounded divisions),
     // the steps below fetch their line's span from that lane -- one pair of divisions per line instead of one per lane and line
     const bool words = DATA_TERM == 1 && !OUTLIER && s.fast;   // group-uniform
@@ -340,17 +348,20 @@ __global__ void __launch_bounds__(256) wave_info_kernel(const float* __restrict_
             }
         }
     }
+    // group totals: 64 bits for the value sums (a footprint of 16.9 M pixels of 255 passes 2^32), 32 bits for the pixel count
+    unsigned long long tg = g, t0 = c0, t1 = c1, t2 = c2;
     for (int o = GL / 2; o > 0; o >>= 1) {
-        n += __shfl_xor(n, o, GL); g += __shfl_xor(g, o, GL);
-        if (OUTLIER) { c0 += __shfl_xor(c0, o, GL); c1 += __shfl_xor(c1, o, GL); c2 += __shfl_xor(c2, o, GL); }
+        n += __shfl_xor(n, o, GL); tg += __shfl_xor(tg, o, GL);
+        if (OUTLIER) { t0 += __shfl_xor(t0, o, GL); t1 += __shfl_xor(t1, o, GL); t2 += __shfl_xor(t2, o, GL); }
     }
     uint32_t cnt[2] = {0, 0};   // zero quality, survivors
     if (sub == 0 && act) {
         FaceInfoOut fi; fi.quality = 0.0f; fi.mean_color[0] = fi.mean_color[1] = fi.mean_color[2] = 0.0f;
         // integer sums, one division each -- and a certificate that the result equals the reference's serial fp64 walk bit for bit
         // (dmath.h foot_sums_certified); the footprints it cannot decide (~ n 2^-28 of them) go to rewalk_info_kernel
-        const double C0 = (double)c0 / 255.0, C1 = (double)c1 / 255.0, C2 = (double)c2 / 255.0, CG = (double)g / 255.0;
-        const bool certified = foot_sums_certified<DATA_TERM, OUTLIER>(s, n, C0, C1, C2, CG, cert_shift);
+        // (totals below 2^53: exact as doubles)
+        const double C0 = (double)t0 / 255.0, C1 = (double)t1 / 255.0, C2 = (double)t2 / 255.0, CG = (double)tg / 255.0;
+        const bool certified = lanes_fit && foot_sums_certified<DATA_TERM, OUTLIER>(s, n, C0, C1, C2, CG, cert_shift);
         if (!certified) rewalk[atomicAdd(&counters[C_REWALK], 1ull)] = k;   // left to rewalk_info_kernel (keeps the serial walker's registers out of this kernel)
         else {
             foot_finish<DATA_TERM, OUTLIER>(view, s, n, C0, C1, C2, CG, &fi);

@@ -392,18 +392,20 @@ def test_integer_word_walk_reads_exactly_the_span_pixels():
     """dmath.h foot_walk_gmi_words (the one-lane walk of info_kernel; the lane-group kernel uses the same masks): aligned 32-bit words
     with the bytes outside a span masked, against the plain pixel loop over the spans of foot_row (texture_view.cpp:187-219) -- same
     pixel count and the same integer sum for 2, 3 and 4 scan lines per iteration, on 300 000 random triangles in images of every
-    width modulo 4."""
+    width modulo 4.  No footprint has more pixels than the box bound under which info_kernel lets one lane sum 32 bits
+    (dmath.h foot_words_fit)."""
     import ctypes as C
     path = os.path.join(ROOT, "mvs-texturing_amd", "csrc", "libmvs_dmath_host.so")
     if not os.path.exists(path):
         pytest.skip("libmvs_dmath_host.so not built")
     L = C.CDLL(path)
     L.dmh_word_walk_trials.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
-    out = (C.c_uint64 * 3)()
+    out = (C.c_uint64 * 4)()
     L.dmh_word_walk_trials(5, 300000, out)
-    fast, bad, px = [int(v) for v in out]
+    fast, bad, px, over = [int(v) for v in out]
     assert fast > 200000 and px > 20 * fast, (fast, px)
     assert bad == 0, (fast, bad)
+    assert over == 0, (fast, over)
 
 
 def test_bench_refuses_a_launcher_whose_world_size_disagrees_with_gpus():
