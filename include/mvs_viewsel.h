@@ -263,19 +263,37 @@ void mvs_ctx_destroy(mvs_ctx* ctx);
 /* hipStream_t to launch on from now on (NULL = the device's default stream); a fresh context owns a private stream */
 mvs_status mvs_ctx_set_stream(mvs_ctx* ctx, void* hip_stream);
 mvs_status mvs_ctx_synchronize(mvs_ctx* ctx);
-/* integer options: "stats" (0/1: fill the cull-reason counters of mvs_dc_stats; default 0), "count_rays" (0/1: node visits, triangles fetched
- * and leaf rounds of the occlusion rays into mvs_dc_stats), "verbose" (0/1), "profile" (0/1), "info_wave_area" (sampled footprints above this
- * many pixels are summed by a 16-lane group under an exactness certificate; default 32, 0 = every footprint in the reference's serial order;
- * identical results), "info_wave_area_words" (the same threshold where "info_words" applies -- the gradient term without outlier removal: default 384), "info_words" (1 = the default: the smaller footprints of the gradient term are read four pixels per load and summed
- * as integers under the same certificate, by one lane each; 0 = their serial fp64 walk; identical results), "max_labels" (label-space compression, 0 = off = the reference's model), "mrf_lag" (sweeps the host queues ahead of
- * the energy reports it reads, default 1; identical results), "mrf_graph" (1 = the sweep loop is replayed from a hipGraph, the default;
- * identical results), tuning knobs "mrf_xcd", "mrf_blocks_per_cu", "mrf_late_old", "mrf_run_pad" (4 | 16), "ray_xcd", "prep_fused" (1 = luminance +
- * Sobel in one pass through LDS, the default; identical output), "face_order" (1 = the library lays the faces out along a Hilbert curve, the
- * default; 0 = the caller's face numbering is kept; identical results), "shard_peer_push" (sharded sweep loop: 1 = boundary runs are stored straight into the
- * neighbours' arrays where the communicator's ranks can address each other's memory, the default; 0 = pack / exchange / unpack through the
- * communicator; must agree on all ranks; identical results), "mrf_wide" (1 = nodes whose neighbourhood columns hold 33 .. 64 labels are swept
- * with 8 lanes x 8 labels per node, the default; 0 = 16 lanes x 4 labels; environment MVS_MRF_WIDE; takes effect with the next solve;
- * identical results), test hooks "info_cert_shift", "mrf_force_generic" */
+/* integer options (any other name is MVS_ERR_INVALID).  Only "max_labels" changes results; every other option leaves tables, labels and
+ * energies bit for bit as they are.
+ *   diagnostics:
+ *     "stats"                 0/1, default 0: fill the cull-reason counters of mvs_dc_stats; costs atomics
+ *     "count_rays"            0/1, default 0: node visits, triangles fetched and leaf rounds of the occlusion rays into mvs_dc_stats
+ *     "verbose"               0/1, default 0: progress on stderr
+ *     "profile"               0/1, default 0: per-stage GPU times for mvs_ctx_get_profile
+ *   the model:
+ *     "max_labels"            default 0 = off = the reference's model; 1 .. 65535: label-space compression (CHANGES RESULTS)
+ *   data costs:
+ *     "info_wave_area"        default 32 (environment MVS_INFO_WAVE_AREA): sampled footprints above this many pixels are summed by a
+ *                             16-lane group under an exactness certificate; 0 = every footprint in the reference's serial order
+ *     "info_words"            0/1, default 1: the smaller footprints of the gradient term are read four pixels per load and summed as
+ *                             integers under the same certificate, by one lane each; 0 = their serial fp64 walk
+ *     "info_wave_area_words"  default 384: the "info_wave_area" threshold where "info_words" applies
+ *     "info_cert_shift"       default 0: test hook, widens the certificate by this many bits (forces the serial fallback)
+ *     "prep_fused"            0/1, default 1: luminance + Sobel in one pass through LDS; 0 = two passes
+ *     "face_order"            0/1, default 1: the library lays the faces out along a Hilbert curve; 0 = the caller's face numbering is kept
+ *     "bvh_window"            default 262144: upper levels of the face order are cut exactly inside aligned windows of this many faces
+ *                             (rounded up to a power of two); 0 = the whole mesh, 1 = no upper-level cuts
+ *     "bvh_upper_min_faces"   default 1000000 (environment MVS_BVH_UPPER_MIN_FACES): smaller meshes keep the curve order above the window
+ *     "ray_xcd"               0/1, default 1: XCD-aware block order of the occlusion-ray kernel
+ *   solver:
+ *     "mrf_lag"               default 1: sweeps the host queues ahead of the energy reports it reads
+ *     "mrf_graph"             0/1, default 1: the sweep loop is replayed from a hipGraph; 0 = direct launches
+ *     "mrf_xcd"               0/1, default 1: XCD-aware block order of the sweep kernels
+ *     "mrf_blocks_per_cu"     default 0 = at most as many blocks per fast sweep launch as are resident; n > 0: at most 256 n
+ *     "mrf_force_generic"     0/1, default 0: test hook, every node takes the generic sweep kernel
+ *     "shard_peer_push"       0/1, default 1 (sharded sweep loop; must agree on all ranks): boundary runs are stored straight into the
+ *                             neighbours' arrays where the communicator's ranks can address each other's memory; 0 = pack / exchange /
+ *                             unpack through the communicator */
 mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value);
 
 /* with option "profile": per-stage GPU time from hipEvents recorded on the context's stream,
@@ -370,7 +388,7 @@ typedef struct mvs_mrf_progress {
 /* The sweep is colour-phased Gauss-Seidel: the adjacency graph is coloured at set-up (n_phases colours, each an independent set) and
  * one sweep = for phase in 0 .. n_phases - 1: the nodes of that colour recompute their outgoing messages in place. */
 mvs_status mvs_ctx_mrf_num_phases(mvs_ctx* ctx, uint32_t* n_phases);
-/* diagnostics of the last mvs_ctx_view_selection calls of this context: out[0] = hipGraph launches of the sweep loop (two sweeps each;
+/* diagnostics of the last mvs_ctx_view_selection calls of this context: out[0] = hipGraph launches of the sweep loop (four sweeps each;
  * option "mrf_graph", default 1), out[1] = re-captures pushed into the executable graph with hipGraphExecUpdate, out[2] = graph
  * instantiations, out[3] = nodes the sweep routes to the generic kernel (degree > 3 or a column of > 255 labels at or next to the node) */
 mvs_status mvs_ctx_mrf_diagnostics(mvs_ctx* ctx, uint32_t out[4]);

@@ -185,13 +185,13 @@ uint64_t csr_fingerprint(const mvs_csr* c) {
 bool stash_enabled() { const char* e = getenv("MVS_KEEP_TABLE"); return !(e && e[0] == '0'); }
 }  // namespace
 
-// Captures two sweeps + steps (whatever `one_sweep` launches) on the context's private capture stream and makes ctx->sweep_exec
+// Captures n_sweeps sweeps + steps (whatever `one_sweep` launches) on the context's private capture stream and makes ctx->sweep_exec
 // launch exactly that.  The capture executes nothing; host-side counters the launches advance are restored.  The graph is
 // re-captured for every solve (a dozen launches into a capturing stream) and pushed into the existing executable graph with
 // hipGraphExecUpdate; only a changed topology (another number of node classes per colour) instantiates a new one.
 // Returns false -- the caller then keeps launching directly -- if the runtime refuses any step.
 template <class Sweep>
-static bool prepare_sweep_graph(mvs_ctx* ctx, Sweep&& one_sweep, int n_sweeps = 2) {
+static bool prepare_sweep_graph(mvs_ctx* ctx, Sweep&& one_sweep, int n_sweeps) {
     if (!ctx->cap_stream && hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->mrf_graph = 0; return false; }
     const uint32_t steps0 = ctx->steps_issued, sweep0 = ctx->m_sweep_no;
     hipStream_t user = ctx->stream;
@@ -342,7 +342,6 @@ mvs_status mvs_ctx_create(int device, mvs_ctx** out) {
     // MVS_INFO_WAVE_AREA overrides the default footprint area above which the lane-group sampler takes over (0: every
     // footprint in the reference's serial fp64 order, i.e. bit-exact qualities); mvs_set_option("info_wave_area") still wins
     if (const char* e = getenv("MVS_INFO_WAVE_AREA")) c->info_wave_area = std::max(0, atoi(e));
-    if (const char* e = getenv("MVS_MRF_WIDE")) c->mrf_wide = atoi(e) != 0;   // (A/B of the sweep kernel variants without touching callers)
     if (const char* e = getenv("MVS_BVH_UPPER_MIN_FACES")) c->bvh_upper_min_faces = (uint32_t)std::max(0ll, atoll(e));   // (test runs: 0 puts every mesh of the suite through the upper levels of the face order)
     c->counters.ensure(64);
     *out = c;
@@ -404,14 +403,8 @@ mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value) {
     else if (n == "mrf_lag") ctx->mrf_lag = (int)value;
     else if (n == "shard_peer_push") ctx->shard_peer_push = value != 0;
     else if (n == "mrf_force_generic") ctx->mrf_force_generic = value != 0;
-    else if (n == "mrf_wide") ctx->mrf_wide = value != 0;   // takes effect with the next solve's set-up
     else if (n == "mrf_graph") ctx->mrf_graph = value != 0;
-    else if (n == "mrf_late_old") ctx->mrf_late_old = (int)value;
-    else if (n == "mrf_damp_period") ctx->mrf_damp_period = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64));
-    else if (n == "mrf_run_pad") ctx->mrf_run_pad = (value == 16) ? 16 : 4;
     else if (n == "mrf_blocks_per_cu") ctx->mrf_blocks_per_cu = std::max(0, (int)value);
-    else if (n == "bvh_caller_order") ctx->bvh_caller_order = value != 0;
-    else if (n == "dc_overlap_prep") ctx->dc_overlap_prep = value != 0;
     else if (n == "bvh_upper_min_faces") { ctx->kd_disabled = false; ctx->bvh_upper_min_faces = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 0xFFFFFFFFll)); ctx->order_pinned = false; }
     else if (n == "bvh_window") { ctx->kd_disabled = false; ctx->bvh_window = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 0x40000000)); ctx->order_pinned = false; }   // 0 = whole mesh, 1 = no upper-level cuts; otherwise rounded up to a power of two by the builder
     else if (n == "face_order") { ctx->face_order = value != 0 ? 1 : 0; ctx->order_pinned = false; }   // takes effect with the next data-cost pass (the active table keeps the order it was made in)
@@ -687,30 +680,12 @@ static void read_energy(mvs_ctx* ctx, uint64_t out[2]) {
 
 // The solver's host loop (single GPU): sweeps with exact-energy tracking, the
 // stop rule mirroring StopWhenReturnsDiminish (view_selection.cpp:84), ICM polish.
-// ICM polish of the best labeling (whole graph): rounds of gain + apply until a round moves nothing or max_iters rounds ran.
-// Returns the index of the round that moved nothing (max_iters if none did) -- the oracle's loop counter.  The "moved" counts
-// come back through a pinned ring, `lag` rounds late: the host queues round k + lag before it reads round k's count, so the
-// GPU never idles on a round trip; a round queued after the one that moved nothing finds an empty active list and no winner,
-// i.e. changes nothing.
+// ICM polish of the best labeling (whole graph): rounds of gain + apply (see icm_rounds)
 static int icm_polish(mvs_ctx* ctx, uint32_t F, int max_iters) {
-    constexpr int R = (int)mvs_ctx::ICM_RING, LAG = 2;
-    ensure_report_ring(ctx);
-    int issued = 0, polled = 0, stop = -1;
-    uint32_t seq0 = ctx->icm_seq;
-    auto poll = [&]() { const int k = polled++; wait_report(ctx, mvs_ctx::RING + (uint32_t)(k % R), seq0 + (uint32_t)k + 1u); if (stop < 0 && ctx->h_icm[k % R] == 0u) stop = k; };
-    ProfChain pc(ctx);
-    while (issued < max_iters && stop < 0) {
-        pc.begin();
+    return icm_rounds(ctx, max_iters, ctx->m_moved.p, [&](int) {
         mrf_icm_gain(ctx, 0, F);
         mrf_icm_apply(ctx, 0, F);   // in place: winners form an independent set
-        report_u32(ctx, ctx->m_moved.p, ctx->d_icm + issued % R, mvs_ctx::RING + (uint32_t)(issued % R), seq0 + (uint32_t)issued + 1u);
-        pc.mark("mrf_icm");
-        ++issued;
-        if (issued - polled > LAG) poll();
-    }
-    while (polled < issued) poll();
-    ctx->icm_seq = seq0 + (uint32_t)issued;
-    return stop >= 0 ? stop : max_iters;
+    });
 }
 
 mvs_status mvs_ctx_view_selection(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device,
@@ -728,10 +703,10 @@ mvs_status mvs_ctx_view_selection(mvs_ctx* ctx, const uint32_t* adj_ptr, const u
     // The stop rule runs on the device (mrf_step); the host only polls the report of `lag` sweeps ago, so the next
     // sweep is already queued when a sweep's energy becomes known.  Sweeps issued after the rule fired are no-ops
     // for the result (the best labeling is frozen on the device).
-    // reports outstanding at any time: lag + 2 with direct launches, up to lag + 4 under graph replay (a graph issues two steps before
+    // reports outstanding at any time: lag + 2 with direct launches, up to lag + 2 GS under graph replay (a graph issues GS steps before
     // the host polls, and one more graph stays queued behind it): the ring of RING slots must hold them all
-    // sweeps per graph = one period of the damping schedule (2: a damped and an undamped sweep)
-    const int GS = ctx->mrf_damp_period > 2 ? ctx->mrf_damp_period : 2;
+    // sweeps per graph = one period of the damping schedule (a damped sweep and three undamped ones)
+    constexpr int GS = (int)MRF_DAMP_PERIOD;
     const int lag = std::max(0, std::min(ctx->mrf_lag, (int)mvs_ctx::RING - 2 * GS - 1));
     mvs_mrf_progress pg; memset(&pg, 0, sizeof(pg));
     auto report = [&](uint32_t n) {
@@ -749,12 +724,12 @@ mvs_status mvs_ctx_view_selection(mvs_ctx* ctx, const uint32_t* adj_ptr, const u
         mrf_step(ctx, nullptr);
         pc.mark("mrf_energy");
     };
-    // Sweeps 1 and 2 are launched directly.  From sweep 3 on the loop replays a hipGraph of TWO sweeps (a damped odd one, an undamped
-    // even one) with their steps: a small problem's sweep is a handful of 3 - 10 us kernels, and launching them one by one is bound by
+    // Sweeps 1 .. 4 are launched directly.  From sweep 5 on the loop replays a hipGraph of one damping period, FOUR sweeps (a damped
+    // one, three undamped ones), with their steps: a small problem's sweep is a handful of 3 - 10 us kernels, and launching them one by one is bound by
     // the host's ~3.5 us per launch (MI355X_MICROARCH.md "graph-replay-floor"), not by the GPU.  Every launch of the loop has
     // the same arguments each time (the step kernel numbers its reports itself), sweeps queued after the device-side stop rule fired
     // end at their first instruction, so replaying past the stop costs microseconds.  Not while profiling (stage marks are events).
-    bool graphs = ctx->mrf_graph != 0 && !ctx->profile && P.max_sweeps >= 3 * GS && F > 0 && GS <= 4;
+    bool graphs = ctx->mrf_graph != 0 && !ctx->profile && P.max_sweeps >= 3 * GS && F > 0;
     while (issued < std::min(GS, P.max_sweeps) && !pg.stopped) {
         one_sweep(); ++issued;
         if (issued - lag > polled) report((uint32_t)++polled);

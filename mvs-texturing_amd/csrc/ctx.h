@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -126,14 +127,12 @@ struct mvs_ctx {
     bool prep_fused = true;  // image prep: luminance + Sobel in one pass through LDS (false: the two-pass kernels; identical output)
     bool stats = false;      // fill the cull-reason counters of mvs_dc_stats (diagnostics; costs atomics)
     bool count_rays = false;
-    bool dc_overlap_prep = true;     // dc_phase1: image preparation on a second stream beside the face order + BVH build
     uint32_t* h_kd_flags = nullptr; int kd_pending = 0; bool kd_disabled = false;   // k_kdorder.hip: per-level overflow words (pinned), levels awaiting scene_order_commit, "this mesh keeps the curve order"
     uint32_t* h_rb = nullptr; uint32_t* d_rb = nullptr; uint32_t rb_seq = 0;   // read_words() / read_block(): 64 data words, the sequence number, 4 KB of staging -- pinned
     hipStream_t aux_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the image preparation runs beside the face order + BVH build (k_dc.hip dc_phase1)
     uint32_t bvh_upper_min_faces = 1000000;   // meshes below this many faces keep the Hilbert order above the LDS window (k_bvh.hip build_scene_order)
     uint32_t bvh_window = 262144;    // upper levels of the face order: exact top-down median cuts inside aligned windows of this many positions of the Hilbert order (k_kdorder.hip); 0 = the whole mesh, 1 = none
     mvs::DBuf<float> kd_c[2][3]; mvs::DBuf<uint32_t> kd_id[2], kd_hist, kd_cursor, kd_tie, kd_pivot, kd_box;   // k_kdorder.hip work buffers
-    bool bvh_caller_order = false;   // experiment hook (with face_order = 0): the implicit BVH is built over the caller's face order as it is (tree-quality probes)
     int ray_xcd = 1;         // XCD-aware block order in the packet ray kernel
     int info_wave_area = 32;   // footprints (sampled ones) above this many pixels go to the wave-per-footprint kernel (k_dc.hip wave_info_kernel); 0 = every footprint serial = bit-exact with the reference's fp64 scan order
     int info_wave_area_words = 384;   // the same threshold where info_kernel walks a footprint four pixels per load as integers ("info_words": gradient term, no outlier removal): one lane
@@ -226,7 +225,7 @@ struct mvs_ctx {
     // ---- MRF ----
     mvs::DBuf<uint32_t> m_adj_ptr, m_adj, a_stage_ptr, a_stage; const uint32_t* r_adj_ptr = nullptr; const uint32_t* r_adj = nullptr;   // a_stage*: host lists on their way into the table's order
     uint32_t r_adj_edges = 0; bool r_adj_edges_known = false;   // length of r_adj where set_adjacency learned it (host lists, renumbered lists)
-    mvs::DBuf<mvs::NodeDesc> m_desc; mvs::DBuf<uint8_t> m_ident; mvs::DBuf<uint32_t> m_rec; uint64_t m_rec_words = 0; bool m_fast = false; int mrf_blocks_per_cu = 0 /* 0 = resident count from the occupancy API */, mrf_xcd = 1, mrf_late_old = 1, mrf_run_pad = 4;
+    mvs::DBuf<mvs::NodeDesc> m_desc; mvs::DBuf<uint8_t> m_ident; mvs::DBuf<uint32_t> m_rec; uint64_t m_rec_words = 0; bool m_fast = false; int mrf_blocks_per_cu = 0 /* 0 = resident count from the occupancy API */, mrf_xcd = 1;
     mvs::DBuf<mvs::MrfEdge> m_edge; mvs::DBuf<uint32_t> m_size, m_rev /* reverse directed edge of every in-edge */; mvs::DBuf<uint16_t> m_map;
     mvs::DBuf<uint8_t> m_msg_a;    // messages as 8-bit fixed point over [0, 1/rho], updated in place (one colour class at a time)
     // decode of a sweep = position in the column (sel), label (view + 1) and the unary of that label as the sweeps see it.
@@ -248,10 +247,7 @@ struct mvs_ctx {
     mvs::DBuf<uint32_t> m_colour, m_perm, m_tmp_a, m_tmp_b, m_tmp_c, m_sub; mvs::DBuf<uint8_t> m_cls; uint32_t m_colours = 0, m_n_fast = 0; std::vector<uint32_t> m_sub_begin;
     const uint32_t* m_colour_in = nullptr;   // colours of all nodes kept by a sharded caller (null: mrf_setup colours the graph)
     const uint8_t* m_bnd = nullptr;   // per node: 1 = boundary node of a sharded caller (own node with an edge into another rank's part) -> zone 0 of the schedule (k_mrf.hip); null: no marks
-    int mrf_damp_period = 4;     // damped sweeps: 1, 1 + p, 1 + 2p, ... (4: the solver's definition, restated in the oracle; other values are experiment knobs)
     int mrf_force_generic = 0;   // test hook: every node takes the generic sweep kernel
-    int mrf_wide = 1;            // class-1 nodes (neighbourhood columns of 33 .. 64 labels) through mrf_sweep8_kernel: 8 lanes x 8 labels (k_mrf.hip); 0: mrf_sweep4_kernel<16>
-    bool m_wide_layout = false;  // ... as the last mrf_setup laid the records and runs out
     uint32_t m_range_nb = 0, m_range_ne = 0; std::vector<uint32_t> m_range_q;   // cached own share of every sub-class
     uint32_t m_sweep_no = 0;   // sweeps started since mrf_setup (1-based inside a sweep): sweeps 1, 5, 9, ... are damped
     mvs_mrf_params m_params{};
@@ -260,7 +256,7 @@ struct mvs_ctx {
     static constexpr uint32_t ICM_RING = 8;
     uint32_t* h_icm = nullptr; uint32_t* d_icm = nullptr; uint32_t icm_seq = 0;   // pinned "moved" counts of the ICM rounds, read a few rounds late
     mvs::DBuf<mvs_mrf_progress> m_state; mvs::DBuf<unsigned long long> m_hist; mvs::DBuf<uint32_t> m_ctl;   // m_ctl: {steps of the solve, sequence base} read by the step kernel
-    // the sweep loop as a replayed hipGraph (api.hip): two sweeps (a damped and an undamped one) + their bookkeeping steps, captured on a
+    // the sweep loop as a replayed hipGraph (api.hip): one damping period, MRF_DAMP_PERIOD sweeps + their bookkeeping steps, captured on a
     // private stream, launched on the context's stream; re-captured per solve and pushed into the instantiated graph with hipGraphExecUpdate
     int mrf_graph = 1; hipStream_t cap_stream = nullptr; hipGraphExec_t sweep_exec = nullptr; uint32_t graph_launches = 0, graph_updates = 0, graph_instantiations = 0;
     mvs_mrf_progress* h_ring = nullptr; mvs_mrf_progress* d_ring = nullptr /* the same pinned slots as the device addresses them */; uint32_t steps_issued = 0; int mrf_lag = 1;
@@ -312,6 +308,11 @@ enum { MRF_PART_ALL = 0, MRF_PART_BOUNDARY = 1, MRF_PART_INTERIOR = 2 };
 void ensure_report_ring(mvs_ctx* ctx);
 void report_u32(mvs_ctx* ctx, const uint32_t* d_src, uint32_t* d_dst, uint32_t seq_slot, uint32_t seq);
 void wait_report(mvs_ctx* ctx, uint32_t seq_slot, uint32_t seq);
+// ICM polish rounds until one moves nothing or max_rounds ran (k_mrf.hip): round(k) queues round k, which leaves its "moved" count in
+// the device word d_moved.  Returns the index of the round that moved nothing (max_rounds if none did) -- the oracle's loop counter.
+int icm_rounds(mvs_ctx* ctx, int max_rounds, const uint32_t* d_moved, const std::function<void(int)>& round);
+// damped sweeps: 1, 5, 9, ... -- part of the solver's definition, restated in oracle/oracle.cpp (MRF_DAMP_PERIOD)
+constexpr uint32_t MRF_DAMP_PERIOD = 4;
 // up to 64 words from device memory to the host between two launches of ctx->stream: a one-block kernel stores them into a pinned buffer and
 // announces them with a sequence number the host spins on (k_mrf.hip).  A 4-byte hipMemcpyAsync into pageable memory + hipStreamSynchronize
 // holds the device idle for 22 us, this for 9 (scripts/probe/readback_cost.hip) -- a step has a dozen of them on its critical path.

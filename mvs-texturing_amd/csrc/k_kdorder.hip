@@ -2,7 +2,7 @@
 //
 // The implicit 4-ary tree has no freedom but the ORDER of its triangles: a leaf is 16 consecutive triangles, a level-k node 4 consecutive
 // level-(k-1) nodes.  Rounds 1 - 5 ordered them along a Hilbert curve and re-partitioned only inside windows of 512 (refine_order_kernel).
-// Round 6 measured what the order is worth (scripts/bvh_order_probe.py, profiles/r06_bvh_order_probe_c3.json; BASELINE config 3, ray stage):
+// Round 6 measured what the order is worth (scripts/bvh_order_probe.py, retired after commit 1bd22ac; profiles/r06_bvh_order_probe_c3.json; BASELINE config 3, ray stage):
 //     Hilbert + cuts inside 512-face windows                 39.9 node visits / 61.7 leaf rounds per packet   6.28 ms
 //     ... inside 4 096 / 16 384 / 65 536 / 262 144 faces     35.4 / 32.6 / 30.7 / 28.6 visits                  5.50 / 5.19 / 5.14 / 4.90 ms
 //     the whole tree cut top-down                            26.4 visits / 43.6 rounds                         4.74 ms

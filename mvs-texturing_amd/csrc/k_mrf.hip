@@ -145,12 +145,11 @@ __device__ __forceinline__ float group_min_fused(float v) {
                                 : "=&v"(ra), "=&v"(rb), "=&v"(rc), "=&v"(rd) : "v"(a), "v"(b), "v"(c), "v"(d)); a = ra; b = rb; c = rc; d = rd
 template <int G>
 __device__ __forceinline__ void group_min_fused4(float& a, float& b, float& c, float& d) {
-    if (G == 8 || G == 16) {
+    if (G == 8) {
         float ra, rb, rc, rd;
         MVS_DPP4("s_nop 1\n\t", "quad_perm:[1,0,3,2]");
         MVS_DPP4("", "quad_perm:[2,3,0,1]");
         MVS_DPP4("", "row_half_mirror");
-        if (G == 16) { MVS_DPP4("", "row_mirror"); }
     } else { a = group_min_fused<G>(a); b = group_min_fused<G>(b); c = group_min_fused<G>(c); d = group_min_fused<G>(d); }
 }
 #undef MVS_DPP4
@@ -165,12 +164,12 @@ __device__ __forceinline__ uint32_t group_min_fused(uint32_t v) {
 
 // ---- setup ----
 // Node classes: the sweep is routed PER NODE, not per solve.  A node of degree <= 3 whose own column and whose in-model
-// neighbours' columns hold at most 255 labels is a FAST node, swept by mrf_sweep4_kernel<G> with the lane-group width of its
-// neighbourhood: G = 8 / 16 / 32 / 64 for kmx = max(K_i, K_j) <= 32 / 64 / 128 / 255 (classes 0 .. 3; the node's three outgoing runs are
-// as long as the NEIGHBOURS' label lists, so they count).  Everything else -- a non-manifold edge (degree > 3), a column of more
-// than 255 labels at the node or next to it -- is a GENERIC node (class 4): one wave per node, any degree, any K.  One
-// non-manifold edge or one long column therefore costs a handful of generic nodes, not the whole solve, and the lane-group
-// width follows the local column sizes instead of the largest column of the mesh.  A colour class is an independent set, so
+// neighbours' columns hold at most 255 labels is a FAST node, swept with the lane-group width of its neighbourhood: G = 8 / 8 / 32 / 64
+// lanes for kmx = max(K_i, K_j) <= 32 / 64 / 128 / 255 (classes 0 .. 3: mrf_sweep4_kernel<G>, class 1 mrf_sweep8_kernel with 8 labels
+// per lane; the node's three outgoing runs are as long as the NEIGHBOURS' label lists, so they count).  Everything else -- a non-manifold
+// edge (degree > 3), a column of more than 255 labels at the node or next to it -- is a GENERIC node (class 4): one wave per node, any
+// degree, any K.  One non-manifold edge or one long column therefore costs a handful of generic nodes, not the whole solve, and the
+// lane-group width follows the local column sizes instead of the largest column of the mesh.  A colour class is an independent set, so
 // the order in which its nodes are swept -- hence the split into launches -- cannot change the result.
 constexpr uint32_t CLS_GENERIC = 4;
 __device__ __forceinline__ uint32_t mrf_node_class(uint32_t kmx, uint32_t deg, uint32_t force_generic) {
@@ -205,7 +204,7 @@ __global__ void mrf_size_kernel(const uint32_t* __restrict__ col_ptr, const uint
             for (int q = 0; q < 4; ++q) {
                 if (eb + q >= e1) continue;
                 const uint32_t e = eb + q;
-                size[e] = (k > 0 && kj[q] > 0) ? ((k + pad_mask) & ~pad_mask) : 0u;   // runs padded to a multiple of 4 (8-byte quads) or 16 elements (32-byte sectors)
+                size[e] = (k > 0 && kj[q] > 0) ? ((k + pad_mask) & ~pad_mask) : 0u;   // runs padded to a multiple of pad_mask + 1 elements
                 if (k > 0) kmx = max(kmx, kj[q]);
                 uint32_t r = 0xFFFFFFFFu;                         // the FIRST position of i in j's list
 #pragma unroll
@@ -480,9 +479,9 @@ __global__ void __launch_bounds__(256) mrf_ident_kernel(const uint32_t* __restri
 }
 // rsz[q] = words of the record of node perm[q] (rsz[F] = 0)
 // qpos[i] = position of node i in the (colour, id) order (the inverse of perm)
-// (wide: class-1 nodes are swept by mrf_sweep8_kernel, whose lanes read 8 map bytes at once: their map sections are padded to 8 bytes)
+// (class-1 nodes are swept by mrf_sweep8_kernel, whose lanes read 8 map bytes at once: their map sections are padded to 8 bytes)
 __global__ void mrf_recsize_kernel(const uint32_t* __restrict__ col_ptr, const uint32_t* __restrict__ adj_ptr, const MrfEdge* __restrict__ edge,
-                                   const uint8_t* __restrict__ ident, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ perm, uint32_t F, uint32_t wide,
+                                   const uint8_t* __restrict__ ident, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ perm, uint32_t F,
                                    uint32_t* __restrict__ rsz, uint32_t* __restrict__ qpos) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q > F) return;
@@ -492,7 +491,7 @@ __global__ void mrf_recsize_kernel(const uint32_t* __restrict__ col_ptr, const u
         qpos[i] = q;
         if (K && cls[i] != CLS_GENERIC) {
             w = (K + 3u) & ~3u;
-            const bool w8 = wide != 0u && cls[i] == 1u;
+            const bool w8 = cls[i] == 1u;
             const uint32_t e0 = adj_ptr[i], e1 = adj_ptr[i + 1];
             for (uint32_t eb = e0; eb < e1; eb += 4) {       // four edges at a time: independent loads
                 uint32_t kj[4], id[4];
@@ -513,7 +512,7 @@ __global__ void mrf_recsize_kernel(const uint32_t* __restrict__ col_ptr, const u
 __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restrict__ col_ptr, const uint16_t* __restrict__ view_id, const float* __restrict__ cost,
                                                          const uint32_t* __restrict__ adj_ptr, const uint32_t* __restrict__ adj, const MrfEdge* __restrict__ edge,
                                                          const uint8_t* __restrict__ ident, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ qpos, const uint32_t* __restrict__ roff,
-                                                         uint32_t F, uint32_t wide, uint32_t* __restrict__ rec) {
+                                                         uint32_t F, uint32_t* __restrict__ rec) {
     __shared__ uint16_t s_l[16][256];
     const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t gl = threadIdx.x & 15;
@@ -525,9 +524,9 @@ __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restr
     // (slot = (at & 3) * G + (at >> 2) for position `at` in the sender's list, G = 8 << class lanes per node), so that the lanes of a
     // group read consecutive banks.  "Label absent at the sender" is the +inf slot 4 * G; for G = 64 the slots fill the byte range
     // 0 .. 254 and 0xFF marks absence (the kernel steers it to slot 256).
-    // (a WIDE class-1 node -- mrf_sweep8_kernel: 8 lanes x 8 labels -- has the tile row-major over label mod 8: slot = (at & 7) * 8 + (at >> 3),
+    // (a class-1 node -- mrf_sweep8_kernel: 8 lanes x 8 labels -- has the tile row-major over label mod 8: slot = (at & 7) * 8 + (at >> 3),
     //  "absent" = slot 64, and its map sections padded to 8 bytes)
-    const bool w8 = wide != 0u && ci == 1u;
+    const bool w8 = ci == 1u;
     const uint32_t rs = w8 ? 8u : 8u << ci, none_byte = w8 ? 64u : (ci < 3u ? 4u * rs : 0xFFu);
     const uint32_t lmask = w8 ? 7u : 3u, lshift = w8 ? 3u : 2u;
     const uint32_t q = qpos[i];
@@ -632,7 +631,7 @@ __global__ void mrf_desc_kernel(const uint32_t* __restrict__ col_ptr, const uint
 // (The access-pattern probes of rounds 4 and 5 -- scripts/sweep_probe.py: all accesses inside a 64 KB window, arithmetic removed, one stream
 // dropped at a time, an edge-pair message layout, wider map loads -- are a PATCH on this kernel, scripts/probe/sweep4_probes.patch, which
 // scripts/build_variant.py --patch applies to a copy of this file; the product source carries none of them.)
-template <int G, bool DAMP, bool XCD, bool LATE_OLD>
+template <int G, bool DAMP, bool XCD>
 __global__ void __launch_bounds__(256) mrf_sweep4_kernel(const NodeDesc* __restrict__ desc, const uint32_t* __restrict__ rec, msg_t* msg,
                                                          const mvs_mrf_progress* __restrict__ st, uint32_t* lab2, uint32_t buf_stride,
                                                          uint32_t node_begin /* positions in the (colour, id) order */, uint32_t node_end, float rho, float alpha,
@@ -649,7 +648,7 @@ __global__ void __launch_bounds__(256) mrf_sweep4_kernel(const NodeDesc* __restr
     // (One tile per group, reused by the three out-edges.  A variant with three tiles -- all writes first, then all twelve gathers, one
     // LDS round trip per node and 9 VGPRs fewer -- measured the same at C3 and 28 % slower where a quarter of the nodes take the
     // 64-lane class: profiles/EXPERIMENTS.md.)
-    constexpr int TS = G == 8 ? 40 : G == 16 ? 80 : 4 * G + 4;
+    constexpr int TS = G == 8 ? 40 : 4 * G + 4;
     __shared__ float s_c[NPB * TS];
     __shared__ unsigned long long s_e[8];
     const int grp = threadIdx.x / G, gl = threadIdx.x % G;
@@ -790,7 +789,7 @@ __global__ void __launch_bounds__(256) mrf_sweep4_kernel(const NodeDesc* __restr
 }
 
 
-// ---- the same update with EIGHT labels per lane (class 1: neighbourhood columns of 33 .. 64 labels; option "mrf_wide") ----
+// ---- the same update with EIGHT labels per lane (class 1: neighbourhood columns of 33 .. 64 labels) ----
 // mrf_sweep4_kernel spends one memory instruction on 4 bytes of a run per lane: a 64-lane wave sweeps 4 nodes of this class per iteration
 // and issues 20 loads / stores for them.  The probes of rounds 4 and 5 (EXPERIMENTS.md) say the kernel is bound by the NUMBER of memory
 // instructions and requests per node, not by their bytes.  Here a node takes 8 lanes and a lane 8 consecutive labels: the three incoming
@@ -895,7 +894,7 @@ __global__ void __launch_bounds__(256) mrf_sweep8_kernel(const NodeDesc* __restr
                 w0 = msg_pack_s<DAMP>(min_raw(tile[s0], lam_s), alpha, (float)((rw.old[d].x >> (8 * r)) & 0xFFu), (uint32_t)r, w0);
                 w1 = msg_pack_s<DAMP>(min_raw(tile[s1], lam_s), alpha, (float)((rw.old[d].y >> (8 * r)) & 0xFFu), (uint32_t)r, w1);
             }
-            if (t0 < kj3[d]) st_off<uint2>(mn, o_out[d] + t0, make_uint2(w0, w1));   // one 8-byte store: with "mrf_wide" the runs are padded to 8 elements
+            if (t0 < kj3[d]) st_off<uint2>(mn, o_out[d] + t0, make_uint2(w0, w1));   // one 8-byte store: the runs are padded to 8 elements
 
         }
         const bool owner = node_ok && ((K > 0u) ? ((bt >> 3) == (uint32_t)gl) : (gl == 0));
@@ -1288,6 +1287,7 @@ __global__ void mrf_flip_kernel(mvs_mrf_progress* __restrict__ st) { st->best_w 
 }  // namespace
 
 constexpr uint32_t EPART_BLOCKS = 2048;   // per colour phase: upper bound of the blocks of all its launches together (resident blocks)
+constexpr uint32_t RUN_PAD_MASK = 7;      // message runs padded to multiples of 8 elements: the 8-byte stores of mrf_sweep8_kernel (the 4-label kernels need 4)
 
 // Builds the solver's edge tables for the active CSR (ctx->r_ptr / r_view / r_cost) and adjacency.
 void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
@@ -1314,7 +1314,7 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
     const uint32_t force_generic = (ctx->csr_nnz < 4 || E == 0 || ctx->mrf_force_generic) ? 1u : 0u;
     ctx->m_cls.ensure((size_t)F + 4);
     ctx->m_rev.ensure((size_t)E + 2);
-    if (F) { hipLaunchKernelGGL(mrf_size_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, F, (uint32_t)(ctx->mrf_run_pad == 16 ? 15 : (ctx->mrf_wide ? 7 : 3)), force_generic, ctx->m_size.p, ctx->m_cls.p, maxes, ctx->m_rev.p); MVS_LAUNCH_CHECK(); }
+    if (F) { hipLaunchKernelGGL(mrf_size_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, F, RUN_PAD_MASK, force_generic, ctx->m_size.p, ctx->m_cls.p, maxes, ctx->m_rev.p); MVS_LAUNCH_CHECK(); }
     // ---- colour-phased schedule: colouring (Jones-Plassmann rounds), nodes in (colour, id) order ----
     ctx->m_colour.ensure((size_t)F + 2); ctx->m_perm.ensure((size_t)F + 2); ctx->m_tmp_a.ensure((size_t)MAX_LAYOUT_COLOURS * ((size_t)F + 1) + 72); ctx->m_tmp_b.ensure((size_t)MAX_LAYOUT_COLOURS * ((size_t)F + 1) + 2); ctx->m_tmp_c.ensure((size_t)F + 2);
     ctx->m_colours = 0; ctx->m_sub_begin.assign(N_KEY + 1, 0); ctx->m_n_fast = 0; ctx->m_range_q.clear(); ctx->m_range_nb = ctx->m_range_ne = 0;
@@ -1380,19 +1380,18 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
     ctx->m_ident.ensure((size_t)E + 1);
     MVS_HIP(hipMemsetAsync(ctx->m_ident.p, 0, (size_t)E + 1, s));
     ctx->m_fast = true;   // the sweep kernels of BOTH node classes accumulate the sweep's energy (callers no longer run the energy kernel per sweep)
-    ctx->m_wide_layout = ctx->mrf_wide != 0;   // the records / runs built below are those of this variant: the sweeps follow the set-up, not the option
     const uint32_t n_fast = ctx->m_n_fast, n_generic = F - n_fast;
     if (n_fast) {
         // records + descriptors of the fast nodes.  Upper bound of the record array (no read-back): labels nnz + 3 F, maps <= one byte per message element
-        const size_t rec_cap = (size_t)REC_BASE + ctx->csr_nnz + 8 * (size_t)F + ctx->m_total / 4 + (ctx->mrf_wide ? (size_t)ctx->m_n_adj : 0) + 1024;   // incl. slack for reads past the last record
+        const size_t rec_cap = (size_t)REC_BASE + ctx->csr_nnz + 8 * (size_t)F + ctx->m_total / 4 + (size_t)ctx->m_n_adj + 1024;   // incl. slack for reads past the last record
         ctx->m_rec.ensure(rec_cap);
         MVS_HIP(hipMemsetAsync(ctx->m_rec.p, 0, REC_BASE * sizeof(uint32_t), s));
         hipLaunchKernelGGL(mrf_ident_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, ctx->m_ident.p); MVS_LAUNCH_CHECK();
         uint32_t* rsz = ctx->m_tmp_a.p; uint32_t* roff = ctx->m_tmp_b.p;   // F + 1 entries each
-        hipLaunchKernelGGL(mrf_recsize_kernel, dim3((F + 256) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_perm.p, F, (uint32_t)(ctx->mrf_wide ? 1 : 0), rsz, ctx->m_tmp_c.p); MVS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(mrf_recsize_kernel, dim3((F + 256) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_perm.p, F, rsz, ctx->m_tmp_c.p); MVS_LAUNCH_CHECK();
         exclusive_scan_u32(ctx, rsz, roff, (size_t)F + 1, nullptr);
         hipLaunchKernelGGL(mrf_record_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->r_adj_ptr, ctx->r_adj,
-                           ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_tmp_c.p /* qpos */, roff, F, (uint32_t)(ctx->mrf_wide ? 1 : 0), ctx->m_rec.p); MVS_LAUNCH_CHECK();
+                           ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_tmp_c.p /* qpos */, roff, F, ctx->m_rec.p); MVS_LAUNCH_CHECK();
         ctx->m_desc.ensure((size_t)F + 1);
         hipLaunchKernelGGL(mrf_desc_kernel, dim3((n_fast + 255) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, ctx->m_edge.p, ctx->m_ident.p, ctx->m_perm.p, ctx->m_colour.p, roff, n_fast, ctx->m_desc.p); MVS_LAUNCH_CHECK();
     }
@@ -1541,35 +1540,55 @@ void wait_report(mvs_ctx* ctx, uint32_t seq_slot, uint32_t seq) {
     }
     std::atomic_thread_fence(std::memory_order_acquire);
 }
+// The "moved" counts come back through the pinned ring of ICM_RING slots, LAG rounds late: the host queues round k + LAG before it reads
+// round k's count, so the GPU never idles on a round trip; a round queued after the one that moved nothing changes nothing.
+int icm_rounds(mvs_ctx* ctx, int max_rounds, const uint32_t* d_moved, const std::function<void(int)>& round) {
+    constexpr int R = (int)mvs_ctx::ICM_RING, LAG = 2;
+    ensure_report_ring(ctx);
+    int issued = 0, polled = 0, stop = -1;
+    const uint32_t seq0 = ctx->icm_seq;
+    auto poll = [&]() { const int k = polled++; wait_report(ctx, mvs_ctx::RING + (uint32_t)(k % R), seq0 + (uint32_t)k + 1u); if (stop < 0 && ctx->h_icm[k % R] == 0u) stop = k; };
+    ProfChain pc(ctx);
+    while (issued < max_rounds && stop < 0) {
+        pc.begin();
+        round(issued);
+        report_u32(ctx, d_moved, ctx->d_icm + issued % R, mvs_ctx::RING + (uint32_t)(issued % R), seq0 + (uint32_t)issued + 1u);
+        pc.mark("mrf_icm");
+        ++issued;
+        if (issued - polled > LAG) poll();
+    }
+    while (polled < issued) poll();
+    ctx->icm_seq = seq0 + (uint32_t)issued;
+    return stop >= 0 ? stop : max_rounds;
+}
 
 // Damping schedule (part of the solver's definition, restated in oracle/oracle.cpp): messages are damped with
 // alpha = params.damping on ODD sweeps (1st, 3rd, ...) and written undamped on even sweeps.  Undamped sweeps oscillate
 // (C3: 0.9 % higher final energy), but damping every second sweep suppresses that just as well as damping every sweep
 // (C3: 44 sweeps to E = 1 111 890 with 0.2 on odd sweeps vs 47 to 1 110 970 with 0.1 on all) -- and an undamped sweep
 // does not re-read its previous outgoing messages.
-// Round 6 re-scored the schedule in milliseconds (scripts/schedule_score.py, profiles/r06_schedule_score_*.json): an undamped launch is 14 %
-// cheaper than a damped one, and damping every FOURTH sweep (1st, 5th, ...) holds the oscillation as well: the definition is period 4.
-// (option "mrf_damp_period", an experiment knob: 4 = the definition; p damps sweeps 1, p + 1, 2p + 1, ...; 1 every sweep; 0 none)
+// Round 6 re-scored the schedule in milliseconds (scripts/schedule_score.py, retired after commit 1bd22ac; profiles/r06_schedule_score_*.json):
+// an undamped launch is 14 % cheaper than a damped one, and damping every FOURTH sweep (1st, 5th, ...) holds the oscillation as well:
+// the definition is period 4 (MRF_DAMP_PERIOD).
 static float sweep_alpha(const mvs_ctx* ctx) {
-    const uint32_t p = (uint32_t)std::max(ctx->mrf_damp_period, 0);
-    if (p == 0) return 0.0f;
-    return (p == 1 || ctx->m_sweep_no % p == 1u) ? ctx->m_params.damping : 0.0f;
+    return ctx->m_sweep_no % MRF_DAMP_PERIOD == 1u ? ctx->m_params.damping : 0.0f;
 }
 
-// one launch of the fast kernel over positions [qb, qe) (one (colour, class) range of the schedule order); its per-block energy
-// partials go to slots [slot, slot + blocks) of the phase's region.  Returns the number of blocks (= slots) used.
-template <int G>
-static unsigned launch_sweep4_g(mvs_ctx* ctx, uint32_t phase, uint32_t qb, uint32_t qe, unsigned slot, unsigned slot_cap) {
-    constexpr int NPB = 256 / G;
-    const unsigned need = (qe - qb + NPB - 1) / NPB;
-    const float rho = ctx->m_params.rho, alpha = sweep_alpha(ctx);
-    // persistent lane groups: at most as many blocks as are resident at once (a partial second wave of
-    // blocks would double the tail); mrf_blocks_per_cu > 0 overrides
-    static std::atomic<int> resident_once{0};   // (the same value on every device of a node; in-process ranks race for it: atomic, idempotent)
+// the fast sweep kernels' signature; k[DAMP][XCD] are a kernel's four instantiations
+using FastSweep = void (*)(const NodeDesc*, const uint32_t*, msg_t*, const mvs_mrf_progress*, uint32_t*, uint32_t, uint32_t, uint32_t, float, float, unsigned long long*);
+// one launch of a fast kernel (npb nodes per block) over positions [qb, qe) (one (colour, class) range of the schedule order); its per-block
+// energy partials go to slots [slot, slot + blocks) of the phase's region.  Returns the number of blocks (= slots) used.
+// Persistent lane groups: at most as many blocks as are resident at once (a partial second wave of blocks would double the tail);
+// mrf_blocks_per_cu > 0 overrides.  `resident_once` caches the resident count of k[1][1] (the same value on every device of a node;
+// in-process ranks race for it: atomic, idempotent).
+static unsigned launch_fast(mvs_ctx* ctx, const FastSweep (&k)[2][2], unsigned npb, std::atomic<int>& resident_once,
+                            uint32_t phase, uint32_t qb, uint32_t qe, unsigned slot, unsigned slot_cap) {
+    const unsigned need = (qe - qb + npb - 1) / npb;
+    const float alpha = sweep_alpha(ctx);
     int resident = resident_once.load(std::memory_order_relaxed);
     if (resident == 0) {
         int per_cu = 0; hipDeviceProp_t prop;
-        MVS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mrf_sweep4_kernel<G, true, true, true>, 256, 0));
+        MVS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k[1][1], 256, 0));
         MVS_HIP(hipGetDeviceProperties(&prop, ctx->device));
         resident = std::max(1, per_cu) * prop.multiProcessorCount;
         resident_once.store(resident, std::memory_order_relaxed);
@@ -1579,40 +1598,22 @@ static unsigned launch_sweep4_g(mvs_ctx* ctx, uint32_t phase, uint32_t qb, uint3
     if (blocks > 8) blocks &= ~7u;   // multiple of the 8 XCDs
     msg_t* msg = reinterpret_cast<msg_t*>(ctx->m_msg_a.p);
     unsigned long long* partial = ctx->m_energy.p + 4 + 2 * ((size_t)EPART_BLOCKS * phase + slot);
-#define SWEEP4_ARGS dim3(blocks), dim3(256), 0, ctx->stream, ctx->m_desc.p, ctx->m_rec.p, msg, ctx->m_state.p, ctx->m_lab.p, ctx->m_stride, qb, qe, rho, alpha, partial
-    if (alpha != 0.0f) {
-        if (ctx->mrf_late_old) { if (ctx->mrf_xcd) hipLaunchKernelGGL((mrf_sweep4_kernel<G, true, true, true>), SWEEP4_ARGS); else hipLaunchKernelGGL((mrf_sweep4_kernel<G, true, false, true>), SWEEP4_ARGS); }
-        else { if (ctx->mrf_xcd) hipLaunchKernelGGL((mrf_sweep4_kernel<G, true, true, false>), SWEEP4_ARGS); else hipLaunchKernelGGL((mrf_sweep4_kernel<G, true, false, false>), SWEEP4_ARGS); }
-    } else { if (ctx->mrf_xcd) hipLaunchKernelGGL((mrf_sweep4_kernel<G, false, true, false>), SWEEP4_ARGS); else hipLaunchKernelGGL((mrf_sweep4_kernel<G, false, false, false>), SWEEP4_ARGS); }
-#undef SWEEP4_ARGS
+    hipLaunchKernelGGL(k[alpha != 0.0f][ctx->mrf_xcd != 0], dim3(blocks), dim3(256), 0, ctx->stream, ctx->m_desc.p, ctx->m_rec.p, msg, ctx->m_state.p,
+                       ctx->m_lab.p, ctx->m_stride, qb, qe, ctx->m_params.rho, alpha, partial);
     MVS_LAUNCH_CHECK();
     return blocks;
 }
-// class 1 through mrf_sweep8_kernel (option "mrf_wide"): 8 lanes per node, 32 nodes per block
+template <int G>
+static unsigned launch_sweep4_g(mvs_ctx* ctx, uint32_t phase, uint32_t qb, uint32_t qe, unsigned slot, unsigned slot_cap) {
+    static const FastSweep k[2][2] = {{mrf_sweep4_kernel<G, false, false>, mrf_sweep4_kernel<G, false, true>}, {mrf_sweep4_kernel<G, true, false>, mrf_sweep4_kernel<G, true, true>}};
+    static std::atomic<int> resident{0};
+    return launch_fast(ctx, k, 256 / G, resident, phase, qb, qe, slot, slot_cap);
+}
+// class 1 through mrf_sweep8_kernel: 8 lanes per node, 32 nodes per block
 static unsigned launch_sweep8(mvs_ctx* ctx, uint32_t phase, uint32_t qb, uint32_t qe, unsigned slot, unsigned slot_cap) {
-    constexpr int NPB = 256 / 8;
-    const unsigned need = (qe - qb + NPB - 1) / NPB;
-    const float rho = ctx->m_params.rho, alpha = sweep_alpha(ctx);
-    static std::atomic<int> resident_once{0};   // (the same value on every device of a node; in-process ranks race for it: atomic, idempotent)
-    int resident = resident_once.load(std::memory_order_relaxed);
-    if (resident == 0) {
-        int per_cu = 0; hipDeviceProp_t prop;
-        MVS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mrf_sweep8_kernel<true, true>, 256, 0));
-        MVS_HIP(hipGetDeviceProperties(&prop, ctx->device));
-        resident = std::max(1, per_cu) * prop.multiProcessorCount;
-        resident_once.store(resident, std::memory_order_relaxed);
-    }
-    unsigned blocks = ctx->mrf_blocks_per_cu > 0 ? 256u * (unsigned)ctx->mrf_blocks_per_cu : (unsigned)resident;
-    blocks = std::max(1u, std::min(std::min(need, blocks), slot_cap));
-    if (blocks > 8) blocks &= ~7u;
-    msg_t* msg = reinterpret_cast<msg_t*>(ctx->m_msg_a.p);
-    unsigned long long* partial = ctx->m_energy.p + 4 + 2 * ((size_t)EPART_BLOCKS * phase + slot);
-#define SWEEP8_ARGS dim3(blocks), dim3(256), 0, ctx->stream, ctx->m_desc.p, ctx->m_rec.p, msg, ctx->m_state.p, ctx->m_lab.p, ctx->m_stride, qb, qe, rho, alpha, partial
-    if (alpha != 0.0f) { if (ctx->mrf_xcd) hipLaunchKernelGGL((mrf_sweep8_kernel<true, true>), SWEEP8_ARGS); else hipLaunchKernelGGL((mrf_sweep8_kernel<true, false>), SWEEP8_ARGS); }
-    else { if (ctx->mrf_xcd) hipLaunchKernelGGL((mrf_sweep8_kernel<false, true>), SWEEP8_ARGS); else hipLaunchKernelGGL((mrf_sweep8_kernel<false, false>), SWEEP8_ARGS); }
-#undef SWEEP8_ARGS
-    MVS_LAUNCH_CHECK();
-    return blocks;
+    static const FastSweep k[2][2] = {{mrf_sweep8_kernel<false, false>, mrf_sweep8_kernel<false, true>}, {mrf_sweep8_kernel<true, false>, mrf_sweep8_kernel<true, true>}};
+    static std::atomic<int> resident{0};
+    return launch_fast(ctx, k, 256 / 8, resident, phase, qb, qe, slot, slot_cap);
 }
 static unsigned launch_sweep_generic(mvs_ctx* ctx, uint32_t phase, uint32_t qb, uint32_t qe, unsigned slot, unsigned slot_cap) {
     const unsigned need = qe - qb;   // one block per node
@@ -1675,7 +1676,7 @@ void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, i
         const uint32_t qb = L[k].qb, qe = L[k].qe;
         switch (L[k].g) {
             case 0: slot += launch_sweep4_g<8>(ctx, phase, qb, qe, slot, cap); break;
-            case 1: slot += ctx->m_wide_layout ? launch_sweep8(ctx, phase, qb, qe, slot, cap) : launch_sweep4_g<16>(ctx, phase, qb, qe, slot, cap); break;
+            case 1: slot += launch_sweep8(ctx, phase, qb, qe, slot, cap); break;
             case 2: slot += launch_sweep4_g<32>(ctx, phase, qb, qe, slot, cap); break;
             case 3: slot += launch_sweep4_g<64>(ctx, phase, qb, qe, slot, cap); break;      // one node per wave: several hundred views per face
             default: slot += launch_sweep_generic(ctx, phase, qb, qe, slot, cap);

@@ -1213,53 +1213,33 @@ mvs_status mvs_shard_view_selection(mvs_shard* S, const mvs_mrf_params* params, 
     mrf_exact_costs(ctx, nb, ne);
     // ICM rounds: gains of the own nodes, gains of the boundary nodes to the neighbours, winners move, labels of the boundary nodes
     // to the neighbours; the all-reduced "moved" count of a round reaches the host through the pinned ring two rounds late (as in
-    // the single-context polish, api.hip icm_polish), so no round waits for a read-back.  Every rank reads the same counts at the same
+    // the single-context polish: icm_rounds), so no round waits for a read-back.  Every rank reads the same counts at the same
     // round indices, hence takes the same decisions; a round queued after the one that moved nothing finds no positive gain anywhere.
-    int it = 0;
-    {
-        constexpr int RR = (int)mvs_ctx::ICM_RING, LAG = 2;
-        ensure_report_ring(ctx);
-        int issued = 0, polled_icm = 0, stop = -1;
-        const uint32_t seq0 = ctx->icm_seq;
-        auto poll = [&]() {
-            const int k = polled_icm++;
-            wait_report(ctx, mvs_ctx::RING + (uint32_t)(k % RR), seq0 + (uint32_t)k + 1u);
-            if (stop < 0 && ctx->h_icm[k % RR] == 0u) stop = k;
-        };
-        if (S->peer && P.icm_iters > 0) peer_publish_icm(S);
-        while (issued < P.icm_iters && stop < 0) {
-            Prof pr(ctx, "mrf_icm");
-            mrf_icm_gain(ctx, nb, ne);
-            if (S->peer) {
-                // gains of the boundary nodes into the neighbours' arrays; the winners move once the neighbours' gains are in; labels of the
-                // boundary nodes and the rank's "moved" count behind ONE event that every rank waits for (apply only tests halo labels
-                // against 0, which no move changes: a neighbour's label store may overlap it); the counts are summed on the device
-                peer_push_nodes(S, (const uint32_t*)ctx->m_gain.p, false);
-                const uint64_t ig = peer_record(S);
-                for (int q : S->nbr) peer_wait(S, q, ig);
-                mrf_icm_apply(ctx, nb, ne);
-                peer_push_nodes(S, ctx->b_lab, true);
-                const uint32_t parity = (uint32_t)(issued & 1);
-                hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)ctx->m_moved.p, S->m_pub.p, parity); MVS_LAUNCH_CHECK();
-                const uint64_t im = peer_record(S);
-                WordPtrs wp; wp.n = S->P;
-                for (int q = 0; q < S->P; ++q) { if (q != S->me) peer_wait(S, q, im); wp.p[q] = hub->slot[q].moved; }
-                hipLaunchKernelGGL(sum_words_kernel, dim3(1), dim3(64), 0, s, wp, parity, S->d_moved.p); MVS_LAUNCH_CHECK();
-            } else {
-                if (S->P > 1) exchange_nodes(S, (uint32_t*)ctx->m_gain.p);
-                mrf_icm_apply(ctx, nb, ne);
-                MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-                if (S->P > 1) { comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, s); exchange_nodes(S, ctx->b_lab); }
-            }
-            report_u32(ctx, S->d_moved.p, ctx->d_icm + issued % RR, mvs_ctx::RING + (uint32_t)(issued % RR), seq0 + (uint32_t)issued + 1u);
-            pr.end();
-            ++issued;
-            if (issued - polled_icm > LAG) poll();
+    if (S->peer && P.icm_iters > 0) peer_publish_icm(S);
+    const int it = icm_rounds(ctx, P.icm_iters, S->d_moved.p, [&](int k) {
+        mrf_icm_gain(ctx, nb, ne);
+        if (S->peer) {
+            // gains of the boundary nodes into the neighbours' arrays; the winners move once the neighbours' gains are in; labels of the
+            // boundary nodes and the rank's "moved" count behind ONE event that every rank waits for (apply only tests halo labels
+            // against 0, which no move changes: a neighbour's label store may overlap it); the counts are summed on the device
+            peer_push_nodes(S, (const uint32_t*)ctx->m_gain.p, false);
+            const uint64_t ig = peer_record(S);
+            for (int q : S->nbr) peer_wait(S, q, ig);
+            mrf_icm_apply(ctx, nb, ne);
+            peer_push_nodes(S, ctx->b_lab, true);
+            const uint32_t parity = (uint32_t)(k & 1);
+            hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)ctx->m_moved.p, S->m_pub.p, parity); MVS_LAUNCH_CHECK();
+            const uint64_t im = peer_record(S);
+            WordPtrs wp; wp.n = S->P;
+            for (int q = 0; q < S->P; ++q) { if (q != S->me) peer_wait(S, q, im); wp.p[q] = hub->slot[q].moved; }
+            hipLaunchKernelGGL(sum_words_kernel, dim3(1), dim3(64), 0, s, wp, parity, S->d_moved.p); MVS_LAUNCH_CHECK();
+        } else {
+            if (S->P > 1) exchange_nodes(S, (uint32_t*)ctx->m_gain.p);
+            mrf_icm_apply(ctx, nb, ne);
+            MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            if (S->P > 1) { comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, s); exchange_nodes(S, ctx->b_lab); }
         }
-        while (polled_icm < issued) poll();
-        ctx->icm_seq = seq0 + (uint32_t)issued;
-        it = stop >= 0 ? stop : P.icm_iters;
-    }
+    });
     R.icm_iters = (uint32_t)it;
     mrf_energy(ctx, true, nb, ne, true);
     MVS_HIP(hipMemcpyAsync(S->d_energy.p, ctx->m_energy.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));

@@ -537,6 +537,14 @@ def test_call_order_errors(ctx):
     assert ei.value.status == 6
     with pytest.raises(M.MvsError):
         c2.data_costs()
+    # the options mvs_set_option accepts are exactly those include/mvs_viewsel.h lists; retired ones are unknown names
+    for name in ("mrf_late_old", "mrf_wide", "mrf_run_pad", "mrf_damp_period", "dc_overlap_prep", "bvh_caller_order"):
+        with pytest.raises(M.MvsError, match="unknown option"):
+            c2.set_option(name, 0)
+    for name in ("stats", "count_rays", "verbose", "profile", "info_wave_area", "info_wave_area_words", "info_words", "info_cert_shift",
+                 "max_labels", "prep_fused", "face_order", "bvh_window", "bvh_upper_min_faces", "ray_xcd", "mrf_lag", "mrf_graph",
+                 "mrf_xcd", "mrf_blocks_per_cu", "mrf_force_generic", "shard_peer_push"):
+        c2.set_option(name, 0)
     c2.close()
 
 
