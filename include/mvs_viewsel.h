@@ -291,9 +291,7 @@ mvs_status mvs_ctx_synchronize(mvs_ctx* ctx);
  *     "mrf_xcd"               0/1, default 1: XCD-aware block order of the sweep kernels
  *     "mrf_blocks_per_cu"     default 0 = at most as many blocks per fast sweep launch as are resident; n > 0: at most 256 n
  *     "mrf_force_generic"     0/1, default 0: test hook, every node takes the generic sweep kernel
- *     "shard_peer_push"       0/1, default 1 (sharded sweep loop; must agree on all ranks): boundary runs are stored straight into the
- *                             neighbours' arrays where the communicator's ranks can address each other's memory; 0 = pack / exchange /
- *                             unpack through the communicator */
+ *   (the sharded sweep loop's transport is no option: the communicator decides it, see mvs_shard_transport_info) */
 mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value);
 
 /* with option "profile": per-stage GPU time from hipEvents recorded on the context's stream,
@@ -434,16 +432,17 @@ mvs_status mvs_postprocess_face_infos(uint32_t n_faces, uint32_t n_views, const 
  * labels of that phase's boundary nodes with the ranks that own the neighbours: grouped ncclSend / ncclRecv, neighbours
  * only.  Results are bit-identical to the single-GPU path for any number of parts.
  *
- * Transport of the sweep loop: through the communicator (one pack launch, one grouped exchange, one unpack launch per colour phase), or
- * -- where the ranks can address each other's device memory (the in-process communicator: one process, one host thread per GPU of
- * a node, peer access between the GPUs) -- "peer push": one launch per phase
+ * Transport of the sweep loop, decided by the communicator: over RCCL through the communicator (one pack launch, one grouped exchange,
+ * one unpack launch per colour phase); over the in-process communicator, whose ranks address each other's device memory (one
+ * process, one host thread per GPU of a node, peer access between the GPUs), "peer push": one launch per phase
  * stores the runs at their final places in the neighbours' arrays, ordering is by one stream event per phase and rank (waited for on
  * the stream, never on the host), the sweep's energy pair is published the same way and summed by every rank on the device.
  *
  * Communicators: RCCL (one process per GPU: mvs_comm_unique_id on rank 0, the 128 bytes travel by any means, mvs_comm_create_rccl
  * on every rank) or the in-process one (mvs_comm_create_local_devices: `world` host threads of ONE process, rank r driving a context
  * on devices[r]; distinct GPUs get hipDeviceEnablePeerAccess in both directions and the collectives are peer copies -- the
- * single-node route; devices == NULL or all equal: the ranks time-slice one device, which is how a 1-GPU box tests it).
+ * single-node route; MVS_ERR_UNSUPPORTED if two of the GPUs cannot address each other, RCCL serves such a node; devices == NULL or
+ * all equal: the ranks time-slice one device, which is how a 1-GPU box tests it).
  * A rank whose call fails makes the other ranks' host-side waits of that call end with an error (no rank is left blocked); the
  * communicator stays usable for the next call. */
 #define MVS_COMM_ID_BYTES 128
@@ -458,7 +457,8 @@ mvs_status mvs_comm_create_local_devices(int world, const int* devices /* [world
  * RCCL (mvs_comm_create_rccl) this is a no-op, and a rank that fails inside a sharded call leaves its peers inside the collective they
  * entered -- ending the job is the launcher's business there (torch.distributed.run takes the whole group down when one process dies). */
 void mvs_comm_abort(mvs_comm* comm);
-/* *peer_push = 1: the ranks can store into each other's device memory (the sweep loop takes the peer-push transport); any out may be NULL */
+/* *peer_push = 1: the ranks can store into each other's device memory (in-process communicator: a solve of more than one rank takes
+ * the peer-push transport), 0: RCCL; any out may be NULL */
 mvs_status mvs_comm_info(mvs_comm* comm, int* rank, int* world, int* peer_push);
 void mvs_comm_destroy(mvs_comm* comm);
 /* ctx: the rank's context with the FULL mesh and all views set; adjacency: device pointers to the full graph in the CALLER's face
@@ -474,8 +474,9 @@ mvs_status mvs_shard_data_costs(mvs_shard* shard, const mvs_settings* settings, 
 mvs_status mvs_shard_view_selection(mvs_shard* shard, const mvs_mrf_params* params, uint32_t* labels_own_device, mvs_mrf_stats* stats);
 /* halo plan of the last view selection: message bytes this rank sends per sweep, its boundary nodes, device time of the planning */
 mvs_status mvs_shard_plan_info(mvs_shard* shard, uint64_t* msg_bytes_per_sweep, uint64_t* boundary_nodes, double* plan_ms);
-/* transport of the last view selection: peer_push = 1 if the runs were stored into the peers' arrays; colour phases pushed so far (all solves);
- * ranks this one shares a cut with; colour phases per sweep */
+/* transport of the last view selection: peer_push = 1 if the runs were stored into the peers' arrays (in-process communicator, more
+ * than one rank, at least one colour phase), 0 if they went through the communicator's exchange; colour phases pushed so far (all
+ * solves); ranks this one shares a cut with; colour phases per sweep */
 mvs_status mvs_shard_transport_info(mvs_shard* shard, int* peer_push, uint64_t* phases_pushed, int* neighbours, uint32_t* colour_phases);
 
 #ifdef __cplusplus

@@ -225,7 +225,7 @@ struct mvs_ctx {
     // ---- MRF ----
     mvs::DBuf<uint32_t> m_adj_ptr, m_adj, a_stage_ptr, a_stage; const uint32_t* r_adj_ptr = nullptr; const uint32_t* r_adj = nullptr;   // a_stage*: host lists on their way into the table's order
     uint32_t r_adj_edges = 0; bool r_adj_edges_known = false;   // length of r_adj where set_adjacency learned it (host lists, renumbered lists)
-    mvs::DBuf<mvs::NodeDesc> m_desc; mvs::DBuf<uint8_t> m_ident; mvs::DBuf<uint32_t> m_rec; uint64_t m_rec_words = 0; bool m_fast = false; int mrf_blocks_per_cu = 0 /* 0 = resident count from the occupancy API */, mrf_xcd = 1;
+    mvs::DBuf<mvs::NodeDesc> m_desc; mvs::DBuf<uint8_t> m_ident; mvs::DBuf<uint32_t> m_rec; uint64_t m_rec_words = 0; int mrf_blocks_per_cu = 0 /* 0 = resident count from the occupancy API */, mrf_xcd = 1;
     mvs::DBuf<mvs::MrfEdge> m_edge; mvs::DBuf<uint32_t> m_size, m_rev /* reverse directed edge of every in-edge */; mvs::DBuf<uint16_t> m_map;
     mvs::DBuf<uint8_t> m_msg_a;    // messages as 8-bit fixed point over [0, 1/rho], updated in place (one colour class at a time)
     // decode of a sweep = position in the column (sel), label (view + 1) and the unary of that label as the sweeps see it.
@@ -260,7 +260,6 @@ struct mvs_ctx {
     // private stream, launched on the context's stream; re-captured per solve and pushed into the instantiated graph with hipGraphExecUpdate
     int mrf_graph = 1; hipStream_t cap_stream = nullptr; hipGraphExec_t sweep_exec = nullptr; uint32_t graph_launches = 0, graph_updates = 0, graph_instantiations = 0;
     mvs_mrf_progress* h_ring = nullptr; mvs_mrf_progress* d_ring = nullptr /* the same pinned slots as the device addresses them */; uint32_t steps_issued = 0; int mrf_lag = 1;
-    int shard_peer_push = 1;   // sharded sweep loop: boundary runs stored straight into the peers' arrays where the communicator allows it (shard.hip PeerHub)
     // arrival of a report = its sequence number in the pinned word next to it (written after a system-scope fence): the host polls
     // memory, no event is recorded in the stream.  Sequence numbers never repeat within a context.
     uint32_t* h_seq = nullptr; uint32_t* d_seq = nullptr; uint32_t seq_base = 0;   // [0, RING): solver steps; [RING, RING + ICM_RING): ICM rounds

@@ -17,8 +17,8 @@
 // A phase's nodes read only nodes of other colours, which were exchanged before: labels are bit-identical for any number of parts.
 //
 // Two communicators behind one interface: RCCL (resolved with dlopen at run time, so the library carries no link-time
-// dependency and shares whatever RCCL the process already loaded, e.g. PyTorch's) and an in-process one for `world` host
-// threads sharing a device (tests on a 1-GPU box: the same planner, pack / unpack kernels and loops, copies instead of xGMI).
+// dependency and shares whatever RCCL the process already loaded, e.g. PyTorch's) and an in-process one for `world` host threads
+// whose devices address each other's memory.  It decides the sweep loop's halo transport: in-process ranks push, RCCL ranks exchange.
 #include "ctx.h"
 #include "call_barrier.h"
 
@@ -101,19 +101,19 @@ struct mvs_comm {
     virtual bool aborted() const { return false; }
     virtual void abort_all() {}          // the caller gives this communicator up (mvs_comm_abort): every rank's waits end with an error, for good
     virtual int device() const { return -1; }   // the device this rank's context has to live on (-1: any -- the communicator does not care)
-    // non-null: the ranks of this communicator can store into each other's device memory (see PeerHub); barrier() = host rendezvous
+    // non-null: the ranks can store into each other's device memory (PeerHub; the in-process communicator); barrier() = host rendezvous
     virtual PeerHub* peers() { return nullptr; }
     virtual void barrier() {}
     enum Type { U32, U64, F32 };
     enum Op { SUM, MAX };
     virtual void allreduce(void* buf, size_t n, Type t, Op op, hipStream_t s) = 0;          // in place, device buffer
     virtual void allgather(const void* send, void* recv, size_t bytes, hipStream_t s) = 0;  // recv = world x bytes
-    // true: exchange / exchange2 are world-wide rendezvous -- EVERY rank has to call them, also with nothing to send or receive
-    // (the in-process communicator counts barriers over all ranks); false: point-to-point, a rank without traffic may skip the call
+    // true: exchange is a world-wide rendezvous -- EVERY rank has to call it, also with nothing to send or receive (the in-process
+    // communicator counts barriers over all ranks); false: point-to-point, a rank without traffic may skip the call
     virtual bool exchange_is_collective() const { return false; }
     // neighbour exchange of byte ranges: send + soff[q] .. soff[q + 1] goes to rank q, recv + roff[q] .. comes from rank q
     virtual void exchange(const uint8_t* send, const uint64_t* soff, uint8_t* recv, const uint64_t* roff, hipStream_t s) = 0;
-    // two ranges per peer in ONE group (message bytes + label words of a colour phase)
+    // two ranges per peer in ONE group (message bytes + label words of a colour phase: the sweep loop's Exchange, RCCL ranks only)
     virtual void exchange2(const uint8_t* sa, const uint64_t* soa, uint8_t* ra, const uint64_t* roa,
                            const uint8_t* sb, const uint64_t* sob, uint8_t* rb, const uint64_t* rob, hipStream_t s) {
         exchange(sa, soa, ra, roa, s); exchange(sb, sob, rb, rob, s);
@@ -190,8 +190,8 @@ struct RcclComm : mvs_comm {
 
 // ---- in-process communicator: `world` host threads of ONE process, one per rank ----
 // The ranks' contexts live on the devices named at creation: distinct GPUs of one node (the product's single-node route: peer access
-// is switched on between all of them, halo data is STORED into the neighbours' arrays -- PeerHub -- and the collectives below are
-// peer copies over xGMI) or one shared device (tests on a 1-GPU box: the same code, the ranks time-slice the device).
+// is switched on between all of them -- required --, halo data is STORED into the neighbours' arrays -- PeerHub -- and the collectives
+// below are peer copies over xGMI) or one shared device (tests on a 1-GPU box: the same code, the ranks time-slice the device).
 // Every collective is a rendezvous: post the pointers, barrier, copy (device to device, on the own stream, after the owner's "data
 // ready" event), barrier, wait for the readers of the own send buffer.
 __global__ void reduce_gathered_kernel(const uint8_t* __restrict__ gathered, size_t n, int world, int type /* 0 u32, 1 u64, 2 f32 */, int op /* 0 sum, 1 max */, void* __restrict__ out) {
@@ -204,46 +204,36 @@ __global__ void reduce_gathered_kernel(const uint8_t* __restrict__ gathered, siz
 struct LocalHub {
     int world;
     std::vector<int> device;                 // device of rank r
-    bool peer_ok = true;                     // every rank can address every other rank's device memory
     CallBarrier calls;                       // the ranks' rendezvous and its failure semantics (call_barrier.h: unit-tested on the CPU)
-    std::vector<const uint8_t*> send_a, send_b; std::vector<const uint64_t*> soff_a, soff_b;
+    std::vector<const uint8_t*> send; std::vector<const uint64_t*> soff;
     std::vector<hipEvent_t> ready, done;
     PeerHub peer;
-    explicit LocalHub(int w) : world(w), device(w, 0), calls(w), send_a(w), send_b(w), soff_a(w), soff_b(w), ready(w, nullptr), done(w, nullptr), peer(w) {}
+    explicit LocalHub(int w) : world(w), device(w, 0), calls(w), send(w), soff(w), ready(w, nullptr), done(w, nullptr), peer(w) {}
     ~LocalHub() { for (hipEvent_t e : ready) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e); }
 };
 struct LocalComm : mvs_comm {
     std::shared_ptr<LocalHub> hub;
     DBuf<uint8_t> gathered;                  // all-reduce scratch (world x the operand) on this rank's device
-    ~LocalComm() override {}
     bool exchange_is_collective() const override { return true; }
-    PeerHub* peers() override { return hub->peer_ok ? &hub->peer : nullptr; }
+    PeerHub* peers() override { return &hub->peer; }
     void barrier() override { hub->calls.arrive(call_no); }
     void begin_call() override { hub->calls.begin(++call_no); }
     void fail() override { hub->calls.fail(call_no); }
     bool aborted() const override { return hub->calls.abandoned(call_no); }
     void abort_all() override { hub->calls.abort_all(); }
     int device() const override { return hub->device[rank]; }
-    void rendezvous_copy(const uint8_t* sa, const uint64_t* soa, uint8_t* ra, const uint64_t* roa,
-                         const uint8_t* sb, const uint64_t* sob, uint8_t* rb, const uint64_t* rob, hipStream_t s) {
+    void exchange(const uint8_t* send, const uint64_t* soff, uint8_t* recv, const uint64_t* roff, hipStream_t s) override {
         LocalHub& H = *hub;
-        H.send_a[rank] = sa; H.soff_a[rank] = soa; H.send_b[rank] = sb; H.soff_b[rank] = sob;
+        H.send[rank] = send; H.soff[rank] = soff;
         MVS_HIP(hipEventRecord(H.ready[rank], s));
         barrier();
         for (int q = 0; q < world; ++q) {
             if (q == rank) continue;
             MVS_HIP(hipStreamWaitEvent(s, H.ready[q], 0));
-            const uint64_t na = roa[q + 1] - roa[q];
-            if (na) {
-                if (H.soff_a[q][rank + 1] - H.soff_a[q][rank] != na) throw HipError("local exchange: send / receive sizes disagree");
-                MVS_HIP(hipMemcpyAsync(ra + roa[q], H.send_a[q] + H.soff_a[q][rank], na, hipMemcpyDefault, s));
-            }
-            if (rb) {
-                const uint64_t nb = rob[q + 1] - rob[q];
-                if (nb) {
-                    if (H.soff_b[q][rank + 1] - H.soff_b[q][rank] != nb) throw HipError("local exchange: send / receive sizes disagree");
-                    MVS_HIP(hipMemcpyAsync(rb + rob[q], H.send_b[q] + H.soff_b[q][rank], nb, hipMemcpyDefault, s));
-                }
+            const uint64_t n = roff[q + 1] - roff[q];
+            if (n) {
+                if (H.soff[q][rank + 1] - H.soff[q][rank] != n) throw HipError("local exchange: send / receive sizes disagree");
+                MVS_HIP(hipMemcpyAsync(recv + roff[q], H.send[q] + H.soff[q][rank], n, hipMemcpyDefault, s));
             }
         }
         MVS_HIP(hipEventRecord(H.done[rank], s));
@@ -251,22 +241,15 @@ struct LocalComm : mvs_comm {
         for (int q = 0; q < world; ++q) if (q != rank) MVS_HIP(hipStreamWaitEvent(s, H.done[q], 0));   // my send buffers are free again
         barrier();   // nobody re-posts before everybody has queued its waits on this round's events
     }
-    void exchange(const uint8_t* send, const uint64_t* soff, uint8_t* recv, const uint64_t* roff, hipStream_t s) override {
-        rendezvous_copy(send, soff, recv, roff, nullptr, nullptr, nullptr, nullptr, s);
-    }
-    void exchange2(const uint8_t* sa, const uint64_t* soa, uint8_t* ra, const uint64_t* roa,
-                   const uint8_t* sb, const uint64_t* sob, uint8_t* rb, const uint64_t* rob, hipStream_t s) override {
-        rendezvous_copy(sa, soa, ra, roa, sb, sob, rb, rob, s);
-    }
     // every rank's `bytes` into every rank's recv (rank-major): peer copies, nothing through the host
     void allgather(const void* send, void* recv, size_t bytes, hipStream_t s) override {
         LocalHub& H = *hub;
-        H.send_a[rank] = (const uint8_t*)send;
+        H.send[rank] = (const uint8_t*)send;
         MVS_HIP(hipEventRecord(H.ready[rank], s));
         barrier();
         for (int q = 0; q < world; ++q) {
             if (q != rank) MVS_HIP(hipStreamWaitEvent(s, H.ready[q], 0));
-            if (bytes) MVS_HIP(hipMemcpyAsync((uint8_t*)recv + (size_t)q * bytes, H.send_a[q], bytes, hipMemcpyDefault, s));
+            if (bytes) MVS_HIP(hipMemcpyAsync((uint8_t*)recv + (size_t)q * bytes, H.send[q], bytes, hipMemcpyDefault, s));
         }
         MVS_HIP(hipEventRecord(H.done[rank], s));
         barrier();
@@ -355,13 +338,7 @@ __global__ void plan_node_kernel(const unsigned long long* __restrict__ key, uin
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) node[k] = (uint32_t)(key[k] & 0xFFFFFFFFull);
 }
-// pack / unpack of one exchange: message bytes by element index, labels (or gains) by node id
-__global__ void pack_bytes_kernel(const uint8_t* __restrict__ src, const uint32_t* __restrict__ idx, uint64_t n, uint8_t* __restrict__ dst) {
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) dst[k] = src[idx[k]];
-}
-__global__ void unpack_bytes_kernel(uint8_t* __restrict__ dst, const uint32_t* __restrict__ idx, uint64_t n, const uint8_t* __restrict__ src) {
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) dst[idx[k]] = src[k];
-}
+// pack / unpack of one exchange of node words: labels (or gains) by node id
 __global__ void pack_words_kernel(const uint32_t* __restrict__ src, const mvs_mrf_progress* __restrict__ st, uint32_t buf_stride, const uint32_t* __restrict__ idx, uint64_t n, uint32_t* __restrict__ dst) {
     if (st) src += (size_t)st->w * buf_stride;      // the current decode buffer
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (uint64_t)gridDim.x * blockDim.x) dst[k] = src[idx[k]];
@@ -419,13 +396,6 @@ struct WordPtrs { const uint32_t* p[MAX_PARTS]; int n; };
 __global__ void publish_word_kernel(const uint32_t* __restrict__ v, uint32_t* __restrict__ pub, uint32_t parity) { if (threadIdx.x == 0) pub[parity] = v[0]; }
 __global__ void sum_words_kernel(WordPtrs e, uint32_t parity, uint32_t* __restrict__ out) {
     if (threadIdx.x == 0) { uint32_t a = 0u; for (int q = 0; q < e.n; ++q) a += e.p[q][parity]; out[0] = a; }
-}
-struct EnergyPtrs { const unsigned long long* p[MAX_PARTS]; int n; };
-__global__ void publish_energy_kernel(const unsigned long long* __restrict__ pair, unsigned long long* __restrict__ pub, uint32_t parity) {
-    if (threadIdx.x < 2) pub[2 * parity + threadIdx.x] = pair[threadIdx.x];
-}
-__global__ void sum_energy_kernel(EnergyPtrs e, uint32_t parity, unsigned long long* __restrict__ out) {
-    if (threadIdx.x < 2) { unsigned long long a = 0ull; for (int q = 0; q < e.n; ++q) a += e.p[q][2 * parity + threadIdx.x]; out[threadIdx.x] = a; }
 }
 
 // ---- sharded cost table ----
@@ -499,6 +469,21 @@ __global__ void face_len_kernel(const uint32_t* __restrict__ faces, uint32_t n, 
     if (k <= n) len[k] = k < n ? counts_g[faces[k]] : 0u;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the sweep loop's halo transports
+// ---------------------------------------------------------------------------------------------------------------
+// The steps of a solve (mvs_shard_view_selection) at which the two transports differ.  The communicator decides which one runs.
+struct Transport {
+    virtual ~Transport() {}
+    virtual void start(mvs_shard*) {}                           // start of a solve: set-up and halo plan are in place
+    virtual void before_phase(mvs_shard* S, uint32_t ph) = 0;   // the halo that colour phase `ph` reads has arrived
+    virtual void after_boundary(mvs_shard* S, uint32_t ph) = 0; // the phase's boundary nodes are swept: their runs and labels leave
+    virtual void sweep_energy(mvs_shard* S, int sweep) = 0;     // the sweep's energy pair over all ranks into the stop rule (mrf_step)
+    virtual void icm_round(mvs_shard* S, int k) = 0;            // ICM round k: gains, moves, halo labels; all ranks' "moved" count into d_moved
+    virtual void finish(mvs_shard*, int /*sweeps*/) {}          // the sweeps are queued
+};
+struct Exchange; struct PeerPush;
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -514,8 +499,6 @@ struct mvs_shard {
     // labels to the neighbours and sweeps the interior -- which reads nothing a peer writes -- while they travel.
     DBuf<uint8_t> bnd;
     DBuf<uint32_t> colours; bool colours_valid = false;   // the greedy colouring (a function of the pinned adjacency and the caller's ids): made by the first solve, kept
-    hipStream_t comm_stream = nullptr; hipEvent_t ev_main = nullptr, ev_comm = nullptr;   // exchange route: pack / send-recv / unpack of a phase run beside its interior launch
-    ~mvs_shard() { if (ev_main) (void)hipEventDestroy(ev_main); if (ev_comm) (void)hipEventDestroy(ev_comm); if (comm_stream) (void)hipStreamDestroy(comm_stream); }
     // sharded table (global shape)
     DBuf<uint32_t> t_ptr; DBuf<uint16_t> t_view; DBuf<float> t_cost; DBuf<uint32_t> counts_g, keep, tmp_a, tmp_b, tmp_c;
     uint64_t nnz_global = 0;
@@ -524,10 +507,11 @@ struct mvs_shard {
     struct Lists {
         DBuf<uint32_t> idx;                 // message element indices (bytes) / node ids (words)
         std::vector<uint64_t> off;          // [phase][peer] -> element offset (size phases * P + 1)
+        std::vector<uint64_t> bytes;        // [phase][peer] -> byte offset inside the phase's chunk (size phases * (P + 1)): Exchange's ranges
         uint64_t total = 0;
     } msg_send, msg_recv, node_send, node_recv, all_send, all_recv;   // all_*: every boundary / halo node, by (peer, id): ICM exchanges
     uint32_t phases = 0;
-    DBuf<uint8_t> sbuf_msg, rbuf_msg; DBuf<uint32_t> sbuf_node, rbuf_node; DBuf<uint2> sbuf_col, rbuf_col;
+    DBuf<uint2> sbuf_col, rbuf_col;
     DBuf<unsigned long long> d_energy; DBuf<uint32_t> d_moved;
     double plan_ms = 0.0;
     // Everything that follows from (adjacency, partition, column LENGTHS of all faces) alone -- the shape of the sharded table, the
@@ -538,12 +522,256 @@ struct mvs_shard {
     Lists fs, fr; DBuf<uint32_t> pos_s, pos_r; std::vector<uint64_t> col_so, col_ro; uint64_t rec_s = 0, rec_r = 0;
     uint32_t nnz_l = 0, own_start = 0; bool tables_valid = false;
     bool plan_valid = false; uint32_t plan_colours = 0; uint64_t plan_total = 0; uint32_t plans_built = 0, plans_reused = 0;
-    // peer-push transport of the sweep loop (PeerHub): on when the communicator offers it and option "shard_peer_push" is set
-    DBuf<const unsigned long long*> e_tab;   // device table of the ranks' published energy pairs (read by the step kernel)
-    bool peer = false; DBuf<unsigned long long> e_pub; DBuf<uint32_t> m_pub; uint64_t n_ev = 0; std::vector<int> nbr; uint32_t ev_ring = 0; uint64_t peer_phases = 0;
+    std::unique_ptr<Exchange> xch; std::unique_ptr<PeerPush> push; Transport* route = nullptr;   // the transports, the one the last solve took
 };
 
 namespace {
+
+unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096)); }
+
+// Pack, grouped send / recv through the communicator, unpack; a phase's hand-over runs on a second stream beside its interior launch
+struct Exchange : Transport {
+    hipStream_t stream = nullptr; hipEvent_t ev_main = nullptr, ev_comm = nullptr;
+    bool busy = false;                                          // the last phase's unpack is queued behind ev_comm
+    DBuf<uint8_t> sbuf_msg, rbuf_msg; DBuf<uint32_t> sbuf_node, rbuf_node;   // staging (made to the plan's size by build_plan)
+    ~Exchange() override { if (ev_main) (void)hipEventDestroy(ev_main); if (ev_comm) (void)hipEventDestroy(ev_comm); if (stream) (void)hipStreamDestroy(stream); }
+    void before_phase(mvs_shard* S, uint32_t) override {
+        if (busy) { MVS_HIP(hipStreamWaitEvent(S->ctx->stream, ev_comm, 0)); busy = false; }
+    }
+    // the runs written in phase `ph` over cut edges and the labels of its boundary nodes: pack, grouped send / recv and unpack on the
+    // second stream, beside the interior launch
+    void after_boundary(mvs_shard* S, uint32_t ph) override {
+        mvs_ctx* ctx = S->ctx;
+        const int P = S->P; const size_t b = (size_t)ph * (P + 1);
+        const uint64_t* so_m = S->msg_send.bytes.data() + b; const uint64_t* ro_m = S->msg_recv.bytes.data() + b;
+        const uint64_t* so_n = S->node_send.bytes.data() + b; const uint64_t* ro_n = S->node_recv.bytes.data() + b;
+        // a rank with no boundary or halo node of this colour (or an empty part) skips the call only on a point-to-point communicator:
+        // a collective one is a rendezvous of all ranks, and a rank that stayed away would pair its NEXT operation with this one
+        if (so_m[P] + ro_m[P] + so_n[P] + ro_n[P] == 0 && !S->comm->exchange_is_collective()) return;
+        if (!stream) {
+            MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            MVS_HIP(hipEventCreateWithFlags(&ev_main, hipEventDisableTiming));
+            MVS_HIP(hipEventCreateWithFlags(&ev_comm, hipEventDisableTiming));
+        }
+        MVS_HIP(hipEventRecord(ev_main, ctx->stream));
+        MVS_HIP(hipStreamWaitEvent(stream, ev_main, 0));
+        // ONE pack launch (message bytes and labels of the whole phase, all peers), one grouped exchange, ONE unpack launch
+        const uint64_t ms0 = S->msg_send.off[(size_t)ph * P], nms = S->msg_send.off[(size_t)(ph + 1) * P] - ms0;
+        const uint64_t ns0 = S->node_send.off[(size_t)ph * P], nns = S->node_send.off[(size_t)(ph + 1) * P] - ns0;
+        const uint64_t mr0 = S->msg_recv.off[(size_t)ph * P], nmr = S->msg_recv.off[(size_t)(ph + 1) * P] - mr0;
+        const uint64_t nr0 = S->node_recv.off[(size_t)ph * P], nnr = S->node_recv.off[(size_t)(ph + 1) * P] - nr0;
+        if (nms + nns) {
+            hipLaunchKernelGGL(pack_phase_kernel, dim3(grid_for(std::max(nms, nns))), dim3(256), 0, stream, ctx->m_msg_a.p, S->msg_send.idx.p + ms0, nms, sbuf_msg.p,
+                               ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, S->node_send.idx.p + ns0, nns, sbuf_node.p);
+            MVS_LAUNCH_CHECK();
+        }
+        S->comm->exchange2(sbuf_msg.p, so_m, rbuf_msg.p, ro_m, (const uint8_t*)sbuf_node.p, so_n, (uint8_t*)rbuf_node.p, ro_n, stream);
+        if (nmr + nnr) {
+            hipLaunchKernelGGL(unpack_phase_kernel, dim3(grid_for(std::max(nmr, nnr))), dim3(256), 0, stream, ctx->m_msg_a.p, S->msg_recv.idx.p + mr0, nmr, rbuf_msg.p,
+                               ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, S->node_recv.idx.p + nr0, nnr, rbuf_node.p);
+            MVS_LAUNCH_CHECK();
+        }
+        MVS_HIP(hipEventRecord(ev_comm, stream));
+        busy = true;
+    }
+    void sweep_energy(mvs_shard* S, int) override {
+        mvs_ctx* ctx = S->ctx;
+        before_phase(S, 0);   // the last phase's unpack is in (the all-reduce below runs on the main stream: one communicator, one order)
+        Prof pr(ctx, "mrf_energy");
+        mrf_sweep_energy_reduce(ctx, S->d_energy.p);
+        if (S->P > 1) S->comm->allreduce(S->d_energy.p, 2, mvs_comm::U64, mvs_comm::SUM, ctx->stream);
+        mrf_step(ctx, S->d_energy.p);
+    }
+    void icm_round(mvs_shard* S, int) override {
+        mvs_ctx* ctx = S->ctx;
+        mrf_icm_gain(ctx, S->nb, S->ne);
+        if (S->P > 1) nodes(S, (uint32_t*)ctx->m_gain.p);
+        mrf_icm_apply(ctx, S->nb, S->ne);
+        MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        if (S->P > 1) { S->comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, ctx->stream); nodes(S, ctx->b_lab); }
+    }
+    // gains, or labels of the best labeling (ICM; the halo labels of the argmin-unary start)
+    void nodes(mvs_shard* S, uint32_t* arr) {
+        hipStream_t s = S->ctx->stream;
+        const int P = S->P;
+        const uint64_t* so = S->all_send.bytes.data(); const uint64_t* ro = S->all_recv.bytes.data();   // peer-major lists over all phases
+        if (so[P] + ro[P] == 0 && !S->comm->exchange_is_collective()) return;
+        const uint64_t ns = S->all_send.total, nr = S->all_recv.total;
+        if (ns) { hipLaunchKernelGGL(pack_words_kernel, dim3(grid_for(ns)), dim3(256), 0, s, arr, (const mvs_mrf_progress*)nullptr, 0u, S->all_send.idx.p, ns, sbuf_node.p); MVS_LAUNCH_CHECK(); }
+        S->comm->exchange((const uint8_t*)sbuf_node.p, so, (uint8_t*)rbuf_node.p, ro, s);
+        if (nr) { hipLaunchKernelGGL(unpack_words_kernel, dim3(grid_for(nr)), dim3(256), 0, s, arr, (const mvs_mrf_progress*)nullptr, 0u, S->all_recv.idx.p, nr, rbuf_node.p); MVS_LAUNCH_CHECK(); }
+    }
+};
+
+// Stores straight into the neighbours' arrays, ordered by stream events (see PeerHub)
+struct PeerPush : Transport {
+    DBuf<const unsigned long long*> e_tab;   // device table of the ranks' published energy pairs (read by the step kernel)
+    DBuf<unsigned long long> e_pub;          // [parity][2] this rank's share of a sweep's energy pair
+    DBuf<uint32_t> m_pub;                    // [parity] this rank's ICM "moved" count
+    uint64_t n_ev = 0; uint32_t ev_ring = 0; // events recorded in this solve, size of the rank's event ring
+    std::vector<int> nbr;                    // the ranks this one shares a cut with
+    uint64_t phases_pushed = 0;              // over all solves
+    // start of a solve: every rank publishes where its halo lives (after mrf_setup and the plan, so the pointers are final), learns its
+    // neighbours (ranks it shares any cut edge with) and checks that both ends of every (phase, pair) chunk agree on its size
+    void start(mvs_shard* S) override {
+        mvs_ctx* ctx = S->ctx; mvs_comm* comm = S->comm; PeerHub& H = *comm->peers();
+        const int P = S->P, me = S->me; const uint32_t C = S->phases;
+        e_pub.ensure(4);
+        MVS_HIP(hipMemsetAsync(e_pub.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));     // set-up, plan and the zeroed messages are in place before any peer may store into them
+        comm->barrier();                                // nobody still uses the previous solve's slots or events
+        PeerSlot& mine = H.slot[me];
+        mine.msg = ctx->m_msg_a.p; mine.lab = ctx->m_lab.p; mine.stride = ctx->m_stride; mine.phases = C;
+        mine.msg_recv_idx = S->msg_recv.idx.p; mine.node_recv_idx = S->node_recv.idx.p;
+        mine.msg_recv_off = S->msg_recv.off.data(); mine.node_recv_off = S->node_recv.off.data(); mine.msg_send_off = S->msg_send.off.data();
+        mine.energy = e_pub.p;
+        const uint32_t ring = 2u * std::max<uint32_t>(C, 1u) + 2u;     // a rank is never more than one sweep ahead of a rank that waits for it
+        while (mine.ev.size() < ring) { hipEvent_t e; MVS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); mine.ev.push_back(e); }
+        ev_ring = ring; n_ev = 0;
+        H.recorded[me].store(0, std::memory_order_release);
+        comm->barrier();
+        nbr.clear();
+        for (int q = 0; q < P; ++q) {
+            if (q == me) continue;
+            const PeerSlot& o = H.slot[q];
+            if (o.phases != C) throw HipError("peer push: the ranks disagree on the number of colour phases");
+            uint64_t traffic = 0;
+            for (uint32_t ph = 0; ph < C; ++ph) {
+                const size_t a = (size_t)ph * P;
+                const uint64_t sm = S->msg_send.off[a + q + 1] - S->msg_send.off[a + q], rm = o.msg_recv_off[a + me + 1] - o.msg_recv_off[a + me];
+                const uint64_t sn = S->node_send.off[a + q + 1] - S->node_send.off[a + q], rn = o.node_recv_off[a + me + 1] - o.node_recv_off[a + me];
+                if (sm != rm || sn != rn) throw HipError("peer push: send / receive sizes disagree");
+                traffic += sm + sn + (o.msg_send_off[a + me + 1] - o.msg_send_off[a + me]);
+            }
+            if (traffic) nbr.push_back(q);
+        }
+        std::vector<const unsigned long long*> tab((size_t)P);
+        for (int q = 0; q < P; ++q) tab[q] = H.slot[q].energy;
+        e_tab.ensure((size_t)P + 1);
+        MVS_HIP(hipMemcpyAsync(e_tab.p, tab.data(), (size_t)P * sizeof(tab[0]), hipMemcpyHostToDevice, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    void before_phase(mvs_shard* S, uint32_t ph) override {
+        if (ph == 0) return;   // (phase 0: the all-rank wait of the last sweep's energy)
+        Prof pr(S->ctx, "mrf_halo");
+        for (int q : nbr) wait(S, q, n_ev - 1);   // the neighbours' runs of the previous phase are in place
+    }
+    // this rank's boundary runs and labels of the phase, stored at their places in the neighbours' arrays
+    void after_boundary(mvs_shard* S, uint32_t ph) override {
+        mvs_ctx* ctx = S->ctx; hipStream_t s = ctx->stream; PeerHub& H = *S->comm->peers();
+        Prof pr(ctx, "mrf_halo");
+        const int P = S->P, me = S->me; const size_t a = (size_t)ph * P;
+        PushArgs args; int n = 0; uint64_t longest = 0;
+        auto flush = [&]() {
+            if (!n) return;
+            const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((longest + 255) / 256, 256));
+            hipLaunchKernelGGL(push_phase_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, ctx->m_msg_a.p, ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, args);
+            MVS_LAUNCH_CHECK();
+            n = 0; longest = 0;
+        };
+        for (int q : nbr) {
+            const uint64_t sm = S->msg_send.off[a + q + 1] - S->msg_send.off[a + q], sn = S->node_send.off[a + q + 1] - S->node_send.off[a + q];
+            if (sm + sn == 0) continue;
+            const PeerSlot& o = H.slot[q];
+            PushSeg& g = args.seg[n++];
+            g.sidx = S->msg_send.idx.p + S->msg_send.off[a + q]; g.didx = o.msg_recv_idx + o.msg_recv_off[a + me]; g.dmsg = o.msg; g.nm = (uint32_t)sm;
+            g.nsidx = S->node_send.idx.p + S->node_send.off[a + q]; g.ndidx = o.node_recv_idx + o.node_recv_off[a + me]; g.dlab = o.lab; g.nn = (uint32_t)sn; g.dstride = o.stride;
+            longest = std::max(longest, std::max(sm, sn));
+            if (n == PUSH_SEGS) flush();
+        }
+        flush();
+        if (ph + 1 < S->phases) record(S);
+    }
+    // the rank's pair next to its peers' (written by the reduction itself), one event behind the last phase's push AND the pair; the step
+    // kernel of every rank sums all of them: TWO launches per sweep.  The wait for ALL ranks is also what lets the next sweep's first phase
+    // start (and store into its neighbours)
+    void sweep_energy(mvs_shard* S, int sweep) override {
+        mvs_ctx* ctx = S->ctx;
+        Prof pr(ctx, "mrf_energy");
+        const uint32_t parity = (uint32_t)(sweep & 1);
+        mrf_sweep_energy_reduce(ctx, e_pub.p + 2 * parity);
+        const uint64_t idx = record(S);
+        for (int q = 0; q < S->P; ++q) if (q != S->me) wait(S, q, idx);
+        mrf_step(ctx, nullptr, e_tab.p, (uint32_t)S->P, 2u * parity);
+    }
+    // gains of the boundary nodes into the neighbours' arrays; the winners move once the neighbours' gains are in; labels of the boundary
+    // nodes and the rank's "moved" count behind ONE event that every rank waits for (apply only tests halo labels against 0, which no move
+    // changes: a neighbour's label store may overlap it); the counts are summed on the device
+    void icm_round(mvs_shard* S, int k) override {
+        mvs_ctx* ctx = S->ctx; hipStream_t s = ctx->stream; PeerHub& H = *S->comm->peers();
+        if (k == 0) {   // where this rank's halo gains / labels live (the best labeling's buffer is known only after the sweeps)
+            m_pub.ensure(4);
+            MVS_HIP(hipMemsetAsync(m_pub.p, 0, 4 * sizeof(uint32_t), s));
+            MVS_HIP(hipStreamSynchronize(s));
+            PeerSlot& mine = H.slot[S->me];
+            mine.gain = (uint32_t*)ctx->m_gain.p; mine.blab = ctx->b_lab; mine.moved = m_pub.p;
+            mine.all_recv_idx = S->all_recv.idx.p; mine.all_recv_off = S->all_recv.off.data();
+            S->comm->barrier();
+            for (int q : nbr) {
+                const PeerSlot& o = H.slot[q];
+                if (S->all_send.off[q + 1] - S->all_send.off[q] != o.all_recv_off[S->me + 1] - o.all_recv_off[S->me]) throw HipError("peer push: send / receive sizes disagree (ICM)");
+            }
+        }
+        mrf_icm_gain(ctx, S->nb, S->ne);
+        push_nodes(S, (const uint32_t*)ctx->m_gain.p, false);
+        const uint64_t ig = record(S);
+        for (int q : nbr) wait(S, q, ig);
+        mrf_icm_apply(ctx, S->nb, S->ne);
+        push_nodes(S, ctx->b_lab, true);
+        const uint32_t parity = (uint32_t)(k & 1);
+        hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)ctx->m_moved.p, m_pub.p, parity); MVS_LAUNCH_CHECK();
+        const uint64_t im = record(S);
+        WordPtrs wp; wp.n = S->P;
+        for (int q = 0; q < S->P; ++q) { if (q != S->me) wait(S, q, im); wp.p[q] = H.slot[q].moved; }
+        hipLaunchKernelGGL(sum_words_kernel, dim3(1), dim3(64), 0, s, wp, parity, S->d_moved.p); MVS_LAUNCH_CHECK();
+    }
+    void finish(mvs_shard* S, int sweeps) override {
+        MVS_HIP(hipStreamSynchronize(S->ctx->stream)); S->comm->barrier();   // every rank's stores into this rank have landed
+        phases_pushed += (uint64_t)sweeps * S->phases;
+    }
+    // every boundary node's word of `src` (this rank's gains, or its labels of the best labeling) to its place in the neighbours' arrays
+    void push_nodes(mvs_shard* S, const uint32_t* src, bool labels) {
+        hipStream_t s = S->ctx->stream; PeerHub& H = *S->comm->peers();
+        PushWArgs args; int n = 0; uint64_t longest = 0;
+        auto flush = [&]() {
+            if (!n) return;
+            const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((longest + 255) / 256, 256));
+            hipLaunchKernelGGL(push_words_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, src, args); MVS_LAUNCH_CHECK();
+            n = 0; longest = 0;
+        };
+        for (int q : nbr) {
+            const uint64_t cnt = S->all_send.off[q + 1] - S->all_send.off[q];
+            if (!cnt) continue;
+            const PeerSlot& o = H.slot[q];
+            PushWSeg& g = args.seg[n++];
+            g.sidx = S->all_send.idx.p + S->all_send.off[q]; g.didx = o.all_recv_idx + o.all_recv_off[S->me]; g.dst = labels ? o.blab : o.gain; g.n = (uint32_t)cnt;
+            longest = std::max(longest, cnt);
+            if (n == PUSH_SEGS) flush();
+        }
+        flush();
+    }
+    // one event behind everything this rank queued so far; its index (the same on every rank: one event per colour phase) is returned
+    uint64_t record(mvs_shard* S) {
+        PeerHub& H = *S->comm->peers();
+        const uint64_t idx = n_ev++;
+        MVS_HIP(hipEventRecord(H.slot[S->me].ev[idx % ev_ring], S->ctx->stream));
+        H.recorded[S->me].store(idx + 1, std::memory_order_release);
+        return idx;
+    }
+    // this rank's stream waits for event `idx` of rank q; the host only waits until q has RECORDED it (so that the stream wait refers to that record)
+    void wait(mvs_shard* S, int q, uint64_t idx) {
+        PeerHub& H = *S->comm->peers();
+        const auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t spin = 0; H.recorded[q].load(std::memory_order_acquire) <= idx; ++spin) {
+            if ((spin & 255u) == 255u) {
+                if (S->comm->aborted()) throw HipError("peer push: another rank failed");
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) throw HipError("peer push: a rank did not reach its next colour phase within 120 s");
+                if ((spin & 4095u) == 4095u) std::this_thread::yield();
+            }
+        }
+        MVS_HIP(hipStreamWaitEvent(S->ctx->stream, H.slot[q].ev[idx % ev_ring], 0));
+    }
+};
 
 void sort_pairs(mvs_shard* S, DBuf<unsigned long long>& k, DBuf<unsigned long long>* v, uint32_t n, hipStream_t s) {
     if (n == 0) return;
@@ -615,12 +843,13 @@ void finish_node_list(mvs_shard* S, mvs_shard::Lists& L, DBuf<unsigned long long
     if (n) { hipLaunchKernelGGL(plan_node_kernel, dim3((n + 255) / 256), dim3(256), 0, s, k.p, n, L.idx.p); MVS_LAUNCH_CHECK(); }
 }
 
-// per-peer byte offsets of one phase's chunk (elem = bytes per element)
-void phase_offsets(const mvs_shard::Lists& L, int P, uint32_t phases, uint32_t ph, uint32_t elem, std::vector<uint64_t>& out) {
-    // a phase's chunk of a list is contiguous, peer after peer: offsets relative to the start of the phase
-    out.assign((size_t)P + 1, 0);
-    (void)phases;
-    for (int q = 0; q <= P; ++q) out[q] = (L.off[(size_t)ph * P + q] - L.off[(size_t)ph * P]) * elem;
+// per-peer byte offsets of every phase's chunk of a list, relative to the start of the phase (elem = bytes per element): a phase's
+// chunk is contiguous, peer after peer
+void phase_offsets(mvs_shard::Lists& L, int P, uint32_t elem) {
+    const size_t phases = (L.off.size() - 1) / P;
+    L.bytes.assign(phases * (P + 1), 0);
+    for (size_t ph = 0; ph < phases; ++ph)
+        for (int q = 0; q <= P; ++q) L.bytes[ph * (P + 1) + q] = (L.off[ph * P + q] - L.off[ph * P]) * elem;
 }
 
 void build_plan(mvs_shard* S) {
@@ -658,179 +887,15 @@ void build_plan(mvs_shard* S) {
     sort_pairs(S, S->k2, nullptr, ns, s); sort_pairs(S, S->k3, nullptr, nr, s);
     finish_node_list(S, S->all_send, S->k2, ns, 1, s);
     finish_node_list(S, S->all_recv, S->k3, nr, 1, s);
-    // the same node lists are contiguous per peer (all phases): the ICM exchanges use them with one range per peer
-    S->sbuf_msg.ensure(S->msg_send.total + 64); S->rbuf_msg.ensure(S->msg_recv.total + 64);
-    S->sbuf_node.ensure(S->node_send.total + 16); S->rbuf_node.ensure(S->node_recv.total + 16);
+    phase_offsets(S->msg_send, S->P, 1); phase_offsets(S->msg_recv, S->P, 1);
+    phase_offsets(S->node_send, S->P, 4); phase_offsets(S->node_recv, S->P, 4);
+    phase_offsets(S->all_send, S->P, 4); phase_offsets(S->all_recv, S->P, 4);
+    Exchange& X = *S->xch;   // (its node exchange serves the peer-push route's argmin-unary start too)
+    X.sbuf_msg.ensure(S->msg_send.total + 64); X.rbuf_msg.ensure(S->msg_recv.total + 64); X.sbuf_node.ensure(S->node_send.total + 16); X.rbuf_node.ensure(S->node_recv.total + 16);
     S->d_energy.ensure(4); S->d_moved.ensure(4);
     MVS_HIP(hipEventRecord(e1, s)); MVS_HIP(hipEventSynchronize(e1));
     float ms = 0.0f; MVS_HIP(hipEventElapsedTime(&ms, e0, e1)); S->plan_ms = ms;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-}
-
-unsigned grid_for(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096)); }
-
-// after colour phase `ph`: message runs written in this phase over cut edges + labels of this phase's boundary nodes
-void exchange_phase(mvs_shard* S, uint32_t ph, hipStream_t s) {
-    mvs_ctx* ctx = S->ctx;
-    const int P = S->P; const uint32_t C = S->phases;
-    std::vector<uint64_t> so_m, ro_m, so_n, ro_n;
-    phase_offsets(S->msg_send, P, C, ph, 1, so_m); phase_offsets(S->msg_recv, P, C, ph, 1, ro_m);
-    phase_offsets(S->node_send, P, C, ph, 4, so_n); phase_offsets(S->node_recv, P, C, ph, 4, ro_n);
-    // a rank with no boundary or halo node of this colour (or an empty part) skips the call only on a point-to-point communicator:
-    // the in-process one is a rendezvous of all ranks, and a rank that stayed away would pair its NEXT operation with this one
-    if (so_m[P] + ro_m[P] + so_n[P] + ro_n[P] == 0 && !S->comm->exchange_is_collective()) return;
-    // ONE pack launch (message bytes and labels of the whole phase, all peers), one grouped exchange, ONE unpack launch
-    const uint64_t ms0 = S->msg_send.off[(size_t)ph * P], nms = S->msg_send.off[(size_t)(ph + 1) * P] - ms0;
-    const uint64_t ns0 = S->node_send.off[(size_t)ph * P], nns = S->node_send.off[(size_t)(ph + 1) * P] - ns0;
-    const uint64_t mr0 = S->msg_recv.off[(size_t)ph * P], nmr = S->msg_recv.off[(size_t)(ph + 1) * P] - mr0;
-    const uint64_t nr0 = S->node_recv.off[(size_t)ph * P], nnr = S->node_recv.off[(size_t)(ph + 1) * P] - nr0;
-    if (nms + nns) {
-        hipLaunchKernelGGL(pack_phase_kernel, dim3(grid_for(std::max(nms, nns))), dim3(256), 0, s, ctx->m_msg_a.p, S->msg_send.idx.p + ms0, nms, S->sbuf_msg.p,
-                           ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, S->node_send.idx.p + ns0, nns, S->sbuf_node.p);
-        MVS_LAUNCH_CHECK();
-    }
-    S->comm->exchange2(S->sbuf_msg.p, so_m.data(), S->rbuf_msg.p, ro_m.data(),
-                       (const uint8_t*)S->sbuf_node.p, so_n.data(), (uint8_t*)S->rbuf_node.p, ro_n.data(), s);
-    if (nmr + nnr) {
-        hipLaunchKernelGGL(unpack_phase_kernel, dim3(grid_for(std::max(nmr, nnr))), dim3(256), 0, s, ctx->m_msg_a.p, S->msg_recv.idx.p + mr0, nmr, S->rbuf_msg.p,
-                           ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, S->node_recv.idx.p + nr0, nnr, S->rbuf_node.p);
-        MVS_LAUNCH_CHECK();
-    }
-}
-// every boundary node's word of `arr` (gains, labels of the best labeling) to the neighbours, halo words back: ICM
-void exchange_nodes(mvs_shard* S, uint32_t* arr) {
-    mvs_ctx* ctx = S->ctx; hipStream_t s = ctx->stream;
-    const int P = S->P;
-    std::vector<uint64_t> so((size_t)P + 1), ro((size_t)P + 1);
-    for (int q = 0; q <= P; ++q) { so[q] = S->all_send.off[q] * 4; ro[q] = S->all_recv.off[q] * 4; }   // peer-major lists over all phases
-    if (so[P] + ro[P] == 0 && !S->comm->exchange_is_collective()) return;
-    const uint64_t ns = S->all_send.total, nr = S->all_recv.total;
-    if (ns) { hipLaunchKernelGGL(pack_words_kernel, dim3(grid_for(ns)), dim3(256), 0, s, arr, (const mvs_mrf_progress*)nullptr, 0u, S->all_send.idx.p, ns, S->sbuf_node.p); MVS_LAUNCH_CHECK(); }
-    S->comm->exchange((const uint8_t*)S->sbuf_node.p, so.data(), (uint8_t*)S->rbuf_node.p, ro.data(), s);
-    if (nr) { hipLaunchKernelGGL(unpack_words_kernel, dim3(grid_for(nr)), dim3(256), 0, s, arr, (const mvs_mrf_progress*)nullptr, 0u, S->all_recv.idx.p, nr, S->rbuf_node.p); MVS_LAUNCH_CHECK(); }
-}
-
-// ---- the peer-push transport ----
-// start of a solve: every rank publishes where its halo lives (after mrf_setup and the plan, so the pointers are final), learns its
-// neighbours (ranks it shares any cut edge with) and checks that both ends of every (phase, pair) chunk agree on its size
-void peer_publish(mvs_shard* S) {
-    mvs_ctx* ctx = S->ctx; mvs_comm* comm = S->comm; PeerHub& H = *comm->peers();
-    const int P = S->P, me = S->me; const uint32_t C = S->phases;
-    S->e_pub.ensure(4);
-    MVS_HIP(hipMemsetAsync(S->e_pub.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));     // set-up, plan and the zeroed messages are in place before any peer may store into them
-    comm->barrier();                                // nobody still uses the previous solve's slots or events
-    PeerSlot& mine = H.slot[me];
-    mine.msg = ctx->m_msg_a.p; mine.lab = ctx->m_lab.p; mine.stride = ctx->m_stride; mine.phases = C;
-    mine.msg_recv_idx = S->msg_recv.idx.p; mine.node_recv_idx = S->node_recv.idx.p;
-    mine.msg_recv_off = S->msg_recv.off.data(); mine.node_recv_off = S->node_recv.off.data(); mine.msg_send_off = S->msg_send.off.data();
-    mine.energy = S->e_pub.p;
-    const uint32_t ring = 2u * std::max<uint32_t>(C, 1u) + 2u;     // a rank is never more than one sweep ahead of a rank that waits for it
-    while (mine.ev.size() < ring) { hipEvent_t e; MVS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); mine.ev.push_back(e); }
-    S->ev_ring = ring; S->n_ev = 0;
-    H.recorded[me].store(0, std::memory_order_release);
-    comm->barrier();
-    S->nbr.clear();
-    for (int q = 0; q < P; ++q) {
-        if (q == me) continue;
-        const PeerSlot& o = H.slot[q];
-        if (o.phases != C) throw HipError("peer push: the ranks disagree on the number of colour phases");
-        uint64_t traffic = 0;
-        for (uint32_t ph = 0; ph < C; ++ph) {
-            const size_t a = (size_t)ph * P;
-            const uint64_t sm = S->msg_send.off[a + q + 1] - S->msg_send.off[a + q], rm = o.msg_recv_off[a + me + 1] - o.msg_recv_off[a + me];
-            const uint64_t sn = S->node_send.off[a + q + 1] - S->node_send.off[a + q], rn = o.node_recv_off[a + me + 1] - o.node_recv_off[a + me];
-            if (sm != rm || sn != rn) throw HipError("peer push: send / receive sizes disagree");
-            traffic += sm + sn + (o.msg_send_off[a + me + 1] - o.msg_send_off[a + me]);
-        }
-        if (traffic) S->nbr.push_back(q);
-    }
-    std::vector<const unsigned long long*> tab((size_t)P);
-    for (int q = 0; q < P; ++q) tab[q] = H.slot[q].energy;
-    S->e_tab.ensure((size_t)P + 1);
-    MVS_HIP(hipMemcpyAsync(S->e_tab.p, tab.data(), (size_t)P * sizeof(tab[0]), hipMemcpyHostToDevice, ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-}
-// after colour phase `ph`: this rank's boundary runs and labels of the phase, stored at their places in the neighbours' arrays
-void peer_push_phase(mvs_shard* S, uint32_t ph) {
-    mvs_ctx* ctx = S->ctx; hipStream_t s = ctx->stream; PeerHub& H = *S->comm->peers();
-    const int P = S->P, me = S->me; const size_t a = (size_t)ph * P;
-    PushArgs args; int n = 0; uint64_t longest = 0;
-    auto flush = [&]() {
-        if (!n) return;
-        const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((longest + 255) / 256, 256));
-        hipLaunchKernelGGL(push_phase_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, ctx->m_msg_a.p, ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, args);
-        MVS_LAUNCH_CHECK();
-        n = 0; longest = 0;
-    };
-    for (int q : S->nbr) {
-        const uint64_t sm = S->msg_send.off[a + q + 1] - S->msg_send.off[a + q], sn = S->node_send.off[a + q + 1] - S->node_send.off[a + q];
-        if (sm + sn == 0) continue;
-        const PeerSlot& o = H.slot[q];
-        PushSeg& g = args.seg[n++];
-        g.sidx = S->msg_send.idx.p + S->msg_send.off[a + q]; g.didx = o.msg_recv_idx + o.msg_recv_off[a + me]; g.dmsg = o.msg; g.nm = (uint32_t)sm;
-        g.nsidx = S->node_send.idx.p + S->node_send.off[a + q]; g.ndidx = o.node_recv_idx + o.node_recv_off[a + me]; g.dlab = o.lab; g.nn = (uint32_t)sn; g.dstride = o.stride;
-        longest = std::max(longest, std::max(sm, sn));
-        if (n == PUSH_SEGS) flush();
-    }
-    flush();
-}
-// ICM rounds: where this rank's halo gains / labels live (the best labeling's buffer is known only after the sweeps)
-void peer_publish_icm(mvs_shard* S) {
-    mvs_ctx* ctx = S->ctx; PeerHub& H = *S->comm->peers();
-    S->m_pub.ensure(4);
-    MVS_HIP(hipMemsetAsync(S->m_pub.p, 0, 4 * sizeof(uint32_t), ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-    PeerSlot& mine = H.slot[S->me];
-    mine.gain = (uint32_t*)ctx->m_gain.p; mine.blab = ctx->b_lab; mine.moved = S->m_pub.p;
-    mine.all_recv_idx = S->all_recv.idx.p; mine.all_recv_off = S->all_recv.off.data();
-    S->comm->barrier();
-    for (int q : S->nbr) {
-        const PeerSlot& o = H.slot[q];
-        if (S->all_send.off[q + 1] - S->all_send.off[q] != o.all_recv_off[S->me + 1] - o.all_recv_off[S->me]) throw HipError("peer push: send / receive sizes disagree (ICM)");
-    }
-}
-// every boundary node's word of `src` (this rank's gains, or its labels of the best labeling) to its place in the neighbours' arrays
-void peer_push_nodes(mvs_shard* S, const uint32_t* src, bool labels) {
-    hipStream_t s = S->ctx->stream; PeerHub& H = *S->comm->peers();
-    PushWArgs args; int n = 0; uint64_t longest = 0;
-    auto flush = [&]() {
-        if (!n) return;
-        const unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((longest + 255) / 256, 256));
-        hipLaunchKernelGGL(push_words_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, src, args); MVS_LAUNCH_CHECK();
-        n = 0; longest = 0;
-    };
-    for (int q : S->nbr) {
-        const uint64_t cnt = S->all_send.off[q + 1] - S->all_send.off[q];
-        if (!cnt) continue;
-        const PeerSlot& o = H.slot[q];
-        PushWSeg& g = args.seg[n++];
-        g.sidx = S->all_send.idx.p + S->all_send.off[q]; g.didx = o.all_recv_idx + o.all_recv_off[S->me]; g.dst = labels ? o.blab : o.gain; g.n = (uint32_t)cnt;
-        longest = std::max(longest, cnt);
-        if (n == PUSH_SEGS) flush();
-    }
-    flush();
-}
-// one event behind everything this rank queued so far; its index (the same on every rank: one event per colour phase) is returned
-uint64_t peer_record(mvs_shard* S) {
-    PeerHub& H = *S->comm->peers();
-    const uint64_t idx = S->n_ev++;
-    MVS_HIP(hipEventRecord(H.slot[S->me].ev[idx % S->ev_ring], S->ctx->stream));
-    H.recorded[S->me].store(idx + 1, std::memory_order_release);
-    return idx;
-}
-// this rank's stream waits for event `idx` of rank q; the host only waits until q has RECORDED it (so that the stream wait refers to that record)
-void peer_wait(mvs_shard* S, int q, uint64_t idx) {
-    PeerHub& H = *S->comm->peers();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 0; H.recorded[q].load(std::memory_order_acquire) <= idx; ++spin) {
-        if ((spin & 255u) == 255u) {
-            if (S->comm->aborted()) throw HipError("peer push: another rank failed");
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) throw HipError("peer push: a rank did not reach its next colour phase within 120 s");
-            if ((spin & 4095u) == 4095u) std::this_thread::yield();
-        }
-    }
-    MVS_HIP(hipStreamWaitEvent(S->ctx->stream, H.slot[q].ev[idx % S->ev_ring], 0));
 }
 
 }  // namespace
@@ -867,8 +932,8 @@ mvs_status mvs_comm_create_rccl(int device, int rank, int world, const uint8_t i
 }
 
 /* `world` communicators for as many host threads of this process; rank r drives a context on devices[r] (NULL: all on the current
- * device).  Distinct devices get peer access switched on in both directions between every pair; where a pair cannot address each
- * other the peer-push transport is off for this communicator (the exchange route copies through the runtime instead). */
+ * device).  Distinct devices get peer access switched on in both directions between every pair; a pair that cannot address each
+ * other is MVS_ERR_UNSUPPORTED (one process per GPU over RCCL serves such a node). */
 mvs_status mvs_comm_create_local_devices(int world, const int* devices, mvs_comm** out) {
     if (!out || world < 1 || world > MAX_PARTS) return api_fail(MVS_ERR_INVALID, "bad argument");
     MVS_API_BEGIN
@@ -890,10 +955,12 @@ mvs_status mvs_comm_create_local_devices(int world, const int* devices, mvs_comm
             const int b = hub->device[q];
             if (b == a) continue;
             int can = 0;
-            if (hipDeviceCanAccessPeer(&can, a, b) != hipSuccess || !can) { (void)hipGetLastError(); hub->peer_ok = false; continue; }
-            const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) hub->peer_ok = false;
+            hipError_t e = hipDeviceCanAccessPeer(&can, a, b);
+            if (e == hipSuccess) e = can ? hipDeviceEnablePeerAccess(b, 0) : hipErrorPeerAccessUnsupported;
             (void)hipGetLastError();
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+                throw StatusError(MVS_ERR_UNSUPPORTED, "devices " + std::to_string(a) + " and " + std::to_string(b) + " cannot address each other's memory: "
+                                  "run one process per GPU over RCCL (mvs_comm_create_rccl; bench.py --launch torchrun)");
         }
     }
     for (int r = 0; r < world; ++r) { auto* c = new LocalComm; c->rank = r; c->world = world; c->hub = hub; out[r] = c; }
@@ -905,7 +972,8 @@ mvs_status mvs_comm_create_local(int world, mvs_comm** out) { return mvs_comm_cr
  * blocking (a rank's driver that dies OUTSIDE the library calls this so that its peers are released).  In-process communicators only. */
 void mvs_comm_abort(mvs_comm* comm) { if (comm) comm->abort_all(); }
 
-/* *peer_push = 1: the ranks of this communicator can store into each other's device memory (the sweep loop's peer-push transport) */
+/* *peer_push = 1: the ranks of this communicator can store into each other's device memory (the in-process one): a solve of more than
+ * one rank takes the peer-push transport */
 mvs_status mvs_comm_info(mvs_comm* comm, int* rank, int* world, int* peer_push) {
     if (!comm) return api_fail(MVS_ERR_INVALID, "null argument");
     if (rank) *rank = comm->rank;
@@ -926,6 +994,7 @@ mvs_status mvs_shard_create(mvs_ctx* ctx, mvs_comm* comm, const uint32_t* part_b
     if (comm->device() >= 0 && comm->device() != ctx->device)
         throw StatusError(MVS_ERR_INVALID, "rank " + std::to_string(comm->rank) + " of this communicator drives device " + std::to_string(comm->device()) + ", the context lives on device " + std::to_string(ctx->device));
     std::unique_ptr<mvs_shard> S(new mvs_shard); S->ctx = ctx; S->comm = comm; S->me = comm->rank; S->P = comm->world;
+    S->xch.reset(new Exchange); S->push.reset(new PeerPush);
     S->parts.n = S->P;
     S->F = ctx->n_faces;
     // The parts are contiguous ranges of the LIBRARY's face order (k_bvh.hip build_scene_order: a Hilbert curve over the face
@@ -955,9 +1024,6 @@ mvs_status mvs_shard_create(mvs_ctx* ctx, mvs_comm* comm, const uint32_t* part_b
         hipLaunchKernelGGL(boundary_mark_kernel, dim3((S->ne - S->nb + 255) / 256), dim3(256), 0, ctx->stream, S->d_adj_ptr, S->d_adj, S->parts, S->me, S->nb, S->ne, S->bnd.p);
         MVS_LAUNCH_CHECK();
     }
-    MVS_HIP(hipStreamCreateWithFlags(&S->comm_stream, hipStreamNonBlocking));
-    MVS_HIP(hipEventCreateWithFlags(&S->ev_main, hipEventDisableTiming));
-    MVS_HIP(hipEventCreateWithFlags(&S->ev_comm, hipEventDisableTiming));
     MVS_HIP(hipStreamSynchronize(ctx->stream));
     *out = S.release();
     MVS_API_END
@@ -1138,108 +1204,41 @@ mvs_status mvs_shard_view_selection(mvs_shard* S, const mvs_mrf_params* params, 
     const int lag = std::max(0, std::min(std::max(ctx->mrf_lag, 2), (int)mvs_ctx::RING - 2));
     mvs_mrf_progress pg; memset(&pg, 0, sizeof(pg));
     int issued = 0, polled = 0;
-    S->peer = S->P > 1 && comm->peers() != nullptr && ctx->shard_peer_push != 0 && S->phases > 0;
-    if (comm->peers()) {
-        // every rank takes the same route (the option is per context): a rank that stored into peers which expect an exchange would corrupt them
-        S->d_moved.ensure(4);
-        const uint32_t mine = S->peer ? 1u : 0u; uint32_t all[2] = {mine, mine};
-        MVS_HIP(hipMemcpyAsync(S->d_moved.p, &mine, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (S->P > 1) {
-            comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, s);
-            MVS_HIP(hipMemcpyAsync(&all[0], S->d_moved.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); MVS_HIP(hipStreamSynchronize(s));
-            if (all[0] != 0u && all[0] != (uint32_t)S->P) throw StatusError(MVS_ERR_INVALID, "option shard_peer_push differs between the ranks");
-        }
-    }
-    if (S->peer) peer_publish(S);
-    PeerHub* hub = S->peer ? comm->peers() : nullptr;
+    // The transport follows from the communicator: ranks that can address each other's memory (the in-process communicator) store
+    // into each other's arrays, RCCL ranks exchange.  Every rank takes the same route: the colour phases are those of one global colouring.
+    Transport& T = S->P > 1 && comm->peers() && S->phases > 0 ? static_cast<Transport&>(*S->push) : *S->xch;
+    S->route = &T;
+    T.start(S);
     // A colour phase: BOUNDARY nodes first, their runs and labels leave, then the INTERIOR -- whose nodes have no neighbour on another rank,
     // so their launch neither waits for a peer nor reads anything a peer stores; the hand-over of phase c has the whole interior launch of
     // phase c to land before this rank's boundary nodes of colour c + 1 need it.  (A colour class is an independent set: same values.)
     const bool split = S->P > 1;
-    bool comm_busy = false;
     while (issued < P.max_sweeps && !pg.stopped) {
         for (uint32_t ph = 0; ph < S->phases; ++ph) {
-            if (S->peer && ph > 0) {   // the neighbours' runs of the previous phase are in place (phase 0: the all-rank wait of the last sweep's energy)
-                Prof pr(ctx, "mrf_halo");
-                for (int q : S->nbr) peer_wait(S, q, S->n_ev - 1);
-            } else if (comm_busy) {    // exchange route: the previous phase's unpack is behind ev_comm
-                MVS_HIP(hipStreamWaitEvent(s, S->ev_comm, 0)); comm_busy = false;
-            }
+            T.before_phase(S, ph);
             if (!split) { Prof pr(ctx, "mrf_sweep"); mrf_sweep_phase(ctx, ph, nb, ne, MRF_PART_ALL); continue; }
             { Prof pr(ctx, "mrf_sweep_boundary"); mrf_sweep_phase(ctx, ph, nb, ne, MRF_PART_BOUNDARY); }
-            if (S->peer) {
-                Prof pr(ctx, "mrf_halo");
-                peer_push_phase(S, ph);
-                if (ph + 1 < S->phases) peer_record(S);
-            } else {
-                // pack, grouped send / recv and unpack on the shard's second stream, beside the interior launch
-                MVS_HIP(hipEventRecord(S->ev_main, s));
-                MVS_HIP(hipStreamWaitEvent(S->comm_stream, S->ev_main, 0));
-                exchange_phase(S, ph, S->comm_stream);
-                MVS_HIP(hipEventRecord(S->ev_comm, S->comm_stream));
-                comm_busy = true;
-            }
+            T.after_boundary(S, ph);
             { Prof pr(ctx, "mrf_sweep"); mrf_sweep_phase(ctx, ph, nb, ne, MRF_PART_INTERIOR); }
         }
-        if (comm_busy) { MVS_HIP(hipStreamWaitEvent(s, S->ev_comm, 0)); comm_busy = false; }   // (the all-reduce below runs on the main stream: one communicator, one order)
-        {   // the sweep's energy: own share (accumulated by the sweep kernels, or the energy kernel on the generic path),
-            // all-reduced, fed to the device-side stop rule -- the host polls the report of `lag` sweeps ago
-            Prof pr(ctx, "mrf_energy");
-            if (S->peer) {
-                // the rank's pair next to its peers' (written by the reduction itself), one event behind the last phase's push AND the pair;
-                // the step kernel of every rank sums all of them: TWO launches per sweep.  The wait for ALL ranks is also what lets the next
-                // sweep's first phase start (and store into its neighbours)
-                const uint32_t parity = (uint32_t)(issued & 1);
-                if (ctx->m_fast) mrf_sweep_energy_reduce(ctx, S->e_pub.p + 2 * parity);
-                else { mrf_energy(ctx, false, nb, ne, true); hipLaunchKernelGGL(publish_energy_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long*)ctx->m_energy.p, S->e_pub.p, parity); MVS_LAUNCH_CHECK(); }
-                const uint64_t idx = peer_record(S);
-                for (int q = 0; q < S->P; ++q) if (q != S->me) peer_wait(S, q, idx);
-                mrf_step(ctx, nullptr, S->e_tab.p, (uint32_t)S->P, 2u * parity);
-            } else {
-                if (ctx->m_fast) mrf_sweep_energy_reduce(ctx, S->d_energy.p); else { mrf_energy(ctx, false, nb, ne, true); MVS_HIP(hipMemcpyAsync(S->d_energy.p, ctx->m_energy.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s)); }
-                if (S->P > 1) comm->allreduce(S->d_energy.p, 2, mvs_comm::U64, mvs_comm::SUM, s);
-                mrf_step(ctx, S->d_energy.p);
-            }
-        }
+        // the sweep's energy: own share (accumulated by the sweep kernels), summed over the ranks, fed to the device-side stop rule --
+        // the host polls the report of `lag` sweeps ago
+        T.sweep_energy(S, issued);
         ++issued;
         if (issued - lag > polled) mrf_poll(ctx, (uint32_t)++polled, &pg);
     }
     while (polled < issued && !pg.stopped) mrf_poll(ctx, (uint32_t)++polled, &pg);
     if (issued > 0) mrf_poll(ctx, (uint32_t)issued, &pg);
-    if (S->peer) { MVS_HIP(hipStreamSynchronize(s)); comm->barrier(); S->peer_phases += (uint64_t)issued * S->phases; }   // every rank's stores into this rank have landed
+    T.finish(S, issued);
     R.sweeps = issued > 0 ? pg.stop_sweep : 0u;
     resolve_best(ctx);
-    if (S->P > 1 && issued == 0) exchange_nodes(S, ctx->b_lab);   // argmin-unary start: the halo labels
+    if (S->P > 1 && issued == 0) S->xch->nodes(S, ctx->b_lab);   // argmin-unary start: the halo labels
     mrf_exact_costs(ctx, nb, ne);
     // ICM rounds: gains of the own nodes, gains of the boundary nodes to the neighbours, winners move, labels of the boundary nodes
     // to the neighbours; the all-reduced "moved" count of a round reaches the host through the pinned ring two rounds late (as in
     // the single-context polish: icm_rounds), so no round waits for a read-back.  Every rank reads the same counts at the same
     // round indices, hence takes the same decisions; a round queued after the one that moved nothing finds no positive gain anywhere.
-    if (S->peer && P.icm_iters > 0) peer_publish_icm(S);
-    const int it = icm_rounds(ctx, P.icm_iters, S->d_moved.p, [&](int k) {
-        mrf_icm_gain(ctx, nb, ne);
-        if (S->peer) {
-            // gains of the boundary nodes into the neighbours' arrays; the winners move once the neighbours' gains are in; labels of the
-            // boundary nodes and the rank's "moved" count behind ONE event that every rank waits for (apply only tests halo labels
-            // against 0, which no move changes: a neighbour's label store may overlap it); the counts are summed on the device
-            peer_push_nodes(S, (const uint32_t*)ctx->m_gain.p, false);
-            const uint64_t ig = peer_record(S);
-            for (int q : S->nbr) peer_wait(S, q, ig);
-            mrf_icm_apply(ctx, nb, ne);
-            peer_push_nodes(S, ctx->b_lab, true);
-            const uint32_t parity = (uint32_t)(k & 1);
-            hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)ctx->m_moved.p, S->m_pub.p, parity); MVS_LAUNCH_CHECK();
-            const uint64_t im = peer_record(S);
-            WordPtrs wp; wp.n = S->P;
-            for (int q = 0; q < S->P; ++q) { if (q != S->me) peer_wait(S, q, im); wp.p[q] = hub->slot[q].moved; }
-            hipLaunchKernelGGL(sum_words_kernel, dim3(1), dim3(64), 0, s, wp, parity, S->d_moved.p); MVS_LAUNCH_CHECK();
-        } else {
-            if (S->P > 1) exchange_nodes(S, (uint32_t*)ctx->m_gain.p);
-            mrf_icm_apply(ctx, nb, ne);
-            MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            if (S->P > 1) { comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, s); exchange_nodes(S, ctx->b_lab); }
-        }
-    });
+    const int it = icm_rounds(ctx, P.icm_iters, S->d_moved.p, [&](int k) { T.icm_round(S, k); });
     R.icm_iters = (uint32_t)it;
     mrf_energy(ctx, true, nb, ne, true);
     MVS_HIP(hipMemcpyAsync(S->d_energy.p, ctx->m_energy.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
@@ -1271,9 +1270,9 @@ mvs_status mvs_shard_plan_info(mvs_shard* S, uint64_t* msg_bytes_per_sweep, uint
 
 mvs_status mvs_shard_transport_info(mvs_shard* S, int* peer_push, uint64_t* phases_pushed, int* neighbours, uint32_t* colour_phases) {
     if (!S) return api_fail(MVS_ERR_INVALID, "null argument");
-    if (peer_push) *peer_push = S->peer ? 1 : 0;
-    if (phases_pushed) *phases_pushed = S->peer_phases;
-    if (neighbours) *neighbours = (int)S->nbr.size();
+    if (peer_push) *peer_push = S->route == S->push.get() ? 1 : 0;
+    if (phases_pushed) *phases_pushed = S->push->phases_pushed;
+    if (neighbours) *neighbours = (int)S->push->nbr.size();
     if (colour_phases) *colour_phases = S->phases;
     return MVS_OK;
 }

@@ -2,7 +2,7 @@
 shape with only the rank's OWN and HALO columns filled (what csrc/shard.hip gives a rank), its faces numbered along the library's own
 order so that the rank's nodes are the range [0, F / N).  Timed with the building-block API (mvs_ctx_mrf_*): the solver's set-up, the
 colour phases of a sweep over the own range, one full ICM gain pass -- next to the same calls on the whole table.  The sweeps of a real
-sharded solve add the transport between the phases (scripts/transport_time.py); this script prices the GPU WORK of a rank.
+sharded solve add the transport between the phases (profiles/r06_transport_c3.json); this script prices the GPU WORK of a rank.
 usage: python scripts/rank_share_mrf.py [--config 3] [--parts 8] [--sweeps 10]"""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

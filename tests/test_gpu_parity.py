@@ -538,12 +538,12 @@ def test_call_order_errors(ctx):
     with pytest.raises(M.MvsError):
         c2.data_costs()
     # the options mvs_set_option accepts are exactly those include/mvs_viewsel.h lists; retired ones are unknown names
-    for name in ("mrf_late_old", "mrf_wide", "mrf_run_pad", "mrf_damp_period", "dc_overlap_prep", "bvh_caller_order"):
+    for name in ("mrf_late_old", "mrf_wide", "mrf_run_pad", "mrf_damp_period", "dc_overlap_prep", "bvh_caller_order", "shard_peer_push"):
         with pytest.raises(M.MvsError, match="unknown option"):
             c2.set_option(name, 0)
     for name in ("stats", "count_rays", "verbose", "profile", "info_wave_area", "info_wave_area_words", "info_words", "info_cert_shift",
                  "max_labels", "prep_fused", "face_order", "bvh_window", "bvh_upper_min_faces", "ray_xcd", "mrf_lag", "mrf_graph",
-                 "mrf_xcd", "mrf_blocks_per_cu", "mrf_force_generic", "shard_peer_push"):
+                 "mrf_xcd", "mrf_blocks_per_cu", "mrf_force_generic"):
         c2.set_option(name, 0)
     c2.close()
 
@@ -832,7 +832,7 @@ def test_cpp_sharded_path_equals_single_gpu(name, P):
         assert cut_share < 0.25, cut_share
 
 
-def _cpp_shards_equal_single(s, P, reps=2, settings_kw=None, max_labels=0, check_oracle_labels=False, peer_push=None, rccl_uid=None):
+def _cpp_shards_equal_single(s, P, reps=2, settings_kw=None, max_labels=0, check_oracle_labels=False, rccl_uid=None):
     """runs the scene through a single context and through P thread-ranks of csrc/shard.hip; asserts equality (see the callers);
     returns the share of faces that are halo faces of some rank.  rccl_uid: every rank makes its communicator with mvs_comm_create_rccl
     from this unique id (inside the rank's thread: ncclCommInitRank blocks until all ranks joined) instead of the in-process one."""
@@ -881,7 +881,6 @@ def _cpp_shards_equal_single(s, P, reps=2, settings_kw=None, max_labels=0, check
                 assert comms[r].info() == {"rank": r, "world": P, "peer_push": False}
             c = M.Context(0); c.set_mesh(tv, tf, tn); c.set_views(s.cams, timg)
             if max_labels: c.set_option("max_labels", max_labels)
-            if peer_push is not None: c.set_option("shard_peer_push", peer_push)
             sh = M.shard.Shard(c, comms[r], pb_arg, tap, tad)
             own = sh.own_faces()
             for rep in range(reps):                                # twice: steady-state reuse of plan buffers and tables
@@ -920,25 +919,17 @@ def _cpp_shards_equal_single(s, P, reps=2, settings_kw=None, max_labels=0, check
         assert (ms["energy_fixed"], ms["cut_edges"], ms["sweeps"], ms["icm_iters"], ms["unseen"]) == \
                (st0["energy_fixed"], st0["cut_edges"], st0["sweeps"], st0["icm_iters"], st0["unseen"]), "rank %d" % r
         assert (info["boundary_nodes"] > 0 and info["msg_bytes_per_sweep"] > 0) or len(own) < 100
-        # the sweep loop's transport: runs stored straight into the peers' arrays unless switched off (the in-process ranks share an address space)
-        assert info["peer_push"] == (P > 1 and peer_push != 0 and rccl_uid is None) and (info["phases_pushed"] > 0) == info["peer_push"], info
+        # the sweep loop's transport follows from the communicator: the in-process ranks store straight into the peers' arrays, RCCL ranks exchange
+        assert info["peer_push"] == (P > 1 and rccl_uid is None) and (info["phases_pushed"] > 0) == info["peer_push"], info
         got[own] = labels
     assert np.array_equal(got, lab0), "labels depend on the partition"
     for c in comms: c.close()
     return halo_total / max(F, 1)
 
 
-@pytest.mark.parametrize("name,P", [("bumpy", 3), ("spiky32", 4), ("bumpy", (0.0, 0.5, 0.5, 1.0))], ids=["bumpy-3", "spiky32-4", "bumpy-empty-part"])
-def test_cpp_sharded_path_through_the_communicators_exchange(name, P):
-    """the same runs with option shard_peer_push = 0: pack launch, exchange through the communicator (what the RCCL communicator does
-    with grouped ncclSend / ncclRecv), unpack launch per colour phase instead of stores into the peers' arrays -- identical results"""
-    _cpp_shards_equal_single(get_scene(name), P, reps=2, peer_push=0)
-
-
 def test_a_failing_rank_does_not_leave_the_others_blocked():
     """one rank of the in-process communicator fails inside a sharded call (bad settings: it throws before the call's first
-    collective): the other rank's host-side wait ends with an error instead of blocking, and the communicator serves the next call --
-    on both transports"""
+    collective): the other rank's host-side wait ends with an error instead of blocking, and the communicator serves the next call"""
     import threading
     import time
     import torch
@@ -971,10 +962,8 @@ def test_a_failing_rank_does_not_leave_the_others_blocked():
                 first[r] = (str(e), time.time() - t)
             with pytest.raises(M.MvsError, match="needs data costs"):   # neither rank has a table now: a call that fails its own checks is
                 sh.view_selection(labels)                               # numbered like any other (the ranks stay in step)
-            for push in (1, 0):                                    # the communicator is not poisoned: the next calls run, on either transport
-                c.set_option("shard_peer_push", push)
-                sh.data_costs(M.Settings()); ms = sh.view_selection(labels); c.synchronize()
-                assert sh.transport_info()["peer_push"] == bool(push)
+            sh.data_costs(M.Settings()); ms = sh.view_selection(labels); c.synchronize()   # the communicator is not poisoned: the next calls run
+            assert sh.transport_info()["peer_push"] is True
             out[r] = (own, labels.cpu().numpy().view(np.uint32)[:len(own)], ms)
             sh.close(); c.close()
         except Exception as e:  # noqa: BLE001
@@ -1070,8 +1059,8 @@ def test_config5_in_full_on_eight_logical_ranks(tmp_path):
 
 
 @isolated
-@pytest.mark.parametrize("name,P", [("bumpy", 2), ("bumpy", 3), ("spiky32", 8), ("bumpy", (0.0, 0.5, 0.5, 1.0)), ("bumpy-shuffled", 3)],
-                         ids=["bumpy-2", "bumpy-3", "spiky32-8", "bumpy-empty-part", "bumpy-shuffled-3"])
+@pytest.mark.parametrize("name,P", [("bumpy", 2), ("bumpy", 3), ("spiky32", 4), ("spiky32", 8), ("bumpy", (0.0, 0.5, 0.5, 1.0)), ("bumpy-shuffled", 3)],
+                         ids=["bumpy-2", "bumpy-3", "spiky32-4", "spiky32-8", "bumpy-empty-part", "bumpy-shuffled-3"])
 def test_cpp_sharded_path_over_the_rccl_communicator_with_peers(name, P):
     """The RCCL communicator of csrc/shard.hip (mvs_comm_create_rccl; RcclComm::post / exchange2: one ncclGroup of sends and receives per
     colour phase on the shard's second stream, beside the interior launch; ncclAllReduce of the data-cost barrier, of the per-sweep energy
