@@ -13,13 +13,23 @@ apps/texrecon/texrecon.cpp:96-127.
 
 Prints ONE JSON line (rank 0).  `value` = faces of the scene / max-over-ranks seconds per
 step.  N > 1 runs the SAME scene partitioned over the ranks (BASELINE.json config 4):
-"scaling": "strong".
+"scaling": "strong".  A plain run does what that line needs and nothing else: it builds the
+scene, uploads it, warms up, times the steps and prints.
 
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
 
 also writes what the last timed step computed -- labels, solver statistics, the data-cost table (a
 fixed, seeded sample of its faces when large) -- as DIR/<name>.npy (float32 / float64, at most 64 MB);
 the scene is seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+
+also measures and checks everything beside the headline, never inside the timed steps:
+the stage breakdown and the rooflines (extra, untimed steps; rocprofv3 counter passes that re-run this
+script), the upload, partition, adjacency and sub-graph entry points, the CPU oracle and the reference's
+own code, the real-like, shuffled and drop-in workloads, and the oracle check of the timed step (exit
+status 3 on any difference; N > 1: the labels against a single context).  The --no-* options leave
+parts of it out.
 """
 import argparse
 import json
@@ -310,7 +320,7 @@ def shuffled_workload(device, dev, scene, t_img, settings, params, steps=5, warm
 
 
 def pmc_pass(config, counters, timeout_s=420, extra_args=()):
-    """One `rocprofv3 --pmc <counters>` pass over ONE step of this script (no traces in the same run).  Returns
+    """One `rocprofv3 --pmc <counters>` pass over ONE step of a plain run of this script (no traces in the same run).  Returns
     {kernel short name: [dispatches, {counter: sum over dispatches}]} or raises."""
     import csv, glob, re, shutil, subprocess, tempfile
     rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
@@ -320,7 +330,7 @@ def pmc_pass(config, counters, timeout_s=420, extra_args=()):
     env = dict(os.environ, TMPDIR="/tmp")
     try:
         cmd = [rocprof, "--pmc"] + list(counters) + ["--output-format", "csv", "-d", tmp, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
-               "--config", str(config), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-parity", "--no-traffic", "--no-real-like", "--pmc-child"] + list(extra_args)
+               "--config", str(config), "--steps", "1", "--warmup", "0"] + list(extra_args)
         r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s)
         files = glob.glob(os.path.join(tmp, "**", "*counter_collection.csv"), recursive=True)
         if r.returncode != 0 or not files:
@@ -541,13 +551,15 @@ def run_inproc(args, cfg, max_labels):
             ctx.synchronize(); gate.wait()
             elapsed = time.perf_counter() - t
             labels = lab.cpu().numpy().view(np.uint32)[:len(own)].copy()
-            ctx.set_option("profile", 1); ctx.get_profile()
-            for _ in range(n_prof if args.steps > 0 else 0):
-                step()
-            prof = ctx.get_profile()
+            prof = {}
+            if args.full and args.steps > 0:
+                ctx.set_option("profile", 1); ctx.get_profile()
+                for _ in range(n_prof):
+                    step()
+                prof = ctx.get_profile()
             nph = C.c_uint32(0); ctx.L.mvs_ctx_mrf_num_phases(ctx.h, C.byref(nph))
             res[r] = dict(elapsed=elapsed, own=own, labels=labels, prof=prof, n_phases=max(int(nph.value), 1), plan=dict(sh.plan_info(), **sh.transport_info()), **box)
-            if r == 0 and not args.no_parity and args.steps > 0:
+            if r == 0 and args.full and not args.no_parity and args.steps > 0:
                 # the single-context reference on this rank's GPU, while the other ranks are done with their device work
                 c1 = M.Context(d)
                 try:
@@ -598,12 +610,14 @@ def run_inproc(args, cfg, max_labels):
                       "damping": "alpha = %.2f on every fourth sweep (1st, 5th, ...), none on the others; rho = %.2f" % (params.damping, params.rho),
                       "arithmetic": "fp32 geometry and messages, fp64 footprint sums, 32.32 fixed-point energies; messages STORED as 8-bit codes"},
            "launch": "in-process: 1 process, %d host threads, one per GPU%s" % (N, " (MVS_BENCH_ONE_GPU: all ranks time-slice cuda:0 -- a test, not a scaling number)" if one_gpu else ""),
-           "devices": devices, "roofline": roof, "stages": stages, "per_rank_ms_per_step": [1000.0 * o["elapsed"] / max(args.steps, 1) for o in res],
+           "devices": devices, "per_rank_ms_per_step": [1000.0 * o["elapsed"] / max(args.steps, 1) for o in res],
            "halo": dict(r0["plan"], peer_access=bool(peer_ok), driver="C++ (csrc/shard.hip); sweep transport: " +
                         ("peer push (stores into the neighbours' arrays, one stream event per colour phase)" if r0["plan"].get("peer_push") else "pack / rendezvous copies / unpack per colour phase")),
            "sharded_driver": "C++ / in-process communicator (csrc/shard.hip)", "cpu_baseline": None,
            "hardware": ("UNMEASURED ON HARDWARE: %d logical ranks time-slice ONE device (every launch of every rank serialises on it); a test of the N > 1 code path, not a scaling number" % N) if one_gpu
                        else "%d devices, one rank each" % N}
+    if args.full:
+        out.update({"roofline": roof, "stages": stages})
     if args.dump_outputs is not None and args.steps > 0:
         labels = np.zeros(F, dtype=np.uint32)
         for o in res:
@@ -636,20 +650,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="3", help="BASELINE.md config: 2 = 200k faces / 50 views, 3 = 2M faces / 200 views (the headline), 5 = one rank's share of the 10M-face / 1000-view scene; "
                                                   "'real' = the real-like second workload as the main workload (profiling runs; never the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline, outside the timed steps: stages, rooflines, "
+                                                        "upload and entry points, CPU baseline, real-like / shuffled / drop-in workloads, the oracle check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=170.0, help="seconds the cpu_baseline leg may take: the whole scene through the oracle, best of up to 3 runs (a scene too large for it is sampled)")
     ap.add_argument("--max-labels", type=int, default=-1, help="label-space compression (mvs_set_option max_labels); default: off, 64 for --config 5")
     ap.add_argument("--config5-n", type=int, default=250, help="icosphere frequency of the reduced config-5 run (250 = one rank's share of 8)")
-    ap.add_argument("--no-real-like", action="store_true", help="skip the second workload (synth.CONFIGS['real']: a scene shaped like a real capture) reported beside the headline")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed step's table (N = 1 only)")
-    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the counter passes' own runs: exactly one step, nothing else
-    ap.add_argument("--no-dropin", action="store_true", help="skip the timing of the real drop-in path (tex:: adapter on host containers)")
+    ap.add_argument("--no-real-like", action="store_true", help="--full without the second workload (synth.CONFIGS['real']: a scene shaped like a real capture) reported beside the headline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the oracle check of the timed step's table (N > 1: without the single-context check)")
+    ap.add_argument("--no-dropin", action="store_true", help="--full without the timing of the real drop-in path (tex:: adapter on host containers)")
     ap.add_argument("--parity-faces", type=int, default=100000)
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes that fill roofline.traffic")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the rocprofv3 --pmc passes that fill roofline.traffic")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--shard", action="store_true", help="take the sharded C++ / RCCL path even at world size 1 (test of the N > 1 code path on one GPU)")
     ap.add_argument("--shuffle-main", action="store_true", help="experiments: the main workload with faces and vertices in random order")
-    ap.add_argument("--no-shuffled", action="store_true", help="skip the extra leg that runs the headline scene with faces AND vertices randomly permuted")
+    ap.add_argument("--no-shuffled", action="store_true", help="--full without the extra leg that runs the headline scene with faces AND vertices randomly permuted")
     ap.add_argument("--launch", default="inproc", choices=["inproc", "torchrun"],
                     help="--gpus N > 1 started without a launcher: 'inproc' = one process, one host thread per GPU, peer-push transport (the single-node route); "
                          "'torchrun' = start torch.distributed.run as a child process, one process per GPU, RCCL")
@@ -739,11 +754,11 @@ def main():
         log("scene: %d faces, %d views %dx%d, built in %.1fs" % (F, V, cfg["width"], cfg["height"], time.time() - t0))
     part = G.equal_parts(F, world)   # == the library's own equal cut (mvs_ctx_partition_faces) of its order
 
-    # ---- inputs resident in HBM (the upload is timed and reported as h2d_ms; it is never part of `value`) ----
+    # ---- inputs resident in HBM (with --full the upload is timed and reported as h2d_ms; it is never part of `value`) ----
     # timed through the library's own host-pointer entry (what the tex:: drop-in calls: mvs_scene_set_mesh / mvs_scene_set_views pin the
     # caller's buffers in place for the copy): twice on one context -- the first call also allocates the device buffers
     h2d_first_ms = h2d_ms = 0.0
-    if rank == 0 and args.steps > 0 and not args.pmc_child:
+    if rank == 0 and args.full and args.steps > 0:
         ch = M.Context(local_rank)
         for k in range(2):
             t_h2d = time.perf_counter()
@@ -804,9 +819,9 @@ def main():
             info["nnz_global"] = info["pipe"].nnz_global
         info["dc"], info["mrf"] = st, ms
 
-    # row f1 (outside the headline window, reported separately): tex::build_adjacency_graph on the GPU
+    # row f1 (outside the headline window, reported separately with --full): tex::build_adjacency_graph on the GPU
     pre = {}
-    if not harness:
+    if args.full and not harness:
         # the partition the sharded path uses, as an entry point of its own: order + cut on the device (also part of every timed step:
         # stage dc_order)
         ctx.partition_faces(max(world, 1))   # (first call: allocations)
@@ -817,7 +832,7 @@ def main():
         pp = ctx.get_profile()
         if "partition" in pp:
             pre["partition_ms"] = pp["partition"][0] / max(pp["partition"][1], 1)   # device time of mvs_ctx_partition_faces: order + cut (the same pass is stage dc_order of every step)
-    if world == 1 and not args.shard and not args.pmc_child:
+    if args.full and world == 1 and not args.shard:
         ctx.build_adjacency(); ctx.get_profile()
         for _ in range(3):
             ctx.build_adjacency()
@@ -850,13 +865,15 @@ def main():
             dump_outputs(args.dump_outputs, info["timed"]["labels"], mrf_stats(info["mrf"], info["nnz_global"]) + ([("percentile", pct)] if pct is not None else []),
                          ctx.costs_download())
     n_prof = min(max(args.steps, 1), 3)
-    ctx.set_option("profile", 1)
-    for _ in range(n_prof if (args.steps > 0 and not args.pmc_child) else 0):
-        step()
-    prof = ctx.get_profile()
-    # row f3 (outside the headline window, reported separately): UniGraph::get_subgraphs of the labeling, all labels at once
+    prof = {}
+    if args.full and args.steps > 0:
+        ctx.set_option("profile", 1)
+        for _ in range(n_prof):
+            step()
+        prof = ctx.get_profile()
+    # row f3 (outside the headline window, reported separately with --full): UniGraph::get_subgraphs of the labeling, all labels at once
     post = {}
-    if world == 1 and args.steps > 0 and not args.shard and not args.pmc_child:
+    if args.full and world == 1 and args.steps > 0 and not args.shard:
         ctx.get_subgraphs(t_ap, t_ad, t_lab, V + 1, on_device=True); ctx.get_profile()
         for _ in range(3):
             sg = ctx.get_subgraphs(t_ap, t_ad, t_lab, V + 1, on_device=True)
@@ -916,7 +933,7 @@ def main():
     # bytes the path does not move earn no credit).  N_ray_nodes / N_ray_tris = node visits and (ray, triangle) tests of the packet
     # traversal of this scene, counted once outside the timed region (option "count_rays").
     roof_path = None
-    if rank == 0 and world == 1 and not args.shard and args.steps > 0 and not args.no_traffic:   # (--no-traffic = the counter passes' own child runs)
+    if args.full and rank == 0 and world == 1 and not args.shard and args.steps > 0 and not args.no_traffic:   # (its SQ counter pass: --no-traffic leaves it out)
         W, H = cfg["width"], cfg["height"]
         c2 = M.Context(local_rank)   # its own context: the table of the last timed step stays on `ctx` for the parity check
         try:
@@ -975,16 +992,17 @@ def main():
                       "energy": float(mrf["energy"]), "partition": ("harness-caller-order-%d" if harness else "library-hilbert-%d") % world, "face_order_in": "shuffled" if args.shuffle_main else "as built", "msg_bits": 8, "max_labels": max_labels,
                       "stop_rule": "window %d / %.2f %% / >= %d sweeps (the reference hands StopWhenReturnsDiminish(5, 0.01) to mapMAP, view_selection.cpp:84)" % (params.window, 100.0 * params.min_improvement, params.min_sweeps),
                       "damping": "alpha = %.2f on every fourth sweep (1st, 5th, ...), none on the others; rho = %.2f" % (params.damping, params.rho),
-                      "arithmetic": "fp32 geometry and messages, fp64 footprint sums, 32.32 fixed-point energies; messages STORED as 8-bit codes"},
-           "h2d_ms": h2d_ms, "h2d_first_ms": h2d_first_ms, "h2d_GBps": h2d_bytes / max(h2d_ms, 1e-9) / 1e6,
-           "pcie_inclusive_value": F / ((ms_per_step + h2d_ms) / 1000.0),
-           "roofline": roof, "roofline_path": roof_path, "stages": stages, "pre_path": pre, "post_path": post}
+                      "arithmetic": "fp32 geometry and messages, fp64 footprint sums, 32.32 fixed-point energies; messages STORED as 8-bit codes"}}
+    if args.full:
+        out.update({"h2d_ms": h2d_ms, "h2d_first_ms": h2d_first_ms, "h2d_GBps": h2d_bytes / max(h2d_ms, 1e-9) / 1e6,
+                    "pcie_inclusive_value": F / ((ms_per_step + h2d_ms) / 1000.0),
+                    "roofline": roof, "roofline_path": roof_path, "stages": stages, "pre_path": pre, "post_path": post})
     if "plan" in info:
         out["halo"] = dict(info["plan"], driver="C++ (csrc/shard.hip); sweep transport: " + ("peer push (stores into the neighbours' arrays, one stream event per colour phase)"
                                                                                                if info["plan"].get("peer_push") else "grouped ncclSend/ncclRecv per colour phase, bytes on the wire"))
     if world > 1 or args.shard:
         out["sharded_driver"] = "C++ / RCCL (csrc/shard.hip)" if args.backend == "nccl" else "python test harness over %s (one-GPU test mode)" % args.backend
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(scene, faces, normals, adj_ptr, adj,
                                                dict(max_sweeps=params.max_sweeps, min_sweeps=params.min_sweeps), args.cpu_budget)
@@ -995,25 +1013,25 @@ def main():
                 out["cpu_baseline"]["reference_data_costs"] = reference_leg(scene, faces, normals)
         except Exception as e:  # noqa: BLE001
             log("reference leg failed:", e)
-    if rank == 0 and world == 1 and not args.no_real_like and not args.shard and args.config == 3 and args.steps > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_real_like and not args.shard and args.config == 3 and args.steps > 0:
         try:
             out["real_like"] = real_like_workload(local_rank, dev, params)
         except Exception as e:  # noqa: BLE001 -- an extra, never at the expense of the headline
             out["real_like"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_shuffled and not args.no_traffic and not args.shard and args.steps > 0 and args.config in (2, 3) and not args.shuffle_main:
+    if args.full and rank == 0 and world == 1 and not args.no_shuffled and not args.no_traffic and not args.shard and args.steps > 0 and args.config in (2, 3) and not args.shuffle_main:
         try:
             out["shuffled"] = shuffled_workload(local_rank, dev, scene, t_img, settings, params, steps=min(max(args.steps, 1), 5), check=not args.no_parity, n_check=args.parity_faces)
             out["shuffled"]["vs_headline_ms"] = out["shuffled"]["ms_per_step"] / ms_per_step
         except Exception as e:  # noqa: BLE001 -- an extra, never at the expense of the headline
             out["shuffled"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_dropin and not args.no_traffic and not args.shard and args.steps > 0 and args.config in (2, 3):
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and not args.no_traffic and not args.shard and args.steps > 0 and args.config in (2, 3):
         try:
             out["dropin"] = dropin_timing(cfg)
             out["dropin_ms"] = out["dropin"]["dropin_ms"]
         except Exception as e:  # noqa: BLE001 -- an extra, never at the expense of the headline
             out["dropin"] = {"error": repr(e)}
     rc = 0
-    if rank == 0 and world == 1 and not args.no_parity and args.steps > 0 and not args.shard:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and args.steps > 0 and not args.shard:
         try:
             out["parity"] = parity_check(ctx, scene, faces, normals, adj_ptr, adj, params, args.parity_faces, info["timed"], max_labels, dc.get("percentile"))
             out["parity_checked"] = bool(out["parity"]["ok"])

@@ -1754,30 +1754,51 @@ def test_row_f2_scene_folder_to_spt_and_vec(tmp_path):
 
 def test_bench_contract_single_and_two_ranks(tmp_path):
     """bench.py prints ONE JSON line with the contract's keys; the N > 1 code path (torch.distributed.run, one process
-    per rank) runs end to end -- here with 2 ranks sharing cuda:0 over gloo, the collectives' call pattern is the RCCL one"""
+    per rank) runs end to end -- here with 2 ranks sharing cuda:0 over gloo, the collectives' call pattern is the RCCL one.
+    A plain run (no --full) times the same steps and computes the same outputs, and measures or checks nothing else."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-traffic",
-                        "--parity-faces", "30000"], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-traffic",
+                        "--parity-faces", "30000", "--dump-outputs", str(tmp_path / "full")], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d1 = json.loads(lines[0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+    headline = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+    for k in headline + ("roofline",):
         assert k in d1, k
     assert d1["n_gpus"] == 1 and d1["steps"] == 2 and d1["config"]["faces"] == 200000 and d1["roofline"]["bound"] == "hbm"
     # the checker leg: the timed step's table against the oracle (pattern, qualities bit for bit) + solver parity on the sample
     assert d1["parity_checked"] is True and d1["parity"]["faces"] == 30000 and d1["parity"]["labels_equal"], d1.get("parity")
     assert d1["config"]["msg_bits"] == 8 and d1["h2d_ms"] > 0
+    # the plain run: the headline keys and nothing that takes work of its own; the last timed step's outputs equal the full run's
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain")],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    dp = json.loads(lines[0])
+    for k in headline:
+        assert k in dp, k
+    for k in ("roofline", "roofline_path", "stages", "pre_path", "post_path", "h2d_ms", "cpu_baseline", "real_like", "shuffled", "dropin", "parity", "parity_checked"):
+        assert k not in dp, k
+    assert dp["unit"] == d1["unit"] == "faces/s" and dp["metric"] == d1["metric"] and dp["dtype"] == d1["dtype"] and dp["higher_is_better"] is True
+    assert dp["steps"] == 2 and dp["warmup"] == 1 and dp["ms_per_step"] > 0 and abs(dp["value"] - 200000 / (dp["ms_per_step"] / 1000.0)) <= 1e-6 * dp["value"]
+    assert dp["config"] == d1["config"]
+    names = sorted(os.listdir(tmp_path / "full"))
+    assert names == sorted(os.listdir(tmp_path / "plain")) and "labels.npy" in names and "table_cost.npy" in names
+    for n in names:
+        a, b = np.load(tmp_path / "full" / n), np.load(tmp_path / "plain" / n)
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8)), n
     # the N > 1 code path of the product (C++ shard driver + RCCL) launched the way the driver launches it, at the world size a
     # 1-GPU box allows: same nnz, sweeps and energy as the plain single-GPU path
     port = 29400 + os.getpid() % 150
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "2", "--steps", "2", "--warmup", "1",
-                        "--shard", "--no-cpu-baseline", "--no-traffic"], capture_output=True, text=True, env=env, timeout=900)
+                        "--shard", "--full", "--no-cpu-baseline", "--no-traffic"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     ds = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert ds["config"]["nnz"] == d1["config"]["nnz"] and ds["config"]["sweeps"] == d1["config"]["sweeps"] and abs(ds["config"]["energy"] - d1["config"]["energy"]) < 1e-6
@@ -1799,7 +1820,7 @@ def test_bench_contract_single_and_two_ranks(tmp_path):
     # the command the driver runs for a scaling point -- `python bench.py --gpus N`, no launcher: N in-process ranks (one host thread per GPU,
     # peer-push transport; here all of them on cuda:0), n_gpus = N, labels of all ranks equal to a single context's
     for n in (2, 3):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", "2", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, env=env, timeout=900)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", "2", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1

@@ -172,12 +172,12 @@ def test_kernel_arithmetic_on_host_equals_oracle():
 
 
 def test_bench_cli_contract():
-    """bench.py exposes the driver's flags (--gpus/--steps/--warmup) and needs no GPU to say so"""
+    """bench.py exposes the driver's flags (--gpus/--steps/--warmup, --full for everything beside the headline) and needs no GPU to say so"""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full"):
         assert flag in r.stdout
 
 
