@@ -402,6 +402,55 @@ mvs_status mvs_ctx_get_subgraphs(mvs_ctx* ctx, uint32_t n_faces, const uint32_t*
                                  const uint32_t* labels, int labels_on_device, uint32_t n_labels, mvs_subgraphs* out,
                                  int out_on_device);
 
+/* Row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp) with tone mapping `none`, from the caller's labels
+ * (0 = unseen, L = view L - 1) on the context's mesh and views; no data-cost pass is needed.  adj_ptr / adj: the face adjacency
+ * of mvs_ctx_get_subgraphs.  The definition -- the vertex rows, the patches generate_texture_patches would make, the seam samples,
+ * the normal equations and their Jacobi-preconditioned CG -- is DESIGN.md section 4 "Global seam leveling"; every output is the
+ * same bits on any device.  Everything is keyed on the caller's face and vertex ids:
+ *   x_ptr[v] .. x_ptr[v + 1]: the unknowns (x rows) of vertex v, one per distinct non-zero label of its faces, labels ascending
+ *   (x_label); x_adjust[3 row + c]: the adjustment of that (vertex, label) in channel c, mean removed;
+ *   corner_adjust[9 f + 3 k + c]: the adjustment of corner k of face f (zeros for label 0) -- upstream's patch_adjust_values
+ *   (global_seam_leveling.cpp:300-318), face by face.
+ * MVS_ERR_LABELING when a label exceeds the number of views or a labelled face's box leaves its view's image (the asserts of
+ * generate_candidate); MVS_ERR_STATE without mesh or views.  With out_on_device the four arrays are device pointers owned by
+ * the context (valid until its next call), otherwise malloc'ed host copies (mvs_gsl_result_free). */
+typedef struct mvs_gsl_params {
+    float tolerance;          /* CG tolerance (1e-4) */
+    uint32_t max_iterations;  /* per channel (1000) */
+    float lambda;             /* weight of the smoothness rows Gamma (0.1) */
+    uint32_t reserved;
+} mvs_gsl_params;
+void mvs_gsl_default_params(mvs_gsl_params* p);
+typedef struct mvs_gsl_result {
+    uint32_t n_verts, n_faces, x_rows, reserved;
+    uint32_t* x_ptr;          /* [n_verts + 1] */
+    uint32_t* x_label;        /* [x_rows] */
+    float* x_adjust;          /* [3 x_rows] */
+    float* corner_adjust;     /* [9 n_faces] */
+} mvs_gsl_result;
+typedef struct mvs_gsl_stats {
+    uint64_t patches, merged;          /* texture patches; candidates absorbed by another of their label */
+    uint64_t x_rows, a_rows, gamma_rows, lhs_nnz_lower;
+    uint64_t seam_edges, samples;      /* seam-edge entries of all A rows; bilinear samples taken */
+    uint32_t iterations[3];            /* CG iterations per channel (the breaking iteration not counted) */
+    float error[3];                    /* sqrt(|r|^2 / |Rhs|^2) per channel */
+    float ms_rows, ms_patches, ms_system, ms_solve, ms_output, ms_total;   /* device time per phase */
+} mvs_gsl_stats;
+mvs_status mvs_ctx_global_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device,
+                                        const uint32_t* labels, int labels_on_device, const mvs_gsl_params* params,
+                                        mvs_gsl_result* out, int out_on_device, mvs_gsl_stats* stats);
+void mvs_gsl_result_free(mvs_gsl_result* r);
+/* host copies of the last call's system (tests): Lhs as its lower triangle (CSR, columns ascending), Rhs [3 x_rows], the A rows
+ * (x rows a_col[2 r] with +1, a_col[2 r + 1] with -1) and b [3 a_rows], x before the mean [3 x_rows]; mvs_gsl_system_free */
+typedef struct mvs_gsl_system {
+    uint32_t x_rows, a_rows;
+    uint64_t lhs_nnz;
+    uint32_t* lhs_ptr; uint32_t* lhs_col; float* lhs_val;
+    float* rhs; uint32_t* a_col; float* b; float* x_raw;
+} mvs_gsl_system;
+mvs_status mvs_ctx_gsl_system(mvs_ctx* ctx, mvs_gsl_system* out);
+void mvs_gsl_system_free(mvs_gsl_system* s);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

@@ -115,6 +115,8 @@ struct alignas(16) NodeDesc {
 };
 static_assert(sizeof(NodeDesc) == 48, "NodeDesc must be 48 bytes");
 
+struct GslDev;   // row f5 (k_seam.hip)
+
 }  // namespace mvs
 
 struct mvs_ctx {
@@ -217,6 +219,9 @@ struct mvs_ctx {
 
     // ---- row f3: patch components (k_patch.hip) ----
     mvs::DBuf<uint32_t> p_label_ptr, p_comp_ptr, p_comp_faces, p_parent, p_root, p_state, p_flag, p_pos, p_roots, p_roots2, p_rlab, p_rlab2, p_adj_ptr, p_adj, p_labels;
+
+    // ---- row f5: global seam leveling (k_seam.hip): buffers allocated on first use ----
+    mvs::GslDev* gsl = nullptr;
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -321,4 +326,6 @@ void read_block(mvs_ctx* ctx, const void* d_src, void* out, size_t bytes);   // 
 void exclusive_scan_u32(mvs_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n, uint32_t* d_total);
 // exact 64-bit total of a u32 array (blocking): the guard in front of scans whose total may pass 2^32
 uint64_t sum_u32(mvs_ctx* ctx, const uint32_t* in, size_t n);
+// frees the buffers of row f5 (k_seam.hip)
+void gsl_release(mvs_ctx* ctx);
 }  // namespace mvs

@@ -72,6 +72,28 @@ class Subgraphs(C.Structure):
                 ("label_ptr", C.c_void_p), ("comp_ptr", C.c_void_p), ("comp_faces", C.c_void_p)]
 
 
+class GslParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("max_iterations", C.c_uint32), ("lam", C.c_float), ("reserved", C.c_uint32)]
+
+
+class GslResult(C.Structure):
+    _fields_ = [("n_verts", C.c_uint32), ("n_faces", C.c_uint32), ("x_rows", C.c_uint32), ("reserved", C.c_uint32),
+                ("x_ptr", C.c_void_p), ("x_label", C.c_void_p), ("x_adjust", C.c_void_p), ("corner_adjust", C.c_void_p)]
+
+
+GSL_COUNTS = ("patches", "merged", "x_rows", "a_rows", "gamma_rows", "lhs_nnz_lower", "seam_edges", "samples")
+GSL_MS = ("ms_rows", "ms_patches", "ms_system", "ms_solve", "ms_output", "ms_total")
+
+
+class GslStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in GSL_COUNTS] + [("iterations", C.c_uint32 * 3), ("error", C.c_float * 3)] + [(k, C.c_float) for k in GSL_MS]
+
+
+class GslSystem(C.Structure):
+    _fields_ = [("x_rows", C.c_uint32), ("a_rows", C.c_uint32), ("lhs_nnz", C.c_uint64), ("lhs_ptr", C.c_void_p), ("lhs_col", C.c_void_p),
+                ("lhs_val", C.c_void_p), ("rhs", C.c_void_p), ("a_col", C.c_void_p), ("b", C.c_void_p), ("x_raw", C.c_void_p)]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -164,6 +186,9 @@ def load_library():
         "mvs_shard_own_faces": [vp, vp, C.POINTER(u32)],
         "mvs_ctx_partition_faces": [vp, i32, vp, vp], "mvs_partition_faces": [C.POINTER(CMesh), i32, vp, vp],
         "mvs_ctx_table_order": [vp, vp, C.POINTER(i32)],
+        "mvs_gsl_default_params": [C.POINTER(GslParams)], "mvs_gsl_result_free": [C.POINTER(GslResult)], "mvs_gsl_system_free": [C.POINTER(GslSystem)],
+        "mvs_ctx_global_seam_leveling": [vp, vp, vp, i32, vp, i32, C.POINTER(GslParams), C.POINTER(GslResult), i32, C.POINTER(GslStats)],
+        "mvs_ctx_gsl_system": [vp, C.POINTER(GslSystem)],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -187,7 +212,8 @@ def load_library():
         else:
             fn = getattr(L, name)
         fn.argtypes = argtypes
-        if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+        if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -426,6 +452,71 @@ class Context:
         if on_device:
             return DevArray(sg.label_ptr, n_labels + 1), DevArray(sg.comp_ptr, sg.n_components + 1), DevArray(sg.comp_faces, F)
         return _subgraphs_to_numpy(self.L, sg)
+
+    def global_seam_leveling(self, adj_ptr, adj, labels, params=None, on_device=False):
+        """Row f5: tex::global_seam_leveling on the context's mesh and views from the caller's labels (0 = unseen, L = view L - 1).
+        Returns ({x_ptr, x_label, x_adjust (x_rows, 3), corner_adjust (F, 3, 3)}, stats); with on_device=True the four arrays are
+        DevArrays owned by the context (valid until the next call).  params: default_gsl_params(...)."""
+        pa, d0 = _ptr(adj_ptr); pb, d1 = _ptr(adj); pl, dl = _ptr(labels)
+        assert d0 == d1
+        p = params or default_gsl_params()
+        res, st = GslResult(), GslStats()
+        self._keep["gsl"] = (adj_ptr, adj, labels)
+        _check(self.L, self.L.mvs_ctx_global_seam_leveling(self.h, pa, pb, d0, pl, dl, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st)))
+        stats = {k: int(getattr(st, k)) for k in GSL_COUNTS}
+        stats.update({k: float(getattr(st, k)) for k in GSL_MS})
+        stats["iterations"] = [int(x) for x in st.iterations]
+        stats["error"] = np.array(list(st.error), np.float32)
+        NV, F, XR = int(res.n_verts), int(res.n_faces), int(res.x_rows)
+        if on_device:
+            return dict(x_ptr=DevArray(res.x_ptr, NV + 1), x_label=DevArray(res.x_label, XR), x_adjust=DevArray(res.x_adjust, 3 * XR),
+                        corner_adjust=DevArray(res.corner_adjust, 9 * F)), stats
+        out = dict(x_ptr=_grab(res.x_ptr, NV + 1, C.c_uint32), x_label=_grab(res.x_label, XR, C.c_uint32),
+                   x_adjust=_grab(res.x_adjust, 3 * XR, C.c_float).reshape(XR, 3), corner_adjust=_grab(res.corner_adjust, 9 * F, C.c_float).reshape(F, 3, 3))
+        self.L.mvs_gsl_result_free(C.byref(res))
+        return out, stats
+
+    def gsl_system(self):
+        """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
+        a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
+        s = GslSystem()
+        _check(self.L, self.L.mvs_ctx_gsl_system(self.h, C.byref(s)))
+        XR, AR, NZ = int(s.x_rows), int(s.a_rows), int(s.lhs_nnz)
+        out = dict(lhs_ptr=_grab(s.lhs_ptr, XR + 1, C.c_uint32), lhs_col=_grab(s.lhs_col, NZ, C.c_uint32), lhs_val=_grab(s.lhs_val, NZ, C.c_float),
+                   rhs=_grab(s.rhs, 3 * XR, C.c_float).reshape(XR, 3), a_col=_grab(s.a_col, 2 * AR, C.c_uint32).reshape(AR, 2),
+                   b=_grab(s.b, 3 * AR, C.c_float).reshape(AR, 3), x_raw=_grab(s.x_raw, 3 * XR, C.c_float).reshape(XR, 3))
+        self.L.mvs_gsl_system_free(C.byref(s))
+        return out
+
+
+def _grab(ptr, n, ctype):
+    if n == 0:
+        return np.zeros(0, np.uint32 if ctype is C.c_uint32 else np.float32)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n,)).copy()
+
+
+def default_gsl_params(**kw):
+    """mvs_gsl_default_params (tolerance 1e-4, max_iterations 1000, lam 0.1) with overrides"""
+    p = GslParams()
+    load_library().mvs_gsl_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def global_seam_leveling(scene, labels, params=None, ctx=None):
+    """tex::global_seam_leveling for a synth.Scene-like object (verts, faces, normals, cams, images, adj_ptr, adj) and its labels
+    (texrecon.cpp:169-172): returns (arrays, stats) of Context.global_seam_leveling."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
+        ctx.set_views(scene.cams, scene.images)
+        return ctx.global_seam_leveling(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
+                                        np.ascontiguousarray(labels, dtype=np.uint32), params)
+    finally:
+        if own:
+            ctx.close()
 
 
 def _subgraphs_to_numpy(L, sg):
