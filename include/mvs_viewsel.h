@@ -451,6 +451,51 @@ typedef struct mvs_gsl_system {
 mvs_status mvs_ctx_gsl_system(mvs_ctx* ctx, mvs_gsl_system* out);
 void mvs_gsl_system_free(mvs_gsl_system* s);
 
+/* Row f6: generate_texture_patches for the labelled faces (generate_texture_patches.cpp:78-138, :484-508) followed by
+ * TexturePatch::adjust_colors (texture_patch.cpp:41-122) on every patch, tone mapping `none`: from the caller's labels and the
+ * per-corner adjustments of row f5 (corner_adjust[9 f + 3 k + c]; NULL = zeros, upstream's branch without global seam leveling,
+ * texrecon.cpp:173-184) to the packed patch images and masks.  The definition is DESIGN.md section 4 "Texture patches"; every
+ * array is the same bits on any device and in every run.  The call stands alone: it needs the mesh and the views, no data-cost
+ * pass and no previous mvs_ctx_global_seam_leveling.  Patch p (ids in label order, as row f5 numbers them):
+ *   label[p]; box[4 p ..] = min_x, min_y, width, height of its frame in the view's pixels (one pixel of border, so min may be -1);
+ *   faces[face_ptr[p] .. face_ptr[p + 1]): its face list in upstream's order (the surviving candidate's faces, then the absorbed
+ *   lists); texcoords[6 e + 2 k ..]: corner k of list entry e in the patch's pixels;
+ *   pixels [pix_ptr[p], pix_ptr[p + 1]): the patch row-major, patches back to back: image[3 i + c] (float, interleaved RGB),
+ *   validity[i] in {0, 255}, blending[i] in {0, 64, 255}.
+ * params.max_pixels (0 = no cap): when the pixel total exceeds it the call fails with MVS_ERR_UNSUPPORTED before the pixel arrays
+ * are allocated; stats (patches, merged, listed_faces, pixels) is filled all the same.  MVS_ERR_LABELING / MVS_ERR_STATE as row f5.
+ * With out_on_device the arrays are device pointers owned by the context (valid until its next texture_patches call or its
+ * destruction), otherwise malloc'ed host copies (mvs_patch_set_free). */
+typedef struct mvs_patch_params {
+    uint64_t max_pixels;      /* refuse a result of more pixels than this (0: no cap) */
+    uint64_t reserved;
+} mvs_patch_params;
+void mvs_patch_default_params(mvs_patch_params* p);
+typedef struct mvs_patch_set {
+    uint32_t n_patches, n_listed;   /* n_listed = face_ptr[n_patches]: the labelled faces */
+    uint64_t n_pixels;              /* pix_ptr[n_patches] */
+    uint32_t* label;          /* [n_patches] */
+    int32_t* box;             /* [4 n_patches] */
+    uint32_t* face_ptr;       /* [n_patches + 1] */
+    uint32_t* faces;          /* [n_listed] */
+    float* texcoords;         /* [6 n_listed] */
+    uint64_t* pix_ptr;        /* [n_patches + 1] */
+    float* image;             /* [3 n_pixels] */
+    uint8_t* validity;        /* [n_pixels] */
+    uint8_t* blending;        /* [n_pixels] */
+} mvs_patch_set;
+typedef struct mvs_patch_stats {
+    uint64_t patches, merged;             /* as mvs_gsl_stats */
+    uint64_t listed_faces, degenerate_faces;   /* list entries; those adjust_colors skips (area < FLT_EPSILON) */
+    uint64_t pixels, valid_pixels, near_pixels;   /* all; validity 255; blending 64 */
+    float ms_tables, ms_lists, ms_mark, ms_resolve, ms_total;   /* device time: patch tables; geometry, lists and scans; mark; resolve */
+    float reserved;
+} mvs_patch_stats;
+mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device,
+                                   const uint32_t* labels, int labels_on_device, const float* corner_adjust, int adjust_on_device,
+                                   const mvs_patch_params* params, mvs_patch_set* out, int out_on_device, mvs_patch_stats* stats);
+void mvs_patch_set_free(mvs_patch_set* s);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

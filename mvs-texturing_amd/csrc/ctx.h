@@ -116,6 +116,20 @@ struct alignas(16) NodeDesc {
 static_assert(sizeof(NodeDesc) == 48, "NodeDesc must be 48 bytes");
 
 struct GslDev;   // row f5 (k_seam.hip)
+struct TexPatchDev;   // row f6 (k_texpatch.hip)
+
+// The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
+// build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
+// candidate that absorbed it (parent, NONE for a survivor), where its list starts in that one's list (off), the list length after the
+// merges (len), alive, the patch id of a survivor (pscan) and of the chain's root (cand_pid) with the list position of the
+// candidate's first face there (cand_pos); per face its candidate and place in it (fcand, fidx), its patch and list position (fpid,
+// fpos) and its corners' pixel coordinates in its view (pc).
+struct PatchTables {
+    DBuf<int4> box; DBuf<float2> pc;
+    DBuf<uint32_t> fcand, fidx, parent, off, len, alive, pscan, cand_pid, cand_pos, fpid, fpos, flags;
+    DBuf<unsigned long long> merged; DBuf<ViewParams> views;
+    uint32_t C = 0, n_patches = 0; uint64_t n_merged = 0;   // of the last build_patch_tables
+};
 
 }  // namespace mvs
 
@@ -221,7 +235,7 @@ struct mvs_ctx {
     mvs::DBuf<uint32_t> p_label_ptr, p_comp_ptr, p_comp_faces, p_parent, p_root, p_state, p_flag, p_pos, p_roots, p_roots2, p_rlab, p_rlab2, p_adj_ptr, p_adj, p_labels;
 
     // ---- row f5: global seam leveling (k_seam.hip): buffers allocated on first use ----
-    mvs::GslDev* gsl = nullptr;
+    mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr;
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -328,4 +342,12 @@ void exclusive_scan_u32(mvs_ctx* ctx, const uint32_t* in, uint32_t* out, size_t 
 uint64_t sum_u32(mvs_ctx* ctx, const uint32_t* in, size_t n);
 // frees the buffers of row f5 (k_seam.hip)
 void gsl_release(mvs_ctx* ctx);
+// frees the buffers of row f6 (k_texpatch.hip)
+void texpatch_release(mvs_ctx* ctx);
+// rows f5 / f6 (k_texpatch.hip): the views' parameters on the device and the checks on the caller's labels and faces -- throws MVS_ERR_LABELING
+// for a label above the number of views, MVS_ERR_INVALID for a vertex id >= n_verts; `who` starts the message
+void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, const char* who);
+// the candidates of every label (get_subgraphs), their boxes, the merge loop, patch ids, every face's patch and position: fills T and
+// T.C / n_patches / n_merged; throws MVS_ERR_LABELING when a labelled face leaves its view's image.  Needs patch_check_inputs first.
+void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const char* who);
 }  // namespace mvs

@@ -1,9 +1,10 @@
 // k_seam.hip -- row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp) with tone mapping `none`, together with the
-//   parts of generate_texture_patches it reads (candidate boxes and merges, generate_texture_patches.cpp:78-138 / :484-508; the vertex
-//   projections merge_vertex_projection_infos keeps, :40-65).  The definition (DESIGN.md section 4 "Global seam leveling", items
+//   parts of generate_texture_patches it reads (candidate boxes and merges, generate_texture_patches.cpp:78-138 / :484-508 -- the
+//   tables of build_patch_tables, k_texpatch.hip, which row f6 builds with the same functions; the vertex projections
+//   merge_vertex_projection_infos keeps, :40-65).  The definition (DESIGN.md section 4 "Global seam leveling", items
 //   1-9) is shared with the CPU model of the tests (tests/tools/seam_model.cpp): every output is bit-identical to it on any device.
 //   Structure: sorted (vertex, value) pairs for the vertex -> faces lists, the vertex rows and the rings; one thread per face
-//   (boxes), per label (the merge loop is sequential), per candidate (frame chains), per vertex (A rows), per A row (seam edges and
+//   (boxes), per label (the merge loop is sequential), per candidate (frame chains) -- those three in k_texpatch.hip --, per vertex (A rows), per A row (seam edges and
 //   the b sampler: each row's accumulation order is fixed), per x row (Lhs, Rhs).
 //   Solve: Jacobi-preconditioned CG on the three channels at once, each with its own alpha, beta and stop state; two launches per
 //   iteration (the SpMV forms p = z + beta p on the fly for every column it reads; the update forms x, r and the next partials),
@@ -17,7 +18,6 @@
 namespace mvs {
 
 mvs_status api_fail(mvs_status st, const std::string& msg);
-uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, uint32_t F, uint32_t n_labels);
 
 namespace {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
@@ -26,8 +26,8 @@ constexpr uint32_t RED_BLOCKS = 1024;       // level one of the reduction tree: 
 constexpr int GSL_GRAPH_ITERS = 16;         // CG iterations per graph replay (even: the ping-pong buffers alternate by iteration)
 // partial-sum slots of RED_BLOCKS floats: [0, 3) p.Ap per channel; 3 + 6 q + {0: r.r, 3: r.z} + c for the parity q; [15, 18) sums of x
 constexpr uint32_t SLOT_RR = 3, SLOT_MEAN = 15, SLOTS = 18;
-enum { C_MERGED = 0, C_SEAM, C_SAMPLES, C_GAMMA2, C_LOWER, C_N };                  // 64-bit counters
-enum { F_LABEL = 0, F_VERTEX, F_BOX, F_DONE, F_N };                                // flag words
+enum { C_SEAM = 0, C_SAMPLES, C_GAMMA2, C_LOWER, C_N };                            // 64-bit counters
+enum { F_DONE = 0, F_N };                                                          // flag words
 }  // namespace
 
 struct GslChan { float rhs2, thr, rz, err; uint32_t active, iters, pad0, pad1; };
@@ -37,11 +37,11 @@ struct GslState { GslChan ch[3]; uint32_t k, pad[3]; };
 struct GslDev {
     DBuf<unsigned long long> keys, keys2; DBuf<uint32_t> flag, pos, cnt;
     DBuf<uint32_t> vf_ptr, vf, x_ptr, x_label, x_vert, ring_ptr, ring;
-    DBuf<int4> box; DBuf<float2> pc; DBuf<uint32_t> fcand, fidx, parent, off, len, alive, pscan, cand_pid, cand_pos, fpid, fpos;
+    PatchTables pt;
     DBuf<uint32_t> a_ptr, a_col, a_vert; DBuf<float> b;
     DBuf<uint32_t> lhs_ptr, lhs_col; DBuf<float> lhs_val, invdiag, rhs;
     DBuf<float> x, r, p, ap, xadj, corner, part;
-    DBuf<GslState> st; DBuf<unsigned long long> c64; DBuf<uint32_t> flags, labels, adj_ptr, adj; DBuf<ViewParams> views;
+    DBuf<GslState> st; DBuf<unsigned long long> c64; DBuf<uint32_t> flags, labels, adj_ptr, adj;
     hipStream_t cap = nullptr;
     uint32_t NV = 0, F = 0, XR = 0, AR = 0; uint64_t NNZ = 0; bool valid = false;   // shapes of the last successful call
     ~GslDev() { if (cap) (void)hipStreamDestroy(cap); }
@@ -66,14 +66,7 @@ struct GslView {
     const ViewParams* views;
 };
 
-// ---- 1. checks, (vertex, value) pairs -> CSR ----
-__global__ void gsl_check_kernel(const uint32_t* __restrict__ faces, const uint32_t* __restrict__ labels, uint32_t F, uint32_t NV, uint32_t n_views,
-                                 uint32_t* __restrict__ flags) {
-    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    if (labels[f] > n_views) flags[F_LABEL] = 1u;   // rare: plain racy store of the same value
-    if (faces[3 * f] >= NV || faces[3 * f + 1] >= NV || faces[3 * f + 2] >= NV) flags[F_VERTEX] = 1u;
-}
+// ---- 1. (vertex, value) pairs -> CSR (the checks on labels and faces: patch_check_inputs, k_texpatch.hip) ----
 // what 0: (vertex, face), a repeated corner once; 1: (vertex, label) of the labelled faces; 2: (vertex, other corner) -- keys row << 32 | value
 __global__ void gsl_key_kernel(const uint32_t* __restrict__ faces, const uint32_t* __restrict__ labels, uint32_t F, int what, unsigned long long* __restrict__ keys) {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,79 +99,7 @@ __global__ void gsl_unique_compact_kernel(const unsigned long long* __restrict__
     atomicAdd(cnt + row, 1u);
 }
 
-// ---- 3. patches ----
-__global__ void gsl_box_init_kernel(int4* __restrict__ box, uint32_t C) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) box[c] = make_int4(INT_MAX, INT_MAX, INT_MIN, INT_MIN);
-}
-// one thread per position of the component lists: the face's candidate, its place in it, its corners' pixel coordinates, the box
-__global__ void gsl_face_box_kernel(const uint32_t* __restrict__ comp_ptr, const uint32_t* __restrict__ comp_faces, uint32_t C, uint32_t F,
-                                    const uint32_t* __restrict__ labels, const uint32_t* __restrict__ faces, const float* __restrict__ verts,
-                                    const ViewParams* __restrict__ views, int4* __restrict__ box, float2* __restrict__ pc, uint32_t* __restrict__ fcand,
-                                    uint32_t* __restrict__ fidx, uint32_t* __restrict__ flags) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= F) return;
-    uint32_t lo = 0, hi = C;   // the last component starting at or before p
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (comp_ptr[mid] <= p) lo = mid; else hi = mid; }
-    const uint32_t c = lo, f = comp_faces[p];
-    fcand[f] = c; fidx[f] = p - comp_ptr[c];
-    const uint32_t L = labels[f];
-    if (!L) return;
-    const ViewParams& vw = views[L - 1];
-    int mnx = INT_MAX, mny = INT_MAX, mxx = INT_MIN, mxy = INT_MIN;
-    bool ok = true;
-    for (int k = 0; k < 3; ++k) {
-        const uint32_t v = faces[3 * f + k];
-        const V2 q = pixel_coords(vw, V3{verts[3 * (size_t)v], verts[3 * (size_t)v + 1], verts[3 * (size_t)v + 2]});
-        pc[3 * (size_t)f + k] = make_float2(q.x, q.y);
-        const float fx = floorf(q.x), fy = floorf(q.y), cx = ceilf(q.x), cy = ceilf(q.y);
-        if (!(fx >= 0.0f && fy >= 0.0f && cx <= (float)(vw.width - 1) && cy <= (float)(vw.height - 1))) { ok = false; continue; }
-        mnx = min(mnx, (int)fx); mny = min(mny, (int)fy); mxx = max(mxx, (int)cx); mxy = max(mxy, (int)cy);
-    }
-    if (!ok) { flags[F_BOX] = 1u; return; }
-    atomicMin(&box[c].x, mnx); atomicMin(&box[c].y, mny); atomicMax(&box[c].z, mxx); atomicMax(&box[c].w, mxy);
-}
-// one thread per label: upstream's merge loop (generate_texture_patches.cpp:484-508) over the label's candidates in order; the frame
-// gets its border (min - 1) first.  parent / off: the candidate that absorbed this one and where its list starts in that one's list.
-__global__ void gsl_merge_kernel(const uint32_t* __restrict__ label_ptr, uint32_t n_labels, const uint32_t* __restrict__ comp_ptr, int4* __restrict__ box,
-                                 uint32_t* __restrict__ parent, uint32_t* __restrict__ off, uint32_t* __restrict__ len, uint32_t* __restrict__ alive,
-                                 unsigned long long* __restrict__ c64) {
-    const uint32_t L = blockIdx.x * blockDim.x + threadIdx.x;
-    if (L >= n_labels) return;
-    const uint32_t c0 = label_ptr[L], c1 = label_ptr[L + 1];
-    for (uint32_t c = c0; c < c1; ++c) {
-        parent[c] = NONE; off[c] = 0; len[c] = comp_ptr[c + 1] - comp_ptr[c]; alive[c] = L ? 1u : 0u;
-        if (L) { int4 b = box[c]; b.x -= 1; b.y -= 1; box[c] = b; }
-    }
-    if (!L) return;
-    unsigned long long merged = 0;
-    for (uint32_t i = c0; i < c1; ++i) {
-        if (!alive[i]) continue;
-        const int4 a = box[i];
-        for (uint32_t j = c0; j < c1; ++j) {
-            if (j == i || !alive[j]) continue;
-            const int4 s = box[j];
-            if (s.x >= a.x && s.z <= a.z && s.y >= a.y && s.w <= a.w) { parent[j] = i; off[j] = len[i]; len[i] += len[j]; alive[j] = 0u; ++merged; }
-        }
-    }
-    if (merged) atomicAdd(c64 + C_MERGED, merged);
-}
-__global__ void gsl_cand_final_kernel(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ off, const uint32_t* __restrict__ pscan,
-                                      uint32_t C, uint32_t* __restrict__ cand_pid, uint32_t* __restrict__ cand_pos) {
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    uint32_t r = c, p0 = 0;
-    while (parent[r] != NONE) { p0 += off[r]; r = parent[r]; }
-    cand_pid[c] = pscan[r]; cand_pos[c] = p0;
-}
-__global__ void gsl_face_patch_kernel(const uint32_t* __restrict__ labels, const uint32_t* __restrict__ fcand, const uint32_t* __restrict__ fidx,
-                                      const uint32_t* __restrict__ cand_pid, const uint32_t* __restrict__ cand_pos, uint32_t F,
-                                      uint32_t* __restrict__ fpid, uint32_t* __restrict__ fpos) {
-    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    const uint32_t c = fcand[f];
-    fpid[f] = labels[f] ? cand_pid[c] : NONE; fpos[f] = cand_pos[c] + fidx[f];
-}
+// ---- 3. patches: build_patch_tables (k_texpatch.hip), shared with row f6 ----
 
 // ---- 4.-6. seam edges, projections, samples ----
 __device__ inline bool in_list(const uint32_t* a, uint32_t b0, uint32_t b1, uint32_t x) {
@@ -622,7 +543,7 @@ uint32_t pairs_csr(mvs_ctx* ctx, GslDev& G, uint32_t n, uint32_t rows, DBuf<uint
 void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const mvs_gsl_params& P,
              mvs_gsl_stats& S) {
     hipStream_t s = ctx->stream;
-    const uint32_t F = ctx->n_faces, NV = ctx->n_verts, V = ctx->n_views;
+    const uint32_t F = ctx->n_faces, NV = ctx->n_verts;
     G.valid = false;
     hipEvent_t ev[6];
     for (auto& e : ev) MVS_HIP(hipEventCreate(&e));
@@ -631,15 +552,8 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     G.flags.ensure(F_N); G.c64.ensure(C_N);
     MVS_HIP(hipMemsetAsync(G.flags.p, 0, F_N * sizeof(uint32_t), s));
     MVS_HIP(hipMemsetAsync(G.c64.p, 0, C_N * sizeof(unsigned long long), s));
-    G.views.ensure(V);
-    MVS_HIP(hipMemcpyAsync(G.views.p, ctx->h_views.data(), V * sizeof(ViewParams), hipMemcpyHostToDevice, s));
     // 1.-2. inputs checked; vertex -> faces, vertex rows, rings
-    hipLaunchKernelGGL(gsl_check_kernel, dim3(grid(F)), dim3(256), 0, s, ctx->d_faces, d_labels, F, NV, V, G.flags.p); MVS_LAUNCH_CHECK();
-    uint32_t fl[F_N];
-    MVS_HIP(hipMemcpyAsync(fl, G.flags.p, sizeof(fl), hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipStreamSynchronize(s));
-    if (fl[F_LABEL]) throw StatusError(MVS_ERR_LABELING, "global_seam_leveling: a label is greater than the number of views");
-    if (fl[F_VERTEX]) throw StatusError(MVS_ERR_INVALID, "global_seam_leveling: a face refers to a vertex >= n_verts");
+    patch_check_inputs(ctx, G.pt, d_labels, "global_seam_leveling");
     if ((uint64_t)F * 6 >= 0xFFFFFFFFull) throw StatusError(MVS_ERR_INVALID, "global_seam_leveling: too many faces");
     G.keys.ensure(6 * (size_t)F + 1);
     hipLaunchKernelGGL(gsl_key_kernel, dim3(grid(F)), dim3(256), 0, s, ctx->d_faces, d_labels, F, 0, G.keys.p); MVS_LAUNCH_CHECK();
@@ -650,28 +564,13 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     pairs_csr(ctx, G, 6 * F, NV, G.ring_ptr, G.ring, nullptr);
     MVS_HIP(hipEventRecord(ev[1], s));
     // 3. candidates (components of every label), boxes, merges, patch ids
-    const uint32_t C = get_subgraphs(ctx, d_adj_ptr, d_adj, d_labels, F, V + 1);
-    const uint32_t* comp_ptr = ctx->p_comp_ptr.p; const uint32_t* comp_faces = ctx->p_comp_faces.p; const uint32_t* label_ptr = ctx->p_label_ptr.p;
-    G.box.ensure((size_t)C + 1); G.pc.ensure(3 * (size_t)F + 1); G.fcand.ensure((size_t)F + 1); G.fidx.ensure((size_t)F + 1);
-    G.parent.ensure((size_t)C + 1); G.off.ensure((size_t)C + 1); G.len.ensure((size_t)C + 1); G.alive.ensure((size_t)C + 1);
-    G.pscan.ensure((size_t)C + 2); G.cand_pid.ensure((size_t)C + 1); G.cand_pos.ensure((size_t)C + 1); G.fpid.ensure((size_t)F + 1); G.fpos.ensure((size_t)F + 1);
-    hipLaunchKernelGGL(gsl_box_init_kernel, dim3(grid(C)), dim3(256), 0, s, G.box.p, C); MVS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gsl_face_box_kernel, dim3(grid(F)), dim3(256), 0, s, comp_ptr, comp_faces, C, F, d_labels, ctx->d_faces, ctx->d_verts,
-                       (const ViewParams*)G.views.p, G.box.p, G.pc.p, G.fcand.p, G.fidx.p, G.flags.p);
-    MVS_LAUNCH_CHECK();
-    if (read_u32(ctx, G.flags.p + F_BOX)) throw StatusError(MVS_ERR_LABELING, "global_seam_leveling: a labelled face leaves its view's image");
-    hipLaunchKernelGGL(gsl_merge_kernel, dim3(grid(V + 1)), dim3(256), 0, s, label_ptr, V + 1, comp_ptr, G.box.p, G.parent.p, G.off.p, G.len.p,
-                       G.alive.p, G.c64.p);
-    MVS_LAUNCH_CHECK();
-    exclusive_scan_u32(ctx, G.alive.p, G.pscan.p, C, G.pscan.p + C);
-    const uint32_t n_patches = read_u32(ctx, G.pscan.p + C);
-    hipLaunchKernelGGL(gsl_cand_final_kernel, dim3(grid(C)), dim3(256), 0, s, G.parent.p, G.off.p, G.pscan.p, C, G.cand_pid.p, G.cand_pos.p); MVS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gsl_face_patch_kernel, dim3(grid(F)), dim3(256), 0, s, d_labels, G.fcand.p, G.fidx.p, G.cand_pid.p, G.cand_pos.p, F, G.fpid.p, G.fpos.p);
-    MVS_LAUNCH_CHECK();
+    PatchTables& T = G.pt;
+    build_patch_tables(ctx, T, d_adj_ptr, d_adj, d_labels, "global_seam_leveling");
+    const uint32_t n_patches = T.n_patches;
     MVS_HIP(hipEventRecord(ev[2], s));
     // 4.-7. A rows, b, Lhs, Rhs
     const GslView gv{ctx->d_verts, ctx->d_faces, d_labels, G.vf_ptr.p, G.vf.p, G.x_ptr.p, G.x_label.p, G.ring_ptr.p, G.ring.p,
-                     G.box.p, G.pc.p, G.fcand.p, G.parent.p, G.fpid.p, G.fpos.p, G.views.p};
+                     T.box.p, T.pc.p, T.fcand.p, T.parent.p, T.fpid.p, T.fpos.p, T.views.p};
     G.cnt.ensure((size_t)std::max(NV, XR) + 1); G.a_ptr.ensure((size_t)NV + 2);
     hipLaunchKernelGGL(gsl_a_rows_kernel, dim3(grid(NV)), dim3(256), 0, s, gv, NV, 0, G.cnt.p, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     MVS_LAUNCH_CHECK();
@@ -739,7 +638,7 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     MVS_HIP(hipMemcpyAsync(c64, G.c64.p, sizeof(c64), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipStreamSynchronize(s));
     S = mvs_gsl_stats{};
-    S.patches = n_patches; S.merged = c64[C_MERGED]; S.x_rows = XR; S.a_rows = AR; S.gamma_rows = c64[C_GAMMA2] / 2;
+    S.patches = n_patches; S.merged = T.n_merged; S.x_rows = XR; S.a_rows = AR; S.gamma_rows = c64[C_GAMMA2] / 2;
     S.lhs_nnz_lower = c64[C_LOWER]; S.seam_edges = c64[C_SEAM]; S.samples = c64[C_SAMPLES];
     for (int c = 0; c < 3; ++c) { S.iterations[c] = XR ? fin.ch[c].iters : 0u; S.error[c] = XR ? fin.ch[c].err : 0.0f; }
     float ms[5];

@@ -94,6 +94,23 @@ class GslSystem(C.Structure):
                 ("lhs_val", C.c_void_p), ("rhs", C.c_void_p), ("a_col", C.c_void_p), ("b", C.c_void_p), ("x_raw", C.c_void_p)]
 
 
+class PatchParams(C.Structure):
+    _fields_ = [("max_pixels", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class PatchSet(C.Structure):
+    _fields_ = [("n_patches", C.c_uint32), ("n_listed", C.c_uint32), ("n_pixels", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("label", "box", "face_ptr", "faces", "texcoords", "pix_ptr", "image", "validity", "blending")]
+
+
+PATCH_COUNTS = ("patches", "merged", "listed_faces", "degenerate_faces", "pixels", "valid_pixels", "near_pixels")
+PATCH_MS = ("ms_tables", "ms_lists", "ms_mark", "ms_resolve", "ms_total")
+
+
+class PatchStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in PATCH_COUNTS] + [(k, C.c_float) for k in PATCH_MS] + [("reserved", C.c_float)]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -189,6 +206,8 @@ def load_library():
         "mvs_gsl_default_params": [C.POINTER(GslParams)], "mvs_gsl_result_free": [C.POINTER(GslResult)], "mvs_gsl_system_free": [C.POINTER(GslSystem)],
         "mvs_ctx_global_seam_leveling": [vp, vp, vp, i32, vp, i32, C.POINTER(GslParams), C.POINTER(GslResult), i32, C.POINTER(GslStats)],
         "mvs_ctx_gsl_system": [vp, C.POINTER(GslSystem)],
+        "mvs_patch_default_params": [C.POINTER(PatchParams)], "mvs_patch_set_free": [C.POINTER(PatchSet)],
+        "mvs_ctx_texture_patches": [vp, vp, vp, i32, vp, i32, vp, i32, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -213,7 +232,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -476,6 +495,42 @@ class Context:
         self.L.mvs_gsl_result_free(C.byref(res))
         return out, stats
 
+    def texture_patches(self, adj_ptr, adj, labels, corner_adjust=None, params=None, on_device=False):
+        """Row f6: the texture patches of the labelled faces with TexturePatch::adjust_colors applied (DESIGN.md section 4 "Texture
+        patches"), from the caller's labels and the per-corner adjustments of global_seam_leveling (corner_adjust (F, 3, 3) or its
+        device array; None = zeros: masks only).  Returns (arrays, stats): label (P,), box (P, 4) = min_x, min_y, width, height,
+        face_ptr (P + 1,), faces, texcoords (n_listed, 3, 2), pix_ptr (P + 1,) uint64, image (n_pixels, 3), validity, blending
+        (n_pixels,) -- patch_view(arrays, i) cuts patch i out; with on_device=True DevArrays owned by the context (valid until the next
+        texture_patches call).  A pixel total above params.max_pixels raises MvsError (status 7) with `.stats` holding the counts."""
+        pa, d0 = _ptr(adj_ptr); pb, d1 = _ptr(adj); pl, dl = _ptr(labels)
+        assert d0 == d1
+        if corner_adjust is not None and not (_is_torch(corner_adjust) or isinstance(corner_adjust, DevArray)):
+            corner_adjust = np.ascontiguousarray(corner_adjust, np.float32)
+        pc, dc = _ptr(corner_adjust)
+        p = params or default_patch_params()
+        res, st = PatchSet(), PatchStats()
+        self._keep["patches"] = (adj_ptr, adj, labels, corner_adjust)
+        rc = self.L.mvs_ctx_texture_patches(self.h, pa, pb, d0, pl, dl, pc, dc, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        stats = {k: int(getattr(st, k)) for k in PATCH_COUNTS}
+        stats.update({k: float(getattr(st, k)) for k in PATCH_MS})
+        if rc != 0:
+            try:
+                _check(self.L, rc)
+            except MvsError as e:
+                e.stats = stats
+                raise
+        P, NL, NP = int(res.n_patches), int(res.n_listed), int(res.n_pixels)
+        shapes = dict(label=(P, np.uint32), box=(4 * P, np.int32), face_ptr=(P + 1, np.uint32), faces=(NL, np.uint32), texcoords=(6 * NL, np.float32),
+                      pix_ptr=(P + 1, np.uint64), image=(3 * NP, np.float32), validity=(NP, np.uint8), blending=(NP, np.uint8))
+        if on_device:
+            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
+        out = {}
+        for k, (n, dt) in shapes.items():
+            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
+        self.L.mvs_patch_set_free(C.byref(res))
+        out["box"] = out["box"].reshape(P, 4); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2); out["image"] = out["image"].reshape(NP, 3)
+        return out, stats
+
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
         a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
@@ -502,6 +557,37 @@ def default_gsl_params(**kw):
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_patch_params(**kw):
+    """mvs_patch_default_params (max_pixels 0 = no cap) with overrides"""
+    p = PatchParams()
+    load_library().mvs_patch_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def patch_view(arrays, i):
+    """patch i of Context.texture_patches' host arrays: (image (h, w, 3), validity (h, w), blending (h, w)) as views of the packed arrays"""
+    w, h = int(arrays["box"][i, 2]), int(arrays["box"][i, 3])
+    a, b = int(arrays["pix_ptr"][i]), int(arrays["pix_ptr"][i + 1])
+    return arrays["image"][a:b].reshape(h, w, 3), arrays["validity"][a:b].reshape(h, w), arrays["blending"][a:b].reshape(h, w)
+
+
+def texture_patches(scene, labels, corner_adjust=None, ctx=None):
+    """the texture patches (generate_texture_patches for the labelled faces + adjust_colors, texrecon.cpp:160-184) of a synth.Scene-like
+    object and its labels: returns (arrays, stats) of Context.texture_patches."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
+        ctx.set_views(scene.cams, scene.images)
+        return ctx.texture_patches(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
+                                   np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust)
+    finally:
+        if own:
+            ctx.close()
 
 
 def global_seam_leveling(scene, labels, params=None, ctx=None):
