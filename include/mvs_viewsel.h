@@ -496,6 +496,51 @@ mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const 
                                    const mvs_patch_params* params, mvs_patch_set* out, int out_on_device, mvs_patch_stats* stats);
 void mvs_patch_set_free(mvs_patch_set* s);
 
+/* Row f7: tex::local_seam_leveling (local_seam_leveling.cpp:105-204) on a patch set as mvs_patch_set describes it, tone mapping
+ * `none`, labelled faces only: seam-edge and seam-vertex colours (the mean over the patches that meet there) are written into every
+ * patch, prepare_blending_mask(strip_width) fixes everything but a strip along the patch border, and the strip is re-solved as a
+ * Poisson problem that keeps the original image's Laplacian (poisson_blend with alpha 1); pixels of mask 64 lose their validity.
+ * The definition is DESIGN.md section 4 "Local seam leveling"; upstream's direct solve is replaced by conjugate gradients per patch
+ * (one fixed reduction tree per unknown count: every output is the same bits on any device, in every run, whatever else is in the
+ * set).  Needs the mesh, not the views.  `patches` may be the device output of mvs_ctx_texture_patches (patches_on_device: ALL its
+ * arrays are device pointers) or host arrays; it is not modified.  Output: image [3 n_pixels], validity [n_pixels] and the PREPARED
+ * blending mask [n_pixels] (0 inner / outside, 64 and 128 fixed, 255 strip), packed as the input (pix_ptr); with out_on_device
+ * device pointers owned by the context (valid until its next local_seam_leveling call), otherwise malloc'ed (mvs_lsl_result_free).
+ * params.max_iterations = 0 returns the state before the solve.  MVS_ERR_LABELING when a listed face's label differs from its
+ * patch's or a face id is out of range; MVS_ERR_STATE without a mesh; MVS_ERR_UNSUPPORTED for a patch of label 0, texture
+ * coordinates that are not finite or beyond 2^20, or totals that would wrap 32 bits (pixels, samples, keys). */
+typedef struct mvs_lsl_params {
+    float tolerance;          /* CG stops at sqrt(|r|^2 / |b|^2) < tolerance, per patch and channel (1e-6) */
+    uint32_t max_iterations;  /* per patch and channel (700); 0: no solve */
+    uint32_t strip_width;     /* prepare_blending_mask's argument (20; at most 250) */
+    uint32_t lds_bytes;       /* a patch whose solver image (12 B per pixel + 16 B per unknown) exceeds this takes the global-memory
+                                 path (147456 = the default and the most; 0: every patch) -- same arithmetic, same bits */
+} mvs_lsl_params;
+void mvs_lsl_default_params(mvs_lsl_params* p);
+typedef struct mvs_lsl_result {
+    uint32_t n_patches, reserved;
+    uint64_t n_pixels;
+    float* image;             /* [3 n_pixels] */
+    uint8_t* validity;        /* [n_pixels] */
+    uint8_t* blending;        /* [n_pixels] */
+} mvs_lsl_result;
+typedef struct mvs_lsl_stats {
+    uint64_t seam_edges, skipped_pairs;          /* seam edges listed; adjacent pairs of different labels that do not share exactly two vertices */
+    uint64_t vertex_infos, edge_projections;     /* (vertex, patch) infos; (seam edge, patch) projections = lines */
+    uint64_t colour_samples, invalid_samples;    /* bilinear samples taken (edges and vertices); those upstream's valid_pixel would refuse */
+    uint64_t vertex_writes, line_writes;         /* pixel writes attempted by vertices / by lines */
+    uint64_t written_pixels, outside_frame, invalid_writes;   /* distinct pixels written; writes dropped outside the frame; writes onto validity 0 */
+    uint64_t strip_pixels, fixed_pixels, demoted;             /* unknowns; pixels of mask 64 / 128; 255s without four usable neighbours, held fixed */
+    uint64_t patches_lds, patches_global, pixels_global;      /* patches solved in LDS / in global memory (patches without unknowns in neither); pixels of the latter */
+    uint64_t iterations_total, hit_max_iterations;            /* over patches and channels; patches with a channel that ran into max_iterations */
+    uint32_t iterations_max; float error_max;                 /* over patches and channels; error = sqrt(|r|^2 / |b|^2) */
+    float ms_topology, ms_colours, ms_writes, ms_mask, ms_solve, ms_total;   /* device time per phase */
+} mvs_lsl_stats;
+mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device,
+                                       const uint32_t* labels, int labels_on_device, const mvs_patch_set* patches, int patches_on_device,
+                                       const mvs_lsl_params* params, mvs_lsl_result* out, int out_on_device, mvs_lsl_stats* stats);
+void mvs_lsl_result_free(mvs_lsl_result* r);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

@@ -111,6 +111,25 @@ class PatchStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PATCH_COUNTS] + [(k, C.c_float) for k in PATCH_MS] + [("reserved", C.c_float)]
 
 
+class LslParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("max_iterations", C.c_uint32), ("strip_width", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
+class LslResult(C.Structure):
+    _fields_ = [("n_patches", C.c_uint32), ("reserved", C.c_uint32), ("n_pixels", C.c_uint64), ("image", C.c_void_p), ("validity", C.c_void_p),
+                ("blending", C.c_void_p)]
+
+
+LSL_COUNTS = ("seam_edges", "skipped_pairs", "vertex_infos", "edge_projections", "colour_samples", "invalid_samples", "vertex_writes", "line_writes",
+              "written_pixels", "outside_frame", "invalid_writes", "strip_pixels", "fixed_pixels", "demoted", "patches_lds", "patches_global",
+              "pixels_global", "iterations_total", "hit_max_iterations")
+LSL_MS = ("ms_topology", "ms_colours", "ms_writes", "ms_mask", "ms_solve", "ms_total")
+
+
+class LslStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in LSL_COUNTS] + [("iterations_max", C.c_uint32), ("error_max", C.c_float)] + [(k, C.c_float) for k in LSL_MS]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -208,6 +227,8 @@ def load_library():
         "mvs_ctx_gsl_system": [vp, C.POINTER(GslSystem)],
         "mvs_patch_default_params": [C.POINTER(PatchParams)], "mvs_patch_set_free": [C.POINTER(PatchSet)],
         "mvs_ctx_texture_patches": [vp, vp, vp, i32, vp, i32, vp, i32, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
+        "mvs_lsl_default_params": [C.POINTER(LslParams)], "mvs_lsl_result_free": [C.POINTER(LslResult)],
+        "mvs_ctx_local_seam_leveling": [vp, vp, vp, i32, vp, i32, C.POINTER(PatchSet), i32, C.POINTER(LslParams), C.POINTER(LslResult), i32, C.POINTER(LslStats)],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -232,7 +253,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -531,6 +552,53 @@ class Context:
         out["box"] = out["box"].reshape(P, 4); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2); out["image"] = out["image"].reshape(NP, 3)
         return out, stats
 
+    def local_seam_leveling(self, adj_ptr, adj, labels, patches, params=None, on_device=False):
+        """Row f7: tex::local_seam_leveling on a patch set (DESIGN.md section 4 "Local seam leveling"): `patches` is the dict of
+        texture_patches -- all host arrays or all DevArrays / CUDA tensors (its on_device=True output can be passed straight in) --
+        and is not modified.  Returns ({image (n_pixels, 3), validity, blending (n_pixels,)}, stats): the blended image, validity
+        after the blend and the PREPARED blending mask, packed as the input, so patch_view works on the result merged over the
+        input dict; with on_device=True DevArrays owned by the context (valid until the next local_seam_leveling call).
+        params: default_lsl_params(...); max_iterations=0 returns the state before the solve."""
+        pa, d0 = _ptr(adj_ptr); pb, d1 = _ptr(adj); pl, dl = _ptr(labels)
+        assert d0 == d1
+        dts = dict(label=np.uint32, box=np.int32, face_ptr=np.uint32, faces=np.uint32, texcoords=np.float32, pix_ptr=np.uint64, image=np.float32,
+                   validity=np.uint8, blending=np.uint8)
+        dev = [_is_torch(patches[k]) or isinstance(patches[k], DevArray) for k in dts]
+        assert all(dev) or not any(dev), "the patch set must be all host or all device arrays"
+        held = {k: patches[k] if dev[0] else np.ascontiguousarray(patches[k], dts[k]).reshape(-1) for k in dts}
+        ps = PatchSet()
+        if dev[0]:
+            P = int(held["label"].shape[0]); ps.n_listed = int(held["faces"].shape[0]); ps.n_pixels = int(held["validity"].shape[0])
+        else:
+            P = held["label"].size; ps.n_listed = held["faces"].size; ps.n_pixels = held["validity"].size
+        ps.n_patches = P
+        for k in dts:
+            setattr(ps, k, _ptr(held[k])[0] if (dev[0] or held[k].size) else None)
+        p = params or default_lsl_params()
+        res, st = LslResult(), LslStats()
+        self._keep["lsl"] = (adj_ptr, adj, labels, held)
+        rc = self.L.mvs_ctx_local_seam_leveling(self.h, pa, pb, d0, pl, dl, C.byref(ps), 1 if dev[0] else 0, C.byref(p), C.byref(res),
+                                                1 if on_device else 0, C.byref(st))
+        stats = {k: int(getattr(st, k)) for k in LSL_COUNTS + ("iterations_max",)}
+        stats["error_max"] = float(st.error_max)
+        stats.update({k: float(getattr(st, k)) for k in LSL_MS})
+        if rc != 0:
+            try:
+                _check(self.L, rc)
+            except MvsError as e:
+                e.stats = stats
+                raise
+        NP = int(res.n_pixels)
+        shapes = dict(image=(3 * NP, np.float32), validity=(NP, np.uint8), blending=(NP, np.uint8))
+        if on_device:
+            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
+        out = {}
+        for k, (n, dt) in shapes.items():
+            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
+        self.L.mvs_lsl_result_free(C.byref(res))
+        out["image"] = out["image"].reshape(NP, 3)
+        return out, stats
+
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
         a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
@@ -568,6 +636,15 @@ def default_patch_params(**kw):
     return p
 
 
+def default_lsl_params(**kw):
+    """mvs_lsl_default_params (tolerance 1e-6, max_iterations 700, strip_width 20, lds_bytes 147456) with overrides"""
+    p = LslParams()
+    load_library().mvs_lsl_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 def patch_view(arrays, i):
     """patch i of Context.texture_patches' host arrays: (image (h, w, 3), validity (h, w), blending (h, w)) as views of the packed arrays"""
     w, h = int(arrays["box"][i, 2]), int(arrays["box"][i, 3])
@@ -585,6 +662,28 @@ def texture_patches(scene, labels, corner_adjust=None, ctx=None):
         ctx.set_views(scene.cams, scene.images)
         return ctx.texture_patches(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
                                    np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust)
+    finally:
+        if own:
+            ctx.close()
+
+
+def local_seam_leveling(scene, labels, params=None, ctx=None):
+    """texrecon.cpp:169-189 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with
+    its adjustments (row f6) and local seam leveling (row f7), the patches staying on the device in between.  Returns (arrays, stats):
+    the patch set of Context.texture_patches with image, validity and blending replaced by row f7's, and row f7's stats."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
+        ctx.set_views(scene.cams, scene.images)
+        a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        gsl, _ = ctx.global_seam_leveling(a, b, lab, on_device=True)
+        dev, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        out, stats = ctx.local_seam_leveling(a, b, lab, dev, params)
+        host, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"])
+        host.update(out)
+        return host, stats
     finally:
         if own:
             ctx.close()
