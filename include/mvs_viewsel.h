@@ -291,6 +291,7 @@ mvs_status mvs_ctx_synchronize(mvs_ctx* ctx);
  *     "mrf_xcd"               0/1, default 1: XCD-aware block order of the sweep kernels
  *     "mrf_blocks_per_cu"     default 0 = at most as many blocks per fast sweep launch as are resident; n > 0: at most 256 n
  *     "mrf_force_generic"     0/1, default 0: test hook, every node takes the generic sweep kernel
+ *     "mrf_force_lists"       0/1, default 0: test hook, the solver's set-up works from the neighbours' view lists instead of view-set bitmaps
  *   (the sharded sweep loop's transport is no option: the communicator decides it, see mvs_shard_transport_info) */
 mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value);
 

@@ -51,6 +51,11 @@ mvs_status mvs_ctx_mrf_setup_marked(mvs_ctx* ctx, const uint32_t* adj_ptr, const
 mvs_status mvs_ctx_mrf_sweep_phase_part(mvs_ctx* ctx, uint32_t phase, uint32_t node_begin, uint32_t node_end, int part);
 /* all phases in turn over nodes [node_begin, node_end) (no exchange in between: unsharded use) */
 mvs_status mvs_ctx_mrf_sweep(mvs_ctx* ctx, uint32_t node_begin, uint32_t node_end);
+/* what the last set-up built, for tests that compare two builds or two routes of it byte for byte: which = 0 one 64-bit word, 1 = the
+ * set-up worked from view-set bitmaps, 0 = from the view lists; 1 the fast nodes' records (32-bit words, the zero words in front included);
+ * 2 their descriptors (48 bytes each, schedule order); 3 the identical-lists flag of every directed edge (bytes, adjacency order).
+ * *n_bytes = size of the table; out_host == null: the size only */
+mvs_status mvs_ctx_mrf_setup_tables(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 /* message layout for the halo planner: in_off_host[e] = first message element of the run of directed edge e
  * (adjacency-list order, e < adj_ptr[n_faces]); runs are laid out in (colour, face id) node order */
 mvs_status mvs_ctx_mrf_layout(mvs_ctx* ctx, uint32_t* in_off_host, uint64_t n_edges);

@@ -268,6 +268,10 @@ struct mvs_ctx {
     const uint32_t* m_colour_in = nullptr;   // colours of all nodes kept by a sharded caller (null: mrf_setup colours the graph)
     const uint8_t* m_bnd = nullptr;   // per node: 1 = boundary node of a sharded caller (own node with an edge into another rank's part) -> zone 0 of the schedule (k_mrf.hip); null: no marks
     int mrf_force_generic = 0;   // test hook: every node takes the generic sweep kernel
+    // view-set bitmaps of the active table, F x ceil(csr_views / 64) words, rebuilt by every mrf_setup (k_mrf.hip mrf_bitmap_kernel); m_bitmaps:
+    // the last set-up took the bitmap route (not: more than 1024 views, a column that is not strictly ascending, the hook below)
+    mvs::DBuf<unsigned long long> m_bits; bool m_bitmaps = false;
+    int mrf_force_lists = 0;     // test hook: the set-up compares and searches the neighbours' view lists at any number of views
     uint32_t m_range_nb = 0, m_range_ne = 0; std::vector<uint32_t> m_range_q;   // cached own share of every sub-class
     uint32_t m_sweep_no = 0;   // sweeps started since mrf_setup (1-based inside a sweep): sweeps 1, 5, 9, ... are damped
     mvs_mrf_params m_params{};
@@ -330,6 +334,7 @@ void wait_report(mvs_ctx* ctx, uint32_t seq_slot, uint32_t seq);
 // ICM polish rounds until one moves nothing or max_rounds ran (k_mrf.hip): round(k) queues round k, which leaves its "moved" count in
 // the device word d_moved.  Returns the index of the round that moved nothing (max_rounds if none did) -- the oracle's loop counter.
 int icm_rounds(mvs_ctx* ctx, int max_rounds, const uint32_t* d_moved, const std::function<void(int)>& round);
+constexpr uint32_t MRF_REC_BASE = 256;   // the first record starts at this word of m_rec (k_mrf.hip REC_BASE)
 // damped sweeps: 1, 5, 9, ... -- part of the solver's definition, restated in oracle/oracle.cpp (MRF_DAMP_PERIOD)
 constexpr uint32_t MRF_DAMP_PERIOD = 4;
 // up to 64 words from device memory to the host between two launches of ctx->stream: a one-block kernel stores them into a pinned buffer and

@@ -546,6 +546,42 @@ MVS_HD uint32_t hist_bin(float value, float maxv, uint32_t num_bins) {
     return (uint32_t)floorf(((clamped - 0.0f) / (maxv - 0.0f)) * (float)(num_bins - 1));
 }
 
+// ---- view-set bitmaps (k_mrf.hip set-up) ----
+// A column's view ids are strictly ascending (calculate_data_costs.cpp:272), so a column IS a bitmap of W = ceil(V / 64) words, bit v of
+// word v / 64 = "view v is in the column".  Two columns are identical iff their bitmaps are equal; the position of view v in the column
+// is the number of set bits below bit v.  Neither identity holds for a column with a duplicate or a descending pair: such tables never
+// reach these helpers (k_mrf.hip mrf_bitmap_kernel flags them).
+constexpr uint32_t BITMAP_NONE = 0xFFFFFFFFu;
+MVS_HD uint32_t bitmap_words(uint32_t n_views) { return (n_views + 63u) >> 6; }
+MVS_HD uint64_t bitmap_below(uint32_t p) { return (1ull << p) - 1ull; }                       // bits 0 .. p - 1 of a word, p in [0, 63]
+MVS_HD uint32_t bitmap_popc(uint64_t x) { return (uint32_t)__builtin_popcountll(x); }
+// position of view v in the column whose word v / 64 is `word` and whose words below that one hold `before` views; BITMAP_NONE = absent
+MVS_HD uint32_t bitmap_rank_word(uint64_t word, uint32_t before, uint32_t v) {
+    const uint32_t p = v & 63u;
+    return ((word >> p) & 1ull) ? before + bitmap_popc(word & bitmap_below(p)) : BITMAP_NONE;
+}
+MVS_HD uint32_t bitmap_rank(const uint64_t* bits, uint32_t W, uint32_t v) {
+    const uint32_t w = v >> 6;
+    if (w >= W) return BITMAP_NONE;
+    uint32_t before = 0;
+    for (uint32_t k = 0; k < w; ++k) before += bitmap_popc(bits[k]);
+    return bitmap_rank_word(bits[w], before, v);
+}
+MVS_HD bool bitmap_equal(const uint64_t* a, const uint64_t* b, uint32_t W) {
+    uint64_t d = 0;
+    for (uint32_t k = 0; k < W; ++k) d |= a[k] ^ b[k];
+    return d == 0;
+}
+// bit position of the n-th (0-based) set bit of x, n < popcount(x): six halving steps on the popcount of the low half
+MVS_HD uint32_t bitmap_select(uint64_t x, uint32_t n) {
+    uint32_t pos = 0;
+    for (uint32_t sh = 32; sh > 0; sh >>= 1) {
+        const uint32_t c = bitmap_popc(x & bitmap_below(sh));
+        if (n >= c) { n -= c; x >>= sh; pos += sh; }
+    }
+    return pos;
+}
+
 // Host-side constant for cull_pair: the smallest float c with
 // !( (double)std::acos(c) > MATH_DEG2RAD(75.0f) ) -- calculate_data_costs.cpp:187 evaluated
 // with the HOST's acosf (the one a CPU build of the reference would call).  Returns NaN if

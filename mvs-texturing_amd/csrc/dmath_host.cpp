@@ -108,6 +108,27 @@ void dmh_gradient_magnitude(const uint8_t* rgb, int w, int h, uint8_t* gmi) {
 
 uint32_t dmh_hist_bin(float value, float maxv) { return hist_bin(value, maxv, 10000u); }
 
+// view-set bitmaps (dmath.h): the bitmap of a view list as mrf_bitmap_kernel builds it (ids >= n_views are dropped), and the three
+// questions the solver's set-up asks of it
+uint32_t dmh_bitmap_words(uint32_t n_views) { return bitmap_words(n_views); }
+void dmh_bitmap_of_list(const uint16_t* list, uint32_t n, uint32_t n_views, uint64_t* bits) {
+    const uint32_t W = bitmap_words(n_views);
+    for (uint32_t w = 0; w < W; ++w) bits[w] = 0;
+    for (uint32_t t = 0; t < n; ++t) if (list[t] < n_views) bits[list[t] >> 6] |= 1ull << (list[t] & 63u);
+}
+void dmh_bitmap_rank(const uint64_t* bits, uint32_t W, const uint32_t* query, uint32_t nq, uint32_t* out) {
+    for (uint32_t q = 0; q < nq; ++q) out[q] = bitmap_rank(bits, W, query[q]);
+}
+int dmh_bitmap_equal(const uint64_t* a, const uint64_t* b, uint32_t W) { return bitmap_equal(a, b, W) ? 1 : 0; }
+// out[t] = the t-th view of the bitmap, t < n <= its popcount: the word from the running counts, the bit by bitmap_select
+void dmh_bitmap_select(const uint64_t* bits, uint32_t W, uint32_t n, uint32_t* out) {
+    for (uint32_t t = 0; t < n; ++t) {
+        uint32_t w = 0, before = 0;
+        while (w + 1 < W && before + bitmap_popc(bits[w]) <= t) { before += bitmap_popc(bits[w]); ++w; }
+        out[t] = 64u * w + bitmap_select(bits[w], t - before);
+    }
+}
+
 // Exactness certificate of the lane-group footprint sampler (dmath.h foot_sums_certified) against what it certifies: `trials` random
 // footprints of 33 .. max_n pixels (u8 values from a random sub-range, as in an image region), random area; the integer-sum result
 // next to the serial fp64 sums of the quotients in three orders (forward = the reference's, backward, strided).

@@ -366,17 +366,82 @@ __global__ void mrf_inoff_kernel(const uint32_t* __restrict__ perm, const uint32
     }
 }
 
+// ---- view-set bitmaps: a column as W = ceil(V / 64) words (dmath.h "view-set bitmaps") ----
+// bits[i * W + w] = word w of column i's bitmap, built from the table mrf_setup is handed, every call: one streaming pass over the view
+// ids, 16 lanes per node, the words collected in the group's LDS tile (a group never spans waves and LDS operations of a wave execute
+// in order: no barrier).  The set-up's questions about a NEIGHBOUR's list -- is it the same list, where does view v sit in it -- are
+// then answered from W words instead of from the list (mrf_edge_kernel, mrf_record_bits_kernel, mrf_map_bits_kernel).
+// That rests on strictly ascending ids below V.  The library's own tables have them; a caller's table (mvs_ctx_costs_upload) is taken as
+// it is, so every id is bound-checked before its bit is set and every adjacent pair is compared: *flag is raised for a table that breaks
+// the rule, and mrf_setup then keeps to the list kernels, whose behaviour on such input is what it always was.
+constexpr uint32_t BITMAP_MAX_WORDS = 16;   // V <= 1024: one word per lane of a node's group (64 MB at 2 M faces x 200 views; beyond: the list kernels)
+// A lane takes FOUR consecutive entries per pass (one 8-byte load of view ids at 2-byte alignment, one 16-byte load of costs at 4-byte
+// alignment -- global loads need no natural alignment on gfx950), so a column of up to 64 entries is one pass of its group and all its
+// loads are in flight at once; one entry per lane made these kernels wait for three dependent rounds of 32-byte requests per column.
+// The last three entries of the table are read one by one: a wide load there would pass the end of the array.
+template <class T> __device__ __forceinline__ T ld_unaligned(const void* p) { T v; __builtin_memcpy(&v, p, sizeof(T)); return v; }
+__device__ __forceinline__ void ld_views4(const uint16_t* __restrict__ view_id, uint64_t at, uint32_t n, uint64_t nnz, uint32_t (&v)[4]) {
+    if (at + 4u <= nnz) { const uint2 w = ld_unaligned<uint2>(view_id + at); v[0] = w.x & 0xFFFFu; v[1] = w.x >> 16; v[2] = w.y & 0xFFFFu; v[3] = w.y >> 16; }
+    else {
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) v[r] = (r < n) ? (uint32_t)view_id[at + r] : 0u;
+    }
+}
+__global__ void __launch_bounds__(256) mrf_bitmap_kernel(const uint32_t* __restrict__ col_ptr, const uint16_t* __restrict__ view_id, uint64_t nnz, uint32_t F, uint32_t V, uint32_t W,
+                                                         unsigned long long* __restrict__ bits, uint32_t* __restrict__ flag) {
+    __shared__ uint32_t s_b[16][2 * BITMAP_MAX_WORDS];
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t gl = threadIdx.x & 15;
+    if (i >= F) return;
+    uint32_t* tile = s_b[threadIdx.x >> 4];
+    tile[2 * gl] = 0u; tile[2 * gl + 1] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const uint32_t p0 = col_ptr[i], K = col_ptr[i + 1] - p0;
+    bool bad = false;
+    uint32_t carry = 0u;                                        // the last id of the previous pass
+    for (uint32_t t0 = 0; t0 < K; t0 += 64) {
+        const uint32_t t = t0 + 4u * gl, n = t < K ? min(K - t, 4u) : 0u;
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+        if (n) ld_views4(view_id, (uint64_t)p0 + t, n, nnz, v);
+        uint32_t before = (uint32_t)__shfl_up((int)v[3], 1, 16);   // (a lane with entries has a left neighbour with four)
+        if (gl == 0u) before = carry;
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            if (r < n) {
+                bad = bad || v[r] >= V || ((t + r) != 0u && before >= v[r]);
+                if (v[r] < V) atomicOr(&tile[v[r] >> 5], 1u << (v[r] & 31u));
+            }
+            before = v[r];
+        }
+        carry = (uint32_t)__shfl((int)v[3], 15, 16);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (gl < W) bits[(size_t)i * W + gl] = (unsigned long long)tile[2 * gl] | ((unsigned long long)tile[2 * gl + 1] << 32);
+    if (bad) *flag = 1u;                                        // racing stores of the same value
+}
+
+// (bits != null -- the bitmap route: ident[e] = 1 iff the two label lists of the valid edge e of a FAST node are identical, i.e. the two
+//  bitmaps are equal; what mrf_ident_kernel finds by comparing the lists)
 __global__ void mrf_edge_kernel(const uint32_t* __restrict__ col_ptr, const uint32_t* __restrict__ adj_ptr, const uint32_t* __restrict__ adj,
-                                uint32_t F, const uint32_t* __restrict__ in_off, const uint32_t* __restrict__ size, const uint32_t* __restrict__ rev, MrfEdge* __restrict__ edge) {
+                                uint32_t F, const uint32_t* __restrict__ in_off, const uint32_t* __restrict__ size, const uint32_t* __restrict__ rev, MrfEdge* __restrict__ edge,
+                                const uint8_t* __restrict__ cls, const unsigned long long* __restrict__ bits, uint32_t W, uint8_t* __restrict__ ident) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F) return;
     const uint32_t e0 = adj_ptr[i], e1 = adj_ptr[i + 1];
+    const bool fast = bits && cls[i] != CLS_GENERIC;           // only fast nodes have records
     for (uint32_t eb = e0; eb < e1; eb += 4) {               // four edges at a time: the loads of a level are independent
         uint32_t j[4], r[4], io[4], sz[4], oo[4], kj[4];
+        unsigned long long diff[4] = {0ull, 0ull, 0ull, 0ull};
 #pragma unroll
         for (int t = 0; t < 4; ++t) { const bool on = eb + t < e1; j[t] = on ? adj[eb + t] : i; r[t] = on ? rev[eb + t] : 0xFFFFFFFFu; io[t] = on ? in_off[eb + t] : 0u; sz[t] = on ? size[eb + t] : 0u; }
 #pragma unroll
         for (int t = 0; t < 4; ++t) { oo[t] = (r[t] != 0xFFFFFFFFu) ? in_off[r[t]] : 0u; kj[t] = col_ptr[j[t] + 1] - col_ptr[j[t]]; }
+        if (fast)
+            for (uint32_t w = 0; w < W; ++w) {
+                const unsigned long long own = bits[(size_t)i * W + w];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) diff[t] |= own ^ bits[(size_t)j[t] * W + w];
+            }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             if (eb + t >= e1) continue;
@@ -386,6 +451,7 @@ __global__ void mrf_edge_kernel(const uint32_t* __restrict__ col_ptr, const uint
             m.out_off = has ? MSG_BASE + oo[t] : 0u;
             m.kj = (sz[t] > 0 && has) ? kj[t] : 0u;
             edge[eb + t] = m;
+            if (bits) ident[eb + t] = (uint8_t)((fast && m.kj != 0u && diff[t] == 0ull) ? 1u : 0u);
         }
     }
 }
@@ -429,7 +495,7 @@ __global__ void __launch_bounds__(256) mrf_map_kernel(const uint32_t* __restrict
 // read every third column of the CSR), the view id of the decoded label is already in a register (no gather), the unaries
 // are 16-bit fixed point (2 instead of 4 bytes; part of the solver's definition, restated in oracle/oracle.cpp), the
 // re-alignment maps are bytes (K <= 255; 0xFF = label absent at the sender) and exist only where the lists differ.
-constexpr uint32_t REC_BASE = 256;            // words [0, REC_BASE) of the record array are zero: where masked lanes load
+constexpr uint32_t REC_BASE = MRF_REC_BASE;   // words [0, REC_BASE) of the record array are zero: where masked lanes load
 constexpr float COST_SCALE = 65535.0f;
 __device__ __forceinline__ uint32_t cost_code(float c) { return (uint32_t)(c * COST_SCALE + 0.5f); }   // c in [0, 1]
 __device__ __forceinline__ float cost_value(uint32_t code) { return (float)code * (1.0f / 65535.0f); }
@@ -605,6 +671,161 @@ __global__ void mrf_desc_kernel(const uint32_t* __restrict__ col_ptr, const uint
         nd.in_off[d] = m.in_off | flag_low; nd.out_off[d] = m.out_off | flag_ident; nd.kk |= m.kj << (8 + 8 * d); nd.nbr[d] = nb;
     }
     desc[q] = nd;
+}
+
+// ---- the bitmap route of the two kernels above and of mrf_map_kernel: the same bytes, no neighbour list is read ----
+// a bitmap word per lane -> the group's LDS tile: the words and, beside them, the number of views in the words below each (an exclusive
+// scan over the group's 16 lanes), which is what a rank or a select needs besides the word itself
+__device__ __forceinline__ void bitmap_to_tile(unsigned long long word, uint32_t gl, unsigned long long* __restrict__ t_bits, uint32_t* __restrict__ t_pre) {
+    const uint32_t c = bitmap_popc(word);
+    uint32_t incl = c;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 16); incl += (gl >= (uint32_t)o) ? up : 0u; }
+    t_bits[gl] = word; t_pre[gl] = incl - c;
+}
+// Record AND descriptor of node i, 16 lanes per node, nodes in face order (see mrf_record_kernel).  The map of out-edge d holds, for
+// every label of the RECEIVER nb[d] in its list order, the slot of that label in THIS node's list.  The receiver's labels are the set
+// bits of its bitmap in ascending order: lane gl finds the first of its group of four from the word counts (bitmap_select) and walks on
+// from there; the position of view v in the own list is the number of own bits below v (bitmap_rank_word).  Slot formulas, the "absent"
+// byte and the padding are those of mrf_record_kernel -- the records are the same bytes.
+// The group also has everything the node's descriptor is made of (edge words, identity flags, roff[q]) in registers: lane 0 writes it;
+// the neighbours' colours are requested together with the edge words.  Nodes with an empty column have a descriptor and no record.
+__global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __restrict__ col_ptr, const uint16_t* __restrict__ view_id, const float* __restrict__ cost,
+                                                              const uint32_t* __restrict__ adj_ptr, const uint32_t* __restrict__ adj, const MrfEdge* __restrict__ edge,
+                                                              const uint8_t* __restrict__ ident, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ qpos, const uint32_t* __restrict__ roff,
+                                                              const uint32_t* __restrict__ colour, const unsigned long long* __restrict__ bits, uint32_t W, uint64_t nnz, uint32_t F, uint32_t n_fast,
+                                                              uint32_t* __restrict__ rec, NodeDesc* __restrict__ desc) {
+    __shared__ unsigned long long s_bits[16][4][BITMAP_MAX_WORDS];   // [group][own, receiver 0 .. 2][word]
+    __shared__ uint32_t s_pre[16][4][BITMAP_MAX_WORDS];
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t gl = threadIdx.x & 15;
+    if (i >= F) return;
+    const uint32_t ci = cls[i];
+    if (ci == CLS_GENERIC) return;                             // (a fast node: degree <= 3)
+    const uint32_t p0 = col_ptr[i], K = col_ptr[i + 1] - p0;
+    const uint32_t q = qpos[i], ro = roff[q], col_i = colour[i];
+    const uint32_t e0 = adj_ptr[i], deg = min(adj_ptr[i + 1] - e0, 3u);
+    MrfEdge m[3]; uint32_t idn[3], nb[3], col_n[3], kj3[3];
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d) {
+        const bool on = d < deg;
+        m[d].in_off = on ? edge[e0 + d].in_off : 0u; m[d].out_off = on ? edge[e0 + d].out_off : 0u; m[d].kj = on ? edge[e0 + d].kj : 0u;
+        idn[d] = on ? (uint32_t)ident[e0 + d] : 0u; nb[d] = on ? adj[e0 + d] : i;
+    }
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d) {
+        col_n[d] = colour[nb[d]];
+        if (K == 0u || m[d].kj == 0u) { m[d].in_off = 0u; m[d].out_off = 0u; m[d].kj = 0u; }   // edge not in the model: the sweep reads the reserved zero run
+        kj3[d] = idn[d] ? 0u : m[d].kj;                         // a map only where the lists differ
+    }
+    const bool maps = (kj3[0] | kj3[1] | kj3[2]) != 0u;         // group-uniform
+    unsigned long long bw[4] = {0ull, 0ull, 0ull, 0ull};
+    if (maps && gl < W) {
+        bw[0] = bits[(size_t)i * W + gl];
+#pragma unroll
+        for (uint32_t d = 0; d < 3; ++d) if (kj3[d]) bw[d + 1] = bits[(size_t)nb[d] * W + gl];
+    }
+    if (gl == 0u && q < n_fast) {
+        NodeDesc nd;
+        nd.rec = K ? REC_BASE + ro : 0u; nd.id = i; nd.kk = K;
+#pragma unroll
+        for (uint32_t d = 0; d < 3; ++d) {
+            const uint32_t flag_low = (d < deg && col_n[d] < col_i) ? 1u : 0u, flag_ident = (m[d].kj && idn[d]) ? 1u : 0u;
+            nd.in_off[d] = m[d].in_off | flag_low; nd.out_off[d] = m[d].out_off | flag_ident; nd.kk |= m[d].kj << (8 + 8 * d); nd.nbr[d] = nb[d];
+        }
+        desc[q] = nd;
+    }
+    if (K == 0u) return;
+    const bool w8 = ci == 1u;
+    const uint32_t rs = w8 ? 8u : 8u << ci, none_byte = w8 ? 64u : (ci < 3u ? 4u * rs : 0xFFu);
+    const uint32_t lmask = w8 ? 7u : 3u, lshift = w8 ? 3u : 2u;
+    uint32_t* out = rec + REC_BASE + ro;
+    const uint32_t K4 = (K + 3u) & ~3u;
+    for (uint32_t t = 4u * gl; t < K4; t += 64) {             // (records start at multiples of four words: 16-byte stores)
+        const uint32_t n = min(K - t, 4u);
+        const uint64_t at = (uint64_t)p0 + t;
+        uint32_t v[4]; float c[4];
+        ld_views4(view_id, at, n, nnz, v);
+        if (at + 4u <= nnz) { const float4 cc = ld_unaligned<float4>(cost + at); c[0] = cc.x; c[1] = cc.y; c[2] = cc.z; c[3] = cc.w; }
+        else {
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) c[r] = (r < n) ? cost[at + r] : 0.0f;
+        }
+        uint4 w;
+        w.x = (cost_code(c[0]) << 16) | v[0];
+        w.y = (n > 1u) ? (cost_code(c[1]) << 16) | v[1] : 0u;
+        w.z = (n > 2u) ? (cost_code(c[2]) << 16) | v[2] : 0u;
+        w.w = (n > 3u) ? (cost_code(c[3]) << 16) | v[3] : 0u;
+        *reinterpret_cast<uint4*>(out + t) = w;
+    }
+    uint32_t pos = K4;
+    if (maps) {
+        unsigned long long (*t_bits)[BITMAP_MAX_WORDS] = s_bits[threadIdx.x >> 4];
+        uint32_t (*t_pre)[BITMAP_MAX_WORDS] = s_pre[threadIdx.x >> 4];
+#pragma unroll
+        for (uint32_t b = 0; b < 4; ++b) bitmap_to_tile(bw[b], gl, t_bits[b], t_pre[b]);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+        for (uint32_t d = 0; d < 3; ++d) {
+            const uint32_t kj = kj3[d];
+            if (kj == 0u) continue;                            // group-uniform: not in the model, or identical lists (no map)
+            const uint32_t nw = w8 ? 2u * ((kj + 7u) >> 3) : (kj + 3u) >> 2;
+            for (uint32_t wI = gl; wI < nw; wI += 16) {
+                const uint32_t n = 4u * wI;                    // the receiver's labels n .. n + 3
+                uint32_t word = none_byte * 0x01010101u;
+                if (n < kj) {
+                    uint32_t w = 0u;                           // the last word with at most n views below it holds label n
+                    for (uint32_t ww = 1u; ww < W; ++ww) w = (t_pre[d + 1][ww] <= n) ? ww : w;
+                    unsigned long long x = t_bits[d + 1][w];
+                    x &= ~bitmap_below(bitmap_select(x, n - t_pre[d + 1][w]));
+                    word = 0u;
+#pragma unroll
+                    for (uint32_t r = 0; r < 4; ++r) {
+                        uint32_t byte = none_byte;
+                        if (n + r < kj) {
+                            while (x == 0ull && w + 1u < W) { ++w; x = t_bits[d + 1][w]; }
+                            if (x != 0ull) {
+                                const uint32_t p = (uint32_t)__builtin_ctzll(x);
+                                x &= x - 1ull;
+                                const uint32_t at = bitmap_rank_word(t_bits[0][w], t_pre[0][w], p);   // position of that view in the own list
+                                if (at != BITMAP_NONE) byte = (at & lmask) * rs + (at >> lshift);
+                            }
+                        }
+                        word |= byte << (8 * r);
+                    }
+                }
+                out[pos + wI] = word;
+            }
+            pos += nw;
+        }
+    }
+    for (uint32_t t = pos + gl; t < ((pos + 3u) & ~3u); t += 16) out[t] = 0u;
+}
+// mrf_map_kernel on the bitmap route: the position of L_i[t] in the generic sender's list = its rank in the sender's bitmap
+__global__ void __launch_bounds__(256) mrf_map_bits_kernel(const uint32_t* __restrict__ col_ptr, const uint16_t* __restrict__ view_id, const uint32_t* __restrict__ adj_ptr,
+                                                           const uint32_t* __restrict__ adj, uint32_t F, const MrfEdge* __restrict__ edge, const uint8_t* __restrict__ cls,
+                                                           const unsigned long long* __restrict__ bits, uint32_t W, uint16_t* __restrict__ map) {
+    __shared__ unsigned long long s_bits[16][BITMAP_MAX_WORDS];
+    __shared__ uint32_t s_pre[16][BITMAP_MAX_WORDS];
+    const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint32_t gl = threadIdx.x & 15;
+    if (i >= F) return;
+    unsigned long long* t_bits = s_bits[threadIdx.x >> 4];
+    uint32_t* t_pre = s_pre[threadIdx.x >> 4];
+    const uint32_t p0 = col_ptr[i], K = col_ptr[i + 1] - p0;
+    for (uint32_t e = adj_ptr[i]; e < adj_ptr[i + 1]; ++e) {
+        const MrfEdge m = edge[e];
+        const uint32_t j = adj[e];
+        if (m.kj == 0 || cls[j] != CLS_GENERIC) continue;      // group-uniform
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the previous edge's reads of the tile)
+        bitmap_to_tile(gl < W ? bits[(size_t)j * W + gl] : 0ull, gl, t_bits, t_pre);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (uint32_t t = gl; t < K; t += 16) {
+            const uint32_t v = view_id[p0 + t], w = v >> 6;
+            const uint32_t at = (w < W) ? bitmap_rank_word(t_bits[w], t_pre[w], v) : BITMAP_NONE;
+            map[m.in_off + t] = (at != BITMAP_NONE) ? (uint16_t)at : MAP_NONE;
+        }
+    }
 }
 
 // ---- one colour phase of a sweep; fast path: degree <= 3, K <= 255 (and K <= 4 * G) ----
@@ -1312,6 +1533,15 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
     const unsigned nb = (F + 255) / 256;
     // degenerate inputs (fewer than four table entries, no edge at all) take the generic kernel throughout; "mrf_force_generic" is a test hook
     const uint32_t force_generic = (ctx->csr_nnz < 4 || E == 0 || ctx->mrf_force_generic) ? 1u : 0u;
+    // view-set bitmaps of the table as it is handed in (whatever made it: this context's data costs, an upload, pruning, a shard's face
+    // range), built anew every call; the word behind the two maxima says whether the table keeps the rule they rest on.  More than
+    // BITMAP_MAX_WORDS words per face, or "mrf_force_lists" (a test hook): the list kernels.
+    const uint32_t W = bitmap_words(ctx->csr_views);
+    bool bitmaps = F && W >= 1 && W <= BITMAP_MAX_WORDS && !ctx->mrf_force_lists;
+    if (bitmaps) {
+        ctx->m_bits.ensure((size_t)F * W + 1);
+        hipLaunchKernelGGL(mrf_bitmap_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, (uint64_t)ctx->csr_nnz, F, ctx->csr_views, W, ctx->m_bits.p, maxes + 3); MVS_LAUNCH_CHECK();
+    }
     ctx->m_cls.ensure((size_t)F + 4);
     ctx->m_rev.ensure((size_t)E + 2);
     if (F) { hipLaunchKernelGGL(mrf_size_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, F, RUN_PAD_MASK, force_generic, ctx->m_size.p, ctx->m_cls.p, maxes, ctx->m_rev.p); MVS_LAUNCH_CHECK(); }
@@ -1373,31 +1603,40 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
         hipLaunchKernelGGL(mrf_inoff_kernel, dim3(nb), dim3(256), 0, s, ctx->m_perm.p, ctx->m_colour.p, ctx->r_adj_ptr, ctx->r_adj, ctx->m_size.p, ctx->m_rev.p, ctx->m_tmp_b.p, F, n_col, in_off.p); MVS_LAUNCH_CHECK();
         MVS_HIP(hipMemcpyAsync(maxes + 2, ctx->m_tmp_b.p + (n_ent - 1), sizeof(uint32_t), hipMemcpyDeviceToDevice, s));   // (next to the two maxima: one read-back)
     } else MVS_HIP(hipMemsetAsync(maxes + 2, 0, sizeof(uint32_t), s));
-    { uint32_t hm[3]; read_words(ctx, maxes, hm, 3); h[1] = hm[0]; h[2] = hm[1]; h[0] = hm[2]; }
+    { uint32_t hm[4]; read_words(ctx, maxes, hm, 4); h[1] = hm[0]; h[2] = hm[1]; h[0] = hm[2]; if (hm[3]) bitmaps = false; }   // (a column that is not strictly ascending below csr_views)
+    ctx->m_bitmaps = bitmaps;
+    const unsigned long long* bits = bitmaps ? ctx->m_bits.p : nullptr;
     ctx->m_total = (uint64_t)MSG_BASE + h[0]; ctx->m_kmax = h[1]; ctx->m_degmax = h[2];
     if (ctx->m_total >= 0xFFFFFFF0ull) throw StatusError(MVS_ERR_UNSUPPORTED, "message array exceeds 2^32 elements");
-    if (F) { hipLaunchKernelGGL(mrf_edge_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, F, in_off.p, ctx->m_size.p, ctx->m_rev.p, ctx->m_edge.p); MVS_LAUNCH_CHECK(); }
     ctx->m_ident.ensure((size_t)E + 1);
-    MVS_HIP(hipMemsetAsync(ctx->m_ident.p, 0, (size_t)E + 1, s));
+    if (!bitmaps) MVS_HIP(hipMemsetAsync(ctx->m_ident.p, 0, (size_t)E + 1, s));   // (the bitmap route's edge kernel writes every flag)
+    if (F) { hipLaunchKernelGGL(mrf_edge_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, F, in_off.p, ctx->m_size.p, ctx->m_rev.p, ctx->m_edge.p, ctx->m_cls.p, bits, W, ctx->m_ident.p); MVS_LAUNCH_CHECK(); }
     const uint32_t n_fast = ctx->m_n_fast, n_generic = F - n_fast;
     if (n_fast) {
         // records + descriptors of the fast nodes.  Upper bound of the record array (no read-back): labels nnz + 3 F, maps <= one byte per message element
         const size_t rec_cap = (size_t)REC_BASE + ctx->csr_nnz + 8 * (size_t)F + ctx->m_total / 4 + (size_t)ctx->m_n_adj + 1024;   // incl. slack for reads past the last record
         ctx->m_rec.ensure(rec_cap);
         MVS_HIP(hipMemsetAsync(ctx->m_rec.p, 0, REC_BASE * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(mrf_ident_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, ctx->m_ident.p); MVS_LAUNCH_CHECK();
+        if (!bitmaps) { hipLaunchKernelGGL(mrf_ident_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, ctx->m_ident.p); MVS_LAUNCH_CHECK(); }
         uint32_t* rsz = ctx->m_tmp_a.p; uint32_t* roff = ctx->m_tmp_b.p;   // F + 1 entries each
         hipLaunchKernelGGL(mrf_recsize_kernel, dim3((F + 256) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_perm.p, F, rsz, ctx->m_tmp_c.p); MVS_LAUNCH_CHECK();
         exclusive_scan_u32(ctx, rsz, roff, (size_t)F + 1, nullptr);
-        hipLaunchKernelGGL(mrf_record_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->r_adj_ptr, ctx->r_adj,
-                           ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_tmp_c.p /* qpos */, roff, F, ctx->m_rec.p); MVS_LAUNCH_CHECK();
         ctx->m_desc.ensure((size_t)F + 1);
-        hipLaunchKernelGGL(mrf_desc_kernel, dim3((n_fast + 255) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, ctx->m_edge.p, ctx->m_ident.p, ctx->m_perm.p, ctx->m_colour.p, roff, n_fast, ctx->m_desc.p); MVS_LAUNCH_CHECK();
+        if (bitmaps) {   // records and descriptors in one pass
+            hipLaunchKernelGGL(mrf_record_bits_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->r_adj_ptr, ctx->r_adj,
+                               ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_tmp_c.p /* qpos */, roff, ctx->m_colour.p, bits, W, (uint64_t)ctx->csr_nnz, F, n_fast, ctx->m_rec.p, ctx->m_desc.p); MVS_LAUNCH_CHECK();
+        } else {
+            hipLaunchKernelGGL(mrf_record_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->r_adj_ptr, ctx->r_adj,
+                               ctx->m_edge.p, ctx->m_ident.p, ctx->m_cls.p, ctx->m_tmp_c.p /* qpos */, roff, F, ctx->m_rec.p); MVS_LAUNCH_CHECK();
+            hipLaunchKernelGGL(mrf_desc_kernel, dim3((n_fast + 255) / 256), dim3(256), 0, s, ctx->r_ptr, ctx->r_adj_ptr, ctx->r_adj, ctx->m_edge.p, ctx->m_ident.p, ctx->m_perm.p, ctx->m_colour.p, roff, n_fast, ctx->m_desc.p); MVS_LAUNCH_CHECK();
+        }
     }
     if (n_generic) {
         // 16-bit re-alignment maps of the runs the generic nodes SEND (indexed like the messages); only those elements are ever read
         ctx->m_map.ensure(ctx->m_total + 8);
-        hipLaunchKernelGGL(mrf_map_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, ctx->m_map.p); MVS_LAUNCH_CHECK();
+        if (bitmaps) hipLaunchKernelGGL(mrf_map_bits_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, bits, W, ctx->m_map.p);
+        else hipLaunchKernelGGL(mrf_map_kernel, dim3((unsigned)(((size_t)F * 16 + 255) / 256)), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_adj_ptr, ctx->r_adj, F, ctx->m_edge.p, ctx->m_cls.p, ctx->m_map.p);
+        MVS_LAUNCH_CHECK();
         ctx->pq.ensure(ctx->csr_nnz + 1);   // scratch row per generic node (the data-cost work buffer is free by now)
     }
     ctx->m_msg_a.ensure(ctx->m_total + 1024);   // slack: lanes beyond a run read on (up to 4 * 64 elements)

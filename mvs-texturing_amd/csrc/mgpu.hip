@@ -169,6 +169,29 @@ mvs_status mvs_ctx_mrf_sweep_phase_part(mvs_ctx* ctx, uint32_t phase, uint32_t n
     mrf_sweep_phase(ctx, phase, nb0, ne0, part);
     MVS_API_END
 }
+mvs_status mvs_ctx_mrf_setup_tables(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
+    if (!ctx || !n_bytes || which < 0 || which > 3) return api_fail(MVS_ERR_INVALID, "bad argument");
+    if (!ctx->m_state.p) return api_fail(MVS_ERR_STATE, "mrf setup first");
+    MVS_API_BEGIN
+    const uint32_t F = ctx->csr_faces, n_fast = ctx->m_n_fast;
+    const void* src = nullptr; uint64_t n = 0, route = ctx->m_bitmaps ? 1u : 0u;
+    if (which == 0) { n = sizeof(route); }
+    else if (which == 1 && n_fast) {   // roff[F] = words of all records, still where the set-up's scan left it
+        uint32_t words = 0;
+        MVS_HIP(hipMemcpyAsync(&words, ctx->m_tmp_b.p + F, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+        src = ctx->m_rec.p; n = ((uint64_t)MRF_REC_BASE + words) * sizeof(uint32_t);
+    }
+    else if (which == 2 && n_fast) { src = ctx->m_desc.p; n = (uint64_t)n_fast * sizeof(NodeDesc); }
+    else if (which == 3) { src = ctx->m_ident.p; n = ctx->m_n_adj; }
+    *n_bytes = n;
+    if (out_host && n) {
+        if (cap_bytes < n) throw StatusError(MVS_ERR_INVALID, "setup tables: buffer too small");
+        if (which == 0) memcpy(out_host, &route, sizeof(route));
+        else { MVS_HIP(hipMemcpyAsync(out_host, src, n, hipMemcpyDeviceToHost, ctx->stream)); MVS_HIP(hipStreamSynchronize(ctx->stream)); }
+    }
+    MVS_API_END
+}
 mvs_status mvs_ctx_mrf_layout(mvs_ctx* ctx, uint32_t* in_off_host, uint64_t n_edges) {
     if (!ctx || (n_edges && !in_off_host)) return api_fail(MVS_ERR_INVALID, "null argument");
     MVS_API_BEGIN

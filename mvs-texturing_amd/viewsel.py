@@ -153,7 +153,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables"))
 
 
 _lib = None
@@ -210,6 +210,7 @@ def load_library():
         "mvs_ctx_mrf_step": [vp, vp], "mvs_ctx_mrf_poll": [vp, u32, C.POINTER(MrfProgress)],
         "mvs_ctx_mrf_icm_gain": [vp, u32, u32], "mvs_ctx_mrf_icm_apply": [vp, u32, u32, vp],
         "mvs_ctx_mrf_labels": [vp, u32, u32, vp, C.POINTER(u32)],
+        "mvs_ctx_mrf_setup_tables": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_comm_unique_id": [vp], "mvs_comm_create_rccl": [i32, i32, i32, vp, C.POINTER(vp)], "mvs_comm_create_local": [i32, C.POINTER(vp)], "mvs_comm_create_local_devices": [i32, vp, C.POINTER(vp)],
@@ -473,6 +474,20 @@ class Context:
         _check(self.L, self.L.mvs_ctx_view_selection(self.h, pa, pb, d0, C.byref(p), pl, dl, C.byref(ms)))
         return labels_out, _stats_dict(ms)
 
+
+    def mrf_setup_tables(self):
+        """what the last solve's set-up built (mvs_ctx_mrf_setup_tables, building-blocks library): {"bitmaps": the set-up worked from
+        view-set bitmaps, "rec": uint32 record words, "desc": uint32 (n_fast, 12) descriptors, "ident": uint8 flag per directed edge}"""
+        out = {}
+        for which, key, dt in ((0, "bitmaps", np.uint64), (1, "rec", np.uint32), (2, "desc", np.uint32), (3, "ident", np.uint8)):
+            n = C.c_uint64(0)
+            _check(self.L, self.L.mvs_ctx_mrf_setup_tables(self.h, which, None, 0, C.byref(n)))
+            buf = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
+            if n.value:
+                _check(self.L, self.L.mvs_ctx_mrf_setup_tables(self.h, which, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+            out[key] = buf
+        out["bitmaps"] = bool(out["bitmaps"][0]); out["desc"] = out["desc"].reshape(-1, 12)
+        return out
 
     def mrf_diagnostics(self):
         """{graph_launches, graph_updates, graph_instantiations, generic_nodes} of this context's view selections"""
