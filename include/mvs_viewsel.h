@@ -542,6 +542,56 @@ mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, co
                                        const mvs_lsl_params* params, mvs_lsl_result* out, int out_on_device, mvs_lsl_stats* stats);
 void mvs_lsl_result_free(mvs_lsl_result* r);
 
+/* Row f8: tex::generate_texture_atlases (generate_texture_atlases.cpp:35-166, texture_atlas.cpp, rectangular_bin.cpp) on a patch set
+ * as mvs_patch_set describes it (row f7's image and validity merged over row f6's set; `label` and `blending` are not read), tone
+ * mapping `none`: the patches are ordered and packed into square atlases (256 .. 8192, padding = size >> 7), their pixels quantised
+ * (float_to_byte_image) and copied with their validity, every atlas dilated by apply_edge_padding, the texture coordinates moved into
+ * the atlas and merged.  The definition is DESIGN.md section 4 "Texture atlases"; every array is the same bits on any device and in
+ * every run.  Needs neither mesh nor views; `patches` is all host arrays or all device pointers (patches_on_device) and is not
+ * modified.  For A = n_atlases, in upstream's creation order:
+ *   atlas_size[a]; atlas a's pixels are image[3 atlas_pix_ptr[a] ..) (uint8, interleaved RGB, row-major, after the edge padding);
+ *   patch_atlas[p], patch_pos[2 p ..] = rect.min_x, rect.min_y (the patch's pixel (0, 0) lies `padding` further in both directions);
+ *   patch_order: the patches in insertion order (grouped by atlas); faces[face_ptr[a] .. face_ptr[a + 1]): atlas a's faces (patches in
+ *   insertion order, list order within a patch), texcoords[6 e + 2 k ..]: corner k of entry e before the merge;
+ *   texcoords_merged[2 (tc_ptr[a] + i) ..]: coordinate i of atlas a, texcoord_ids[3 e + k]: its id within the atlas.
+ * params.max_pixels (0 = no cap): when the atlases' pixel total exceeds it the call fails with MVS_ERR_UNSUPPORTED before the pixel
+ * arrays are allocated; stats (atlases, pixels, free_rects_peak) is filled all the same.  MVS_ERR_UNSUPPORTED as well for a patch with
+ * width + 128 >= 8192 or height + 128 >= 8192 (upstream asserts) and for a texture coordinate that is not finite once it is in the atlas.
+ * The packing itself runs on the host inside the call.  With
+ * out_on_device the arrays are device pointers owned by the context (valid until its next texture_atlases call or its destruction),
+ * otherwise malloc'ed host copies (mvs_atlas_set_free). */
+typedef struct mvs_atlas_params {
+    uint64_t max_pixels;      /* refuse a result of more atlas pixels than this (0: no cap) */
+    uint64_t reserved;
+} mvs_atlas_params;
+void mvs_atlas_default_params(mvs_atlas_params* p);
+typedef struct mvs_atlas_set {
+    uint32_t n_atlases, n_patches, n_listed, n_merged;   /* n_merged = tc_ptr[n_atlases] */
+    uint64_t n_pixels;              /* atlas_pix_ptr[n_atlases] */
+    uint32_t* atlas_size;           /* [n_atlases] */
+    uint64_t* atlas_pix_ptr;        /* [n_atlases + 1] */
+    uint8_t* image;                 /* [3 n_pixels] */
+    uint32_t* patch_atlas;          /* [n_patches] */
+    int32_t* patch_pos;             /* [2 n_patches] */
+    uint32_t* patch_order;          /* [n_patches] */
+    uint32_t* face_ptr;             /* [n_atlases + 1] */
+    uint32_t* faces;                /* [n_listed] */
+    float* texcoords;               /* [6 n_listed] */
+    uint32_t* tc_ptr;               /* [n_atlases + 1] */
+    float* texcoords_merged;        /* [2 n_merged] */
+    uint32_t* texcoord_ids;         /* [3 n_listed] */
+} mvs_atlas_set;
+typedef struct mvs_atlas_stats {
+    uint64_t atlases, atlases_by_size[6];          /* all; of side 256, 512, 1024, 2048, 4096, 8192 */
+    uint64_t pixels, valid_pixels, padded_pixels;  /* atlas pixels; validity 255 before the padding; filled by the padding */
+    uint64_t free_rects_peak, merged_texcoords;    /* longest free list of a bin; texcoords after the merge */
+    float ms_pack, ms_compose, ms_pad, ms_texcoords, ms_total;   /* ms_pack: HOST time (ordering, packing, per-patch tables and their uploads); device time: clear, quantise and scatter; sweeps; coordinates and merge; ms_total: the sum of the four */
+    float reserved;
+} mvs_atlas_stats;
+mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, int patches_on_device, const mvs_atlas_params* params,
+                                   mvs_atlas_set* out, int out_on_device, mvs_atlas_stats* stats);
+void mvs_atlas_set_free(mvs_atlas_set* a);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

@@ -353,7 +353,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto* b : ctx->own_rgb) delete b;
-    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx);
+    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx);
     if (ctx->sweep_exec) (void)hipGraphExecDestroy(ctx->sweep_exec);
     if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }

@@ -118,6 +118,7 @@ static_assert(sizeof(NodeDesc) == 48, "NodeDesc must be 48 bytes");
 struct GslDev;   // row f5 (k_seam.hip)
 struct TexPatchDev;   // row f6 (k_texpatch.hip)
 struct LslDev;   // row f7 (k_localseam.hip)
+struct AtlasDev; // row f8 (k_atlas.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -236,7 +237,7 @@ struct mvs_ctx {
     mvs::DBuf<uint32_t> p_label_ptr, p_comp_ptr, p_comp_faces, p_parent, p_root, p_state, p_flag, p_pos, p_roots, p_roots2, p_rlab, p_rlab2, p_adj_ptr, p_adj, p_labels;
 
     // ---- row f5: global seam leveling (k_seam.hip): buffers allocated on first use ----
-    mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr;
+    mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -352,6 +353,7 @@ void gsl_release(mvs_ctx* ctx);
 void texpatch_release(mvs_ctx* ctx);
 // frees the buffers of row f7 (k_localseam.hip)
 void lsl_release(mvs_ctx* ctx);
+void atlas_release(mvs_ctx* ctx);
 // rows f5 / f6 (k_texpatch.hip): the views' parameters on the device and the checks on the caller's labels and faces -- throws MVS_ERR_LABELING
 // for a label above the number of views, MVS_ERR_INVALID for a vertex id >= n_verts; `who` starts the message
 void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, const char* who);

@@ -130,6 +130,28 @@ class LslStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in LSL_COUNTS] + [("iterations_max", C.c_uint32), ("error_max", C.c_float)] + [(k, C.c_float) for k in LSL_MS]
 
 
+class AtlasParams(C.Structure):
+    _fields_ = [("max_pixels", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+ATLAS_ARRAYS = ("atlas_size", "atlas_pix_ptr", "image", "patch_atlas", "patch_pos", "patch_order", "face_ptr", "faces", "texcoords", "tc_ptr",
+                "texcoords_merged", "texcoord_ids")
+
+
+class AtlasSet(C.Structure):
+    _fields_ = [("n_atlases", C.c_uint32), ("n_patches", C.c_uint32), ("n_listed", C.c_uint32), ("n_merged", C.c_uint32), ("n_pixels", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ATLAS_ARRAYS]
+
+
+ATLAS_COUNTS = ("atlases", "atlases_256", "atlases_512", "atlases_1024", "atlases_2048", "atlases_4096", "atlases_8192", "pixels", "valid_pixels",
+                "padded_pixels", "free_rects_peak", "merged_texcoords")
+ATLAS_MS = ("ms_pack", "ms_compose", "ms_pad", "ms_texcoords", "ms_total")
+
+
+class AtlasStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ATLAS_COUNTS] + [(k, C.c_float) for k in ATLAS_MS] + [("reserved", C.c_float)]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -230,6 +252,8 @@ def load_library():
         "mvs_ctx_texture_patches": [vp, vp, vp, i32, vp, i32, vp, i32, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
         "mvs_lsl_default_params": [C.POINTER(LslParams)], "mvs_lsl_result_free": [C.POINTER(LslResult)],
         "mvs_ctx_local_seam_leveling": [vp, vp, vp, i32, vp, i32, C.POINTER(PatchSet), i32, C.POINTER(LslParams), C.POINTER(LslResult), i32, C.POINTER(LslStats)],
+        "mvs_atlas_default_params": [C.POINTER(AtlasParams)], "mvs_atlas_set_free": [C.POINTER(AtlasSet)],
+        "mvs_ctx_texture_atlases": [vp, C.POINTER(PatchSet), i32, C.POINTER(AtlasParams), C.POINTER(AtlasSet), i32, C.POINTER(AtlasStats)],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -254,7 +278,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -614,6 +638,53 @@ class Context:
         out["image"] = out["image"].reshape(NP, 3)
         return out, stats
 
+    def texture_atlases(self, patches, params=None, on_device=False):
+        """Row f8: tex::generate_texture_atlases on a patch set (DESIGN.md section 4 "Texture atlases"): `patches` is the dict of
+        texture_patches with row f7's image and validity merged over it -- all host arrays or all DevArrays / CUDA tensors; label and
+        blending are not read -- and is not modified.  Needs neither mesh nor views.  Returns (arrays, stats): atlas_size (A,),
+        atlas_pix_ptr (A + 1,) uint64, image (n_pixels, 3) uint8 -- atlas_view(arrays, a) cuts atlas a out --, patch_atlas (P,), patch_pos
+        (P, 2), patch_order (P,), face_ptr (A + 1,), faces, texcoords (n_listed, 3, 2), tc_ptr (A + 1,), texcoords_merged (n_merged, 2),
+        texcoord_ids (n_listed, 3); with on_device=True DevArrays owned by the context (valid until the next texture_atlases call).
+        An atlas pixel total above params.max_pixels raises MvsError (status 7) with `.stats` holding the counts."""
+        dts = dict(box=np.int32, face_ptr=np.uint32, faces=np.uint32, texcoords=np.float32, pix_ptr=np.uint64, image=np.float32, validity=np.uint8)
+        dev = [_is_torch(patches[k]) or isinstance(patches[k], DevArray) for k in dts]
+        assert all(dev) or not any(dev), "the patch set must be all host or all device arrays"
+        held = {k: patches[k] if dev[0] else np.ascontiguousarray(patches[k], dts[k]).reshape(-1) for k in dts}
+        ps = PatchSet()
+        if dev[0]:
+            count = lambda x: int(x.numel()) if _is_torch(x) else int(x.shape[0])
+            P = count(held["box"]) // 4; ps.n_listed = count(held["faces"]); ps.n_pixels = count(held["validity"])
+        else:
+            P = held["box"].size // 4; ps.n_listed = held["faces"].size; ps.n_pixels = held["validity"].size
+        ps.n_patches = P
+        for k in dts:
+            setattr(ps, k, _ptr(held[k])[0] if (dev[0] or held[k].size) else None)
+        p = params or default_atlas_params()
+        res, st = AtlasSet(), AtlasStats()
+        self._keep["atlas"] = held
+        rc = self.L.mvs_ctx_texture_atlases(self.h, C.byref(ps), 1 if dev[0] else 0, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        stats = {k: int(getattr(st, k)) for k in ATLAS_COUNTS}
+        stats.update({k: float(getattr(st, k)) for k in ATLAS_MS})
+        if rc != 0:
+            try:
+                _check(self.L, rc)
+            except MvsError as e:
+                e.stats = stats
+                raise
+        A, NL, NM, NP = int(res.n_atlases), int(res.n_listed), int(res.n_merged), int(res.n_pixels)
+        shapes = dict(atlas_size=(A, np.uint32), atlas_pix_ptr=(A + 1, np.uint64), image=(3 * NP, np.uint8), patch_atlas=(P, np.uint32), patch_pos=(2 * P, np.int32),
+                      patch_order=(P, np.uint32), face_ptr=(A + 1, np.uint32), faces=(NL, np.uint32), texcoords=(6 * NL, np.float32), tc_ptr=(A + 1, np.uint32),
+                      texcoords_merged=(2 * NM, np.float32), texcoord_ids=(3 * NL, np.uint32))
+        if on_device:
+            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
+        out = {}
+        for k, (n, dt) in shapes.items():
+            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
+        self.L.mvs_atlas_set_free(C.byref(res))
+        out["image"] = out["image"].reshape(NP, 3); out["patch_pos"] = out["patch_pos"].reshape(P, 2); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2)
+        out["texcoords_merged"] = out["texcoords_merged"].reshape(NM, 2); out["texcoord_ids"] = out["texcoord_ids"].reshape(NL, 3)
+        return out, stats
+
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
         a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
@@ -660,6 +731,21 @@ def default_lsl_params(**kw):
     return p
 
 
+def default_atlas_params(**kw):
+    """mvs_atlas_default_params (max_pixels 0 = no cap) with overrides"""
+    p = AtlasParams()
+    load_library().mvs_atlas_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def atlas_view(arrays, a):
+    """atlas a of Context.texture_atlases' host arrays: its (size, size, 3) uint8 image as a view of the packed array"""
+    s = int(arrays["atlas_size"][a]); o = int(arrays["atlas_pix_ptr"][a])
+    return arrays["image"][o:o + s * s].reshape(s, s, 3)
+
+
 def patch_view(arrays, i):
     """patch i of Context.texture_patches' host arrays: (image (h, w, 3), validity (h, w), blending (h, w)) as views of the packed arrays"""
     w, h = int(arrays["box"][i, 2]), int(arrays["box"][i, 3])
@@ -699,6 +785,27 @@ def local_seam_leveling(scene, labels, params=None, ctx=None):
         host, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"])
         host.update(out)
         return host, stats
+    finally:
+        if own:
+            ctx.close()
+
+
+def texture_atlases(scene, labels, params=None, ctx=None):
+    """texrecon.cpp:169-195 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with its
+    adjustments (row f6), local seam leveling (row f7) and the texture atlases (row f8), the patches staying on the device in
+    between.  Returns (arrays, stats) of Context.texture_atlases."""
+    own = ctx is None
+    ctx = ctx or Context()
+    try:
+        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
+        ctx.set_views(scene.cams, scene.images)
+        a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        gsl, _ = ctx.global_seam_leveling(a, b, lab, on_device=True)
+        dev, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        lsl, _ = ctx.local_seam_leveling(a, b, lab, dev, on_device=True)
+        dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
+        return ctx.texture_atlases(dev, params)
     finally:
         if own:
             ctx.close()

@@ -1,0 +1,210 @@
+"""Row f8 without a GPU: the CPU model (tests/tools/atlas_model.cpp, DESIGN.md section 4 "Texture atlases") equals what upstream's compiled
+generate_texture_atlases left for the recorded cases (tests/golden/texture_atlas_pins.npz) bit for bit; the numpy statements of the
+order-free forms the device uses (packing: the first remaining patch after the cursor that fits; padding: levels of chessboard
+distance) equal the model's list and set loops on the pins and on random crafted sets; the model's counters show that every
+situation the definition names occurs; the library exports the entry points."""
+import os
+
+import numpy as np
+import pytest
+
+import mvs_texturing_amd as M
+import atlas_model as AM
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "texture_atlas_pins.npz")
+PACK_PINS = ("s256", "s512", "s1024", "s2048", "s4096", "s8192", "waits", "break_widest", "ties", "many")
+PIXEL_PINS = (("p256", 256), ("p512", 512), ("p1024", 1024))
+UP_KEYS = ("atlas_size", "image", "faces", "face_ptr", "tc_ptr", "texcoords_merged", "texcoord_ids")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _model_built():
+    AM.build()
+
+
+def _raw(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32).ravel() if a.dtype == np.float32 else a.ravel()
+
+
+def pack_pins():
+    """(name, wh, upstream's atlas_size, patch_atlas, patch_pos (n, 2), patch_order)"""
+    z = np.load(GOLDEN)
+    for name in PACK_PINS:
+        g = lambda k: z["pack__%s__%s" % (name, k)]
+        yield name, g("wh").astype(np.int32), g("atlas_size").astype(np.uint32), g("patch_atlas").astype(np.uint32), g("patch_pos").astype(np.int32), g("patch_order")
+
+
+def pixel_pins():
+    """(name, atlas side, patch set, upstream's arrays)"""
+    z = np.load(GOLDEN)
+    for name, side in PIXEL_PINS:
+        pa = {k: z["pix__%s__in_%s" % (name, k)] for k in AM.PATCH_ARRAYS}
+        pa["image"] = pa["image"].astype(np.float32)                    # stored as float16, exactly
+        yield name, side, pa, {k: z["pix__%s__out_%s" % (name, k)] for k in UP_KEYS}
+
+
+def crafted_sets():
+    """random crafted patch sets: holes, valid pixels on the frames' edges (so that rings cross into neighbours), out-of-range colours
+    and a NaN, repeated corners; several atlases in the last"""
+    rng = np.random.default_rng(8)
+    out = {}
+    out["small"] = AM.craft(rng, [(40, 30), (25, 25), (30, 12), (9, 9), (50, 8), (17, 23), (3, 3), (1, 1), (12, 12), (12, 12)], hole=0.2)
+    out["no_edges"] = AM.craft(rng, [(20, 20)] * 6 + [(5, 9)] * 5, hole=0.1, edge_valid=False)
+    out["wide_512"] = AM.craft(rng, [(300, 16), (40, 30), (9, 9), (50, 8), (2, 2)], hole=0.15)
+    out["two_atlases"] = AM.craft(rng, [(60, 60)] * 5 + [(300, 9)] + [(50, 50)] * 10 + [(600, 4)] + [(20, 20)] * 20, hole=0.3, faces_per_patch=2)
+    out["odd_validity"] = AM.craft(rng, [(30, 30), (31, 17), (8, 40)], hole=0.3)
+    v = out["odd_validity"]["validity"]; v[rng.random(v.size) < 0.1] = 7          # neither 0 nor 255: padded in sweep 0 only
+    out["no_faces"] = AM.craft(rng, [(10, 10), (20, 5), (6, 6)], faces_per_patch=0)
+    return out
+
+
+def test_model_equals_upstream_on_the_packing_pins():
+    total = dict.fromkeys(AM.COUNTERS, 0)
+    sizes = set()
+    for name, wh, size, atlas, pos, order in pack_pins():
+        st, got, stats, cnt, _ = AM.run(AM.set_from_sizes(wh), pack_only=True)
+        assert st == 0
+        assert np.array_equal(got["atlas_size"], size) and np.array_equal(got["patch_atlas"], atlas), name
+        assert np.array_equal(got["patch_pos"].reshape(-1, 2), pos) and np.array_equal(got["patch_order"], order), name
+        assert stats["atlases"] == len(size) and stats["pixels"] == int((size.astype(np.int64) ** 2).sum())
+        for k in total:
+            total[k] += cnt[k]
+        sizes |= set(int(s) for s in size)
+        if name == "s256":
+            assert cnt["halvings"] == 4 and cnt["pref_jumps"] == 1            # 8192 -> 4096, then halved four times
+        if name == "s8192":
+            assert cnt["pref_jumps"] == 0 and list(size) == [8192]
+        if name == "waits":
+            assert cnt["waits_too_wide"] >= 1 and len(size) == 2 and atlas[np.flatnonzero(wh[:, 0] == 600)[0]] == 1
+        if name == "break_widest":
+            assert cnt["break_is_widest"] >= 1
+        if name == "ties":
+            assert cnt["ties"] >= 8
+        if name == "many":
+            assert len(wh) == 3000 and len(size) > 10 and stats["free_rects_peak"] > 100
+    assert sizes == set(AM.SIZES)
+    for k in ("pref_jumps", "halvings", "breaks", "break_is_widest", "waits_too_wide", "ties", "refused_inserts"):
+        assert total[k] >= 1, (k, total)
+
+
+def test_tie_order_is_higher_id_first():
+    wh = np.array([(30, 20), (20, 30), (25, 24), (24, 25)], np.int32)
+    _, got, _, _, _ = AM.run(AM.set_from_sizes(wh), pack_only=True)
+    assert list(got["patch_order"]) == [3, 2, 1, 0]
+
+
+def test_order_free_packing_equals_the_model():
+    rng = np.random.default_rng(3)
+    cases = [(name, wh) for name, wh, *_ in pack_pins()]
+    cases.append(("random", np.maximum(2, np.exp(rng.normal(np.log(30), 0.8, (700, 2)))).astype(np.int32)))
+    cases.append(("random_wide", np.stack([rng.integers(1, 900, 150), rng.integers(1, 40, 150)], 1).astype(np.int32)))
+    for name, wh in cases:
+        st, want, _, _, _ = AM.run(AM.set_from_sizes(wh), pack_only=True)
+        assert st == 0
+        size, atlas, pos, order = AM.rule_pack(wh)
+        assert np.array_equal(size, want["atlas_size"]) and np.array_equal(atlas, want["patch_atlas"]), name
+        assert np.array_equal(pos, want["patch_pos"].reshape(-1, 2)) and np.array_equal(order, want["patch_order"]), name
+
+
+def test_bin_alone_first_minimum_and_split():
+    out = AM.bin_insert(256, [(100, 50), (100, 50), (156, 50), (300, 1), (256, 156)])
+    assert out[0].tolist() == [1, 0, 0] and out[3].tolist() == [0, 0, 0]
+    assert out[:, 0].tolist() == [1, 1, 1, 0, 1]
+
+
+def test_model_equals_upstream_on_the_pixel_pins():
+    foreign = 0
+    for name, side, pa, want in pixel_pins():
+        st, got, stats, cnt, _ = AM.run(pa)
+        assert st == 0 and list(got["atlas_size"]) == [side], name
+        for k in UP_KEYS:
+            assert got[k].size == want[k].size and np.array_equal(_raw(got[k]), _raw(want[k])), (name, k)
+        assert stats["padded_pixels"] > 0 and cnt["outer_ring"] > 0, name
+        assert np.array_equal(_raw(got["texcoords_merged"].reshape(-1, 2)[got["texcoord_ids"] + 0]), _raw(got["texcoords"])), name   # one atlas: ids index the merged list
+        assert (pa["validity"] == 0).any() and stats["merged_texcoords"] < got["texcoord_ids"].size
+        foreign += cnt["foreign_fill"]
+    assert foreign >= 3                     # a patch's outer ring reached into its neighbour's rectangle
+
+
+def _distance(valid, cap):
+    """chessboard distance to the nearest valid pixel, 255 beyond `cap`"""
+    d = np.where(valid, 0, 255).astype(np.int64)
+    cur = valid.copy()
+    for k in range(1, cap + 1):
+        grown = cur.copy()
+        for j in (-1, 0, 1):
+            for i in (-1, 0, 1):
+                grown |= AM._shift(cur, i, j, False)
+        d[grown & ~cur] = k
+        cur = grown
+    return d
+
+
+def _check_rules(name, pa):
+    st, got, stats, cnt, _ = AM.run(pa)
+    assert st == 0, name
+    filled = 0
+    for a in range(len(got["atlas_size"])):
+        img, mask = AM.compose(pa, got, a)
+        pad = int(got["atlas_size"][a]) >> 7
+        out, lev = AM.rule_pad(img, mask, pad)
+        assert np.array_equal(out, AM.atlas_view(got, a)), (name, a)
+        filled += int(((lev > 0) & (lev < 255)).sum())
+        if set(np.unique(mask)) <= {0, 255}:                      # the levels ARE the chessboard distance to the nearest valid pixel, capped
+            assert np.array_equal(_distance(mask == 255, pad + 1), lev), (name, a)
+    assert filled == stats["padded_pixels"], name
+    return stats, cnt
+
+
+def test_order_free_padding_and_composition_equal_the_model():
+    for name, side, pa, _ in pixel_pins():
+        _check_rules(name, pa)
+    for name, pa in crafted_sets().items():
+        stats, cnt = _check_rules(name, pa)
+        if name == "two_atlases":
+            assert stats["atlases"] == 2 and cnt["waits_too_wide"] >= 1
+        if name == "no_edges":
+            assert cnt["foreign_fill"] == 0
+
+
+def test_float_to_byte_definition():
+    x = np.array([np.nan, -1.0, -0.0, 0.0, 0.6 / 255, 0.4 / 255, 1.0, 1.5, 254.6 / 255, np.inf, -np.inf, 0.5], np.float32)
+    pa = dict(box=np.array([[0, 0, len(x), 1]], np.int32), face_ptr=np.zeros(2, np.uint32), faces=np.zeros(0, np.uint32), texcoords=np.zeros(0, np.float32),
+              pix_ptr=np.array([0, len(x)], np.uint64), image=np.repeat(x, 3), validity=np.full(len(x), 255, np.uint8))
+    st, got, _, _, _ = AM.run(pa)
+    row = AM.atlas_view(got, 0)[2, 2:2 + len(x), 0]
+    assert row.tolist() == [0, 0, 0, 0, 1, 0, 255, 255, 255, 255, 0, 128]
+
+
+def test_refusals_and_the_empty_set():
+    assert AM.run(AM.set_from_sizes([(8064, 4)]), pack_only=True)[0] == AM.UNSUPPORTED
+    assert AM.run(AM.set_from_sizes([(4, 8064)]), pack_only=True)[0] == AM.UNSUPPORTED
+    st, got, stats, _, _ = AM.run(AM.set_from_sizes([(8063, 4)]), pack_only=True)
+    assert st == 0 and list(got["atlas_size"]) == [8192]
+    st, got, stats, _, _ = AM.run(AM.set_from_sizes(np.zeros((0, 2), np.int32)))
+    assert st == 0 and stats["atlases"] == 0 and got["image"].size == 0 and list(got["atlas_pix_ptr"]) == [0]
+
+
+def test_non_finite_texcoords_are_refused():
+    for bad in (np.nan, np.inf, -np.inf, 3.0e38):
+        pa = AM.craft(np.random.default_rng(1), [(10, 10), (20, 5)])
+        pa["texcoords"][7] = bad                                   # (3.0e38 + offset) / size is finite: not refused
+        st = AM.run(pa)[0]
+        assert st == (0 if bad == 3.0e38 else AM.UNSUPPORTED), bad
+
+
+def test_library_exports_and_ctypes_table():
+    import ctypes as C
+    assert os.path.exists(M.lib_path()), "build the library first (__graft_entry__.build)"
+    raw = C.CDLL(M.lib_path())
+    L = M.load_library()
+    for name in ("mvs_ctx_texture_atlases", "mvs_atlas_default_params", "mvs_atlas_set_free"):
+        assert hasattr(raw, name), name
+        assert name in L._declared and getattr(L, name).argtypes is not None, name
+    p = M.default_atlas_params()
+    assert p.max_pixels == 0
+    assert M.default_atlas_params(max_pixels=5).max_pixels == 5
+    assert callable(M.texture_atlases) and callable(M.atlas_view) and hasattr(M.Context, "texture_atlases")
+    from mvs_texturing_amd import viewsel
+    assert viewsel.ATLAS_COUNTS == AM.STATS

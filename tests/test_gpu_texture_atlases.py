@@ -1,0 +1,222 @@
+"""Row f8 on the GPU: Context.texture_atlases equals the CPU model (tests/tools/atlas_model.cpp: upstream's loops and containers,
+DESIGN.md section 4 "Texture atlases") bit for bit on every output array and every counter -- the suite's scenes (labels from the
+library's own view selection, patches from its rows f5 - f7), shuffled meshes, the crafted sets of tests/test_atlas_model.py, config 2,
+and the cases of tests/golden/texture_atlas_pins.npz against what upstream's compiled generate_texture_atlases left for them."""
+import numpy as np
+import pytest
+
+import mvs_texturing_amd as M
+import atlas_model as AM
+from conftest import get_scene
+from test_atlas_model import UP_KEYS, crafted_sets, pack_pins, pixel_pins
+
+pytestmark = pytest.mark.gpu
+
+KEYS = tuple(AM.ARRAYS)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _model_built():
+    AM.build()
+
+
+def _ctx(s):
+    c = M.Context(0)
+    c.set_mesh(s.verts, s.faces, s.normals)
+    c.set_views(s.cams, s.images)
+    return c
+
+
+_labels_cache = {}
+
+
+def _library_labels(name, s):
+    if name not in _labels_cache:
+        c = _ctx(s)
+        c.data_costs(M.Settings())
+        _labels_cache[name], _ = c.view_selection(s.adj_ptr, s.adj)
+        c.close()
+    return _labels_cache[name]
+
+
+def _raw(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32).ravel() if a.dtype == np.float32 else a.ravel()
+
+
+def _same(got, want, what="", keys=KEYS):
+    for k in keys:
+        assert got[k].size == want[k].size and np.array_equal(_raw(got[k]), _raw(want[k])), (what, k)
+
+
+def _compare(pa, ctx=None, what=""):
+    """one GPU run on the patch set pa against the model; returns (gpu arrays, gpu stats, model counters)"""
+    st, want, wst, cnt, _ = AM.run(pa)
+    assert st == 0
+    c = ctx or M.Context(0)
+    try:
+        got, gst = c.texture_atlases(pa)
+    finally:
+        if ctx is None:
+            c.close()
+    _same(got, want, what)
+    for k in AM.STATS:
+        assert gst[k] == wst[k], (what, k, gst[k], wst[k])
+    return got, gst, cnt
+
+
+def _pipeline_patches(s, labels):
+    """rows f5 - f7 of the library on the host: row f7's image and validity merged over row f6's set"""
+    c = _ctx(s)
+    gsl, _ = c.global_seam_leveling(s.adj_ptr, s.adj, labels)
+    pa, _ = c.texture_patches(s.adj_ptr, s.adj, labels, gsl["corner_adjust"])
+    lsl, _ = c.local_seam_leveling(s.adj_ptr, s.adj, labels, pa)
+    c.close()
+    pa = dict(pa); pa.update(image=lsl["image"], validity=lsl["validity"])
+    return pa
+
+
+@pytest.mark.parametrize("name", ["tiny", "bumpy", "oddw", "mixed", "spiky", "close", "manyviews"])
+def test_scenes_equal_the_model(name):
+    s = get_scene(name)
+    labels = _library_labels(name, s)
+    pa = _pipeline_patches(s, labels)
+    got, gst, _ = _compare(pa, what=name)
+    assert gst["atlases"] >= 1 and gst["valid_pixels"] > 0 and gst["padded_pixels"] > 0 and gst["merged_texcoords"] > 0
+    assert gst["merged_texcoords"] < 3 * len(pa["faces"])
+    assert sorted(got["faces"].tolist()) == sorted(pa["faces"].tolist())
+
+
+@pytest.mark.parametrize("name", ["tiny", "bumpy"])
+def test_shuffled_scenes_equal_the_model(name):
+    s = get_scene(name)
+    p = M.synth.permute_scene(s, seed=7)
+    labels = _library_labels(name, s)[p.face_perm]
+    _compare(_pipeline_patches(p, labels), what=name + "/shuffled")
+
+
+def test_crafted_sets_equal_the_model():
+    c = M.Context(0)                                       # neither mesh nor views
+    for name, pa in crafted_sets().items():
+        got, gst, cnt = _compare(pa, ctx=c, what=name)
+        if name == "two_atlases":
+            assert gst["atlases"] == 2 and cnt["waits_too_wide"] >= 1
+        if name == "small":
+            assert cnt["foreign_fill"] > 0
+    c.close()
+
+
+def test_upstream_pins_on_the_gpu():
+    """the recorded cases fed to the GPU directly: upstream's own arrays"""
+    c = M.Context(0)
+    sizes = set()
+    for name, wh, size, atlas, pos, order in pack_pins():
+        pa = AM.set_from_sizes(wh)
+        n = int(pa["pix_ptr"][-1])
+        pa["image"] = np.zeros(3 * n, np.float32); pa["validity"] = np.full(n, 255, np.uint8)
+        got, gst = c.texture_atlases(pa)
+        assert np.array_equal(got["atlas_size"], size) and np.array_equal(got["patch_atlas"], atlas), name
+        assert np.array_equal(got["patch_pos"], pos) and np.array_equal(got["patch_order"], order), name
+        sizes |= set(int(x) for x in size)
+    assert sizes == set(AM.SIZES)
+    for name, side, pa, want in pixel_pins():
+        got, gst = c.texture_atlases(pa)
+        _same(got, want, name, UP_KEYS)
+    c.close()
+
+
+def _device_host(dev, dtype):
+    """a DevArray of the context copied to the host through torch (no copy on the device)"""
+    import torch
+    dt = np.dtype(dtype)
+    n = dev.shape[0]
+    if n == 0:
+        return np.zeros(0, dt)
+
+    class _Dev:
+        __cuda_array_interface__ = {"shape": (n * dt.itemsize,), "typestr": "|u1", "data": (dev.data_ptr(), False), "version": 2}
+    return torch.as_tensor(_Dev(), device="cuda").cpu().numpy().view(dt)
+
+
+def test_host_and_device_inputs_outputs_and_repeat():
+    s = get_scene("bumpy")
+    labels = _library_labels("bumpy", s)
+    pa = _pipeline_patches(s, labels)
+    c = _ctx(s)
+    a, ast, _ = _compare(pa, ctx=c, what="host")
+    b, _ = c.texture_atlases(pa)
+    _same(b, a, "repeat")
+    gsl, _ = c.global_seam_leveling(s.adj_ptr, s.adj, labels, on_device=True)
+    dev, _ = c.texture_patches(s.adj_ptr, s.adj, labels, gsl["corner_adjust"], on_device=True)
+    lsl, _ = c.local_seam_leveling(s.adj_ptr, s.adj, labels, dev, on_device=True)
+    merged = dict(dev); merged.update(image=lsl["image"], validity=lsl["validity"])      # row f7's device output merged over row f6's
+    d, dst = c.texture_atlases(merged)
+    _same(d, a, "device patches")
+    e, est = c.texture_atlases(merged, on_device=True)
+    c.synchronize()
+    host = {k: _device_host(e[k], AM.ARRAYS[k]) for k in KEYS}
+    _same(host, a, "device inputs and outputs")
+    assert est["ms_total"] > 0 and est["ms_pack"] > 0 and est["ms_compose"] > 0 and est["ms_pad"] > 0 and est["ms_texcoords"] > 0
+    for k in AM.STATS:
+        assert est[k] == ast[k], k
+    after = {k: _device_host(merged[k], AM.PATCH_ARRAYS[k]) for k in AM.PATCH_ARRAYS}       # the input was not modified
+    for k in AM.PATCH_ARRAYS:
+        assert np.array_equal(_raw(after[k]), _raw(pa[k])), k
+    c.close()
+    img = M.atlas_view(a, 0)
+    assert img.shape == (int(a["atlas_size"][0]),) * 2 + (3,) and img.dtype == np.uint8
+
+
+def test_max_pixels_refuses_with_stats_filled():
+    pa = crafted_sets()["two_atlases"]
+    c = M.Context(0)
+    with pytest.raises(M.MvsError) as e:
+        c.texture_atlases(pa, M.default_atlas_params(max_pixels=512 * 512 + 1024 * 1024 - 1))
+    assert e.value.status == 7
+    assert e.value.stats["atlases"] == 2 and e.value.stats["pixels"] == 512 * 512 + 1024 * 1024 and e.value.stats["free_rects_peak"] > 1
+    assert e.value.stats["atlases_512"] == 1 and e.value.stats["atlases_1024"] == 1 and e.value.stats["valid_pixels"] == 0
+    got, gst = c.texture_atlases(pa, M.default_atlas_params(max_pixels=512 * 512 + 1024 * 1024))
+    assert gst["atlases"] == 2
+    _compare(pa, ctx=c, what="after the refusal")
+    c.close()
+
+
+def test_over_wide_patch_and_empty_set():
+    c = M.Context(0)
+    for wh in ((8064, 2), (2, 8064)):
+        pa = AM.set_from_sizes([wh, (5, 5)])
+        n = int(pa["pix_ptr"][-1])
+        pa["image"] = np.zeros(3 * n, np.float32); pa["validity"] = np.full(n, 255, np.uint8)
+        assert AM.run(pa, pack_only=True)[0] == AM.UNSUPPORTED
+        with pytest.raises(M.MvsError) as e:
+            c.texture_atlases(pa)
+        assert e.value.status == 7
+    for bad in (np.nan, np.inf):                                      # not finite: merge_texcoords has no order for them
+        pa = crafted_sets()["small"]; pa["texcoords"][7] = bad
+        assert AM.run(pa)[0] == AM.UNSUPPORTED
+        with pytest.raises(M.MvsError) as e:
+            c.texture_atlases(pa)
+        assert e.value.status == 7
+    empty = AM.set_from_sizes(np.zeros((0, 2), np.int32))
+    got, gst = c.texture_atlases(empty)
+    assert gst["atlases"] == 0 and gst["pixels"] == 0 and got["image"].shape == (0, 3) and got["atlas_size"].size == 0
+    assert got["atlas_pix_ptr"].tolist() == [0] and got["face_ptr"].tolist() == [0] and got["tc_ptr"].tolist() == [0]
+    _compare(crafted_sets()["small"], ctx=c, what="after the errors")
+    c.close()
+
+
+def test_module_level_entry():
+    s = get_scene("tiny")
+    labels = _library_labels("tiny", s)
+    got, gst = M.texture_atlases(s, labels)
+    st, want, wst, _, _ = AM.run(_pipeline_patches(s, labels))
+    _same(got, want)
+    assert gst["padded_pixels"] == wst["padded_pixels"]
+
+
+def test_config2_equals_the_model():
+    s = M.synth.make_scene(**M.synth.CONFIGS[2])
+    labels = _library_labels("config2", s)
+    pa = _pipeline_patches(s, labels)
+    got, gst, _ = _compare(pa, what="config 2")
+    assert gst["atlases"] >= 1 and gst["padded_pixels"] > 0
