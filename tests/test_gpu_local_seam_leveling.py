@@ -2,7 +2,9 @@
 DESIGN.md section 4 "Local seam leveling") bit for bit on image, validity and the prepared blending mask and on every counter -- the
 suite's scenes (labels from the library's own view selection, patches from its rows f5 and f6), shuffled meshes, the crafted sets of
 tests/test_local_seam_model.py and config 2; with the default parameters and with max_iterations = 0 (the state before the solve);
-and the patch sets of tests/golden/local_seam_pins.npz against what upstream's compiled local_seam_leveling left for them."""
+the patch sets of tests/golden/local_seam_pins.npz against what upstream's compiled local_seam_leveling left for them; and the
+edge sets of tests/test_local_seam_model.py (skipped pairs, sanitized pixels, an idle channel, the ladder of unknown counts) with
+iteration caps, tolerances and strip widths moved, on the LDS path and in global memory."""
 import numpy as np
 import pytest
 
@@ -11,7 +13,7 @@ import blend_model as BM
 import patch_model as PM
 import seam_model as SM
 from conftest import get_scene
-from test_local_seam_model import crafted_sets, pin_cases
+from test_local_seam_model import EDGE_REACHES, crafted_sets, edge_sets, ladder_sets, mid_cap, pin_cases, unknown_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -142,6 +144,107 @@ def test_global_memory_path_equals_the_model_and_the_lds_path():
     g, labels, pa = crafted_sets()["wide"]                       # patches of 12 000 pixels: global memory under the default threshold
     _, wst, _, _ = _compare(g, labels, pa, what="wide")
     assert wst["patches_global"] >= 1
+
+
+def test_edge_sets_equal_the_model():
+    """the sets of edge_sets(): a skipped pair (one shared vertex, once and twice), the sanitize pass converting pixels, an idle
+    channel, black views and the ladder of unknown counts -- with the default parameters and before the solve"""
+    for name, (g, labels, pa) in edge_sets().items():
+        c = _ctx(g)
+        got, gst, want, wst = _compare(g, labels, pa, ctx=c, what=name)
+        assert gst["hit_max_iterations"] == 0 and gst["outside_frame"] == 0 and gst["demoted"] == 0, (name, gst)
+        raw, rst, before, _ = _compare(g, labels, pa, ctx=c, what=name + "/no solve", max_iterations=0)
+        c.close()
+        kind, key = EDGE_REACHES.get(name, (None, None))
+        if kind == "stats":
+            assert gst[key] > 0 and rst[key] == gst[key], (name, key, gst)
+        elif key == "sanitized":     # no counter on the device: pixels the writes left at 128 that its prepared mask holds as 255
+            assert int(((before["blend_writes"] == 128) & (raw["blending"] == 255)).sum()) > 0, name
+            assert int(((before["blend_writes"] == 128) & (got["blending"] == 255)).sum()) > 0, name
+        else:
+            assert gst["skipped_pairs"] == 0, (name, gst)
+        if name == "black":
+            assert gst["iterations_total"] == 0 and gst["strip_pixels"] > 0 and gst["error_max"] == 0.0
+        if name == "const_channel":      # the idle channel: its unknowns keep the bits the writes left, the other two move
+            st, alone, _, _ = BM.run_scene(g, labels, pa)
+            assert np.all(alone["iters"][:, 1] == 0) and np.all(alone["iters"][:, [0, 2]] > 0)
+            u = raw["blending"] == 255
+            assert np.array_equal(_raw(got["image"].reshape(-1, 3)[u, 1]), _raw(raw["image"].reshape(-1, 3)[u, 1]))
+            assert not np.array_equal(_raw(got["image"].reshape(-1, 3)[u, 0]), _raw(raw["image"].reshape(-1, 3)[u, 0]))
+
+
+def _both_paths(g, labels, pa, ctx, what, **params):
+    """one run under the default LDS threshold and one in global memory: each equals the model, and they equal each other"""
+    lds, lst, want, wst = _compare(g, labels, pa, ctx=ctx, what=what, **params)
+    glob, gst, _, _ = _compare(g, labels, pa, ctx=ctx, what=what + "/global", lds_bytes=0, **params)
+    assert gst["patches_lds"] == 0 and gst["patches_global"] == lst["patches_lds"] + lst["patches_global"], (what, lst, gst)
+    _same(glob, lds, what + ": global == lds")
+    for k in ("iterations_total", "iterations_max", "hit_max_iterations"):
+        assert gst[k] == lst[k], (what, k)
+    assert np.float32(gst["error_max"]).view(np.uint32) == np.float32(lst["error_max"]).view(np.uint32), what
+    return lst, want
+
+
+def test_unknown_ladder_on_both_paths():
+    """1, 2, 255 .. 257, 1023 .. 1025, 2047 .. 2049 and 4158 unknowns in a patch: the tails of the tree's lanes and of the workgroup"""
+    seen = []
+    for name, (g, labels, pa) in ladder_sets().items():
+        c = _ctx(g)
+        lst, _ = _both_paths(g, labels, pa, c, name)
+        c.close()
+        counts = unknown_counts(g, labels, pa)
+        assert lst["patches_lds"] == len(counts) and lst["patches_global"] == 0 and lst["strip_pixels"] == sum(counts), (name, lst)
+        seen += counts
+    assert {1, 2, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049} <= set(seen) and any(n > 4096 and n % 1024 for n in seen), seen
+
+
+def test_iteration_caps_on_both_paths():
+    """max_iterations of 1, 2, 5 and half the set's converged count: the capped iteration is counted and leaves p alone"""
+    sets = {k: crafted_sets()[k] for k in ("grid", "wide")}
+    sets.update({k: v for k, v in edge_sets().items() if k == "const_channel" or k.startswith("unknown_ladder")})
+    for name, (g, labels, pa) in sets.items():
+        st, base, bst, _ = BM.run_scene(g, labels, pa)
+        assert st == 0 and bst["hit_max_iterations"] == 0
+        caps = [1, 2, 5, mid_cap(base["iters"])]
+        if name == "const_channel":      # between the two moving channels of patch 0: one idle, one capped, one converged
+            a, b = sorted(int(v) for v in base["iters"][0, [0, 2]])
+            assert base["iters"][0, 1] == 0 and 0 < a < b
+            caps.append((a + b + 1) // 2)
+        c = _ctx(g)
+        for cap in caps:
+            lst, want = _both_paths(g, labels, pa, c, "%s/cap %d" % (name, cap), max_iterations=cap)
+            assert np.array_equal(want["iters"], np.minimum(base["iters"], cap)), (name, cap)
+            assert lst["hit_max_iterations"] == int((base["iters"] >= cap).any(1).sum()), (name, cap, lst)
+            if bst["iterations_max"] > cap:
+                assert lst["hit_max_iterations"] > 0 and lst["iterations_max"] == cap, (name, cap, lst)
+            if name == "const_channel":
+                assert len(set(want["iters"][0].tolist())) == (3 if cap == caps[-1] else 2), (cap, want["iters"])
+        _compare(g, labels, pa, ctx=c, what=name + "/after the caps")
+        c.close()
+
+
+def test_tolerances_equal_the_model():
+    for name in ("grid", "wide"):
+        g, labels, pa = crafted_sets()[name]
+        c = _ctx(g)
+        its = [_compare(g, labels, pa, ctx=c, what="%s/tolerance %g" % (name, tol), tolerance=tol)[1]["iterations_max"] for tol in (1e-3, 1e-5, 1e-6)]
+        c.close()
+        assert 0 < its[0] < its[1] < its[2], (name, its)
+
+
+def test_strip_widths_equal_the_model():
+    for name in ("wide", "grid"):
+        g, labels, pa = crafted_sets()[name]
+        c = _ctx(g)
+        strips = {}
+        for sw in (0, 1, 3, 250):
+            strips[sw] = _compare(g, labels, pa, ctx=c, what="%s/strip_width %d" % (name, sw), strip_width=sw)[1]["strip_pixels"]
+        assert strips[0] == 0 and strips[1] < strips[3] < strips[250], (name, strips)          # width 0: no strip, nothing to solve
+        with pytest.raises(M.MvsError) as e:
+            c.local_seam_leveling(g.adj_ptr, g.adj, labels, pa, M.default_lsl_params(strip_width=251))
+        assert e.value.status == 1                                        # MVS_ERR_INVALID
+        _compare(g, labels, pa, ctx=c, what=name + "/after the refused width")
+        c.close()
 
 
 def _device_host(dev, dtype):

@@ -7,7 +7,7 @@ import pytest
 import mvs_texturing_amd as M
 import seam_model as SM
 from conftest import get_scene
-from test_seam_model import PLANTED_RATIO
+from test_seam_model import CAPS, PLANTED_RATIO, TOLERANCES
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def _compare(s, labels, ctx=None, **kw):
     c = ctx or _ctx(s)
     try:
         got, gst = c.global_seam_leveling(s.adj_ptr, s.adj, np.ascontiguousarray(labels, np.uint32),
-                                          M.default_gsl_params(**({"tolerance": kw["tolerance"]} if "tolerance" in kw else {})))
+                                          M.default_gsl_params(**{k: kw[k] for k in ("tolerance", "max_iterations") if k in kw}))
         sysg = c.gsl_system()
     finally:
         if ctx is None:
@@ -104,6 +104,43 @@ def test_crafted_labelings_and_meshes():
     got, gst = c.global_seam_leveling(g.adj_ptr, g.adj, np.zeros(len(g.faces), np.uint32))    # all labels 0: empty outputs
     assert gst["x_rows"] == 0 and len(got["x_adjust"]) == 0 and got["corner_adjust"].shape == (len(g.faces), 3, 3) and not np.any(got["corner_adjust"])
     c.close()
+
+
+def _caps_and_tolerances(s, labels, **kw):
+    """every cap of test_seam_model.CAPS and both tolerances on ONE context, then an uncapped run on it: nothing of a cut-short replay
+    of the captured graph (the device's done word, the ping-pong state, p) leaks into the next call.  kw: the tolerance of the capped
+    and uncapped runs where it is not the default.  Returns the uncapped iterations."""
+    c = _ctx(s)
+    try:
+        _, base, _ = _compare(s, labels, ctx=c, **kw)
+        default = base["iterations"]
+        for cap in CAPS:
+            _, gst, _ = _compare(s, labels, ctx=c, max_iterations=cap, **kw)
+            assert gst["iterations"] == [min(cap, d) for d in default], (cap, gst["iterations"], default)
+        for tol in TOLERANCES:
+            _, gst, _ = _compare(s, labels, ctx=c, tolerance=tol)
+            assert max(gst["iterations"]) < 1000
+        _, again, _ = _compare(s, labels, ctx=c, **kw)
+        assert again["iterations"] == default and np.array_equal(_bits(again["error"]), _bits(base["error"]))
+    finally:
+        c.close()
+    return default
+
+
+@pytest.mark.parametrize("name", ["random", "blocks"])
+def test_iteration_caps_around_the_graph_replay_and_tolerances(name):
+    """caps inside (1, 15, 17, 31, 33), at the end of (16, 32) and before (0) the replays of 16 captured iterations"""
+    s = get_scene("tiny")
+    default = _caps_and_tolerances(s, SM.crafted_labelings(s)[name])
+    assert min(default) > max(CAPS), default                              # every cap binds on every channel
+
+
+def test_iteration_caps_with_a_single_reduction_block():
+    g = SM.grid_scene()
+    _, gst, _ = _compare(g, SM.grid_labels(g))
+    assert 0 < gst["x_rows"] <= 256                                       # one tile: level two of the tree sums one partial
+    default = _caps_and_tolerances(g, SM.grid_labels(g), tolerance=1e-7)  # 18 to 22 iterations at the default tolerance: below the later caps
+    assert min(default) > max(CAPS), default
 
 
 def test_host_and_device_inputs_and_repeat():

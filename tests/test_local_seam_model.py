@@ -100,6 +100,132 @@ def crafted_sets():
     return out
 
 
+LADDER_BASE = dict(n=6, W=128, H=80)     # two patches of about 80 x 82 pixels and 4091 / 4158 unknowns: both fit the LDS tier
+LADDER = ((1, 2), (255, 256), (257, 1023), (1024, 1025), (2047, 2048), (2049, None))      # unknowns wanted per patch; None: all of them
+# what each set of edge_sets() is made to reach: ("stats" | "counters", name), or None where the solve's own arrays say it
+EDGE_REACHES = {"skipped_pair": ("stats", "skipped_pairs"), "skipped_pair_twice": ("stats", "skipped_pairs"),
+                "sanitized_vertex": ("counters", "sanitized"), "sanitized_input": ("counters", "sanitized")}
+
+
+def _with_adjacency(g, f, a):
+    """a copy of the scene with one symmetric adjacency entry f <-> a appended to both faces' lists"""
+    import copy
+    lists = [g.adj[g.adj_ptr[i]:g.adj_ptr[i + 1]].tolist() for i in range(len(g.faces))]
+    lists[f].append(a); lists[a].append(f)
+    s = copy.copy(g)
+    s.adj_ptr = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.uint32)
+    s.adj = np.array([x for l in lists for x in l], np.uint32)
+    return s
+
+
+def _with_images(g, edit):
+    import copy
+    s = copy.copy(g)
+    s.images = [np.ascontiguousarray(edit(im.copy())) for im in g.images]
+    return s
+
+
+def unknown_pixels(mask):
+    """flat row-major indices of the unknowns of a prepared mask (h, w): 255, off the frame's edge, no 4-neighbour of mask 0"""
+    m = np.asarray(mask)
+    u = np.zeros(m.shape, bool)
+    u[1:-1, 1:-1] = (m[1:-1, 1:-1] == 255) & (m[1:-1, :-2] != 0) & (m[1:-1, 2:] != 0) & (m[:-2, 1:-1] != 0) & (m[2:, 1:-1] != 0)
+    return np.flatnonzero(u.ravel())
+
+
+def unknown_counts(scene, labels, pa, **params):
+    """per patch, from the model's prepared mask through its per-patch entry"""
+    st, out, _, _ = BM.run_scene(scene, labels, pa, max_iterations=0, **params)
+    assert st == 0
+    return [BM.solve(BM.patch(pa, out, i)[2], BM.patch(pa, pa, i)[0], BM.patch(pa, pa, i)[0], max_iterations=0)[3][0] for i in range(len(pa["label"]))]
+
+
+def _ladder_set(g, labels, pa, wanted):
+    """the patch set with all but the first wanted[i] unknowns (row-major) of patch i fixed: their input blending becomes 64, which
+    item 7 passes through, item 8 keeps as a fixed value and no neighbour is demoted by (64 is not 0)"""
+    st, out, _, _ = BM.run_scene(g, labels, pa, max_iterations=0)
+    assert st == 0
+    pa = dict(pa); bl = pa["blending"].copy()
+    for i, n in enumerate(wanted):
+        if n is None:
+            continue
+        idx = unknown_pixels(BM.patch(pa, out, i)[2])
+        assert len(idx) >= n, (i, len(idx), n)
+        bl[int(pa["pix_ptr"][i]) + idx[n:]] = 64
+    pa["blending"] = bl
+    return pa
+
+
+def edge_sets():
+    """name -> (scene, labels, patch set): the situations of the definition that crafted_sets() does not reach -- a listed pair that
+    shares one vertex (once, and twice through a face with a repeated vertex id), the sanitize pass of item 7 converting pixels (after
+    a vertex moved into the strip, and from a 128 in the input), a channel that is idle from the start beside two that iterate, black
+    views, and patches whose unknown counts sit on and beside the edges of the reduction tree (LADDER)."""
+    out = {}
+    g, labels = crafted_set()["grid"]
+    pa = patches_of(g, labels)
+    faces = g.faces.astype(np.int64)
+    sets = [set(f.tolist()) for f in faces]
+    near = lambda f: set(g.adj[g.adj_ptr[f]:g.adj_ptr[f + 1]].tolist())
+    f, a = next((f, a) for f in range(len(faces)) for a in range(f + 1, len(faces))
+                if labels[f] and labels[a] and labels[f] != labels[a] and len(sets[f] & sets[a]) == 1 and a not in near(f))
+    out["skipped_pair"] = (_with_adjacency(g, f, a), labels, pa)
+    # a face (va, va, vb) on an edge inside one label region whose end va lies on the seam, listed against a face of the other label
+    # that holds va and not vb: upstream's double loop collects va twice
+    import copy
+    labels_at = lambda v: {int(labels[k]) for k in range(len(faces)) if v in sets[k]}
+    va, vb = next((int(u), int(v)) for tri in faces for u in tri for v in tri if u != v and len(labels_at(u)) == 2 and len(labels_at(v)) == 1)
+    inner = labels_at(vb).pop()
+    other = next(k for k in range(len(faces)) if va in sets[k] and labels[k] != inner)
+    d = copy.copy(g)
+    d.faces = np.ascontiguousarray(np.concatenate([g.faces, np.array([[va, va, vb]], g.faces.dtype)]))
+    d.normals = np.ascontiguousarray(np.concatenate([g.normals, g.normals[:1]]))
+    d.adj_ptr, d.adj = SM.face_adjacency(d.faces)
+    dl = np.concatenate([labels, [inner]]).astype(np.uint32)
+    out["skipped_pair_twice"] = (_with_adjacency(d, other, len(faces)), dl, patches_of(d, dl))
+    # one seam vertex of patch 0 moved to the middle of its frame (every corner of it in the patch's list): its pixel and the ends of its
+    # lines land among 255s
+    box = pa["box"].reshape(-1, 4)
+    e0 = int(pa["face_ptr"][1])
+    ids = faces[pa["faces"][:e0]]
+    seam = sorted(set(ids.ravel().tolist()) & set(faces[pa["faces"][e0:]].ravel().tolist()))
+    for v in seam:                                              # the first seam vertex whose lines then run diagonally somewhere: a 128 between four 255s
+        tc = pa["texcoords"].reshape(-1, 3, 2).copy()
+        tc[:e0][ids == v] = np.float32([box[0, 2] / 2.0, box[0, 3] / 2.0])
+        pv = dict(pa); pv["texcoords"] = tc.reshape(-1)
+        if BM.run_scene(g, labels, pv, max_iterations=0)[3]["sanitized"] > 0:
+            break
+    out["sanitized_vertex"] = (g, labels, pv)
+    # a single 128 in the input whose four neighbours stay 255 after the writes
+    st, res, _, _ = BM.run_scene(g, labels, pa, max_iterations=0)
+    assert st == 0
+    bw = BM.patch(pa, dict(image=res["after_writes"], validity=pa["validity"], blending=res["blend_writes"]), 0)[2]
+    ok = np.zeros(bw.shape, bool)
+    ok[1:-1, 1:-1] = (bw[1:-1, 1:-1] == 255) & (bw[1:-1, :-2] == 255) & (bw[1:-1, 2:] == 255) & (bw[:-2, 1:-1] == 255) & (bw[2:, 1:-1] == 255)
+    pi = dict(pa); bl = pa["blending"].copy()
+    bl[np.flatnonzero(ok.ravel())[int(ok.sum()) // 2]] = 128      # patch 0 starts at pixel 0
+    pi["blending"] = bl
+    out["sanitized_input"] = (g, labels, pi)
+
+    def green77(im):
+        im[..., 1] = 77
+        return im
+    c = _with_images(g, green77)                                # channel 1 constant: no seam in it, so it never iterates
+    out["const_channel"] = (c, labels, patches_of(c, labels, adjust=False))
+    b = _with_images(g, lambda im: np.zeros_like(im))
+    out["black"] = (b, labels, patches_of(b, labels, adjust=False))
+    g = SM.grid_scene(**LADDER_BASE)
+    labels = SM.grid_labels(g)
+    pa = patches_of(g, labels)
+    for wanted in LADDER:
+        out["unknown_ladder_%s_%s" % wanted] = (g, labels, _ladder_set(g, labels, pa, wanted))
+    return out
+
+
+def ladder_sets():
+    return {k: v for k, v in edge_sets().items() if k.startswith("unknown_ladder")}
+
+
 def suite_sets():
     """(name, scene, labels, patch set) on suite scenes with crafted labelings (the library's own labels need a GPU)"""
     for name, keys in (("tiny", ("random", "blocks", "random_with_unseen")), ("bumpy", ("blocks",))):
@@ -379,6 +505,133 @@ def test_fixed_pixels_keep_their_bits_and_patches_do_not_couple():
             x, it, err, _ = BM.solve(mask, orig, after)
             assert np.array_equal(_bits(x), _bits(img)), (name, i)
             assert np.array_equal(it, out["iters"][i]) and np.array_equal(_bits(err), _bits(out["err"][i])), (name, i)
+
+
+def mid_cap(iters):
+    """a cap in the middle of a set's converged iteration counts (at least 1)"""
+    return max(1, int(np.max(iters)) // 2)
+
+
+def test_edge_sets_equal_the_order_free_rules_and_reach_their_situations():
+    """The second variant of the skipped pair needs a face with a repeated vertex id, (va, va, vb): the row f6 model accepts that mesh
+    (status 0; the face joins the patch of its edge's label), so both variants are kept."""
+    sets = edge_sets()
+    for name, (g, labels, pa) in sets.items():
+        st, out, stats, cnt = BM.run_scene(g, labels, pa, max_iterations=0)
+        assert st == 0, name
+        img, bl = rule_writes(g, labels, pa)
+        assert np.array_equal(_bits(img), _bits(out["after_writes"])), name
+        assert np.array_equal(bl, out["blend_writes"]), name
+        assert np.array_equal(_bits(out["image"]), _bits(out["after_writes"])), name
+        for i in range(len(pa["label"])):
+            _, val, _ = BM.patch(pa, pa, i)
+            blw = BM.patch(pa, dict(image=out["after_writes"], validity=pa["validity"], blending=out["blend_writes"]), i)[2]
+            mask = BM.patch(pa, out, i)[2]
+            assert np.array_equal(BM.rule_prepare_mask(val, blw), mask), (name, i)
+            assert np.array_equal(BM.prepare_mask(val, blw), mask), (name, i)
+        assert np.array_equal(out["validity"], np.where(out["blending"] == 64, 0, BM.flat(pa)["validity"])), name
+        assert stats["outside_frame"] == 0 and stats["demoted"] == 0 and cnt["clamped_idx"] == 0, (name, stats)
+        if name in EDGE_REACHES:
+            kind, key = EDGE_REACHES[name]
+            assert (stats if kind == "stats" else cnt)[key] > 0, (name, key)
+        else:
+            assert stats["skipped_pairs"] == 0 and cnt["sanitized"] == 0, (name, stats, cnt)
+    base = BM.run_scene(*crafted_sets()["grid"], max_iterations=0)[2]
+    for name in ("skipped_pair", "skipped_pair_twice"):               # the listed pair is skipped, not taken as an edge
+        stats = BM.run_scene(*sets[name], max_iterations=0)[2]
+        assert stats["skipped_pairs"] == 1 and stats["seam_edges"] == base["seam_edges"], (name, stats)
+    g, labels, pa = sets["skipped_pair_twice"]
+    assert len(set(g.faces[-1].tolist())) == 2 and len(g.faces) - 1 in pa["faces"]
+    assert BM.run_scene(*sets["sanitized_input"], max_iterations=0)[3]["sanitized"] == 1
+    # the sanitized pixels are 255 in the prepared mask and unknowns of the solve
+    for name in ("sanitized_vertex", "sanitized_input"):
+        st, out, stats, cnt = BM.run_scene(*sets[name], max_iterations=0)
+        assert int(((out["blend_writes"] == 128) & (out["blending"] == 255)).sum()) == cnt["sanitized"], name
+
+
+def test_const_channel_and_black_views_idle_in_different_ways():
+    sets = edge_sets()
+    g, labels, pa = sets["const_channel"]
+    st, out, stats, _ = BM.run_scene(g, labels, pa)
+    assert st == 0 and stats["hit_max_iterations"] == 0
+    assert np.all(out["iters"][:, 1] == 0) and np.all(out["iters"][:, [0, 2]] > 0), out["iters"]
+    assert np.all(out["err"][:, 1] > 0)                              # |rhs|^2 is not 0 (rounding): the channel stops on |r0|^2 < threshold
+    assert np.all(out["iters"][:, 0] != out["iters"][:, 2])          # a cap between the two leaves one capped and one converged
+    g, labels, pa = sets["black"]
+    st, out, stats, _ = BM.run_scene(g, labels, pa)
+    assert st == 0 and stats["iterations_total"] == 0 and stats["strip_pixels"] > 0 and stats["error_max"] == 0.0      # |rhs|^2 = 0
+    assert np.array_equal(_bits(out["image"]), _bits(pa["image"]))
+
+
+def test_unknown_ladder_reaches_the_edges_of_the_reduction_tree():
+    """1 and 2 unknowns, and the counts on and beside 256 (the LDS variant's threads), 1024 (the tree's lanes) and 2048; one count
+    above 4096 that is no multiple of 1024"""
+    got = []
+    for name, (g, labels, pa) in ladder_sets().items():
+        counts = unknown_counts(g, labels, pa)
+        st, out, stats, _ = BM.run_scene(g, labels, pa)
+        assert st == 0 and stats["strip_pixels"] == sum(counts) and stats["demoted"] == 0, name
+        assert stats["patches_lds"] == len(counts) and stats["patches_global"] == 0, (name, stats)      # every patch fits the LDS tier
+        got += counts
+    for n in (1, 2, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049):
+        assert n in got, (n, got)
+    assert any(n > 4096 and n % 1024 for n in got), got
+
+
+def _fixed_and_uncoupled(name, g, labels, pa, **params):
+    """fixed pixels keep their bits; the per-patch entry on one patch alone == its bits inside the set.  Returns (arrays, stats)."""
+    st, out, stats, _ = BM.run_scene(g, labels, pa, **params)
+    assert st == 0, name
+    fixed = out["blending"] != 255
+    assert np.array_equal(_bits(out["image"][fixed]), _bits(out["after_writes"][fixed])), name
+    assert stats["strip_pixels"] + stats["demoted"] == int((out["blending"] == 255).sum()), name
+    assert stats["fixed_pixels"] == int(np.isin(out["blending"], (64, 128)).sum()), name
+    for i in range(len(pa["label"])):
+        img, _, mask = BM.patch(pa, out, i)
+        orig = BM.patch(pa, pa, i)[0]
+        after = BM.patch(pa, dict(image=out["after_writes"], validity=out["validity"], blending=out["blending"]), i)[0]
+        x, it, err, _ = BM.solve(mask, orig, after, **params)
+        assert np.array_equal(_bits(x), _bits(img)), (name, i, params)
+        assert np.array_equal(it, out["iters"][i]) and np.array_equal(_bits(err), _bits(out["err"][i])), (name, i, params)
+    return out, stats
+
+
+def test_caps_bind_and_patches_do_not_couple_under_them():
+    sets = dict(edge_sets())
+    sets.update({k: crafted_sets()[k] for k in ("grid", "wide")})
+    bound = 0
+    for name, (g, labels, pa) in sets.items():
+        base, bst = _fixed_and_uncoupled(name, g, labels, pa)
+        assert bst["hit_max_iterations"] == 0, (name, bst)
+        for cap in (1, 2, mid_cap(base["iters"])):
+            out, stats = _fixed_and_uncoupled(name, g, labels, pa, max_iterations=cap)
+            assert np.array_equal(out["iters"], np.minimum(base["iters"], cap)), (name, cap)      # the breaking iteration is not counted
+            want = int((base["iters"] >= cap).any(1).sum())
+            assert stats["hit_max_iterations"] == want, (name, cap, stats)
+            bound += want
+            if name != "black" and cap == 1 and bst["iterations_max"] > 1:
+                assert stats["hit_max_iterations"] > 0 and stats["error_max"] > bst["error_max"], (name, stats)
+    assert bound > 0
+
+
+def test_tolerance_shortens_the_solve():
+    for name in ("grid", "wide"):
+        g, labels, pa = crafted_sets()[name]
+        it = [BM.run_scene(g, labels, pa, tolerance=t)[2]["iterations_max"] for t in (1e-3, 1e-5, 1e-6)]
+        assert 0 < it[0] < it[1] < it[2], (name, it)
+
+
+def test_line_index_clamp_cannot_fire():
+    """item 6: idx = floor(fl(t * float(n - 1))) for t < 1.  The largest such t is 1 - 2^-24, and for every sample count n from 2 to
+    2^25 (the device refuses more than 2^22 samples on one edge) the product stays below n - 1 in fp32: the clamp to n - 2 is dead."""
+    t = np.nextafter(np.float32(1), np.float32(0))
+    assert t < 1 and t.dtype == np.float32
+    step = 1 << 22
+    for lo in range(1, 1 << 25, step):
+        m = np.arange(lo, min(lo + step, 1 << 25), dtype=np.int64)      # n - 1
+        prod = t * m.astype(np.float32)
+        assert prod.dtype == np.float32
+        assert np.all(np.floor(prod).astype(np.int64) <= m - 1), lo
 
 
 def _constant_scene(colour):

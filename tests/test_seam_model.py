@@ -129,6 +129,38 @@ def test_model_recovers_planted_view_offsets(name):
     assert before > 0.05 and after <= PLANTED_RATIO * before, (before, after)
 
 
+# caps inside, at the end of and just after the device's replays of 16 iterations, and tolerances on both sides of the default
+CAPS = (0, 1, 15, 16, 17, 31, 32, 33)
+TOLERANCES = (1e-2, 1e-7)
+
+
+@pytest.mark.parametrize("name", ["random", "blocks"])
+def test_model_under_iteration_caps_and_tolerances(name):
+    s = get_scene("tiny")
+    labels = SM.crafted_labelings(s)[name]
+    st, base, bstats = SM.run_scene(s, labels)
+    default = bstats["iterations"]
+    assert st == 0 and min(default) > max(CAPS), default            # every cap binds on every channel
+    capped = {}
+    for cap in CAPS:
+        st, out, stats = SM.run_scene(s, labels, max_iterations=cap)
+        assert st == 0 and stats["iterations"] == [min(cap, d) for d in default], (cap, stats["iterations"])   # a capped iteration is counted
+        capped[cap] = (out, stats)
+    assert not np.any(capped[0][0]["x_raw"]) and np.all(capped[0][1]["error"] == 1)          # x0 = 0, r0 = Rhs
+    assert np.all(capped[1][1]["error"] > bstats["error"]) and np.all(capped[1][1]["error"] < 1)
+    assert np.all(capped[33][1]["error"] < capped[1][1]["error"])
+    for a, b in zip(CAPS, CAPS[1:]):                                                         # one more iteration moves x
+        assert not np.array_equal(capped[a][0]["x_raw"], capped[b][0]["x_raw"]), (a, b)
+    its = {}
+    for tol in TOLERANCES:
+        st, out, stats = SM.run_scene(s, labels, tolerance=tol)
+        assert st == 0 and max(stats["iterations"]) < 1000
+        # the stop is |r|^2 < fl(tol tol) |Rhs|^2 in fp32: the error is below tol up to a few roundings
+        assert np.all(stats["error"] <= tol * (1 + 1e-5)), (tol, stats["error"])
+        its[tol] = stats["iterations"]
+    assert all(a < d < b for a, d, b in zip(its[1e-2], default, its[1e-7])), (its, default)
+
+
 def test_model_crafted_meshes_and_errors():
     for kw in (dict(), dict(fin=True), dict(zero_edge=True), dict(fin=True, zero_edge=True)):
         g = SM.grid_scene(**kw)
