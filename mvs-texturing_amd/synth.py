@@ -121,14 +121,23 @@ CONFIGS = {
 }
 
 
-def permute_scene(scene, seed=1):
+def permute_scene(scene, seed=1, face_perm=None, vert_perm=None):
     """The same scene with its faces AND vertices in random order (a decimated / cleaned mesh file in arbitrary order): faces,
     normals and adjacency lists renumbered (list order kept, build_adjacency_graph.cpp:16-53 semantics), vertex indices remapped.
-    Attributes face_perm / vert_perm: new face k = old face face_perm[k], new vertex k = old vertex vert_perm[k]."""
+    Attributes face_perm / vert_perm: new face k = old face face_perm[k], new vertex k = old vertex vert_perm[k].  An explicit
+    face_perm / vert_perm replaces the random one (the random draws are made all the same, so the other stays what `seed` gives)."""
     rng = np.random.default_rng(seed)
     F, NV = scene.faces.shape[0], scene.verts.shape[0]
     fp = rng.permutation(F).astype(np.uint32)
     vp = rng.permutation(NV).astype(np.uint32)
+    if face_perm is not None:
+        fp = np.ascontiguousarray(face_perm, dtype=np.uint32)
+        if not np.array_equal(np.sort(fp), np.arange(F, dtype=np.uint32)):
+            raise ValueError("face_perm is not a permutation of the faces")
+    if vert_perm is not None:
+        vp = np.ascontiguousarray(vert_perm, dtype=np.uint32)
+        if not np.array_equal(np.sort(vp), np.arange(NV, dtype=np.uint32)):
+            raise ValueError("vert_perm is not a permutation of the vertices")
     vinv = np.empty(NV, dtype=np.uint32); vinv[vp] = np.arange(NV, dtype=np.uint32)
     finv = np.empty(F, dtype=np.uint32); finv[fp] = np.arange(F, dtype=np.uint32)
     s = Scene()

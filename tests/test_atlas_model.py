@@ -56,7 +56,41 @@ def crafted_sets():
     out["odd_validity"] = AM.craft(rng, [(30, 30), (31, 17), (8, 40)], hole=0.3)
     v = out["odd_validity"]["validity"]; v[rng.random(v.size) < 0.1] = 7          # neither 0 nor 255: padded in sweep 0 only
     out["no_faces"] = AM.craft(rng, [(10, 10), (20, 5), (6, 6)], faces_per_patch=0)
+    # patches without faces in front of, between and behind the others in insertion order (descending size)
+    out["some_faceless"] = AM.craft(rng, [(30, 30), (28, 28), (25, 25), (20, 20), (18, 18), (15, 15), (10, 10), (5, 5), (4, 4)], hole=0.2,
+                                    faces_per_patch=[0, 0, 2, 0, 0, 3, 1, 0, 0])
+    # atlases of 2048, 4096 and 8192 pixels: padding 16, 32 and 64, so 17, 33 and 65 sweeps of the edge padding
+    for name, sizes in DEEP_SETS.items():
+        out[name] = AM.craft(rng, sizes, hole=0.3)
+    # a 2048 and an 8192 atlas in one call: the wide patch waits for its own atlas, and the first patch of either lands on (0, 0), so its
+    # corner (0, 0) becomes (16 / 2048, 16 / 2048) in one and (64 / 8192, 64 / 8192) in the other -- the same bits
+    pa = AM.set_from_sizes([(100, 100)] * 3 + [(4100, 2)] + [(20, 20)] * 5)
+    n = int(pa["pix_ptr"][-1])
+    pa["validity"] = np.where(rng.random(n) < 0.3, 0, 255).astype(np.uint8)
+    img = rng.uniform(-0.1, 1.1, (n, 3)).astype(np.float32); img[pa["validity"] == 0] = 0
+    pa["image"] = img.reshape(-1)
+    out["mixed_sizes"] = pa
     return out
+
+
+DEEP_SETS = {"deep_2048": [(1100, 40), (300, 200), (64, 64), (17, 5), (3, 3)],
+             "deep_4096": [(2100, 30), (300, 200), (64, 64), (17, 5), (3, 3)],
+             "deep_8192": [(4100, 12), (300, 100), (64, 64), (17, 5), (3, 3)]}
+
+
+def check_merged_texcoords(got):
+    """item 8 on one output (the model's or the library's): every corner's id leads to its coordinate's bits in its atlas's merged list,
+    and no atlas holds a coordinate twice"""
+    tc = _raw(got["texcoords"]).reshape(-1, 2); merged = _raw(got["texcoords_merged"]).reshape(-1, 2)
+    ids = np.asarray(got["texcoord_ids"], np.int64).ravel()                       # the library hands them out per face, (n, 3)
+    fp = np.asarray(got["face_ptr"], np.int64); tp = np.asarray(got["tc_ptr"], np.int64)
+    assert len(ids) == len(tc) == 3 * fp[-1] and len(merged) == tp[-1]
+    for a in range(len(fp) - 1):
+        c0, c1 = 3 * fp[a], 3 * fp[a + 1]
+        assert np.all(ids[c0:c1] < tp[a + 1] - tp[a]), a
+        assert np.array_equal(merged[tp[a] + ids[c0:c1]], tc[c0:c1]), a
+        own = np.asarray(got["texcoords_merged"]).reshape(-1, 2)[tp[a]:tp[a + 1]]      # float equality: -0.0f and 0.0f are one coordinate
+        assert len(np.unique(own, axis=0)) == len(own), a
 
 
 def test_model_equals_upstream_on_the_packing_pins():
@@ -145,11 +179,22 @@ def _check_rules(name, pa):
     st, got, stats, cnt, _ = AM.run(pa)
     assert st == 0, name
     filled = 0
+    check_merged_texcoords(got)
     for a in range(len(got["atlas_size"])):
         img, mask = AM.compose(pa, got, a)
         pad = int(got["atlas_size"][a]) >> 7
+        view = AM.atlas_view(got, a)
+        # the padding reaches pad + 1 pixels from a valid one: the rules run on the window that holds every patch pixel and pad + 2 pixels
+        # around them (an atlas of 8192 is 67 M pixels, mostly empty); outside it the atlas is what the composition left, zeros
+        ys, xs = np.flatnonzero(mask.any(1)), np.flatnonzero(mask.any(0))
+        win = (slice(0, 0), slice(0, 0))
+        if len(ys):
+            win = (slice(max(int(ys[0]) - pad - 2, 0), int(ys[-1]) + pad + 3), slice(max(int(xs[0]) - pad - 2, 0), int(xs[-1]) + pad + 3))
+        for rest in ((slice(0, win[0].start), slice(None)), (slice(win[0].stop, None), slice(None)), (win[0], slice(0, win[1].start)), (win[0], slice(win[1].stop, None))):
+            assert np.array_equal(view[rest], img[rest]), (name, a)
+        img, mask, view = img[win], mask[win], view[win]
         out, lev = AM.rule_pad(img, mask, pad)
-        assert np.array_equal(out, AM.atlas_view(got, a)), (name, a)
+        assert np.array_equal(out, view), (name, a)
         filled += int(((lev > 0) & (lev < 255)).sum())
         if set(np.unique(mask)) <= {0, 255}:                      # the levels ARE the chessboard distance to the nearest valid pixel, capped
             assert np.array_equal(_distance(mask == 255, pad + 1), lev), (name, a)
@@ -160,12 +205,46 @@ def _check_rules(name, pa):
 def test_order_free_padding_and_composition_equal_the_model():
     for name, side, pa, _ in pixel_pins():
         _check_rules(name, pa)
+    sizes = dict.fromkeys(("atlases_2048", "atlases_4096", "atlases_8192"), 0)
     for name, pa in crafted_sets().items():
         stats, cnt = _check_rules(name, pa)
         if name == "two_atlases":
             assert stats["atlases"] == 2 and cnt["waits_too_wide"] >= 1
         if name == "no_edges":
             assert cnt["foreign_fill"] == 0
+        if name in DEEP_SETS or name == "mixed_sizes":
+            for k in sizes:
+                sizes[k] += stats[k]
+        if name in DEEP_SETS:                                     # one atlas of the name's size, padded to its last level: padding + 1
+            assert stats["atlases"] == 1 and stats["atlases_" + name[5:]] == 1, (name, stats)
+            assert cnt["outer_ring"] > 0 and cnt["foreign_fill"] > 0, (name, cnt)
+        print(name, {k: v for k, v in stats.items() if v}, {k: v for k, v in cnt.items() if v})
+    assert all(v >= 1 for v in sizes.values()), sizes
+
+
+def test_mixed_sizes_share_a_coordinate_between_atlases():
+    """one (x, y) bit pair of `texcoords` in an atlas of 2048 and in one of 8192: each atlas counts it once (what `atlas << 32` in the
+    device's sort key is for)"""
+    st, got, stats, cnt, _ = AM.run(crafted_sets()["mixed_sizes"])
+    assert st == 0 and got["atlas_size"].tolist() == [2048, 8192] and cnt["waits_too_wide"] == 1, (got["atlas_size"], cnt)
+    tc = _raw(got["texcoords"]).reshape(-1, 2); fp = got["face_ptr"].astype(np.int64); tp = got["tc_ptr"].astype(np.int64)
+    per = [set(map(tuple, tc[3 * fp[a]:3 * fp[a + 1]].tolist())) for a in range(2)]
+    shared = per[0] & per[1]
+    assert len(shared) >= 1
+    check_merged_texcoords(got)                                   # ... which holds every atlas to its own distinct coordinates
+    assert [int(tp[a + 1] - tp[a]) for a in range(2)] == [len(per[0]), len(per[1])]       # so a shared pair is counted in both
+    assert stats["merged_texcoords"] == len(per[0]) + len(per[1]) > len(per[0] | per[1])
+
+
+def test_some_faceless_interleaves_patches_without_faces():
+    pa = crafted_sets()["some_faceless"]
+    st, got, stats, _, _ = AM.run(pa)
+    assert st == 0 and stats["atlases"] == 1
+    n = np.diff(pa["face_ptr"].astype(np.int64))[got["patch_order"]]           # faces per patch in insertion order
+    assert n[0] == 0 and n[-1] == 0 and n.tolist().count(0) == 6 and (n > 0).sum() == 3
+    inner = np.flatnonzero(n > 0)
+    assert np.any(n[inner[0]:inner[-1]] == 0)                                  # ... and one between two patches that have faces
+    assert sorted(got["faces"].tolist()) == sorted(pa["faces"].tolist())
 
 
 def test_float_to_byte_definition():

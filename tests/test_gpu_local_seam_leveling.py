@@ -1,7 +1,7 @@
 """Row f7 on the GPU: Context.local_seam_leveling equals the CPU model (tests/tools/blend_model.cpp: upstream's loops, the solve of
 DESIGN.md section 4 "Local seam leveling") bit for bit on image, validity and the prepared blending mask and on every counter -- the
 suite's scenes (labels from the library's own view selection, patches from its rows f5 and f6), shuffled meshes, the crafted sets of
-tests/test_local_seam_model.py and config 2; with the default parameters and with max_iterations = 0 (the state before the solve);
+tests/test_local_seam_model.py, the nested set of tests/test_patch_model.py (merge chains, equal boxes) and config 2; with the default parameters and with max_iterations = 0 (the state before the solve);
 the patch sets of tests/golden/local_seam_pins.npz against what upstream's compiled local_seam_leveling left for them; and the
 edge sets of tests/test_local_seam_model.py (skipped pairs, sanitized pixels, an idle channel, the ladder of unknown counts) with
 iteration caps, tolerances and strip widths moved, on the LDS path and in global memory."""
@@ -13,6 +13,7 @@ import blend_model as BM
 import patch_model as PM
 import seam_model as SM
 from conftest import get_scene
+from test_patch_model import nested_set
 from test_local_seam_model import EDGE_REACHES, crafted_sets, edge_sets, ladder_sets, mid_cap, pin_cases, unknown_counts
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,17 @@ def test_crafted_sets_equal_the_model():
             assert gst["outside_frame"] > 0
         if name == "demoted":
             assert gst["demoted"] > 0
+
+
+def test_nested_set_equals_the_model():
+    """patches whose lists were merged through chains, in all six candidate orders, and two patches of one frame: rows f5 and f6 of the
+    library give the set, this row equals its model on it"""
+    for name, (g, labels) in nested_set().items():
+        pa = _pipeline_patches(g, labels)
+        assert len(pa["label"]) == 2, name
+        got, gst, _, _ = _compare(g, labels, pa, what=name)
+        assert gst["strip_pixels"] > 0 and gst["seam_edges"] > 0 and gst["hit_max_iterations"] == 0, (name, gst)
+        _compare(g, labels, pa, what=name + "/no solve", max_iterations=0)
 
 
 def test_upstream_pins_on_the_gpu():

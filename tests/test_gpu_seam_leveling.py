@@ -1,12 +1,14 @@
 """Row f5 on the GPU: Context.global_seam_leveling equals the CPU model (tests/tools/seam_model.cpp) bit for bit -- structure, Lhs,
 Rhs, b, x before and after the mean, per-corner adjustments, CG iterations and errors -- on the suite's scenes (labels from the
-library's own view selection), shuffled meshes and crafted cases; plus the checks of tests/test_seam_model.py on the GPU's output."""
+library's own view selection), shuffled meshes, crafted cases and the nested set of tests/test_patch_model.py (merge chains in every
+candidate order, equal boxes); plus the checks of tests/test_seam_model.py on the GPU's output."""
 import numpy as np
 import pytest
 
 import mvs_texturing_amd as M
 import seam_model as SM
 from conftest import get_scene
+from test_patch_model import nested_set
 from test_seam_model import CAPS, PLANTED_RATIO, TOLERANCES
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +106,14 @@ def test_crafted_labelings_and_meshes():
     got, gst = c.global_seam_leveling(g.adj_ptr, g.adj, np.zeros(len(g.faces), np.uint32))    # all labels 0: empty outputs
     assert gst["x_rows"] == 0 and len(got["x_adjust"]) == 0 and got["corner_adjust"].shape == (len(g.faces), 3, 3) and not np.any(got["corner_adjust"])
     c.close()
+
+
+def test_nested_set_equals_the_model():
+    """candidates absorbed through chains, in all six candidate orders, and two candidates with one box: the vertex projections go up
+    several frames and the patch ids follow the merge"""
+    for name, (g, labels) in nested_set().items():
+        _, gst, _ = _compare(g, labels)
+        assert gst["patches"] == 2 and gst["merged"] == 3 and gst["a_rows"] > 0, (name, gst)
 
 
 def _caps_and_tolerances(s, labels, **kw):

@@ -1,6 +1,7 @@
 """Row f8 on the GPU: Context.texture_atlases equals the CPU model (tests/tools/atlas_model.cpp: upstream's loops and containers,
 DESIGN.md section 4 "Texture atlases") bit for bit on every output array and every counter -- the suite's scenes (labels from the
-library's own view selection, patches from its rows f5 - f7), shuffled meshes, the crafted sets of tests/test_atlas_model.py, config 2,
+library's own view selection, patches from its rows f5 - f7), shuffled meshes, the crafted sets of tests/test_atlas_model.py (atlases of
+2048 to 8192 padded 17 to 65 levels deep, two sizes in one call), the nested set of tests/test_patch_model.py, config 2,
 and the cases of tests/golden/texture_atlas_pins.npz against what upstream's compiled generate_texture_atlases left for them."""
 import numpy as np
 import pytest
@@ -8,7 +9,8 @@ import pytest
 import mvs_texturing_amd as M
 import atlas_model as AM
 from conftest import get_scene
-from test_atlas_model import UP_KEYS, crafted_sets, pack_pins, pixel_pins
+from test_atlas_model import DEEP_SETS, UP_KEYS, check_merged_texcoords, crafted_sets, pack_pins, pixel_pins
+from test_patch_model import nested_set
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +64,7 @@ def _compare(pa, ctx=None, what=""):
     _same(got, want, what)
     for k in AM.STATS:
         assert gst[k] == wst[k], (what, k, gst[k], wst[k])
+    check_merged_texcoords(got)
     return got, gst, cnt
 
 
@@ -103,7 +106,19 @@ def test_crafted_sets_equal_the_model():
             assert gst["atlases"] == 2 and cnt["waits_too_wide"] >= 1
         if name == "small":
             assert cnt["foreign_fill"] > 0
+        if name in DEEP_SETS:                              # padded to the last level, padding + 1, and into a neighbour's rectangle
+            assert got["atlas_size"].tolist() == [int(name[5:])] and cnt["outer_ring"] > 0 and cnt["foreign_fill"] > 0, (name, cnt)
+        if name == "mixed_sizes":
+            assert got["atlas_size"].tolist() == [2048, 8192] and cnt["waits_too_wide"] == 1
     c.close()
+
+
+def test_nested_set_equals_the_model():
+    """patch sets whose lists were merged through chains, in all six candidate orders, and two patches of one frame, through rows f5 - f7"""
+    for name, (g, labels) in nested_set().items():
+        pa = _pipeline_patches(g, labels)
+        got, gst, _ = _compare(pa, what=name)
+        assert gst["atlases"] == 1 and sorted(got["faces"].tolist()) == sorted(pa["faces"].tolist()), name
 
 
 def test_upstream_pins_on_the_gpu():

@@ -1,7 +1,8 @@
 """Row f6 on the GPU: Context.texture_patches equals the CPU model (tests/tools/patch_model.cpp, upstream's sequential loop) bit for
 bit on every array of mvs_patch_set -- labels, frames, lists, texture coordinates, pixel offsets, images, both masks -- and on the
 counts, on the suite's scenes (labels from the library's own view selection, adjustments from its own global seam leveling, and
-none), shuffled meshes, the crafted set of tests/test_patch_model.py and config 2; plus the checks of that file on the GPU's output."""
+none), shuffled meshes, the crafted and nested sets of tests/test_patch_model.py (merge chains in every candidate order, equal boxes),
+crafted labelings on the scenes where chains occur by themselves, and config 2; plus the checks of that file on the GPU's output."""
 import numpy as np
 import pytest
 
@@ -9,7 +10,7 @@ import mvs_texturing_amd as M
 import patch_model as PM
 import seam_model as SM
 from conftest import get_scene
-from test_patch_model import check_constant_adjustment, check_invariants, corner_adjust, crafted_set
+from test_patch_model import check_constant_adjustment, check_invariants, check_nested_list, corner_adjust, crafted_set, nested_set
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,14 @@ def _compare(s, labels, ca=None, ctx=None, what=""):
     return got, gst, cnt
 
 
-@pytest.mark.parametrize("name", ["tiny", "bumpy", "oddw", "mixed", "spiky", "close", "manyviews"])
+# which side of the 512-pixel split between tp_mark_kernel and tp_mark_big_kernel a scene's list entries fall on (patch_model.entry_pixels
+# on the model's output under the labels of the reference's own view selection, which the library's equal): both, at least 77 entries
+# on either side, except that manyviews' faces cover a few pixels of its 160 x 120 views (ranges of at most 81 pixels) and bigfoot's
+# thousands of its 1024 x 768 views (at least 1548)
+SPLIT_SIDES = {"manyviews": ("small",), "bigfoot": ("big",)}
+
+
+@pytest.mark.parametrize("name", ["tiny", "bumpy", "oddw", "mixed", "spiky", "close", "manyviews", "bigfoot"])
 def test_scenes_equal_the_model(name):
     s = get_scene(name)
     labels = _library_labels(name, s)
@@ -77,6 +85,13 @@ def test_scenes_equal_the_model(name):
     assert np.any(gsl["corner_adjust"])
     got, gst, _ = _compare(s, labels, gsl["corner_adjust"], what=name + "/gsl")
     assert gst["valid_pixels"] > 0 and gst["near_pixels"] > 0
+    n = PM.entry_pixels(PM.run_scene(s, labels)[1])                       # from the model's texcoords and frames
+    sides = {"small": int(((n > 0) & (n <= 512)).sum()), "big": int((n > 512).sum())}
+    print("%s: entries of <= 512 / > 512 pixels: %d / %d, the largest %d" % (name, sides["small"], sides["big"], int(n.max())))
+    for side in SPLIT_SIDES.get(name, ("small", "big")):
+        assert sides[side] > 0, (name, sides)
+    if name == "bigfoot":
+        assert int(n.max()) > 20 * 256                                    # many strides of a block of tp_mark_big_kernel
     zero, zst, _ = _compare(s, labels, None, what=name + "/none")
     check_invariants(s, labels, zero, zst)
     for k in KEYS:
@@ -107,11 +122,49 @@ def test_crafted_set_equals_the_model():
         got, gst, _ = _compare(s, labels, corner_adjust(s, labels), what="tiny/" + lname)
         if lname == "random":
             assert gst["merged"] > 0
+        if lname == "first":                                              # an entry on either side of the split, to the pixel
+            n = PM.entry_pixels(got)
+            assert (n == 512).any() and (n == 513).any()
     g = SM.grid_scene()
     c = _ctx(g)                                                           # all labels 0: an empty set
     got, gst = c.texture_patches(g.adj_ptr, g.adj, np.zeros(len(g.faces), np.uint32))
     assert gst["patches"] == 0 and gst["pixels"] == 0 and got["image"].shape == (0, 3) and got["pix_ptr"].tolist() == [0]
     c.close()
+
+
+def test_nested_set_equals_the_model():
+    """chains of absorptions in all six candidate orders and two candidates with one box: every array and count, with adjustments and
+    without; the label-1 list of the DEVICE against the literal order derived by hand (tests/test_patch_model.py NESTED_LISTS)"""
+    total = {k: 0 for k in PM.COUNTERS}
+    for name, (g, labels) in nested_set().items():
+        got, gst, cnt = _compare(g, labels, corner_adjust(g, labels), what=name)
+        check_invariants(g, labels, got, gst)
+        _compare(g, labels, None, what=name + "/none")
+        for k in total:
+            total[k] += cnt[k]
+        assert gst["patches"] == 2 and gst["merged"] == 3, (name, gst)
+    for order in PM.NESTED_ORDERS:
+        g, labels, region = PM.nested_scene(order)
+        c = _ctx(g)
+        got, _ = c.texture_patches(g.adj_ptr, g.adj, labels)
+        c.close()
+        check_nested_list(order, region, got)
+    assert total["chain"] >= 2 and total["absorber_later"] >= 2 and total["equal_boxes"] >= 1, total
+    assert total["clamped"] == 0 and total["magenta_inside"] == 0, total
+
+
+@pytest.mark.parametrize("name", ["spiky", "oddw"])
+def test_crafted_labelings_where_chains_occur(name):
+    """the scenes on which random labelings build chains by themselves (an absorbed candidate that had absorbed others)"""
+    s = get_scene(name)
+    total = {k: 0 for k in PM.COUNTERS}
+    for lname, labels in SM.crafted_labelings(s).items():
+        _, gst, cnt = _compare(s, labels, corner_adjust(s, labels), what=name + "/" + lname)
+        for k in total:
+            total[k] += cnt[k]
+    print("%s: chain %d, absorber_later %d, equal_boxes %d, absorbed %d" % (name, total["chain"], total["absorber_later"], total["equal_boxes"], total["absorbed"]))
+    assert total["chain"] >= 1 and total["absorber_later"] >= 1, total
+    assert total["clamped"] == 0, total
 
 
 def test_constant_adjustment_on_the_gpu():

@@ -39,6 +39,33 @@ def crafted_set():
     return out
 
 
+# The label-1 patch's face list of PM.nested_scene(order) as blocks of whole regions, derived by hand from the merge loop (DESIGN.md
+# section 4 item 3: "scan in order, a candidate whose box lies inside another's of its label is absorbed, its list appended"; the boxes
+# nest outer > annulus > core; candidates c0 < c1 < c2 are `order`; i runs over the living candidates, j over all others, both ascending):
+NESTED_LISTS = {
+    # i = outer takes annulus, then core.
+    ("outer", "annulus", "core"): ("outer", "annulus", "core"),
+    # i = outer takes core (j = 1), then annulus (j = 2).
+    ("outer", "core", "annulus"): ("outer", "core", "annulus"),
+    # i = annulus: outer does not fit, core does -> [annulus, core]; i = outer takes that list whole (a chain, the absorber is later).
+    ("annulus", "outer", "core"): ("outer", "annulus", "core"),
+    # i = annulus takes core; core is dead; i = outer takes [annulus, core] (a chain, the absorber is later).
+    ("annulus", "core", "outer"): ("outer", "annulus", "core"),
+    # i = core takes nothing; i = outer takes core (j = 0, the absorber is later), then annulus (j = 2).
+    ("core", "outer", "annulus"): ("outer", "core", "annulus"),
+    # i = core takes nothing; i = annulus takes core (later); i = outer: core is dead, takes [annulus, core] (a chain, later).
+    ("core", "annulus", "outer"): ("outer", "annulus", "core"),
+}
+NESTED_SIZES = {"outer": 176, "annulus": 80, "core": 2}   # faces: 2 (13^2 - 9^2), 2 (7^2 - 3^2), 2
+
+
+def nested_set():
+    """name -> (scene, labels): PM.nested_scene in the six candidate orders and PM.equal_box_scene"""
+    out = {"nested_" + "_".join(o): PM.nested_scene(o)[:2] for o in PM.NESTED_ORDERS}        # lowest candidate first
+    out["equal_boxes"] = PM.equal_box_scene()
+    return out
+
+
 def corner_values(scene, seed=11, amp=0.06):
     """per-corner adjustments as row f5 would hand them over: one value per (vertex, label), so faces of a patch agree on shared corners"""
     rng = np.random.default_rng(seed)
@@ -118,6 +145,65 @@ def test_model_equals_the_order_free_rule_and_the_cases_are_not_vacuous():
     assert total["magenta"] >= 1 and total["magenta_near"] >= 1, total   # ... its fill colour reaches near-only pixels, never inside ones
 
 
+def test_nested_scene_as_the_grid_is_built():
+    g, labels, region = PM.nested_scene()
+    assert len(g.faces) == 338
+    st, arrays, stats, cnt = PM.run_scene(g, labels)
+    assert st == 0 and stats["patches"] == 2 and stats["merged"] == 3 and stats["pixels"] == 10840
+    assert arrays["face_ptr"].tolist() == [0, 258, 338] and arrays["label"].tolist() == [1, 2]
+    assert arrays["box"].reshape(-1, 4)[0, :2].tolist() == [-1, -1] and cnt["frame_negative"] == 1
+    p = M.synth.permute_scene(g, seed=5)                              # a random renumbering gives the same patches
+    st, shuffled, sstats, _ = PM.run_scene(p, labels[p.face_perm])
+    assert all(sstats[k] == stats[k] for k in PM.STATS) and np.array_equal(shuffled["box"], arrays["box"]) and np.array_equal(shuffled["face_ptr"], arrays["face_ptr"])
+
+
+def _blocks(ids):
+    """the runs of equal values in ids: [(value, length)]"""
+    ids = np.asarray(ids)
+    cut = np.flatnonzero(np.diff(ids)) + 1
+    return [(int(ids[a]), int(b - a)) for a, b in zip(np.r_[0, cut], np.r_[cut, len(ids)])]
+
+
+def check_nested_list(order, region, arrays):
+    """the label-1 patch's face list (the model's or the library's) is NESTED_LISTS[order], region by region; the label-2 patch lists the
+    outer ring, then the inner one, whichever came first"""
+    assert arrays["label"].tolist() == [1, 2] and arrays["face_ptr"].tolist() == [0, 258, 338], order
+    faces = arrays["faces"]
+    want = [(PM.NESTED_REGIONS.index(r), NESTED_SIZES[r]) for r in NESTED_LISTS[tuple(order)]]
+    assert _blocks(region[faces[:258]]) == want, (order, _blocks(region[faces[:258]]))
+    assert _blocks(region[faces[258:]]) == [(3, 64), (4, 16)], order
+
+
+def test_nested_orders_give_the_lists_derived_by_hand():
+    assert set(NESTED_LISTS) == set(PM.NESTED_ORDERS) and len(PM.NESTED_ORDERS) == 6
+    for order in PM.NESTED_ORDERS:
+        g, labels, region = PM.nested_scene(order)
+        lowest = [int(np.flatnonzero(region == PM.NESTED_REGIONS.index(r)).min()) for r in order]
+        assert lowest == sorted(lowest) and lowest[0] == 0, (order, lowest)      # the candidate order asked for
+        st, arrays, stats, _ = PM.run_scene(g, labels)
+        assert st == 0 and stats["patches"] == 2 and stats["merged"] == 3 and stats["pixels"] == 10840, (order, stats)
+        check_nested_list(order, region, arrays)
+
+
+def test_nested_set_reaches_chains_later_absorbers_and_equal_boxes():
+    total = {k: 0 for k in PM.COUNTERS}
+    for name, (g, labels) in nested_set().items():
+        for ca in (corner_adjust(g, labels), None):
+            st, arrays, stats, cnt = PM.run_scene(g, labels, ca)
+            assert st == 0, name
+            _rule_on_model(g, arrays, ca)
+        for k in total:
+            total[k] += cnt[k]
+        assert cnt["clamped"] == 0 and cnt["magenta_inside"] == 0, (name, cnt)
+        if name == "equal_boxes":
+            box = arrays["box"].reshape(-1, 4)
+            assert cnt["equal_boxes"] >= 1 and stats["patches"] == 2 and np.array_equal(box[0], box[1]), (cnt, box)
+    assert total["chain"] >= 2, total                 # an absorbed candidate that had absorbed others: cand_pos sums several offsets
+    assert total["absorber_later"] >= 2, total        # the absorber comes after what it absorbs (j < i)
+    assert total["equal_boxes"] >= 1, total           # two candidates with the same box: the earlier one absorbs
+    print("nested set counters:", total)
+
+
 def _strictly_inside(tc):
     """(ys, xs) of the integer pixels certainly inside the triangle tc (3, 2) in fp32: float64 barycentrics above the fp32 evaluation
     error -- each numerator is a sum of two products of differences (relative error u each), so it is off by at most
@@ -160,13 +246,16 @@ def check_invariants(scene, labels, arrays, stats, zero_arrays=None):
             assert np.all(pbl[ys, xs] == 255), (i, e)
 
 
-@pytest.mark.parametrize("name", ["tiny", "bumpy", "grid", "grid_fin_zero", "island"])
+@pytest.mark.parametrize("name", ["tiny", "bumpy", "grid", "grid_fin_zero", "island", "nested_annulus_core_outer", "equal_boxes"])
 def test_invariants_and_patch_counts(name):
     if name in ("tiny", "bumpy"):
         s = get_scene(name)
         cases = SM.crafted_labelings(s)
         if name == "bumpy":
             cases = {k: cases[k] for k in ("random", "random_with_unseen")}
+    elif name == "equal_boxes" or name.startswith("nested_"):
+        s, labels = nested_set()[name]
+        cases = {"crafted": labels}
     else:
         s, labels = crafted_set()[name]
         cases = {"crafted": labels}

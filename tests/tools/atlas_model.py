@@ -104,9 +104,10 @@ def atlas_view(arrays, a):
 
 def craft(rng, sizes, hole=0.15, edge_valid=True, faces_per_patch=3):
     """a crafted patch set: random colours (some outside [0, 1], a NaN), validity with holes (and, with edge_valid, valid pixels on the
-    frame's edges), `faces_per_patch` faces each whose corners repeat within the patch"""
+    frame's edges), `faces_per_patch` faces each (one number, or one per patch) whose corners repeat within the patch"""
     sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
     n = len(sizes)
+    per_patch = np.broadcast_to(np.asarray(faces_per_patch, np.int64), (n,))
     box = np.zeros((n, 4), np.int32); box[:, 2:] = sizes
     pix_ptr = np.zeros(n + 1, np.uint64); pix_ptr[1:] = np.cumsum(sizes[:, 0] * sizes[:, 1])
     N = int(pix_ptr[-1])
@@ -123,7 +124,7 @@ def craft(rng, sizes, hole=0.15, edge_valid=True, faces_per_patch=3):
     for p in range(n):
         w, h = sizes[p]
         corners = np.stack([rng.integers(0, w + 1, 4), rng.integers(0, h + 1, 4)], 1).astype(np.float32) + rng.choice([0.0, 0.5, 0.25], (4, 2)).astype(np.float32)
-        for k in range(faces_per_patch):
+        for k in range(int(per_patch[p])):
             faces.append(len(faces))
             tcs.append(corners[[k % 4, (k + 1) % 4, (k + 2) % 4]])
         fptr.append(len(faces))
@@ -219,32 +220,35 @@ def _shift(a, i, j, fill):
 
 def rule_pad(image, mask, padding):
     """item 7 in its level form: image (s, s, 3) uint8 and mask (s, s) after composition -> (padded image, levels); level 0 = valid at the
-    start, d = filled in iteration d - 1 from the neighbours of lower level, 255 = never"""
-    img = np.asarray(image, np.uint8).copy(); mask = np.asarray(mask, np.uint8)
-    lev = np.where(mask == 255, 0, 255).astype(np.int64)
+    start, d = filled in iteration d - 1 from the neighbours of lower level, 255 = never.  Level d is looked for among the neighbours of
+    level d - 1 only (index lists, not whole-image passes: an atlas of 8192 has 65 levels)."""
+    mask = np.asarray(mask, np.uint8)
+    h, w = mask.shape
+    img = np.zeros((h + 2, w + 2, 3), np.uint8); img[1:-1, 1:-1] = np.asarray(image, np.uint8)    # a border of level 255: never read
+    lev = np.full((h + 2, w + 2), 255, np.int64); lev[1:-1, 1:-1] = np.where(mask == 255, 0, 255)
+    open_ = np.zeros((h + 2, w + 2), bool)
     f32 = np.float32
-    gauss = {(i, j): f32((2 - abs(i)) * (2 - abs(j))) / f32(16) for j in (-1, 0, 1) for i in (-1, 0, 1)}
+    nbrs = [(i, j) for j in (-1, 0, 1) for i in (-1, 0, 1)]                                       # j outer, i inner
+    gauss = {(i, j): f32((2 - abs(i)) * (2 - abs(j))) / f32(16) for i, j in nbrs}
+    ys, xs = np.nonzero(lev == 0)
     for d in range(1, padding + 2):
-        near = np.zeros(mask.shape, bool)
-        for j in (-1, 0, 1):
-            for i in (-1, 0, 1):
-                near |= _shift(lev, i, j, 255) == d - 1
-        cand = (lev == 255) & near & ((mask != 255) if d == 1 else (mask == 0))
-        if not cand.any():
+        open_[1:-1, 1:-1] = (lev[1:-1, 1:-1] == 255) & ((mask != 255) if d == 1 else (mask == 0))
+        cy = np.concatenate([ys + j for i, j in nbrs]); cx = np.concatenate([xs + i for i, j in nbrs])
+        keep = open_[cy, cx]
+        flat = np.unique(cy[keep] * (w + 2) + cx[keep])
+        if not len(flat):
             break
-        norm = np.zeros(mask.shape, f32); value = np.zeros(mask.shape + (3,), f32)
-        for j in (-1, 0, 1):
-            for i in (-1, 0, 1):
-                ok = _shift(lev, i, j, 255) < d
-                w = gauss[(i, j)]
-                norm = np.where(ok, norm + w, norm)
-                px = _shift(img, i, j, 0).astype(f32) / f32(255.0)
-                value = np.where(ok[..., None], value + px * w, value)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            out = ((value / norm[..., None]) * f32(255.0))
-        img[cand] = out[cand].astype(np.uint8)
-        lev[cand] = d
-    return img, lev
+        ys, xs = flat // (w + 2), flat % (w + 2)
+        norm = np.zeros(len(flat), f32); value = np.zeros((len(flat), 3), f32)
+        for i, j in nbrs:
+            ok = lev[ys + j, xs + i] < d
+            wgt = gauss[(i, j)]
+            norm = np.where(ok, norm + wgt, norm)
+            px = img[ys + j, xs + i].astype(f32) / f32(255.0)
+            value = np.where(ok[:, None], value + px * wgt, value)
+        img[ys, xs] = ((value / norm[:, None]) * f32(255.0)).astype(np.uint8)
+        lev[ys, xs] = d
+    return img[1:-1, 1:-1], lev[1:-1, 1:-1]
 
 
 def compose(patches, arrays, a):

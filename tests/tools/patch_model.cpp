@@ -29,7 +29,8 @@ void pixel_coords(const View& v, const float* p, float& px, float& py) {
 }
 
 // counters that show what the inputs exercised (tests assert they are non-zero on the crafted set)
-enum { N_ABSORBED = 0, N_INSIDE_TWICE, N_NEAR_THEN_INSIDE, N_DEGENERATE, N_FRAME_NEG, N_MAGENTA_NEAR, N_MAGENTA_INSIDE, N_MAGENTA, N_CLAMPED, N_COUNTERS };
+enum { N_ABSORBED = 0, N_INSIDE_TWICE, N_NEAR_THEN_INSIDE, N_DEGENERATE, N_FRAME_NEG, N_MAGENTA_NEAR, N_MAGENTA_INSIDE, N_MAGENTA, N_CLAMPED, N_CHAIN, N_ABSORBER_LATER, N_EQUAL_BOXES,
+       N_COUNTERS };
 
 struct Tri {
     float v1x, v1y, v2x, v2y, v3x, v3y, detT, min_x, min_y, max_x, max_y;
@@ -107,7 +108,7 @@ struct Model {
     uint64_t cnt[N_COUNTERS] = {0};
 };
 
-struct Cand { std::vector<uint32_t> faces; std::vector<float> texcoords; int min_x, min_y, max_x, max_y; uint32_t label; bool alive = true; };
+struct Cand { std::vector<uint32_t> faces; std::vector<float> texcoords; int min_x, min_y, max_x, max_y; uint32_t label; bool alive = true; uint32_t absorbed = 0; };
 
 }  // namespace
 
@@ -168,6 +169,10 @@ void* patch_model_run(uint32_t n_verts, const float* verts, uint32_t n_faces, co
                 const float ox = (float)(s.min_x - a.min_x), oy = (float)(s.min_y - a.min_y);
                 for (size_t t = 0; t < s.texcoords.size(); t += 2) { a.texcoords.push_back(s.texcoords[t] + ox); a.texcoords.push_back(s.texcoords[t + 1] + oy); }
                 s.alive = false; ++M->stats[1]; ++M->cnt[N_ABSORBED];
+                if (s.absorbed) ++M->cnt[N_CHAIN];                    // its list already holds other candidates' faces and offsets
+                if (j < i) ++M->cnt[N_ABSORBER_LATER];
+                if (s.min_x == a.min_x && s.max_x == a.max_x && s.min_y == a.min_y && s.max_y == a.max_y) ++M->cnt[N_EQUAL_BOXES];
+                ++a.absorbed;
             }
         }
         // every survivor becomes a patch: crop + byte_to_float_image, then adjust_colors

@@ -12,7 +12,8 @@ LIB = os.path.join(HERE, "libpatch_model.so")
 ARRAYS = {"label": np.uint32, "box": np.int32, "face_ptr": np.uint32, "faces": np.uint32, "texcoords": np.float32, "pix_ptr": np.uint64,
           "image": np.float32, "validity": np.uint8, "blending": np.uint8}
 STATS = ("patches", "merged", "listed_faces", "degenerate_faces", "pixels", "valid_pixels", "near_pixels")
-COUNTERS = ("absorbed", "inside_twice", "near_then_inside", "degenerate", "frame_negative", "magenta_near", "magenta_inside", "magenta", "clamped")
+COUNTERS = ("absorbed", "inside_twice", "near_then_inside", "degenerate", "frame_negative", "magenta_near", "magenta_inside", "magenta", "clamped",
+            "chain", "absorber_later", "equal_boxes")
 _lib = None
 
 
@@ -195,3 +196,75 @@ def island_scene():
     core = (ix == 3) & (iy == 3)
     labels[ring & ~core] = 2
     return g, labels
+
+
+def _grid_cells(g, n):
+    """(ix, iy) of every face's cell in seam_model.grid_scene(n=n) (no fin, no extra faces)"""
+    assert len(g.faces) == 2 * (n - 1) * (n - 1)
+    cell = np.arange(len(g.faces)) // 2
+    return cell % (n - 1), cell // (n - 1)
+
+
+NESTED_REGIONS = ("outer", "annulus", "core")
+NESTED_ORDERS = tuple((a, b, c) for a in NESTED_REGIONS for b in NESTED_REGIONS for c in NESTED_REGIONS if len({a, b, c}) == 3)
+
+
+def nested_scene(order=None, seed=0):
+    """seam_model.grid_scene(n=14, W=96, H=72), 338 faces; d = chessboard distance of a face's cell to cell (6, 6): label 2 where d is 4
+    or 1, label 1 elsewhere.  Label 1 has three candidates whose boxes nest -- outer (d >= 5), annulus (d of 2 or 3), core (d == 0) --
+    and label 2 two nested rings, so the merge ends with one patch per label whatever the candidate order, and in four of the six
+    orders a candidate is absorbed that had absorbed another one: a chain.  Candidates are ordered by
+    their smallest face, so `order` -- a permutation of NESTED_REGIONS, lowest first -- is produced by renumbering: the faces of the three
+    regions in that order (shuffled within a region), then the two rings (inner first for every other order), vertices shuffled.
+    order None: the grid as built (outer < annulus < core).  Returns (scene, labels, region): region[f] in 0 .. 2 indexes
+    NESTED_REGIONS for the faces of label 1, 3 / 4 = the outer / inner ring of label 2."""
+    import mvs_texturing_amd as M
+    import seam_model as SM
+    g = SM.grid_scene(n=14, W=96, H=72)
+    ix, iy = _grid_cells(g, 14)
+    d = np.maximum(np.abs(ix - 6), np.abs(iy - 6))
+    region = np.select([d >= 5, d == 4, d >= 2, d == 1], [0, 3, 1, 4], 2)
+    labels = np.where(region >= 3, 2, 1).astype(np.uint32)
+    if order is None:
+        return g, labels, region
+    k = NESTED_ORDERS.index(tuple(order))
+    rng = np.random.default_rng(seed + k)
+    blocks = [NESTED_REGIONS.index(r) for r in order] + ([4, 3] if k % 2 else [3, 4])
+    perm = np.concatenate([rng.permutation(np.flatnonzero(region == b)) for b in blocks])
+    p = M.synth.permute_scene(g, seed=seed + k, face_perm=perm)
+    return p, labels[p.face_perm], region[p.face_perm]
+
+
+def equal_box_scene():
+    """two candidates of one label with IDENTICAL boxes.  Two edge-connected regions of a planar mesh cannot both reach all four sides
+    of a rectangle, so the boxes agree through their rounding: an 8 x 8 vertex grid whose first two and last two columns and rows fall
+    into the same pixel (0.3 and 0.8; W - 1.9 and W - 1.4).  Label 1 = an L along the left and bottom borders (column 0 below the
+    corner cell, the bottom row without its last cell) and an L along the top and right borders; label 2 = the two corner cells
+    between them and the interior, a diagonal band from corner to corner.  Every box of label 1 is (-1, -1) .. (W - 1, H - 1); the
+    corner cells of label 2 lie inside the interior's box and are absorbed too.  Returns (scene, labels)."""
+    import seam_model as SM
+    n, W, H = 8, 64, 48
+    xs = np.concatenate([[0.3, 0.8], np.linspace(8.0, W - 9.0, n - 4), [W - 1.9, W - 1.4]])
+    ys = np.concatenate([[0.4, 0.9], np.linspace(6.0, H - 7.0, n - 4), [H - 1.8, H - 1.3]])
+    g = SM.grid_scene(n=n, W=W, H=H, xs=xs, ys=ys)
+    ix, iy = _grid_cells(g, n)
+    last = n - 2
+    lower = ((ix == 0) & (iy >= 1)) | ((iy == last) & (ix < last))
+    upper = ((iy == 0) & (ix >= 1)) | ((ix == last) & (iy < last))
+    return g, np.where(lower | upper, 1, 2).astype(np.uint32)
+
+
+def entry_pixels(arrays):
+    """per list entry, the number of pixels adjust_colors visits for it: floor(min) - 1 .. ceil(max) + 1 exclusive, clamped to the
+    patch's frame (0 for a face adjust_colors skips as degenerate).  The device walks an entry of up to 512 pixels with a group of
+    lanes and a larger one with a block (k_texpatch.hip SMALL_MAX)."""
+    tc = np.asarray(arrays["texcoords"], np.float32).reshape(-1, 3, 2)
+    box = np.asarray(arrays["box"]).reshape(-1, 4)
+    pid = np.repeat(np.arange(len(box)), np.diff(np.asarray(arrays["face_ptr"]).astype(np.int64)))
+    w, h = box[pid, 2].astype(np.int64), box[pid, 3].astype(np.int64)
+    x0 = np.maximum(np.floor(tc[..., 0].min(1)).astype(np.int64) - 1, 0); y0 = np.maximum(np.floor(tc[..., 1].min(1)).astype(np.int64) - 1, 0)
+    x1 = np.minimum(np.ceil(tc[..., 0].max(1)).astype(np.int64) + 1, w); y1 = np.minimum(np.ceil(tc[..., 1].max(1)).astype(np.int64) + 1, h)
+    u, v = tc[:, 1] - tc[:, 0], tc[:, 2] - tc[:, 0]
+    area = np.float32(0.5) * np.abs(_f(_f(u[:, 0] * v[:, 1]) - _f(u[:, 1] * v[:, 0])))
+    n = np.maximum(x1 - x0, 0) * np.maximum(y1 - y0, 0)
+    return np.where(area < np.float32(np.finfo(np.float32).eps), 0, n)

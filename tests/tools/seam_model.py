@@ -139,14 +139,17 @@ def face_adjacency(faces):
     return adj_ptr, adj
 
 
-def grid_scene(n=6, W=64, H=48, fin=False, zero_edge=False, outside=False, seed=3):
+def grid_scene(n=6, W=64, H=48, fin=False, zero_edge=False, outside=False, seed=3, xs=None, ys=None):
     """an n x n vertex grid on the plane z = 1 seen by two identical pinhole cameras at the origin (different images): vertex (i, j)
     projects to pixel (xs[i], ys[j]); the first column and row land in [0, 1), so a candidate's frame starts at -1, and the last ones
     just below W - 1 / H - 1.  fin: a third face on an interior edge (non-manifold); zero_edge: a face with two vertices at the same
-    point (an edge of length 0); outside: one vertex projects left of the image."""
+    point (an edge of length 0); outside: one vertex projects left of the image.  xs / ys: the n pixel columns / rows instead of
+    the even spacing."""
     import mvs_texturing_amd as M
     f = 50.0; cx, cy = W / 2.0, H / 2.0
-    xs = np.linspace(0.3, W - 1.6, n); ys = np.linspace(0.4, H - 1.7, n)
+    xs = np.linspace(0.3, W - 1.6, n) if xs is None else np.asarray(xs, np.float64)
+    ys = np.linspace(0.4, H - 1.7, n) if ys is None else np.asarray(ys, np.float64)
+    assert len(xs) == n and len(ys) == n
     verts = [[(x + 0.5 - cx) / f, (y + 0.5 - cy) / f, 1.0] for y in ys for x in xs]
     faces = []
     for j in range(n - 1):
