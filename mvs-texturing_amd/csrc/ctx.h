@@ -236,7 +236,9 @@ struct mvs_ctx {
     // ---- row f3: patch components (k_patch.hip) ----
     mvs::DBuf<uint32_t> p_label_ptr, p_comp_ptr, p_comp_faces, p_parent, p_root, p_state, p_flag, p_pos, p_roots, p_roots2, p_rlab, p_rlab2, p_adj_ptr, p_adj, p_labels;
 
-    // ---- row f5: global seam leveling (k_seam.hip): buffers allocated on first use ----
+    // ---- rows f5 - f8 (k_seam.hip, k_texpatch.hip, k_localseam.hip, k_atlas.hip): per-row buffers allocated on first use; the caller's adjacency
+    // and labels where they arrive as host arrays and the pinned read-back of a patch set's frames are shared (rows.h stage_graph, read_patch_set) ----
+    mvs::DBuf<uint32_t> row_adj_ptr, row_adj, row_labels; mvs::HBuf<char> row_pin;
     mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
 
     // ---- region moves (k_region.hip) ----
@@ -342,6 +344,13 @@ constexpr uint32_t MRF_DAMP_PERIOD = 4;
 // announces them with a sequence number the host spins on (k_mrf.hip).  A 4-byte hipMemcpyAsync into pageable memory + hipStreamSynchronize
 // holds the device idle for 22 us, this for 9 (scripts/probe/readback_cost.hip) -- a step has a dozen of them on its critical path.
 void read_words(mvs_ctx* ctx, const void* d_src, void* out, uint32_t n_words);
+// one word the plain way: a 4-byte copy into pageable memory and a drain of ctx->stream (where that drain is wanted anyway, or off the hot path)
+inline uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
+    uint32_t h = 0;
+    MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MVS_HIP(hipStreamSynchronize(ctx->stream));
+    return h;
+}
 void read_block(mvs_ctx* ctx, const void* d_src, void* out, size_t bytes);   // up to 4 KB, through pinned staging
 // generic device exclusive scan (scan.hip): out[i] = sum_{k<i} in[i]; returns total via d_total (device, may be null)
 void exclusive_scan_u32(mvs_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n, uint32_t* d_total);

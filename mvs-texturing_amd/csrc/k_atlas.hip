@@ -9,16 +9,13 @@
 //             <= n; one launch per sweep over all atlases that still pad (reads: levels <= n, writes: unset pixels -- no race);
 //   texcoords one thread per list entry writes faces and coordinates; two stable radix sorts ((atlas, x) over y) group equal
 //             coordinates with their first occurrence in front; heads ranked by first index give upstream's ids.
-#include "ctx.h"
+#include "rows.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <numeric>
-#include <rocprim/rocprim.hpp>
 
 namespace mvs {
-
-mvs_status api_fail(mvs_status st, const std::string& msg);
 
 // per-context buffers of row f8, allocated on first use, freed with the context (atlas_release)
 struct AtlasDev {
@@ -33,18 +30,6 @@ struct AtlasDev {
     // outputs
     DBuf<uint8_t> image; DBuf<uint32_t> o_atlas_size, o_patch_atlas, o_patch_order, o_face_ptr, faces, o_tc_ptr, ids; DBuf<int32_t> o_patch_pos;
     DBuf<unsigned long long> o_pix_ptr; DBuf<float> texcoords, merged;
-    // the per-patch frames of a device-resident set on the host: one pinned buffer (pix_ptr, box, face_ptr back to back)
-    void* pinned = nullptr; size_t pinned_cap = 0;
-    void* pin(size_t bytes) {
-        if (bytes > pinned_cap) {
-            if (pinned) (void)hipHostFree(pinned);
-            pinned = nullptr; pinned_cap = 0;
-            MVS_HIP(hipHostMalloc(&pinned, bytes + bytes / 2, hipHostMallocDefault));
-            pinned_cap = bytes + bytes / 2;
-        }
-        return pinned;
-    }
-    ~AtlasDev() { if (pinned) (void)hipHostFree(pinned); }
 };
 void atlas_release(mvs_ctx* ctx) { delete ctx->atlas; ctx->atlas = nullptr; }
 
@@ -53,7 +38,6 @@ constexpr uint32_t MAX_SIZE = 8192, PREF_SIZE = 4096, MIN_SIZE = 256;
 constexpr uint32_t CHUNK = 1024;          // pixels of one patch a compose block handles
 enum { K_VALID = 0, K_PADDED, K_BAD_TC, K_N };           // 64-bit counters
 inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }
 
 // ---- pack (on the host: profiles/EXPERIMENTS.md "Row f8: the packer") ----
 struct HostPack { std::vector<uint32_t> atlas, seq, size; std::vector<int2> pos; uint32_t peak = 0; };
@@ -264,32 +248,6 @@ __global__ void at_tcptr_kernel(uint32_t A, const uint32_t* __restrict__ corner_
     if (a <= A) tc_ptr[a] = rank[corner_start[a]];
 }
 
-template <class T>
-T* host_copy(const T* d, size_t n, hipStream_t s) {
-    T* h = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!h) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-    if (n) MVS_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    return h;
-}
-template <class T>
-const T* stage(DBuf<T>& buf, const T* src, size_t n, int on_device, hipStream_t s) {
-    if (on_device) return src;
-    buf.ensure(n + 1);
-    if (n) MVS_HIP(hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return buf.p;
-}
-template <class T>
-void upload(DBuf<T>& buf, const std::vector<T>& h, hipStream_t s) {
-    buf.ensure(h.size() + 1);
-    if (!h.empty()) MVS_HIP(hipMemcpyAsync(buf.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
-template <class T>
-void upload(DBuf<T>& buf, const T* h, size_t n, hipStream_t s) {
-    buf.ensure(n + 1);
-    if (n) MVS_HIP(hipMemcpyAsync(buf.p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-}
-
 // host arrays that asynchronous copies read or write: owned by the caller of run_atlas, which drains the stream before they go
 struct HostTables {
     HostPack H;
@@ -305,9 +263,7 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
                const mvs_atlas_params& P, mvs_atlas_stats& st, mvs_atlas_set& set) {
     hipStream_t s = ctx->stream;
     const uint32_t NP = in.NP, L = in.L;
-    hipEvent_t ev[4];   // compose begins / ends, pad ends, texcoords end
-    for (auto& e : ev) MVS_HIP(hipEventCreate(&e));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 4; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
+    StageTimer<4> tm(s);   // marks: compose begins / ends, pad ends, texcoords end
     // ---- pack (host time: ordering, packing, the per-patch tables and their uploads) ----
     const double t_pack = now_ms_host();
     // item 1: popped from the back, then a stable sort by size, descending
@@ -338,7 +294,7 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
     // the per-patch tables: placement, insertion order, output face ranges
     std::vector<int4>& h_place = T.place; std::vector<uint32_t>& h_patch_atlas = T.patch_atlas; std::vector<uint32_t>& h_ord_patch = T.ord_patch;
     std::vector<uint32_t>& h_ord_ptr = T.ord_ptr; std::vector<uint32_t>& h_face_ptr = T.face_ptr; std::vector<uint32_t>& h_corner = T.corner;
-    std::vector<int32_t>& h_pos = T.pos; std::vector<uint32_t>& h_chunk_ptr = T.chunk_ptr; std::vector<uint32_t>& h_chunk_patch = T.chunk_patch;
+    std::vector<int32_t>& h_pos = T.pos;
     h_place.assign(NP, make_int4(0, 0, 0, 0)); h_patch_atlas.assign(NP, 0u); h_ord_patch.assign(NP, 0u); h_ord_ptr.assign((size_t)NP + 1, 0u);
     h_face_ptr.assign((size_t)A + 1, 0u); h_corner.assign((size_t)A + 1, 0u); h_pos.assign(2 * (size_t)NP, 0);
     for (uint32_t k = 0; k < NP; ++k) {
@@ -357,21 +313,15 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
         h_face_ptr[h_patch_atlas[p] + 1] = h_ord_ptr[k + 1];   // insertion order is grouped by atlas, and every atlas holds a patch
     }
     for (uint32_t a = 0; a <= A; ++a) h_corner[a] = 3u * h_face_ptr[a];
-    h_chunk_ptr.assign((size_t)NP + 1, 0u); h_chunk_patch.clear();
-    for (uint32_t p = 0; p < NP; ++p) {
-        const uint32_t nc = (uint32_t)((hp[p + 1] - hp[p] + CHUNK - 1) / CHUNK);
-        h_chunk_ptr[p + 1] = h_chunk_ptr[p] + nc;
-        h_chunk_patch.insert(h_chunk_patch.end(), nc, p);
-    }
-    const uint32_t NC = h_chunk_ptr[NP];
     upload(D.place, h_place, s); upload(D.abase, h_abase, s); upload(D.asize, h_size, s); upload(D.ppix, hp, (size_t)NP + 1, s);
-    upload(D.chunk_ptr, h_chunk_ptr, s); upload(D.chunk_patch, h_chunk_patch, s); upload(D.ord_patch, h_ord_patch, s); upload(D.ord_ptr, h_ord_ptr, s);
+    const uint32_t NC = upload_chunk_tables(ctx, hp, NP, CHUNK, T.chunk_ptr, T.chunk_patch, D.chunk_ptr, D.chunk_patch);
+    upload(D.ord_patch, h_ord_patch, s); upload(D.ord_ptr, h_ord_ptr, s);
     upload(D.in_face_ptr, hf, (size_t)NP + 1, s); upload(D.corner_start, h_corner, s); upload(D.wh, h_wh_patch, s);
     upload(D.o_atlas_size, h_size, s); upload(D.o_pix_ptr, h_abase, s); upload(D.o_patch_atlas, h_patch_atlas, s); upload(D.o_patch_pos, h_pos, s);
     upload(D.o_patch_order, h_ord_patch, s); upload(D.o_face_ptr, h_face_ptr, s);
     st.ms_pack = (float)(now_ms_host() - t_pack);
     // ---- compose (device time from here on: clearing image, mask and levels; quantise and scatter) ----
-    MVS_HIP(hipEventRecord(ev[0], s));
+    tm.mark();
     D.image.ensure(3 * (size_t)NPIXA + 3); D.mask.ensure((size_t)NPIXA + 1); D.lev.ensure((size_t)NPIXA + 1); D.c64.ensure(K_N);
     MVS_HIP(hipMemsetAsync(D.c64.p, 0, K_N * sizeof(unsigned long long), s));
     if (NPIXA) {
@@ -385,7 +335,7 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
                            D.image.p, D.mask.p, D.lev.p, D.c64.p);
         MVS_LAUNCH_CHECK();
     }
-    MVS_HIP(hipEventRecord(ev[1], s));
+    tm.mark();
     // ---- pad ----
     uint32_t max_pad = 0;
     for (uint32_t a = 0; a < A; ++a) max_pad = std::max(max_pad, h_size[a] >> 7);
@@ -397,7 +347,7 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
             MVS_LAUNCH_CHECK();
         }
     }
-    MVS_HIP(hipEventRecord(ev[2], s));
+    tm.mark();
     // ---- texcoords and merge_texcoords ----
     const uint32_t NCR = 3u * L;
     D.faces.ensure((size_t)L + 1); D.texcoords.ensure(6 * (size_t)L + 6); D.entry_atlas.ensure((size_t)L + 1); D.ids.ensure((size_t)NCR + 1); D.merged.ensure(2 * (size_t)NCR + 2);
@@ -409,27 +359,15 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
         hipLaunchKernelGGL(at_texcoord_kernel, dim3(grid(L)), dim3(256), 0, s, L, NP, (const uint32_t*)D.ord_ptr.p, (const uint32_t*)D.ord_patch.p, (const uint32_t*)D.in_face_ptr.p,
                            in.faces, in.texcoords, (const int4*)D.place.p, D.faces.p, D.texcoords.p, D.entry_atlas.p, D.ykey.p, D.idx.p, D.c64.p);
         MVS_LAUNCH_CHECK();
-        size_t tmp = 0;
-        MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, D.ykey.p, D.ykey2.p, D.idx.p, D.idx2.p, (size_t)NCR, 0, 32, s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp, D.ykey.p, D.ykey2.p, D.idx.p, D.idx2.p, (size_t)NCR, 0, 32, s));
+        dev_sort_pairs(ctx, D.ykey.p, D.ykey2.p, D.idx.p, D.idx2.p, (size_t)NCR, 0, 32);
         hipLaunchKernelGGL(at_xkey_kernel, dim3(grid(NCR)), dim3(256), 0, s, NCR, (const uint32_t*)D.idx2.p, (const float*)D.texcoords.p, (const uint32_t*)D.entry_atlas.p, D.xkey.p);
         MVS_LAUNCH_CHECK();
-        tmp = 0;
-        MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, D.xkey.p, D.xkey2.p, D.idx2.p, D.idx.p, (size_t)NCR, 0, 64, s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp, D.xkey.p, D.xkey2.p, D.idx2.p, D.idx.p, (size_t)NCR, 0, 64, s));
+        dev_sort_pairs(ctx, D.xkey.p, D.xkey2.p, D.idx2.p, D.idx.p, (size_t)NCR, 0, 64);
         hipLaunchKernelGGL(at_head_kernel, dim3(grid((size_t)NCR + 1)), dim3(256), 0, s, NCR, (const uint32_t*)D.idx.p, (const unsigned long long*)D.xkey2.p,
                            (const float*)D.texcoords.p, D.headpos.p, D.first.p);
         MVS_LAUNCH_CHECK();
-        tmp = 0;
-        MVS_HIP(rocprim::inclusive_scan(nullptr, tmp, D.headpos.p, D.ykey.p, (size_t)NCR, rocprim::maximum<uint32_t>(), s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::inclusive_scan(ctx->sort_tmp.p, tmp, D.headpos.p, D.ykey.p, (size_t)NCR, rocprim::maximum<uint32_t>(), s));   // ykey: the head's position, per sorted position
-        tmp = 0;
-        MVS_HIP(rocprim::exclusive_scan(nullptr, tmp, D.first.p, D.rank.p, 0u, (size_t)NCR + 1, rocprim::plus<uint32_t>(), s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, D.first.p, D.rank.p, 0u, (size_t)NCR + 1, rocprim::plus<uint32_t>(), s));
+        dev_inclusive_max_scan(ctx, D.headpos.p, D.ykey.p, (size_t)NCR);   // ykey: the head's position, per sorted position
+        dev_exclusive_scan(ctx, D.first.p, D.rank.p, (size_t)NCR + 1);
         hipLaunchKernelGGL(at_ids_kernel, dim3(grid(NCR)), dim3(256), 0, s, NCR, (const uint32_t*)D.idx.p, (const uint32_t*)D.ykey.p, (const uint32_t*)D.rank.p,
                            (const uint32_t*)D.first.p, (const uint32_t*)D.entry_atlas.p, (const uint32_t*)D.corner_start.p, (const float*)D.texcoords.p, D.ids.p, D.merged.p);
         MVS_LAUNCH_CHECK();
@@ -439,16 +377,14 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
     } else {
         MVS_HIP(hipMemsetAsync(D.o_tc_ptr.p, 0, ((size_t)A + 1) * sizeof(uint32_t), s));
     }
-    MVS_HIP(hipEventRecord(ev[3], s));
+    tm.mark();
     unsigned long long* c64 = T.c64;
     MVS_HIP(hipMemcpyAsync(c64, D.c64.p, K_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipStreamSynchronize(s));
     if (c64[K_BAD_TC]) throw StatusError(MVS_ERR_UNSUPPORTED, "texture_atlases: texture coordinates that are not finite");
     st.valid_pixels = c64[K_VALID]; st.padded_pixels = c64[K_PADDED]; st.merged_texcoords = n_merged;
-    float ms[3] = {0.0f, 0.0f, 0.0f};
-    for (int k = 0; k < 3; ++k) MVS_HIP(hipEventElapsedTime(ms + k, ev[k], ev[k + 1]));
-    st.ms_compose = ms[0]; st.ms_pad = ms[1]; st.ms_texcoords = ms[2];
-    st.ms_total = st.ms_pack + ms[0] + ms[1] + ms[2];
+    st.ms_compose = tm.ms(0, 1); st.ms_pad = tm.ms(1, 2); st.ms_texcoords = tm.ms(2, 3);
+    st.ms_total = st.ms_pack + st.ms_compose + st.ms_pad + st.ms_texcoords;
     set.n_atlases = A; set.n_patches = NP; set.n_listed = L; set.n_merged = n_merged; set.n_pixels = NPIXA;
 }
 
@@ -470,7 +406,7 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
     *out = mvs_atlas_set{};
     mvs_atlas_stats st{};
     if (stats) *stats = st;
-    try {
+    return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         if (!ctx->atlas) ctx->atlas = new AtlasDev();
@@ -480,34 +416,12 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
         const mvs_patch_set& in = *patches;
         const uint32_t NP = in.n_patches, L = in.n_listed;
         const uint64_t NPIX = in.n_pixels;
-        if (NP && (!in.box || !in.face_ptr || !in.pix_ptr)) throw StatusError(MVS_ERR_INVALID, "texture_atlases: null array in the patch set");
-        if (L && (!in.faces || !in.texcoords)) throw StatusError(MVS_ERR_INVALID, "texture_atlases: null array in the patch set");
-        if (NPIX && (!in.image || !in.validity)) throw StatusError(MVS_ERR_INVALID, "texture_atlases: null array in the patch set");
+        const PatchFrames h = read_patch_set(ctx, in, patches_on_device, false, "texture_atlases");   // the per-patch frames on the host
+        const int4* hb = h.box; const unsigned long long* hp = h.pix_ptr; const uint32_t* hf = h.face_ptr;
         if ((uint64_t)L * 3u >= 0xFFFFFF00ull) throw StatusError(MVS_ERR_UNSUPPORTED, "texture_atlases: too many list entries for one call");
-        // the per-patch frames on the host: the caller's own arrays, or ONE pinned read-back (pix_ptr, box, face_ptr back to back in a
-        // buffer the context owns)
-        static const unsigned long long zero64 = 0ull; static const uint32_t zero32 = 0u;
-        const int4* hb = nullptr; const unsigned long long* hp = &zero64; const uint32_t* hf = &zero32;
-        if (NP) {
-            const size_t b_pix = ((size_t)NP + 1) * sizeof(unsigned long long), b_box = (size_t)NP * sizeof(int4), b_face = ((size_t)NP + 1) * sizeof(uint32_t);
-            char* pin = (char*)D.pin(b_pix + b_box + b_face);
-            if (patches_on_device) {
-                MVS_HIP(hipMemcpyAsync(pin, in.pix_ptr, b_pix, hipMemcpyDeviceToHost, s));
-                MVS_HIP(hipMemcpyAsync(pin + b_pix, in.box, b_box, hipMemcpyDeviceToHost, s));
-                MVS_HIP(hipMemcpyAsync(pin + b_pix + b_box, in.face_ptr, b_face, hipMemcpyDeviceToHost, s));
-                MVS_HIP(hipStreamSynchronize(s));
-            } else {
-                memcpy(pin, in.pix_ptr, b_pix); memcpy(pin + b_pix, in.box, b_box); memcpy(pin + b_pix + b_box, in.face_ptr, b_face);
-            }
-            hp = (const unsigned long long*)pin; hb = (const int4*)(pin + b_pix); hf = (const uint32_t*)(pin + b_pix + b_box);
-        }
-        if (hp[0] != 0 || hf[0] != 0 || hp[NP] != NPIX || hf[NP] != L) throw StatusError(MVS_ERR_INVALID, "texture_atlases: pix_ptr / face_ptr do not match the totals");
-        for (uint32_t p = 0; p < NP; ++p) {
-            if (hb[p].z < 1 || hb[p].w < 1 || hp[p + 1] < hp[p] || hp[p + 1] - hp[p] != (unsigned long long)hb[p].z * (unsigned long long)hb[p].w || hf[p + 1] < hf[p])
-                throw StatusError(MVS_ERR_INVALID, "texture_atlases: patch " + std::to_string(p) + ": frame, pix_ptr and face_ptr do not agree");
+        for (uint32_t p = 0; p < NP; ++p)
             if (hb[p].z + 128 >= (int)MAX_SIZE || hb[p].w + 128 >= (int)MAX_SIZE)
                 throw StatusError(MVS_ERR_UNSUPPORTED, "texture_atlases: patch " + std::to_string(p) + " does not fit the largest atlas (upstream's assertion)");
-        }
         Input I{NP, L, NPIX, nullptr, nullptr, nullptr, nullptr};
         I.faces = stage(D.in_faces, (const uint32_t*)in.faces, L, patches_on_device, s);
         I.texcoords = stage(D.in_texcoords, (const float*)in.texcoords, 6 * (size_t)L, patches_on_device, s);
@@ -516,10 +430,7 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
         MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
         mvs_atlas_set set{};
         HostTables T;                       // outlives the drain of the stream below
-        try {
-            run_atlas(ctx, D, I, hb, hp, hf, T, P, st, set);
-        } catch (...) { (void)hipStreamSynchronize(s); if (stats) *stats = st; throw; }
-        if (stats) *stats = st;
+        run_with_stats(s, stats, st, [&] { run_atlas(ctx, D, I, hb, hp, hf, T, P, st, set); });
         *out = set;
         const size_t A = set.n_atlases, NC = 3 * (size_t)L;
         if (out_on_device) {
@@ -527,20 +438,16 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
             out->patch_pos = D.o_patch_pos.p; out->patch_order = D.o_patch_order.p; out->face_ptr = D.o_face_ptr.p; out->faces = D.faces.p; out->texcoords = D.texcoords.p;
             out->tc_ptr = D.o_tc_ptr.p; out->texcoords_merged = D.merged.p; out->texcoord_ids = D.ids.p;
         } else {
-            try {
+            download(s, out, mvs_atlas_set_free, [&] {
                 out->atlas_size = host_copy(D.o_atlas_size.p, A, s); out->atlas_pix_ptr = (uint64_t*)host_copy(D.o_pix_ptr.p, A + 1, s);
                 out->image = host_copy(D.image.p, 3 * (size_t)set.n_pixels, s); out->patch_atlas = host_copy(D.o_patch_atlas.p, NP, s);
                 out->patch_pos = host_copy(D.o_patch_pos.p, 2 * (size_t)NP, s); out->patch_order = host_copy(D.o_patch_order.p, NP, s);
                 out->face_ptr = host_copy(D.o_face_ptr.p, A + 1, s); out->faces = host_copy(D.faces.p, L, s); out->texcoords = host_copy(D.texcoords.p, 2 * NC, s);
                 out->tc_ptr = host_copy(D.o_tc_ptr.p, A + 1, s); out->texcoords_merged = host_copy(D.merged.p, 2 * (size_t)set.n_merged, s);
                 out->texcoord_ids = host_copy(D.ids.p, NC, s);
-                MVS_HIP(hipStreamSynchronize(s));
-            } catch (...) { (void)hipStreamSynchronize(s); mvs_atlas_set_free(out); throw; }
+            });
         }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    });
 }
 
 void mvs_atlas_set_free(mvs_atlas_set* a) {

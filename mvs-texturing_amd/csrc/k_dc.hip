@@ -861,7 +861,7 @@ __global__ void set_count_kernel(uint32_t* __restrict__ hist, uint32_t n) { hist
 
 }  // namespace
 
-static uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
+static uint32_t read_word(mvs_ctx* ctx, const uint32_t* d) {   // one word through the pinned route of read_words (ctx.h read_u32 is the plain copy)
     uint32_t h = 0;
     read_words(ctx, d, &h, 1);
     return h;
@@ -1007,7 +1007,7 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
         throw StatusError(MVS_ERR_UNSUPPORTED, "more than 2^32 (face, view) pairs pass the culls in one context: evaluate the faces in ranges (mvs_scene_set_face_range)");
     exclusive_scan_u32(ctx, ctx->pass_base.p, ctx->pass_base.p, pw, d_total);
     pr_rank.end();
-    const uint32_t n_pass = read_u32(ctx, d_total);
+    const uint32_t n_pass = read_word(ctx, d_total);
     if (scene_order_commit(ctx)) return true;                 // (the stream is drained here anyway) the order was rebuilt: once more from the top
     ctx->pq.ensure((size_t)n_pass + 1);
     if (outl) ctx->pcol.ensure(3 * ((size_t)n_pass + 1));
@@ -1042,7 +1042,7 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
         hipLaunchKernelGGL(popc_kernel, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, s, defer_bits, ctx->defer_base.p, pw); MVS_LAUNCH_CHECK();
         uint32_t* d_total2 = (uint32_t*)(ctx->max_q.p + 3);
         exclusive_scan_u32(ctx, ctx->defer_base.p, ctx->defer_base.p, pw, d_total2);
-        const uint32_t n_def = read_u32(ctx, d_total2);
+        const uint32_t n_def = read_word(ctx, d_total2);
         ctx->dc_stats_deferred = n_def;
         if (n_def) {
             ctx->defer_list.ensure((size_t)n_def + 1);
@@ -1073,7 +1073,7 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
     DBuf<uint32_t>& ptr = outl ? ctx->pre_ptr : ctx->csr_ptr;
     ptr.ensure((size_t)nf + 2);
     exclusive_scan_u32(ctx, ctx->face_cnt.p, ptr.p, (size_t)nf + 1, nullptr);
-    const uint32_t nnz_pre = read_u32(ctx, ptr.p + nf);
+    const uint32_t nnz_pre = read_word(ctx, ptr.p + nf);
     ctx->dc_stats.nnz_pre = nnz_pre;
     if (outl) {
         ctx->pre_view.ensure((size_t)nnz_pre + 1); ctx->pre_q.ensure((size_t)nnz_pre + 1); ctx->pre_col.ensure(3 * ((size_t)nnz_pre + 1));
@@ -1086,7 +1086,7 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
         MVS_LAUNCH_CHECK();
         ctx->csr_ptr.ensure((size_t)nf + 2);
         exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)nf + 1, nullptr);
-        const uint32_t nnz = read_u32(ctx, ctx->csr_ptr.p + nf);
+        const uint32_t nnz = read_word(ctx, ctx->csr_ptr.p + nf);
         ctx->csr_view.ensure((size_t)nnz + 1); ctx->csr_q.ensure((size_t)nnz + 1); ctx->csr_cost.ensure((size_t)nnz + 1);
         hipLaunchKernelGGL(nonzero_copy_kernel, dim3(((nf + 63u) / 64u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, ctx->csr_ptr.p, nf, ctx->pre_view.p, ctx->pre_q.p,
                            ctx->csr_view.p, ctx->csr_q.p);
@@ -1247,7 +1247,7 @@ void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t*
         hipLaunchKernelGGL(nonzero_count_kernel, dim3((nf / 64u + 1u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, nf, ctx->pre_q.p, ctx->face_cnt.p);
         MVS_LAUNCH_CHECK();
         exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)nf + 1, nullptr);
-        nnz = read_u32(ctx, ctx->csr_ptr.p + nf);
+        nnz = read_word(ctx, ctx->csr_ptr.p + nf);
     } else MVS_HIP(hipMemcpyAsync(ctx->csr_ptr.p, ctx->pre_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     ctx->csr_view.ensure((size_t)nnz + 1); ctx->csr_q.ensure((size_t)nnz + 1); ctx->csr_cost.ensure((size_t)nnz + 8);
     if (nf) {
@@ -1278,7 +1278,7 @@ static void launch_outlier(mvs_ctx* ctx, const uint32_t* ptr, const uint32_t* co
         uint32_t* d = reinterpret_cast<uint32_t*>(ctx->counters.p + 48);
         MVS_HIP(hipMemsetAsync(d, 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(max_u32_kernel, dim3(std::min<unsigned>((nf + 255) / 256, 1024u)), dim3(256), 0, s, counts, nf, d); MVS_LAUNCH_CHECK();
-        kmax = read_u32(ctx, d);
+        kmax = read_word(ctx, d);
     }
     const uint64_t lds = (uint64_t)std::max<uint32_t>(kmax, 1u) * LDS_PER_ENTRY;
     if (lds <= 64u * 1024u) hipLaunchKernelGGL(outlier_kernel<true>, dim3((nf + 63) / 64), dim3(64), (size_t)lds, s, ptr, nf, col, q, inl, mode, std::max<uint32_t>(kmax, 1u));
@@ -1342,7 +1342,7 @@ void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax) {
     ctx->face_cnt.ensure((size_t)nf + 2); ctx->pre_ptr.ensure((size_t)nf + 2);
     hipLaunchKernelGGL(prune_count_kernel, dim3((nf + 256) / 256), dim3(256), 0, s, ctx->csr_ptr.p, nf, kmax, ctx->face_cnt.p); MVS_LAUNCH_CHECK();
     exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->pre_ptr.p, (size_t)nf + 1, nullptr);
-    const uint32_t nnz2 = read_u32(ctx, ctx->pre_ptr.p + nf);
+    const uint32_t nnz2 = read_word(ctx, ctx->pre_ptr.p + nf);
     if (nnz2 == ctx->csr_nnz) return;                          // no column is longer than kmax
     ctx->pre_view.ensure((size_t)nnz2 + 1); ctx->pre_q.ensure((size_t)nnz2 + 1); ctx->pcol.ensure((size_t)nnz2 + 8);
     if (nf) {

@@ -14,20 +14,17 @@
 //             recomputed instead of stored, the three channels together with their own scalars and stop state, every dot product
 //             by the one tree of the definition (lane l of 1024 adds unknowns l, l + 1024, ... in order; the lanes halve): a workgroup of 256
 //             owns four lanes per thread (LDS), one of 1024 one each (global memory).
-#include "ctx.h"
+#include "rows.h"
 #include <cfloat>
 #include <climits>
 #include <cmath>
-#include <rocprim/rocprim.hpp>
 
 namespace mvs {
-
-mvs_status api_fail(mvs_status st, const std::string& msg);
 
 // per-context buffers of row f7, allocated on first use, freed with the context (lsl_release)
 struct LslDev {
     // staged inputs (host callers)
-    DBuf<uint32_t> adj_ptr, adj, labels, in_label, in_face_ptr, in_faces; DBuf<int4> in_box; DBuf<float> in_texcoords, in_image;
+    DBuf<uint32_t> in_label, in_face_ptr, in_faces; DBuf<int4> in_box; DBuf<float> in_texcoords, in_image;
     DBuf<unsigned long long> in_pix_ptr; DBuf<uint8_t> in_validity, in_blending;
     // topology
     DBuf<uint32_t> epid, flag, idx, info_head, vptr, sflag, sidx, edge_v, ep_cnt, ep_ptr, ep_patch, ep_c1, ep_c2, ep_edge, en, ecol_ptr, flags;
@@ -48,7 +45,6 @@ constexpr uint32_t MAX_SAMPLES = 1u << 22;    // samples of one edge at most (te
 constexpr float TC_MAX = 1048576.0f;
 enum { F_FACE = 0, F_LABEL, F_VERTEX, F_ADJ, F_TC, F_N };   // flag words
 enum { K_SKIPPED = 0, K_SAMPLES, K_BAD_SAMPLES, K_VWRITES, K_LWRITES, K_WRITTEN, K_OUTSIDE, K_BAD_WRITES, K_STRIP, K_FIXED, K_DEMOTED, K_NSAMPLES, K_N };   // 64-bit counters
-inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }
 
 struct Patches {   // the patch set on the device
     uint32_t P, L; const uint32_t* label; const int4* box; const uint32_t* face_ptr; const uint32_t* faces; const float* texcoords;
@@ -509,38 +505,16 @@ __global__ void __launch_bounds__(THREADS) ls_solve_kernel(Patches S, const uint
 }
 #undef LS_FOR_UNKNOWNS
 
-template <class T>
-T* host_copy(const T* d, size_t n, hipStream_t s) {
-    T* h = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!h) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-    if (n) MVS_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    return h;
-}
 struct ToU32 { __host__ __device__ uint32_t operator()(uint8_t v) const { return (uint32_t)v; } };
-template <class It>
-void scan_u32(mvs_ctx* ctx, It in, uint32_t* out, size_t n) {   // exclusive, n entries (the callers pass one entry more than they flag)
-    size_t tmp = 0;
-    MVS_HIP(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-    ctx->sort_tmp.ensure(tmp + 16);
-    MVS_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), ctx->stream));
-}
-uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
-    uint32_t h = 0;
-    MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-    return h;
-}
 
-// hp: host copy of pix_ptr (checked by the caller)
+// hp: host copy of pix_ptr (checked by the caller); the exclusive scans run over one entry more than their kernels flag: the total lands there
 void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, uint32_t E, const uint32_t* d_labels, const Patches& S,
-             const std::vector<unsigned long long>& hp, const mvs_lsl_params& P, mvs_lsl_stats& st) {
+             const unsigned long long* hp, const mvs_lsl_params& P, mvs_lsl_stats& st) {
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces, NV = ctx->n_verts, NP = S.P, L = S.L;
     const size_t NPIX = (size_t)hp[NP];
-    hipEvent_t ev[6];
-    for (auto& e : ev) MVS_HIP(hipEventCreate(&e));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
-    MVS_HIP(hipEventRecord(ev[0], s));
+    StageTimer<6> tm(s);   // marks: begin, topology, colours, writes, masks, solve
+    tm.mark();
     D.flags.ensure(F_N); D.c64.ensure(K_N);
     MVS_HIP(hipMemsetAsync(D.flags.p, 0, F_N * sizeof(uint32_t), s));
     MVS_HIP(hipMemsetAsync(D.c64.p, 0, K_N * sizeof(unsigned long long), s));
@@ -560,15 +534,10 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
     D.vptr.ensure((size_t)NV + 2);
     if (L) { hipLaunchKernelGGL(ls_entry_kernel, dim3(grid(L)), dim3(256), 0, s, S, (const uint32_t*)ctx->d_faces, d_labels, F, NV, D.epid.p, D.keys.p, D.flags.p); MVS_LAUNCH_CHECK(); }
     check_flags();
-    if (NK) {
-        size_t tmp = 0;
-        MVS_HIP(rocprim::radix_sort_keys(nullptr, tmp, D.keys.p, D.keys2.p, (size_t)NK, 0, 64, s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_keys(ctx->sort_tmp.p, tmp, D.keys.p, D.keys2.p, (size_t)NK, 0, 64, s));
-    }
+    if (NK) dev_sort_keys(ctx, D.keys.p, D.keys2.p, (size_t)NK, 0, 64);
     const unsigned long long* keys = D.keys2.p;
     hipLaunchKernelGGL(ls_head_kernel, dim3(grid((size_t)NK + 1)), dim3(256), 0, s, keys, NK, (const uint32_t*)D.epid.p, D.flag.p); MVS_LAUNCH_CHECK();
-    scan_u32(ctx, (const uint32_t*)D.flag.p, D.idx.p, (size_t)NK + 1);
+    dev_exclusive_scan(ctx, (const uint32_t*)D.flag.p, D.idx.p, (size_t)NK + 1);
     const uint32_t NI = read_u32(ctx, D.idx.p + NK);
     D.info_head.ensure((size_t)NI + 1);
     if (NK) { hipLaunchKernelGGL(ls_info_kernel, dim3(grid(NK)), dim3(256), 0, s, (const uint32_t*)D.flag.p, (const uint32_t*)D.idx.p, NK, D.info_head.p); MVS_LAUNCH_CHECK(); }
@@ -577,7 +546,7 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
     hipLaunchKernelGGL(ls_seam_kernel, dim3(grid((size_t)E + 1)), dim3(256), 0, s, d_adj_ptr, d_adj, d_labels, (const uint32_t*)ctx->d_faces, F, NV, E, 0, D.sflag.p,
                        (const uint32_t*)nullptr, (uint32_t*)nullptr, D.flags.p, D.c64.p);
     MVS_LAUNCH_CHECK();
-    scan_u32(ctx, (const uint32_t*)D.sflag.p, D.sidx.p, (size_t)E + 1);
+    dev_exclusive_scan(ctx, (const uint32_t*)D.sflag.p, D.sidx.p, (size_t)E + 1);
     check_flags();
     const uint32_t NE = read_u32(ctx, D.sidx.p + E);
     D.edge_v.ensure(2 * (size_t)NE + 2); D.ep_cnt.ensure((size_t)NE + 2); D.ep_ptr.ensure((size_t)NE + 2); D.en.ensure((size_t)NE + 2); D.ecol_ptr.ensure((size_t)NE + 2);
@@ -593,11 +562,11 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
             MVS_LAUNCH_CHECK();
         };
         eproj(0);
-        scan_u32(ctx, (const uint32_t*)D.ep_cnt.p, D.ep_ptr.p, (size_t)NE + 1);
+        dev_exclusive_scan(ctx, (const uint32_t*)D.ep_cnt.p, D.ep_ptr.p, (size_t)NE + 1);
         NEP = read_u32(ctx, D.ep_ptr.p + NE);
         D.ep_patch.ensure((size_t)NEP + 1); D.ep_c1.ensure((size_t)NEP + 1); D.ep_c2.ensure((size_t)NEP + 1); D.ep_edge.ensure((size_t)NEP + 1);
         eproj(1);
-        scan_u32(ctx, (const uint32_t*)D.en.p, D.ecol_ptr.p, (size_t)NE + 1);
+        dev_exclusive_scan(ctx, (const uint32_t*)D.en.p, D.ecol_ptr.p, (size_t)NE + 1);
         check_flags();
         unsigned long long total = 0;
         MVS_HIP(hipMemcpyAsync(&total, D.c64.p + K_NSAMPLES, sizeof(total), hipMemcpyDeviceToHost, s));
@@ -607,7 +576,7 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
     }
     if ((unsigned long long)NI + NEP >= 0xFFFFFFF0ull) throw StatusError(MVS_ERR_UNSUPPORTED, "local_seam_leveling: too many writers for one call");
     st.seam_edges = NE; st.vertex_infos = NI; st.edge_projections = NEP;
-    MVS_HIP(hipEventRecord(ev[1], s));
+    tm.mark();
     // ---- colours ----
     D.ecol.ensure(3 * (size_t)NS + 3); D.vcol.ensure(3 * (size_t)NV + 3);
     if (NS) {
@@ -620,7 +589,7 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
                            keys, (const uint32_t*)D.epid.p, S, D.vcol.p, D.c64.p);
         MVS_LAUNCH_CHECK();
     }
-    MVS_HIP(hipEventRecord(ev[2], s));
+    tm.mark();
     // ---- writes ----
     D.win.ensure(NPIX + 1); D.image.ensure(3 * NPIX + 3); D.blendw.ensure(NPIX + 1); D.mask.ensure(NPIX + 1); D.validity.ensure(NPIX + 1);
     D.hv.ensure(NPIX + 1); D.unk.ensure(NPIX + 2); D.rank.ensure(NPIX + 2);
@@ -642,18 +611,11 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
         LS_WRITE(1)
 #undef LS_WRITE
     }
-    MVS_HIP(hipEventRecord(ev[3], s));
+    tm.mark();
     // ---- masks ----
-    std::vector<uint32_t> h_chunk_ptr((size_t)NP + 1, 0), h_chunk_patch;
-    for (uint32_t p = 0; p < NP; ++p) {
-        const uint32_t nc = (uint32_t)((hp[p + 1] - hp[p] + CHUNK - 1) / CHUNK);
-        h_chunk_ptr[p + 1] = h_chunk_ptr[p] + nc;
-        h_chunk_patch.insert(h_chunk_patch.end(), nc, p);
-    }
-    const uint32_t NC = h_chunk_ptr[NP];
-    D.chunk_ptr.ensure((size_t)NP + 2); D.chunk_patch.ensure((size_t)NC + 1); D.n_unk.ensure((size_t)NP + 1);
-    MVS_HIP(hipMemcpyAsync(D.chunk_ptr.p, h_chunk_ptr.data(), ((size_t)NP + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (NC) MVS_HIP(hipMemcpyAsync(D.chunk_patch.p, h_chunk_patch.data(), (size_t)NC * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    std::vector<uint32_t> h_chunk_ptr, h_chunk_patch;   // read by the uploads: alive until the drain at the end of this phase
+    const uint32_t NC = upload_chunk_tables(ctx, hp, NP, CHUNK, h_chunk_ptr, h_chunk_patch, D.chunk_ptr, D.chunk_patch);
+    D.n_unk.ensure((size_t)NP + 1);
     std::vector<uint32_t> h_unk(NP, 0);
     if (NC) {
         const int strip = (int)P.strip_width;
@@ -665,11 +627,11 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
                            D.unk.p, D.validity.p, D.c64.p);
         MVS_LAUNCH_CHECK();
         MVS_HIP(hipMemsetAsync(D.unk.p + NPIX, 0, 1, s));
-        scan_u32(ctx, rocprim::make_transform_iterator((const uint8_t*)D.unk.p, ToU32()), D.rank.p, NPIX + 1);
+        dev_exclusive_scan(ctx, rocprim::make_transform_iterator((const uint8_t*)D.unk.p, ToU32()), D.rank.p, NPIX + 1);
         hipLaunchKernelGGL(ls_count_kernel, dim3(grid(NP)), dim3(256), 0, s, S, (const uint32_t*)D.rank.p, D.n_unk.p); MVS_LAUNCH_CHECK();
         MVS_HIP(hipMemcpyAsync(h_unk.data(), D.n_unk.p, (size_t)NP * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
-    MVS_HIP(hipEventRecord(ev[4], s));
+    tm.mark();
     MVS_HIP(hipStreamSynchronize(s));
     // ---- solve: patches with unknowns, largest working set first; tiers of LDS, the rest in global memory ----
     D.iters.ensure(3 * (size_t)NP + 3); D.err.ensure(3 * (size_t)NP + 3);
@@ -706,7 +668,7 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
             a = b;
         }
     }
-    MVS_HIP(hipEventRecord(ev[5], s));
+    tm.mark();
     std::vector<uint32_t> h_it(3 * (size_t)NP); std::vector<float> h_err(3 * (size_t)NP);
     unsigned long long c64[K_N];
     if (NP) {
@@ -727,25 +689,8 @@ void run_lsl(mvs_ctx* ctx, LslDev& D, const uint32_t* d_adj_ptr, const uint32_t*
     st.skipped_pairs = c64[K_SKIPPED]; st.colour_samples = c64[K_SAMPLES]; st.invalid_samples = c64[K_BAD_SAMPLES];
     st.vertex_writes = c64[K_VWRITES]; st.line_writes = c64[K_LWRITES]; st.written_pixels = c64[K_WRITTEN]; st.outside_frame = c64[K_OUTSIDE];
     st.invalid_writes = c64[K_BAD_WRITES]; st.strip_pixels = c64[K_STRIP]; st.fixed_pixels = c64[K_FIXED]; st.demoted = c64[K_DEMOTED];
-    float ms[5];
-    for (int k = 0; k < 5; ++k) MVS_HIP(hipEventElapsedTime(ms + k, ev[k], ev[k + 1]));
-    st.ms_topology = ms[0]; st.ms_colours = ms[1]; st.ms_writes = ms[2]; st.ms_mask = ms[3]; st.ms_solve = ms[4];
-    MVS_HIP(hipEventElapsedTime(&st.ms_total, ev[0], ev[5]));
-}
-
-template <class T>
-const T* stage(DBuf<T>& buf, const T* src, size_t n, int on_device, hipStream_t s) {
-    if (on_device) return src;
-    buf.ensure(n + 1);
-    if (n) MVS_HIP(hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return buf.p;
-}
-template <class T>
-void to_host(std::vector<T>& h, const T* src, size_t n, int on_device, hipStream_t s) {
-    h.resize(n);
-    if (!n) return;
-    if (on_device) MVS_HIP(hipMemcpyAsync(h.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    else memcpy(h.data(), src, n * sizeof(T));
+    st.ms_topology = tm.ms(0, 1); st.ms_colours = tm.ms(1, 2); st.ms_writes = tm.ms(2, 3); st.ms_mask = tm.ms(3, 4); st.ms_solve = tm.ms(4, 5);
+    st.ms_total = tm.ms(0, 5);
 }
 
 }  // namespace
@@ -770,7 +715,7 @@ mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, co
     *out = mvs_lsl_result{};
     mvs_lsl_stats st{};
     if (stats) *stats = st;
-    try {
+    return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         if (!ctx->lsl) ctx->lsl = new LslDev();
@@ -782,30 +727,15 @@ mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, co
         const mvs_patch_set& in = *patches;
         const uint32_t NP = in.n_patches, L = in.n_listed;
         const uint64_t NPIX = in.n_pixels;
-        if (NP && (!in.label || !in.box || !in.face_ptr || !in.pix_ptr)) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: null array in the patch set");
-        if (L && (!in.faces || !in.texcoords)) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: null array in the patch set");
-        if (NPIX && (!in.image || !in.validity || !in.blending)) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: null array in the patch set");
+        if (NPIX && !in.blending) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: null array in the patch set");
+        const PatchFrames h = read_patch_set(ctx, in, patches_on_device, true, "local_seam_leveling");   // the small per-patch arrays are read on the host as well
+        const unsigned long long* hp = h.pix_ptr;
         if (NPIX >= 0xFFFFFF00ull || (uint64_t)L * 3u >= 0xFFFFFF00ull) throw StatusError(MVS_ERR_UNSUPPORTED, "local_seam_leveling: too many pixels or list entries for one call");
-        // the small per-patch arrays are read on the host as well
-        std::vector<int4> hb; std::vector<unsigned long long> hp; std::vector<uint32_t> hf, hl;
-        to_host(hb, (const int4*)in.box, NP, patches_on_device, s); to_host(hp, (const unsigned long long*)in.pix_ptr, NP ? (size_t)NP + 1 : 0, patches_on_device, s);
-        to_host(hf, (const uint32_t*)in.face_ptr, NP ? (size_t)NP + 1 : 0, patches_on_device, s); to_host(hl, (const uint32_t*)in.label, NP, patches_on_device, s);
-        uint32_t E = 0;
-        if (F) {
-            if (adj_on_device) MVS_HIP(hipMemcpyAsync(&E, adj_ptr + F, sizeof(uint32_t), hipMemcpyDeviceToHost, s)); else E = adj_ptr[F];
-        }
-        MVS_HIP(hipStreamSynchronize(s));
-        if (!NP) { hp.assign(1, 0ull); hf.assign(1, 0u); }
-        if (hp[0] != 0 || hf[0] != 0 || hp[NP] != NPIX || hf[NP] != L) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: pix_ptr / face_ptr do not match the totals");
         for (uint32_t p = 0; p < NP; ++p) {
-            if (hb[p].z < 1 || hb[p].w < 1 || hp[p + 1] < hp[p] || hp[p + 1] - hp[p] != (unsigned long long)hb[p].z * (unsigned long long)hb[p].w || hf[p + 1] < hf[p])
-                throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: patch " + std::to_string(p) + ": frame, pix_ptr and face_ptr do not agree");
             if (hp[p + 1] - hp[p] >= 0x10000000ull) throw StatusError(MVS_ERR_UNSUPPORTED, "local_seam_leveling: a patch of 2^28 pixels or more");
-            if (hl[p] == 0) throw StatusError(MVS_ERR_UNSUPPORTED, "local_seam_leveling: a patch of label 0");
+            if (h.label[p] == 0) throw StatusError(MVS_ERR_UNSUPPORTED, "local_seam_leveling: a patch of label 0");
         }
-        const uint32_t* d_adj_ptr = F ? stage(D.adj_ptr, adj_ptr, (size_t)F + 1, adj_on_device, s) : nullptr;
-        const uint32_t* d_adj = F ? stage(D.adj, adj, E, adj_on_device, s) : nullptr;
-        const uint32_t* d_labels = F ? stage(D.labels, labels, F, labels_on_device, s) : nullptr;
+        const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device, true);   // E sizes the seam search
         Patches S{};
         S.P = NP; S.L = L;
         S.label = stage(D.in_label, (const uint32_t*)in.label, NP, patches_on_device, s);
@@ -818,24 +748,17 @@ mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, co
         S.validity = stage(D.in_validity, (const uint8_t*)in.validity, (size_t)NPIX, patches_on_device, s);
         S.blending = stage(D.in_blending, (const uint8_t*)in.blending, (size_t)NPIX, patches_on_device, s);
         MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
-        try {
-            run_lsl(ctx, D, d_adj_ptr, d_adj, E, d_labels, S, hp, P, st);
-        } catch (...) { (void)hipStreamSynchronize(s); if (stats) *stats = st; throw; }
-        if (stats) *stats = st;
+        run_with_stats(s, stats, st, [&] { run_lsl(ctx, D, g.adj_ptr, g.adj, g.E, g.labels, S, hp, P, st); });
         out->n_patches = NP; out->n_pixels = NPIX;
         if (out_on_device) {
             out->image = D.image.p; out->validity = D.validity.p; out->blending = D.mask.p;
         } else {
-            try {
+            download(s, out, mvs_lsl_result_free, [&] {
                 out->image = host_copy(D.image.p, 3 * (size_t)NPIX, s); out->validity = host_copy(D.validity.p, (size_t)NPIX, s);
                 out->blending = host_copy(D.mask.p, (size_t)NPIX, s);
-                MVS_HIP(hipStreamSynchronize(s));
-            } catch (...) { (void)hipStreamSynchronize(s); mvs_lsl_result_free(out); throw; }
+            });
         }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    });
 }
 
 void mvs_lsl_result_free(mvs_lsl_result* r) {

@@ -172,13 +172,6 @@ __global__ void compact_faces_kernel(const float* __restrict__ verts, const uint
     normals_out[3 * o] = n.x; normals_out[3 * o + 1] = n.y; normals_out[3 * o + 2] = n.z;
 }
 
-uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
-    uint32_t h = 0;
-    MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-    return h;
-}
-
 }  // namespace
 
 // adjacency of `d_faces` into ctx->g_adj_ptr / ctx->g_adj (device); returns the number of list entries

@@ -194,13 +194,6 @@ __global__ void rg_apply_kernel(const uint32_t* __restrict__ col_ptr, const uint
     if (i == R) atomicAdd(moved, 1u);
 }
 
-uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
-    uint32_t h = 0;
-    MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-    return h;
-}
-
 }  // namespace
 
 // One round of region moves on the best labeling (whole graph; exact unaries must be in place: mrf_exact_costs).

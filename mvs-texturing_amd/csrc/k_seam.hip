@@ -10,14 +10,11 @@
 //   iteration (the SpMV forms p = z + beta p on the fly for every column it reads; the update forms x, r and the next partials),
 //   replayed as a linear captured graph of GSL_GRAPH_ITERS iterations; a device word says when every channel has stopped.
 //   Reductions follow the fixed two-level tree of item 8 (grid from x_rows only), so the bits do not depend on the device.
-#include "ctx.h"
+#include "rows.h"
 #include <cfloat>
 #include <climits>
-#include <rocprim/rocprim.hpp>
 
 namespace mvs {
-
-mvs_status api_fail(mvs_status st, const std::string& msg);
 
 namespace {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
@@ -41,7 +38,7 @@ struct GslDev {
     DBuf<uint32_t> a_ptr, a_col, a_vert; DBuf<float> b;
     DBuf<uint32_t> lhs_ptr, lhs_col; DBuf<float> lhs_val, invdiag, rhs;
     DBuf<float> x, r, p, ap, xadj, corner, part;
-    DBuf<GslState> st; DBuf<unsigned long long> c64; DBuf<uint32_t> flags, labels, adj_ptr, adj;
+    DBuf<GslState> st; DBuf<unsigned long long> c64; DBuf<uint32_t> flags;
     hipStream_t cap = nullptr;
     uint32_t NV = 0, F = 0, XR = 0, AR = 0; uint64_t NNZ = 0; bool valid = false;   // shapes of the last successful call
     ~GslDev() { if (cap) (void)hipStreamDestroy(cap); }
@@ -49,14 +46,6 @@ struct GslDev {
 void gsl_release(mvs_ctx* ctx) { delete ctx->gsl; ctx->gsl = nullptr; }
 
 namespace {
-
-uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
-    uint32_t h = 0;
-    MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MVS_HIP(hipStreamSynchronize(ctx->stream));
-    return h;
-}
-inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }
 
 // the device arrays the per-row kernels read
 struct GslView {
@@ -519,10 +508,7 @@ uint32_t pairs_csr(mvs_ctx* ctx, GslDev& G, uint32_t n, uint32_t rows, DBuf<uint
     uint32_t total = 0;
     if (n) {
         G.keys2.ensure(n); G.flag.ensure(n); G.pos.ensure((size_t)n + 1);
-        size_t tmp = 0;
-        MVS_HIP(rocprim::radix_sort_keys(nullptr, tmp, G.keys.p, G.keys2.p, n, 0, 64, s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_keys(ctx->sort_tmp.p, tmp, G.keys.p, G.keys2.p, n, 0, 64, s));
+        dev_sort_keys(ctx, G.keys.p, G.keys2.p, n, 0, 64);
         hipLaunchKernelGGL(gsl_unique_flag_kernel, dim3(grid(n)), dim3(256), 0, s, G.keys2.p, n, G.flag.p); MVS_LAUNCH_CHECK();
         exclusive_scan_u32(ctx, G.flag.p, G.pos.p, n, G.pos.p + n);
         total = read_u32(ctx, G.pos.p + n);
@@ -545,10 +531,8 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces, NV = ctx->n_verts;
     G.valid = false;
-    hipEvent_t ev[6];
-    for (auto& e : ev) MVS_HIP(hipEventCreate(&e));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
-    MVS_HIP(hipEventRecord(ev[0], s));
+    StageTimer<6> tm(s);   // marks: begin, rows, patches, system, solve, output
+    tm.mark();
     G.flags.ensure(F_N); G.c64.ensure(C_N);
     MVS_HIP(hipMemsetAsync(G.flags.p, 0, F_N * sizeof(uint32_t), s));
     MVS_HIP(hipMemsetAsync(G.c64.p, 0, C_N * sizeof(unsigned long long), s));
@@ -562,12 +546,12 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     const uint32_t XR = pairs_csr(ctx, G, 3 * F, NV, G.x_ptr, G.x_label, &G.x_vert);
     hipLaunchKernelGGL(gsl_key_kernel, dim3(grid(F)), dim3(256), 0, s, ctx->d_faces, d_labels, F, 2, G.keys.p); MVS_LAUNCH_CHECK();
     pairs_csr(ctx, G, 6 * F, NV, G.ring_ptr, G.ring, nullptr);
-    MVS_HIP(hipEventRecord(ev[1], s));
+    tm.mark();
     // 3. candidates (components of every label), boxes, merges, patch ids
     PatchTables& T = G.pt;
     build_patch_tables(ctx, T, d_adj_ptr, d_adj, d_labels, "global_seam_leveling");
     const uint32_t n_patches = T.n_patches;
-    MVS_HIP(hipEventRecord(ev[2], s));
+    tm.mark();
     // 4.-7. A rows, b, Lhs, Rhs
     const GslView gv{ctx->d_verts, ctx->d_faces, d_labels, G.vf_ptr.p, G.vf.p, G.x_ptr.p, G.x_label.p, G.ring_ptr.p, G.ring.p,
                      T.box.p, T.pc.p, T.fcand.p, T.parent.p, T.fpid.p, T.fpos.p, T.views.p};
@@ -589,7 +573,7 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     hipLaunchKernelGGL(gsl_lhs_fill_kernel, dim3(grid(XR)), dim3(256), 0, s, gv, XR, G.x_vert.p, G.a_ptr.p, G.a_col.p, G.b.p, G.lhs_ptr.p, gam,
                        G.lhs_col.p, G.lhs_val.p, G.invdiag.p, G.rhs.p);
     MVS_LAUNCH_CHECK();
-    MVS_HIP(hipEventRecord(ev[3], s));
+    tm.mark();
     // 8. the solve
     G.x.ensure(3 * (size_t)XR + 3); G.r.ensure(3 * (size_t)XR + 3); G.p.ensure(6 * (size_t)XR + 6); G.ap.ensure(3 * (size_t)XR + 3);
     G.xadj.ensure(3 * (size_t)XR + 3); G.part.ensure((size_t)SLOTS * RED_BLOCKS); G.st.ensure(3);
@@ -624,16 +608,16 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
         }
         if (!done) throw HipError("global_seam_leveling: the CG loop did not stop");
         MVS_HIP(hipMemcpyAsync(&fin, G.st.p + 2, sizeof(GslState), hipMemcpyDeviceToHost, s));
-        MVS_HIP(hipEventRecord(ev[4], s));
+        tm.mark();
         hipLaunchKernelGGL(gsl_mean_part_kernel, dim3(NB), dim3(256), 0, s, XR, NB, G.x.p, G.part.p); MVS_LAUNCH_CHECK();
         hipLaunchKernelGGL(gsl_mean_apply_kernel, dim3(NB), dim3(256), 0, s, XR, NB, G.x.p, G.part.p, G.xadj.p); MVS_LAUNCH_CHECK();
     } else {
-        MVS_HIP(hipEventRecord(ev[4], s));
+        tm.mark();
     }
     // 9.
     G.corner.ensure(9 * (size_t)F + 9);
     hipLaunchKernelGGL(gsl_corner_kernel, dim3(grid(F)), dim3(256), 0, s, gv, F, G.xadj.p, G.corner.p); MVS_LAUNCH_CHECK();
-    MVS_HIP(hipEventRecord(ev[5], s));
+    tm.mark();
     unsigned long long c64[C_N];
     MVS_HIP(hipMemcpyAsync(c64, G.c64.p, sizeof(c64), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipStreamSynchronize(s));
@@ -641,19 +625,9 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     S.patches = n_patches; S.merged = T.n_merged; S.x_rows = XR; S.a_rows = AR; S.gamma_rows = c64[C_GAMMA2] / 2;
     S.lhs_nnz_lower = c64[C_LOWER]; S.seam_edges = c64[C_SEAM]; S.samples = c64[C_SAMPLES];
     for (int c = 0; c < 3; ++c) { S.iterations[c] = XR ? fin.ch[c].iters : 0u; S.error[c] = XR ? fin.ch[c].err : 0.0f; }
-    float ms[5];
-    for (int k = 0; k < 5; ++k) MVS_HIP(hipEventElapsedTime(ms + k, ev[k], ev[k + 1]));
-    S.ms_rows = ms[0]; S.ms_patches = ms[1]; S.ms_system = ms[2]; S.ms_solve = ms[3]; S.ms_output = ms[4];
-    MVS_HIP(hipEventElapsedTime(&S.ms_total, ev[0], ev[5]));
+    S.ms_rows = tm.ms(0, 1); S.ms_patches = tm.ms(1, 2); S.ms_system = tm.ms(2, 3); S.ms_solve = tm.ms(3, 4); S.ms_output = tm.ms(4, 5);
+    S.ms_total = tm.ms(0, 5);
     G.NV = NV; G.F = F; G.XR = XR; G.AR = AR; G.NNZ = NNZ; G.valid = true;
-}
-
-template <class T>
-T* host_copy(const T* d, size_t n, hipStream_t s) {
-    T* h = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!h) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-    if (n) MVS_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    return h;
 }
 
 }  // namespace
@@ -677,44 +651,28 @@ mvs_status mvs_ctx_global_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, c
     const uint32_t F = ctx->n_faces, NV = ctx->n_verts;
     if (F && (!adj_ptr || !adj || !labels)) return api_fail(MVS_ERR_INVALID, "null argument");
     *out = mvs_gsl_result{};
-    try {
+    return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         if (!ctx->gsl) ctx->gsl = new GslDev();
         GslDev& G = *ctx->gsl;
         mvs_gsl_params P;
         if (params) P = *params; else mvs_gsl_default_params(&P);
-        const uint32_t* d_adj_ptr = adj_ptr; const uint32_t* d_adj = adj; const uint32_t* d_labels = labels;
-        if (!adj_on_device && F) {
-            const size_t E = adj_ptr[F];
-            G.adj_ptr.ensure((size_t)F + 2); G.adj.ensure(E + 1);
-            MVS_HIP(hipMemcpyAsync(G.adj_ptr.p, adj_ptr, ((size_t)F + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            if (E) MVS_HIP(hipMemcpyAsync(G.adj.p, adj, E * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_adj_ptr = G.adj_ptr.p; d_adj = G.adj.p;
-        }
-        if (!labels_on_device && F) {
-            G.labels.ensure((size_t)F + 1);
-            MVS_HIP(hipMemcpyAsync(G.labels.p, labels, (size_t)F * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_labels = G.labels.p;
-        }
+        const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device);
         if (F && (!adj_on_device || !labels_on_device)) MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
         mvs_gsl_stats S{};
-        run_gsl(ctx, G, d_adj_ptr, d_adj, d_labels, P, S);
+        run_gsl(ctx, G, g.adj_ptr, g.adj, g.labels, P, S);
         if (stats) *stats = S;
         out->n_verts = NV; out->n_faces = F; out->x_rows = G.XR;
         if (out_on_device) {
             out->x_ptr = G.x_ptr.p; out->x_label = G.x_label.p; out->x_adjust = G.xadj.p; out->corner_adjust = G.corner.p;
         } else {
-            try {
+            download(s, out, mvs_gsl_result_free, [&] {
                 out->x_ptr = host_copy(G.x_ptr.p, (size_t)NV + 1, s); out->x_label = host_copy(G.x_label.p, G.XR, s);
                 out->x_adjust = host_copy(G.xadj.p, 3 * (size_t)G.XR, s); out->corner_adjust = host_copy(G.corner.p, 9 * (size_t)F, s);
-                MVS_HIP(hipStreamSynchronize(s));
-            } catch (...) { (void)hipStreamSynchronize(s); mvs_gsl_result_free(out); throw; }
+            });
         }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    });
 }
 
 void mvs_gsl_result_free(mvs_gsl_result* r) {
@@ -727,7 +685,7 @@ mvs_status mvs_ctx_gsl_system(mvs_ctx* ctx, mvs_gsl_system* out) {
     if (!ctx || !out) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->gsl || !ctx->gsl->valid) return api_fail(MVS_ERR_STATE, "no global seam leveling on this context");
     *out = mvs_gsl_system{};
-    try {
+    return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         GslDev& G = *ctx->gsl;
@@ -761,10 +719,7 @@ mvs_status mvs_ctx_gsl_system(mvs_ctx* ctx, mvs_gsl_system* out) {
             }
             for (uint32_t i = 0; i < XR; ++i) for (int c = 0; c < 3; ++c) { out->rhs[3 * (size_t)i + c] = rhs[(size_t)c * XR + i]; out->x_raw[3 * (size_t)i + c] = x[(size_t)c * XR + i]; }
         } catch (...) { (void)hipStreamSynchronize(s); mvs_gsl_system_free(out); throw; }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    });
 }
 
 void mvs_gsl_system_free(mvs_gsl_system* s) {

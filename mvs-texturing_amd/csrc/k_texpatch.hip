@@ -7,20 +7,17 @@
 //   ones: integer atomicMax / atomicMin of the list position into two winner words per pixel -- order-free, so every run gives the
 //   same bits) and resolve (one thread per pixel in chunks of one patch: the winner's barycentrics again with the identical
 //   expression, crop + adjustment, the two masks).  No float atomics anywhere.
-#include "ctx.h"
+#include "rows.h"
 #include <cfloat>
 #include <climits>
-#include <rocprim/rocprim.hpp>
 
 namespace mvs {
 
-mvs_status api_fail(mvs_status st, const std::string& msg);
 uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, uint32_t F, uint32_t n_labels);
 
 namespace {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 enum { F_LABEL = 0, F_VERTEX, F_BOX, F_N };   // flag words of PatchTables
-inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }
 
 // ---- the shared tables (items 3-4 of "Global seam leveling") ----
 __global__ void pt_check_kernel(const uint32_t* __restrict__ faces, const uint32_t* __restrict__ labels, uint32_t F, uint32_t NV, uint32_t n_views,
@@ -122,12 +119,6 @@ void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, 
 void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const char* who) {
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces, V = ctx->n_views;
-    auto read_u32 = [&](const uint32_t* d) {
-        uint32_t h = 0;
-        MVS_HIP(hipMemcpyAsync(&h, d, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        MVS_HIP(hipStreamSynchronize(s));
-        return h;
-    };
     const uint32_t C = get_subgraphs(ctx, d_adj_ptr, d_adj, d_labels, F, V + 1);
     const uint32_t* comp_ptr = ctx->p_comp_ptr.p; const uint32_t* comp_faces = ctx->p_comp_faces.p; const uint32_t* label_ptr = ctx->p_label_ptr.p;
     T.box.ensure((size_t)C + 1); T.pc.ensure(3 * (size_t)F + 1); T.fcand.ensure((size_t)F + 1); T.fidx.ensure((size_t)F + 1);
@@ -137,14 +128,14 @@ void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr,
     hipLaunchKernelGGL(pt_face_box_kernel, dim3(grid(F)), dim3(256), 0, s, comp_ptr, comp_faces, C, F, d_labels, ctx->d_faces, ctx->d_verts,
                        (const ViewParams*)T.views.p, T.box.p, T.pc.p, T.fcand.p, T.fidx.p, T.flags.p);
     MVS_LAUNCH_CHECK();
-    if (read_u32(T.flags.p + F_BOX)) throw StatusError(MVS_ERR_LABELING, std::string(who) + ": a labelled face leaves its view's image");
+    if (read_u32(ctx, T.flags.p + F_BOX)) throw StatusError(MVS_ERR_LABELING, std::string(who) + ": a labelled face leaves its view's image");
     hipLaunchKernelGGL(pt_merge_kernel, dim3(grid(V + 1)), dim3(256), 0, s, label_ptr, V + 1, comp_ptr, T.box.p, T.parent.p, T.off.p, T.len.p,
                        T.alive.p, T.merged.p);
     MVS_LAUNCH_CHECK();
     exclusive_scan_u32(ctx, T.alive.p, T.pscan.p, C, T.pscan.p + C);
     unsigned long long merged = 0;
     MVS_HIP(hipMemcpyAsync(&merged, T.merged.p, sizeof(merged), hipMemcpyDeviceToHost, s));
-    T.n_patches = read_u32(T.pscan.p + C);
+    T.n_patches = read_u32(ctx, T.pscan.p + C);
     T.C = C; T.n_merged = merged;
     hipLaunchKernelGGL(pt_cand_final_kernel, dim3(grid(C)), dim3(256), 0, s, T.parent.p, T.off.p, T.pscan.p, C, T.cand_pid.p, T.cand_pos.p); MVS_LAUNCH_CHECK();
     hipLaunchKernelGGL(pt_face_patch_kernel, dim3(grid(F)), dim3(256), 0, s, d_labels, T.fcand.p, T.fidx.p, T.cand_pid.p, T.cand_pos.p, F, T.fpid.p, T.fpos.p);
@@ -155,7 +146,7 @@ void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr,
 // per-context buffers of row f6, allocated on first use, freed with the context (texpatch_release)
 struct TexPatchDev {
     PatchTables pt;
-    DBuf<uint32_t> label, cnt, face_ptr, faces, epid, nchunk, chunk_ptr, win_in, win_near, big, labels, adj_ptr, adj;
+    DBuf<uint32_t> label, cnt, face_ptr, faces, epid, nchunk, chunk_ptr, win_in, win_near, big;
     DBuf<int4> box; DBuf<float> texcoords, image, adjust; DBuf<unsigned long long> npix, pix_ptr, c64; DBuf<uint8_t> validity, blending;
 };
 void texpatch_release(mvs_ctx* ctx) { delete ctx->texpatch; ctx->texpatch = nullptr; }
@@ -337,27 +328,17 @@ __global__ void __launch_bounds__(256) tp_resolve_kernel(uint32_t P, const uint3
     }
 }
 
-template <class T>
-T* host_copy(const T* d, size_t n, hipStream_t s) {
-    T* h = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!h) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-    if (n) MVS_HIP(hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    return h;
-}
-
 // the whole row on the context's stream; the pixel arrays are left in D
 void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const float* d_adjust,
                   const mvs_patch_params& P, mvs_patch_stats& S, uint32_t& n_listed, uint64_t& n_pixels) {
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces;
     PatchTables& T = D.pt;
-    hipEvent_t ev[5];
-    for (auto& e : ev) MVS_HIP(hipEventCreate(&e));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 5; ++k) (void)hipEventDestroy(e[k]); } } evg{ev};
-    MVS_HIP(hipEventRecord(ev[0], s));
+    StageTimer<5> tm(s);   // marks: begin, tables, lists, mark, resolve
+    tm.mark();
     patch_check_inputs(ctx, T, d_labels, "texture_patches");
     build_patch_tables(ctx, T, d_adj_ptr, d_adj, d_labels, "texture_patches");
-    MVS_HIP(hipEventRecord(ev[1], s));
+    tm.mark();
     // geometry, sizes, the three scans, the lists
     const uint32_t NP = T.n_patches, C = T.C;
     D.label.ensure((size_t)NP + 1); D.box.ensure((size_t)NP + 1); D.cnt.ensure((size_t)NP + 2); D.face_ptr.ensure((size_t)NP + 2);
@@ -370,12 +351,7 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
                        D.cnt.p, D.npix.p, D.nchunk.p);
     MVS_LAUNCH_CHECK();
     exclusive_scan_u32(ctx, D.cnt.p, D.face_ptr.p, NP, D.face_ptr.p + NP);
-    {
-        size_t tmp = 0;
-        MVS_HIP(rocprim::exclusive_scan(nullptr, tmp, D.npix.p, D.pix_ptr.p, 0ull, (size_t)NP + 1, rocprim::plus<unsigned long long>(), s));
-        ctx->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, D.npix.p, D.pix_ptr.p, 0ull, (size_t)NP + 1, rocprim::plus<unsigned long long>(), s));
-    }
+    dev_exclusive_scan(ctx, D.npix.p, D.pix_ptr.p, (size_t)NP + 1);
     unsigned long long total = 0; uint32_t listed = 0;
     MVS_HIP(hipMemcpyAsync(&total, D.pix_ptr.p + NP, sizeof(total), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipMemcpyAsync(&listed, D.face_ptr.p + NP, sizeof(listed), hipMemcpyDeviceToHost, s));
@@ -393,7 +369,7 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
     MVS_LAUNCH_CHECK();
     uint32_t n_chunks = 0;
     MVS_HIP(hipMemcpyAsync(&n_chunks, D.chunk_ptr.p + NP, sizeof(n_chunks), hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipEventRecord(ev[2], s));
+    tm.mark();
     // mark
     D.win_in.ensure((size_t)total + 1); D.win_near.ensure((size_t)total + 1);
     D.image.ensure(3 * (size_t)total + 3); D.validity.ensure((size_t)total + 1); D.blending.ensure((size_t)total + 1);
@@ -408,7 +384,7 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
                            (const unsigned long long*)D.pix_ptr.p, D.win_in.p, D.win_near.p);
         MVS_LAUNCH_CHECK();
     }
-    MVS_HIP(hipEventRecord(ev[3], s));
+    tm.mark();
     // resolve
     MVS_HIP(hipStreamSynchronize(s));   // n_chunks
     if (n_chunks) {
@@ -418,15 +394,13 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
                            (const uint32_t*)D.win_near.p, D.image.p, D.validity.p, D.blending.p, D.c64.p);
         MVS_LAUNCH_CHECK();
     }
-    MVS_HIP(hipEventRecord(ev[4], s));
+    tm.mark();
     unsigned long long c64[K_N];
     MVS_HIP(hipMemcpyAsync(c64, D.c64.p, sizeof(c64), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipStreamSynchronize(s));
     S.degenerate_faces = c64[K_DEGENERATE]; S.valid_pixels = c64[K_VALID]; S.near_pixels = c64[K_NEAR];
-    float ms[4];
-    for (int k = 0; k < 4; ++k) MVS_HIP(hipEventElapsedTime(ms + k, ev[k], ev[k + 1]));
-    S.ms_tables = ms[0]; S.ms_lists = ms[1]; S.ms_mark = ms[2]; S.ms_resolve = ms[3];
-    MVS_HIP(hipEventElapsedTime(&S.ms_total, ev[0], ev[4]));
+    S.ms_tables = tm.ms(0, 1); S.ms_lists = tm.ms(1, 2); S.ms_mark = tm.ms(2, 3); S.ms_resolve = tm.ms(3, 4);
+    S.ms_total = tm.ms(0, 4);
 }
 
 }  // namespace
@@ -451,57 +425,34 @@ mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const 
     if (F && (!adj_ptr || !adj || !labels)) return api_fail(MVS_ERR_INVALID, "null argument");
     *out = mvs_patch_set{};
     mvs_patch_stats S{};
-    try {
+    return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         if (!ctx->texpatch) ctx->texpatch = new TexPatchDev();
         TexPatchDev& D = *ctx->texpatch;
         mvs_patch_params P;
         if (params) P = *params; else mvs_patch_default_params(&P);
-        const uint32_t* d_adj_ptr = adj_ptr; const uint32_t* d_adj = adj; const uint32_t* d_labels = labels; const float* d_adjust = corner_adjust;
-        if (!adj_on_device && F) {
-            const size_t E = adj_ptr[F];
-            D.adj_ptr.ensure((size_t)F + 2); D.adj.ensure(E + 1);
-            MVS_HIP(hipMemcpyAsync(D.adj_ptr.p, adj_ptr, ((size_t)F + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            if (E) MVS_HIP(hipMemcpyAsync(D.adj.p, adj, E * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_adj_ptr = D.adj_ptr.p; d_adj = D.adj.p;
-        }
-        if (!labels_on_device && F) {
-            D.labels.ensure((size_t)F + 1);
-            MVS_HIP(hipMemcpyAsync(D.labels.p, labels, (size_t)F * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            d_labels = D.labels.p;
-        }
-        if (corner_adjust && !adjust_on_device && F) {
-            D.adjust.ensure(9 * (size_t)F + 9);
-            MVS_HIP(hipMemcpyAsync(D.adjust.p, corner_adjust, 9 * (size_t)F * sizeof(float), hipMemcpyHostToDevice, s));
-            d_adjust = D.adjust.p;
-        }
+        const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device);
+        const float* d_adjust = corner_adjust && F ? stage(D.adjust, corner_adjust, 9 * (size_t)F, adjust_on_device, s) : corner_adjust;
         if (F) MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
         uint32_t n_listed = 0; uint64_t n_pixels = 0;
-        try {
-            run_texpatch(ctx, D, d_adj_ptr, d_adj, d_labels, d_adjust, P, S, n_listed, n_pixels);
-        } catch (...) { (void)hipStreamSynchronize(s); if (stats) *stats = S; throw; }
-        if (stats) *stats = S;
+        run_with_stats(s, stats, S, [&] { run_texpatch(ctx, D, g.adj_ptr, g.adj, g.labels, d_adjust, P, S, n_listed, n_pixels); });
         const uint32_t NP = D.pt.n_patches;
         out->n_patches = NP; out->n_listed = n_listed; out->n_pixels = n_pixels;
         if (out_on_device) {
             out->label = D.label.p; out->box = (int32_t*)D.box.p; out->face_ptr = D.face_ptr.p; out->faces = D.faces.p; out->texcoords = D.texcoords.p;
             out->pix_ptr = (uint64_t*)D.pix_ptr.p; out->image = D.image.p; out->validity = D.validity.p; out->blending = D.blending.p;
         } else {
-            try {
+            download(s, out, mvs_patch_set_free, [&] {
                 out->label = host_copy(D.label.p, NP, s); out->box = host_copy((const int32_t*)D.box.p, 4 * (size_t)NP, s);
                 out->face_ptr = host_copy(D.face_ptr.p, (size_t)NP + 1, s); out->faces = host_copy(D.faces.p, n_listed, s);
                 out->texcoords = host_copy(D.texcoords.p, 6 * (size_t)n_listed, s);
                 out->pix_ptr = host_copy((const uint64_t*)D.pix_ptr.p, (size_t)NP + 1, s);
                 out->image = host_copy(D.image.p, 3 * (size_t)n_pixels, s); out->validity = host_copy(D.validity.p, (size_t)n_pixels, s);
                 out->blending = host_copy(D.blending.p, (size_t)n_pixels, s);
-                MVS_HIP(hipStreamSynchronize(s));
-            } catch (...) { (void)hipStreamSynchronize(s); mvs_patch_set_free(out); throw; }
+            });
         }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    });
 }
 
 void mvs_patch_set_free(mvs_patch_set* r) {

@@ -6,6 +6,7 @@ Mirrors the reference interface for the path:
 Arrays may be numpy arrays (host) or torch CUDA tensors (device-resident; torch
 is only used for the device memory and the stream).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -320,12 +321,53 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p), 0
 
 
-def default_mrf_params(**kw):
-    p = MrfParams()
-    load_library().mvs_mrf_default_params(C.byref(p))
+def _default_params(cls, fn_name, kw):
+    """the library's defaults of a parameter struct with overrides"""
+    p = cls()
+    getattr(load_library(), fn_name)(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_mrf_params(**kw):
+    return _default_params(MrfParams, "mvs_mrf_default_params", kw)
+
+
+def _check_with_stats(L, rc, stats):
+    """_check for the calls that fill their stats before they refuse: the MvsError carries them as `.stats`"""
+    try:
+        _check(L, rc)
+    except MvsError as e:
+        e.stats = stats
+        raise
+
+
+def _download(res, shapes, free_fn):
+    """the arrays {name: (count, dtype)} of a result struct: DevArrays owned by the context (free_fn None: the call left them on the
+    device), else flat host copies, after which free_fn releases the library's own"""
+    if free_fn is None:
+        return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}
+    out = {}
+    for k, (n, dt) in shapes.items():
+        out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
+    free_fn(C.byref(res))
+    return out
+
+
+def _patch_set_struct(patches, dts):
+    """the arrays `dts` ({name: dtype}) of a patch-set dict as a PatchSet: (ps, held, on_device) -- all host arrays (made contiguous and
+    flat; `held` keeps them alive) or all DevArrays / CUDA tensors; n_patches is counted on box, which every row reads"""
+    dev = [_is_torch(patches[k]) or isinstance(patches[k], DevArray) for k in dts]
+    assert all(dev) or not any(dev), "the patch set must be all host or all device arrays"
+    on_device = dev[0]
+    held = {k: patches[k] if on_device else np.ascontiguousarray(patches[k], dts[k]).reshape(-1) for k in dts}
+    count = lambda x: int(x.numel()) if _is_torch(x) else int(x.shape[0])   # tensors of any shape, DevArrays and flat numpy arrays alike
+    ps = PatchSet()
+    ps.n_patches = count(held["box"]) // 4; ps.n_listed = count(held["faces"]); ps.n_pixels = count(held["validity"])
+    for k in dts:
+        setattr(ps, k, _ptr(held[k])[0] if (on_device or held[k].size) else None)
+    return ps, held, 1 if on_device else 0
 
 
 class DataCosts:
@@ -573,21 +615,13 @@ class Context:
         rc = self.L.mvs_ctx_texture_patches(self.h, pa, pb, d0, pl, dl, pc, dc, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
         stats = {k: int(getattr(st, k)) for k in PATCH_COUNTS}
         stats.update({k: float(getattr(st, k)) for k in PATCH_MS})
-        if rc != 0:
-            try:
-                _check(self.L, rc)
-            except MvsError as e:
-                e.stats = stats
-                raise
+        _check_with_stats(self.L, rc, stats)
         P, NL, NP = int(res.n_patches), int(res.n_listed), int(res.n_pixels)
         shapes = dict(label=(P, np.uint32), box=(4 * P, np.int32), face_ptr=(P + 1, np.uint32), faces=(NL, np.uint32), texcoords=(6 * NL, np.float32),
                       pix_ptr=(P + 1, np.uint64), image=(3 * NP, np.float32), validity=(NP, np.uint8), blending=(NP, np.uint8))
+        out = _download(res, shapes, None if on_device else self.L.mvs_patch_set_free)
         if on_device:
-            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
-        out = {}
-        for k, (n, dt) in shapes.items():
-            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
-        self.L.mvs_patch_set_free(C.byref(res))
+            return out, stats
         out["box"] = out["box"].reshape(P, 4); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2); out["image"] = out["image"].reshape(NP, 3)
         return out, stats
 
@@ -602,39 +636,21 @@ class Context:
         assert d0 == d1
         dts = dict(label=np.uint32, box=np.int32, face_ptr=np.uint32, faces=np.uint32, texcoords=np.float32, pix_ptr=np.uint64, image=np.float32,
                    validity=np.uint8, blending=np.uint8)
-        dev = [_is_torch(patches[k]) or isinstance(patches[k], DevArray) for k in dts]
-        assert all(dev) or not any(dev), "the patch set must be all host or all device arrays"
-        held = {k: patches[k] if dev[0] else np.ascontiguousarray(patches[k], dts[k]).reshape(-1) for k in dts}
-        ps = PatchSet()
-        if dev[0]:
-            P = int(held["label"].shape[0]); ps.n_listed = int(held["faces"].shape[0]); ps.n_pixels = int(held["validity"].shape[0])
-        else:
-            P = held["label"].size; ps.n_listed = held["faces"].size; ps.n_pixels = held["validity"].size
-        ps.n_patches = P
-        for k in dts:
-            setattr(ps, k, _ptr(held[k])[0] if (dev[0] or held[k].size) else None)
+        ps, held, dev = _patch_set_struct(patches, dts)
         p = params or default_lsl_params()
         res, st = LslResult(), LslStats()
         self._keep["lsl"] = (adj_ptr, adj, labels, held)
-        rc = self.L.mvs_ctx_local_seam_leveling(self.h, pa, pb, d0, pl, dl, C.byref(ps), 1 if dev[0] else 0, C.byref(p), C.byref(res),
+        rc = self.L.mvs_ctx_local_seam_leveling(self.h, pa, pb, d0, pl, dl, C.byref(ps), dev, C.byref(p), C.byref(res),
                                                 1 if on_device else 0, C.byref(st))
         stats = {k: int(getattr(st, k)) for k in LSL_COUNTS + ("iterations_max",)}
         stats["error_max"] = float(st.error_max)
         stats.update({k: float(getattr(st, k)) for k in LSL_MS})
-        if rc != 0:
-            try:
-                _check(self.L, rc)
-            except MvsError as e:
-                e.stats = stats
-                raise
+        _check_with_stats(self.L, rc, stats)
         NP = int(res.n_pixels)
         shapes = dict(image=(3 * NP, np.float32), validity=(NP, np.uint8), blending=(NP, np.uint8))
+        out = _download(res, shapes, None if on_device else self.L.mvs_lsl_result_free)
         if on_device:
-            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
-        out = {}
-        for k, (n, dt) in shapes.items():
-            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
-        self.L.mvs_lsl_result_free(C.byref(res))
+            return out, stats
         out["image"] = out["image"].reshape(NP, 3)
         return out, stats
 
@@ -647,40 +663,22 @@ class Context:
         texcoord_ids (n_listed, 3); with on_device=True DevArrays owned by the context (valid until the next texture_atlases call).
         An atlas pixel total above params.max_pixels raises MvsError (status 7) with `.stats` holding the counts."""
         dts = dict(box=np.int32, face_ptr=np.uint32, faces=np.uint32, texcoords=np.float32, pix_ptr=np.uint64, image=np.float32, validity=np.uint8)
-        dev = [_is_torch(patches[k]) or isinstance(patches[k], DevArray) for k in dts]
-        assert all(dev) or not any(dev), "the patch set must be all host or all device arrays"
-        held = {k: patches[k] if dev[0] else np.ascontiguousarray(patches[k], dts[k]).reshape(-1) for k in dts}
-        ps = PatchSet()
-        if dev[0]:
-            count = lambda x: int(x.numel()) if _is_torch(x) else int(x.shape[0])
-            P = count(held["box"]) // 4; ps.n_listed = count(held["faces"]); ps.n_pixels = count(held["validity"])
-        else:
-            P = held["box"].size // 4; ps.n_listed = held["faces"].size; ps.n_pixels = held["validity"].size
-        ps.n_patches = P
-        for k in dts:
-            setattr(ps, k, _ptr(held[k])[0] if (dev[0] or held[k].size) else None)
+        ps, held, dev = _patch_set_struct(patches, dts)
+        P = int(ps.n_patches)
         p = params or default_atlas_params()
         res, st = AtlasSet(), AtlasStats()
         self._keep["atlas"] = held
-        rc = self.L.mvs_ctx_texture_atlases(self.h, C.byref(ps), 1 if dev[0] else 0, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        rc = self.L.mvs_ctx_texture_atlases(self.h, C.byref(ps), dev, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
         stats = {k: int(getattr(st, k)) for k in ATLAS_COUNTS}
         stats.update({k: float(getattr(st, k)) for k in ATLAS_MS})
-        if rc != 0:
-            try:
-                _check(self.L, rc)
-            except MvsError as e:
-                e.stats = stats
-                raise
+        _check_with_stats(self.L, rc, stats)
         A, NL, NM, NP = int(res.n_atlases), int(res.n_listed), int(res.n_merged), int(res.n_pixels)
         shapes = dict(atlas_size=(A, np.uint32), atlas_pix_ptr=(A + 1, np.uint64), image=(3 * NP, np.uint8), patch_atlas=(P, np.uint32), patch_pos=(2 * P, np.int32),
                       patch_order=(P, np.uint32), face_ptr=(A + 1, np.uint32), faces=(NL, np.uint32), texcoords=(6 * NL, np.float32), tc_ptr=(A + 1, np.uint32),
                       texcoords_merged=(2 * NM, np.float32), texcoord_ids=(3 * NL, np.uint32))
+        out = _download(res, shapes, None if on_device else self.L.mvs_atlas_set_free)
         if on_device:
-            return {k: DevArray(getattr(res, k), n) for k, (n, _) in shapes.items()}, stats
-        out = {}
-        for k, (n, dt) in shapes.items():
-            out[k] = np.frombuffer(C.string_at(getattr(res, k), n * np.dtype(dt).itemsize), dt).copy() if n else np.zeros(0, dt)
-        self.L.mvs_atlas_set_free(C.byref(res))
+            return out, stats
         out["image"] = out["image"].reshape(NP, 3); out["patch_pos"] = out["patch_pos"].reshape(P, 2); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2)
         out["texcoords_merged"] = out["texcoords_merged"].reshape(NM, 2); out["texcoord_ids"] = out["texcoord_ids"].reshape(NL, 3)
         return out, stats
@@ -706,38 +704,22 @@ def _grab(ptr, n, ctype):
 
 def default_gsl_params(**kw):
     """mvs_gsl_default_params (tolerance 1e-4, max_iterations 1000, lam 0.1) with overrides"""
-    p = GslParams()
-    load_library().mvs_gsl_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _default_params(GslParams, "mvs_gsl_default_params", kw)
 
 
 def default_patch_params(**kw):
     """mvs_patch_default_params (max_pixels 0 = no cap) with overrides"""
-    p = PatchParams()
-    load_library().mvs_patch_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _default_params(PatchParams, "mvs_patch_default_params", kw)
 
 
 def default_lsl_params(**kw):
     """mvs_lsl_default_params (tolerance 1e-6, max_iterations 700, strip_width 20, lds_bytes 147456) with overrides"""
-    p = LslParams()
-    load_library().mvs_lsl_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _default_params(LslParams, "mvs_lsl_default_params", kw)
 
 
 def default_atlas_params(**kw):
     """mvs_atlas_default_params (max_pixels 0 = no cap) with overrides"""
-    p = AtlasParams()
-    load_library().mvs_atlas_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _default_params(AtlasParams, "mvs_atlas_default_params", kw)
 
 
 def atlas_view(arrays, a):
@@ -753,77 +735,63 @@ def patch_view(arrays, i):
     return arrays["image"][a:b].reshape(h, w, 3), arrays["validity"][a:b].reshape(h, w), arrays["blending"][a:b].reshape(h, w)
 
 
-def texture_patches(scene, labels, corner_adjust=None, ctx=None):
-    """the texture patches (generate_texture_patches for the labelled faces + adjust_colors, texrecon.cpp:160-184) of a synth.Scene-like
-    object and its labels: returns (arrays, stats) of Context.texture_patches."""
+@contextlib.contextmanager
+def _scene_context(scene, ctx):
+    """the caller's context, or one of its own that is closed on the way out, with the scene's mesh and views set"""
     own = ctx is None
     ctx = ctx or Context()
     try:
         ctx.set_mesh(scene.verts, scene.faces, scene.normals)
         ctx.set_views(scene.cams, scene.images)
-        return ctx.texture_patches(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
-                                   np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust)
+        yield ctx
     finally:
         if own:
             ctx.close()
+
+
+def texture_patches(scene, labels, corner_adjust=None, ctx=None):
+    """the texture patches (generate_texture_patches for the labelled faces + adjust_colors, texrecon.cpp:160-184) of a synth.Scene-like
+    object and its labels: returns (arrays, stats) of Context.texture_patches."""
+    with _scene_context(scene, ctx) as c:
+        return c.texture_patches(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
+                                 np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust)
 
 
 def local_seam_leveling(scene, labels, params=None, ctx=None):
     """texrecon.cpp:169-189 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with
     its adjustments (row f6) and local seam leveling (row f7), the patches staying on the device in between.  Returns (arrays, stats):
     the patch set of Context.texture_patches with image, validity and blending replaced by row f7's, and row f7's stats."""
-    own = ctx is None
-    ctx = ctx or Context()
-    try:
-        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images)
+    with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
-        gsl, _ = ctx.global_seam_leveling(a, b, lab, on_device=True)
-        dev, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
-        out, stats = ctx.local_seam_leveling(a, b, lab, dev, params)
-        host, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"])
+        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
+        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        out, stats = c.local_seam_leveling(a, b, lab, dev, params)
+        host, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"])
         host.update(out)
         return host, stats
-    finally:
-        if own:
-            ctx.close()
 
 
 def texture_atlases(scene, labels, params=None, ctx=None):
     """texrecon.cpp:169-195 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with its
     adjustments (row f6), local seam leveling (row f7) and the texture atlases (row f8), the patches staying on the device in
     between.  Returns (arrays, stats) of Context.texture_atlases."""
-    own = ctx is None
-    ctx = ctx or Context()
-    try:
-        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images)
+    with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
-        gsl, _ = ctx.global_seam_leveling(a, b, lab, on_device=True)
-        dev, _ = ctx.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
-        lsl, _ = ctx.local_seam_leveling(a, b, lab, dev, on_device=True)
+        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
+        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
         dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
-        return ctx.texture_atlases(dev, params)
-    finally:
-        if own:
-            ctx.close()
+        return c.texture_atlases(dev, params)
 
 
 def global_seam_leveling(scene, labels, params=None, ctx=None):
     """tex::global_seam_leveling for a synth.Scene-like object (verts, faces, normals, cams, images, adj_ptr, adj) and its labels
     (texrecon.cpp:169-172): returns (arrays, stats) of Context.global_seam_leveling."""
-    own = ctx is None
-    ctx = ctx or Context()
-    try:
-        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images)
-        return ctx.global_seam_leveling(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
-                                        np.ascontiguousarray(labels, dtype=np.uint32), params)
-    finally:
-        if own:
-            ctx.close()
+    with _scene_context(scene, ctx) as c:
+        return c.global_seam_leveling(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
+                                      np.ascontiguousarray(labels, dtype=np.uint32), params)
 
 
 def _subgraphs_to_numpy(L, sg):
@@ -849,16 +817,9 @@ def get_subgraphs(adj_ptr, adj, labels, n_labels):
 def calculate_data_costs(scene, settings=None, ctx=None):
     """tex::calculate_data_costs(mesh, &texture_views, settings, &data_costs) on a synth.Scene-like
     object (verts, faces, normals, cams, images).  Returns (DataCosts on the host, stats)."""
-    own = ctx is None
-    ctx = ctx or Context()
-    try:
-        ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images)
-        stats = ctx.data_costs(settings)
-        return ctx.costs_download(), stats
-    finally:
-        if own:
-            ctx.close()
+    with _scene_context(scene, ctx) as c:
+        stats = c.data_costs(settings)
+        return c.costs_download(), stats
 
 
 def view_selection(data_costs, adj_ptr, adj, params=None, ctx=None):

@@ -2,7 +2,8 @@
 DESIGN.md section 4 "Texture atlases") bit for bit on every output array and every counter -- the suite's scenes (labels from the
 library's own view selection, patches from its rows f5 - f7), shuffled meshes, the crafted sets of tests/test_atlas_model.py (atlases of
 2048 to 8192 padded 17 to 65 levels deep, two sizes in one call), the nested set of tests/test_patch_model.py, config 2,
-and the cases of tests/golden/texture_atlas_pins.npz against what upstream's compiled generate_texture_atlases left for them."""
+the cases of tests/golden/texture_atlas_pins.npz against what upstream's compiled generate_texture_atlases left for them, and the
+refusal of inconsistent patch sets by the checker this row shares with row f7."""
 import numpy as np
 import pytest
 
@@ -235,3 +236,59 @@ def test_config2_equals_the_model():
     pa = _pipeline_patches(s, labels)
     got, gst, _ = _compare(pa, what="config 2")
     assert gst["atlases"] >= 1 and gst["padded_pixels"] > 0
+
+
+def test_inconsistent_patch_sets_are_refused_by_rows_f7_and_f8():
+    """the one reader and checker of a patch set both rows call: a pix_ptr that ends past the pixel total, a frame one pixel wider than its
+    pix_ptr range and a face_ptr with two neighbouring entries swapped are refused with MVS_ERR_INVALID by local_seam_leveling and by
+    texture_atlases, from host arrays and from CUDA tensors -- on the host, before any kernel of the row -- and the context then runs the
+    unbroken set as the models do.  `grid` has two patches, so its swapped face_ptr also misses the total; the three patches of
+    `three_labels_and_unseen` leave first and last entry alone: the descending pair is all that is wrong there."""
+    import torch
+    import blend_model as BM
+    import patch_model as PM
+    import seam_model as SM
+    from test_local_seam_model import crafted_sets as lsl_crafted_sets
+    SM.build(); PM.build(); BM.build()
+    sets = lsl_crafted_sets()
+    flat = lambda pa: {k: np.ascontiguousarray(pa[k], dt).reshape(-1) for k, dt in BM.PATCH_ARRAYS.items()}
+    signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
+    cuda = lambda x: torch.from_numpy(x.view(signed.get(x.dtype, x.dtype))).cuda()
+
+    def edited(good, key, edit):
+        b = dict(good); b[key] = good[key].copy(); edit(b[key])
+        return b
+
+    def swap12(fp):
+        fp[[1, 2]] = fp[[2, 1]]
+
+    def refused(c, g, labels, b, what):
+        for where, s in (("host", b), ("device", {k: cuda(v) for k, v in b.items()})):
+            with pytest.raises(M.MvsError) as e:
+                c.local_seam_leveling(g.adj_ptr, g.adj, labels, s)
+            assert e.value.status == 1, (what, where, "local_seam_leveling", str(e.value))
+            with pytest.raises(M.MvsError) as e:
+                c.texture_atlases(s)
+            assert e.value.status == 1, (what, where, "texture_atlases", str(e.value))
+
+    g, labels, pa = sets["grid"]
+    labels = np.ascontiguousarray(labels, np.uint32)
+    good = flat(pa)
+    assert good["face_ptr"][1] < good["face_ptr"][2]
+    c = _ctx(g)
+    refused(c, g, labels, edited(good, "pix_ptr", lambda a: a.__setitem__(-1, a[-1] + 1)), "pix_ptr past the total")
+    refused(c, g, labels, edited(good, "box", lambda a: a.__setitem__(2, a[2] + 1)), "a frame one pixel wider")
+    refused(c, g, labels, edited(good, "face_ptr", swap12), "face_ptr swapped")
+    st, want, _, _ = BM.run_scene(g, labels, pa)
+    assert st == 0
+    got, _ = c.local_seam_leveling(g.adj_ptr, g.adj, labels, good)
+    for k in ("image", "validity", "blending"):
+        assert got[k].size == want[k].size and np.array_equal(_raw(got[k]), _raw(want[k])), k
+    _compare(good, ctx=c, what="after the refusals")
+    c.close()
+    g, labels, pa = sets["three_labels_and_unseen"]
+    good = flat(pa)
+    assert good["label"].size == 3 and good["face_ptr"][1] < good["face_ptr"][2] < good["face_ptr"][3]
+    c = _ctx(g)
+    refused(c, g, np.ascontiguousarray(labels, np.uint32), edited(good, "face_ptr", swap12), "face_ptr descends")
+    c.close()
