@@ -223,11 +223,15 @@ mvs_status mvs_write_labeling_vec(const uint32_t* labels, uint32_t n_faces, cons
  * SURVEY.md 8(f) row f1 -- the two stages immediately BEFORE the path (apps/texrecon/texrecon.cpp:78-92)
  * ------------------------------------------------------------------------ */
 /* replaces tex::prepare_mesh (libs/tex/texturing.h:45-46, prepare_mesh.cpp:57-70): removes redundant faces
- * (prepare_mesh.cpp:14-55) and computes face normals; faces_out / normals_out hold 3 * n_faces entries */
+ * (prepare_mesh.cpp:14-55) and computes face normals; faces_out / normals_out hold 3 * n_faces entries.  MVS_ERR_INVALID ("vertex id out of
+ * range") when an index in faces is >= n_verts. */
 mvs_status mvs_prepare_mesh(uint32_t n_verts, const float* verts, uint32_t n_faces, const uint32_t* faces,
                             uint32_t* faces_out, float* normals_out, uint32_t* n_kept);
 /* replaces tex::build_adjacency_graph (texturing.h:58-60, build_adjacency_graph.cpp:16-53): UniGraph adjacency lists
- * flattened in list order; adj_ptr_out[n_faces + 1] caller allocated, *adj_out malloc'ed by the library (free()) */
+ * flattened in list order; adj_ptr_out[n_faces + 1] caller allocated, *adj_out malloc'ed by the library (free()).  MVS_ERR_INVALID ("vertex id
+ * out of range") when an index in faces is >= n_verts.  MVS_ERR_UNSUPPORTED for a face with more than 48 neighbours of smaller id or
+ * more than 48 of larger id; in a mesh that has a face with a repeated vertex, for a face with more than 48 neighbours in all or with
+ * more than 128 other faces at its vertices. */
 mvs_status mvs_build_adjacency_graph(uint32_t n_verts, uint32_t n_faces, const uint32_t* faces,
                                      uint32_t* adj_ptr_out, uint32_t** adj_out, uint64_t* n_entries);
 

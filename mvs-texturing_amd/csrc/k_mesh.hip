@@ -13,7 +13,7 @@ mvs_status api_fail(mvs_status st, const std::string& msg);
 
 namespace {
 
-constexpr int MAX_NEIGHBOURS = 48;   // distinct neighbours of one face (3 for a manifold mesh)
+constexpr int MAX_NEIGHBOURS = 48;   // distinct neighbours of one face (3 for a manifold mesh); adjacency_kernel: of smaller id and of larger id, each
 
 __global__ void edge_key_kernel(const uint32_t* __restrict__ faces, uint32_t n_faces, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals,
                                 uint32_t* __restrict__ n_repeated) {
@@ -193,7 +193,7 @@ uint64_t build_adjacency(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint
         MVS_LAUNCH_CHECK();
         exclusive_scan_u32(ctx, ctx->g_cnt.p, ctx->g_adj_ptr.p, (size_t)F + 1, nullptr);
         const uint32_t total = read_u32(ctx, ctx->g_adj_ptr.p + F);
-        if (read_u32(ctx, overflow)) throw StatusError(MVS_ERR_UNSUPPORTED, "a face has more than 48 distinct neighbours (or a repeated vertex with more than 128 faces)");
+        if (read_u32(ctx, overflow)) throw StatusError(MVS_ERR_UNSUPPORTED, "a face has more than 48 distinct neighbours, or more than 128 other faces at its vertices (the mesh has a face with a repeated vertex)");
         ctx->g_adj.ensure((size_t)total + 1);
         hipLaunchKernelGGL(adjacency_general_kernel<true>, dim3((F + 127) / 128), dim3(128), 0, s, d_faces, F, (const uint32_t*)ctx->vf_ptr.p,
                            (const uint32_t*)ctx->vf.p, ctx->g_cnt.p, (const uint32_t*)ctx->g_adj_ptr.p, ctx->g_adj.p, overflow);
@@ -212,7 +212,7 @@ uint64_t build_adjacency(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint
     MVS_LAUNCH_CHECK();
     exclusive_scan_u32(ctx, ctx->g_cnt.p, ctx->g_adj_ptr.p, (size_t)F + 1, nullptr);
     const uint32_t total = read_u32(ctx, ctx->g_adj_ptr.p + F);
-    if (read_u32(ctx, overflow)) throw StatusError(MVS_ERR_UNSUPPORTED, "a face has more than 48 distinct neighbours");
+    if (read_u32(ctx, overflow)) throw StatusError(MVS_ERR_UNSUPPORTED, "a face has more than 48 neighbours of smaller id or more than 48 of larger id");
     ctx->g_adj.ensure((size_t)total + 1);
     hipLaunchKernelGGL(adjacency_kernel<true>, dim3((F + 127) / 128), dim3(128), 0, s, ctx->g_keys2.p, ctx->g_vals2.p, ctx->g_pos.p, F, ctx->g_cnt.p,
                        (const uint32_t*)ctx->g_adj_ptr.p, ctx->g_adj.p, overflow);
@@ -240,6 +240,13 @@ uint32_t prepare_mesh(mvs_ctx* ctx, const float* d_verts, const uint32_t* d_face
 
 using namespace mvs;
 
+// the one-shot entry points take host arrays: an index >= n_verts would address vf_ptr / vf_cursor past their ends on the device
+// (build_vertex_faces) and fall outside the 32 + bits(n_verts) key bits build_adjacency sorts by
+static bool vertex_ids_in_range(const uint32_t* faces, uint32_t n_faces, uint32_t n_verts) {
+    for (size_t i = 0; i < 3 * (size_t)n_faces; ++i) if (faces[i] >= n_verts) return false;
+    return true;
+}
+
 #define MVS_API_BEGIN try { MVS_HIP(hipSetDevice(ctx->device));
 #define MVS_API_END                                                               \
     } catch (const StatusError& e) { return api_fail(e.st, e.what()); }           \
@@ -265,6 +272,7 @@ mvs_status mvs_ctx_build_adjacency(mvs_ctx* ctx, uint32_t** adj_ptr_device, uint
 
 mvs_status mvs_build_adjacency_graph(uint32_t n_verts, uint32_t n_faces, const uint32_t* faces, uint32_t* adj_ptr_out, uint32_t** adj_out, uint64_t* n_entries) {
     if ((!faces && n_faces) || !adj_ptr_out || !adj_out) return api_fail(MVS_ERR_INVALID, "null argument");
+    if (!vertex_ids_in_range(faces, n_faces, n_verts)) return api_fail(MVS_ERR_INVALID, "vertex id out of range");
     mvs_ctx* ctx = nullptr;
     mvs_status st = mvs_ctx_create(mvs::default_device(), &ctx);
     if (st != MVS_OK) return st;
@@ -285,6 +293,7 @@ mvs_status mvs_build_adjacency_graph(uint32_t n_verts, uint32_t n_faces, const u
 
 mvs_status mvs_prepare_mesh(uint32_t n_verts, const float* verts, uint32_t n_faces, const uint32_t* faces, uint32_t* faces_out, float* normals_out, uint32_t* n_kept) {
     if ((!verts && n_verts) || (!faces && n_faces) || !faces_out || !normals_out || !n_kept) return api_fail(MVS_ERR_INVALID, "null argument");
+    if (!vertex_ids_in_range(faces, n_faces, n_verts)) return api_fail(MVS_ERR_INVALID, "vertex id out of range");
     mvs_ctx* ctx = nullptr;
     mvs_status st = mvs_ctx_create(mvs::default_device(), &ctx);
     if (st != MVS_OK) return st;

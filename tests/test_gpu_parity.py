@@ -750,6 +750,8 @@ def test_face_order_upper_levels_change_no_result(name):
     c.data_costs(M.Settings()); t0 = c.costs_download(); l0, s0 = c.view_selection(s.adj_ptr, s.adj)
     perm0, _ = c.partition_faces(1)
     c.close()
+    import order_model as OM
+    assert OM.check_order(s.verts, s.faces, perm0, 1)["violations"] == []      # (by default the upper levels start at a million faces)
     seen = [perm0]
     for window in (262144, 0, 8192):
         perms = []
@@ -759,6 +761,9 @@ def test_face_order_upper_levels_change_no_result(name):
             perm, _ = c.partition_faces(1)
             c.close()
             assert sorted(perm.tolist()) == list(range(F))
+            # every cut is where the kernels say it is (tests/tools/order_model.py), the upper levels stay inside their top windows
+            assert OM.check_order(s.verts, s.faces, perm, window)["violations"] == []
+            assert OM.check_windows(perm, perm0, F, window) == []
             assert np.array_equal(t1.col_ptr, t0.col_ptr) and np.array_equal(t1.view_id, t0.view_id) and np.array_equal(t1.cost.view(np.uint32), t0.cost.view(np.uint32))
             assert np.array_equal(l1, l0) and (s1["energy_fixed"], s1["sweeps"], s1["icm_iters"]) == (s0["energy_fixed"], s0["sweeps"], s0["icm_iters"])
             perms.append(perm)

@@ -10,6 +10,7 @@ import pytest
 import oracle_py as O
 from conftest import get_scene
 from util_cases import brute_force_optimum, energy_numpy, random_mrf
+import util_cases as U
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -274,6 +275,81 @@ def test_prepare_mesh_restatement():
     assert (n3[-1] == 0).all()                                               # zero-area face: zero normal, no NaN
 
 
+def _adjacency_numpy(faces):
+    """the neighbour SETS of a mesh without repeated-vertex faces: faces sharing an (unordered) edge, as sorted (face, neighbour) pairs"""
+    F = len(faces)
+    f = faces.astype(np.int64)
+    e = np.concatenate([np.sort(f[:, [0, 1]], axis=1), np.sort(f[:, [1, 2]], axis=1), np.sort(f[:, [2, 0]], axis=1)])
+    key = e[:, 0] << 32 | e[:, 1]
+    own = np.tile(np.arange(F), 3)
+    o = np.argsort(key, kind="stable"); key, own = key[o], own[o]
+    first = np.searchsorted(key, key, side="left"); last = np.searchsorted(key, key, side="right")
+    pairs = set()
+    for d in range(1, int((last - first).max())):
+        i = np.arange(len(key)); m = i + d < last
+        a, b = own[i[m]], own[i[m] + d]
+        ne = a != b
+        pairs |= set(zip(a[ne].tolist(), b[ne].tolist())) | set(zip(b[ne].tolist(), a[ne].tolist()))
+    return pairs
+
+
+def test_row_f1_cases_past_one_tile_and_at_the_capacity_limits():
+    """the oracle side of tests/test_gpu_mesh_stages.py: 20 480-face meshes (as built, repeated vertices, duplicates, open, each also
+    permuted) and the fans / discs at the capacity limits of csrc/k_mesh.hip -- lists are symmetric and without self loops, equal as
+    sets to an independent numpy edge match where no face repeats a vertex; the fans have the neighbour counts the limits are about"""
+    big = U.f1_large_meshes(get_scene("spiky32"))
+    assert len(big["built"][1]) == 20480 and len(big["built"][0]) == 10242
+    cases = {k: v for k, v in big.items()}
+    cases.update({k: (v[0], v[1]) for k, v in U.f1_limit_meshes().items()})
+    deg = {}
+    for name, (verts, faces) in cases.items():
+        ap, ad = O.build_adjacency(faces)
+        F = len(faces)
+        src = np.repeat(np.arange(F), np.diff(ap.astype(np.int64)))
+        assert not (src == ad).any(), name
+        fwd = set(zip(src.tolist(), ad.tolist()))
+        assert len(fwd) == len(ad) and all((g, i) in fwd for i, g in fwd), name
+        if not (faces[:, 0] == faces[:, 1]).any() and not (faces[:, 1] == faces[:, 2]).any() and not (faces[:, 0] == faces[:, 2]).any():
+            assert fwd == _adjacency_numpy(faces), name
+        deg[name] = np.diff(ap.astype(np.int64))
+        f2, n2 = O.prepare_mesh(verts, faces)
+        assert len(f2) <= F and n2.shape == f2.shape, name
+    assert (deg["built"] == 3).all() and deg["open"].min() < 3
+    assert len(O.prepare_mesh(*big["duplicates"])[0]) == 20480 and len(O.prepare_mesh(*big["duplicates-permuted"])[0]) == 20480
+    for tag in ("", "-general"):
+        assert (deg["fan49" + tag][:49] == 48).all() and (deg["fan50" + tag][:50] == 49).all()
+        assert deg["two_fans" + tag][48] == 96 and np.delete(deg["two_fans" + tag][:97], 48).max() == 48
+    assert (deg["fan97"] == 96).all()
+    assert (deg["disc129"][:129] == 2).all() and (deg["disc130"][:130] == 2).all()
+
+
+# Where the oracle alone misses the 2 ulp: the largest distance met, in units of 2^-23, of an oracle normal component from the float64
+# normal (measured with the test below).  At 2^-40 the squares of the cross product's components (2^-170) underflow and at 2^40 they
+# overflow (2^150) in float32: the length is 0 or infinite, the oracle -- and the device, bit for bit -- return the unnormalised cross
+# product or the zero vector, a whole unit vector away.  The coordinates stay normal numbers, the squared length does not.
+F1_NORMAL_ULPS = {"scale2^-40": 8387435.634032583, "scale2^40": 8387435.634032583}
+
+
+def test_row_f1_normals_over_the_exponent_range():
+    """the oracle side of the scaled meshes of tests/test_gpu_mesh_stages.py: the oracle's float32 normals (pinned to upstream) against
+    a float64 cross product and normalise of the float32 edge vectors, per component, in ulps of a unit vector's components (2^-23;
+    2 ulp = the atol = 2e-6 of test_prepare_mesh_restatement restated for unit vectors, eight times tighter).  Measured: 0.992 ulp at
+    2^-20 and 2^20, 0.531 ulp translated by 2^20 -- and 8 387 435.634 ulp (0.99986, the whole vector) at 2^-40 and 2^40, see
+    F1_NORMAL_ULPS: there the bound is that figure plus one ulp.  At 2^-70 even the cross products are denormal and no unit vector
+    comes out of float32 at all: that case is compared between device and oracle only."""
+    s = get_scene("tiny")
+    for name, (verts, faces) in U.f1_scaled_meshes(s).items():
+        f2, n2 = O.prepare_mesh(verts, faces)
+        assert np.array_equal(f2, faces), name
+        if name == "scale2^-70":
+            continue
+        ref = U.normals_float64(verts, faces)
+        assert np.isfinite(ref).all(), name
+        err = np.abs(n2.astype(np.float64) - ref).max() / 2.0 ** -23
+        print("f1 normals %-14s max error %.3f ulp" % (name, err))
+        assert err <= (F1_NORMAL_ULPS[name] + 1 if name in F1_NORMAL_ULPS else 2), (name, err)
+
+
 def _f3_cases():
     """(adj_ptr, adj, labels, n_labels) for the row-f3 stage: mesh graphs with few / many labels, one giant
     component, isolated nodes, and a random multigraph with duplicate list entries and high degrees"""
@@ -331,6 +407,28 @@ def test_get_subgraphs_restatement():
         g = sp.coo_matrix((np.ones(int(keep.sum())), (rows[keep], adj[keep].astype(np.int64))), shape=(F, F))
         ncc, _ = connected_components(g, directed=False)
         assert ncc == len(comp_ptr) - 1, name
+
+
+def test_row_f3_cases_past_one_tile_and_one_chunk():
+    """the oracle side of tests/test_gpu_mesh_stages.py: thousands of components, components far above the 256 nodes one BFS chunk
+    holds, frontiers above 256 nodes with degrees around 20 and duplicate list entries, a star, a path, one label, 70 000 labels --
+    against a plain-Python BFS; the cases are what they claim to be"""
+    cases = U.f3_large_cases(get_scene("spiky32"))
+    seen = {}
+    for name, (adj_ptr, adj, labels, n_labels) in cases.items():
+        label_ptr, comp_ptr, comp_faces = O.get_subgraphs(adj_ptr, adj, labels, n_labels)
+        lp, cp, cf, widest = U.subgraphs_python(adj_ptr, adj, labels, n_labels)
+        assert np.array_equal(label_ptr, lp) and np.array_equal(comp_ptr, cp) and np.array_equal(comp_faces, cf), name
+        seen[name] = (len(comp_ptr) - 1, int(np.diff(comp_ptr.astype(np.int64)).max()), widest)
+    assert seen["noisy40"][0] > 2048 and seen["sparse_labels"][0] > 2048
+    assert seen["bands"][1] > 4 * 256 and seen["one_label"] [:2] == (1, 20480)
+    assert seen["multigraph"][2] > 256 and seen["multigraph2"][2] > 256
+    ap, ad = cases["multigraph"][:2]
+    src = np.repeat(np.arange(3000), np.diff(ap.astype(np.int64)))
+    assert len(ad) > 55000 and len(set(zip(src.tolist(), ad.tolist()))) < len(ad)                  # degrees around 20, duplicates kept
+    assert seen["star"][:2] == (1, 1501) and seen["path"] == (1, 3000, 1)
+    lp = O.get_subgraphs(*cases["sparse_labels"])[0]
+    assert lp[5] == 0 and lp[69990] == lp[70000] == seen["sparse_labels"][0]
 
 
 def test_energy_is_within_a_fraction_of_a_percent_of_the_lp_lower_bound():

@@ -187,3 +187,200 @@ def isolated(fn):
                            env=dict(os.environ, MVS_TEST_ISOLATED="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
         assert r.returncode == 0 and " passed" in r.stdout, "isolated run of %s failed (exit code %d):\n%s" % (node, r.returncode, r.stdout[-6000:])
     return wrapper
+
+
+# ---- mesh-side cases past one tile: rows f1 and f3, the face order (tests/test_gpu_mesh_stages.py, test_gpu_face_order.py; the
+# ---- oracle side of every case runs in tests/test_oracle.py)
+
+def permuted_mesh(verts, faces, seed):
+    """the mesh through synth.permute_scene (faces and vertices in random order)"""
+    import mvs_texturing_amd as M
+    s = M.synth.Scene()
+    s.verts, s.faces = np.ascontiguousarray(verts), np.ascontiguousarray(faces)
+    s.normals = np.zeros((len(faces), 3), np.float32)
+    p = M.synth.permute_scene(s, seed=seed)
+    return p.verts, p.faces
+
+
+def f1_large_meshes(s):
+    """name -> (verts, faces) from the 20 480-face scene `s` (10 tiles of the 2048-element scan): as built, 1 % of the faces with a
+    repeated vertex (adjacency_general_kernel), 500 duplicated faces appended -- a third rotated, a third mirrored -- (the compaction of
+    prepare_mesh across tiles), the second half dropped (open boundary); each also with faces and vertices in random order"""
+    rng = np.random.default_rng(11)
+    F = len(s.faces)
+    out = {"built": (s.verts, s.faces)}
+    rep = s.faces.copy()
+    idx = rng.choice(F, F // 100, replace=False)
+    rep[idx, 1] = rep[idx, 0]
+    out["repeated"] = (s.verts, np.ascontiguousarray(rep))
+    d = s.faces[rng.choice(F, 500, replace=False)].copy()
+    d[0::3] = d[0::3][:, [1, 2, 0]]
+    d[1::3] = d[1::3][:, [0, 2, 1]]
+    out["duplicates"] = (s.verts, np.ascontiguousarray(np.concatenate([s.faces, d])))
+    out["open"] = (s.verts, np.ascontiguousarray(s.faces[: F // 2]))
+    for k, name in enumerate(list(out)):
+        out[name + "-permuted"] = permuted_mesh(*out[name], seed=20 + k)
+    return out
+
+
+def _with_repeated_face(faces, n_verts):
+    """one face (a, a, b) on two vertices of its own: the mesh takes adjacency_general_kernel, no other list changes"""
+    return np.concatenate([faces, np.array([[n_verts, n_verts, n_verts + 1]], np.uint32)]), n_verts + 2
+
+
+def fan_mesh(n, general=False, seed=1):
+    """n faces on ONE edge (0, 1), each with a third vertex of its own: every face has n - 1 neighbours, face i has i of smaller id"""
+    faces = np.stack([np.zeros(n, np.uint32), np.ones(n, np.uint32), 2 + np.arange(n, dtype=np.uint32)], axis=1)
+    nv = n + 2
+    if general:
+        faces, nv = _with_repeated_face(faces, nv)
+    verts = np.random.default_rng(seed).standard_normal((nv, 3)).astype(np.float32)
+    return verts, np.ascontiguousarray(faces.astype(np.uint32))
+
+
+def two_fans_mesh(general=False, seed=2):
+    """face 48 = (0, 1, 2) between a fan of 48 faces on its edge (0, 1), all of smaller id, and a fan of 48 on its edge (1, 2), all of
+    larger id: 96 neighbours, 48 on either side; no other face has more than 48"""
+    lo = np.stack([np.zeros(48, np.uint32), np.ones(48, np.uint32), 3 + np.arange(48, dtype=np.uint32)], axis=1)
+    hi = np.stack([np.ones(48, np.uint32), np.full(48, 2, np.uint32), 51 + np.arange(48, dtype=np.uint32)], axis=1)
+    faces = np.concatenate([lo, np.array([[0, 1, 2]], np.uint32), hi])
+    nv = 99
+    if general:
+        faces, nv = _with_repeated_face(faces, nv)
+    verts = np.random.default_rng(seed).standard_normal((nv, 3)).astype(np.float32)
+    return verts, np.ascontiguousarray(faces.astype(np.uint32))
+
+
+def disc_mesh(k, seed=3):
+    """k triangles around the hub vertex 0 (a closed disc) + one repeated-vertex face elsewhere: on the general path every hub face
+    sees the k - 1 others as candidates"""
+    i = np.arange(k, dtype=np.uint32)
+    faces = np.stack([np.zeros(k, np.uint32), 1 + i, 1 + (i + 1) % k], axis=1)
+    faces, nv = _with_repeated_face(faces, k + 1)
+    verts = np.random.default_rng(seed).standard_normal((nv, 3)).astype(np.float32)
+    return verts, np.ascontiguousarray(faces.astype(np.uint32))
+
+
+def f1_limit_meshes():
+    """name -> (verts, faces, refused): the capacity limits of csrc/k_mesh.hip (48 neighbours, 128 candidates) on either side.
+    `refused` follows from the kernels' own overflow counters: adjacency_kernel keeps up to 48 neighbours of smaller id and 48 of
+    larger id, adjacency_general_kernel 48 in all and 128 candidates."""
+    out = {}
+    for general in (False, True):
+        tag = "-general" if general else ""
+        out["fan49" + tag] = fan_mesh(49, general) + (False,)
+        out["fan50" + tag] = fan_mesh(50, general) + (True,)
+        out["two_fans" + tag] = two_fans_mesh(general) + (general,)
+    out["fan97"] = fan_mesh(97) + (True,)
+    out["disc129"] = disc_mesh(129) + (False,)
+    out["disc130"] = disc_mesh(130) + (True,)
+    return out
+
+
+def f1_scaled_meshes(s):
+    """name -> (verts, faces): the small mesh `s` scaled by powers of two, and translated by 2^20 at unit size (b - a cancels)"""
+    out = {}
+    for e in (-40, -20, 20, 40, -70):
+        out["scale2^%d" % e] = (np.ascontiguousarray(np.ldexp(s.verts, e).astype(np.float32)), s.faces)
+    out["translate2^20"] = (np.ascontiguousarray((s.verts + np.float32(2.0 ** 20)).astype(np.float32)), s.faces)
+    return out
+
+
+def normals_float64(verts, faces):
+    """float64 cross product and normalise of the float32 edge vectors b - a, c - a (NaN rows for zero-area faces)"""
+    v = np.asarray(verts, np.float32)
+    a, b, c = v[faces[:, 0]], v[faces[:, 1]], v[faces[:, 2]]
+    n = np.cross((b - a).astype(np.float32).astype(np.float64), (c - a).astype(np.float32).astype(np.float64))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def f1_id_meshes(s):
+    """name -> (n_verts, verts, faces) for n_verts = 512 and 513 (the key-bit boundary of the edge sort): the small mesh `s` padded with
+    unused vertices, its vertex 0 renumbered to the largest valid id n_verts - 1"""
+    out = {}
+    for nv in (512, 513):
+        assert len(s.verts) < nv
+        verts = np.zeros((nv, 3), np.float32); verts[:len(s.verts)] = s.verts
+        verts[nv - 1] = verts[0]; verts[0] = 0
+        faces = s.faces.copy(); faces[s.faces == 0] = nv - 1
+        out["nv%d" % nv] = (nv, verts, np.ascontiguousarray(faces))
+    return out
+
+
+def _lists_to_csr(lists):
+    ap = np.zeros(len(lists) + 1, np.uint32); ap[1:] = np.cumsum([len(l) for l in lists])
+    return ap, np.array([g for l in lists for g in l], dtype=np.uint32)
+
+
+def f3_large_cases(s):
+    """name -> (adj_ptr, adj, labels, n_labels) past one scan tile and one 256-node BFS chunk; `s` = the 20 480-face scene"""
+    rng = np.random.default_rng(17)
+    F = s.n_faces
+    out = {"noisy40": (s.adj_ptr, s.adj, rng.integers(0, 40, F).astype(np.uint32), 40),
+           "bands": (s.adj_ptr, s.adj, (np.arange(F) // 2000).astype(np.uint32), F // 2000 + 1),
+           "one_label": (s.adj_ptr, s.adj, np.zeros(F, np.uint32), 1)}
+    used = np.sort(rng.choice(np.arange(5, 69990), 50, replace=False)).astype(np.uint32)     # labels 0 .. 4 and 69 990 .. 69 999 stay empty
+    out["sparse_labels"] = (s.adj_ptr, s.adj, used[rng.integers(0, 50, F)], 70000)
+    n = 3000
+    lists = [[] for _ in range(n)]
+    for a, b in zip(rng.integers(0, n, 30000).tolist(), rng.integers(0, n, 30000).tolist()):
+        if a != b:
+            lists[a].append(b); lists[b].append(a)                       # duplicates stay in the lists
+    ap, ad = _lists_to_csr(lists)
+    out["multigraph"] = (ap, ad, np.zeros(n, np.uint32), 1)
+    out["multigraph2"] = (ap, ad, rng.integers(0, 2, n).astype(np.uint32), 2)
+    hub = [g for leaf in range(1, 1501) for g in (leaf, leaf)]           # every leaf twice in the hub's list
+    ap, ad = _lists_to_csr([hub] + [[0] for _ in range(1500)])
+    out["star"] = (ap, ad, np.ones(1501, np.uint32), 2)
+    ap, ad = _lists_to_csr([[g for g in (i - 1, i + 1) if 0 <= g < 3000] for i in range(3000)])
+    out["path"] = (ap, ad, np.zeros(3000, np.uint32), 1)
+    return out
+
+
+def subgraphs_python(adj_ptr, adj, labels, n_labels):
+    """uni_graph.cpp:21-55 for every label, in plain Python: (label_ptr, comp_ptr, comp_faces); also the largest BFS frontier met"""
+    import collections
+    F = len(adj_ptr) - 1
+    lists = np.split(np.asarray(adj), np.asarray(adj_ptr[1:-1]).astype(np.int64)) if F else []
+    lists = [l.tolist() for l in lists]
+    lab = np.asarray(labels).tolist()
+    used = [False] * F
+    by_label = collections.defaultdict(list)
+    widest = 0
+    for i in range(F):
+        if used[i]:
+            continue
+        q = collections.deque([i]); used[i] = True; comp = []
+        while q:
+            widest = max(widest, len(q))
+            u = q.popleft(); comp.append(u)
+            for v in lists[u]:
+                if lab[v] == lab[i] and not used[v]:
+                    used[v] = True; q.append(v)
+        by_label[lab[i]].append(comp)
+    label_ptr = np.zeros(n_labels + 1, np.uint32); comp_ptr = [0]; faces = []
+    for L in sorted(by_label):
+        label_ptr[L + 1:] += len(by_label[L])
+        for comp in by_label[L]:
+            faces += comp; comp_ptr.append(len(faces))
+    return label_ptr, np.array(comp_ptr, np.uint32), np.array(faces, np.uint32), widest
+
+
+def tie_mesh(m, seed=9):
+    """8192 faces, every one on three vertices of its own, laid out along x: 3072 distinct small triangles with centroid x < 0, then m
+    copies of ONE triangle whose centroid x is exactly 0, then 5120 - m distinct ones with x > 0.  The top cut of the whole mesh (rank
+    4096 along x, the longest extent) falls inside the copies for 1024 < m: m keys equal the pivot."""
+    rng = np.random.default_rng(seed)
+    F, n_neg = 8192, 3072
+    cx = np.concatenate([-rng.uniform(0.05, 1.0, n_neg), np.zeros(m), rng.uniform(0.05, 1.0, F - n_neg - m)])
+    centre = np.stack([cx, rng.uniform(-0.3, 0.3, F), rng.uniform(-0.3, 0.3, F)], axis=1)
+    centre[n_neg:n_neg + m, 1:] = [0.11, -0.07]
+    off = 0.01 * rng.standard_normal((F, 3, 3))
+    off[n_neg:n_neg + m] = [[-0.01, 0.0, 0.0], [0.0, 0.01, 0.0], [0.01, 0.0, 0.005]]          # x: -d + 0 + d = 0 exactly
+    verts = (centre[:, None, :] + off).reshape(-1, 3)
+    verts[3 * n_neg:3 * (n_neg + m), 0] = off[n_neg:n_neg + m, :, 0].reshape(-1)
+    verts = np.ascontiguousarray(verts.astype(np.float32))
+    faces = np.arange(3 * F, dtype=np.uint32).reshape(F, 3)
+    order = rng.permutation(F)                                                                 # the caller's numbering says nothing
+    return verts, np.ascontiguousarray(faces[order])
