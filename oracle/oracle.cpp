@@ -446,7 +446,13 @@ inline double multi_gauss(const double x[3], const double mu[3], const double ci
     return std::exp((w[0] * mr[0] + w[1] * mr[1]) + w[2] * mr[2]);
 }
 
-bool photometric_outlier_detection(std::vector<FaceInfo>* infos, const orc_settings& st) {
+// `trace` (tests only; the arithmetic does not read it): [0] the exit taken -- 0 nothing to do (no infos / no outlier removal),
+// 1 fewer than 4 inliers, 2 covariance below the minimum, 3 covariance not invertible, 4 all ten rounds; [1] the round of the exit
+// (10 after the loop); [2] inliers at the exit; [3] whether the last completed round still changed the inlier set
+bool photometric_outlier_detection(std::vector<FaceInfo>* infos, const orc_settings& st, int* trace = nullptr) {
+    int trace_none[4];
+    if (!trace) trace = trace_none;
+    trace[0] = trace[1] = trace[2] = trace[3] = 0;
     if (infos->size() == 0) return true;
     double const gauss_rejection_threshold = 6e-3;
     double const minimal_covariance = 5e-4;
@@ -463,7 +469,8 @@ bool photometric_outlier_detection(std::vector<FaceInfo>* infos, const orc_setti
     size_t n_in = n;
     double var_mean[3] = {0, 0, 0}, cov[3][3], cov_inv[3][3] = {{0}};
     for (int it = 0; it < outlier_detection_iterations; ++it) {
-        if ((int)n_in < minimal_num_inliers) return false;
+        trace[1] = it; trace[2] = (int)n_in;
+        if ((int)n_in < minimal_num_inliers) { trace[0] = 1; return false; }
         for (int a = 0; a < 3; ++a) {
             double s = 0.0;
             for (size_t r = 0; r < n; ++r) if (is_inlier[r]) s += (double)(*infos)[r].mean_color[a];
@@ -475,23 +482,31 @@ bool photometric_outlier_detection(std::vector<FaceInfo>* infos, const orc_setti
                 s += ((double)(*infos)[r].mean_color[a] - var_mean[a]) * ((double)(*infos)[r].mean_color[b] - var_mean[b]);
             cov[a][b] = s / double(n_in - 1);
         }
-        double mx = 0.0;
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) mx = std::max(mx, std::abs(cov[a][b]));
+        // covariance.array().abs().maxCoeff(): the reduction starts from the FIRST coefficient and replaces it only by a greater one,
+        // so a NaN variance of the first channel (a NaN colour) stays and fails the comparison below -- the function then returns
+        // false at the rank test, where a maximum started from 0 would return true here (same qualities, another return value)
+        double mx = std::abs(cov[0][0]);
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) if (std::abs(cov[a][b]) > mx) mx = std::abs(cov[a][b]);
         if (mx < minimal_covariance) {
             for (size_t r = 0; r < n; ++r) if (!is_inlier[r]) (*infos)[r].quality = 0.0f;
+            trace[0] = 2;
             return true;
         }
         Lu3 lu(cov);
-        if (!lu.invertible()) return false;
+        if (!lu.invertible()) { trace[0] = 3; return false; }
         lu.inverse(cov_inv);
         n_in = 0;
+        trace[3] = 0;
         for (size_t r = 0; r < n; ++r) {
             const double c[3] = {(*infos)[r].mean_color[0], (*infos)[r].mean_color[1], (*infos)[r].mean_color[2]};
             double g = multi_gauss(c, var_mean, cov_inv);
-            is_inlier[r] = (g >= gauss_rejection_threshold ? 1 : 0);
+            const uint32_t in = (g >= gauss_rejection_threshold ? 1 : 0);
+            if (in != is_inlier[r]) trace[3] = 1;
+            is_inlier[r] = in;
             n_in += is_inlier[r];
         }
     }
+    trace[0] = 4; trace[1] = outlier_detection_iterations; trace[2] = (int)n_in;
     for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) cov_inv[a][b] *= outlier_removal_factor;
     for (FaceInfo& info : *infos) {
         const double c[3] = {info.mean_color[0], info.mean_color[1], info.mean_color[2]};
@@ -599,14 +614,19 @@ int orc_ray_hit(const orc_bvh* b, const orc_mesh* mesh, const float origin[3], c
 }
 // photometric_outlier_detection (calculate_data_costs.cpp:35-129) on one face's infos, in the order given: mean_color[3n]
 // (already YCbCr), quality[n] updated in place; returns the function's bool
+int orc_outlier_detection_trace(uint32_t n, const float* mean_color, float* quality, int outlier_removal, int trace[4]);
 int orc_outlier_detection(uint32_t n, const float* mean_color, float* quality, int outlier_removal) {
+    return orc_outlier_detection_trace(n, mean_color, quality, outlier_removal, nullptr);
+}
+// the same, and which exit the function took (see photometric_outlier_detection; trace may be null)
+int orc_outlier_detection_trace(uint32_t n, const float* mean_color, float* quality, int outlier_removal, int trace[4]) {
     std::vector<FaceInfo> infos(n);
     for (uint32_t i = 0; i < n; ++i) {
         infos[i].view_id = (uint16_t)i; infos[i].quality = quality[i];
         for (int a = 0; a < 3; ++a) infos[i].mean_color[a] = mean_color[3 * (size_t)i + a];
     }
     orc_settings st; st.data_term = 0; st.outlier_removal = outlier_removal; st.geometric_visibility_test = 0;
-    const bool ok = photometric_outlier_detection(&infos, st);
+    const bool ok = photometric_outlier_detection(&infos, st, trace);
     for (uint32_t i = 0; i < n; ++i) quality[i] = infos[i].quality;
     return ok ? 1 : 0;
 }

@@ -108,6 +108,10 @@ int orc_ray_occluded(const orc_bvh* b, const orc_mesh* mesh, const float origin[
 int orc_ray_hit(const orc_bvh* b, const orc_mesh* mesh, const float origin[3], const float dir[3], float tmin, float tmax, int brute);
 /* photometric_outlier_detection (calculate_data_costs.cpp:35-129) on one face's infos in the order given */
 int orc_outlier_detection(uint32_t n, const float* mean_color, float* quality, int outlier_removal);
+/* the same, and the exit it took: trace[0] 0 nothing to do, 1 fewer than 4 inliers, 2 covariance below the minimum, 3 not
+ * invertible, 4 all ten rounds; trace[1] the round of the exit; trace[2] inliers at the exit; trace[3] whether the last completed
+ * round still changed the inlier set (tests only) */
+int orc_outlier_detection_trace(uint32_t n, const float* mean_color, float* quality, int outlier_removal, int trace[4]);
 
 /* ---- histogram (histogram.cpp:22-63) ---- */
 float orc_percentile(const float* values, uint64_t n, float max_value, float percentile);

@@ -1145,7 +1145,7 @@ def test_postprocess_face_infos_entry_point_equals_upstream_code():
     """mvs_postprocess_face_infos (tex::postprocess_face_infos, texturing.h:71-74) against the reference's OWN
     calculate_data_costs.cpp:253-306 compiled into oracle/_ref: infos in arbitrary (shuffled) order, zero qualities, empty
     faces, faces with < 4 infos, all three outlier modes.  Pattern and view ids identical; costs bit-equal without outlier
-    removal, within 1e-4 relative with it (fp64 exp: glibc vs OCML).  The reference's results are stored in
+    removal and with gauss_clamping, within 1e-4 relative with gauss_damping (fp64 exp: glibc vs OCML).  The reference's results are stored in
     tests/golden/reference_postprocess.npz (checked against the library where it is built, standing in for it elsewhere;
     re-record with the library built: MVS_RECORD_REFERENCE_PINS=1)."""
     ref_path = os.path.join(os.path.dirname(os.path.dirname(__file__)), "oracle", "_ref", "libtexref.so")
@@ -1158,8 +1158,9 @@ def test_postprocess_face_infos_entry_point_equals_upstream_code():
         got, st = M.viewsel.postprocess_face_infos(V, ptr, view, q, col, M.Settings(outlier_removal=name))
         assert got.nnz == m and np.array_equal(got.col_ptr, rp), name
         assert np.array_equal(got.view_id, rv[:m]), name
-        if mode == 0:
-            assert np.array_equal(got.cost.view(np.uint32), rc[:m].view(np.uint32))
+        print(name, "costs that differ from upstream's in bits:", int((got.cost.view(np.uint32) != rc[:m].view(np.uint32)).sum()), "of", m)
+        if name != "gauss_damping":                        # no exponential reaches the output: clamping only compares with a threshold
+            assert np.array_equal(got.cost.view(np.uint32), rc[:m].view(np.uint32)), name
         else:
             assert np.allclose(got.cost, rc[:m], rtol=REL_TOL, atol=1e-6), name
         assert (m == n) if mode == 0 else (0 < m < n)      # the zero-quality erase belongs to the outlier branch (:265-271)

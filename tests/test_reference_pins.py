@@ -654,7 +654,8 @@ def test_data_costs_on_a_hostile_soup_equal_the_reference(R, seed, spread):
 def test_outlier_detection_equals_the_reference_function(R):
     """row D1: photometric_outlier_detection (calculate_data_costs.cpp:35-129) itself, on synthetic colour sets that reach
     every exit: fewer than 4 inliers, covariance below 5e-4 (outliers zeroed), singular covariance (not invertible),
-    10 iterations without convergence, damping and clamping."""
+    10 iterations without convergence, damping and clamping; and on the non-finite colour sets and 20 of the exactly collinear /
+    coplanar sets the device is judged by (tests/tools/postprocess_model.py)."""
     OL = O.load()
     OL.orc_outlier_detection.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]; OL.orc_outlier_detection.restype = C.c_int
     R.ref_outlier_detection.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]; R.ref_outlier_detection.restype = C.c_int
@@ -673,6 +674,10 @@ def test_outlier_detection_equals_the_reference_function(R):
     cases.append(line.astype(np.float32))
     plane = rng.random((30, 3)).astype(np.float32); plane[:, 2] = plane[:, 0]                    # rank 2
     cases.append(plane)
+    import postprocess_model as PM
+    crafted = PM.non_finite_faces(np.random.default_rng(12)) + PM.rank_deficient_faces(np.random.default_rng(13), 20)
+    assert len(crafted) == 38 and not all(np.isfinite(f[0]).all() for f in crafted)
+    cases += [f[0] for f in crafted]
     outcomes = set()
     for col in cases:
         col = np.ascontiguousarray(col, np.float32)
