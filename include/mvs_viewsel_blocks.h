@@ -22,6 +22,14 @@ mvs_status mvs_ctx_dc_set_histogram(mvs_ctx* ctx, const uint32_t* src_device);
 /* copy the resident costs into caller-owned DEVICE arrays (stream-ordered): counts[n_faces] = column lengths, view_id[nnz], cost[nnz]
  * -- the pieces a driver all-gathers into the global table */
 mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts_device, uint16_t* view_id_device, float* cost_device);
+/* HARNESS ONLY (tests/test_gpu_occlusion_rays.py): the bit matrices of the occlusion-ray stage (csrc/k_bvh.hip) as the context's last
+ * data-cost pass left them: which = 0 the NEED bits (some face on the vertex passed the culls for the view: the ray is traced), 1 the OCCLUDED
+ * bits (what ray_packet3_kernel wrote).  View-major, (n_verts + 63) / 64 64-bit words per view, bit (v & 63) of word (v >> 6) = vertex v in
+ * the CALLER's vertex numbering (the device matrices follow the library's curve order; the entry maps them back).  which = 2: that order
+ * itself, n_verts 32-bit words, entry s = the caller's id of the vertex at curve position s -- 64 consecutive positions share a device word,
+ * i.e. a ray packet.  *n_bytes = size of the matrix / the order; out_host == null: the size only.  MVS_ERR_STATE before a data-cost pass
+ * with the geometric visibility test, or when the last pass covered a face range and not the whole mesh. */
+mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----
  * Every rank holds the FULL cost table and adjacency (288 GB of HBM make the

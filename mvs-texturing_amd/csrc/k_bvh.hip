@@ -545,12 +545,18 @@ __global__ void __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) r
     s_ray[wv][lane][1] = make_float4(r.d.x, r.d.y, r.d.z, r.tmax);
     s_src[wv][lane] = (uint8_t)lane; if (lane < 16) s_src[wv][64 + lane] = (uint8_t)lane;
     const V3 inv = {1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z};
-    const V3 oi = {r.o.x * inv.x, r.o.y * inv.y, r.o.z * inv.z};
+    // An axis on which the ray does not move (d == 0, 1 / d = +-inf; likewise a huge or NaN 1 / d) has no crossing times: bound * inv and
+    // o * inv are both infinite there and the slab test's bound * inv - o * inv is -inf, +inf or NaN by the SIGNS of bound and o, not by their
+    // order -- a box that straddles the coordinate origin on that axis lost rays that run inside it (tests/test_gpu_occlusion_rays.py,
+    // ray_terrace).  With o * inv = NaN both times of the axis are NaN for every box, the generic test's fmin / fmax drop them and the axis
+    // decides nothing: conservative, and the hit predicate alone decides the bit.  Such a lane always puts its packet on the generic test.
+    const float big = 1e30f;
+    const float no_t = __builtin_nanf("");
+    const V3 oi = {fabsf(inv.x) < big ? r.o.x * inv.x : no_t, fabsf(inv.y) < big ? r.o.y * inv.y : no_t, fabsf(inv.z) < big ? r.o.z * inv.z : no_t};
     const float t0 = r.tmin * 0.999f, t1 = r.tmax * 1.001f;
     const unsigned long long actm = __builtin_amdgcn_ballot_w64(active);
     unsigned long long live = actm;
     // direction-sign octant of the packet over its live lanes; 8 = mixed / degenerate
-    const float big = 1e30f;
     const unsigned long long okm = __builtin_amdgcn_ballot_w64(fabsf(inv.x) < big && fabsf(inv.y) < big && fabsf(inv.z) < big) & actm;
     const unsigned long long nxm = __builtin_amdgcn_ballot_w64(inv.x < 0.0f) & actm, nym = __builtin_amdgcn_ballot_w64(inv.y < 0.0f) & actm,
                              nzm = __builtin_amdgcn_ballot_w64(inv.z < 0.0f) & actm;

@@ -124,6 +124,46 @@ mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts, uint16_t* view_i
     MVS_API_END
 }
 
+// harness only: need / occluded bits of the last data-cost pass (k_dc.hip dc_phase1 -> k_bvh.hip trace_rays), device rows in curve order ->
+// host rows in the caller's vertex numbering through vperm (position s of the curve = the caller's vertex vperm[s])
+mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
+    if (!ctx || !n_bytes || which < 0 || which > 2) return api_fail(MVS_ERR_INVALID, "bad argument");
+    // dc_stats.pairs: set by the pass over the scene (faces of the range x views), zero after mvs_postprocess_face_infos
+    const uint64_t whole = (uint64_t)ctx->n_faces * ctx->n_views;
+    if (ctx->dc_phase < 1 || !ctx->dc_settings.geometric_visibility_test || whole == 0 || ctx->n_verts == 0 || ctx->dc_stats.pairs != whole ||
+        ctx->face_begin != 0 || ctx->face_end != ctx->n_faces || !ctx->need_bits.p || !ctx->occl_bits.p || !ctx->vperm.p)
+        return api_fail(MVS_ERR_STATE, "ray bits: needs a data-cost pass with the visibility test over the whole mesh");
+    MVS_API_BEGIN
+    const uint32_t NV = ctx->n_verts, V = ctx->n_views, vwords = (NV + 63) / 64;
+    const uint64_t words = (uint64_t)V * vwords, n = which == 2 ? (uint64_t)NV * sizeof(uint32_t) : words * sizeof(unsigned long long);
+    *n_bytes = n;
+    if (out_host && cap_bytes < n) throw StatusError(MVS_ERR_INVALID, "ray bits: buffer too small");
+    if (out_host && which == 2) {
+        MVS_HIP(hipMemcpyAsync(out_host, ctx->vperm.p, n, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    } else if (out_host) {
+        std::vector<unsigned long long> dev(words);
+        std::vector<uint32_t> vperm(NV);
+        MVS_HIP(hipMemcpyAsync(dev.data(), which == 0 ? ctx->need_bits.p : ctx->occl_bits.p, n, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipMemcpyAsync(vperm.data(), ctx->vperm.p, (size_t)NV * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+        unsigned long long* out = (unsigned long long*)out_host;
+        memset(out, 0, n);
+        for (uint32_t j = 0; j < V; ++j)
+            for (uint32_t s = 0; s < NV; ++s)
+                if ((dev[(size_t)j * vwords + (s >> 6)] >> (s & 63u)) & 1ull) {
+                    const uint32_t v = vperm[s];
+                    if (v >= NV) throw StatusError(MVS_ERR_STATE, "ray bits: vertex order is not a permutation");
+                    out[(size_t)j * vwords + (v >> 6)] |= 1ull << (v & 63u);
+                }
+        // lanes behind the last vertex of a row must be clear on the device: they have no vertex to be mapped to
+        if (NV & 63u)
+            for (uint32_t j = 0; j < V; ++j)
+                if (dev[(size_t)j * vwords + vwords - 1] >> (NV & 63u)) throw StatusError(MVS_ERR_STATE, "ray bits: a bit behind the last vertex is set");
+    }
+    MVS_API_END
+}
+
 mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");

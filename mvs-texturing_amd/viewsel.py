@@ -176,7 +176,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits"))
 
 
 _lib = None
@@ -234,6 +234,7 @@ def load_library():
         "mvs_ctx_mrf_icm_gain": [vp, u32, u32], "mvs_ctx_mrf_icm_apply": [vp, u32, u32, vp],
         "mvs_ctx_mrf_labels": [vp, u32, u32, vp, C.POINTER(u32)],
         "mvs_ctx_mrf_setup_tables": [vp, i32, vp, u64, C.POINTER(u64)],
+        "mvs_ctx_ray_bits": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_comm_unique_id": [vp], "mvs_comm_create_rccl": [i32, i32, i32, vp, C.POINTER(vp)], "mvs_comm_create_local": [i32, C.POINTER(vp)], "mvs_comm_create_local_devices": [i32, vp, C.POINTER(vp)],
@@ -554,6 +555,31 @@ class Context:
             out[key] = buf
         out["bitmaps"] = bool(out["bitmaps"][0]); out["desc"] = out["desc"].reshape(-1, 12)
         return out
+
+    def ray_bits(self):
+        """the bit matrices of the occlusion-ray stage after the last data-cost pass (mvs_ctx_ray_bits, building-blocks library; test harness
+        only): (need, occl), bool arrays [n_views, n_verts] in the caller's vertex numbering -- need[j, v]: the ray from vertex v to camera j
+        was traced, occl[j, v]: it was found occluded"""
+        nv = int(self._keep["mesh"][0].shape[0])
+        out = []
+        for which in (0, 1):
+            n = C.c_uint64(0)
+            _check(self.L, self.L.mvs_ctx_ray_bits(self.h, which, None, 0, C.byref(n)))
+            buf = np.zeros(n.value // 8, dtype=np.uint64)
+            _check(self.L, self.L.mvs_ctx_ray_bits(self.h, which, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+            bits = np.unpackbits(buf.view(np.uint8).reshape(self.n_views, -1), axis=1, bitorder="little")
+            assert not bits[:, nv:].any()
+            out.append(bits[:, :nv].astype(bool))
+        return out[0], out[1]
+
+    def ray_vertex_order(self):
+        """uint32[n_verts]: the caller's id of the vertex at every position of the library's vertex order (mvs_ctx_ray_bits, which = 2): the
+        rays of 64 consecutive positions and one view form a packet of the ray kernel"""
+        n = C.c_uint64(0)
+        _check(self.L, self.L.mvs_ctx_ray_bits(self.h, 2, None, 0, C.byref(n)))
+        buf = np.zeros(n.value // 4, dtype=np.uint32)
+        _check(self.L, self.L.mvs_ctx_ray_bits(self.h, 2, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return buf
 
     def mrf_diagnostics(self):
         """{graph_launches, graph_updates, graph_instantiations, generic_nodes} of this context's view selections"""

@@ -544,3 +544,71 @@ def test_ray_predicate_agrees_with_exact_geometry_away_from_boundaries():
         assert bool(got) == truth, (tri, o, p, margins)
         checked += 1; hits += truth
     assert checked > 2500 and 100 < hits < checked - 100
+
+
+# ---- the oracle half of the crafted ray scenes (tests/util_cases.py ray_*; the GPU half is tests/test_gpu_occlusion_rays.py): the
+# ---- conditions that keep the GPU tests from passing vacuously
+
+@pytest.mark.parametrize("name", list(U.ray_scenes()))
+def test_crafted_ray_scenes_bvh_equals_brute_force_and_occlusion_decides(name):
+    """every crafted ray scene: the oracle's BVH and its brute-force loop give the same pattern and counters, some pairs are culled as
+    occluded and some survive, no pair is culled for zero quality (the need bits are derived from the pattern without the rays)"""
+    s = U.ray_scenes()[name]()
+    a, sa = O.data_costs(s, brute=False)
+    b, sb = O.data_costs(s, brute=True)
+    assert np.array_equal(a.col_ptr, b.col_ptr) and np.array_equal(a.view_id, b.view_id)
+    for k in ("cull_backface", "cull_angle", "cull_outside", "cull_occluded", "cull_zero_quality", "nnz_pre"):
+        assert sa[k] == sb[k], k
+    assert sa["cull_occluded"] > 0 and a.nnz > 0 and sa["cull_zero_quality"] == 0
+    nv, sn = O.data_costs(s, geometric_visibility_test=False)
+    assert sn["cull_zero_quality"] == 0 and nv.nnz == a.nnz + sa["cull_occluded"]
+    need = U.need_from_pass_pattern(s, nv.col_ptr, nv.view_id)
+    occl = U.ray_truth(s, need)
+    assert occl.any() and (need & ~occl).any()
+    if name.startswith("strip"):
+        assert not need[:, s.faces.max() + 1:].any()                       # vertices no face references need no ray
+    if name == "octants":
+        per_view = np.bincount(a.view_id, minlength=s.n_views)
+        assert (per_view > 0).all() and occl.any(axis=1).all() and s.n_views == 8
+        d = s.cams["pos"][:, None, :] - s.verts[None, :, :]                 # all rays towards one camera share their three signs
+        assert (np.sign(d) == np.sign(s.cams["pos"])[:, None, :]).all() and len({tuple(r) for r in np.sign(s.cams["pos"])}) == 8
+    if name == "fence":
+        vid = {(int(x), int(y)): k for k, (x, y, z) in enumerate(s.verts[:81])}
+        col = [vid[0, y] for y in range(-4, 4)]                                # the ground vertices in the wall's plane that camera 0 needs
+        assert need[0, col].all() and (s.cams["pos"][0, 0] - s.verts[col, 0] == 0).all()
+        # from (0, -1, 0) and (0, 0, 0) the segment to (0, 4, 3) runs through the wall's area (z = 1.2 / 0.75 at y = 1): in its plane, no hit
+        assert not occl[0].any()
+        # from behind the wall level with its edge y = 1: the hit lies ON the upright edge and counts
+        assert occl[2, [vid[2, 1], vid[4, 1]]].all() and need[1, 81:].all() and not occl[1, 81:].any()
+    if name == "confetti":
+        assert np.nonzero(occl[0])[0].tolist() == sorted(U.CONFETTI_VERTS) and need[0, list(U.CONFETTI_VERTS)].all()
+        assert not occl[1].any() and need[1].sum() > 81
+        assert len(s.faces) == 141 and len(s.verts) == 120
+
+
+def test_ray_terrace_has_exact_zero_components_and_boundary_rays():
+    """ray_terrace as built: 136 faces on 90 vertices (a partial last need word); needed rays whose fp32 direction has one and two
+    components exactly zero; the rays through the plate's rim, an inner edge, its centre vertex and a shared diagonal are needed, and
+    the predicate's brute-force answers for them are recorded here (the GPU must reproduce them, whatever they are)"""
+    s = U.ray_terrace()
+    assert s.faces.shape == (136, 3) and s.verts.shape == (90, 3) and s.n_views == 10
+    assert np.array_equal(s.verts[40], np.float32([0, 0, 0]))
+    nv, sn = O.data_costs(s, geometric_visibility_test=False)
+    need = U.need_from_pass_pattern(s, nv.col_ptr, nv.view_id)
+    occl = U.ray_truth(s, need)
+    d = s.cams["pos"][:, None, :] - s.verts[None, :, :]                     # fp32 subtraction, as make_ray forms it
+    zeros = (d == 0).sum(axis=2)
+    assert (need & (zeros == 1)).sum() >= 40 and (need[:5, :81] & (zeros[:5, :81] == 2)).sum() == 5   # the five vertices under cameras 0 - 4
+    # both signs of the non-zero components beside a zero one, and a zero component on every axis but z (no camera is level with the ground)
+    for a in (0, 1):
+        assert (need & (d[:, :, a] == 0) & (d[:, :, 1 - a] > 0)).any() and (need & (d[:, :, a] == 0) & (d[:, :, 1 - a] < 0)).any()
+    vid = {(int(x), int(y)): k for k, (x, y, z) in enumerate(s.verts[:81])}
+    # camera 5 at (-2, 0, 2): from the origin the ray meets z = 0.5 at x = -0.5, the plate's rim
+    assert need[5, vid[0, 0]] and np.array_equal(s.cams["pos"][5], np.float32([-2, 0, 2]))
+    recorded = {"rim": bool(occl[5, vid[0, 0]]), "inner_edge": bool(occl[0, vid[0, 0]]), "centre_vertex": bool(occl[1, vid[1, 0]]),
+                "diagonal": bool(occl[2, vid[2, 1]]), "inner_edge_2": bool(occl[3, vid[1, 1]]), "clear": bool(occl[4, vid[-3, -2]])}
+    assert all(need[j, vid[xy]] for j, xy in ((0, (0, 0)), (1, (1, 0)), (2, (2, 1)), (3, (1, 1)), (4, (-3, -2))))
+    # a hit ON an edge, a corner or the shared diagonal belongs to at least one of the triangles that meet there: the plate has no leak
+    assert recorded == {"rim": recorded["rim"], "inner_edge": True, "centre_vertex": True, "diagonal": True, "inner_edge_2": True, "clear": False}
+    assert recorded["rim"] is True, recorded
+    assert need[9].sum() == 0                                                # level with the plate: the angle cull leaves that view no pair

@@ -384,3 +384,181 @@ def tie_mesh(m, seed=9):
     faces = np.arange(3 * F, dtype=np.uint32).reshape(F, 3)
     order = rng.permutation(F)                                                                 # the caller's numbering says nothing
     return verts, np.ascontiguousarray(faces[order])
+
+
+# ---- crafted scenes for the occlusion rays (csrc/k_bvh.hip): every (vertex, view) bit is checked against the oracle's brute-force loop in
+# ---- tests/test_gpu_occlusion_rays.py; the oracle side of every scene runs in tests/test_oracle.py.  Coordinates are small integers or
+# ---- halves, so rays through edges, corners and diagonals, zero direction components and flat boxes are exact in fp32.
+
+def lookat_scene(verts, faces, normals, cam_pos, cam_target, sizes, focal=0.9, seed=0):
+    """a synth.Scene (no adjacency) of the mesh with one pinhole camera per row of cam_pos looking at cam_target[j] (up = +z, or +y for a
+    camera that looks along z), focal length `focal` x the larger image side, sizes[j % len(sizes)] = (width, height), noise images >= 1"""
+    import mvs_texturing_amd as M
+    rng = np.random.default_rng(seed)
+    s = M.synth.Scene()
+    s.verts = np.ascontiguousarray(verts, dtype=np.float32)
+    s.faces = np.ascontiguousarray(faces, dtype=np.uint32)
+    s.normals = np.ascontiguousarray(normals, dtype=np.float32)
+    cams = {k: [] for k in ("pos", "viewdir", "K", "w2c", "width", "height")}
+    for j, (p, t) in enumerate(zip(np.asarray(cam_pos, np.float64), np.asarray(cam_target, np.float64))):
+        w, h = sizes[j % len(sizes)]
+        fwd = (t - p) / np.linalg.norm(t - p)
+        up = np.array([0.0, 0.0, 1.0]) if abs(fwd[2]) < 0.9 else np.array([0.0, 1.0, 0.0])
+        right = np.cross(fwd, up); right /= np.linalg.norm(right)
+        down = np.cross(fwd, right)
+        R = np.stack([right, down, fwd]).astype(np.float32)
+        p32 = p.astype(np.float32)
+        w2c = np.eye(4, dtype=np.float32); w2c[:3, :3] = R; w2c[:3, 3] = -(R @ p32)
+        fl = np.float32(focal * max(w, h))
+        K = np.float32([[fl, 0, w / 2], [0, fl, h / 2], [0, 0, 1]])
+        cams["pos"].append(p32); cams["viewdir"].append(fwd.astype(np.float32)); cams["K"].append(K.ravel()); cams["w2c"].append(w2c.ravel())
+        cams["width"].append(w); cams["height"].append(h)
+        s.images.append(np.ascontiguousarray(rng.integers(1, 255, (h, w, 3)).astype(np.uint8)))
+    s.cams = {k: np.ascontiguousarray(np.array(v, dtype=np.int32 if k in ("width", "height") else np.float32)) for k, v in cams.items()}
+    return s
+
+
+def _quad_grid(xs, ys, z):
+    """(verts, faces): len(xs) x len(ys) vertices at height z (vertex iy * len(xs) + ix), every quad cut along its (low, low) - (high, high)
+    diagonal, counter-clockwise seen from +z"""
+    nx, ny = len(xs), len(ys)
+    verts = np.array([[x, y, z] for y in ys for x in xs], np.float64)
+    faces = []
+    for iy in range(ny - 1):
+        for ix in range(nx - 1):
+            a = iy * nx + ix; b = a + 1; c = a + nx + 1; d = a + nx
+            faces += [[a, b, c], [a, c, d]]
+    return verts, np.array(faces, np.uint32)
+
+
+def _terrace_mesh():
+    """8 x 8 unit quads in z = 0 over [-4, 4]^2 (81 vertices, vertex 40 at the origin) and a plate of 2 x 2 quads at z = 0.5 over
+    x in [-0.5, 2.5], y in [-1.5, 1.5]: 136 faces, 90 vertices"""
+    gv, gf = _quad_grid(np.arange(-4.0, 5.0), np.arange(-4.0, 5.0), 0.0)
+    pv, pf = _quad_grid([-0.5, 1.0, 2.5], [-1.5, 0.0, 1.5], 0.5)
+    return np.concatenate([gv, pv]), np.concatenate([gf, pf + len(gv)])
+
+
+# the ten cameras of ray_terrace: position, target.  0 - 4 hang straight above ground vertices: the ray from that vertex has direction
+# (0, 0, 1), the rays from its row and column one zero component; 0 crosses the plate on an inner edge, 1 in the plate's centre vertex, 2 on the
+# shared diagonal of two plate triangles, 3 on another inner edge, 4 is clear of the plate.  5: the ray from the origin crosses z = 0.5 at
+# x = -0.5, exactly on the plate's rim.  9 lies in the plate's own plane (the angle cull leaves it no pair: its need words are empty).
+TERRACE_CAMS = [((0, 0, 6), (0, 0, 0)), ((1, 0, 6), (1, 0, 0)), ((2, 1, 6), (2, 1, 0)), ((1, 1, 6), (1, 1, 0)), ((-3, -2, 6), (-3, -2, 0)),
+                ((-2, 0, 2), (0.5, 0, 0)), ((-1.5, 0, 1), (0.5, 0, 0)), ((5, 5, 5), (0, 0, 0)), ((-5, 5, 2), (0, 0, 0)), ((6, 0, 0.5), (0, 0, 0.5))]
+RAY_SIZES = [(200, 150), (160, 120), (320, 240), (173, 131)]
+
+
+def ray_terrace(off=(0, 0, 0), scale=1.0):
+    """a flat ground with a plate half a unit above it, cameras that put rays through the plate's rim, an inner edge, a corner and a shared
+    diagonal and give directions with one or two components exactly zero; moved by `off` after scaling by `scale` (mesh and cameras alike)"""
+    v, f = _terrace_mesh()
+    off = np.asarray(off, np.float64)
+    n = np.tile(np.float32([0, 0, 1]), (len(f), 1))
+    pos = np.array([c[0] for c in TERRACE_CAMS], np.float64) * scale + off
+    tgt = np.array([c[1] for c in TERRACE_CAMS], np.float64) * scale + off
+    return lookat_scene(v * scale + off, f, n, pos, tgt, RAY_SIZES, focal=0.5, seed=31)
+
+
+def ray_octants():
+    """the terrace and its mirror image below it (z -> -z - 0.01, winding reversed), eight cameras at (+-20, +-20, +-20): every ray towards
+    camera j has the same three direction signs, so view j runs one sign-specialised instance of the traversal and the eight views all eight"""
+    v, f = _terrace_mesh()
+    v2 = v.copy(); v2[:, 2] = -v2[:, 2] - 0.01
+    verts = np.concatenate([v, v2]); faces = np.concatenate([f, f[:, [0, 2, 1]] + len(v)])
+    n = np.concatenate([np.tile(np.float32([0, 0, 1]), (len(f), 1)), np.tile(np.float32([0, 0, -1]), (len(f), 1))])
+    pos = np.array([[sx * 20.0, sy * 20.0, sz * 20.0] for sz in (1, -1) for sy in (1, -1) for sx in (1, -1)])
+    return lookat_scene(verts, faces, n, pos, np.zeros_like(pos), RAY_SIZES, focal=2.5, seed=32)
+
+
+CONFETTI_VERTS = (3, 4, 5, 6, 7, 20, 33, 40, 41, 60, 63, 64, 80)
+CONFETTI_CAM = (0.25, -0.25, 6.0)
+
+
+def ray_confetti():
+    """the 8 x 8 ground (81 vertices) under thirteen triangles of half-width 0.02 at z = 0.5, each centred on the segment from one ground
+    vertex of CONFETTI_VERTS to camera 0: view 0 has exactly those thirteen vertices occluded, each by a triangle of its own, and the
+    thirteen triangles fill a leaf or two; camera 1 at (3, 2, 7) is shadowed by none"""
+    gv, gf = _quad_grid(np.arange(-4.0, 5.0), np.arange(-4.0, 5.0), 0.0)
+    cam = np.array(CONFETTI_CAM)
+    verts = [gv]; faces = [gf]
+    for i, k in enumerate(CONFETTI_VERTS):
+        c = gv[k] + (cam - gv[k]) * (0.5 / cam[2])
+        verts.append(c + np.array([[-0.02, -0.01, 0.0], [0.02, -0.01, 0.0], [0.0, 0.02, 0.0]]))
+        faces.append(np.array([[0, 1, 2]], np.uint32) + 81 + 3 * i)
+    verts = np.concatenate(verts); faces = np.concatenate(faces)
+    n = np.tile(np.float32([0, 0, 1]), (len(faces), 1))
+    return lookat_scene(verts, faces, n, [CONFETTI_CAM, (3.0, 2.0, 7.0)], [(0.0, 0.0, 0.0), (0.0, 0.0, 0.0)], [(320, 240), (200, 150)], focal=0.5, seed=33)
+
+
+RAY_STRIP_SIZES = (3, 15, 16, 17, 63, 64, 65, 66, 255, 256, 257, 258, 1024, 1025, 4097)
+
+
+def ray_strip(F, extra_verts=0, plate="middle"):
+    """F faces: F - 2 ground triangles in a zigzag strip along x (vertex k at (k / 2, k % 2, 0)) and a plate of two triangles half a unit
+    above its middle -- or, plate = "end", above its far end, reaching past it: the triangles of largest x, which the face order puts into
+    the LAST leaf; three cameras over the plate.  With 16 triangles per leaf and four children per node the sizes of RAY_STRIP_SIZES
+    give trees of one to five levels on both sides of every boundary, partial last leaves and level-0 nodes with one to four children.
+    extra_verts: vertices that no face references, placed last (under the plate, inside the scene's box)."""
+    k = np.arange(F)
+    gv = np.stack([k * 0.5, (k % 2).astype(np.float64), np.zeros(F)], axis=1)
+    gf = np.array([[i, i + 1, i + 2] if i % 2 else [i, i + 2, i + 1] for i in range(F - 2)], np.uint32).reshape(-1, 3)
+    mid = np.floor((F - 1) * 0.25 * 2.0) / 2.0 if plate == "middle" else (F - 1) * 0.5
+    pv = np.array([[mid - 0.75, -0.25, 0.5], [mid + 0.75, -0.25, 0.5], [mid + 0.75, 1.25, 0.5], [mid - 0.75, 1.25, 0.5]])
+    pf = np.array([[0, 1, 2], [0, 2, 3]], np.uint32) + F
+    verts = np.concatenate([gv, pv] + ([np.tile([[mid, 0.5, 0.25]], (extra_verts, 1))] if extra_verts else []))
+    faces = np.concatenate([gf, pf])
+    n = np.tile(np.float32([0, 0, 1]), (len(faces), 1))
+    pos = [(mid, 0.5, 6.0), (mid + 3.0, 0.5, 4.0), (mid - 7.0, 0.5, 4.0)]
+    return lookat_scene(verts, faces, n, pos, [(mid, 0.5, 0.0)] * 3, [(160, 120), (200, 150)], seed=34)
+
+
+FENCE_CAMS = [((0, 4, 3), (0, 0, 0)), ((4, 2, 2), (0, 1, 0.5)), ((-4, 1, 2), (0, 1, 0.5))]
+
+
+def ray_fence():
+    """the 8 x 8 ground and an upright wall of two triangles in the plane x = 0 (y in [1, 2], z in [0.5, 1.5], normal +x): a box of zero
+    thickness along x.  Camera 0 lies IN that plane: the rays from the ground vertices (0, y, 0) run inside the wall's plane (direction x
+    exactly zero, origin x equal to the box's) and two of them through the wall's area -- a ray in a triangle's plane does not hit it.
+    Camera 1 sees the wall's front, rays from behind it are stopped; camera 2 behind it is level with the wall's edge y = 1: the rays from
+    (2, 1, 0) and (4, 1, 0) meet the wall ON that upright edge."""
+    gv, gf = _quad_grid(np.arange(-4.0, 5.0), np.arange(-4.0, 5.0), 0.0)
+    wv = np.array([[0, 1, 0.5], [0, 2, 0.5], [0, 2, 1.5], [0, 1, 1.5]], np.float64)
+    wf = np.array([[0, 1, 2], [0, 2, 3]], np.uint32) + len(gv)
+    n = np.concatenate([np.tile(np.float32([0, 0, 1]), (len(gf), 1)), np.tile(np.float32([1, 0, 0]), (2, 1))])
+    return lookat_scene(np.concatenate([gv, wv]), np.concatenate([gf, wf]), n, [c[0] for c in FENCE_CAMS], [c[1] for c in FENCE_CAMS],
+                        RAY_SIZES, focal=0.5, seed=35)
+
+
+def ray_scenes():
+    """name -> builder of every crafted ray scene and variant (tests/test_oracle.py and tests/test_gpu_occlusion_rays.py walk the same list)"""
+    out = {"terrace": ray_terrace, "terrace-far": lambda: ray_terrace(off=(1000, -2000, 500)), "terrace-small": lambda: ray_terrace(scale=1e-3),
+           "terrace-large": lambda: ray_terrace(off=(1e5, 0, 0), scale=1e3), "octants": ray_octants, "confetti": ray_confetti, "fence": ray_fence}
+    for F in RAY_STRIP_SIZES:
+        out["strip%d" % F] = (lambda F=F: ray_strip(F, extra_verts=3 if F == 63 else 0))
+    for F in (3, 17, 65, 257, 1025, 4097):       # one face, or one leaf, node or level more than full: the plate in the last leaf
+        out["strip%d-end" % F] = (lambda F=F: ray_strip(F, plate="end"))
+    return out
+
+
+def ray_truth(s, need):
+    """occl[j, v] for every need[j, v]: the oracle's any-hit predicate evaluated by brute force over all triangles (orc_ray_occluded)"""
+    import ctypes as C
+    import oracle_py as O
+    L = O.load()
+    mesh = O.mesh_struct(s)
+    out = np.zeros(need.shape, bool)
+    for j, v in zip(*np.nonzero(need)):
+        o = np.ascontiguousarray(s.verts[v]); p = np.ascontiguousarray(s.cams["pos"][j])
+        out[j, v] = bool(L.orc_ray_occluded(None, C.byref(mesh), o.ctypes.data, p.ctypes.data, 1))
+    return out
+
+
+def need_from_pass_pattern(s, col_ptr, view_id):
+    """need[j, v] = some face on vertex v is in column pattern (col_ptr, view_id) for view j -- with the pattern of a pass WITHOUT the
+    visibility test (and no zero-quality pairs) that is "a face on v passed the culls in front of the rays" """
+    F, V, NV = s.n_faces, s.n_views, s.verts.shape[0]
+    face_of = np.repeat(np.arange(F), np.diff(col_ptr.astype(np.int64)))
+    need = np.zeros((V, NV), bool)
+    for c in range(3):
+        need[view_id.astype(np.int64), s.faces[face_of, c]] = True
+    return need
