@@ -124,6 +124,10 @@ typedef struct {
 } mvs_mrf_stats;
 
 typedef struct {
+    /* After a ranged pass (option "dc_range_pairs") pairs, the five cull counters, nnz_pre, nnz, footprints_lane_group and footprints_rewalked
+     * are sums over the ranges and EQUAL the unranged pass's values (each is a count per (face, view) pair); max_quality and percentile are
+     * the global ones; rays, ray_nodes, ray_tris, ray_packets, ray_packets_generic and ray_leaf_rounds are sums over the ranges and MAY
+     * EXCEED the unranged values: a vertex shared by faces of two ranges is traced once per range. */
     uint64_t pairs;
     /* the five cull counters and `rays` are filled only with mvs_set_option("stats", 1) */
     uint64_t cull_backface;     /* calculate_data_costs.cpp:183-185 */
@@ -133,7 +137,7 @@ typedef struct {
     uint64_t cull_zero_quality; /* :222 */
     uint64_t nnz_pre;           /* FaceProjectionInfos emitted (:227-228) */
     uint64_t nnz;
-    uint64_t rays;              /* (vertex, view) rays traced -- each distinct ray once */
+    uint64_t rays;              /* (vertex, view) rays traced -- each distinct ray once (once per range of a ranged pass) */
     uint64_t ray_nodes;         /* BVH node visits of the 64-ray packets: one 128-byte node = 4 child boxes each  (only with mvs_set_option("count_rays", 1)) */
     uint64_t ray_tris;          /* triangles fetched: 16 per leaf a packet's rays enter   (idem) */
     uint64_t ray_packets;         /* 64-ray packets traced (with "stats") */
@@ -277,6 +281,18 @@ mvs_status mvs_ctx_synchronize(mvs_ctx* ctx);
  *   the model:
  *     "max_labels"            default 0 = off = the reference's model; 1 .. 65535: label-space compression (CHANGES RESULTS)
  *   data costs:
+ *     "dc_range_pairs"        default 0 (environment MVS_DC_RANGE_PAIRS): B > 0: mvs_ctx_data_costs walks the context's faces in consecutive
+ *                             ranges of exactly max(1, floor(B / n_views)) faces (the last range holds the rest), keeps what each range
+ *                             leaves and takes maximum, histogram and percentile once over all of them: ONE table, bit for bit the
+ *                             unranged one, with phase 1's working set bounded by the range.  0 = one range, unless faces x views
+ *                             reaches 0xFFFFFFF0: then the fewest equal ranges that stay below it.  Like every option but
+ *                             "max_labels" it changes no table, label or energy.  The sharded path ignores it (one range per rank).
+ *                             Two 32-bit limits remain whatever the ranges (MVS_ERR_UNSUPPORTED): the qualities ALL ranges keep until the
+ *                             percentile is known must number fewer than 0xFFFFFFF0 (the histogram counts its values in one 32-bit word,
+ *                             as the reference's int does), and so must the entries of the table that comes out (after "max_labels").
+ *                             The kept arrays (6 bytes per kept quality, beside the table) are released when the call returns.
+ *                             The environment variable is read when a context is created and again by every one-shot call
+ *                             (mvs_data_costs, mvs_data_costs_stream), whose contexts outlive the call.
  *     "info_wave_area"        default 32 (environment MVS_INFO_WAVE_AREA): sampled footprints above this many pixels are summed by a
  *                             16-lane group under an exactness certificate; 0 = every footprint in the reference's serial order
  *     "info_words"            0/1, default 1: the smaller footprints of the gradient term are read four pixels per load and summed as
@@ -312,8 +328,16 @@ mvs_status mvs_scene_set_views_from(mvs_ctx* ctx, const mvs_view* views, uint32_
  * option "face_order" = 0); the whole mesh stays the occluder set.  Default: all faces.  (Building block of the sharded drivers.) */
 mvs_status mvs_scene_set_face_range(mvs_ctx* ctx, uint32_t begin, uint32_t end);
 
-/* tex::calculate_data_costs on the resident scene; result stays on the device. */
+/* tex::calculate_data_costs on the resident scene; result stays on the device.  The (face, view) pairs that pass the culls are ranked
+ * in 32 bits per range of faces: a scene of 2^32 pairs and more is walked in ranges (option "dc_range_pairs").  What has to fit 32 bits
+ * then is the number of qualities that survive the culls in all ranges together (the histogram's count word) and the table that comes out
+ * (its column pointers; see "max_labels") -- a scene beyond either is MVS_ERR_UNSUPPORTED. */
 mvs_status mvs_ctx_data_costs(mvs_ctx* ctx, const mvs_settings* settings, mvs_dc_stats* stats);
+/* What the last data-cost pass of the context did: the number of face ranges it walked and the faces of its FIRST range (every range
+ * but the last has that many).  An unranged pass, a phase-wise pass and mvs_postprocess_face_infos report (1, faces of the pass); so does
+ * a pass with nothing to evaluate -- an empty mesh reports (1, 0), a scene without views (1, faces).  Either pointer may be NULL.
+ * MVS_ERR_STATE before the first pass. */
+mvs_status mvs_ctx_dc_ranges(mvs_ctx* ctx, uint32_t* n_ranges, uint32_t* range_faces);
 /* The same, split at the global barrier of postprocess_face_infos
  * (calculate_data_costs.cpp:278-288): csrc/shard.hip all-reduces the maximum quality and the
  * 10000-bin histogram between the phases (a driver of its own reaches the two buffers through

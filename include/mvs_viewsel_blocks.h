@@ -28,7 +28,8 @@ mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts_device, uint16_t*
  * the CALLER's vertex numbering (the device matrices follow the library's curve order; the entry maps them back).  which = 2: that order
  * itself, n_verts 32-bit words, entry s = the caller's id of the vertex at curve position s -- 64 consecutive positions share a device word,
  * i.e. a ray packet.  *n_bytes = size of the matrix / the order; out_host == null: the size only.  MVS_ERR_STATE before a data-cost pass
- * with the geometric visibility test, or when the last pass covered a face range and not the whole mesh. */
+ * with the geometric visibility test, when the last pass covered a face range and not the whole mesh, or (which = 0, 1) when it walked
+ * the mesh in more than one range (option "dc_range_pairs"): the matrices then hold the last range's rays only. */
 mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----

@@ -18,6 +18,7 @@ namespace mvs {
 void dc_phase1(mvs_ctx* ctx, const mvs_settings* st);
 void dc_phase2(mvs_ctx* ctx);
 void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats);
+void dc_run(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats);
 void undistort_image(mvs_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, double flen, double d0, double d1);
 void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax);
 void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t* h_ptr, const uint16_t* h_view_rev, const float* h_q_rev, const float* h_col_rev, const mvs_settings* st);
@@ -326,6 +327,9 @@ void mvs_default_settings(mvs_settings* s) {  /* settings.h:85-90 */
     s->data_term = MVS_DATA_TERM_GMI; s->outlier_removal = MVS_OUTLIER_NONE; s->geometric_visibility_test = 1;
 }
 
+// MVS_DC_RANGE_PAIRS (0 when unset): read where a context is made and again by every one-shot call, whose contexts outlive the call
+static uint64_t env_dc_range_pairs() { const char* e = getenv("MVS_DC_RANGE_PAIRS"); return e ? (uint64_t)std::max(0ll, atoll(e)) : 0ull; }
+
 mvs_status mvs_ctx_create(int device, mvs_ctx** out) {
     if (!out) return fail(MVS_ERR_INVALID, "out is null");
     *out = nullptr;
@@ -342,6 +346,8 @@ mvs_status mvs_ctx_create(int device, mvs_ctx** out) {
     // MVS_INFO_WAVE_AREA overrides the default footprint area above which the lane-group sampler takes over (0: every
     // footprint in the reference's serial fp64 order, i.e. bit-exact qualities); mvs_set_option("info_wave_area") still wins
     if (const char* e = getenv("MVS_INFO_WAVE_AREA")) c->info_wave_area = std::max(0, atoi(e));
+    // MVS_DC_RANGE_PAIRS: the option "dc_range_pairs" for the one-shot entry points and the link-time drop-in (mvs_set_option still wins)
+    c->dc_range_pairs = env_dc_range_pairs();
     if (const char* e = getenv("MVS_BVH_UPPER_MIN_FACES")) c->bvh_upper_min_faces = (uint32_t)std::max(0ll, atoll(e));   // (test runs: 0 puts every mesh of the suite through the upper levels of the face order)
     c->counters.ensure(64);
     *out = c;
@@ -397,6 +403,7 @@ mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value) {
     else if (n == "info_words") ctx->info_words = value != 0;
     else if (n == "info_cert_shift") ctx->info_cert_shift = (int)std::max<int64_t>(0, std::min<int64_t>(value, 40));
     else if (n == "max_labels") { if (value < 0 || value > 65535) return fail(MVS_ERR_INVALID, "max_labels: 0 (off) .. 65535"); ctx->max_labels = (int)value; }
+    else if (n == "dc_range_pairs") { if (value < 0) return fail(MVS_ERR_INVALID, "dc_range_pairs: 0 (one range) or the (face, view) pairs of a range"); ctx->dc_range_pairs = (uint64_t)value; }
     else if (n == "profile") ctx->profile = value != 0;
     else if (n == "prep_fused") ctx->prep_fused = value != 0;
     else if (n == "ray_xcd") ctx->ray_xcd = (int)value;
@@ -583,10 +590,16 @@ mvs_status mvs_ctx_data_costs(mvs_ctx* ctx, const mvs_settings* settings, mvs_dc
     MVS_API_BEGIN
     MVS_HIP(hipSetDevice(ctx->device));
     RoctxRange range("Calculating data costs");   /* texrecon.cpp:118 */
-    dc_phase1(ctx, settings);
-    dc_phase2(ctx);
-    dc_phase3(ctx, stats);
+    dc_run(ctx, settings, stats);   // the three phases, or the ranged walk (option "dc_range_pairs")
     MVS_API_END
+}
+
+mvs_status mvs_ctx_dc_ranges(mvs_ctx* ctx, uint32_t* n_ranges, uint32_t* range_faces) {
+    if (!ctx) return fail(MVS_ERR_INVALID, "ctx is null");
+    if (ctx->dc_phase < 1) return fail(MVS_ERR_STATE, "no data-cost pass on this context");
+    if (n_ranges) *n_ranges = ctx->dc_n_ranges;
+    if (range_faces) *range_faces = ctx->dc_range_faces;
+    return MVS_OK;
 }
 
 mvs_status mvs_ctx_prune_labels(mvs_ctx* ctx, uint32_t max_labels) {
@@ -799,7 +812,9 @@ mvs_status mvs_data_costs(const mvs_mesh* mesh, const mvs_view* views, uint32_t 
     t[2] = now_ms();
     if (st == MVS_OK) st = mvs_scene_set_views(ctx, views, n_views, 0);
     t[3] = now_ms();
+    ctx->dc_range_pairs = env_dc_range_pairs();   // (a parked context was made under whatever the variable said then)
     if (st == MVS_OK) st = mvs_ctx_data_costs(ctx, settings, stats);
+    const uint32_t n_ranges = st == MVS_OK ? ctx->dc_n_ranges : 0u;
     if (st == MVS_OK) (void)hipStreamSynchronize(ctx->stream);
     t[4] = now_ms();
     if (st == MVS_OK) st = mvs_ctx_costs_download(ctx, out, nullptr);
@@ -813,7 +828,7 @@ mvs_status mvs_data_costs(const mvs_mesh* mesh, const mvs_view* views, uint32_t 
     if (!kept) { if (stash_enabled() && st == MVS_OK) park_spare(ctx); else mvs_ctx_destroy(ctx); }
     char buf[512];
     snprintf(buf, sizeof(buf), "{\"call\": \"mvs_data_costs\", \"ctx_ms\": %.3f, \"mesh_h2d_ms\": %.3f, \"images_h2d_ms\": %.3f, \"compute_ms\": %.3f, \"download_ms\": %.3f, "
-             "\"fingerprint_ms\": %.3f, \"table_kept_on_device\": %s}", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], kept ? "true" : "false");
+             "\"fingerprint_ms\": %.3f, \"dc_ranges\": %u, \"table_kept_on_device\": %s}", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], n_ranges, kept ? "true" : "false");
     g_call_profile = buf;
     return st;
 }
@@ -855,7 +870,9 @@ static mvs_status data_costs_stream_impl(const mvs_mesh* mesh, const mvs_view* v
     t[2] = now_ms();
     if (st == MVS_OK) st = set_views_impl(ctx, views, n_views, 0, images);
     t[3] = now_ms();
+    ctx->dc_range_pairs = env_dc_range_pairs();   // (a parked context was made under whatever the variable said then)
     if (st == MVS_OK) st = mvs_ctx_data_costs(ctx, settings, stats);
+    const uint32_t n_ranges = st == MVS_OK ? ctx->dc_n_ranges : 0u;
     uint64_t fp = 0; double first_chunk_ms = 0.0;
     if (st == MVS_OK) {
         try {
@@ -913,7 +930,7 @@ static mvs_status data_costs_stream_impl(const mvs_mesh* mesh, const mvs_view* v
     if (!kept) { if (stash_enabled() && st == MVS_OK) park_spare(ctx); else mvs_ctx_destroy(ctx); }
     char buf[640];
     snprintf(buf, sizeof(buf), "{\"call\": \"mvs_data_costs_stream\", \"ctx_ms\": %.3f, \"mesh_h2d_ms\": %.3f, \"images_h2d_ms\": %.3f, \"compute_ms\": %.3f, \"first_chunk_ms\": %.3f, "
-             "\"chunks_and_callbacks_ms\": %.3f, \"fingerprint\": \"device\", \"table_kept_on_device\": %s}", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], first_chunk_ms, t[5] - t[4], kept ? "true" : "false");
+             "\"chunks_and_callbacks_ms\": %.3f, \"fingerprint\": \"device\", \"dc_ranges\": %u, \"table_kept_on_device\": %s}", t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], first_chunk_ms, t[5] - t[4], n_ranges, kept ? "true" : "false");
     g_call_profile = buf;
     return st;
 }

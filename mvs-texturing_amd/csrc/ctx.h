@@ -228,6 +228,11 @@ struct mvs_ctx {
     bool csr_q_valid = false;   // csr_q holds the qualities of the active CSR (set by the data-cost stage)
     bool have_costs = false;
     mvs_settings dc_settings{}; mvs_dc_stats dc_stats{}; int dc_phase = 0;
+    // ranged data-cost pass (k_dc.hip dc_ranged; planner and accounting in dc_ranges.h): option "dc_range_pairs", what the last pass did
+    // (mvs_ctx_dc_ranges), "the order, the BVH and the prepared views of this call are resident" for the ranges after the first, and the
+    // (col_ptr, view_id, quality) every range leaves behind until the percentile is known -- back to back, 64-bit bases on the host
+    uint64_t dc_range_pairs = 0; uint32_t dc_n_ranges = 1, dc_range_faces = 0; bool dc_walk_resident = false;
+    mvs::DBuf<uint32_t> k_ptr, k_max; mvs::DBuf<uint16_t> k_view; mvs::DBuf<float> k_q;
 
     // ---- row f1: mesh preparation + adjacency graph (k_mesh.hip) ----
     mvs::DBuf<unsigned long long> g_keys, g_keys2; mvs::DBuf<uint32_t> g_vals, g_vals2, g_pos, g_cnt, g_adj_ptr, g_adj, g_faces; mvs::DBuf<float> g_normals;

@@ -14,6 +14,7 @@
 //   outlier_kernel    photometric_outlier_detection (:35-129) per face, fp64 in registers;
 //   max / histogram / percentile / cost  = postprocess_face_infos (:278-302).
 #include "ctx.h"
+#include "dc_ranges.h"
 
 namespace mvs {
 
@@ -905,6 +906,7 @@ static void upload_views_and_prepare(mvs_ctx* ctx, bool need_gmi) {
 // phase 1: everything up to the per-face sorted infos + local max quality
 static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st);
 void dc_phase1(mvs_ctx* ctx, const mvs_settings* st) {
+    ctx->dc_walk_resident = false; ctx->dc_n_ranges = 1; ctx->dc_range_faces = ctx->face_end - ctx->face_begin;
     // (a second pass only when the face order had to be rebuilt -- scene_order_commit: a mesh with thousands of equal centroid coordinates)
     if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
 }
@@ -941,6 +943,8 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
     // beside BOTH.  The fork is recorded HERE, in front of the order's launches (recorded behind them -- as it was until the kernel timeline
     // of a step showed the main stream idle for 0.7 ms in front of the culls -- prep overlapped the BVH build only); prep's launches are
     // still QUEUED after the order's and the BVH's, because prep's flood fill makes the host wait (for its own stream only).
+    // (the ranges of a ranged pass after its first find all of that resident: dc_ranged)
+    if (!ctx->dc_walk_resident) {
     if (!ctx->aux_stream) { MVS_HIP(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming)); }
     MVS_HIP(hipEventRecord(ctx->ev_fork, s));                          // (the counters' memset above is what prep has to see)
     MVS_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
@@ -959,6 +963,7 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
         MVS_HIP(hipEventRecord(ctx->ev_join, ctx->aux_stream));
         ctx->stream = s;
         MVS_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
+    }
     }
 
     const size_t pw = (size_t)V * fwords;
@@ -1002,9 +1007,10 @@ static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
     ctx->max_q.ensure(4);
     uint32_t* d_total = (uint32_t*)(ctx->max_q.p + 2);
     // ranks, CSR pointers and nnz are 32 bits wide (the reference uses size_t containers): a scene whose passing pairs could
-    // reach 2^32 gets an exact 64-bit count first and is refused instead of wrapping the scan (shard the faces: face ranges)
+    // reach 2^32 gets an exact 64-bit count first and is refused instead of wrapping the scan.  (The planner of the ranged pass, dc_ranges.h,
+    // never produces such a range by itself: only a caller's own "dc_range_pairs" can.)
     if ((uint64_t)nf * V >= 0xFFFFFFF0ull && sum_u32(ctx, ctx->pass_base.p, pw) >= 0xFFFFFFF0ull)
-        throw StatusError(MVS_ERR_UNSUPPORTED, "more than 2^32 (face, view) pairs pass the culls in one context: evaluate the faces in ranges (mvs_scene_set_face_range)");
+        throw StatusError(MVS_ERR_UNSUPPORTED, "more than 2^32 (face, view) pairs pass the culls in one range of faces: evaluate the faces in smaller ranges (option dc_range_pairs)");
     exclusive_scan_u32(ctx, ctx->pass_base.p, ctx->pass_base.p, pw, d_total);
     pr_rank.end();
     const uint32_t n_pass = read_word(ctx, d_total);
@@ -1225,6 +1231,7 @@ void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t*
     const uint32_t n = h_ptr[nf];
     ctx->dc_settings = *st; ctx->have_costs = false;
     ctx->t_perm = nullptr; ctx->t_pos = nullptr; ctx->u_valid = false;   // the caller's infos, the caller's order
+    ctx->dc_n_ranges = 1; ctx->dc_range_faces = nf;
     memset(&ctx->dc_stats, 0, sizeof(ctx->dc_stats));
     ctx->dc_stats.nnz_pre = n;
     ctx->counters.ensure(64);
@@ -1359,6 +1366,159 @@ void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax) {
     }
     ctx->csr_nnz = nnz2; ctx->dc_stats.nnz = nnz2; ctx->u_valid = false;
     ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p;
+}
+
+// ---- ranged evaluation inside one context (DESIGN.md section 4 "Ranged data costs"; planner and accounting: dc_ranges.h) ----
+// The context's faces are walked in consecutive ranges.  Phase 1 runs per range as it is; what a range leaves -- (col_ptr, view_id,
+// quality) -- is kept.  The two reductions of postprocess_face_infos (:278-288) then see all ranges: one maximum, one histogram against
+// it, one percentile.  Costs are written range by range straight into ONE table with rebased column pointers.
+__global__ void max_merge_kernel(uint32_t* __restrict__ global_bits, const uint32_t* __restrict__ local_bits) {   // qualities are > 0: uint order = float order
+    if (*local_bits > *global_bits) *global_bits = *local_bits;
+}
+__global__ void rebase_ptr_kernel(const uint32_t* __restrict__ src, uint32_t n, uint32_t base, uint32_t* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i] + base;
+}
+// cost_kernel fused with the append of a range's columns (no pruning: the range's entries are one contiguous run of the final table)
+__global__ void cost_append_kernel(const uint16_t* __restrict__ view, const float* __restrict__ q, size_t n, const float* __restrict__ pctl,
+                                   uint16_t* __restrict__ view_out, float* __restrict__ q_out, float* __restrict__ cost_out) {
+    const float p = *pctl;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float x = q[i];
+        view_out[i] = view[i]; q_out[i] = x; cost_out[i] = 1.0f - smin(1.0f, x / p);
+    }
+}
+
+// grows a kept array WITHOUT losing its first `used` elements (DBuf::ensure drops the contents)
+template <class T>
+static void keep_reserve(mvs_ctx* ctx, DBuf<T>& b, size_t used, size_t need) {
+    if (need <= b.cap) return;
+    DBuf<T> nb;
+    nb.ensure(std::max(need, b.cap + b.cap / 2));
+    if (used) MVS_HIP(hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    MVS_HIP(hipStreamSynchronize(ctx->stream));
+    std::swap(b.p, nb.p); std::swap(b.cap, nb.cap);
+}
+
+static void dc_ranged(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats, const DcPlan& plan) {
+    hipStream_t s = ctx->stream;
+    const uint32_t FB = ctx->face_begin, FE = ctx->face_end, NF = FE - FB, V = ctx->n_views;
+    struct Restore { mvs_ctx* c; uint32_t b, e; bool done = false;
+                     ~Restore() { c->face_begin = b; c->face_end = e; c->dc_walk_resident = false;
+                                  if (!done) { c->dc_phase = 0; c->have_costs = false; }            // one range's fragment is no table
+                                  c->k_ptr.release(); c->k_view.release(); c->k_q.release(); } } restore{ctx, FB, FE};   // the kept arrays live for the call only
+    ctx->dc_n_ranges = plan.n; ctx->dc_range_faces = plan.first_faces();
+    ctx->dc_phase = 0; ctx->have_costs = false;   // (a walk that throws half way leaves no phase to continue from: see Restore)
+    DcKept kept;
+    mvs_dc_stats S; memset(&S, 0, sizeof(S));
+    unsigned long long hsum[16] = {0};
+    uint64_t deferred = 0;
+    ctx->k_max.ensure(4);
+    MVS_HIP(hipMemsetAsync(ctx->k_max.p, 0, 4 * sizeof(uint32_t), s));
+    keep_reserve(ctx, ctx->k_ptr, 0, (size_t)NF + plan.n + 1);
+    for (uint32_t r = 0; r < plan.n; ++r) {
+        const DcRange g = plan.range(r);
+        const uint32_t nf = g.end - g.begin;
+        ctx->face_begin = g.begin; ctx->face_end = g.end; ctx->dc_walk_resident = r > 0;
+        // the order can only be rebuilt where it is built: in the first range, before anything is kept -- the walk starts again, once
+        if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
+        const size_t nnz = (size_t)ctx->csr_nnz, at = (size_t)kept.total();
+        if (r == 0) { const size_t guess = nnz + nnz / 8; keep_reserve(ctx, ctx->k_view, 0, guess * plan.n + 1); keep_reserve(ctx, ctx->k_q, 0, guess * plan.n + 1); }
+        keep_reserve(ctx, ctx->k_view, at, at + nnz + 1); keep_reserve(ctx, ctx->k_q, at, at + nnz + 1);
+        MVS_HIP(hipMemcpyAsync(ctx->k_ptr.p + kept.ptr_base.back(), ctx->csr_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        if (nnz) {
+            MVS_HIP(hipMemcpyAsync(ctx->k_view.p + at, ctx->csr_view.p, nnz * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+            MVS_HIP(hipMemcpyAsync(ctx->k_q.p + at, ctx->csr_q.p, nnz * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        hipLaunchKernelGGL(max_merge_kernel, dim3(1), dim3(1), 0, s, ctx->k_max.p, (const uint32_t*)ctx->max_q.p); MVS_LAUNCH_CHECK();
+        kept.push(nf, (uint32_t)nnz);
+        // every counter is a count per (face, view) pair or per ray of this range: summed on the host (the next range clears them)
+        unsigned long long hc[14];
+        read_words(ctx, ctx->counters.p, hc, (uint32_t)(sizeof(hc) / 4));
+        for (int k = 0; k < 14; ++k) hsum[k] += hc[k];
+        S.pairs += ctx->dc_stats.pairs; S.nnz_pre += ctx->dc_stats.nnz_pre; deferred += ctx->dc_stats_deferred;
+    }
+    ctx->face_begin = FB; ctx->face_end = FE; ctx->dc_walk_resident = false;
+    if (ctx->mesh_ordered && NF && V) {   // the table of the context's faces, as an unranged pass names it (nothing to evaluate: no order was built)
+        if (FB == 0 && NF == ctx->n_faces) { ctx->t_perm = ctx->f_perm.p; ctx->t_pos = ctx->f_pos.p; }
+        else { ctx->t_perm = ctx->f_perm.p + FB; ctx->t_pos = nullptr; }
+    }
+    // the histogram's "number of values" is one 32-bit word, here as in the reference (an int, histogram.cpp:21)
+    if (kept.total() >= DC_LIMIT_32)
+        throw StatusError(MVS_ERR_UNSUPPORTED, "the faces of this context keep " + std::to_string(kept.total()) + " qualities in all, the histogram of postprocess_face_infos counts its values in "
+                          "32 bits: give the context fewer faces (mvs_scene_set_face_range; the sharded path mvs_shard_* takes one part of the mesh per context)");
+    Prof pr_post(ctx, "dc_post");
+    ctx->max_q.ensure(4); ctx->hist.ensure(HIST_BINS + 8); ctx->pctl.ensure(4);
+    MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), s));
+    MVS_HIP(hipMemcpyAsync(ctx->max_q.p, ctx->k_max.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    MVS_HIP(hipMemsetAsync(ctx->hist.p, 0, (HIST_BINS + 8) * sizeof(uint32_t), s));
+    for (size_t r = 0; r < kept.ranges(); ++r) if (kept.entries(r)) {
+        hipLaunchKernelGGL(hist_kernel, dim3(512), dim3(1024), 0, s, ctx->k_q.p + kept.base[r], (size_t)kept.entries(r), ctx->max_q.p, ctx->hist.p);
+        MVS_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(set_count_kernel, dim3(1), dim3(1), 0, s, ctx->hist.p, (uint32_t)kept.total()); MVS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(percentile_kernel, dim3(1), dim3(1024), 0, s, ctx->hist.p, ctx->max_q.p, 0.995f, ctx->pctl.p, ctx->counters.p + 14);
+    MVS_LAUNCH_CHECK();
+    pr_post.end();
+    // the exact 64-bit size of the final table first: only IT has to fit 32-bit column pointers
+    const uint32_t kmax = ctx->max_labels > 0 ? (uint32_t)ctx->max_labels : 0u;
+    uint64_t total = kept.total();
+    Prof pr_app(ctx, "dc_append");
+    ctx->csr_ptr.ensure((size_t)NF + 2);
+    if (kmax) {
+        ctx->face_cnt.ensure((size_t)NF + 2);
+        for (uint32_t r = 0; r < plan.n; ++r) {   // (the sentinel a range writes behind its last face is the next range's first count)
+            const DcRange g = plan.range(r); const uint32_t nf = g.end - g.begin;
+            hipLaunchKernelGGL(prune_count_kernel, dim3((nf + 256) / 256), dim3(256), 0, s, (const uint32_t*)(ctx->k_ptr.p + kept.ptr_base[r]), nf, kmax, ctx->face_cnt.p + (g.begin - FB));
+            MVS_LAUNCH_CHECK();
+        }
+        total = sum_u32(ctx, ctx->face_cnt.p, NF);
+    }
+    if (!dc_final_fits(total))
+        throw StatusError(MVS_ERR_UNSUPPORTED, "the data-cost table of this context has " + std::to_string(total) + " entries, its column pointers are 32 bits wide: set the option max_labels");
+    ctx->csr_view.ensure((size_t)total + 1); ctx->csr_q.ensure((size_t)total + 1); ctx->csr_cost.ensure((size_t)total + 8);
+    if (kmax) {
+        exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)NF + 1, nullptr);
+        size_t longest = 0; for (size_t r = 0; r < kept.ranges(); ++r) longest = std::max<size_t>(longest, (size_t)kept.entries(r));
+        ctx->pcol.ensure(longest + 8);
+    }
+    for (uint32_t r = 0; r < plan.n; ++r) {
+        const DcRange g = plan.range(r); const uint32_t nf = g.end - g.begin, off = g.begin - FB;
+        const size_t n = (size_t)kept.entries(r);
+        const uint32_t* kp = ctx->k_ptr.p + kept.ptr_base[r]; const uint16_t* kv = ctx->k_view.p + kept.base[r]; const float* kq = ctx->k_q.p + kept.base[r];
+        if (kmax) {   // pruning is per column: pruning a range is pruning the whole (prune_write_kernel copies the columns it does not cut)
+            if (!n || !nf) continue;
+            hipLaunchKernelGGL(cost_kernel, dim3(2048), dim3(256), 0, s, kq, n, (const float*)ctx->pctl.p, ctx->pcol.p); MVS_LAUNCH_CHECK();
+            hipLaunchKernelGGL(prune_write_kernel, dim3((unsigned)(((size_t)nf * 64 + 255) / 256)), dim3(256), 0, s, kp, kv, (const float*)ctx->pcol.p, kq, nf, kmax,
+                               (const uint32_t*)(ctx->csr_ptr.p + off), ctx->csr_view.p, ctx->csr_cost.p, ctx->csr_q.p);
+            MVS_LAUNCH_CHECK();
+        } else {
+            const size_t base = (size_t)kept.base[r];   // < DC_LIMIT_32: dc_final_fits
+            hipLaunchKernelGGL(rebase_ptr_kernel, dim3((nf + 256) / 256), dim3(256), 0, s, kp, nf + 1, (uint32_t)base, ctx->csr_ptr.p + off); MVS_LAUNCH_CHECK();
+            if (n) { hipLaunchKernelGGL(cost_append_kernel, dim3(2048), dim3(256), 0, s, kv, kq, n, (const float*)ctx->pctl.p, ctx->csr_view.p + base, ctx->csr_q.p + base, ctx->csr_cost.p + base); MVS_LAUNCH_CHECK(); }
+        }
+    }
+    pr_app.end();
+    ctx->csr_nnz = total; ctx->csr_faces = NF; ctx->csr_views = V;
+    unsigned long long rep[2];
+    read_words(ctx, ctx->counters.p + 14, rep, 4);
+    float mq, pc; { const uint32_t a = (uint32_t)rep[0], b = (uint32_t)rep[1]; memcpy(&mq, &a, 4); memcpy(&pc, &b, 4); }
+    S.cull_backface = hsum[C_BACK]; S.cull_angle = hsum[C_ANGLE]; S.cull_outside = hsum[C_OUTSIDE]; S.cull_occluded = hsum[C_OCCL];
+    S.cull_zero_quality = hsum[C_ZEROQ]; S.rays = hsum[C_RAYS]; S.ray_nodes = hsum[C_RNODES]; S.ray_tris = hsum[C_RTRIS] * 16ull; S.ray_leaf_rounds = hsum[13];
+    S.ray_packets = hsum[10]; S.ray_packets_generic = hsum[11]; S.footprints_lane_group = deferred; S.footprints_rewalked = hsum[C_REWALK];
+    S.nnz = total; S.max_quality = mq; S.percentile = pc;
+    ctx->dc_stats = S;
+    ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p; ctx->csr_q_valid = true; ctx->u_valid = false;
+    ctx->have_costs = true; ctx->dc_phase = 3; restore.done = true;
+    if (stats) *stats = S;
+}
+
+// mvs_ctx_data_costs: one range through the three phases as they are, or the ranged walk (option "dc_range_pairs"; by itself only where
+// faces x views would pass the 32-bit ranks of one range)
+void dc_run(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats) {
+    const DcPlan plan = dc_plan(ctx->face_begin, ctx->face_end, ctx->n_views, ctx->dc_range_pairs);
+    if (ctx->dc_range_pairs == 0 && plan.n == 1) { dc_phase1(ctx, st); dc_phase2(ctx); dc_phase3(ctx, stats); return; }
+    dc_ranged(ctx, st, stats, plan);
 }
 
 }  // namespace mvs

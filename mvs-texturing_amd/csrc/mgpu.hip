@@ -133,6 +133,9 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
     if (ctx->dc_phase < 1 || !ctx->dc_settings.geometric_visibility_test || whole == 0 || ctx->n_verts == 0 || ctx->dc_stats.pairs != whole ||
         ctx->face_begin != 0 || ctx->face_end != ctx->n_faces || !ctx->need_bits.p || !ctx->occl_bits.p || !ctx->vperm.p)
         return api_fail(MVS_ERR_STATE, "ray bits: needs a data-cost pass with the visibility test over the whole mesh");
+    // after a ranged pass (k_dc.hip dc_ranged) the matrices hold the LAST range's rays only
+    if (which < 2 && ctx->dc_n_ranges > 1)
+        return api_fail(MVS_ERR_STATE, "ray bits: the last data-cost pass evaluated the faces in " + std::to_string(ctx->dc_n_ranges) + " ranges (option dc_range_pairs); the matrices hold the last range only");
     MVS_API_BEGIN
     const uint32_t NV = ctx->n_verts, V = ctx->n_views, vwords = (NV + 63) / 64;
     const uint64_t words = (uint64_t)V * vwords, n = which == 2 ? (uint64_t)NV * sizeof(uint32_t) : words * sizeof(unsigned long long);

@@ -218,7 +218,7 @@ def load_library():
         "mvs_ctx_get_profile": [vp, C.c_char_p, C.c_size_t],
         "mvs_scene_set_mesh": [vp, C.POINTER(CMesh), i32], "mvs_scene_set_views": [vp, C.POINTER(CView), u32, i32],
         "mvs_scene_set_face_range": [vp, u32, u32],
-        "mvs_ctx_data_costs": [vp, C.POINTER(Settings), C.POINTER(DcStats)],
+        "mvs_ctx_data_costs": [vp, C.POINTER(Settings), C.POINTER(DcStats)], "mvs_ctx_dc_ranges": [vp, C.POINTER(u32), C.POINTER(u32)],
         "mvs_ctx_dc_phase1": [vp, C.POINTER(Settings)], "mvs_ctx_dc_get_max": [vp, vp], "mvs_ctx_dc_set_max": [vp, vp],
         "mvs_ctx_dc_phase2": [vp], "mvs_ctx_dc_get_histogram": [vp, vp], "mvs_ctx_dc_set_histogram": [vp, vp],
         "mvs_ctx_dc_phase3": [vp, C.POINTER(DcStats)],
@@ -505,6 +505,12 @@ class Context:
         ds = DcStats()
         _check(self.L, self.L.mvs_ctx_data_costs(self.h, C.byref(st), C.byref(ds)))
         return _stats_dict(ds)
+
+    def dc_ranges(self):
+        """(n_ranges, faces of the first range) of the last data-cost pass (mvs_ctx_dc_ranges; option "dc_range_pairs")"""
+        n, per = C.c_uint32(0), C.c_uint32(0)
+        _check(self.L, self.L.mvs_ctx_dc_ranges(self.h, C.byref(n), C.byref(per)))
+        return n.value, per.value
 
     def costs_download(self):
         out = CCsr(); q = C.c_void_p()
