@@ -51,6 +51,8 @@ mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32
 /* NOTE: once the device-side stop rule has fired (mvs_mrf_progress.stopped, set by mvs_ctx_mrf_step) every later sweep / sweep phase
  * ends at its first instruction -- it changes no message, no decode and no energy partial: the best labeling is frozen.  A driver that
  * wants more sweeps than the rule allows raises max_sweeps / min_sweeps in the params of mvs_ctx_mrf_setup instead. */
+/* The phases of a sweep run in ascending order, every sweep from phase 0.  A phase may be cut into several node ranges: consecutive calls
+ * of the same phase belong to one sweep (one damping factor); a call whose phase number is smaller than the previous call's starts the next. */
 mvs_status mvs_ctx_mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t node_begin, uint32_t node_end);
 /* Boundary-first phases (what csrc/shard.hip does per rank): marks_device[i] != 0 puts node i into the BOUNDARY zone of its colour class
  * (own nodes with an edge into another rank's part); a phase then runs as part 1 (boundary zone) -> hand-over -> part 2 (interior zone).

@@ -194,7 +194,7 @@ bool stash_enabled() { const char* e = getenv("MVS_KEEP_TABLE"); return !(e && e
 template <class Sweep>
 static bool prepare_sweep_graph(mvs_ctx* ctx, Sweep&& one_sweep, int n_sweeps) {
     if (!ctx->cap_stream && hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->mrf_graph = 0; return false; }
-    const uint32_t steps0 = ctx->steps_issued, sweep0 = ctx->m_sweep_no;
+    const uint32_t steps0 = ctx->steps_issued, sweep0 = ctx->m_sweep_no, phase0 = ctx->m_last_phase;
     hipStream_t user = ctx->stream;
     hipGraph_t graph = nullptr;
     bool ok = hipStreamBeginCapture(ctx->cap_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -204,7 +204,7 @@ static bool prepare_sweep_graph(mvs_ctx* ctx, Sweep&& one_sweep, int n_sweeps) {
         ctx->stream = user;
         if (hipStreamEndCapture(ctx->cap_stream, &graph) != hipSuccess || !graph) ok = false;
     }
-    ctx->steps_issued = steps0; ctx->m_sweep_no = sweep0;
+    ctx->steps_issued = steps0; ctx->m_sweep_no = sweep0; ctx->m_last_phase = phase0;
     if (ok && ctx->sweep_exec) {
         hipGraphNode_t bad = nullptr; hipGraphExecUpdateResult res = hipGraphExecUpdateError;
         if (hipGraphExecUpdate(ctx->sweep_exec, graph, &bad, &res) == hipSuccess && res == hipGraphExecUpdateSuccess) ++ctx->graph_updates;

@@ -282,6 +282,7 @@ struct mvs_ctx {
     int mrf_force_lists = 0;     // test hook: the set-up compares and searches the neighbours' view lists at any number of views
     uint32_t m_range_nb = 0, m_range_ne = 0; std::vector<uint32_t> m_range_q;   // cached own share of every sub-class
     uint32_t m_sweep_no = 0;   // sweeps started since mrf_setup (1-based inside a sweep): sweeps 1, 5, 9, ... are damped
+    uint32_t m_last_phase = 0xFFFFFFFFu;   // colour phase of the last mrf_sweep_phase since mrf_setup (none yet: 0xFFFFFFFF): a smaller phase number starts a sweep
     mvs_mrf_params m_params{};
     // device-side stop rule (k_mrf.hip mrf_step): solver state in HBM, per-step reports through a pinned ring
     static constexpr uint32_t RING = 16;

@@ -1548,7 +1548,7 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
     // ---- colour-phased schedule: colouring (Jones-Plassmann rounds), nodes in (colour, id) order ----
     ctx->m_colour.ensure((size_t)F + 2); ctx->m_perm.ensure((size_t)F + 2); ctx->m_tmp_a.ensure((size_t)MAX_LAYOUT_COLOURS * ((size_t)F + 1) + 72); ctx->m_tmp_b.ensure((size_t)MAX_LAYOUT_COLOURS * ((size_t)F + 1) + 2); ctx->m_tmp_c.ensure((size_t)F + 2);
     ctx->m_colours = 0; ctx->m_sub_begin.assign(N_KEY + 1, 0); ctx->m_n_fast = 0; ctx->m_range_q.clear(); ctx->m_range_nb = ctx->m_range_ne = 0;
-    ctx->m_sweep_no = 0;
+    ctx->m_sweep_no = 0; ctx->m_last_phase = 0xFFFFFFFFu;
     if (F) {
         uint32_t* pending = ctx->m_moved.p + 1;   // [0] a node is still waiting, [1] a node saw all 64 colours around it
         hipLaunchKernelGGL(mrf_colour_init_kernel, dim3(nb), dim3(256), 0, s, ctx->m_colour.p, ctx->m_tmp_a.p /* iota */, F); MVS_LAUNCH_CHECK();
@@ -1894,7 +1894,11 @@ static void sub_range(mvs_ctx* ctx, uint32_t sub, uint32_t zone, uint32_t nb0, u
 //       MRF_PART_BOUNDARY / MRF_PART_INTERIOR = one zone -- a sharded caller runs BOUNDARY, hands over, then INTERIOR.
 // A solve keeps to one of the two modes (the slots of a launch differ between them).
 void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part) {
-    if (phase == 0 && part != MRF_PART_INTERIOR) ++ctx->m_sweep_no;      // sweeps are counted by their first phase (every caller runs the phases in order, a split phase boundary first)
+    // A sweep starts when the phase number falls back (or with the first call after the set-up).  Callers run the phases in ascending
+    // order, a split phase boundary first; consecutive calls of one phase -- a phase cut into several node ranges -- belong to one sweep.
+    // A graph of one colour has no edge, hence no message a damping factor could reach: there every call counts.
+    if (part != MRF_PART_INTERIOR && (phase < ctx->m_last_phase || ctx->m_last_phase == 0xFFFFFFFFu || ctx->m_colours <= 1u)) ++ctx->m_sweep_no;
+    ctx->m_last_phase = phase;
     if (phase >= ctx->m_colours || ne0 <= nb0) return;
     constexpr unsigned EPART_BOUNDARY = 256;
     struct Launch { uint32_t g, qb, qe; } L[10]; int n = 0;

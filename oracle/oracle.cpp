@@ -909,6 +909,8 @@ namespace {
 const uint16_t MAP_NONE = 0xFFFF;
 uint64_t* g_trace = nullptr; int g_trace_len = 0;
 // optional per-sweep energy trace (experiments)
+uint32_t* g_dtrace_lab = nullptr; uint32_t* g_dtrace_best = nullptr; int g_dtrace_len = 0;
+// optional per-sweep decode trace (tests): labels of the decode and of the best labeling after every sweep
 
 inline uint64_t fix32(float d) { return (uint64_t)((double)d * 4294967296.0); }
 
@@ -1223,6 +1225,7 @@ uint32_t orc_msg_code(float raw, float rho, float alpha, uint32_t old_code) {
     return msg_code(raw * ((1.0f - alpha) * q.scale), alpha, old_code);
 }
 void orc_mrf_set_trace(uint64_t* buf, int len) { g_trace = buf; g_trace_len = len; }
+void orc_mrf_set_decode_trace(uint32_t* lab, uint32_t* best, int len) { g_dtrace_lab = lab; g_dtrace_best = best; g_dtrace_len = (lab && best) ? len : 0; }
 
 void orc_mrf_default_params(orc_mrf_params* p) {
     p->max_sweeps = 200; p->min_sweeps = 20; p->window = 5; p->min_improvement = 0.005f;
@@ -1269,6 +1272,14 @@ int orc_view_selection(const orc_csr* costs, const uint32_t* adj_ptr, const uint
         if (e < best_e) { best_e = e; best_cuts = cuts; best_sel = sel; }
         hist.push_back(best_e);
         if (g_trace && (int)s <= g_trace_len) g_trace[s - 1] = e;
+        if ((int)s <= g_dtrace_len) {   // rows s - 1 of the two [len x F] tables: this sweep's decode, the best labeling after the bookkeeping above
+            uint32_t* tl = g_dtrace_lab + (size_t)(s - 1) * g.F; uint32_t* tb = g_dtrace_best + (size_t)(s - 1) * g.F;
+            for (uint32_t i = 0; i < g.F; ++i) {
+                const uint32_t p0 = g.col_ptr[i];
+                tl[i] = g.K(i) ? (uint32_t)g.view_id[p0 + sel[i]] + 1u : 0u;
+                tb[i] = g.K(i) ? (uint32_t)g.view_id[p0 + best_sel[i]] + 1u : 0u;
+            }
+        }
         if ((int)s >= P.min_sweeps && (int)s > P.window) {
             const uint64_t prev = hist[s - P.window];
             if ((double)(prev - best_e) < (double)P.min_improvement * (double)prev) break;

@@ -153,6 +153,11 @@ void orc_tri(const float p[6], float out[5], const float* xy, uint32_t n, uint8_
 uint32_t orc_msg_code(float raw, float rho, float alpha, uint32_t old_code);   /* the 8-bit code a message value is stored as (damped against the old code) */
 /* experiments: per-sweep energies of the decoded labeling are written to buf[0..len) */
 void orc_mrf_set_trace(uint64_t* buf, int len);
+/* tests: per-sweep decode trace of the solves that follow.  For every sweep s <= len, row s - 1 of lab[len x n_faces] receives the labels
+ * (view + 1, 0 for an empty column) the sweep decoded, row s - 1 of best[len x n_faces] the labels of the best labeling AFTER that sweep's
+ * bookkeeping (the labeling kept so far).  Rows of sweeps that did not run stay untouched; null pointers switch the trace off.  Changes
+ * nothing in what the solver computes. */
+void orc_mrf_set_decode_trace(uint32_t* lab, uint32_t* best, int len);
 int orc_view_selection(const orc_csr* costs, const uint32_t* adj_ptr, const uint32_t* adj,
                        const orc_mrf_params* params, int n_threads, uint32_t* labels,
                        orc_mrf_stats* stats);

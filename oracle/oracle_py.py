@@ -212,6 +212,25 @@ def view_selection(csr, adj_ptr, adj, params=None, n_threads=0, timing=False):
     return labels, {f[0]: getattr(st, f[0]) for f in MrfStats._fields_}
 
 
+def view_selection_traced(csr, adj_ptr, adj, params=None, n_sweeps=16, n_threads=0):
+    """view_selection with the oracle's per-sweep traces switched on for this one solve: (labels, stats, trace) with
+    trace = {"energy": uint64[n] tracking energy of every sweep's decode (16-bit cost codes + 65535 per cut edge), "lab": uint32[n, F] the
+    decoded labels (view + 1, 0 for an empty column), "best": uint32[n, F] the best labeling after the sweep's bookkeeping}, n = the
+    sweeps that ran, at most n_sweeps"""
+    L = load()
+    L.orc_mrf_set_trace.argtypes = [C.c_void_p, C.c_int]
+    L.orc_mrf_set_decode_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    n = max(int(n_sweeps), 1)
+    e = np.zeros(n, np.uint64); lab = np.zeros((n, csr.n_faces), np.uint32); best = np.zeros((n, csr.n_faces), np.uint32)
+    L.orc_mrf_set_trace(_ptr(e), n); L.orc_mrf_set_decode_trace(_ptr(lab), _ptr(best), n)
+    try:
+        labels, st = view_selection(csr, adj_ptr, adj, params, n_threads)
+    finally:
+        L.orc_mrf_set_trace(None, 0); L.orc_mrf_set_decode_trace(None, None, 0)
+    ran = min(n, int(st["sweeps"]))
+    return labels, st, {"energy": e[:ran], "lab": lab[:ran], "best": best[:ran]}
+
+
 def energy(csr, adj_ptr, adj, labels):
     L = load()
     cs = csr.as_struct(); cuts = C.c_uint64(0)

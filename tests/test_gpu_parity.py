@@ -617,59 +617,8 @@ def test_logical_shards_on_one_gpu_equal_single(P):
     assert np.array_equal(np.concatenate([p.cost for p in pieces]).view(np.uint32), full.cost.view(np.uint32))
     # P shards: MRF with planned halo exchange, every shard holding the full table
     params = M.viewsel.default_mrf_params()
-    tap, tad = torch.from_numpy(adj_ptr.view(np.int32)).to(dev), torch.from_numpy(adj.view(np.int32)).to(dev)
-    ops = []
-    for r, c in enumerate(ctxs):
-        c.costs_upload(M.viewsel.DataCosts(full.n_faces, full.n_views, full.col_ptr, full.view_id, full.cost))
-        o = G.GpuShardOps(c, tap, tad, params); o.setup(); ops.append(o)
-    layouts = [o.layout(len(adj)) for o in ops]
-    assert all(np.array_equal(layouts[0], l) for l in layouts)          # every shard derives the same colouring and message layout
-    n_phases = ops[0].n_phases()
-    assert 2 <= n_phases <= 4 and all(o.n_phases() == n_phases for o in ops)
-    plans = [G.HaloPlan(full.col_ptr, adj_ptr, adj, pb, r, in_off=layouts[r]) for r in range(P)]
-    def dev_idx(a):
-        return torch.from_numpy(np.asarray(a, dtype=np.uint32).astype(np.int64)).to(dev).to(torch.int32)
-    hx_idx = [{k: [dev_idx(x) for x in getattr(plans[r], k)] for k in ("msg_send", "msg_recv", "node_send", "node_recv")} for r in range(P)]
-
-    def exchange(kinds):
-        bufs = {}
-        for r in range(P):
-            for q in range(P):
-                parts = []
-                for k, which in kinds:
-                    idx = hx_idx[r][k + "_send"][q]
-                    t = torch.zeros(len(idx), dtype=torch.int32, device=dev)
-                    if len(idx): ops[r].gather(which, idx, t)
-                    parts.append(t)
-                bufs[(r, q)] = parts
-        torch.cuda.synchronize()
-        for r in range(P):
-            for q in range(P):
-                for (k, which), t in zip(kinds, bufs[(q, r)]):
-                    idx = hx_idx[r][k + "_recv"][q]
-                    if len(idx): ops[r].scatter(which, idx, t)
-        torch.cuda.synchronize()
-
-    best = 2 ** 64 - 1; hist_e = [best]; sweeps = 0
-    for sw in range(1, params.max_sweeps + 1):
-        for ph in range(n_phases):                                    # colour-phased Gauss-Seidel: exchange after every phase
-            for r in range(P): ops[r].sweep_phase(ph, int(pb[r]), int(pb[r + 1]))
-            exchange([("msg", G.MSG), ("node", G.LAB)])
-        e = sum(int(ops[r].energy(G.LAB, int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P)) & (2 ** 64 - 1)
-        if e < best:
-            best = e
-            for o in ops: o.keep_best()
-        hist_e.append(best); sweeps = sw
-        if G.stop_rule(hist_e, sw, params): break
-    icm = 0
-    for icm in range(params.icm_iters):
-        for r in range(P): ops[r].icm_gain(int(pb[r]), int(pb[r + 1]))
-        exchange([("node", G.GAIN)])
-        moved = sum(int(ops[r].icm_apply(int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P))
-        exchange([("node", G.BEST_LAB)])
-        if moved == 0: break
-    labels = np.concatenate([ops[r].labels(int(pb[r]), int(pb[r + 1])).cpu().numpy().view(np.uint32) for r in range(P)])
-    e = sum(int(ops[r].energy(G.BEST_LAB, int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P)) & (2 ** 64 - 1)
+    labels, (e, sweeps, icm), n_phases = G.logical_shards_view_selection(ctxs, full, adj_ptr, adj, pb, params, dev)
+    assert 2 <= n_phases <= 4
     assert np.array_equal(labels, lab0), "labels depend on the partition"
     assert (e, sweeps, icm) == (st0["energy_fixed"], st0["sweeps"], st0["icm_iters"])
     for c in ctxs + [c0]: c.close()

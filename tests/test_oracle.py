@@ -612,3 +612,94 @@ def test_ray_terrace_has_exact_zero_components_and_boundary_rays():
     assert recorded == {"rim": recorded["rim"], "inner_edge": True, "centre_vertex": True, "diagonal": True, "inner_edge_2": True, "clear": False}
     assert recorded["rim"] is True, recorded
     assert need[9].sum() == 0                                                # level with the plate: the angle cull leaves that view no pair
+
+
+# ---- crafted MRF instances (util_cases "crafted MRF instances"): every generator's own property, the oracle's per-sweep traces against
+# ---- numpy restatements of the tracking energy, the keep-the-best rule and the ICM polish; tests/test_gpu_mrf_crafted.py runs the same
+# ---- instances against the GPU
+
+def _mrf_csr(case):
+    return O.CsrNp(len(case.col_ptr) - 1, case.n_views, case.col_ptr, case.view_id, case.cost)
+
+
+def test_crafted_mrf_generators_hold_their_properties():
+    """the generators assert what they exist for themselves (classes per the documented rule, colours per the restated greedy colouring,
+    tied minima, kinds of neighbouring lists); here they all run, and the planted entries are looked at once more from outside"""
+    cases = U.crafted_cases()
+    assert len(cases) == 6 + sum(len(U.small_range_counts(c)) for c in range(5))
+    assert [U.small_range_counts(c) for c in range(5)] == [[1, 2, 3, 31, 32, 33], [1, 2, 3, 31, 32, 33], [1, 2, 3, 7, 8, 9], [1, 2, 3, 4, 5], [1, 2, 3]]
+    for name, build in cases.items():
+        case = build()
+        F = len(case.col_ptr) - 1
+        assert F <= 2500 and int(np.diff(case.col_ptr.astype(np.int64)).max()) <= 257, name
+        assert len(case.adj_ptr) == F + 1 and case.view_id.max() < case.n_views
+        for i in range(F):                                           # strictly ascending label lists, symmetric adjacency
+            assert np.all(np.diff(case.view_id[case.col_ptr[i]:case.col_ptr[i + 1]].astype(np.int64)) > 0)
+        src = np.repeat(np.arange(F), np.diff(case.adj_ptr.astype(np.int64)))
+        assert sorted(zip(src.tolist(), case.adj.tolist())) == sorted(zip(case.adj.tolist(), src.tolist())), name
+    for L, seed in U.TIED_CASES:
+        case = U.tied_mrf(L, seed)
+        codes = U.cost_codes(case.cost)
+        step = np.nonzero((np.diff(codes.astype(np.int64)) == -1) & (np.nextafter(case.cost[1:], np.float32(2.0)) == case.cost[:-1]))[0]
+        assert len(step) >= 20, "neighbouring floats on either side of a rounding point"
+        same = np.nonzero((codes[:-1] == 0) & (codes[1:] == 0) & (case.cost[:-1] > 0) & (case.cost[1:] == 0))[0]
+        assert len(same) >= 5, "equal codes, different costs"
+    lo, hi = U.rounding_pair(0)
+    assert 0 < lo < hi and U.cost_codes(lo) == 0 and U.cost_codes(hi) == 1 and np.nextafter(lo, np.float32(1)) == hi
+    case = U.isolated_mrf()
+    first = U.first_min_code_labels(case)
+    exact = np.array([0 if a == b else int(case.view_id[a + int(np.argmin(case.cost[a:b]))]) + 1 for a, b in zip(case.col_ptr[:-1], case.col_ptr[1:])], np.uint32)
+    assert int((first != exact).sum()) >= 10, "columns whose first smallest CODE is not their smallest cost"
+
+
+TRACE_CASES = ("tied1", "tied15", "boundary", "isolated")          # the instances whose every sweep the GPU is compared on
+TRACE_PARAMS = dict(max_sweeps=16, min_sweeps=16)                  # 16 sweeps: four damped ones
+
+
+@pytest.mark.parametrize("name", TRACE_CASES)
+def test_mrf_traces_agree_with_numpy_restatements(name):
+    """the decode trace against restatements that owe the oracle nothing: every sweep's tracking energy = the 16-bit codes of the traced
+    labels + 65535 per cut edge; the traced best labeling = the decode of the FIRST sweep that reached the smallest energy so far; the
+    final labels = the restated ICM polish of the last best labeling (and that labeling itself without a polish); an instance without
+    model edges decodes the first smallest code in every sweep"""
+    case = U.crafted_cases()[name]()
+    csr = _mrf_csr(case)
+    labels, st, tr = O.view_selection_traced(csr, case.adj_ptr, case.adj, O.default_mrf_params(**TRACE_PARAMS), n_sweeps=16)
+    assert st["sweeps"] == 16 and tr["lab"].shape == (16, csr.n_faces)
+    kept = 0
+    for s in range(16):
+        assert U.tracking_energy_numpy(case, tr["lab"][s]) == int(tr["energy"][s]), "sweep %d" % (s + 1)
+        if tr["energy"][s] < tr["energy"][kept]: kept = s
+        assert np.array_equal(tr["best"][s], tr["lab"][kept]), "sweep %d: the kept labeling is not sweep %d's" % (s + 1, kept + 1)
+    polished, its = U.icm_numpy(case, tr["best"][-1], 50)
+    assert np.array_equal(labels, polished) and st["icm_iters"] == its
+    assert energy_numpy(case.col_ptr, case.view_id, case.cost, case.adj_ptr, case.adj, labels) == (st["energy_fixed"], st["cut_edges"])
+    l0, s0 = O.view_selection(csr, case.adj_ptr, case.adj, O.default_mrf_params(icm_iters=0, **TRACE_PARAMS))
+    assert np.array_equal(l0, tr["best"][-1]) and s0["icm_iters"] == 0
+    l1, s1 = O.view_selection(csr, case.adj_ptr, case.adj, O.default_mrf_params(**TRACE_PARAMS))
+    assert np.array_equal(l1, labels) and s1 == {**st, "t_setup": s1["t_setup"], "t_solve": s1["t_solve"]}, "the trace changes what the solver computes"
+    if name == "isolated":
+        assert np.all(tr["lab"] == U.first_min_code_labels(case)[None, :])
+
+
+def test_best_sweep_tie_instance_has_a_tied_sweep():
+    """BEST_TIE_CASE under the "best_tie" parameters: some sweep's tracking energy EQUALS the best so far while its labeling differs from
+    the kept one -- "keep the best" with `<=` for `<` would end on another labeling; without a polish nothing repairs that"""
+    case = U.tied_mrf(*U.BEST_TIE_CASE)
+    labels, st, tr = O.view_selection_traced(_mrf_csr(case), case.adj_ptr, case.adj, O.default_mrf_params(**U.CRAFTED_PARAMS["best_tie"]), n_sweeps=40)
+    e = tr["energy"]
+    assert st["sweeps"] == 40 and len(e) == 40
+    tied = [s for s in range(1, 40) if e[s] == e[:s].min() and not np.array_equal(tr["lab"][s], tr["best"][s])]
+    assert tied, "no sweep ties the best energy with another labeling: search another seed"
+    assert np.array_equal(labels, tr["best"][-1]) and not np.array_equal(labels, tr["lab"][tied[-1]])
+    assert int(e.min()) == U.tracking_energy_numpy(case, labels)
+
+
+def test_plateau_parameters_run_every_sweep():
+    """min_improvement = 0: `improvement < 0 * previous` is never true, so the stop rule's strict `<` runs all 40 sweeps on every crafted
+    instance -- although each of them sits on a plateau (no improvement over a window) long before"""
+    for name in ("tied1", "tied3", "tied15", "tied255", "boundary", "isolated"):
+        case = U.crafted_cases()[name]()
+        labels, st, tr = O.view_selection_traced(_mrf_csr(case), case.adj_ptr, case.adj, O.default_mrf_params(**U.CRAFTED_PARAMS["plateau"]), n_sweeps=40)
+        best = np.minimum.accumulate(tr["energy"])
+        assert st["sweeps"] == 40 and any(best[s] == best[s - 5] for s in range(6, 40)), name

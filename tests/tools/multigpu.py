@@ -401,6 +401,69 @@ class GpuShardOps:
         return out[:ne - nb]
 
 
+def logical_shards_view_selection(ctxs, table, adj_ptr, adj, part_begin, params, device):
+    """tex::view_selection over len(ctxs) contexts on ONE device, context r owning the nodes [part_begin[r], part_begin[r + 1]) and every
+    context holding the full table: the building blocks driven by hand, halo exchange by the planned index lists (no collective), the
+    stop rule and "keep the best" on the host.  Returns (labels of all nodes, (energy_fixed, sweeps, icm_iters), colour phases)."""
+    import torch
+    import mvs_texturing_amd as M
+    P = len(ctxs); pb = part_begin
+    tap, tad = torch.from_numpy(adj_ptr.view(np.int32)).to(device), torch.from_numpy(adj.view(np.int32)).to(device)
+    ops = []
+    for r, c in enumerate(ctxs):
+        c.costs_upload(M.viewsel.DataCosts(table.n_faces, table.n_views, table.col_ptr, table.view_id, table.cost))
+        o = GpuShardOps(c, tap, tad, params); o.setup(); ops.append(o)
+    layouts = [o.layout(len(adj)) for o in ops]
+    assert all(np.array_equal(layouts[0], l) for l in layouts)          # every shard derives the same colouring and message layout
+    n_phases = ops[0].n_phases()
+    assert all(o.n_phases() == n_phases for o in ops)
+    plans = [HaloPlan(table.col_ptr, adj_ptr, adj, pb, r, in_off=layouts[r]) for r in range(P)]
+    def dev_idx(a):
+        return torch.from_numpy(np.asarray(a, dtype=np.uint32).astype(np.int64)).to(device).to(torch.int32)
+    hx_idx = [{k: [dev_idx(x) for x in getattr(plans[r], k)] for k in ("msg_send", "msg_recv", "node_send", "node_recv")} for r in range(P)]
+
+    def exchange(kinds):
+        bufs = {}
+        for r in range(P):
+            for q in range(P):
+                parts = []
+                for k, which in kinds:
+                    idx = hx_idx[r][k + "_send"][q]
+                    t = torch.zeros(len(idx), dtype=torch.int32, device=device)
+                    if len(idx): ops[r].gather(which, idx, t)
+                    parts.append(t)
+                bufs[(r, q)] = parts
+        torch.cuda.synchronize()
+        for r in range(P):
+            for q in range(P):
+                for (k, which), t in zip(kinds, bufs[(q, r)]):
+                    idx = hx_idx[r][k + "_recv"][q]
+                    if len(idx): ops[r].scatter(which, idx, t)
+        torch.cuda.synchronize()
+
+    best = 2 ** 64 - 1; hist_e = [best]; sweeps = 0
+    for sw in range(1, params.max_sweeps + 1):
+        for ph in range(n_phases):                                    # colour-phased Gauss-Seidel: exchange after every phase
+            for r in range(P): ops[r].sweep_phase(ph, int(pb[r]), int(pb[r + 1]))
+            exchange([("msg", MSG), ("node", LAB)])
+        e = sum(int(ops[r].energy(LAB, int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P)) & (2 ** 64 - 1)
+        if e < best:
+            best = e
+            for o in ops: o.keep_best()
+        hist_e.append(best); sweeps = sw
+        if stop_rule(hist_e, sw, params): break
+    icm = 0
+    for icm in range(params.icm_iters):
+        for r in range(P): ops[r].icm_gain(int(pb[r]), int(pb[r + 1]))
+        exchange([("node", GAIN)])
+        moved = sum(int(ops[r].icm_apply(int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P))
+        exchange([("node", BEST_LAB)])
+        if moved == 0: break
+    labels = np.concatenate([ops[r].labels(int(pb[r]), int(pb[r + 1])).cpu().numpy().view(np.uint32) for r in range(P)])
+    e = sum(int(ops[r].energy(BEST_LAB, int(pb[r]), int(pb[r + 1]))[0].item()) for r in range(P)) & (2 ** 64 - 1)
+    return labels, (e, sweeps, icm), n_phases
+
+
 def boundary_faces(adj_ptr, adj, part_begin, me):
     """For every peer p: send[p] = faces of part `me` with a neighbour in part p, recv[p] = faces of part p with a neighbour
     in part `me` (sorted, unique).  From the adjacency alone, so send[p] here == recv[me] on rank p."""

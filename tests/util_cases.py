@@ -1,4 +1,7 @@
 """Shared helpers for the tests: random MRF instances and independent numpy re-statements."""
+import collections
+import functools
+
 import numpy as np
 
 
@@ -562,3 +565,400 @@ def need_from_pass_pattern(s, col_ptr, view_id):
     for c in range(3):
         need[view_id.astype(np.int64), s.faces[face_of, c]] = True
     return need
+
+
+# ---- crafted MRF instances (tests/test_gpu_mrf_crafted.py; the oracle side and every generator's own property run in tests/test_oracle.py):
+# ---- tied costs, columns exactly at the boundaries of the solver's per-node routing, launches of one to three nodes, nodes without a
+# ---- neighbour in the model.  Deterministic from their arguments; built once per process and shared -- callers do not write into them.
+
+MrfCase = collections.namedtuple("MrfCase", "n_views col_ptr view_id cost adj_ptr adj")
+CRAFTED_VIEWS = 640                    # 10 words of a view-set bitmap; two disjoint columns of 257 labels fit
+TIED_K = (1, 3, 4, 5, 31, 32, 33, 57, 63, 64, 65, 127, 128, 129, 254, 255, 256, 257)
+TIED_TIERS = ((1, 3, 4, 5, 31, 32), (33, 57, 63, 64), (65, 127, 128), (129, 254, 255), (256, 257))   # TIED_K by the class a neighbourhood of them gets
+# tier of each of the 40 segments of tied_mrf: 20, 10, 5, 3 and 2 segments of tiers 0 .. 4 (the long columns cost the oracle most), interleaved
+TIED_SEGMENT_TIER = tuple(([0] * 20 + [1] * 10 + [2] * 5 + [3] * 3 + [4] * 2)[(7 * k) % 40] for k in range(40))
+# nodes per 256-thread block of the five sweep launches (csrc/k_mrf.hip): launch_sweep4_g<G> hands launch_fast 256 / G with G = 8, 32, 64
+# for classes 0, 2, 3, launch_sweep8 256 / 8 for class 1, launch_sweep_generic one block per node
+MRF_NODES_PER_BLOCK = (256 // 8, 256 // 8, 256 // 32, 256 // 64, 1)
+MRF_CLASS_K = ((1, 32), (33, 64), (65, 128), (129, 255), (256, 257))      # kmx of classes 0 .. 3 (mrf_node_class); 4: a column past 255 labels
+
+
+def cost_codes(cost):
+    """the 16-bit code the sweeps read a unary as: trunc(c * 65535 + 0.5), both operations rounded to fp32"""
+    return (np.asarray(cost, np.float32) * np.float32(65535.0) + np.float32(0.5)).astype(np.uint32)
+
+
+def rounding_pair(c):
+    """the two neighbouring floats on either side of the rounding point (c + 0.5) / 65535 of code c: (lo, hi), codes c and c + 1"""
+    x = np.float32((c + 0.5) / 65535.0)
+    for _ in range(8):
+        if cost_codes(x) <= c: break
+        x = np.nextafter(x, np.float32(0.0))
+    for _ in range(8):
+        if cost_codes(np.nextafter(x, np.float32(2.0))) > c: break
+        x = np.nextafter(x, np.float32(2.0))
+    lo, hi = np.float32(x), np.nextafter(x, np.float32(2.0))
+    assert int(cost_codes(lo)) == c and int(cost_codes(hi)) == c + 1
+    return lo, hi
+
+
+def mrf_hash32(x):
+    """the hash of the colouring's keys as csrc/k_mrf.hip and oracle.cpp give it"""
+    x = np.asarray(x, np.uint64).copy(); m = np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & m
+    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & m
+    x ^= x >> np.uint64(16)
+    return x
+
+
+def colouring_numpy(adj_ptr, adj):
+    """greedy colouring in the order of the keys (hash32(id), id): a node takes the smallest colour no earlier neighbour holds"""
+    F = len(adj_ptr) - 1
+    ids = np.arange(F)
+    colour = np.full(F, -1, np.int64)
+    for i in np.lexsort((ids, mrf_hash32(ids))):
+        used = set(colour[adj[adj_ptr[i]:adj_ptr[i + 1]].astype(np.int64)].tolist())
+        c = 0
+        while c in used: c += 1
+        colour[i] = c
+    return colour
+
+
+def node_classes_numpy(col_ptr, adj_ptr, adj):
+    """mrf_node_class as csrc/k_mrf.hip documents it: kmx = the longest column among the node and its neighbours (0 for a node whose own
+    column is empty); degree > 3 (neighbours with empty columns count) or kmx > 255 -> 4 (generic), else 0 / 1 / 2 / 3 for
+    kmx <= 32 / 64 / 128 / 255.  A table of fewer than four entries or a graph without an edge is generic throughout."""
+    K = np.diff(np.asarray(col_ptr, np.int64)); F = len(K)
+    cls = np.zeros(F, np.int64)
+    if int(K.sum()) < 4 or len(adj) == 0:
+        return cls + 4
+    for i in range(F):
+        nb = adj[adj_ptr[i]:adj_ptr[i + 1]].astype(np.int64)
+        kmx = max(int(K[i]), int(K[nb].max()) if len(nb) else 0) if K[i] > 0 else 0
+        cls[i] = 4 if (len(nb) > 3 or kmx > 255) else 0 if kmx <= 32 else 1 if kmx <= 64 else 2 if kmx <= 128 else 3
+    return cls
+
+
+def _entry_index(case, labels):
+    """position in the table of every node's label (nodes with an empty column: -1); asserts that every label is in its column"""
+    cp = case.col_ptr.astype(np.int64); K = np.diff(cp)
+    labels = np.asarray(labels, np.int64)
+    keys = np.repeat(np.arange(len(K), dtype=np.int64), K) * 65536 + case.view_id.astype(np.int64)      # ascending: node major, views ascending
+    want = np.arange(len(K), dtype=np.int64) * 65536 + labels - 1
+    pos = np.searchsorted(keys, want)
+    seen = K > 0
+    assert np.all(labels[~seen] == 0) and np.all(labels[seen] > 0)
+    assert np.all(pos[seen] < len(keys)) and np.all(keys[np.minimum(pos[seen], len(keys) - 1)] == want[seen]), "a label outside its node's column"
+    return np.where(seen, pos, -1)
+
+
+def model_edges(case):
+    """(i, j), i < j, of every edge of the model: adjacent nodes whose columns are both non-empty (an edge listed twice counts twice)"""
+    K = np.diff(case.col_ptr.astype(np.int64))
+    src = np.repeat(np.arange(len(K), dtype=np.int64), np.diff(case.adj_ptr.astype(np.int64))); dst = case.adj.astype(np.int64)
+    m = (src < dst) & (K[src] > 0) & (K[dst] > 0)
+    return src[m], dst[m]
+
+
+def tracking_energy_numpy(case, labels):
+    """the solver's tracking energy of a labeling, written independently: the 16-bit cost codes of the chosen entries, 65535 for a node
+    with an empty column, 65535 per cut edge"""
+    pos = _entry_index(case, labels)
+    codes = cost_codes(case.cost).astype(np.int64)
+    unary = int(codes[pos[pos >= 0]].sum()) + 65535 * int((pos < 0).sum())
+    i, j = model_edges(case)
+    labels = np.asarray(labels, np.int64)
+    return unary + 65535 * int((labels[i] != labels[j]).sum())
+
+
+def first_min_code_labels(case):
+    """per node the label at the FIRST position of its smallest cost code (0 for an empty column): what a node without a neighbour in the
+    model decodes in every sweep"""
+    codes = cost_codes(case.cost)
+    out = np.zeros(len(case.col_ptr) - 1, np.uint32)
+    for i in range(len(out)):
+        a, b = int(case.col_ptr[i]), int(case.col_ptr[i + 1])
+        if b > a: out[i] = int(case.view_id[a + int(np.argmin(codes[a:b]))]) + 1
+    return out
+
+
+def icm_numpy(case, labels, max_iters):
+    """the ICM polish restated: per node the FIRST label of smallest exact cost + number of differently labelled model neighbours (fp32),
+    gain = current - smallest; a node moves iff its gain is positive and no model neighbour has a larger gain, or an equal one and a
+    smaller id.  Returns (labels, iterations that moved something)."""
+    cp = case.col_ptr.astype(np.int64); K = np.diff(cp); F = len(K)
+    ap = case.adj_ptr.astype(np.int64); ad = case.adj.astype(np.int64)
+    nbs = [ad[ap[i]:ap[i + 1]][K[ad[ap[i]:ap[i + 1]]] > 0] if K[i] > 0 else ad[:0] for i in range(F)]
+    lab = np.asarray(labels, np.int64).copy()
+    it = 0
+    for it in range(max_iters):
+        gain = np.zeros(F, np.float32); cand = lab.copy()
+        for i in range(F):
+            if K[i] == 0: continue
+            L = case.view_id[cp[i]:cp[i + 1]].astype(np.int64) + 1
+            nl = lab[nbs[i]]
+            diff = (len(nl) - (nl[None, :] == L[:, None]).sum(axis=1)).astype(np.float32)
+            en = case.cost[cp[i]:cp[i + 1]].astype(np.float32) + diff
+            bt = int(np.argmin(en))
+            gain[i] = en[int(np.nonzero(L == lab[i])[0][0])] - en[bt]; cand[i] = L[bt]
+        new = lab.copy(); moved = 0
+        for i in np.nonzero(gain > 0)[0]:
+            g = gain[nbs[i]]
+            if not np.any((g > gain[i]) | ((g == gain[i]) & (nbs[i] < i))):
+                new[i] = cand[i]; moved += 1
+        lab = new
+        if moved == 0: break
+    else:
+        it = max_iters
+    return lab.astype(np.uint32), it
+
+
+def _mrf_case(lists, cols, n_views, perm=None):
+    """MrfCase from adjacency lists (insertion order, as UniGraph::add_edge leaves them) and per node (ascending views, costs); perm[i] = new id of node i"""
+    n = len(lists)
+    if perm is not None:
+        inv = np.argsort(perm)
+        lists = [[int(perm[g]) for g in lists[inv[k]]] for k in range(n)]
+        cols = [cols[inv[k]] for k in range(n)]
+    ap, ad = _lists_to_csr(lists)
+    cp = np.zeros(n + 1, np.uint32); cp[1:] = np.cumsum([len(v) for v, _ in cols])
+    vi = np.concatenate([np.asarray(v, np.uint16) for v, _ in cols] + [np.zeros(0, np.uint16)])
+    co = np.concatenate([np.asarray(c, np.float32) for _, c in cols] + [np.zeros(0, np.float32)])
+    for a in (cp, vi, co, ap, ad): a.setflags(write=False)
+    return MrfCase(n_views, cp, vi, co, ap, ad)
+
+
+def _grid_costs(rng, K, levels, tie):
+    """K costs on the grid k / levels; tie: the minimum is copied to a second position"""
+    c = (rng.integers(0, levels + 1, K).astype(np.float32) / np.float32(levels)).astype(np.float32)
+    if tie and K >= 2:
+        p = int(np.argmin(c)); q = int(rng.integers(0, K - 1)); q += q >= p
+        c[q] = c[p]
+    return c
+
+
+def _plant(c, variant, code):
+    """entries planted into a column of at least five costs: variant 0 -- exactly 1.0, exactly 0.0 and the floats on either side of code's
+    rounding point; variant 1 -- the larger-than-zero float that still has code 0 IN FRONT of an exact 0.0 (equal codes, different costs:
+    the decode takes the first, the polish the smaller) and the float next to it, whose code is 1"""
+    lo, hi = rounding_pair(code if variant == 0 else 0)
+    if variant == 0: c[0], c[1], c[2], c[3] = 1.0, hi, lo, 0.0
+    else: c[0], c[1], c[2], c[3] = hi, lo, 0.0, 1.0
+    return c
+
+
+def edge_kinds(case):
+    """how the two label lists of every model edge relate: counts of "identical", "equal_length" (but different), "subset" (one a strict
+    subset of the other), "disjoint", and "other" for the rest"""
+    out = collections.Counter()
+    for i, j in zip(*model_edges(case)):
+        a = set(case.view_id[case.col_ptr[i]:case.col_ptr[i + 1]].tolist()); b = set(case.view_id[case.col_ptr[j]:case.col_ptr[j + 1]].tolist())
+        out["identical" if a == b else "disjoint" if not (a & b) else "subset" if (a < b or b < a) else "equal_length" if len(a) == len(b) else "other"] += 1
+    return out
+
+
+def min_code_tie_fraction(case):
+    """fraction of the nodes with a non-empty column whose smallest cost code stands at two or more positions"""
+    codes = cost_codes(case.cost); K = np.diff(case.col_ptr.astype(np.int64))
+    tied = sum(int((codes[a:a + k] == codes[a:a + k].min()).sum() >= 2) for a, k in zip(case.col_ptr[:-1].astype(np.int64), K) if k)
+    return tied / max(int((K > 0).sum()), 1)
+
+
+@functools.lru_cache(maxsize=None)
+def tied_mrf(levels, seed):
+    """2000 nodes of degree 3 -- a ring, and one chord per node inside its 50-node segment -- with costs on the grid k / levels, in half
+    of the columns the minimum copied to a second position.  Every segment draws its K from one tier of TIED_TIERS (TIED_SEGMENT_TIER), so
+    every class of the routing holds a hundred nodes and more and every K of TIED_K occurs; along the ring a node keeps its predecessor's label list (55 %), takes another of the
+    same length, a strict subset or superset, or a disjoint one (15 % each); 3 % of the columns are empty.  Every 40th node carries the
+    planted entries of _plant.  Property: at least a quarter of the non-empty nodes reach their smallest cost code at two or more
+    positions, every class has at least 20 nodes, each of the four kinds of neighbouring lists is on at least 5 % of the model's edges."""
+    n, seg, V = 2000, 50, CRAFTED_VIEWS
+    rng = np.random.default_rng([levels, seed, 7])
+    lists = [[(i - 1) % n, (i + 1) % n] for i in range(n)]
+    for s0 in range(0, n, seg):
+        while True:
+            pairs = rng.permutation(seg).reshape(-1, 2)
+            if np.all(np.abs(pairs[:, 0] - pairs[:, 1]) > 1): break
+        for a, b in pairs.tolist():
+            lists[s0 + a].append(s0 + b); lists[s0 + b].append(s0 + a)
+    cols = []; prev = None
+    for i in range(n):
+        tier = TIED_TIERS[TIED_SEGMENT_TIER[i // seg]]
+        if i % seg == 0: prev = None
+        if rng.random() < 0.03:
+            cols.append((np.zeros(0, np.uint16), np.zeros(0, np.float32))); continue
+        r = rng.random()
+        if prev is None:
+            v = np.sort(rng.choice(V, int(rng.choice(tier)), replace=False))
+        elif r < 0.55:
+            v = prev
+        elif r < 0.70:
+            v = prev
+            while np.array_equal(v, prev): v = np.sort(rng.choice(V, len(prev), replace=False))
+        elif r < 0.85:
+            k2 = int(rng.choice([k for k in tier if k != len(prev)]))
+            rest = np.setdiff1d(np.arange(V), prev)
+            v = np.sort(rng.choice(prev, k2, replace=False)) if k2 < len(prev) else np.sort(np.concatenate([prev, rng.choice(rest, k2 - len(prev), replace=False)]))
+        else:
+            v = np.sort(rng.choice(np.setdiff1d(np.arange(V), prev), int(rng.choice(tier)), replace=False))
+        prev = v
+        c = _grid_costs(rng, len(v), levels, tie=rng.random() < 0.5)
+        if i % 40 == 7 and len(v) >= 5: c = _plant(c, (i // 40) % 2, int(rng.integers(1, 65534)))
+        cols.append((v, c))
+    case = _mrf_case(lists, cols, V)
+    K = np.diff(case.col_ptr.astype(np.int64))
+    assert set(TIED_K) <= set(K.tolist()) and int((K == 0).sum()) >= 10
+    assert min_code_tie_fraction(case) >= 0.25
+    assert np.all(np.bincount(node_classes_numpy(case.col_ptr, case.adj_ptr, case.adj), minlength=5) >= 20)
+    kinds = edge_kinds(case); total = sum(kinds.values())
+    assert all(kinds[k] >= 0.05 * total for k in ("identical", "equal_length", "subset", "disjoint")), kinds
+    assert np.any(case.cost == 0.0) and np.any(case.cost == 1.0)
+    return case
+
+
+def _pool_column(rng, K, levels=7):
+    """K views out of the first K + K / 4 + 8 (neighbouring columns share most of their labels), costs on a grid"""
+    v = np.sort(rng.choice(min(CRAFTED_VIEWS, K + K // 4 + 8), K, replace=False)) if K else np.zeros(0, np.int64)
+    return v, _grid_costs(rng, K, levels, tie=bool(K) and rng.random() < 0.5)
+
+
+class _Builder:
+    def __init__(self, rng): self.rng, self.lists, self.cols = rng, [], []
+
+    def node(self, K):
+        self.lists.append([]); self.cols.append(_pool_column(self.rng, K)); return len(self.lists) - 1
+
+    def edge(self, a, b): self.lists[a].append(b); self.lists[b].append(a)
+
+    def path(self, Ks):
+        ids = [self.node(K) for K in Ks]
+        for a, b in zip(ids, ids[1:]): self.edge(a, b)
+        return ids
+
+    def star(self, Kc, Kl):
+        c = self.node(Kc)
+        for K in Kl: self.edge(c, self.node(K))
+        return c
+
+    def clique(self, Ks):
+        ids = [self.node(K) for K in Ks]
+        for x, a in enumerate(ids):
+            for b in ids[x + 1:]: self.edge(a, b)
+        return ids
+
+    def case(self, shuffle=True):
+        return _mrf_case(self.lists, self.cols, CRAFTED_VIEWS, self.rng.permutation(len(self.lists)) if shuffle else None)
+
+
+BOUNDARY_PAIRS = ((32, 32), (32, 33), (64, 64), (64, 65), (128, 128), (128, 129), (255, 255), (255, 256), (1, 255), (2, 256), (1, 32), (33, 64), (65, 128))
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_class_mrf(seed):
+    """(case, marks): nodes whose class a NEIGHBOUR decides -- paths A - B - A - B for every (A, B) of BOUNDARY_PAIRS: K = 1 next to 255 is
+    class 3, K = 2 next to 256 generic, K = 32 next to 33 class 1 -- ; stars of degree exactly 3 (fast) and exactly 4 (generic), also with
+    one leaf whose column is empty; a star of degree 7 and a hub of degree 300 (two passes of the generic kernel's 256-thread edge
+    loop): all but the first four leaves stand past position 4 of the centre's list, where the reverse-edge search of mrf_size_kernel
+    leaves its four-entry head and walks the list (its slow path); a 9-clique (nine colour phases, more than the message layout keeps apart).  Node ids are shuffled.  marks: name ->
+    node ids for the assertions below, which restate the class rule and the colouring in numpy."""
+    rng = np.random.default_rng([seed, 11])
+    b = _Builder(rng); m = collections.defaultdict(list)
+    for A, B in BOUNDARY_PAIRS:
+        for _ in range(2): m["pair%d_%d" % (A, B)] += b.path([A, B, A, B])
+    for Kc in (5, 32, 33, 255):
+        m["deg3"].append(b.star(Kc, [3, 4, 5]))
+        m["deg4"].append(b.star(Kc, [3, 4, 5, 4]))
+    m["deg3"].append(b.star(5, [3, 0, 5])); m["deg4"].append(b.star(5, [3, 0, 5, 4]))
+    m["deg7"].append(b.star(6, [3, 4, 5, 6, 5, 4, 3]))
+    m["hub"].append(b.star(5, [3 + k % 3 for k in range(300)]))
+    m["clique"] += b.clique([3, 4, 5, 6, 7, 8, 9, 10, 4])
+    n = len(b.lists); perm = rng.permutation(n)
+    case = _mrf_case(b.lists, b.cols, CRAFTED_VIEWS, perm)
+    marks = {k: perm[np.array(v)] for k, v in m.items()}
+    K = np.diff(case.col_ptr.astype(np.int64)); deg = np.diff(case.adj_ptr.astype(np.int64))
+    cls = node_classes_numpy(case.col_ptr, case.adj_ptr, case.adj)
+    for (A, B), want in zip(BOUNDARY_PAIRS, (0, 1, 1, 2, 2, 3, 3, 4, 3, 4, 0, 1, 2)):
+        ids = marks["pair%d_%d" % (A, B)]
+        assert sorted(K[ids].tolist()) == sorted([A, B] * 4) and np.all(cls[ids] == want), (A, B)
+    assert np.all(deg[marks["deg3"]] == 3) and np.all(cls[marks["deg3"]] == [0, 0, 1, 3, 0])
+    assert np.all(deg[marks["deg4"]] == 4) and np.all(cls[marks["deg4"]] == 4)
+    hub = int(marks["hub"][0])
+    assert deg[hub] == 300 and cls[hub] == 4 and deg[marks["deg7"][0]] == 7
+    leaves = case.adj[case.adj_ptr[hub]:case.adj_ptr[hub + 1]]
+    assert np.all(deg[leaves] == 1) and np.all(cls[leaves] == 0)          # 296 leaves stand past position 4 of the hub's list: the reverse-edge search walks it
+    colour = colouring_numpy(case.adj_ptr, case.adj)
+    assert sorted(colour[marks["clique"]].tolist()) == list(range(9)) and colour.max() == 8
+    assert np.all(np.bincount(cls, minlength=5) > 0)
+    return case, marks
+
+
+@functools.lru_cache(maxsize=None)
+def small_range_mrf(cls, count):
+    """`count` separate 4-cliques (every node of degree exactly 3) whose columns all have a length of class `cls` (MRF_CLASS_K; the first
+    clique sits on the class's upper boundary): the greedy colouring gives every clique the colours 0, 1, 2, 3 once, so each of the four
+    (colour, class) ranges of the schedule -- each one launch -- holds exactly `count` nodes.  With count = 1, 2, 3 and one block's node
+    count (MRF_NODES_PER_BLOCK) - 1, + 0, + 1 the prologue and epilogue of a kernel's software pipeline are the whole launch, and a
+    launch ends one node short of, on and one node past a block."""
+    lo, hi = MRF_CLASS_K[cls]
+    rng = np.random.default_rng([cls, count, 13])
+    b = _Builder(rng)
+    for q in range(count):
+        b.clique([hi] * 4 if q == 0 else [int(k) for k in rng.integers(lo, hi + 1, 4)])
+    case = b.case(shuffle=True)
+    assert np.all(node_classes_numpy(case.col_ptr, case.adj_ptr, case.adj) == cls)
+    colour = colouring_numpy(case.adj_ptr, case.adj)
+    assert np.array_equal(np.bincount(colour), [count] * 4)
+    return case
+
+
+def small_range_counts(cls):
+    npb = MRF_NODES_PER_BLOCK[cls]
+    return sorted({c for c in (1, 2, 3, npb - 1, npb, npb + 1) if c >= 1})
+
+
+@functools.lru_cache(maxsize=None)
+def isolated_mrf():
+    """nodes of every K of TIED_K without a neighbour in the model: of degree 0, and with 1, 3 and 4 neighbours whose columns are all
+    empty (4: generic by its degree).  No message ever reaches them, so every sweep decodes the first position of the smallest cost
+    code (first_min_code_labels: numpy alone).  Costs on the grid k / 3 with a tied minimum; columns of five and more labels carry the
+    planted entries of _plant, among them two entries of EQUAL code and different cost."""
+    rng = np.random.default_rng(17)
+    b = _Builder(rng)
+    for x, K in enumerate(TIED_K):
+        for n_empty in (0, 1, 3, 4):
+            c = b.star(K, [0] * n_empty)
+            v, co = b.cols[c]
+            co = _grid_costs(rng, K, 3, tie=True)
+            if K >= 5 and n_empty != 1: co = _plant(co, (x + n_empty) % 2, int(rng.integers(1, 65534)))
+            b.cols[c] = (v, co)
+    case = b.case(shuffle=True)
+    assert len(model_edges(case)[0]) == 0 and len(case.adj) > 0
+    K = np.diff(case.col_ptr.astype(np.int64)); cls = node_classes_numpy(case.col_ptr, case.adj_ptr, case.adj)
+    assert all(int(((K == k) & (cls == (4 if k > 255 else c))).sum()) >= 3 for c, tier in enumerate(TIED_TIERS) for k in tier)
+    return case
+
+
+# the solver parameters the crafted instances run with (tests/test_oracle.py on the CPU, tests/test_gpu_mrf_crafted.py against the GPU)
+CRAFTED_PARAMS = {
+    "defaults": dict(),
+    "s30": dict(max_sweeps=30, min_sweeps=12),
+    "plateau": dict(min_improvement=0.0, max_sweeps=40, min_sweeps=6),          # strict `<` of the stop rule: never stops on a plateau, all 40 sweeps run
+    "best_tie": dict(damping=0.0, rho=1.0, icm_iters=0, max_sweeps=40, min_sweeps=40),   # nothing repairs which sweep was kept
+    "icm_only": dict(max_sweeps=0, icm_iters=100),                              # the argmin-unary start: `<` on the exact costs
+    "window1": dict(window=1, min_sweeps=1),
+    "window5": dict(window=5, min_sweeps=5),
+}
+BEST_TIE_CASE = (1, 5)      # tied_mrf(levels, seed) on which later sweeps' tracking energy EQUALS the best so far with another labeling (seeds searched on the CPU; tests/test_oracle.py asserts it)
+TIED_CASES = (BEST_TIE_CASE, (3, 1), (15, 1), (255, 1))
+BOUNDARY_SEED = 3
+
+
+def crafted_cases():
+    """name -> builder of every crafted MRF instance (tests/test_oracle.py and tests/test_gpu_mrf_crafted.py walk the same list)"""
+    out = {"tied%d" % L: (lambda L=L, sd=sd: tied_mrf(L, sd)) for L, sd in TIED_CASES}
+    out["boundary"] = lambda: boundary_class_mrf(BOUNDARY_SEED)[0]
+    out["isolated"] = isolated_mrf
+    for cls in range(5):
+        for n in small_range_counts(cls):
+            out["range_c%d_n%d" % (cls, n)] = (lambda cls=cls, n=n: small_range_mrf(cls, n))
+    return out
