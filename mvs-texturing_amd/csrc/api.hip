@@ -14,40 +14,12 @@
 #include <thread>
 #include <vector>
 
-namespace mvs {
-void dc_phase1(mvs_ctx* ctx, const mvs_settings* st);
-void dc_phase2(mvs_ctx* ctx);
-void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats);
-void dc_run(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats);
-void undistort_image(mvs_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, double flen, double d0, double d1);
-void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax);
-void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t* h_ptr, const uint16_t* h_view_rev, const float* h_q_rev, const float* h_col_rev, const mvs_settings* st);
-void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params);
-void mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_energy(mvs_ctx* ctx, bool best, uint32_t nb0, uint32_t ne0, bool reduce = true);
-void mrf_keep_best(mvs_ctx* ctx);
-void mrf_exact_costs(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-uint32_t mrf_region_round(mvs_ctx* ctx);
-void mrf_step(mvs_ctx* ctx, const unsigned long long* energy, const unsigned long long* const* peer_tab = nullptr, uint32_t n_peer = 0, uint32_t peer_off = 0);
-void mrf_poll(mvs_ctx* ctx, uint32_t step, mvs_mrf_progress* out);
-void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order = false);
-}  // namespace mvs
-
 using namespace mvs;
 
 static thread_local std::string g_last_error;
 
 static mvs_status fail(mvs_status st, const std::string& msg) { g_last_error = msg; return st; }
 namespace mvs { mvs_status api_fail(mvs_status st, const std::string& msg) { return fail(st, msg); } }
-
-#define MVS_API_BEGIN try {
-#define MVS_API_END                                                          \
-    } catch (const StatusError& e) { return fail(e.st, e.what()); }          \
-      catch (const HipError& e) { return fail(MVS_ERR_HIP, e.what()); }      \
-      catch (const std::exception& e) { return fail(MVS_ERR_HIP, e.what()); } \
-    return MVS_OK;
 
 #include <dlfcn.h>
 namespace mvs {
@@ -81,8 +53,6 @@ static float compute_cos_limit() {
 }
 
 namespace mvs {
-bool table_to_caller_order(mvs_ctx* ctx, bool with_quality);
-void adjacency_to_table_order(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, size_t E);
 // The adjacency lists arrive in the caller's numbering (UniGraph, uni_graph.h:22).  A table that lives in the library's own order
 // (ctx->t_perm; k_order.hip) gets them renumbered on the device, list order kept; `table_order` = the lists already are in the
 // table's order (the sharded driver renumbers once for all its calls).
@@ -350,6 +320,8 @@ mvs_status mvs_ctx_create(int device, mvs_ctx** out) {
     c->dc_range_pairs = env_dc_range_pairs();
     if (const char* e = getenv("MVS_BVH_UPPER_MIN_FACES")) c->bvh_upper_min_faces = (uint32_t)std::max(0ll, atoll(e));   // (test runs: 0 puts every mesh of the suite through the upper levels of the face order)
     c->counters.ensure(64);
+    MVS_HIP(hipMalloc((void**)&c->words, sizeof(SolverWords)));
+    MVS_HIP(hipMemset(c->words, 0, sizeof(SolverWords)));
     *out = c;
     MVS_API_END
 }
@@ -365,6 +337,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
+    if (ctx->words) (void)hipFree(ctx->words);
     if (ctx->h_kd_flags) (void)hipHostFree(ctx->h_kd_flags);
     if (ctx->h_icm) (void)hipHostFree(ctx->h_icm);
     if (ctx->h_rb) (void)hipHostFree(ctx->h_rb);
@@ -696,7 +669,7 @@ static void read_energy(mvs_ctx* ctx, uint64_t out[2]) {
 // stop rule mirroring StopWhenReturnsDiminish (view_selection.cpp:84), ICM polish.
 // ICM polish of the best labeling (whole graph): rounds of gain + apply (see icm_rounds)
 static int icm_polish(mvs_ctx* ctx, uint32_t F, int max_iters) {
-    return icm_rounds(ctx, max_iters, ctx->m_moved.p, [&](int) {
+    return icm_rounds(ctx, max_iters, &ctx->words->icm_n_moved, [&](int) {
         mrf_icm_gain(ctx, 0, F);
         mrf_icm_apply(ctx, 0, F);   // in place: winners form an independent set
     });

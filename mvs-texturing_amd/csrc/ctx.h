@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <string.h>
 #include <algorithm>
 #include <functional>
@@ -114,6 +115,22 @@ struct alignas(16) NodeDesc {
     uint32_t nbr[3];      // neighbour node ids (0xFFFFFFFF = none)
 };
 static_assert(sizeof(NodeDesc) == 48, "NodeDesc must be 48 bytes");
+
+// The single words the solver's stages (and the rows that borrow a context) count in and read back: one named field per purpose, in one
+// device allocation made with the context and never re-allocated.  A stage clears its own fields before it counts in them and touches
+// nobody else's.  Fields on one line travel together (a kernel indexes them from the first, or one copy / read_words fetches them).
+struct SolverWords {
+    uint32_t icm_n_moved, icm_cursor;                                // mrf_icm_apply: nodes moved, length of the active list (the kernels' moved[0], moved[1])
+    uint32_t labels_bad, labels_unseen;                            // mrf_labels: labels above the number of views (+ foreign ones), faces left with label 0
+    uint32_t colour_pending, colour_full;                          // mrf_setup's colouring: a node is still waiting, a node saw all 64 colours around it
+    uint32_t setup_kmax, setup_degmax, setup_total, setup_unsorted;   // mrf_setup: largest column, largest degree, message elements, "a column is not strictly ascending"
+    uint32_t exact_foreign;                                        // mrf_exact_costs: labels that are no entry of their node's column (mrf_labels adds them to "bad")
+    uint32_t adj_overflow, adj_self;                               // k_mesh.hip build_adjacency: a neighbour list overflowed, faces with a repeated vertex
+    uint32_t patch_bad;                                            // k_patch.hip get_subgraphs: a label >= n_labels
+    uint32_t region_moved;                                         // k_region.hip mrf_region_round: regions that moved
+};
+static_assert(sizeof(SolverWords) <= 64 * sizeof(uint32_t), "SolverWords must fit one read_words");
+static_assert(offsetof(SolverWords, setup_unsorted) - offsetof(SolverWords, colour_pending) == 5 * sizeof(uint32_t), "mrf_setup clears colour_pending .. setup_unsorted with one memset");
 
 struct GslDev;   // row f5 (k_seam.hip)
 struct TexPatchDev;   // row f6 (k_texpatch.hip)
@@ -264,7 +281,7 @@ struct mvs_ctx {
     uint32_t m_stride = 0;      // F + 1: offset of the second buffer
     bool exact_valid = false; uint32_t exact_nb = 0, exact_ne = 0;   // b_sel / b_cost of nodes [exact_nb, exact_ne) are derived from b_lab (k_mrf.hip mrf_exact_costs)
     uint32_t* b_sel = nullptr; uint32_t* b_lab = nullptr; float* b_cost = nullptr; bool best_resolved = false;   // the best buffer, once the host knows which one it is (resolve_best)
-    mvs::DBuf<unsigned long long> m_energy; mvs::DBuf<uint32_t> m_moved; mvs::DBuf<uint32_t> m_alist; bool icm_dirty_valid = false;   // ICM active set: nodes whose gain the next pass re-evaluates
+    mvs::DBuf<unsigned long long> m_energy; mvs::SolverWords* words = nullptr /* allocated by mvs_ctx_create */; mvs::DBuf<uint32_t> m_alist; bool icm_dirty_valid = false;   // ICM active set: nodes whose gain the next pass re-evaluates
     uint32_t m_n_adj = 0;      // directed edges of the adjacency given to mrf_setup
     uint32_t m_energy_blocks = 0;   // per-block partial pairs the last mrf_energy left behind m_energy.p + 4
     bool m_energy_from_sweep = false;   // ... or the last sweep's own kernels did (fast path: the energy is accumulated while sweeping)
@@ -375,4 +392,71 @@ void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, 
 // the candidates of every label (get_subgraphs), their boxes, the merge loop, patch ids, every face's patch and position: fills T and
 // T.C / n_patches / n_merged; throws MVS_ERR_LABELING when a labelled face leaves its view's image.  Needs patch_check_inputs first.
 void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const char* who);
+
+// ---- every other function one source file defines and another calls: declared here and nowhere else, grouped by the defining file ----
+// api.hip
+mvs_status api_fail(mvs_status st, const std::string& msg);   // records the message of mvs_last_error, returns st
+// the caller's adjacency lists (host or device) as ctx->r_adj_ptr / r_adj in the order of the active table; table_order: they already are
+void set_adjacency(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int on_device, bool table_order);
+// k_prep.hip
+void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const size_t* d_mask_off);   // image preparation of all views (ctx->d_views uploaded)
+void undistort_image(mvs_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, double flen, double d0, double d1);
+// k_bvh.hip
+void build_scene_order(mvs_ctx* ctx);    // the resident mesh along a Hilbert curve: ctx->iv / ifc / inr, f_perm / f_pos
+bool scene_order_commit(mvs_ctx* ctx);   // true: the upper levels of the order overflowed and it was rebuilt without them -- derive again what came from it
+void build_bvh(mvs_ctx* ctx);            // BVH + vertex -> face incidence of the mesh in the layout of build_scene_order
+void trace_rays(mvs_ctx* ctx);
+void build_vertex_faces(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint32_t NV);   // vertex -> incident faces (CSR ctx->vf_ptr / vf)
+// k_kdorder.hip
+void kd_refine_order(mvs_ctx* ctx, const float* verts, const uint32_t* faces, uint32_t* order, uint32_t F, uint32_t window, uint32_t leaf_window);   // upper levels of the face order
+// k_dc.hip
+void dc_phase1(mvs_ctx* ctx, const mvs_settings* st);     // everything up to the per-face sorted infos + the local maximum quality
+void dc_phase2(mvs_ctx* ctx);                             // histogram of the local qualities against the (possibly all-reduced) maximum
+void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats);        // percentile from the (possibly all-reduced) histogram, cost write
+void dc_run(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats);   // the three phases, or the ranged walk (option "dc_range_pairs")
+void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax);        // prunes the context's own active table in place
+// postprocess_face_infos on host lists (every face's list reversed): outlier detection, then phases 2 and 3
+void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t* h_ptr, const uint16_t* h_view_rev, const float* h_q_rev, const float* h_col_rev, const mvs_settings* st);
+// k_order.hip
+bool table_to_caller_order(mvs_ctx* ctx, bool with_quality);   // the active table -> ctx->u_*; false: it already is in the caller's order (read r_*)
+void adjacency_to_table_order(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, size_t E);   // device lists -> ctx->m_adj_ptr / m_adj
+// device lists in the caller's numbering -> out_ptr / out_adj in the order `perm` (position -> caller's id; `pos` its inverse), list order kept
+void renumber_adjacency(mvs_ctx* ctx, uint32_t F, const uint32_t* perm, const uint32_t* pos, const uint32_t* d_adj_ptr, const uint32_t* d_adj, size_t E,
+                        DBuf<uint32_t>& out_ptr, DBuf<uint32_t>& out_adj);
+// k_patch.hip
+// components of equal labels -> ctx->p_label_ptr [n_labels + 1], p_comp_ptr [C + 1], p_comp_faces [F]; returns C
+uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, uint32_t F, uint32_t n_labels);
+// k_region.hip
+uint32_t mrf_region_round(mvs_ctx* ctx);   // one round of region moves on the best labeling (needs mrf_exact_costs); returns the regions moved
+// k_mrf.hip -- node ranges [nb0, ne0) are positions of the active table
+void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params);   // the solver's tables for the active table and adjacency
+void mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);     // one sweep = every colour phase in turn
+void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part = MRF_PART_ALL);   // one colour phase, both zones or one
+void mrf_sweep_energy_reduce(mvs_ctx* ctx, unsigned long long* out2 = nullptr);   // the last sweep's per-block energy partials -> ctx->m_energy (and out2)
+void mrf_energy(mvs_ctx* ctx, bool best, uint32_t nb0, uint32_t ne0, bool reduce = true);   // energy of the current decode or the best labeling -> ctx->m_energy
+void mrf_keep_best(mvs_ctx* ctx);                             // best labeling := the current decode
+void mrf_exact_costs(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);   // position and exact unary of every label of the best labeling (idempotent)
+// one bookkeeping step of the device-side stop rule; energy = the all-reduced pair, or null: per-block partials (or the peers' tables)
+void mrf_step(mvs_ctx* ctx, const unsigned long long* energy, const unsigned long long* const* peer_tab = nullptr, uint32_t n_peer = 0, uint32_t peer_off = 0);
+void mrf_poll(mvs_ctx* ctx, uint32_t step, mvs_mrf_progress* out);   // waits for the report of one of the last 16 steps
+void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);  // ICM on the best labeling: gains and candidates
+void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0); // ... the winners move; the count lands in words->icm_n_moved
+// labels of the best labeling into d_labels; out = {bad, unseen}; caller_order: the whole graph's labels at the caller's face ids
+void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order = false);
+void resolve_best(mvs_ctx* ctx);                              // ctx->b_sel / b_lab / b_cost := the best labeling's buffers (one read-back)
+
+// ---- around the body of an entry point: what it throws becomes the call's status and the message of mvs_last_error ----
+#define MVS_CATCH_TO_STATUS                                                                \
+    catch (const mvs::StatusError& e) { return mvs::api_fail(e.st, e.what()); }            \
+    catch (const mvs::HipError& e) { return mvs::api_fail(MVS_ERR_HIP, e.what()); }        \
+    catch (const std::exception& e) { return mvs::api_fail(MVS_ERR_HIP, e.what()); }
+template <class Body>
+mvs_status api_guard(Body&& body) {
+    try { body(); } MVS_CATCH_TO_STATUS
+    return MVS_OK;
+}
+// the same as a bracket around the statements of a function that returns mvs_status; MVS_CTX_API_BEGIN makes ctx->device current first
+#define MVS_API_BEGIN try {
+#define MVS_API_END } MVS_CATCH_TO_STATUS return MVS_OK;
+#define MVS_CTX_API_BEGIN MVS_API_BEGIN MVS_HIP(hipSetDevice(ctx->device));
 }  // namespace mvs

@@ -627,9 +627,6 @@ void sort_by_key30(mvs_ctx* ctx, uint32_t* k_in, uint32_t* k_out, uint32_t* v_in
 }
 }  // namespace
 
-void kd_refine_order(mvs_ctx* ctx, const float* verts, const uint32_t* faces, uint32_t* order, uint32_t F, uint32_t window, uint32_t leaf_window);   // k_kdorder.hip
-void build_scene_order(mvs_ctx* ctx);
-
 // The upper levels of the order report "a cut had more equal keys than its tie list holds" through pinned memory, without a wait of their own
 // (k_kdorder.hip).  Called where the caller synchronises anyway: true = that happened, the order has been rebuilt WITHOUT upper levels (and
 // stays so until another mesh arrives) -- whatever was derived from the order since (BVH, bit matrices) must be derived again.

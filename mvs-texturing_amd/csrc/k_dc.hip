@@ -18,12 +18,6 @@
 
 namespace mvs {
 
-void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const size_t* d_mask_off);
-void build_scene_order(mvs_ctx* ctx);
-bool scene_order_commit(mvs_ctx* ctx);
-void build_bvh(mvs_ctx* ctx);
-void trace_rays(mvs_ctx* ctx);
-
 namespace {
 
 constexpr int VIEW_CHUNK = 32;
@@ -1310,7 +1304,6 @@ void dc_phase2(mvs_ctx* ctx) {
 }
 
 // phase 3: percentile from the (possibly all-reduced) histogram, cost write (:288-298)
-void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax);
 void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats) {
     if (ctx->dc_phase != 2) throw StatusError(MVS_ERR_STATE, "dc_phase3 needs dc_phase2");
     hipStream_t s = ctx->stream;

@@ -8,9 +8,6 @@
 
 namespace mvs {
 
-void build_vertex_faces(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint32_t NV);   // k_bvh.hip
-mvs_status api_fail(mvs_status st, const std::string& msg);
-
 namespace {
 
 constexpr int MAX_NEIGHBOURS = 48;   // distinct neighbours of one face (3 for a manifold mesh); adjacency_kernel: of smaller id and of larger id, each
@@ -181,8 +178,7 @@ uint64_t build_adjacency(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint
     if (F == 0) { MVS_HIP(hipMemsetAsync(ctx->g_adj_ptr.p, 0, 2 * sizeof(uint32_t), s)); ctx->g_adj.ensure(4); return 0; }
     const uint32_t n = 3 * F;
     ctx->g_keys.ensure(n); ctx->g_keys2.ensure(n); ctx->g_vals.ensure(n); ctx->g_vals2.ensure(n); ctx->g_pos.ensure(n); ctx->g_cnt.ensure((size_t)F + 2);
-    ctx->m_moved.ensure(8);
-    uint32_t* overflow = ctx->m_moved.p + 6;     // [0] overflow, [1] edges (a, a)
+    uint32_t* overflow = &ctx->words->adj_overflow;   // [0] overflow, [1] edges (a, a)
     MVS_HIP(hipMemsetAsync(overflow, 0, 2 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(edge_key_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_faces, F, ctx->g_keys.p, ctx->g_vals.p, overflow + 1);
     MVS_LAUNCH_CHECK();
@@ -247,19 +243,12 @@ static bool vertex_ids_in_range(const uint32_t* faces, uint32_t n_faces, uint32_
     return true;
 }
 
-#define MVS_API_BEGIN try { MVS_HIP(hipSetDevice(ctx->device));
-#define MVS_API_END                                                               \
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }           \
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }       \
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); } \
-    return MVS_OK;
-
 extern "C" {
 
 mvs_status mvs_ctx_build_adjacency(mvs_ctx* ctx, uint32_t** adj_ptr_device, uint32_t** adj_device, uint64_t* n_entries) {
     if (!ctx) return api_fail(MVS_ERR_INVALID, "ctx is null");
     if (!ctx->d_faces && ctx->n_faces) return api_fail(MVS_ERR_STATE, "no mesh resident");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     Prof pr(ctx, "build_adjacency");
     const uint64_t n = build_adjacency(ctx, ctx->d_faces, ctx->n_faces, ctx->n_verts);
     pr.end();

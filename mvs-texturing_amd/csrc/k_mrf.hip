@@ -543,9 +543,43 @@ __global__ void __launch_bounds__(256) mrf_ident_kernel(const uint32_t* __restri
         if (gl < 3 && e + gl < e1 && kj[gl] != 0u) ident[e + gl] = (uint8_t)((same >> gl) & 1u);
     }
 }
+
+// ---- the record and descriptor format of the fast nodes: written down here, used by the four set-up kernels below (mrf_recsize_kernel,
+// mrf_record_kernel, mrf_desc_kernel, mrf_record_bits_kernel) and by nothing else -- the sweep kernels decode with arithmetic of their own ----
+// A map byte is the SLOT of the sweep kernel's LDS tile that holds the sender's label: the tile is row-major over r = label mod 4
+// (slot = (at & 3) * G + (at >> 2) for position `at` in the sender's list, G = 8 << class lanes per node), so that the lanes of a
+// group read consecutive banks.  "Label absent at the sender" is the +inf slot 4 * G; for G = 64 the slots fill the byte range
+// 0 .. 254 and 0xFF marks absence (the kernel steers it to slot 256).
+// (a class-1 node -- mrf_sweep8_kernel: 8 lanes x 8 labels -- has the tile row-major over label mod 8: slot = (at & 7) * 8 + (at >> 3),
+//  "absent" = slot 64, and its map sections padded to 8 bytes: its lanes read 8 map bytes at once)
+struct RecLayout {
+    bool w8; uint32_t rs /* row stride of the tile */, none_byte /* "absent" */, lmask, lshift;
+    __device__ __forceinline__ explicit RecLayout(uint32_t cls)
+        : w8(cls == 1u), rs(w8 ? 8u : 8u << cls), none_byte(w8 ? 64u : (cls < 3u ? 4u * rs : 0xFFu)), lmask(w8 ? 7u : 3u), lshift(w8 ? 3u : 2u) {}
+    __device__ __forceinline__ uint32_t slot(uint32_t at) const { return (at & lmask) * rs + (at >> lshift); }                // map byte of position `at`
+    __device__ __forceinline__ uint32_t map_words(uint32_t kj) const { return w8 ? 2u * ((kj + 7u) >> 3) : (kj + 3u) >> 2; }  // words of a map of kj bytes
+};
+__device__ __forceinline__ uint32_t label_word(float c, uint32_t view) { return (cost_code(c) << 16) | view; }
+// The descriptor of fast node i: K labels, record at word rec_off behind REC_BASE (none for an empty column), and per slot d < 3 the edge
+// words m[d], "identical label lists" ident[d], the neighbour nb[d] (the node itself where there is none: a valid index, masked by kj = 0
+// wherever it is used) and "that neighbour has a lower colour" low[d].  An edge that is not in the model (beyond the degree, an empty
+// column at either end) gets kj = 0 and the offsets of the reserved zero run.
+__device__ __forceinline__ NodeDesc make_desc(uint32_t i, uint32_t K, uint32_t rec_off, uint32_t deg, const MrfEdge (&m)[3], const uint32_t (&ident)[3],
+                                              const uint32_t (&nb)[3], const uint32_t (&low)[3]) {
+    NodeDesc nd;
+    nd.rec = K ? REC_BASE + rec_off : 0u; nd.id = i; nd.kk = K;
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d) {
+        const bool on = d < deg && K != 0u && m[d].kj != 0u;
+        const uint32_t flag_low = (d < deg && low[d]) ? 1u : 0u, flag_ident = (on && ident[d]) ? 1u : 0u;
+        nd.in_off[d] = (on ? m[d].in_off : 0u) | flag_low; nd.out_off[d] = (on ? m[d].out_off : 0u) | flag_ident;
+        nd.kk |= (on ? m[d].kj : 0u) << (8 + 8 * d); nd.nbr[d] = nb[d];
+    }
+    return nd;
+}
+
 // rsz[q] = words of the record of node perm[q] (rsz[F] = 0)
 // qpos[i] = position of node i in the (colour, id) order (the inverse of perm)
-// (class-1 nodes are swept by mrf_sweep8_kernel, whose lanes read 8 map bytes at once: their map sections are padded to 8 bytes)
 __global__ void mrf_recsize_kernel(const uint32_t* __restrict__ col_ptr, const uint32_t* __restrict__ adj_ptr, const MrfEdge* __restrict__ edge,
                                    const uint8_t* __restrict__ ident, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ perm, uint32_t F,
                                    uint32_t* __restrict__ rsz, uint32_t* __restrict__ qpos) {
@@ -557,14 +591,14 @@ __global__ void mrf_recsize_kernel(const uint32_t* __restrict__ col_ptr, const u
         qpos[i] = q;
         if (K && cls[i] != CLS_GENERIC) {
             w = (K + 3u) & ~3u;
-            const bool w8 = cls[i] == 1u;
+            const RecLayout L(cls[i]);
             const uint32_t e0 = adj_ptr[i], e1 = adj_ptr[i + 1];
             for (uint32_t eb = e0; eb < e1; eb += 4) {       // four edges at a time: independent loads
                 uint32_t kj[4], id[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) { const bool on = eb + t < e1; kj[t] = on ? edge[eb + t].kj : 0u; id[t] = on ? ident[eb + t] : 1u; }
 #pragma unroll
-                for (int t = 0; t < 4; ++t) if (kj[t] && !id[t]) w += w8 ? 2u * ((kj[t] + 7u) >> 3) : (kj[t] + 3u) >> 2;
+                for (int t = 0; t < 4; ++t) if (kj[t] && !id[t]) w += L.map_words(kj[t]);
             }
             w = (w + 3u) & ~3u;
         }
@@ -586,15 +620,7 @@ __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restr
     const uint32_t p0 = col_ptr[i], K = col_ptr[i + 1] - p0;
     const uint32_t ci = cls[i];
     if (K == 0 || ci == CLS_GENERIC) return;
-    // A map byte is the SLOT of the sweep kernel's LDS tile that holds the sender's label: the tile is row-major over r = label mod 4
-    // (slot = (at & 3) * G + (at >> 2) for position `at` in the sender's list, G = 8 << class lanes per node), so that the lanes of a
-    // group read consecutive banks.  "Label absent at the sender" is the +inf slot 4 * G; for G = 64 the slots fill the byte range
-    // 0 .. 254 and 0xFF marks absence (the kernel steers it to slot 256).
-    // (a class-1 node -- mrf_sweep8_kernel: 8 lanes x 8 labels -- has the tile row-major over label mod 8: slot = (at & 7) * 8 + (at >> 3),
-    //  "absent" = slot 64, and its map sections padded to 8 bytes)
-    const bool w8 = ci == 1u;
-    const uint32_t rs = w8 ? 8u : 8u << ci, none_byte = w8 ? 64u : (ci < 3u ? 4u * rs : 0xFFu);
-    const uint32_t lmask = w8 ? 7u : 3u, lshift = w8 ? 3u : 2u;
+    const RecLayout L(ci);
     const uint32_t q = qpos[i];
     uint16_t* tile = s_l[threadIdx.x >> 4];
     uint32_t* out = rec + REC_BASE + roff[q];
@@ -612,7 +638,7 @@ __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restr
     }
     for (uint32_t t = gl; t < K4; t += 16) {
         uint32_t w = 0u;
-        if (t < K) { const uint32_t v = view_id[p0 + t]; tile[t] = (uint16_t)v; w = (cost_code(cost[p0 + t]) << 16) | v; }
+        if (t < K) { const uint32_t v = view_id[p0 + t]; tile[t] = (uint16_t)v; w = label_word(cost[p0 + t], v); }
         out[t] = w;
     }
     uint32_t pos = K4;
@@ -620,7 +646,7 @@ __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restr
     for (uint32_t d = 0; d < 3; ++d) {
         const uint32_t kj = kj3[d];
         if (kj == 0) continue;                                 // group-uniform: not in the model, or identical lists (no map)
-        const uint32_t q0 = q03[d], nw = w8 ? 2u * ((kj + 7u) >> 3) : (kj + 3u) >> 2;
+        const uint32_t q0 = q03[d], nw = L.map_words(kj);
         for (uint32_t wI = gl; wI < nw; wI += 16) {
             // positions of the RECEIVER's labels 4 wI .. 4 wI + 3 in this (the sender's) list: four lower-bound searches in
             // lockstep (the step count depends on K only), so their LDS reads are independent
@@ -638,7 +664,7 @@ __global__ void __launch_bounds__(256) mrf_record_kernel(const uint32_t* __restr
             for (uint32_t r = 0; r < 4; ++r) {
                 // lo = the last candidate position: the key sits there, or one further (beyond the list), or nowhere
                 uint32_t at = lo[r] + (((uint32_t)tile[lo[r]] < key[r]) ? 1u : 0u);
-                const uint32_t byte = (at < K && (uint32_t)tile[at < K ? at : 0u] == key[r]) ? (at & lmask) * rs + (at >> lshift) : none_byte;
+                const uint32_t byte = (at < K && (uint32_t)tile[at < K ? at : 0u] == key[r]) ? L.slot(at) : L.none_byte;
                 word |= byte << (8 * r);
             }
             out[pos + wI] = word;
@@ -653,24 +679,21 @@ __global__ void mrf_desc_kernel(const uint32_t* __restrict__ col_ptr, const uint
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;   // position in the schedule order; the fast nodes come first
     if (q >= n_fast) return;
     const uint32_t i = perm[q];
-    NodeDesc nd;
     const uint32_t k = col_ptr[i + 1] - col_ptr[i];
-    nd.rec = k ? REC_BASE + roff[q] : 0u; nd.id = i; nd.kk = k;
     const uint32_t e0 = adj_ptr[i], deg = adj_ptr[i + 1] - e0, ci = colour[i];
-    for (int d = 0; d < 3; ++d) {
-        MrfEdge m; m.in_off = 0; m.out_off = 0; m.kj = 0;
-        uint32_t flag_ident = 0, flag_low = 0, nb = i;          // absent neighbour: the node itself (a valid index; masked by kj = 0 wherever it is used)
-        if ((uint32_t)d < deg) { nb = adj[e0 + d]; flag_low = (colour[nb] < ci) ? 1u : 0u; }
-        if ((uint32_t)d < deg && k > 0) {
-            m = edge[e0 + d];
+    MrfEdge m[3]; uint32_t idn[3], nb[3], low[3];
+#pragma unroll
+    for (uint32_t d = 0; d < 3; ++d) {
+        m[d].in_off = 0u; m[d].out_off = 0u; m[d].kj = 0u; idn[d] = 0u; low[d] = 0u; nb[d] = i;
+        if (d < deg) { nb[d] = adj[e0 + d]; low[d] = (colour[nb[d]] < ci) ? 1u : 0u; }
+        if (d < deg && k > 0) {
+            m[d] = edge[e0 + d];
             // the message written over out-edge d is aligned with the neighbour's list: identity iff the lists are equal
             // (a symmetric property, so the in-edge's flag serves)
-            if (m.kj && ident[e0 + d]) flag_ident = 1u;
-            if (m.kj == 0) { m.in_off = 0; m.out_off = 0; }    // edge not in the model: the sweep reads the reserved zero run
+            idn[d] = (m[d].kj && ident[e0 + d]) ? 1u : 0u;
         }
-        nd.in_off[d] = m.in_off | flag_low; nd.out_off[d] = m.out_off | flag_ident; nd.kk |= m.kj << (8 + 8 * d); nd.nbr[d] = nb;
     }
-    desc[q] = nd;
+    desc[q] = make_desc(i, k, roff[q], deg, m, idn, nb, low);
 }
 
 // ---- the bitmap route of the two kernels above and of mrf_map_kernel: the same bytes, no neighbour list is read ----
@@ -687,7 +710,7 @@ __device__ __forceinline__ void bitmap_to_tile(unsigned long long word, uint32_t
 // every label of the RECEIVER nb[d] in its list order, the slot of that label in THIS node's list.  The receiver's labels are the set
 // bits of its bitmap in ascending order: lane gl finds the first of its group of four from the word counts (bitmap_select) and walks on
 // from there; the position of view v in the own list is the number of own bits below v (bitmap_rank_word).  Slot formulas, the "absent"
-// byte and the padding are those of mrf_record_kernel -- the records are the same bytes.
+// byte and the padding are RecLayout's, as in mrf_record_kernel -- the records are the same bytes.
 // The group also has everything the node's descriptor is made of (edge words, identity flags, roff[q]) in registers: lane 0 writes it;
 // the neighbours' colours are requested together with the edge words.  Nodes with an empty column have a descriptor and no record.
 __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __restrict__ col_ptr, const uint16_t* __restrict__ view_id, const float* __restrict__ cost,
@@ -705,7 +728,7 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
     const uint32_t p0 = col_ptr[i], K = col_ptr[i + 1] - p0;
     const uint32_t q = qpos[i], ro = roff[q], col_i = colour[i];
     const uint32_t e0 = adj_ptr[i], deg = min(adj_ptr[i + 1] - e0, 3u);
-    MrfEdge m[3]; uint32_t idn[3], nb[3], col_n[3], kj3[3];
+    MrfEdge m[3]; uint32_t idn[3], nb[3], low[3], kj3[3];
 #pragma unroll
     for (uint32_t d = 0; d < 3; ++d) {
         const bool on = d < deg;
@@ -714,9 +737,8 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
     }
 #pragma unroll
     for (uint32_t d = 0; d < 3; ++d) {
-        col_n[d] = colour[nb[d]];
-        if (K == 0u || m[d].kj == 0u) { m[d].in_off = 0u; m[d].out_off = 0u; m[d].kj = 0u; }   // edge not in the model: the sweep reads the reserved zero run
-        kj3[d] = idn[d] ? 0u : m[d].kj;                         // a map only where the lists differ
+        low[d] = (colour[nb[d]] < col_i) ? 1u : 0u;
+        kj3[d] = (K == 0u || idn[d]) ? 0u : m[d].kj;            // a map only where the edge is in the model and the lists differ
     }
     const bool maps = (kj3[0] | kj3[1] | kj3[2]) != 0u;         // group-uniform
     unsigned long long bw[4] = {0ull, 0ull, 0ull, 0ull};
@@ -725,20 +747,9 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
 #pragma unroll
         for (uint32_t d = 0; d < 3; ++d) if (kj3[d]) bw[d + 1] = bits[(size_t)nb[d] * W + gl];
     }
-    if (gl == 0u && q < n_fast) {
-        NodeDesc nd;
-        nd.rec = K ? REC_BASE + ro : 0u; nd.id = i; nd.kk = K;
-#pragma unroll
-        for (uint32_t d = 0; d < 3; ++d) {
-            const uint32_t flag_low = (d < deg && col_n[d] < col_i) ? 1u : 0u, flag_ident = (m[d].kj && idn[d]) ? 1u : 0u;
-            nd.in_off[d] = m[d].in_off | flag_low; nd.out_off[d] = m[d].out_off | flag_ident; nd.kk |= m[d].kj << (8 + 8 * d); nd.nbr[d] = nb[d];
-        }
-        desc[q] = nd;
-    }
+    if (gl == 0u && q < n_fast) desc[q] = make_desc(i, K, ro, deg, m, idn, nb, low);
     if (K == 0u) return;
-    const bool w8 = ci == 1u;
-    const uint32_t rs = w8 ? 8u : 8u << ci, none_byte = w8 ? 64u : (ci < 3u ? 4u * rs : 0xFFu);
-    const uint32_t lmask = w8 ? 7u : 3u, lshift = w8 ? 3u : 2u;
+    const RecLayout L(ci);
     uint32_t* out = rec + REC_BASE + ro;
     const uint32_t K4 = (K + 3u) & ~3u;
     for (uint32_t t = 4u * gl; t < K4; t += 64) {             // (records start at multiples of four words: 16-byte stores)
@@ -752,10 +763,10 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
             for (uint32_t r = 0; r < 4; ++r) c[r] = (r < n) ? cost[at + r] : 0.0f;
         }
         uint4 w;
-        w.x = (cost_code(c[0]) << 16) | v[0];
-        w.y = (n > 1u) ? (cost_code(c[1]) << 16) | v[1] : 0u;
-        w.z = (n > 2u) ? (cost_code(c[2]) << 16) | v[2] : 0u;
-        w.w = (n > 3u) ? (cost_code(c[3]) << 16) | v[3] : 0u;
+        w.x = label_word(c[0], v[0]);
+        w.y = (n > 1u) ? label_word(c[1], v[1]) : 0u;
+        w.z = (n > 2u) ? label_word(c[2], v[2]) : 0u;
+        w.w = (n > 3u) ? label_word(c[3], v[3]) : 0u;
         *reinterpret_cast<uint4*>(out + t) = w;
     }
     uint32_t pos = K4;
@@ -769,10 +780,10 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
         for (uint32_t d = 0; d < 3; ++d) {
             const uint32_t kj = kj3[d];
             if (kj == 0u) continue;                            // group-uniform: not in the model, or identical lists (no map)
-            const uint32_t nw = w8 ? 2u * ((kj + 7u) >> 3) : (kj + 3u) >> 2;
+            const uint32_t nw = L.map_words(kj);
             for (uint32_t wI = gl; wI < nw; wI += 16) {
                 const uint32_t n = 4u * wI;                    // the receiver's labels n .. n + 3
-                uint32_t word = none_byte * 0x01010101u;
+                uint32_t word = L.none_byte * 0x01010101u;
                 if (n < kj) {
                     uint32_t w = 0u;                           // the last word with at most n views below it holds label n
                     for (uint32_t ww = 1u; ww < W; ++ww) w = (t_pre[d + 1][ww] <= n) ? ww : w;
@@ -781,14 +792,14 @@ __global__ void __launch_bounds__(256) mrf_record_bits_kernel(const uint32_t* __
                     word = 0u;
 #pragma unroll
                     for (uint32_t r = 0; r < 4; ++r) {
-                        uint32_t byte = none_byte;
+                        uint32_t byte = L.none_byte;
                         if (n + r < kj) {
                             while (x == 0ull && w + 1u < W) { ++w; x = t_bits[d + 1][w]; }
                             if (x != 0ull) {
                                 const uint32_t p = (uint32_t)__builtin_ctzll(x);
                                 x &= x - 1ull;
                                 const uint32_t at = bitmap_rank_word(t_bits[0][w], t_pre[0][w], p);   // position of that view in the own list
-                                if (at != BITMAP_NONE) byte = (at & lmask) * rs + (at >> lshift);
+                                if (at != BITMAP_NONE) byte = L.slot(at);
                             }
                         }
                         word |= byte << (8 * r);
@@ -1525,10 +1536,11 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
         MVS_HIP(hipMemcpyAsync(&E, ctx->r_adj_ptr + F, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         MVS_HIP(hipStreamSynchronize(s));
     }
-    ctx->m_size.ensure((size_t)E + 2); ctx->m_edge.ensure((size_t)E + 1); ctx->m_moved.ensure(8 + 2 * 64);
+    ctx->m_size.ensure((size_t)E + 2); ctx->m_edge.ensure((size_t)E + 1);
     ctx->m_n_adj = E;
-    uint32_t* maxes = ctx->m_moved.p + 4;
-    MVS_HIP(hipMemsetAsync(ctx->m_moved.p, 0, 8 * sizeof(uint32_t), s));
+    uint32_t* pending = &ctx->words->colour_pending;   // [0] a node is still waiting, [1] a node saw all 64 colours around it
+    uint32_t* maxes = &ctx->words->setup_kmax;         // [0] kmax, [1] degmax, [2] message total, [3] a column is not strictly ascending
+    MVS_HIP(hipMemsetAsync(pending, 0, 6 * sizeof(uint32_t), s));   // the colouring's two words and the four behind them
     MVS_HIP(hipMemsetAsync(ctx->m_size.p, 0, ((size_t)E + 2) * sizeof(uint32_t), s));
     const unsigned nb = (F + 255) / 256;
     // degenerate inputs (fewer than four table entries, no edge at all) take the generic kernel throughout; "mrf_force_generic" is a test hook
@@ -1550,7 +1562,6 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
     ctx->m_colours = 0; ctx->m_sub_begin.assign(N_KEY + 1, 0); ctx->m_n_fast = 0; ctx->m_range_q.clear(); ctx->m_range_nb = ctx->m_range_ne = 0;
     ctx->m_sweep_no = 0; ctx->m_last_phase = 0xFFFFFFFFu;
     if (F) {
-        uint32_t* pending = ctx->m_moved.p + 1;   // [0] a node is still waiting, [1] a node saw all 64 colours around it
         hipLaunchKernelGGL(mrf_colour_init_kernel, dim3(nb), dim3(256), 0, s, ctx->m_colour.p, ctx->m_tmp_a.p /* iota */, F); MVS_LAUNCH_CHECK();
         // a sharded caller hands in the colouring it kept from its first solve (the colours follow from the adjacency alone, which a
         // shard pins at creation, like its layout): no rounds
@@ -1566,7 +1577,6 @@ void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params) {
             if (hp[1]) throw StatusError(MVS_ERR_UNSUPPORTED, "adjacency graph needs more than 64 colours (a node with >= 64 mutually constrained neighbours)");
             if (!hp[0]) break;
         }
-        MVS_HIP(hipMemsetAsync(ctx->m_moved.p, 0, 4 * sizeof(uint32_t), s));
         // stable sort of the node ids by sub-class key: perm = the schedule order; every (colour, class) pair is a contiguous range
         hipLaunchKernelGGL(mrf_sortkey_kernel, dim3(nb), dim3(256), 0, s, ctx->m_colour.p, ctx->m_cls.p, ctx->m_bnd, F, ctx->m_tmp_c.p); MVS_LAUNCH_CHECK();
         size_t tmp_bytes = 0;
@@ -1699,10 +1709,9 @@ void mrf_step(mvs_ctx* ctx, const unsigned long long* energy, const unsigned lon
     hipStream_t s = ctx->stream;
     const mvs_mrf_params& P = ctx->m_params;
     if (!ctx->h_ring) throw StatusError(MVS_ERR_STATE, "mrf step before mrf setup");
-    const uint32_t n = ++ctx->steps_issued, slot = n % mvs_ctx::RING;
+    ++ctx->steps_issued;   // the kernel derives the ring slot and the sequence number from its own step counter (ctl), which mirrors this one
     const unsigned long long* partial = nullptr; uint32_t n_partial = 0;
     if (!energy && !peer_tab) { partial = ctx->m_energy.p + 4; n_partial = ctx->m_energy_from_sweep ? EPART_BLOCKS * std::max<uint32_t>(ctx->m_colours, 1u) : ctx->m_energy_blocks; }
-    (void)n; (void)slot;   // the kernel derives both from its own step counter (ctl), which mirrors ctx->steps_issued
     hipLaunchKernelGGL(mrf_step_kernel, dim3(1), dim3(1024), 0, s, ctx->m_state.p, ctx->m_hist.p, energy, partial, n_partial, ctx->m_energy.p,
                        ctx->d_ring, ctx->d_seq, (uint32_t)mvs_ctx::RING, ctx->m_ctl.p, P.max_sweeps, P.min_sweeps, P.window, P.min_improvement, peer_tab, n_peer, peer_off);
     MVS_LAUNCH_CHECK();
@@ -1955,8 +1964,8 @@ void mrf_exact_costs(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
     // the polish and the region moves keep position / label / unary of the best labeling consistent: derived once per labeling and range
     if (ctx->exact_valid && ctx->exact_nb == nb0 && ctx->exact_ne == ne0) return;
     ctx->exact_valid = true; ctx->exact_nb = nb0; ctx->exact_ne = ne0;
-    MVS_HIP(hipMemsetAsync(ctx->m_moved.p + 6, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(mrf_exact_cost_kernel, dim3((ne0 - nb0 + 255) / 256), dim3(256), 0, ctx->stream, ctx->r_ptr, ctx->r_view, ctx->r_cost, (const uint32_t*)ctx->b_lab, nb0, ne0, ctx->b_sel, ctx->b_cost, ctx->m_moved.p + 6);
+    MVS_HIP(hipMemsetAsync(&ctx->words->exact_foreign, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(mrf_exact_cost_kernel, dim3((ne0 - nb0 + 255) / 256), dim3(256), 0, ctx->stream, ctx->r_ptr, ctx->r_view, ctx->r_cost, (const uint32_t*)ctx->b_lab, nb0, ne0, ctx->b_sel, ctx->b_cost, &ctx->words->exact_foreign);
     MVS_LAUNCH_CHECK();
 }
 
@@ -2005,7 +2014,7 @@ void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
     // full pass would compute.  Sharded callers exchange labels behind the library's back, so they evaluate all.
     // The list's length is read on the device (fixed grid, grid-stride loop): no host round trip between the rounds.
     if (whole && ctx->icm_dirty_valid) {
-        const uint32_t* list = ctx->m_alist.p; const uint32_t* cnt = ctx->m_moved.p + 1;
+        const uint32_t* list = ctx->m_alist.p; const uint32_t* cnt = &ctx->words->icm_cursor;
 #define ICM_L(GG) hipLaunchKernelGGL(mrf_icm_gain_kernel<GG>, dim3(std::max(1u, std::min<unsigned>((n + (256 / GG) - 1) / (256 / GG), 1024u))), dim3(256), 0, ctx->stream, ctx->r_ptr, ctx->r_view, ctx->r_cost, \
                                      ctx->r_adj_ptr, ctx->r_adj, ctx->b_sel, ctx->b_lab, 0u, 0u, ctx->m_gain.p, ctx->m_cand.p, list, cnt)
         if (K <= 8) ICM_L(8); else if (K <= 16) ICM_L(16); else if (K <= 32) ICM_L(32); else ICM_L(64);
@@ -2034,7 +2043,7 @@ void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
     ctx->icm_dirty_valid = whole;   // every gain is current: the next apply starts the list
 }
 void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
-    MVS_HIP(hipMemsetAsync(ctx->m_moved.p, 0, 2 * sizeof(uint32_t), ctx->stream));
+    MVS_HIP(hipMemsetAsync(&ctx->words->icm_n_moved, 0, 2 * sizeof(uint32_t), ctx->stream));   // moved count and list cursor
     if (ne0 <= nb0) return;
     resolve_best(ctx);
     const bool whole = nb0 == 0 && ne0 == ctx->csr_faces;
@@ -2045,17 +2054,17 @@ void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
         alist = ctx->m_alist.p;
     }
     hipLaunchKernelGGL(mrf_icm_apply_kernel, dim3((ne0 - nb0 + 255) / 256), dim3(256), 0, ctx->stream, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->r_adj_ptr, ctx->r_adj,
-                       ctx->m_gain.p, ctx->m_cand.p, ctx->b_sel, ctx->b_lab, ctx->b_cost, nb0, ne0, ctx->m_moved.p, alist, ctx->t_perm);
+                       ctx->m_gain.p, ctx->m_cand.p, ctx->b_sel, ctx->b_lab, ctx->b_cost, nb0, ne0, &ctx->words->icm_n_moved, alist, ctx->t_perm);
     MVS_LAUNCH_CHECK();
 }
 // labels of nodes [nb0, ne0) of the best labeling into d_labels[0 .. ne0 - nb0); out = {bad, unseen}
 // (caller_order: the whole graph's labels at the caller's face ids -- ctx->t_perm; otherwise positions nb0 .. of the table's order)
 void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order) {
-    uint32_t* bu = ctx->m_moved.p + 2;
+    uint32_t* bu = &ctx->words->labels_bad;   // [0] bad, [1] unseen
     resolve_best(ctx);
     MVS_HIP(hipMemsetAsync(bu, 0, 2 * sizeof(uint32_t), ctx->stream));
     if (ne0 > nb0) {
-        const uint32_t* foreign = (ctx->exact_valid && ctx->exact_nb == nb0 && ctx->exact_ne == ne0) ? ctx->m_moved.p + 6 : (const uint32_t*)nullptr;
+        const uint32_t* foreign = (ctx->exact_valid && ctx->exact_nb == nb0 && ctx->exact_ne == ne0) ? &ctx->words->exact_foreign : (const uint32_t*)nullptr;
         hipLaunchKernelGGL(mrf_labels_kernel, dim3((ne0 - nb0 + 255) / 256), dim3(256), 0, ctx->stream, ctx->b_lab, nb0, ne0, ctx->csr_views, d_labels, bu, caller_order ? ctx->t_perm : (const uint32_t*)nullptr, foreign);
         MVS_LAUNCH_CHECK();
     }

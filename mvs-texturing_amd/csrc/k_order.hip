@@ -14,9 +14,6 @@
 #include "ctx.h"
 
 namespace mvs {
-void build_scene_order(mvs_ctx* ctx);
-bool scene_order_commit(mvs_ctx* ctx);
-mvs_status api_fail(mvs_status st, const std::string& msg);
 
 namespace {
 
@@ -104,13 +101,6 @@ void adjacency_to_table_order(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uin
 }  // namespace mvs
 
 using namespace mvs;
-
-#define MVS_API_BEGIN try {
-#define MVS_API_END                                                               \
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }           \
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }       \
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); } \
-    return MVS_OK;
 
 static void equal_cut(uint32_t F, int world, uint32_t* part_begin) {
     for (int q = 0; q <= world; ++q) part_begin[q] = (uint32_t)(((uint64_t)F * (uint64_t)q) / (uint64_t)world);

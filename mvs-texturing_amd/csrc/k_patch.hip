@@ -15,8 +15,6 @@
 
 namespace mvs {
 
-mvs_status api_fail(mvs_status st, const std::string& msg);
-
 namespace {
 
 __device__ inline uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -168,8 +166,7 @@ uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* 
     const unsigned nb = (F + 255) / 256;
     ctx->p_parent.ensure((size_t)F + 1); ctx->p_root.ensure((size_t)F + 1); ctx->p_state.ensure((size_t)F + 1);
     ctx->p_flag.ensure((size_t)F + 2); ctx->p_pos.ensure((size_t)F + 2);
-    ctx->m_moved.ensure(8);
-    uint32_t* bad = ctx->m_moved.p + 7;
+    uint32_t* bad = &ctx->words->patch_bad;
     MVS_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), s));
     hipLaunchKernelGGL(cc_check_labels_kernel, dim3(nb), dim3(256), 0, s, d_labels, F, n_labels, bad); MVS_LAUNCH_CHECK();
     hipLaunchKernelGGL(cc_init_kernel, dim3(nb), dim3(256), 0, s, ctx->p_parent.p, ctx->p_state.p, F); MVS_LAUNCH_CHECK();
@@ -213,8 +210,7 @@ extern "C" {
 mvs_status mvs_ctx_get_subgraphs(mvs_ctx* ctx, uint32_t n_faces, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device,
                                  const uint32_t* labels, int labels_on_device, uint32_t n_labels, mvs_subgraphs* out, int out_on_device) {
     if (!ctx || !out || (n_faces && (!adj_ptr || !adj || !labels))) return api_fail(MVS_ERR_INVALID, "null argument");
-    try {
-        MVS_HIP(hipSetDevice(ctx->device));
+    MVS_CTX_API_BEGIN
         hipStream_t s = ctx->stream;
         const uint32_t* d_adj_ptr = adj_ptr; const uint32_t* d_adj = adj; const uint32_t* d_labels = labels;
         if (!adj_on_device && n_faces) {
@@ -245,10 +241,7 @@ mvs_status mvs_ctx_get_subgraphs(mvs_ctx* ctx, uint32_t n_faces, const uint32_t*
             if (n_faces) MVS_HIP(hipMemcpyAsync(out->comp_faces, ctx->p_comp_faces.p, (size_t)n_faces * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             MVS_HIP(hipStreamSynchronize(s));
         }
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
+    MVS_API_END
 }
 
 mvs_status mvs_get_subgraphs(uint32_t n_faces, const uint32_t* adj_ptr, const uint32_t* adj, const uint32_t* labels, uint32_t n_labels, mvs_subgraphs* out) {

@@ -16,7 +16,6 @@
 #include <rocprim/rocprim.hpp>
 
 namespace mvs {
-void resolve_best(mvs_ctx* ctx);
 
 namespace {
 
@@ -243,12 +242,12 @@ uint32_t mrf_region_round(mvs_ctx* ctx) {
         name = ctx->rg_name.p;
     }
     hipLaunchKernelGGL(rg_lose_kernel, dim3((n_cut + 255) / 256), dim3(256), 0, s, ctx->rg_cut.p, n_cut, ctx->rg_root.p, ctx->rg_gain.p, name, ctx->rg_lose.p); MVS_LAUNCH_CHECK();
-    ctx->m_moved.ensure(8 + 2 * 64);
-    MVS_HIP(hipMemsetAsync(ctx->m_moved.p + 7, 0, sizeof(uint32_t), s));
+    uint32_t* moved = &ctx->words->region_moved;
+    MVS_HIP(hipMemsetAsync(moved, 0, sizeof(uint32_t), s));
     hipLaunchKernelGGL(rg_apply_kernel, dim3(nb), dim3(256), 0, s, ctx->r_ptr, ctx->r_view, ctx->r_cost, ctx->rg_root.p, ctx->rg_gain.p, ctx->rg_bestl.p, ctx->rg_lose.p, F,
-                       ctx->b_sel, ctx->b_lab, ctx->b_cost, ctx->m_moved.p + 7); MVS_LAUNCH_CHECK();
+                       ctx->b_sel, ctx->b_lab, ctx->b_cost, moved); MVS_LAUNCH_CHECK();
     ctx->icm_dirty_valid = false;   // labels changed behind the ICM's active list
-    return read_u32(ctx, ctx->m_moved.p + 7);
+    return read_u32(ctx, moved);
 }
 
 }  // namespace mvs

@@ -13,8 +13,6 @@
 
 namespace mvs {
 
-uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, uint32_t F, uint32_t n_labels);
-
 namespace {
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 enum { F_LABEL = 0, F_VERTEX, F_BOX, F_N };   // flag words of PatchTables

@@ -7,20 +7,6 @@
 #include <vector>
 
 namespace mvs {
-void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params);
-void mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_energy(mvs_ctx* ctx, bool best, uint32_t nb0, uint32_t ne0, bool reduce = true);
-void mrf_keep_best(mvs_ctx* ctx);
-void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part = MRF_PART_ALL);
-void mrf_step(mvs_ctx* ctx, const unsigned long long* energy, const unsigned long long* const* peer_tab = nullptr, uint32_t n_peer = 0, uint32_t peer_off = 0);
-void mrf_poll(mvs_ctx* ctx, uint32_t step, mvs_mrf_progress* out);
-void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order = false);
-void resolve_best(mvs_ctx* ctx);
-void set_adjacency(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int on_device, bool table_order);
-mvs_status api_fail(mvs_status st, const std::string& msg);
-
 namespace {
 // st != null: the array is the CURRENT decode buffer, i.e. offset st->w * buf_stride (the step kernel flips w on the device)
 __global__ void gather_kernel(const uint32_t* __restrict__ src, const mvs_mrf_progress* __restrict__ st, uint32_t buf_stride, const uint32_t* __restrict__ idx, uint64_t n, uint32_t* __restrict__ dst) {
@@ -75,40 +61,33 @@ static uint32_t* mrf_array(mvs_ctx* ctx, int which, const mvs_mrf_progress** st)
 
 using namespace mvs;
 
-#define MVS_API_BEGIN try { MVS_HIP(hipSetDevice(ctx->device));
-#define MVS_API_END                                                               \
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }           \
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }       \
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); } \
-    return MVS_OK;
-
 extern "C" {
 
 mvs_status mvs_ctx_dc_get_max(mvs_ctx* ctx, float* dst) {
     if (!ctx || !dst) return api_fail(MVS_ERR_INVALID, "null argument");
     if (ctx->dc_phase < 1) return api_fail(MVS_ERR_STATE, "dc_phase1 first");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     MVS_HIP(hipMemcpyAsync(dst, ctx->max_q.p, sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
 }
 mvs_status mvs_ctx_dc_set_max(mvs_ctx* ctx, const float* src) {
     if (!ctx || !src) return api_fail(MVS_ERR_INVALID, "null argument");
     if (ctx->dc_phase < 1) return api_fail(MVS_ERR_STATE, "dc_phase1 first");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     MVS_HIP(hipMemcpyAsync(ctx->max_q.p, src, sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
 }
 mvs_status mvs_ctx_dc_get_histogram(mvs_ctx* ctx, uint32_t* dst) {
     if (!ctx || !dst) return api_fail(MVS_ERR_INVALID, "null argument");
     if (ctx->dc_phase < 2) return api_fail(MVS_ERR_STATE, "dc_phase2 first");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     MVS_HIP(hipMemcpyAsync(dst, ctx->hist.p, MVS_HIST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
 }
 mvs_status mvs_ctx_dc_set_histogram(mvs_ctx* ctx, const uint32_t* src) {
     if (!ctx || !src) return api_fail(MVS_ERR_INVALID, "null argument");
     if (ctx->dc_phase < 2) return api_fail(MVS_ERR_STATE, "dc_phase2 first");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     MVS_HIP(hipMemcpyAsync(ctx->hist.p, src, MVS_HIST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
 }
@@ -116,7 +95,7 @@ mvs_status mvs_ctx_dc_set_histogram(mvs_ctx* ctx, const uint32_t* src) {
 mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts, uint16_t* view_id, float* cost) {
     if (!ctx || !counts) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "no data costs on the device");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     const uint32_t F = ctx->csr_faces;
     if (F) { hipLaunchKernelGGL(counts_kernel, dim3((F + 255) / 256), dim3(256), 0, ctx->stream, ctx->r_ptr, F, counts); MVS_LAUNCH_CHECK(); }
     if (ctx->csr_nnz && view_id) MVS_HIP(hipMemcpyAsync(view_id, ctx->r_view, ctx->csr_nnz * sizeof(uint16_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -136,7 +115,7 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
     // after a ranged pass (k_dc.hip dc_ranged) the matrices hold the LAST range's rays only
     if (which < 2 && ctx->dc_n_ranges > 1)
         return api_fail(MVS_ERR_STATE, "ray bits: the last data-cost pass evaluated the faces in " + std::to_string(ctx->dc_n_ranges) + " ranges (option dc_range_pairs); the matrices hold the last range only");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     const uint32_t NV = ctx->n_verts, V = ctx->n_views, vwords = (NV + 63) / 64;
     const uint64_t words = (uint64_t)V * vwords, n = which == 2 ? (uint64_t)NV * sizeof(uint32_t) : words * sizeof(unsigned long long);
     *n_bytes = n;
@@ -170,7 +149,7 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
 mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mvs_mrf_params P; if (params) P = *params; else mvs_mrf_default_params(&P);
     set_adjacency(ctx, adj_ptr, adj, adj_on_device, false);
     mrf_setup(ctx, &P);
@@ -179,7 +158,7 @@ mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32
 
 mvs_status mvs_ctx_mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
     if (!ctx || nb0 > ne0 || ne0 > ctx->csr_faces) return api_fail(MVS_ERR_INVALID, "bad node range");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     Prof pr(ctx, "mrf_sweep");
     mrf_sweep(ctx, nb0, ne0);
     MVS_API_END
@@ -187,7 +166,7 @@ mvs_status mvs_ctx_mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
 
 mvs_status mvs_ctx_mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0) {
     if (!ctx || nb0 > ne0 || ne0 > ctx->csr_faces || phase >= ctx->m_colours) return api_fail(MVS_ERR_INVALID, "bad phase or node range");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     Prof pr(ctx, "mrf_sweep");
     mrf_sweep_phase(ctx, phase, nb0, ne0);
     MVS_API_END
@@ -197,7 +176,7 @@ mvs_status mvs_ctx_mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, u
 mvs_status mvs_ctx_mrf_setup_marked(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params, const uint8_t* marks_device) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mvs_mrf_params P; if (params) P = *params; else mvs_mrf_default_params(&P);
     set_adjacency(ctx, adj_ptr, adj, adj_on_device, false);
     struct Marks { mvs_ctx* c; ~Marks() { c->m_bnd = nullptr; } } marks{ctx};
@@ -207,7 +186,7 @@ mvs_status mvs_ctx_mrf_setup_marked(mvs_ctx* ctx, const uint32_t* adj_ptr, const
 }
 mvs_status mvs_ctx_mrf_sweep_phase_part(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part) {
     if (!ctx || nb0 > ne0 || ne0 > ctx->csr_faces || phase >= ctx->m_colours || part < 0 || part > 2) return api_fail(MVS_ERR_INVALID, "bad phase, node range or part");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     Prof pr(ctx, part == MRF_PART_BOUNDARY ? "mrf_sweep_boundary" : "mrf_sweep");
     mrf_sweep_phase(ctx, phase, nb0, ne0, part);
     MVS_API_END
@@ -215,7 +194,7 @@ mvs_status mvs_ctx_mrf_sweep_phase_part(mvs_ctx* ctx, uint32_t phase, uint32_t n
 mvs_status mvs_ctx_mrf_setup_tables(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
     if (!ctx || !n_bytes || which < 0 || which > 3) return api_fail(MVS_ERR_INVALID, "bad argument");
     if (!ctx->m_state.p) return api_fail(MVS_ERR_STATE, "mrf setup first");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     const uint32_t F = ctx->csr_faces, n_fast = ctx->m_n_fast;
     const void* src = nullptr; uint64_t n = 0, route = ctx->m_bitmaps ? 1u : 0u;
     if (which == 0) { n = sizeof(route); }
@@ -237,7 +216,7 @@ mvs_status mvs_ctx_mrf_setup_tables(mvs_ctx* ctx, int which, void* out_host, uin
 }
 mvs_status mvs_ctx_mrf_layout(mvs_ctx* ctx, uint32_t* in_off_host, uint64_t n_edges) {
     if (!ctx || (n_edges && !in_off_host)) return api_fail(MVS_ERR_INVALID, "null argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     // MrfEdge = {in_off, out_off, kj}: strided copy of the first member
     if (n_edges) MVS_HIP(hipMemcpy2DAsync(in_off_host, sizeof(uint32_t), ctx->m_edge.p, sizeof(MrfEdge), sizeof(uint32_t), n_edges, hipMemcpyDeviceToHost, ctx->stream));
     MVS_HIP(hipStreamSynchronize(ctx->stream));
@@ -246,7 +225,7 @@ mvs_status mvs_ctx_mrf_layout(mvs_ctx* ctx, uint32_t* in_off_host, uint64_t n_ed
 
 mvs_status mvs_ctx_mrf_gather(mvs_ctx* ctx, int which, const uint32_t* idx, uint64_t n, void* dst) {
     if (!ctx || (n && (!idx || !dst))) return api_fail(MVS_ERR_INVALID, "null argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     if (n && which == MVS_MRF_MSG_LAB) {
         if (ctx->m_total >= 0x80000000ull) throw StatusError(MVS_ERR_UNSUPPORTED, "combined addressing needs < 2^31 message words");
         hipLaunchKernelGGL(gather2_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream, mrf_msg(ctx), ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, idx, n, (uint32_t*)dst);
@@ -263,7 +242,7 @@ mvs_status mvs_ctx_mrf_gather(mvs_ctx* ctx, int which, const uint32_t* idx, uint
 }
 mvs_status mvs_ctx_mrf_scatter(mvs_ctx* ctx, int which, const uint32_t* idx, uint64_t n, const void* src) {
     if (!ctx || (n && (!idx || !src))) return api_fail(MVS_ERR_INVALID, "null argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     if (n) { ctx->icm_dirty_valid = false; ctx->exact_valid = false; }   // labels changed behind the ICM active set
     if (n && which == MVS_MRF_MSG_LAB) {
         hipLaunchKernelGGL(scatter2_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream, mrf_msg(ctx), ctx->m_lab.p, ctx->m_state.p, ctx->m_stride, idx, n, (const uint32_t*)src);
@@ -282,7 +261,7 @@ mvs_status mvs_ctx_mrf_scatter(mvs_ctx* ctx, int which, const uint32_t* idx, uin
 mvs_status mvs_ctx_mrf_energy(mvs_ctx* ctx, int which_sel, uint32_t nb0, uint32_t ne0, uint64_t* dst) {
     if (!ctx || !dst || nb0 > ne0 || ne0 > ctx->csr_faces) return api_fail(MVS_ERR_INVALID, "bad argument");
     if (which_sel != MVS_MRF_LAB && which_sel != MVS_MRF_BEST_LAB) return api_fail(MVS_ERR_INVALID, "energy: LAB or BEST_LAB");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_energy(ctx, which_sel == MVS_MRF_BEST_LAB, nb0, ne0);
     MVS_HIP(hipMemcpyAsync(dst, ctx->m_energy.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
@@ -290,41 +269,41 @@ mvs_status mvs_ctx_mrf_energy(mvs_ctx* ctx, int which_sel, uint32_t nb0, uint32_
 
 mvs_status mvs_ctx_mrf_keep_best(mvs_ctx* ctx) {
     if (!ctx) return api_fail(MVS_ERR_INVALID, "ctx is null");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_keep_best(ctx);
     MVS_API_END
 }
 
 mvs_status mvs_ctx_mrf_step(mvs_ctx* ctx, const uint64_t* energy_device) {
     if (!ctx) return api_fail(MVS_ERR_INVALID, "ctx is null");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_step(ctx, (const unsigned long long*)energy_device);
     MVS_API_END
 }
 mvs_status mvs_ctx_mrf_poll(mvs_ctx* ctx, uint32_t step, mvs_mrf_progress* out) {
     if (!ctx || !out) return api_fail(MVS_ERR_INVALID, "null argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_poll(ctx, step, out);
     MVS_API_END
 }
 
 mvs_status mvs_ctx_mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0) {
     if (!ctx || nb0 > ne0 || ne0 > ctx->csr_faces) return api_fail(MVS_ERR_INVALID, "bad node range");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_icm_gain(ctx, nb0, ne0);
     MVS_API_END
 }
 mvs_status mvs_ctx_mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* moved) {
     if (!ctx || !moved || nb0 > ne0 || ne0 > ctx->csr_faces) return api_fail(MVS_ERR_INVALID, "bad argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     mrf_icm_apply(ctx, nb0, ne0);  // in place: winners form an independent set
-    MVS_HIP(hipMemcpyAsync(moved, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    MVS_HIP(hipMemcpyAsync(moved, &ctx->words->icm_n_moved, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     MVS_API_END
 }
 
 mvs_status mvs_ctx_mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* labels, uint32_t* unseen_out) {
     if (!ctx || !labels || nb0 > ne0 || ne0 > ctx->csr_faces) return api_fail(MVS_ERR_INVALID, "bad argument");
-    MVS_API_BEGIN
+    MVS_CTX_API_BEGIN
     uint32_t bu[2];
     mrf_labels(ctx, nb0, ne0, labels, bu);
     if (unseen_out) *unseen_out = bu[1];

@@ -7,8 +7,6 @@
 
 namespace mvs {
 
-mvs_status api_fail(mvs_status st, const std::string& msg);   // api.hip: records the message of mvs_last_error
-
 inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }   // blocks of 256 threads, at least one
 
 // ---- copies (all asynchronous on `s`: the caller drains the stream before the host side goes away) ----
@@ -73,15 +71,7 @@ struct StageTimer {
     float ms(int a, int b) const { float t = 0.0f; MVS_HIP(hipEventElapsedTime(&t, ev[a], ev[b])); return t; }
 };
 
-// ---- around the body of an entry point ----
-template <class Body>
-mvs_status api_guard(Body&& body) {   // what the body throws becomes the call's status and the message of mvs_last_error
-    try { body(); }
-    catch (const StatusError& e) { return api_fail(e.st, e.what()); }
-    catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); }
-    return MVS_OK;
-}
+// ---- around the body of an entry point (api_guard: ctx.h) ----
 // the row itself: `st` reaches the caller's stats whether run() returns or throws (after a throw the stream is drained first)
 template <class Stats, class Run>
 void run_with_stats(hipStream_t s, Stats* stats, const Stats& st, Run&& run) {

@@ -33,29 +33,6 @@
 #include <mutex>
 #include <thread>
 
-namespace mvs {
-void dc_phase1(mvs_ctx* ctx, const mvs_settings* st);
-void dc_phase2(mvs_ctx* ctx);
-void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats);
-void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params);
-void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part = MRF_PART_ALL);
-void mrf_sweep_energy_reduce(mvs_ctx* ctx, unsigned long long* out2 = nullptr);
-void mrf_energy(mvs_ctx* ctx, bool best, uint32_t nb0, uint32_t ne0, bool reduce = true);
-void mrf_exact_costs(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_step(mvs_ctx* ctx, const unsigned long long* energy, const unsigned long long* const* peer_tab = nullptr, uint32_t n_peer = 0, uint32_t peer_off = 0);
-void mrf_poll(mvs_ctx* ctx, uint32_t step, mvs_mrf_progress* out);
-void mrf_icm_gain(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);
-void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order = false);
-void resolve_best(mvs_ctx* ctx);
-void set_adjacency(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int on_device, bool table_order);
-void build_scene_order(mvs_ctx* ctx);
-bool scene_order_commit(mvs_ctx* ctx);
-void renumber_adjacency(mvs_ctx* ctx, uint32_t F, const uint32_t* perm, const uint32_t* pos, const uint32_t* d_adj_ptr, const uint32_t* d_adj, size_t E,
-                        DBuf<uint32_t>& out_ptr, DBuf<uint32_t>& out_adj);
-mvs_status api_fail(mvs_status st, const std::string& msg);
-}  // namespace mvs
-
 using namespace mvs;
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -587,7 +564,7 @@ struct Exchange : Transport {
         mrf_icm_gain(ctx, S->nb, S->ne);
         if (S->P > 1) nodes(S, (uint32_t*)ctx->m_gain.p);
         mrf_icm_apply(ctx, S->nb, S->ne);
-        MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        MVS_HIP(hipMemcpyAsync(S->d_moved.p, &ctx->words->icm_n_moved, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
         if (S->P > 1) { S->comm->allreduce(S->d_moved.p, 1, mvs_comm::U32, mvs_comm::SUM, ctx->stream); nodes(S, ctx->b_lab); }
     }
     // gains, or labels of the best labeling (ICM; the halo labels of the argmin-unary start)
@@ -719,7 +696,7 @@ struct PeerPush : Transport {
         mrf_icm_apply(ctx, S->nb, S->ne);
         push_nodes(S, ctx->b_lab, true);
         const uint32_t parity = (uint32_t)(k & 1);
-        hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)ctx->m_moved.p, m_pub.p, parity); MVS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(publish_word_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)&ctx->words->icm_n_moved, m_pub.p, parity); MVS_LAUNCH_CHECK();
         const uint64_t im = record(S);
         WordPtrs wp; wp.n = S->P;
         for (int q = 0; q < S->P; ++q) { if (q != S->me) wait(S, q, im); wp.p[q] = H.slot[q].moved; }
@@ -899,13 +876,6 @@ void build_plan(mvs_shard* S) {
 }
 
 }  // namespace
-
-#define MVS_API_BEGIN try {
-#define MVS_API_END                                                               \
-    } catch (const StatusError& e) { return api_fail(e.st, e.what()); }           \
-      catch (const HipError& e) { return api_fail(MVS_ERR_HIP, e.what()); }       \
-      catch (const std::exception& e) { return api_fail(MVS_ERR_HIP, e.what()); } \
-    return MVS_OK;
 
 extern "C" {
 
@@ -1249,7 +1219,7 @@ mvs_status mvs_shard_view_selection(mvs_shard* S, const mvs_mrf_params* params, 
     R.energy_fixed = e[0]; R.energy = (double)e[0] / 4294967296.0; R.cut_edges = e[1];
     uint32_t bu[2];
     mrf_labels(ctx, nb, ne, labels_own_device, bu);
-    MVS_HIP(hipMemcpyAsync(S->d_moved.p, ctx->m_moved.p + 2, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    MVS_HIP(hipMemcpyAsync(S->d_moved.p, &ctx->words->labels_bad, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (S->P > 1) comm->allreduce(S->d_moved.p, 2, mvs_comm::U32, mvs_comm::SUM, s);
     MVS_HIP(hipMemcpyAsync(bu, S->d_moved.p, sizeof(bu), hipMemcpyDeviceToHost, s));
     MVS_HIP(hipStreamSynchronize(s));
