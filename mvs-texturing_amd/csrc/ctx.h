@@ -54,7 +54,7 @@ struct DBuf {
     DBuf& operator=(const DBuf&) = delete;
 };
 
-// Growable PINNED host buffer (device-to-host staging of the streamed table download, api.hip)
+// Growable PINNED host buffer (device-to-host staging of the streamed table download, oneshot.hip)
 template <class T>
 struct HBuf {
     T* p = nullptr;
@@ -213,7 +213,7 @@ struct mvs_ctx {
     const uint32_t* t_perm = nullptr; const uint32_t* t_pos = nullptr;
     mvs::DBuf<uint32_t> u_ptr, u_cnt; mvs::DBuf<uint16_t> u_view; mvs::DBuf<float> u_cost, u_q;   // the table in the caller's order (built on demand)
     bool u_valid = false, u_q_valid = false;
-    mvs::DBuf<unsigned long long> fp_acc;   // device-side fingerprint of the table handed out (api.hip mvs_data_costs_stream)
+    mvs::DBuf<unsigned long long> fp_acc;   // device-side fingerprint of the table handed out (oneshot.hip mvs_data_costs_stream)
     mvs::HBuf<uint32_t> stage_ptr; mvs::HBuf<uint16_t> stage_view[2]; mvs::HBuf<float> stage_cost[2];   // pinned staging of the chunked download
 
     // ---- BVH + incidence ----
@@ -306,7 +306,7 @@ struct mvs_ctx {
     static constexpr uint32_t ICM_RING = 8;
     uint32_t* h_icm = nullptr; uint32_t* d_icm = nullptr; uint32_t icm_seq = 0;   // pinned "moved" counts of the ICM rounds, read a few rounds late
     mvs::DBuf<mvs_mrf_progress> m_state; mvs::DBuf<unsigned long long> m_hist; mvs::DBuf<uint32_t> m_ctl;   // m_ctl: {steps of the solve, sequence base} read by the step kernel
-    // the sweep loop as a replayed hipGraph (api.hip): one damping period, MRF_DAMP_PERIOD sweeps + their bookkeeping steps, captured on a
+    // the sweep loop as a replayed hipGraph (solve.hip): one damping period, MRF_DAMP_PERIOD sweeps + their bookkeeping steps, captured on a
     // private stream, launched on the context's stream; re-captured per solve and pushed into the instantiated graph with hipGraphExecUpdate
     int mrf_graph = 1; hipStream_t cap_stream = nullptr; hipGraphExec_t sweep_exec = nullptr; uint32_t graph_launches = 0, graph_updates = 0, graph_instantiations = 0;
     mvs_mrf_progress* h_ring = nullptr; mvs_mrf_progress* d_ring = nullptr /* the same pinned slots as the device addresses them */; uint32_t steps_issued = 0; int mrf_lag = 1;
@@ -351,6 +351,8 @@ struct ProfChain {
 struct RoctxRange { explicit RoctxRange(const char* name); ~RoctxRange(); bool on; };
 // device for the one-shot host entry points (mvs_data_costs, mvs_view_selection, ...): environment MVS_DEVICE, default 0
 int default_device();
+// option "dc_range_pairs" as the environment sets it (MVS_DC_RANGE_PAIRS, 0 when unset): for a new context and for every one-shot call
+uint64_t env_dc_range_pairs();
 // which zone(s) of a colour phase mrf_sweep_phase sweeps (k_mrf.hip)
 enum { MRF_PART_ALL = 0, MRF_PART_BOUNDARY = 1, MRF_PART_INTERIOR = 2 };
 // reports through pinned host memory (k_mrf.hip)
@@ -398,6 +400,9 @@ void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr,
 mvs_status api_fail(mvs_status st, const std::string& msg);   // records the message of mvs_last_error, returns st
 // the caller's adjacency lists (host or device) as ctx->r_adj_ptr / r_adj in the order of the active table; table_order: they already are
 void set_adjacency(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int on_device, bool table_order);
+void release_upload_rings();   // frees the pinned upload ring of every device (mvs_release_cached; the next host-image upload allocates again)
+// solve.hip
+void sweep_graph_release(mvs_ctx* ctx);   // destroys the sweep loop's executable graph and capture stream
 // k_prep.hip
 void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const size_t* d_mask_off);   // image preparation of all views (ctx->d_views uploaded)
 void undistort_image(mvs_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, double flen, double d0, double d1);

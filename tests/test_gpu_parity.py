@@ -418,7 +418,7 @@ def test_mrf_mixed_node_classes_in_one_graph(seed):
 
 
 def test_sweep_loop_as_a_replayed_graph_equals_direct_launches():
-    """the sweep loop replayed from a hipGraph (one period of the damping schedule = four sweeps + their steps per launch; api.hip
+    """the sweep loop replayed from a hipGraph (one period of the damping schedule = four sweeps + their steps per launch; solve.hip
     prepare_sweep_graph) against direct launches and the oracle: same labels, energy, sweep count; the second solve on the context
     updates the executable graph instead of instantiating a new one; a max_sweeps that is no multiple of four ends with directly
     launched sweeps; a mixed-class instance (another graph topology) after a uniform one re-instantiates."""
@@ -528,6 +528,132 @@ def test_one_shot_calls_keep_the_table_on_the_device():
     assert np.array_equal(l3, lm) and e3 == sm["energy_fixed"] and old > 0.5
     L.mvs_csr_free(C.byref(out))
     L.mvs_release_cached()
+
+
+def _one_shot_inputs(s, width=None):
+    """(mesh, views, keep-alive) for mvs_data_costs on the scene's host arrays; width: ONE view (the first) claiming that image width"""
+    mesh = M.viewsel.CMesh(s.verts.shape[0], s.n_faces, s.verts.ctypes.data, s.faces.ctypes.data, s.normals.ctypes.data)
+    n = s.n_views if width is None else 1
+    views = (M.viewsel.CView * n)()
+    for j in range(n):
+        v = views[j]
+        v.pos[:] = s.cams["pos"][j].tolist(); v.viewdir[:] = s.cams["viewdir"][j].tolist()
+        v.K[:] = s.cams["K"][j].tolist(); v.w2c[:] = s.cams["w2c"][j].tolist()
+        v.width, v.height, v.rgb = int(s.cams["width"][j]) if width is None else width, int(s.cams["height"][j]), s.images[j].ctypes.data
+    return mesh, views, n
+
+
+def _table_fingerprint(n_faces, n_views, col_ptr, view_id, cost):
+    """the fingerprint of a table as include/mvs_viewsel.h defines it (mvs_fp_mix summed modulo 2^64)"""
+    def mix(k, v):
+        k = np.asarray(k, np.uint64).reshape(-1); v = np.asarray(v, np.uint64).reshape(-1)
+        x = (k * np.uint64(0x9E3779B97F4A7C15)) ^ (v + np.uint64(0x7F4A7C15D6E8FEB8))
+        x ^= x >> np.uint64(29); x *= np.uint64(0xBF58476D1CE4E5B9); x ^= x >> np.uint64(32)
+        return int(x.sum(dtype=np.uint64))
+    n = len(view_id)
+    h = mix([n_faces], [n_views]) + mix([n], [1]) + mix(np.arange(n_faces, dtype=np.uint64), col_ptr[1:])
+    h += mix(np.uint64(1 << 40) + np.arange(n, dtype=np.uint64), (view_id.astype(np.uint64) << np.uint64(32)) | cost.view(np.uint32).astype(np.uint64))
+    return h & 0xFFFFFFFFFFFFFFFF
+
+
+_PROFILE_KEYS = {
+    "mvs_data_costs": ["call", "ctx_ms", "mesh_h2d_ms", "images_h2d_ms", "compute_ms", "download_ms", "fingerprint_ms", "dc_ranges", "table_kept_on_device"],
+    "mvs_data_costs_stream": ["call", "ctx_ms", "mesh_h2d_ms", "images_h2d_ms", "compute_ms", "first_chunk_ms", "chunks_and_callbacks_ms", "fingerprint", "dc_ranges",
+                              "table_kept_on_device"],
+    "mvs_view_selection": ["call", "fingerprint_ms", "ctx_and_table_upload_ms", "solve_ms", "table_reused_on_device"],
+    "mvs_view_selection_cached": ["call", "lookup_ms", "solve_ms", "table_reused_on_device"],
+}
+
+
+def _last_call_profile(L, call):
+    """the profile of the last one-shot call: it is `call`'s, with exactly that call's keys in their order"""
+    import json
+    prof = json.loads(L.mvs_last_call_profile().decode())
+    assert prof["call"] == call and list(prof) == _PROFILE_KEYS[call], prof
+    return prof
+
+
+def test_one_shot_calls_with_the_stash_switched_off():
+    """MVS_KEEP_TABLE=0: mvs_data_costs keeps nothing on the device, mvs_view_selection uploads the table (and labels like the oracle),
+    mvs_view_selection_cached finds no parked table even under the table's own fingerprint"""
+    s = get_scene("tiny")
+    L = M.load_library()
+    ref, _ = O.data_costs(s)
+    lo, so = O.view_selection(ref, s.adj_ptr, s.adj)
+    L.mvs_release_cached()
+    before = os.environ.get("MVS_KEEP_TABLE")
+    os.environ["MVS_KEEP_TABLE"] = "0"
+    try:
+        mesh, views, n = _one_shot_inputs(s)
+        out = M.viewsel.CCsr(); st = M.Settings()
+        assert L.mvs_data_costs(C.byref(mesh), views, n, C.byref(st), C.byref(out), None) == 0, L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_data_costs")["table_kept_on_device"] is False
+        labels = np.zeros(s.n_faces, np.uint32); ms = M.viewsel.MrfStats()
+        assert L.mvs_view_selection(C.byref(out), s.adj_ptr.ctypes.data, s.adj.ctypes.data, None, labels.ctypes.data, C.byref(ms)) == 0, L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_view_selection")["table_reused_on_device"] is False
+        assert np.array_equal(labels, lo) and ms.energy_fixed == so["energy_fixed"]
+        assert out.nnz == ref.nnz
+        fp = _table_fingerprint(ref.n_faces, ref.n_views, ref.col_ptr, ref.view_id, ref.cost)
+        assert L.mvs_view_selection_cached(fp, out.n_faces, out.n_views, out.nnz, s.adj_ptr.ctypes.data, s.adj.ctypes.data, None, labels.ctypes.data, None) == 6
+        assert b"no parked table with this fingerprint" in L.mvs_last_error()
+        L.mvs_csr_free(C.byref(out))
+    finally:
+        if before is None:
+            del os.environ["MVS_KEEP_TABLE"]
+        else:
+            os.environ["MVS_KEEP_TABLE"] = before
+        L.mvs_release_cached()
+
+
+def test_a_failed_data_cost_call_takes_the_parked_table_with_it():
+    """a table is parked; the next mvs_data_costs works on that context (never two scenes resident) and fails on its arguments -- a view
+    one pixel wide, refused before any kernel runs: the context is destroyed, so mvs_view_selection on the FIRST table uploads it again and
+    labels like the oracle.  Then the streamed pair: mvs_data_costs_stream parks, mvs_view_selection_cached hits under the fingerprint of
+    the chunks it handed out."""
+    s = get_scene("tiny")
+    L = M.load_library()
+    ref, _ = O.data_costs(s)
+    lo, so = O.view_selection(ref, s.adj_ptr, s.adj)
+    L.mvs_release_cached()
+    try:
+        mesh, views, n = _one_shot_inputs(s)
+        out = M.viewsel.CCsr(); st = M.Settings()
+        assert L.mvs_data_costs(C.byref(mesh), views, n, C.byref(st), C.byref(out), None) == 0, L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_data_costs")["table_kept_on_device"] is True
+        mesh1, views1, n1 = _one_shot_inputs(s, width=1)
+        bad = M.viewsel.CCsr()
+        assert L.mvs_data_costs(C.byref(mesh1), views1, n1, C.byref(st), C.byref(bad), None) == 1
+        assert b"view 0: bad image" in L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_data_costs")["table_kept_on_device"] is False
+        labels = np.zeros(s.n_faces, np.uint32); ms = M.viewsel.MrfStats()
+        assert L.mvs_view_selection(C.byref(out), s.adj_ptr.ctypes.data, s.adj.ctypes.data, None, labels.ctypes.data, C.byref(ms)) == 0, L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_view_selection")["table_reused_on_device"] is False
+        assert np.array_equal(labels, lo) and ms.energy_fixed == so["energy_fixed"]
+        L.mvs_csr_free(C.byref(out))
+
+        chunks = []
+        CHUNK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_float))
+
+        def take(user, f0, nf, col_ptr, view_id, cost):
+            cp = np.ctypeslib.as_array(col_ptr, (nf + 1,)).copy(); ne = int(cp[-1] - cp[0])
+            chunks.append((f0, cp, np.ctypeslib.as_array(view_id, (max(ne, 1),))[:ne].copy(), np.ctypeslib.as_array(cost, (max(ne, 1),))[:ne].copy()))
+        fn = CHUNK_FN(take)
+        shape = M.viewsel.CCsr()
+        assert L.mvs_data_costs_stream(C.byref(mesh), views, n, C.byref(st), C.cast(fn, C.c_void_p), None, C.byref(shape), None) == 0, L.mvs_last_error()
+        prof = _last_call_profile(L, "mvs_data_costs_stream")
+        assert prof["table_kept_on_device"] is True and prof["fingerprint"] == "device"
+        col_ptr = np.concatenate([chunks[0][1][:1]] + [c[1][1:] for c in chunks])
+        view_id = np.concatenate([c[2] for c in chunks]); cost = np.concatenate([c[3] for c in chunks])
+        assert [c[0] for c in chunks] == list(range(0, s.n_faces, 1 << 16)) and (shape.n_faces, shape.n_views, shape.nnz) == (ref.n_faces, ref.n_views, ref.nnz)
+        assert np.array_equal(col_ptr, ref.col_ptr) and np.array_equal(view_id, ref.view_id) and np.array_equal(cost.view(np.uint32), ref.cost.view(np.uint32))
+        fp = _table_fingerprint(shape.n_faces, shape.n_views, col_ptr, view_id, cost)
+        labels[:] = 0
+        assert L.mvs_view_selection_cached(fp ^ 1, shape.n_faces, shape.n_views, shape.nnz, s.adj_ptr.ctypes.data, s.adj.ctypes.data, None, labels.ctypes.data, None) == 6
+        assert L.mvs_view_selection_cached(fp, shape.n_faces, shape.n_views, shape.nnz, s.adj_ptr.ctypes.data, s.adj.ctypes.data, None, labels.ctypes.data, C.byref(ms)) == 0, L.mvs_last_error()
+        assert _last_call_profile(L, "mvs_view_selection_cached")["table_reused_on_device"] is True
+        assert np.array_equal(labels, lo) and ms.energy_fixed == so["energy_fixed"]
+    finally:
+        L.mvs_release_cached()
 
 
 def test_call_order_errors(ctx):

@@ -257,7 +257,7 @@ def test_gloo_world2_with_sharded_tables_equals_single_rank(tmp_path, world):
 
 
 def test_stop_rule_is_the_library_rule():
-    """same decision as api.hip: (prev - best) < min_improvement * prev over `window` sweeps"""
+    """same decision as solve.hip: (prev - best) < min_improvement * prev over `window` sweeps"""
     p = M.viewsel.MrfParams(200, 3, 2, 0.01, 0.3, 0.8, 0)
     hist = [2 ** 64 - 1, 1000 << 32, 995 << 32, 994 << 32, 993 << 32]
     assert not G.stop_rule(hist, 2, p)

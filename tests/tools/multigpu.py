@@ -225,7 +225,7 @@ class HaloExchange:
 
 
 # --------------------------------------------------------------------------
-# the per-rank solver loop (mirrors api.hip mvs_ctx_view_selection)
+# the per-rank solver loop (mirrors solve.hip mvs_ctx_view_selection)
 # --------------------------------------------------------------------------
 def stop_rule(hist, sweep, params):
     """StopWhenReturnsDiminish-style rule on the best exact energy (identical on every rank)."""
