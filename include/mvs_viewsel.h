@@ -620,6 +620,55 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
                                    mvs_atlas_set* out, int out_on_device, mvs_atlas_stats* stats);
 void mvs_atlas_set_free(mvs_atlas_set* a);
 
+/* Row f9: tex::build_model (build_obj_model.cpp:18-80), ObjModel::save (obj_model.cpp:23-71) and MaterialLib::save_to_files
+ * (material_lib.cpp:20-46) on the context's mesh and an atlas set as mvs_atlas_set describes it: the text of `<name>.obj` and
+ * `<name>.mtl`, byte for byte what upstream's writers produce, formatted on the device (csrc/k_model.hip; the definition is DESIGN.md
+ * section 4 "Model output"; the same bytes on any device and in every run).  Of `atlases` only n_atlases, n_listed, n_merged, face_ptr,
+ * faces, tc_ptr, texcoords_merged and texcoord_ids are read by mvs_ctx_build_model (image and atlas_size may be NULL there);
+ * mvs_ctx_save_model reads atlas_size, atlas_pix_ptr and image as well.  `atlases` is all host arrays or all device pointers
+ * (atlases_on_device) and is not modified.  vertex_normals: [3 n_verts] floats on the host or the device (normals_on_device), or NULL:
+ * then the `vn` lines are left out and the faces are written V/T instead of V/T/V.  `name` (at most 255 bytes) is what the `mtllib` and
+ * `map_Kd` lines carry; mvs_ctx_save_model takes the part of `prefix` after the last '/'.
+ *   obj [obj_bytes], mtl [mtl_bytes]: the text, not NUL-terminated.  The .obj has n_atlases + 4 sections -- the mtllib line, the v, vt and
+ *   vn lines, then one group per atlas (its usemtl line and its faces): section i is lines section_ptr[i] .. section_ptr[i + 1] and bytes
+ *   section_bytes[i] .. section_bytes[i + 1] (both [n_atlases + 5], host arrays in either mode).
+ * MVS_ERR_STATE without a mesh; MVS_ERR_INVALID for a face id >= n_faces, a texcoord id outside its atlas's range, a face_ptr / tc_ptr
+ * that does not run from 0 to the totals, or a name that is too long; params.max_bytes (0 = no cap): when the .obj text exceeds it the
+ * call fails with MVS_ERR_UNSUPPORTED after the measuring pass, with stats filled.  With out_on_device obj and mtl are device pointers
+ * and the section arrays host arrays owned by the context (valid until its next build_model / save_model call or its destruction),
+ * otherwise everything is malloc'ed (mvs_model_text_free).
+ * mvs_ctx_save_model writes `<prefix>.obj`, `<prefix>.mtl` and per atlas `<prefix>_material<a>_map_Kd.png` (<a> zero-filled to four
+ * characters): the text comes through a pinned buffer, the PNGs are encoded by up to 16 host threads.  PNG: 8-bit RGB, filter 0, one
+ * IDAT; params.png_level 0 (default) = stored deflate blocks, no dependency; 1 .. 9 = libz.so.1 resolved at run time, MVS_ERR_UNSUPPORTED
+ * where it is absent.  mvs_write_png is that encoder on a host image (rgb [height][width][3]). */
+typedef struct mvs_model_params {
+    uint64_t max_bytes;       /* refuse an .obj of more bytes than this (0: no cap) */
+    int32_t png_level;        /* 0 .. 9 */
+    int32_t reserved;
+} mvs_model_params;
+void mvs_model_default_params(mvs_model_params* p);
+typedef struct mvs_model_text {
+    uint32_t n_atlases, reserved;
+    uint64_t obj_bytes, mtl_bytes;
+    char* obj;                      /* [obj_bytes] */
+    char* mtl;                      /* [mtl_bytes] */
+    uint64_t* section_ptr;          /* [n_atlases + 5] lines */
+    uint64_t* section_bytes;        /* [n_atlases + 5] bytes */
+} mvs_model_text;
+typedef struct mvs_model_stats {
+    uint64_t lines[5], bytes[5];                 /* of the .obj: mtllib line, v, vt, vn, all groups */
+    uint64_t mtl_bytes;
+    uint64_t wide_values, nonfinite_values;      /* floats of magnitude >= 2^64 (the multi-word route); inf / nan */
+    float ms_measure, ms_scan, ms_write;         /* device time per phase */
+    float ms_download, ms_files, ms_png;         /* host time of save_model: text to the host, the two text files, the PNGs (copy, encode, write) */
+} mvs_model_stats;
+mvs_status mvs_ctx_build_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
+                               const char* name, const mvs_model_params* params, mvs_model_text* out, int out_on_device, mvs_model_stats* stats);
+mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
+                              const char* prefix, const mvs_model_params* params, mvs_model_stats* stats);
+void mvs_model_text_free(mvs_model_text* t);
+mvs_status mvs_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height, int32_t level);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

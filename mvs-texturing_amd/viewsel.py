@@ -153,6 +153,24 @@ class AtlasStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ATLAS_COUNTS] + [(k, C.c_float) for k in ATLAS_MS] + [("reserved", C.c_float)]
 
 
+class ModelParams(C.Structure):
+    _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModelText(C.Structure):
+    _fields_ = [("n_atlases", C.c_uint32), ("reserved", C.c_uint32), ("obj_bytes", C.c_uint64), ("mtl_bytes", C.c_uint64), ("obj", C.c_void_p), ("mtl", C.c_void_p),
+                ("section_ptr", C.c_void_p), ("section_bytes", C.c_void_p)]
+
+
+MODEL_SECTIONS = ("header", "v", "vt", "vn", "groups")
+MODEL_COUNTS = ("mtl_bytes", "wide_values", "nonfinite_values")
+MODEL_MS = ("ms_measure", "ms_scan", "ms_write", "ms_download", "ms_files", "ms_png")
+
+
+class ModelStats(C.Structure):
+    _fields_ = [("lines", C.c_uint64 * 5), ("bytes", C.c_uint64 * 5)] + [(k, C.c_uint64) for k in MODEL_COUNTS] + [(k, C.c_float) for k in MODEL_MS]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -256,6 +274,10 @@ def load_library():
         "mvs_ctx_local_seam_leveling": [vp, vp, vp, i32, vp, i32, C.POINTER(PatchSet), i32, C.POINTER(LslParams), C.POINTER(LslResult), i32, C.POINTER(LslStats)],
         "mvs_atlas_default_params": [C.POINTER(AtlasParams)], "mvs_atlas_set_free": [C.POINTER(AtlasSet)],
         "mvs_ctx_texture_atlases": [vp, C.POINTER(PatchSet), i32, C.POINTER(AtlasParams), C.POINTER(AtlasSet), i32, C.POINTER(AtlasStats)],
+        "mvs_model_default_params": [C.POINTER(ModelParams)], "mvs_model_text_free": [C.POINTER(ModelText)],
+        "mvs_ctx_build_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelText), i32, C.POINTER(ModelStats)],
+        "mvs_ctx_save_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelStats)],
+        "mvs_write_png": [C.c_char_p, vp, u32, u32, C.c_int32],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -280,7 +302,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -715,6 +737,47 @@ class Context:
         out["texcoords_merged"] = out["texcoords_merged"].reshape(NM, 2); out["texcoord_ids"] = out["texcoord_ids"].reshape(NL, 3)
         return out, stats
 
+    def _model_call(self, atlases, vertex_normals, params):
+        """the arguments build_model and save_model share: (AtlasSet, on_device, normals pointer, normals on device, params, held arrays)"""
+        ps, held, dev = _atlas_set_struct(atlases)
+        if vertex_normals is not None and not (_is_torch(vertex_normals) or isinstance(vertex_normals, DevArray)):
+            vertex_normals = np.ascontiguousarray(vertex_normals, np.float32).reshape(-1)
+            assert "mesh" not in self._keep or vertex_normals.size == 3 * int(self._keep["mesh"][0].shape[0]), "vertex_normals: one normal per mesh vertex"
+        pn, dn = _ptr(vertex_normals)
+        return ps, dev, pn, dn, params or default_model_params(), (held, vertex_normals)
+
+    def build_model(self, atlases, vertex_normals=None, name="model", params=None, on_device=False):
+        """Row f9: the text of tex::build_model + ObjModel::save + MaterialLib::save_to_files (DESIGN.md section 4 "Model output") on the
+        context's mesh and an atlas set -- the dict of texture_atlases (all host arrays or all DevArrays / CUDA tensors; only face_ptr,
+        faces, tc_ptr, texcoords_merged and texcoord_ids are read).  vertex_normals: (n_verts, 3) host or device array, or None: no `vn`
+        lines, faces written V/T.  Returns ({obj, mtl: bytes, section_ptr, section_bytes: uint64 (A + 5,)}, stats); with on_device=True obj
+        and mtl are DevArrays of bytes owned by the context (valid until its next build_model / save_model call).  An .obj above
+        params.max_bytes raises MvsError (status 7) with `.stats` holding the counts."""
+        ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
+        res, st = ModelText(), ModelStats()
+        self._keep["model"] = held
+        rc = self.L.mvs_ctx_build_model(self.h, C.byref(ps), dev, pn, dn, name.encode(), C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        stats = _model_stats(st)
+        _check_with_stats(self.L, rc, stats)
+        NS = int(res.n_atlases) + 5
+        sec = {k: np.frombuffer(C.string_at(getattr(res, k), 8 * NS), np.uint64).copy() for k in ("section_ptr", "section_bytes")}
+        if on_device:
+            return dict(obj=DevArray(res.obj, res.obj_bytes), mtl=DevArray(res.mtl, res.mtl_bytes), **sec), stats
+        out = dict(obj=C.string_at(res.obj, res.obj_bytes), mtl=C.string_at(res.mtl, res.mtl_bytes), **sec)
+        self.L.mvs_model_text_free(C.byref(res))
+        return out, stats
+
+    def save_model(self, atlases, prefix, vertex_normals=None, params=None):
+        """Row f9 to files: `<prefix>.obj`, `<prefix>.mtl` and one `<prefix>_material<a>_map_Kd.png` per atlas (mvs_ctx_save_model; the
+        atlas set needs atlas_size, atlas_pix_ptr and image as well).  Returns the stats; params: default_model_params(png_level=...)."""
+        ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
+        st = ModelStats()
+        self._keep["model"] = held
+        rc = self.L.mvs_ctx_save_model(self.h, C.byref(ps), dev, pn, dn, os.fspath(prefix).encode(), C.byref(p), C.byref(st))
+        stats = _model_stats(st)
+        _check_with_stats(self.L, rc, stats)
+        return stats
+
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
         a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
@@ -752,6 +815,64 @@ def default_lsl_params(**kw):
 def default_atlas_params(**kw):
     """mvs_atlas_default_params (max_pixels 0 = no cap) with overrides"""
     return _default_params(AtlasParams, "mvs_atlas_default_params", kw)
+
+
+def default_model_params(**kw):
+    """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks) with overrides"""
+    return _default_params(ModelParams, "mvs_model_default_params", kw)
+
+
+ATLAS_DTYPES = dict(atlas_size=np.uint32, atlas_pix_ptr=np.uint64, image=np.uint8, patch_atlas=np.uint32, patch_pos=np.int32, patch_order=np.uint32, face_ptr=np.uint32,
+                    faces=np.uint32, texcoords=np.float32, tc_ptr=np.uint32, texcoords_merged=np.float32, texcoord_ids=np.uint32)
+
+
+def _atlas_set_struct(atlases):
+    """an atlas-set dict as an AtlasSet: (struct, held, on_device) -- all host arrays (made contiguous and flat; `held` keeps them alive) or
+    all DevArrays / CUDA tensors; arrays that are absent or None stay NULL.  The counts come from face_ptr, faces, texcoords_merged and
+    (when present) atlas_pix_ptr: a device-resident atlas_pix_ptr costs one 8-byte read."""
+    have = {k: atlases[k] for k in ATLAS_ARRAYS if atlases.get(k) is not None}
+    dev = [_is_torch(v) or isinstance(v, DevArray) for v in have.values()]
+    assert all(dev) or not any(dev), "the atlas set must be all host or all device arrays"
+    on_device = bool(dev) and dev[0]
+    held = {k: v if on_device else np.ascontiguousarray(v, ATLAS_DTYPES[k]).reshape(-1) for k, v in have.items()}
+    count = lambda x: int(x.numel()) if _is_torch(x) else int(x.shape[0])
+    s = AtlasSet()
+    s.n_atlases = count(held["face_ptr"]) - 1 if "face_ptr" in held else 0
+    s.n_listed = count(held["faces"]) if "faces" in held else 0
+    s.n_merged = count(held["texcoords_merged"]) // 2 if "texcoords_merged" in held else 0
+    s.n_patches = count(held["patch_atlas"]) if "patch_atlas" in held else 0
+    s.n_pixels = count(held["image"]) // 3 if "image" in held else 0
+    for k, v in held.items():
+        setattr(s, k, _ptr(v)[0] if (on_device or v.size) else None)
+    return s, held, 1 if on_device else 0
+
+
+def _model_stats(st):
+    stats = {"lines": dict(zip(MODEL_SECTIONS, [int(x) for x in st.lines])), "bytes": dict(zip(MODEL_SECTIONS, [int(x) for x in st.bytes]))}
+    stats.update({k: int(getattr(st, k)) for k in MODEL_COUNTS})
+    stats.update({k: float(getattr(st, k)) for k in MODEL_MS})
+    return stats
+
+
+def write_png(path, rgb, level=0):
+    """mvs_write_png: an (H, W, 3) uint8 host image as an 8-bit RGB PNG (level 0: stored blocks, 1 .. 9: libz.so.1)"""
+    L = load_library()
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    _check(L, L.mvs_write_png(os.fspath(path).encode(), rgb.ctypes.data, rgb.shape[1], rgb.shape[0], int(level)))
+
+
+def vertex_normals(verts, faces):
+    """area-weighted vertex normals of a triangle mesh in numpy, (n_verts, 3) float32: the sum of the incident faces' cross products,
+    normalised (zero where it vanishes).  Plumbing for callers that have none -- NOT MVE's ensure_normals, whose weights differ."""
+    verts = np.asarray(verts, np.float32); faces = np.asarray(faces, np.int64)
+    a, b, c = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    n = np.cross(b - a, c - a).astype(np.float64)
+    out = np.zeros((len(verts), 3), np.float64)
+    for k in range(3):
+        np.add.at(out, faces[:, k], n)
+    norm = np.linalg.norm(out, axis=1, keepdims=True)
+    return np.where(norm > 0, out / np.where(norm > 0, norm, 1), 0).astype(np.float32)
 
 
 def atlas_view(arrays, a):
@@ -816,6 +937,21 @@ def texture_atlases(scene, labels, params=None, ctx=None):
         lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
         dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
         return c.texture_atlases(dev, params)
+
+
+def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None):
+    """texrecon.cpp:169-208 for a synth.Scene-like object and its labels: rows f5 to f8 as texture_atlases runs them, then the model
+    output (row f9) with the atlases left on the device: writes `<prefix>.obj`, `<prefix>.mtl` and the atlas PNGs.  Returns row f9's
+    stats.  vertex_normals: (n_verts, 3) or None (no `vn` lines; vertex_normals(verts, faces) computes area-weighted ones)."""
+    with _scene_context(scene, ctx) as c:
+        a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
+        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
+        dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
+        atlases, _ = c.texture_atlases(dev, on_device=True)
+        return c.save_model(atlases, prefix, vertex_normals, params)
 
 
 def global_seam_leveling(scene, labels, params=None, ctx=None):
