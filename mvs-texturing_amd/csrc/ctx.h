@@ -234,7 +234,7 @@ struct mvs_ctx {
     mvs::DBuf<float> pq;                // quality per passing pair
     mvs::DBuf<float> pcol;              // 3 floats per passing pair (outlier removal only)
     mvs::DBuf<uint32_t> face_cnt, scan_tmp;
-    mvs::DBuf<unsigned long long> counters;  // see k_dc.hip
+    mvs::DBuf<unsigned long long> counters;  // 64 slots, named in dc_counters.h
     mvs::DBuf<float> max_q; mvs::DBuf<uint32_t> hist; mvs::DBuf<float> pctl;
     // pre-outlier CSR (only when outlier removal is on)
     mvs::DBuf<uint32_t> pre_ptr; mvs::DBuf<uint16_t> pre_view; mvs::DBuf<float> pre_q; mvs::DBuf<float> pre_col;
@@ -357,7 +357,7 @@ int default_device();
 uint64_t env_dc_range_pairs();
 // which zone(s) of a colour phase mrf_sweep_phase sweeps (k_mrf.hip)
 enum { MRF_PART_ALL = 0, MRF_PART_BOUNDARY = 1, MRF_PART_INTERIOR = 2 };
-// reports through pinned host memory (k_mrf.hip)
+// reports through pinned host memory (readback.hip)
 void ensure_report_ring(mvs_ctx* ctx);
 void report_u32(mvs_ctx* ctx, const uint32_t* d_src, uint32_t* d_dst, uint32_t seq_slot, uint32_t seq);
 void wait_report(mvs_ctx* ctx, uint32_t seq_slot, uint32_t seq);
@@ -368,7 +368,7 @@ constexpr uint32_t MRF_REC_BASE = 256;   // the first record starts at this word
 // damped sweeps: 1, 5, 9, ... -- part of the solver's definition, restated in oracle/oracle.cpp (MRF_DAMP_PERIOD)
 constexpr uint32_t MRF_DAMP_PERIOD = 4;
 // up to 64 words from device memory to the host between two launches of ctx->stream: a one-block kernel stores them into a pinned buffer and
-// announces them with a sequence number the host spins on (k_mrf.hip).  A 4-byte hipMemcpyAsync into pageable memory + hipStreamSynchronize
+// announces them with a sequence number the host spins on (readback.hip).  A 4-byte hipMemcpyAsync into pageable memory + hipStreamSynchronize
 // holds the device idle for 22 us, this for 9 (scripts/probe/readback_cost.hip) -- a step has a dozen of them on its critical path.
 void read_words(mvs_ctx* ctx, const void* d_src, void* out, uint32_t n_words);
 // one word the plain way: a 4-byte copy into pageable memory and a drain of ctx->stream (where that drain is wanted anyway, or off the hot path)
@@ -378,7 +378,9 @@ inline uint32_t read_u32(mvs_ctx* ctx, const uint32_t* d) {
     MVS_HIP(hipStreamSynchronize(ctx->stream));
     return h;
 }
-void read_block(mvs_ctx* ctx, const void* d_src, void* out, size_t bytes);   // up to 4 KB, through pinned staging
+// one word through the pinned route of read_words: between two launches of a pass, where read_u32's drain would hold the device idle
+inline uint32_t read_word(mvs_ctx* ctx, const uint32_t* d) { uint32_t h = 0; read_words(ctx, d, &h, 1); return h; }
+void read_block(mvs_ctx* ctx, const void* d_src, void* out, size_t bytes);   // up to 4 KB, through pinned staging (readback.hip)
 // generic device exclusive scan (scan.hip): out[i] = sum_{k<i} in[i]; returns total via d_total (device, may be null)
 void exclusive_scan_u32(mvs_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n, uint32_t* d_total);
 // exact 64-bit total of a u32 array (blocking): the guard in front of scans whose total may pass 2^32

@@ -15,6 +15,7 @@
 // (vertex, view), so each distinct ray is traced ONCE (vertices are shared by
 // ~6 faces): need bits -> ray kernel -> occluded bits, view-major bit matrices.
 #include "ctx.h"
+#include "dc_counters.h"
 #include <rocprim/rocprim.hpp>
 #ifndef MVS_LEAF_T
 #define MVS_LEAF_T 16
@@ -563,7 +564,7 @@ __global__ void __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) r
     int oct = 8;
     if (okm == actm && (nxm == 0ull || nxm == actm) && (nym == 0ull || nym == actm) && (nzm == 0ull || nzm == actm))
         oct = (nxm ? 1 : 0) | (nym ? 2 : 0) | (nzm ? 4 : 0);
-    if (counters && lane == 0) { atomicAdd(&counters[10], 1ull); if (oct == 8) atomicAdd(&counters[11], 1ull); }   // diagnostics ("stats" option)
+    if (counters && lane == 0) { atomicAdd(&counters[C_RPACKETS], 1ull); if (oct == 8) atomicAdd(&counters[C_RGENERIC], 1ull); }   // diagnostics ("stats" option)
     uint32_t cnt[3] = {0u, 0u, 0u};
 #define MVS_P3(O) packet3_traverse<O, COUNT>(bvh, s_ray[wv], s_src[wv], lane, pad, inv, oi, t0, t1, live, cnt)
     switch (oct) {
@@ -573,7 +574,7 @@ __global__ void __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(80))) r
     }
 #undef MVS_P3
     if (lane == 0) occl[(size_t)j * vwords + vw] = actm & ~live;
-    if (COUNT && lane == 0) { atomicAdd(&counters[8], (unsigned long long)cnt[0]); atomicAdd(&counters[9], (unsigned long long)cnt[1]); atomicAdd(&counters[13], (unsigned long long)cnt[2]); }
+    if (COUNT && lane == 0) { atomicAdd(&counters[C_RNODES], (unsigned long long)cnt[0]); atomicAdd(&counters[C_RTRIS], (unsigned long long)cnt[1]); atomicAdd(&counters[C_RLEAF_ROUNDS], (unsigned long long)cnt[2]); }
 }
 
 }  // namespace

@@ -13,7 +13,10 @@
 //                     std::sort of :272);
 //   outlier_kernel    photometric_outlier_detection (:35-129) per face, fp64 in registers;
 //   max / histogram / percentile / cost  = postprocess_face_infos (:278-302).
+// In order: the kernels; host helpers (kernel choice from the run-time flags, steps several phases take); phase 1 as a list of stages and
+// postprocess_face_infos on a caller's infos; phases 2 and 3, label pruning; the ranged walk.  Counter slots: dc_counters.h.
 #include "ctx.h"
+#include "dc_counters.h"
 #include "dc_ranges.h"
 
 namespace mvs {
@@ -22,8 +25,6 @@ namespace {
 
 constexpr int VIEW_CHUNK = 32;
 constexpr uint32_t HIST_BINS = 10000;  // calculate_data_costs.cpp:283
-
-enum { C_BACK = 0, C_ANGLE = 1, C_OUTSIDE = 2, C_OCCL = 3, C_ZEROQ = 4, C_SURV = 5, C_RAYS = 6, C_PASS = 7, C_RNODES = 8, C_RTRIS = 9, C_REWALK = 12 };
 
 __device__ __forceinline__ V3 ld3(const float* __restrict__ p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 
@@ -856,265 +857,6 @@ __global__ void set_count_kernel(uint32_t* __restrict__ hist, uint32_t n) { hist
 
 }  // namespace
 
-static uint32_t read_word(mvs_ctx* ctx, const uint32_t* d) {   // one word through the pinned route of read_words (ctx.h read_u32 is the plain copy)
-    uint32_t h = 0;
-    read_words(ctx, d, &h, 1);
-    return h;
-}
-
-// outlier detection over a pre-CSR: LDS-staged when the longest column fits (counts: per-face lengths on the device, or null
-// with the longest column given in kmax_known)
-static void launch_outlier(mvs_ctx* ctx, const uint32_t* ptr, const uint32_t* counts, uint32_t kmax_known, uint32_t nf, const float* col, float* q, uint8_t* inl, int mode);
-
-// (re)compute per-view derived images and upload the view table
-static void upload_views_and_prepare(mvs_ctx* ctx, bool need_gmi) {
-    const uint32_t V = ctx->n_views;
-    ctx->gmi_off.assign(V + 1, 0); ctx->mask_off.assign(V + 1, 0); ctx->msum_off.assign(V + 1, 0);
-    for (uint32_t j = 0; j < V; ++j) {
-        auto& v = ctx->h_views[j];
-        v.mask_stride = (v.width + 31) / 32;
-        v.msum_stride = ((v.mask_stride + 63) / 64) * 2;   // one bit per 32-pixel tile column, rows padded to 64 tiles (a wave's ballot)
-        ctx->gmi_off[j + 1] = ctx->gmi_off[j] + (need_gmi ? (((size_t)v.width * v.height + 15) & ~(size_t)15) : 0);
-        ctx->mask_off[j + 1] = ctx->mask_off[j] + (size_t)v.mask_stride * v.height;
-        ctx->msum_off[j + 1] = ctx->msum_off[j] + (size_t)v.msum_stride * ((v.height + 31) / 32);
-    }
-    ctx->gmi_all.ensure(std::max<size_t>(ctx->gmi_off[V], 16));
-    ctx->mask_all.ensure(std::max<size_t>(ctx->mask_off[V], 16));
-    ctx->mask_zero.ensure(std::max<size_t>(ctx->mask_off[V], 16));
-    ctx->mask_tmp.ensure(std::max<size_t>(ctx->mask_off[V], 16));
-    ctx->msum_all.ensure(std::max<size_t>(ctx->msum_off[V], 16));
-    for (uint32_t j = 0; j < V; ++j) {
-        ctx->h_views[j].gmi = need_gmi ? ctx->gmi_all.p + ctx->gmi_off[j] : nullptr;
-        ctx->h_views[j].mask = ctx->mask_all.p + ctx->mask_off[j];
-        ctx->h_views[j].msum = ctx->msum_all.p + ctx->msum_off[j];
-    }
-    ctx->d_views.ensure(V);
-    MVS_HIP(hipMemcpyAsync(ctx->d_views.p, ctx->h_views.data(), V * sizeof(ViewParams), hipMemcpyHostToDevice, ctx->stream));
-    ctx->view_off.ensure(2 * ((size_t)V + 1));
-    size_t* d_off = ctx->view_off.p;
-    MVS_HIP(hipMemcpyAsync(d_off, ctx->gmi_off.data(), (V + 1) * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
-    MVS_HIP(hipMemcpyAsync(d_off + V + 1, ctx->mask_off.data(), (V + 1) * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
-    prepare_views(ctx, need_gmi, d_off, d_off + V + 1);
-}
-
-// phase 1: everything up to the per-face sorted infos + local max quality
-static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st);
-void dc_phase1(mvs_ctx* ctx, const mvs_settings* st) {
-    ctx->dc_walk_resident = false; ctx->dc_n_ranges = 1; ctx->dc_range_faces = ctx->face_end - ctx->face_begin;
-    // (a second pass only when the face order had to be rebuilt -- scene_order_commit: a mesh with thousands of equal centroid coordinates)
-    if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
-}
-static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
-    if (!ctx->d_verts) throw StatusError(MVS_ERR_STATE, "scene not set (mesh + views)");
-    /* calculate_data_costs.cpp:315-318 -- F is a uint32 here, so only the view guard can fire */
-    if (ctx->n_views > 65535u) throw StatusError(MVS_ERR_TOO_MANY_VIEWS, "Exeeded maximal number of views");
-    if (st->data_term != MVS_DATA_TERM_AREA && st->data_term != MVS_DATA_TERM_GMI) throw StatusError(MVS_ERR_INVALID, "bad data_term");
-    if (st->outlier_removal < 0 || st->outlier_removal > 2) throw StatusError(MVS_ERR_INVALID, "bad outlier_removal");
-    hipStream_t s = ctx->stream;
-    const uint32_t V = ctx->n_views, fb = ctx->face_begin, nf = ctx->face_end - ctx->face_begin;
-    const uint32_t fwords = (nf + 63) / 64, vwords = (ctx->n_verts + 63) / 64;
-    const bool gmi = st->data_term == MVS_DATA_TERM_GMI, outl = st->outlier_removal != MVS_OUTLIER_NONE, vis = st->geometric_visibility_test != 0;
-    ctx->dc_settings = *st; ctx->have_costs = false;
-    ctx->t_perm = nullptr; ctx->t_pos = nullptr; ctx->u_valid = false;
-    memset(&ctx->dc_stats, 0, sizeof(ctx->dc_stats));
-    ctx->dc_stats.pairs = (uint64_t)nf * V;
-    ctx->counters.ensure(64);
-    MVS_HIP(hipMemsetAsync(ctx->counters.p, 0, 64 * sizeof(unsigned long long), s));
-
-    const uint32_t nf_early = ctx->face_end - ctx->face_begin;
-    if (nf_early == 0 || ctx->n_views == 0 || ctx->n_faces == 0) {
-        // nothing to evaluate: every column is empty (the reference's loops simply do not execute)
-        ctx->csr_ptr.ensure((size_t)nf_early + 2); ctx->csr_view.ensure(4); ctx->csr_q.ensure(4); ctx->csr_cost.ensure(4);
-        MVS_HIP(hipMemsetAsync(ctx->csr_ptr.p, 0, ((size_t)nf_early + 2) * sizeof(uint32_t), s));
-        ctx->csr_faces = nf_early; ctx->csr_views = ctx->n_views; ctx->csr_nnz = 0; ctx->dc_phase = 1;
-        ctx->max_q.ensure(4); MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 4 * sizeof(float), s));
-        return false;
-    }
-    // the mesh in the library's own layout (faces [fb, fb + nf) are POSITIONS of that layout); a table over the whole mesh remembers
-    // its order so that it crosses the ABI in the caller's numbering
-    // The image preparation (:157-163) depends on nothing the face order or the BVH build (:144) produce, and neither fills the machine
-    // (prep waits on memory half of its wave cycles, the order / BVH builds are a hundred short launches): prep runs on a second stream
-    // beside BOTH.  The fork is recorded HERE, in front of the order's launches (recorded behind them -- as it was until the kernel timeline
-    // of a step showed the main stream idle for 0.7 ms in front of the culls -- prep overlapped the BVH build only); prep's launches are
-    // still QUEUED after the order's and the BVH's, because prep's flood fill makes the host wait (for its own stream only).
-    // (the ranges of a ranged pass after its first find all of that resident: dc_ranged)
-    if (!ctx->dc_walk_resident) {
-    if (!ctx->aux_stream) { MVS_HIP(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming)); }
-    MVS_HIP(hipEventRecord(ctx->ev_fork, s));                          // (the counters' memset above is what prep has to see)
-    MVS_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-    if (!(ctx->order_pinned && ctx->iv)) { Prof pr(ctx, "dc_order"); build_scene_order(ctx); }   // (pinned: a shard owns this layout, see ctx.h)
-    // (a face RANGE's table remembers which faces its columns belong to -- t_perm = the range's slice of the order -- but has no inverse:
-    //  it leaves as it is, columns in position order, and mvs_ctx_table_order names the faces)
-    if (ctx->mesh_ordered) {
-        if (fb == 0 && nf == ctx->n_faces) { ctx->t_perm = ctx->f_perm.p; ctx->t_pos = ctx->f_pos.p; }
-        else { ctx->t_perm = ctx->f_perm.p + fb; ctx->t_pos = nullptr; }
-    }
-    if (vis) { Prof pr(ctx, "dc_bvh_build"); build_bvh(ctx); }
-    {
-        struct Swap { mvs_ctx* c; hipStream_t main; ~Swap() { c->stream = main; } } swap{ctx, s};
-        ctx->stream = ctx->aux_stream;
-        { Prof pr(ctx, "dc_prep"); upload_views_and_prepare(ctx, gmi); }
-        MVS_HIP(hipEventRecord(ctx->ev_join, ctx->aux_stream));
-        ctx->stream = s;
-        MVS_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));
-    }
-    }
-
-    const size_t pw = (size_t)V * fwords;
-    ctx->pass_bits.ensure(pw + 1); ctx->surv_bits.ensure(pw + 1); ctx->pass_base.ensure(pw + 2);
-    const dim3 fgrid((nf + 255) / 256, (V + VIEW_CHUNK - 1) / VIEW_CHUNK);
-    uint32_t* pass_face = nullptr;
-    if (vis) { ctx->pass_face.ensure((size_t)fgrid.y * fwords * 64u + 1); pass_face = ctx->pass_face.p; }
-    Prof pr_cull(ctx, "dc_cull");
-    // one block per 256 faces walks all view chunks; the chunks are split over blockIdx.y only to reach ~4096 blocks on small meshes
-    const dim3 cgrid(fgrid.x, std::max(1u, std::min<unsigned>(fgrid.y, (4096u + fgrid.x - 1) / fgrid.x)));
-    if (ctx->stats)
-        hipLaunchKernelGGL(cull_kernel<true>, cgrid, dim3(256), 0, s, ctx->iv, ctx->ifc, ctx->inr, ctx->d_views.p, V, fb, nf, fwords,
-                           ctx->cos_limit, ctx->pass_bits.p, pass_face, ctx->counters.p);
-    else
-        hipLaunchKernelGGL(cull_kernel<false>, cgrid, dim3(256), 0, s, ctx->iv, ctx->ifc, ctx->inr, ctx->d_views.p, V, fb, nf, fwords,
-                           ctx->cos_limit, ctx->pass_bits.p, pass_face, ctx->counters.p);
-    MVS_LAUNCH_CHECK();
-    pr_cull.end();
-    if (vis) {
-        const size_t vw = (size_t)V * vwords;
-        ctx->need_bits.ensure(vw + 1); ctx->occl_bits.ensure(vw + 1);
-        MVS_HIP(hipMemsetAsync(ctx->occl_bits.p, 0, vw * sizeof(unsigned long long), s));
-        const dim3 vgrid((ctx->n_verts + 255) / 256, (V + VIEW_CHUNK - 1) / VIEW_CHUNK);
-        Prof pr_need(ctx, "dc_need");
-        if (ctx->stats)
-            hipLaunchKernelGGL(need_kernel<true>, vgrid, dim3(256), 0, s, ctx->vf_ptr.p, ctx->vf.p, ctx->n_verts, V, fb, nf, fwords, vwords,
-                               pass_face, ctx->need_bits.p, ctx->counters.p);
-        else
-            hipLaunchKernelGGL(need_kernel<false>, vgrid, dim3(256), 0, s, ctx->vf_ptr.p, ctx->vf.p, ctx->n_verts, V, fb, nf, fwords, vwords,
-                               pass_face, ctx->need_bits.p, ctx->counters.p);
-        MVS_LAUNCH_CHECK();
-        pr_need.end();
-        Prof pr_rays(ctx, "dc_rays");
-        trace_rays(ctx);
-        pr_rays.end();
-    }
-    // rank of every passing pair
-    Prof pr_rank(ctx, "dc_rank_scan");
-    hipLaunchKernelGGL(popc_kernel, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, s, ctx->pass_bits.p, ctx->pass_base.p, pw);
-    MVS_LAUNCH_CHECK();
-    ctx->max_q.ensure(4);
-    uint32_t* d_total = (uint32_t*)(ctx->max_q.p + 2);
-    // ranks, CSR pointers and nnz are 32 bits wide (the reference uses size_t containers): a scene whose passing pairs could
-    // reach 2^32 gets an exact 64-bit count first and is refused instead of wrapping the scan.  (The planner of the ranged pass, dc_ranges.h,
-    // never produces such a range by itself: only a caller's own "dc_range_pairs" can.)
-    if ((uint64_t)nf * V >= 0xFFFFFFF0ull && sum_u32(ctx, ctx->pass_base.p, pw) >= 0xFFFFFFF0ull)
-        throw StatusError(MVS_ERR_UNSUPPORTED, "more than 2^32 (face, view) pairs pass the culls in one range of faces: evaluate the faces in smaller ranges (option dc_range_pairs)");
-    exclusive_scan_u32(ctx, ctx->pass_base.p, ctx->pass_base.p, pw, d_total);
-    pr_rank.end();
-    const uint32_t n_pass = read_word(ctx, d_total);
-    if (scene_order_commit(ctx)) return true;                 // (the stream is drained here anyway) the order was rebuilt: once more from the top
-    ctx->pq.ensure((size_t)n_pass + 1);
-    if (outl) ctx->pcol.ensure(3 * ((size_t)n_pass + 1));
-
-    Prof pr_info(ctx, "dc_face_info");
-    // footprints above info_wave_area pixels (and only footprints that are sampled at all: gmi or outlier removal) are left to
-    // the wave-per-footprint kernel
-    const bool defer = (gmi || outl) && ctx->info_wave_area > 0;
-    ctx->dc_stats_deferred = 0;
-    const bool words = defer && ctx->info_words && gmi && !outl;   // the integer walk needs the lane-group kernel behind it (for what it cannot certify)
-    // (where info_kernel itself reads four pixels per load -- WORDS -- one lane keeps up with the lane group up to a few hundred pixels)
-    const float defer_area = defer ? (float)(words ? std::max(ctx->info_wave_area, ctx->info_wave_area_words) : ctx->info_wave_area) : INFINITY;
-    unsigned long long* defer_bits = nullptr;
-    if (defer) { ctx->defer_bits.ensure(pw + 1); defer_bits = ctx->defer_bits.p; }
-#define LAUNCH_INFO(DT, OL, VT, WD)                                                                                          \
-    do { if (ctx->stats) LAUNCH_INFO2(DT, OL, VT, true, WD); else LAUNCH_INFO2(DT, OL, VT, false, WD); } while (0)
-#define LAUNCH_INFO2(DT, OL, VT, ST, WD)                                                                                     \
-    hipLaunchKernelGGL((info_kernel<DT, OL, VT, ST, WD>), fgrid, dim3(256), 0, s, ctx->iv, ctx->ifc, ctx->d_views.p, V, fb, nf, \
-                       fwords, vwords, ctx->pass_bits.p, ctx->occl_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p,         \
-                       ctx->surv_bits.p, ctx->counters.p, defer_area, defer_bits, ctx->info_cert_shift)
-    if (gmi) { if (outl) { if (vis) LAUNCH_INFO(1, true, true, false); else LAUNCH_INFO(1, true, false, false); }
-               else if (words) { if (vis) LAUNCH_INFO(1, false, true, true); else LAUNCH_INFO(1, false, false, true); }
-               else      { if (vis) LAUNCH_INFO(1, false, true, false); else LAUNCH_INFO(1, false, false, false); } }
-    else     { if (outl) { if (vis) LAUNCH_INFO(0, true, true, false); else LAUNCH_INFO(0, true, false, false); }
-               else      { if (vis) LAUNCH_INFO(0, false, true, false); else LAUNCH_INFO(0, false, false, false); } }
-#undef LAUNCH_INFO
-#undef LAUNCH_INFO2
-    MVS_LAUNCH_CHECK();
-    if (defer) {
-        // deferred pairs: bit matrix -> ranks -> list (no atomics), then one wave per pair
-        ctx->defer_base.ensure(pw + 2);
-        hipLaunchKernelGGL(popc_kernel, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, s, defer_bits, ctx->defer_base.p, pw); MVS_LAUNCH_CHECK();
-        uint32_t* d_total2 = (uint32_t*)(ctx->max_q.p + 3);
-        exclusive_scan_u32(ctx, ctx->defer_base.p, ctx->defer_base.p, pw, d_total2);
-        const uint32_t n_def = read_word(ctx, d_total2);
-        ctx->dc_stats_deferred = n_def;
-        if (n_def) {
-            ctx->defer_list.ensure((size_t)n_def + 1);
-            hipLaunchKernelGGL(defer_expand_kernel, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, s, defer_bits, ctx->defer_base.p, pw, ctx->defer_list.p); MVS_LAUNCH_CHECK();
-            const dim3 wgrid((unsigned)(((size_t)n_def * 16 + 255) / 256));
-#define WAVE_ARGS ctx->iv, ctx->ifc, ctx->d_views.p, fb, fwords, ctx->defer_list.p, n_def, ctx->pass_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p, ctx->surv_bits.p, ctx->counters.p, ctx->info_cert_shift, ctx->rewalk_list.p
-#define REWALK_ARGS ctx->iv, ctx->ifc, ctx->d_views.p, fb, fwords, ctx->defer_list.p, ctx->rewalk_list.p, ctx->pass_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p, ctx->surv_bits.p, ctx->counters.p
-#define LAUNCH_WAVE(DT, OL) do { if (ctx->stats) { hipLaunchKernelGGL((wave_info_kernel<DT, OL, true>), wgrid, dim3(256), 0, s, WAVE_ARGS); hipLaunchKernelGGL((rewalk_info_kernel<DT, OL, true>), rgrid, dim3(64), 0, s, REWALK_ARGS); } \
-                                 else { hipLaunchKernelGGL((wave_info_kernel<DT, OL, false>), wgrid, dim3(256), 0, s, WAVE_ARGS); hipLaunchKernelGGL((rewalk_info_kernel<DT, OL, false>), rgrid, dim3(64), 0, s, REWALK_ARGS); } } while (0)
-            ctx->rewalk_list.ensure((size_t)n_def + 1);
-            // one wave per uncertified footprint, a fixed grid striding over the device-side count (no read-back): 2048 waves
-            // cover what a scene produces (tens to hundreds) one each; the test hook that fails every certificate takes the grid-stride loop
-            const dim3 rgrid(2048);
-            if (gmi) { if (outl) LAUNCH_WAVE(1, true); else LAUNCH_WAVE(1, false); } else LAUNCH_WAVE(0, true);
-#undef LAUNCH_WAVE
-#undef WAVE_ARGS
-#undef REWALK_ARGS
-            MVS_LAUNCH_CHECK();
-        }
-    }
-    pr_info.end();
-    Prof pr_csr(ctx, "dc_csr");
-
-    // CSR by face
-    ctx->face_cnt.ensure((size_t)nf + 2);
-    hipLaunchKernelGGL(csr_count_kernel, dim3((nf + 255) / 256), dim3(256), 0, s, ctx->surv_bits.p, V, nf, fwords, ctx->face_cnt.p);
-    MVS_LAUNCH_CHECK();
-    DBuf<uint32_t>& ptr = outl ? ctx->pre_ptr : ctx->csr_ptr;
-    ptr.ensure((size_t)nf + 2);
-    exclusive_scan_u32(ctx, ctx->face_cnt.p, ptr.p, (size_t)nf + 1, nullptr);
-    const uint32_t nnz_pre = read_word(ctx, ptr.p + nf);
-    ctx->dc_stats.nnz_pre = nnz_pre;
-    if (outl) {
-        ctx->pre_view.ensure((size_t)nnz_pre + 1); ctx->pre_q.ensure((size_t)nnz_pre + 1); ctx->pre_col.ensure(3 * ((size_t)nnz_pre + 1));
-        ctx->pre_inl.ensure((size_t)nnz_pre + 1);
-        hipLaunchKernelGGL(csr_write_staged_kernel<true>, dim3((fwords + 3) / 4), dim3(256), 0, s, ctx->surv_bits.p, ctx->pass_bits.p, ctx->pass_base.p,
-                           ctx->pq.p, ctx->pcol.p, V, nf, fwords, ctx->pre_ptr.p, ctx->pre_view.p, ctx->pre_q.p, ctx->pre_col.p, (uint32_t*)nullptr);
-        MVS_LAUNCH_CHECK();
-        launch_outlier(ctx, ctx->pre_ptr.p, ctx->face_cnt.p /* still the per-face counts of csr_count_kernel */, 0u, nf, ctx->pre_col.p, ctx->pre_q.p, ctx->pre_inl.p, st->outlier_removal);
-        hipLaunchKernelGGL(nonzero_count_kernel, dim3((nf / 64u + 1u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, nf, ctx->pre_q.p, ctx->face_cnt.p);
-        MVS_LAUNCH_CHECK();
-        ctx->csr_ptr.ensure((size_t)nf + 2);
-        exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)nf + 1, nullptr);
-        const uint32_t nnz = read_word(ctx, ctx->csr_ptr.p + nf);
-        ctx->csr_view.ensure((size_t)nnz + 1); ctx->csr_q.ensure((size_t)nnz + 1); ctx->csr_cost.ensure((size_t)nnz + 1);
-        hipLaunchKernelGGL(nonzero_copy_kernel, dim3(((nf + 63u) / 64u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, ctx->csr_ptr.p, nf, ctx->pre_view.p, ctx->pre_q.p,
-                           ctx->csr_view.p, ctx->csr_q.p);
-        MVS_LAUNCH_CHECK();
-        ctx->csr_nnz = nnz;
-    } else {
-        ctx->csr_view.ensure((size_t)nnz_pre + 1); ctx->csr_q.ensure((size_t)nnz_pre + 1); ctx->csr_cost.ensure((size_t)nnz_pre + 1);
-        MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), s));   // the kernel also leaves the maximum quality behind
-        hipLaunchKernelGGL(csr_write_staged_kernel<false>, dim3((fwords + 3) / 4), dim3(256), 0, s, ctx->surv_bits.p, ctx->pass_bits.p, ctx->pass_base.p,
-                           ctx->pq.p, (const float*)nullptr, V, nf, fwords, ctx->csr_ptr.p, ctx->csr_view.p, ctx->csr_q.p, (float*)nullptr, (uint32_t*)ctx->max_q.p);
-        MVS_LAUNCH_CHECK();
-        ctx->csr_nnz = nnz_pre;
-    }
-    pr_csr.end();
-    Prof pr_post(ctx, "dc_post");
-    ctx->csr_faces = nf; ctx->csr_views = V;
-    // local max quality (:278-281): after outlier removal a pass of its own, otherwise left behind by the CSR kernel
-    if (outl) {
-        MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), s));
-        if (ctx->csr_nnz) {
-            hipLaunchKernelGGL(max_kernel, dim3(1024), dim3(256), 0, s, ctx->csr_q.p, (size_t)ctx->csr_nnz, (uint32_t*)ctx->max_q.p);
-            MVS_LAUNCH_CHECK();
-        }
-    }
-    ctx->dc_phase = 1;
-    return false;
-}
-
 // ---- label-space compression (BASELINE config 5: hundreds of candidate views per face) ----
 // Keeps, per face, the `kmax` entries with the smallest (cost, view id) pairs -- ties to the smaller view id -- in ascending
 // view order; columns of at most kmax entries are untouched.  NOT part of the reference (its model keeps every candidate,
@@ -1211,6 +953,323 @@ __global__ void sort_columns_kernel(const uint32_t* __restrict__ col_ptr, uint32
     }
 }
 
+// ---- the ranged walk's own kernels (dc_ranged) ----
+__global__ void max_merge_kernel(uint32_t* __restrict__ global_bits, const uint32_t* __restrict__ local_bits) {   // qualities are > 0: uint order = float order
+    if (*local_bits > *global_bits) *global_bits = *local_bits;
+}
+__global__ void rebase_ptr_kernel(const uint32_t* __restrict__ src, uint32_t n, uint32_t base, uint32_t* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i] + base;
+}
+// cost_kernel fused with the append of a range's columns (no pruning: the range's entries are one contiguous run of the final table)
+__global__ void cost_append_kernel(const uint16_t* __restrict__ view, const float* __restrict__ q, size_t n, const float* __restrict__ pctl,
+                                   uint16_t* __restrict__ view_out, float* __restrict__ q_out, float* __restrict__ cost_out) {
+    const float p = *pctl;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float x = q[i];
+        view_out[i] = view[i]; q_out[i] = x; cost_out[i] = 1.0f - smin(1.0f, x / p);
+    }
+}
+
+// outlier detection over a pre-CSR: LDS-staged when the longest column fits (counts: per-face lengths on the device, or null
+// with the longest column given in kmax_known)
+static void launch_outlier(mvs_ctx* ctx, const uint32_t* ptr, const uint32_t* counts, uint32_t kmax_known, uint32_t nf, const float* col, float* q, uint8_t* inl, int mode) {
+    hipStream_t s = ctx->stream;
+    if (!nf) return;
+    constexpr uint32_t LDS_PER_ENTRY = 64 * (3 * sizeof(float) + 1);   // 64 faces x (three floats + the inlier flag)
+    uint32_t kmax = kmax_known;
+    if (counts) {
+        ctx->counters.ensure(C_N_SLOTS);
+        uint32_t* d = reinterpret_cast<uint32_t*>(ctx->counters.p + C_KMAX);
+        MVS_HIP(hipMemsetAsync(d, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(max_u32_kernel, dim3(std::min<unsigned>((nf + 255) / 256, 1024u)), dim3(256), 0, s, counts, nf, d); MVS_LAUNCH_CHECK();
+        kmax = read_word(ctx, d);
+    }
+    const uint64_t lds = (uint64_t)std::max<uint32_t>(kmax, 1u) * LDS_PER_ENTRY;
+    const bool staged = lds <= 64u * 1024u;
+    hipLaunchKernelGGL(staged ? outlier_kernel<true> : outlier_kernel<false>, dim3((nf + 63) / 64), dim3(64), staged ? (size_t)lds : 0, s, ptr, nf, col, q, inl, mode,
+                       staged ? std::max<uint32_t>(kmax, 1u) : 0u);
+    MVS_LAUNCH_CHECK();
+}
+
+// (re)compute per-view derived images and upload the view table
+static void upload_views_and_prepare(mvs_ctx* ctx, bool need_gmi) {
+    const uint32_t V = ctx->n_views;
+    ctx->gmi_off.assign(V + 1, 0); ctx->mask_off.assign(V + 1, 0); ctx->msum_off.assign(V + 1, 0);
+    for (uint32_t j = 0; j < V; ++j) {
+        auto& v = ctx->h_views[j];
+        v.mask_stride = (v.width + 31) / 32;
+        v.msum_stride = ((v.mask_stride + 63) / 64) * 2;   // one bit per 32-pixel tile column, rows padded to 64 tiles (a wave's ballot)
+        ctx->gmi_off[j + 1] = ctx->gmi_off[j] + (need_gmi ? (((size_t)v.width * v.height + 15) & ~(size_t)15) : 0);
+        ctx->mask_off[j + 1] = ctx->mask_off[j] + (size_t)v.mask_stride * v.height;
+        ctx->msum_off[j + 1] = ctx->msum_off[j] + (size_t)v.msum_stride * ((v.height + 31) / 32);
+    }
+    ctx->gmi_all.ensure(std::max<size_t>(ctx->gmi_off[V], 16));
+    ctx->mask_all.ensure(std::max<size_t>(ctx->mask_off[V], 16));
+    ctx->mask_zero.ensure(std::max<size_t>(ctx->mask_off[V], 16));
+    ctx->mask_tmp.ensure(std::max<size_t>(ctx->mask_off[V], 16));
+    ctx->msum_all.ensure(std::max<size_t>(ctx->msum_off[V], 16));
+    for (uint32_t j = 0; j < V; ++j) {
+        ctx->h_views[j].gmi = need_gmi ? ctx->gmi_all.p + ctx->gmi_off[j] : nullptr;
+        ctx->h_views[j].mask = ctx->mask_all.p + ctx->mask_off[j];
+        ctx->h_views[j].msum = ctx->msum_all.p + ctx->msum_off[j];
+    }
+    ctx->d_views.ensure(V);
+    MVS_HIP(hipMemcpyAsync(ctx->d_views.p, ctx->h_views.data(), V * sizeof(ViewParams), hipMemcpyHostToDevice, ctx->stream));
+    ctx->view_off.ensure(2 * ((size_t)V + 1));
+    size_t* d_off = ctx->view_off.p;
+    MVS_HIP(hipMemcpyAsync(d_off, ctx->gmi_off.data(), (V + 1) * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+    MVS_HIP(hipMemcpyAsync(d_off + V + 1, ctx->mask_off.data(), (V + 1) * sizeof(size_t), hipMemcpyHostToDevice, ctx->stream));
+    prepare_views(ctx, need_gmi, d_off, d_off + V + 1);
+}
+
+// ---- which instantiation the run-time flags ask for: tables of kernel pointers, every argument list written once where it is launched ----
+using InfoKernel = decltype(&info_kernel<1, false, false, false, false>);
+static InfoKernel info_kernel_for(bool gmi, bool outl, bool vis, bool stats, bool words) {
+    static const InfoKernel k[2][2][2][2] = {   // [data term][outlier removal][visibility test][stats]
+        {{{info_kernel<0, false, false, false, false>, info_kernel<0, false, false, true, false>}, {info_kernel<0, false, true, false, false>, info_kernel<0, false, true, true, false>}},
+         {{info_kernel<0, true, false, false, false>, info_kernel<0, true, false, true, false>}, {info_kernel<0, true, true, false, false>, info_kernel<0, true, true, true, false>}}},
+        {{{info_kernel<1, false, false, false, false>, info_kernel<1, false, false, true, false>}, {info_kernel<1, false, true, false, false>, info_kernel<1, false, true, true, false>}},
+         {{info_kernel<1, true, false, false, false>, info_kernel<1, true, false, true, false>}, {info_kernel<1, true, true, false, false>, info_kernel<1, true, true, true, false>}}}};
+    static const InfoKernel kw[2][2] = {   // the integer word walk (gradient term, no outlier removal): [visibility test][stats]
+        {info_kernel<1, false, false, false, true>, info_kernel<1, false, false, true, true>}, {info_kernel<1, false, true, false, true>, info_kernel<1, false, true, true, true>}};
+    return words ? kw[vis][stats] : k[gmi][outl][vis][stats];
+}
+// the lane-group kernel and the re-walk behind it sample footprints: the gradient term with or without the colours, or the colours alone
+struct WaveKernels { decltype(&wave_info_kernel<1, true, false>) wave; decltype(&rewalk_info_kernel<1, true, false>) rewalk; };
+static const WaveKernels& wave_kernels_for(bool gmi, bool outl, bool stats) {
+    static const WaveKernels k[3][2] = {{{wave_info_kernel<1, true, false>, rewalk_info_kernel<1, true, false>}, {wave_info_kernel<1, true, true>, rewalk_info_kernel<1, true, true>}},
+                                        {{wave_info_kernel<1, false, false>, rewalk_info_kernel<1, false, false>}, {wave_info_kernel<1, false, true>, rewalk_info_kernel<1, false, true>}},
+                                        {{wave_info_kernel<0, true, false>, rewalk_info_kernel<0, true, false>}, {wave_info_kernel<0, true, true>, rewalk_info_kernel<0, true, true>}}};
+    return k[gmi ? (outl ? 0 : 1) : 2][stats];
+}
+
+// start of a pass, behind its caller's checks: no table, no order, no statistics, counters cleared (the first thing a pass queues)
+static void dc_start_pass(mvs_ctx* ctx, const mvs_settings* st) {
+    ctx->dc_settings = *st; ctx->have_costs = false;
+    ctx->t_perm = nullptr; ctx->t_pos = nullptr; ctx->u_valid = false;
+    memset(&ctx->dc_stats, 0, sizeof(ctx->dc_stats));
+    ctx->counters.ensure(C_N_SLOTS);
+    MVS_HIP(hipMemsetAsync(ctx->counters.p, 0, C_N_SLOTS * sizeof(unsigned long long), ctx->stream));
+}
+
+// A table over the whole mesh remembers its order so that it crosses the ABI in the caller's numbering; a face RANGE's table remembers which faces its
+// columns belong to (t_perm = the range's slice of the order) but has no inverse: it leaves in position order, mvs_ctx_table_order names the faces.
+static void name_table_order(mvs_ctx* ctx, uint32_t fb, uint32_t nf) {
+    if (!ctx->mesh_ordered) return;
+    if (fb == 0 && nf == ctx->n_faces) { ctx->t_perm = ctx->f_perm.p; ctx->t_pos = ctx->f_pos.p; }
+    else { ctx->t_perm = ctx->f_perm.p + fb; ctx->t_pos = nullptr; }
+}
+
+// remove quality == 0 entries (:268-270): (pre_ptr, pre_view, pre_q) -> (csr_ptr, csr_view, csr_q); returns what stays
+static uint32_t erase_zero_quality(mvs_ctx* ctx, uint32_t nf) {
+    hipStream_t s = ctx->stream;
+    ctx->csr_ptr.ensure((size_t)nf + 2);
+    hipLaunchKernelGGL(nonzero_count_kernel, dim3((nf / 64u + 1u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, nf, ctx->pre_q.p, ctx->face_cnt.p); MVS_LAUNCH_CHECK();
+    exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)nf + 1, nullptr);
+    const uint32_t nnz = read_word(ctx, ctx->csr_ptr.p + nf);
+    ctx->csr_view.ensure((size_t)nnz + 1); ctx->csr_q.ensure((size_t)nnz + 1); ctx->csr_cost.ensure((size_t)nnz + 8);
+    if (nf) { hipLaunchKernelGGL(nonzero_copy_kernel, dim3(((nf + 63u) / 64u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, ctx->csr_ptr.p, nf, ctx->pre_view.p, ctx->pre_q.p, ctx->csr_view.p, ctx->csr_q.p); MVS_LAUNCH_CHECK(); }
+    return nnz;
+}
+
+static void local_max_quality(mvs_ctx* ctx) {
+    ctx->max_q.ensure(4);
+    MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), ctx->stream));
+    if (ctx->csr_nnz) { hipLaunchKernelGGL(max_kernel, dim3(1024), dim3(256), 0, ctx->stream, ctx->csr_q.p, (size_t)ctx->csr_nnz, (uint32_t*)ctx->max_q.p); MVS_LAUNCH_CHECK(); }
+}
+
+// the histogram against ctx->max_q (:283-286) in pieces, and the percentile from it (:288), which also reports both floats' bits into the counters block
+static void hist_clear(mvs_ctx* ctx) { ctx->hist.ensure(HIST_BINS + 8); MVS_HIP(hipMemsetAsync(ctx->hist.p, 0, (HIST_BINS + 8) * sizeof(uint32_t), ctx->stream)); }
+static void hist_add(mvs_ctx* ctx, const float* q, size_t n) { if (n) { hipLaunchKernelGGL(hist_kernel, dim3(512), dim3(1024), 0, ctx->stream, q, n, ctx->max_q.p, ctx->hist.p); MVS_LAUNCH_CHECK(); } }
+static void hist_set_count(mvs_ctx* ctx, uint32_t n_values) { hipLaunchKernelGGL(set_count_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->hist.p, n_values); MVS_LAUNCH_CHECK(); }
+static void percentile_of_hist(mvs_ctx* ctx) { hipLaunchKernelGGL(percentile_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->hist.p, ctx->max_q.p, 0.995f, ctx->pctl.p, ctx->counters.p + C_MAX_Q_BITS); MVS_LAUNCH_CHECK(); }
+
+static void activate_own_table(mvs_ctx* ctx, bool with_quality) {   // the context's own arrays are the active table
+    ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p;
+    ctx->csr_q_valid = with_quality; ctx->u_valid = false; ctx->have_costs = true;
+}
+
+// ---- phase 1, stage by stage ----
+// what the stages of one pass share (on the stack): pw = words of a view-major bit matrix over the faces, fgrid = 256 faces x one chunk of views per block
+struct DcPass { hipStream_t s; uint32_t V, fb, nf, fwords, vwords; size_t pw; bool gmi, outl, vis; dim3 fgrid; };
+static DcPass dc_pass_of(const mvs_ctx* ctx, const mvs_settings* st) {
+    const uint32_t V = ctx->n_views, nf = ctx->face_end - ctx->face_begin, fwords = (nf + 63) / 64;
+    return DcPass{ctx->stream, V, ctx->face_begin, nf, fwords, (ctx->n_verts + 63) / 64, (size_t)V * fwords, st->data_term == MVS_DATA_TERM_GMI,
+                  st->outlier_removal != MVS_OUTLIER_NONE, st->geometric_visibility_test != 0, dim3((nf + 255) / 256, (V + VIEW_CHUNK - 1) / VIEW_CHUNK)};
+}
+
+// nothing to evaluate: every column is empty (the reference's loops simply do not execute)
+static void dc_empty_table(mvs_ctx* ctx, const DcPass& P) {
+    ctx->csr_ptr.ensure((size_t)P.nf + 2); ctx->csr_view.ensure(4); ctx->csr_q.ensure(4); ctx->csr_cost.ensure(4);
+    MVS_HIP(hipMemsetAsync(ctx->csr_ptr.p, 0, ((size_t)P.nf + 2) * sizeof(uint32_t), P.s));
+    ctx->csr_faces = P.nf; ctx->csr_views = P.V; ctx->csr_nnz = 0; ctx->dc_phase = 1;
+    ctx->max_q.ensure(4); MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 4 * sizeof(float), P.s));
+}
+
+// The mesh in the library's own layout (faces [fb, fb + nf) are POSITIONS of it), the BVH and the prepared views: what the ranges of a ranged pass
+// after its first find resident.  The image preparation (:157-163) depends on nothing the face order or the BVH build (:144) produce and neither fills
+// the machine: prep runs on a second stream beside BOTH.  The fork is recorded in front of the order's launches (behind them the
+// main stream idled for 0.7 ms in front of the culls); prep's launches are still QUEUED last, because its flood fill makes the host wait (for its stream).
+static void dc_resident_inputs(mvs_ctx* ctx, const DcPass& P) {
+    if (!ctx->aux_stream) { MVS_HIP(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)); MVS_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming)); }
+    MVS_HIP(hipEventRecord(ctx->ev_fork, P.s));                          // (the counters' memset of dc_start_pass is what prep has to see)
+    MVS_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+    if (!(ctx->order_pinned && ctx->iv)) { Prof pr(ctx, "dc_order"); build_scene_order(ctx); }   // (pinned: a shard owns this layout, see ctx.h)
+    name_table_order(ctx, P.fb, P.nf);
+    if (P.vis) { Prof pr(ctx, "dc_bvh_build"); build_bvh(ctx); }
+    struct Swap { mvs_ctx* c; hipStream_t main; ~Swap() { c->stream = main; } } swap{ctx, P.s};
+    ctx->stream = ctx->aux_stream;
+    { Prof pr(ctx, "dc_prep"); upload_views_and_prepare(ctx, P.gmi); }
+    MVS_HIP(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+    ctx->stream = P.s;
+    MVS_HIP(hipStreamWaitEvent(P.s, ctx->ev_join, 0));
+}
+
+// the culls (:171-191), and with the visibility test the rays they leave to trace: need bits, then the occluded bits (:194-215)
+static void dc_culls_and_rays(mvs_ctx* ctx, const DcPass& P) {
+    ctx->pass_bits.ensure(P.pw + 1); ctx->surv_bits.ensure(P.pw + 1); ctx->pass_base.ensure(P.pw + 2);
+    uint32_t* pass_face = nullptr;
+    if (P.vis) { ctx->pass_face.ensure((size_t)P.fgrid.y * P.fwords * 64u + 1); pass_face = ctx->pass_face.p; }
+    Prof pr_cull(ctx, "dc_cull");
+    // one block per 256 faces walks all view chunks; the chunks are split over blockIdx.y only to reach ~4096 blocks on small meshes
+    const dim3 cgrid(P.fgrid.x, std::max(1u, std::min<unsigned>(P.fgrid.y, (4096u + P.fgrid.x - 1) / P.fgrid.x)));
+    hipLaunchKernelGGL(ctx->stats ? cull_kernel<true> : cull_kernel<false>, cgrid, dim3(256), 0, P.s, ctx->iv, ctx->ifc, ctx->inr, ctx->d_views.p, P.V, P.fb, P.nf, P.fwords,
+                       ctx->cos_limit, ctx->pass_bits.p, pass_face, ctx->counters.p);
+    MVS_LAUNCH_CHECK();
+    pr_cull.end();
+    if (!P.vis) return;
+    const size_t vw = (size_t)P.V * P.vwords;
+    ctx->need_bits.ensure(vw + 1); ctx->occl_bits.ensure(vw + 1);
+    MVS_HIP(hipMemsetAsync(ctx->occl_bits.p, 0, vw * sizeof(unsigned long long), P.s));
+    const dim3 vgrid((ctx->n_verts + 255) / 256, (P.V + VIEW_CHUNK - 1) / VIEW_CHUNK);
+    Prof pr_need(ctx, "dc_need");
+    hipLaunchKernelGGL(ctx->stats ? need_kernel<true> : need_kernel<false>, vgrid, dim3(256), 0, P.s, ctx->vf_ptr.p, ctx->vf.p, ctx->n_verts, P.V, P.fb, P.nf, P.fwords, P.vwords,
+                       pass_face, ctx->need_bits.p, ctx->counters.p);
+    MVS_LAUNCH_CHECK();
+    pr_need.end();
+    Prof pr_rays(ctx, "dc_rays");
+    trace_rays(ctx);
+}
+
+// rank of every passing pair -> *n_pass of them.  true: the face order was rebuilt (scene_order_commit) -- once more from the top
+static bool dc_rank_scan(mvs_ctx* ctx, const DcPass& P, uint32_t* n_pass) {
+    Prof pr_rank(ctx, "dc_rank_scan");
+    hipLaunchKernelGGL(popc_kernel, dim3((unsigned)((P.pw + 255) / 256)), dim3(256), 0, P.s, ctx->pass_bits.p, ctx->pass_base.p, P.pw);
+    MVS_LAUNCH_CHECK();
+    ctx->max_q.ensure(4);
+    uint32_t* d_total = (uint32_t*)(ctx->max_q.p + 2);
+    // ranks, CSR pointers and nnz are 32 bits wide (the reference uses size_t containers): a scene whose passing pairs could
+    // reach 2^32 gets an exact 64-bit count first and is refused instead of wrapping the scan.  (The planner of the ranged pass, dc_ranges.h,
+    // never produces such a range by itself: only a caller's own "dc_range_pairs" can.)
+    if ((uint64_t)P.nf * P.V >= 0xFFFFFFF0ull && sum_u32(ctx, ctx->pass_base.p, P.pw) >= 0xFFFFFFF0ull)
+        throw StatusError(MVS_ERR_UNSUPPORTED, "more than 2^32 (face, view) pairs pass the culls in one range of faces: evaluate the faces in smaller ranges (option dc_range_pairs)");
+    exclusive_scan_u32(ctx, ctx->pass_base.p, ctx->pass_base.p, P.pw, d_total);
+    pr_rank.end();
+    *n_pass = read_word(ctx, d_total);
+    return scene_order_commit(ctx);   // (the stream is drained here anyway)
+}
+
+// get_face_info (:220) for the passing pairs; sampled footprints above info_wave_area pixels are left to the lane-group kernel, what that cannot certify to the re-walk
+static void dc_face_infos(mvs_ctx* ctx, const DcPass& P, uint32_t n_pass) {
+    ctx->pq.ensure((size_t)n_pass + 1);
+    if (P.outl) ctx->pcol.ensure(3 * ((size_t)n_pass + 1));
+    Prof pr_info(ctx, "dc_face_info");
+    const bool defer = (P.gmi || P.outl) && ctx->info_wave_area > 0;
+    ctx->dc_stats_deferred = 0;
+    const bool words = defer && ctx->info_words && P.gmi && !P.outl;   // the integer walk needs the lane-group kernel behind it (for what it cannot certify)
+    // (where info_kernel itself reads four pixels per load -- WORDS -- one lane keeps up with the lane group up to a few hundred pixels)
+    const float defer_area = defer ? (float)(words ? std::max(ctx->info_wave_area, ctx->info_wave_area_words) : ctx->info_wave_area) : INFINITY;
+    unsigned long long* defer_bits = nullptr;
+    if (defer) { ctx->defer_bits.ensure(P.pw + 1); defer_bits = ctx->defer_bits.p; }
+    hipLaunchKernelGGL(info_kernel_for(P.gmi, P.outl, P.vis, ctx->stats, words), P.fgrid, dim3(256), 0, P.s, ctx->iv, ctx->ifc, ctx->d_views.p, P.V, P.fb, P.nf,
+                       P.fwords, P.vwords, ctx->pass_bits.p, ctx->occl_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p,
+                       ctx->surv_bits.p, ctx->counters.p, defer_area, defer_bits, ctx->info_cert_shift);
+    MVS_LAUNCH_CHECK();
+    if (!defer) return;
+    // deferred pairs: bit matrix -> ranks -> list (no atomics), then sixteen lanes per pair
+    ctx->defer_base.ensure(P.pw + 2);
+    hipLaunchKernelGGL(popc_kernel, dim3((unsigned)((P.pw + 255) / 256)), dim3(256), 0, P.s, defer_bits, ctx->defer_base.p, P.pw); MVS_LAUNCH_CHECK();
+    uint32_t* d_total2 = (uint32_t*)(ctx->max_q.p + 3);
+    exclusive_scan_u32(ctx, ctx->defer_base.p, ctx->defer_base.p, P.pw, d_total2);
+    const uint32_t n_def = read_word(ctx, d_total2);
+    ctx->dc_stats_deferred = n_def;
+    if (!n_def) return;
+    ctx->defer_list.ensure((size_t)n_def + 1);
+    hipLaunchKernelGGL(defer_expand_kernel, dim3((unsigned)((P.pw + 255) / 256)), dim3(256), 0, P.s, defer_bits, ctx->defer_base.p, P.pw, ctx->defer_list.p); MVS_LAUNCH_CHECK();
+    ctx->rewalk_list.ensure((size_t)n_def + 1);
+    const WaveKernels& k = wave_kernels_for(P.gmi, P.outl, ctx->stats);
+    hipLaunchKernelGGL(k.wave, dim3((unsigned)(((size_t)n_def * 16 + 255) / 256)), dim3(256), 0, P.s, ctx->iv, ctx->ifc, ctx->d_views.p, P.fb, P.fwords, ctx->defer_list.p, n_def,
+                       ctx->pass_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p, ctx->surv_bits.p, ctx->counters.p, ctx->info_cert_shift, ctx->rewalk_list.p);
+    // one wave per uncertified footprint, a fixed grid striding over the device-side count (no read-back): 2048 waves
+    // cover what a scene produces (tens to hundreds) one each; the test hook that fails every certificate takes the grid-stride loop
+    hipLaunchKernelGGL(k.rewalk, dim3(2048), dim3(64), 0, P.s, ctx->iv, ctx->ifc, ctx->d_views.p, P.fb, P.fwords, ctx->defer_list.p,
+                       ctx->rewalk_list.p, ctx->pass_bits.p, ctx->pass_base.p, ctx->pq.p, ctx->pcol.p, ctx->surv_bits.p, ctx->counters.p);
+    MVS_LAUNCH_CHECK();
+}
+
+// the surviving pairs as CSR by face; with outlier removal the columns are staged with their colours, judged (:35-129) and stripped of quality 0
+static void dc_csr(mvs_ctx* ctx, const DcPass& P, int outlier_mode) {
+    Prof pr_csr(ctx, "dc_csr");
+    ctx->face_cnt.ensure((size_t)P.nf + 2);
+    hipLaunchKernelGGL(csr_count_kernel, dim3((P.nf + 255) / 256), dim3(256), 0, P.s, ctx->surv_bits.p, P.V, P.nf, P.fwords, ctx->face_cnt.p);
+    MVS_LAUNCH_CHECK();
+    DBuf<uint32_t>& ptr = P.outl ? ctx->pre_ptr : ctx->csr_ptr;
+    ptr.ensure((size_t)P.nf + 2);
+    exclusive_scan_u32(ctx, ctx->face_cnt.p, ptr.p, (size_t)P.nf + 1, nullptr);
+    const uint32_t nnz_pre = read_word(ctx, ptr.p + P.nf);
+    ctx->dc_stats.nnz_pre = nnz_pre;
+    DBuf<uint16_t>& view = P.outl ? ctx->pre_view : ctx->csr_view; DBuf<float>& q = P.outl ? ctx->pre_q : ctx->csr_q;
+    view.ensure((size_t)nnz_pre + 1); q.ensure((size_t)nnz_pre + 1);
+    if (P.outl) { ctx->pre_col.ensure(3 * ((size_t)nnz_pre + 1)); ctx->pre_inl.ensure((size_t)nnz_pre + 1); }
+    else {
+        ctx->csr_cost.ensure((size_t)nnz_pre + 1);
+        MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), P.s));   // the kernel also leaves the maximum quality behind
+    }
+    hipLaunchKernelGGL(P.outl ? csr_write_staged_kernel<true> : csr_write_staged_kernel<false>, dim3((P.fwords + 3) / 4), dim3(256), 0, P.s, ctx->surv_bits.p, ctx->pass_bits.p,
+                       ctx->pass_base.p, ctx->pq.p, P.outl ? ctx->pcol.p : (const float*)nullptr, P.V, P.nf, P.fwords, ptr.p, view.p, q.p,
+                       P.outl ? ctx->pre_col.p : (float*)nullptr, P.outl ? (uint32_t*)nullptr : (uint32_t*)ctx->max_q.p);
+    MVS_LAUNCH_CHECK();
+    ctx->csr_nnz = nnz_pre;
+    if (!P.outl) return;
+    launch_outlier(ctx, ctx->pre_ptr.p, ctx->face_cnt.p /* still the per-face counts of csr_count_kernel */, 0u, P.nf, ctx->pre_col.p, ctx->pre_q.p, ctx->pre_inl.p, outlier_mode);
+    ctx->csr_nnz = erase_zero_quality(ctx, P.nf);
+}
+
+// local max quality (:278-281): after outlier removal a pass of its own, otherwise left behind by the CSR kernel
+static void dc_local_max(mvs_ctx* ctx, const DcPass& P) {
+    Prof pr_post(ctx, "dc_post");
+    ctx->csr_faces = P.nf; ctx->csr_views = P.V;
+    if (P.outl) local_max_quality(ctx);
+    ctx->dc_phase = 1;
+}
+
+// phase 1: everything up to the per-face sorted infos + local max quality.  true: the face order was rebuilt on the way, nothing is left
+static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
+    if (!ctx->d_verts) throw StatusError(MVS_ERR_STATE, "scene not set (mesh + views)");
+    /* calculate_data_costs.cpp:315-318 -- F is a uint32 here, so only the view guard can fire */
+    if (ctx->n_views > 65535u) throw StatusError(MVS_ERR_TOO_MANY_VIEWS, "Exeeded maximal number of views");
+    if (st->data_term != MVS_DATA_TERM_AREA && st->data_term != MVS_DATA_TERM_GMI) throw StatusError(MVS_ERR_INVALID, "bad data_term");
+    if (st->outlier_removal < 0 || st->outlier_removal > 2) throw StatusError(MVS_ERR_INVALID, "bad outlier_removal");
+    dc_start_pass(ctx, st);
+    const DcPass P = dc_pass_of(ctx, st);
+    ctx->dc_stats.pairs = (uint64_t)P.nf * P.V;
+    if (P.nf == 0 || P.V == 0 || ctx->n_faces == 0) { dc_empty_table(ctx, P); return false; }
+    if (!ctx->dc_walk_resident) dc_resident_inputs(ctx, P);
+    dc_culls_and_rays(ctx, P);
+    uint32_t n_pass = 0;
+    if (dc_rank_scan(ctx, P, &n_pass)) return true;
+    dc_face_infos(ctx, P, n_pass);
+    dc_csr(ctx, P, st->outlier_removal);
+    dc_local_max(ctx, P);
+    return false;
+}
+void dc_phase1(mvs_ctx* ctx, const mvs_settings* st) {
+    ctx->dc_walk_resident = false; ctx->dc_n_ranges = 1; ctx->dc_range_faces = ctx->face_end - ctx->face_begin;
+    // (a second pass only when the face order had to be rebuilt -- scene_order_commit: a mesh with thousands of equal centroid coordinates)
+    if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
+}
+
 // tex::postprocess_face_infos (calculate_data_costs.cpp:253-306, exported at texturing.h:71-74) on caller-provided infos:
 // per face outlier detection in the order the infos are given (:265-267), erase quality == 0 (:268-270), sort by view id
 // (:272); then the global maximum, the histogram and the percentile (:278-288) and the costs (:291-298) -- phases 2 and 3.
@@ -1220,16 +1279,12 @@ void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t*
                     const float* h_col_rev, const mvs_settings* st) {
     if (st->outlier_removal < 0 || st->outlier_removal > 2) throw StatusError(MVS_ERR_INVALID, "bad outlier_removal");
     if (n_views > 65535u) throw StatusError(MVS_ERR_TOO_MANY_VIEWS, "Exeeded maximal number of views");
+    dc_start_pass(ctx, st);   // the caller's infos, the caller's order
     hipStream_t s = ctx->stream;
     const bool outl = st->outlier_removal != MVS_OUTLIER_NONE;
     const uint32_t n = h_ptr[nf];
-    ctx->dc_settings = *st; ctx->have_costs = false;
-    ctx->t_perm = nullptr; ctx->t_pos = nullptr; ctx->u_valid = false;   // the caller's infos, the caller's order
     ctx->dc_n_ranges = 1; ctx->dc_range_faces = nf;
-    memset(&ctx->dc_stats, 0, sizeof(ctx->dc_stats));
     ctx->dc_stats.nnz_pre = n;
-    ctx->counters.ensure(64);
-    MVS_HIP(hipMemsetAsync(ctx->counters.p, 0, 64 * sizeof(unsigned long long), s));
     ctx->pre_ptr.ensure((size_t)nf + 2); ctx->pre_view.ensure((size_t)n + 1); ctx->pre_q.ensure((size_t)n + 1);
     MVS_HIP(hipMemcpyAsync(ctx->pre_ptr.p, h_ptr, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (n) {
@@ -1242,90 +1297,52 @@ void dc_postprocess(mvs_ctx* ctx, uint32_t nf, uint32_t n_views, const uint32_t*
         uint32_t kmax_h = 0; for (uint32_t i = 0; i < nf; ++i) kmax_h = std::max(kmax_h, h_ptr[i + 1] - h_ptr[i]);
         launch_outlier(ctx, ctx->pre_ptr.p, nullptr, kmax_h, nf, ctx->pre_col.p, ctx->pre_q.p, ctx->pre_inl.p, st->outlier_removal);
     }
-    ctx->face_cnt.ensure((size_t)nf + 2); ctx->csr_ptr.ensure((size_t)nf + 2);
+    ctx->face_cnt.ensure((size_t)nf + 2);
     uint32_t nnz = n;
-    if (outl) {   // the zero-quality erase belongs to the outlier branch (:265-271): without outlier removal every info stays
-        hipLaunchKernelGGL(nonzero_count_kernel, dim3((nf / 64u + 1u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, nf, ctx->pre_q.p, ctx->face_cnt.p);
-        MVS_LAUNCH_CHECK();
-        exclusive_scan_u32(ctx, ctx->face_cnt.p, ctx->csr_ptr.p, (size_t)nf + 1, nullptr);
-        nnz = read_word(ctx, ctx->csr_ptr.p + nf);
-    } else MVS_HIP(hipMemcpyAsync(ctx->csr_ptr.p, ctx->pre_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    ctx->csr_view.ensure((size_t)nnz + 1); ctx->csr_q.ensure((size_t)nnz + 1); ctx->csr_cost.ensure((size_t)nnz + 8);
-    if (nf) {
-        if (outl) {
-            hipLaunchKernelGGL(nonzero_copy_kernel, dim3(((nf + 63u) / 64u + 3u) / 4u), dim3(256), 0, s, ctx->pre_ptr.p, ctx->csr_ptr.p, nf, ctx->pre_view.p, ctx->pre_q.p, ctx->csr_view.p, ctx->csr_q.p);
-            MVS_LAUNCH_CHECK();
-        } else if (n) {
+    if (outl) nnz = erase_zero_quality(ctx, nf);   // the erase belongs to the outlier branch (:265-271): without outlier removal every info stays
+    else {
+        ctx->csr_ptr.ensure((size_t)nf + 2); ctx->csr_view.ensure((size_t)n + 1); ctx->csr_q.ensure((size_t)n + 1); ctx->csr_cost.ensure((size_t)n + 8);
+        MVS_HIP(hipMemcpyAsync(ctx->csr_ptr.p, ctx->pre_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        if (nf && n) {
             MVS_HIP(hipMemcpyAsync(ctx->csr_view.p, ctx->pre_view.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
             MVS_HIP(hipMemcpyAsync(ctx->csr_q.p, ctx->pre_q.p, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
+    }
+    if (nf) {
         hipLaunchKernelGGL(sort_columns_kernel, dim3((nf + 255) / 256), dim3(256), 0, s, ctx->csr_ptr.p, nf, ctx->csr_view.p, ctx->csr_q.p);
         MVS_LAUNCH_CHECK();
     }
     ctx->csr_nnz = nnz; ctx->csr_faces = nf; ctx->csr_views = n_views;
-    ctx->max_q.ensure(4);
-    MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), s));
-    if (nnz) { hipLaunchKernelGGL(max_kernel, dim3(1024), dim3(256), 0, s, ctx->csr_q.p, (size_t)nnz, (uint32_t*)ctx->max_q.p); MVS_LAUNCH_CHECK(); }
+    local_max_quality(ctx);
     ctx->dc_phase = 1;
-}
-
-static void launch_outlier(mvs_ctx* ctx, const uint32_t* ptr, const uint32_t* counts, uint32_t kmax_known, uint32_t nf, const float* col, float* q, uint8_t* inl, int mode) {
-    hipStream_t s = ctx->stream;
-    if (!nf) return;
-    constexpr uint32_t LDS_PER_ENTRY = 64 * (3 * sizeof(float) + 1);   // 64 faces x (three floats + the inlier flag)
-    uint32_t kmax = kmax_known;
-    if (counts) {
-        ctx->counters.ensure(64);
-        uint32_t* d = reinterpret_cast<uint32_t*>(ctx->counters.p + 48);
-        MVS_HIP(hipMemsetAsync(d, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(max_u32_kernel, dim3(std::min<unsigned>((nf + 255) / 256, 1024u)), dim3(256), 0, s, counts, nf, d); MVS_LAUNCH_CHECK();
-        kmax = read_word(ctx, d);
-    }
-    const uint64_t lds = (uint64_t)std::max<uint32_t>(kmax, 1u) * LDS_PER_ENTRY;
-    if (lds <= 64u * 1024u) hipLaunchKernelGGL(outlier_kernel<true>, dim3((nf + 63) / 64), dim3(64), (size_t)lds, s, ptr, nf, col, q, inl, mode, std::max<uint32_t>(kmax, 1u));
-    else hipLaunchKernelGGL(outlier_kernel<false>, dim3((nf + 63) / 64), dim3(64), 0, s, ptr, nf, col, q, inl, mode, 0u);
-    MVS_LAUNCH_CHECK();
 }
 
 // phase 2: histogram of the local qualities against the (possibly all-reduced) maximum (:283-286)
 void dc_phase2(mvs_ctx* ctx) {
     if (ctx->dc_phase != 1) throw StatusError(MVS_ERR_STATE, "dc_phase2 needs dc_phase1");
-    hipStream_t s = ctx->stream;
     Prof pr(ctx, "dc_post");
-    ctx->hist.ensure(HIST_BINS + 8);
-    MVS_HIP(hipMemsetAsync(ctx->hist.p, 0, (HIST_BINS + 8) * sizeof(uint32_t), s));
-    if (ctx->csr_nnz) {
-        hipLaunchKernelGGL(hist_kernel, dim3(512), dim3(1024), 0, s, ctx->csr_q.p, (size_t)ctx->csr_nnz, ctx->max_q.p, ctx->hist.p);
-        MVS_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(set_count_kernel, dim3(1), dim3(1), 0, s, ctx->hist.p, (uint32_t)ctx->csr_nnz);
-    MVS_LAUNCH_CHECK();
+    hist_clear(ctx);
+    hist_add(ctx, ctx->csr_q.p, (size_t)ctx->csr_nnz);
+    hist_set_count(ctx, (uint32_t)ctx->csr_nnz);
     ctx->dc_phase = 2;
 }
 
 // phase 3: percentile from the (possibly all-reduced) histogram, cost write (:288-298)
 void dc_phase3(mvs_ctx* ctx, mvs_dc_stats* stats) {
     if (ctx->dc_phase != 2) throw StatusError(MVS_ERR_STATE, "dc_phase3 needs dc_phase2");
-    hipStream_t s = ctx->stream;
     ctx->pctl.ensure(4);
     Prof pr(ctx, "dc_post");
-    hipLaunchKernelGGL(percentile_kernel, dim3(1), dim3(1024), 0, s, ctx->hist.p, ctx->max_q.p, 0.995f, ctx->pctl.p, ctx->counters.p + 14);
-    MVS_LAUNCH_CHECK();
+    percentile_of_hist(ctx);
     if (ctx->csr_nnz) {
-        hipLaunchKernelGGL(cost_kernel, dim3(2048), dim3(256), 0, s, ctx->csr_q.p, (size_t)ctx->csr_nnz, ctx->pctl.p, ctx->csr_cost.p);
+        hipLaunchKernelGGL(cost_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->csr_q.p, (size_t)ctx->csr_nnz, ctx->pctl.p, ctx->csr_cost.p);
         MVS_LAUNCH_CHECK();
     }
     pr.end();
-    unsigned long long hc[16];   // counters + (percentile_kernel's report) max quality and percentile: one read-back
+    unsigned long long hc[C_N_STATS];   // counters + (percentile_kernel's report) max quality and percentile: one read-back
     read_words(ctx, ctx->counters.p, hc, (uint32_t)(sizeof(hc) / 4));
-    float mq, pc; { const uint32_t a = (uint32_t)hc[14], b = (uint32_t)hc[15]; memcpy(&mq, &a, 4); memcpy(&pc, &b, 4); }
     mvs_dc_stats& S = ctx->dc_stats;
-    S.cull_backface = hc[C_BACK]; S.cull_angle = hc[C_ANGLE]; S.cull_outside = hc[C_OUTSIDE]; S.cull_occluded = hc[C_OCCL];
-    S.cull_zero_quality = hc[C_ZEROQ]; S.rays = hc[C_RAYS]; S.ray_nodes = hc[C_RNODES]; S.ray_tris = hc[C_RTRIS] * 16ull /* leaf visits -> triangles: 16 per leaf (k_bvh.hip MVS_LEAF_T) */; S.ray_leaf_rounds = hc[13];
-    S.ray_packets = hc[10]; S.ray_packets_generic = hc[11]; S.footprints_lane_group = ctx->dc_stats_deferred; S.footprints_rewalked = hc[C_REWALK];
-    S.nnz = ctx->csr_nnz; S.max_quality = mq; S.percentile = pc;
-    ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p; ctx->csr_q_valid = true;
-    ctx->have_costs = true; ctx->dc_phase = 3;
+    dc_stats_from_counters(hc, ctx->dc_stats_deferred, ctx->csr_nnz, &S);
+    activate_own_table(ctx, true); ctx->dc_phase = 3;
     if (ctx->max_labels > 0) { dc_prune_labels(ctx, (uint32_t)ctx->max_labels); S.nnz = ctx->csr_nnz; }   // label-space compression (option, off by default)
     if (stats) *stats = S;
 }
@@ -1357,30 +1374,14 @@ void dc_prune_labels(mvs_ctx* ctx, uint32_t kmax) {
         MVS_HIP(hipMemcpyAsync(ctx->csr_cost.p, ctx->pcol.p, (size_t)nnz2 * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (have_q) MVS_HIP(hipMemcpyAsync(ctx->csr_q.p, ctx->pre_q.p, (size_t)nnz2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    ctx->csr_nnz = nnz2; ctx->dc_stats.nnz = nnz2; ctx->u_valid = false;
-    ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p;
+    ctx->csr_nnz = nnz2; ctx->dc_stats.nnz = nnz2;
+    activate_own_table(ctx, have_q);
 }
 
 // ---- ranged evaluation inside one context (DESIGN.md section 4 "Ranged data costs"; planner and accounting: dc_ranges.h) ----
 // The context's faces are walked in consecutive ranges.  Phase 1 runs per range as it is; what a range leaves -- (col_ptr, view_id,
 // quality) -- is kept.  The two reductions of postprocess_face_infos (:278-288) then see all ranges: one maximum, one histogram against
 // it, one percentile.  Costs are written range by range straight into ONE table with rebased column pointers.
-__global__ void max_merge_kernel(uint32_t* __restrict__ global_bits, const uint32_t* __restrict__ local_bits) {   // qualities are > 0: uint order = float order
-    if (*local_bits > *global_bits) *global_bits = *local_bits;
-}
-__global__ void rebase_ptr_kernel(const uint32_t* __restrict__ src, uint32_t n, uint32_t base, uint32_t* __restrict__ dst) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[i] + base;
-}
-// cost_kernel fused with the append of a range's columns (no pruning: the range's entries are one contiguous run of the final table)
-__global__ void cost_append_kernel(const uint16_t* __restrict__ view, const float* __restrict__ q, size_t n, const float* __restrict__ pctl,
-                                   uint16_t* __restrict__ view_out, float* __restrict__ q_out, float* __restrict__ cost_out) {
-    const float p = *pctl;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float x = q[i];
-        view_out[i] = view[i]; q_out[i] = x; cost_out[i] = 1.0f - smin(1.0f, x / p);
-    }
-}
 
 // grows a kept array WITHOUT losing its first `used` elements (DBuf::ensure drops the contents)
 template <class T>
@@ -1393,68 +1394,38 @@ static void keep_reserve(mvs_ctx* ctx, DBuf<T>& b, size_t used, size_t need) {
     std::swap(b.p, nb.p); std::swap(b.cap, nb.cap);
 }
 
-static void dc_ranged(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats, const DcPlan& plan) {
+// what phase 1 left of range r (nf faces) goes behind the kept arrays; its maximum is merged into k_max
+static void ranged_keep(mvs_ctx* ctx, DcKept& kept, uint32_t r, uint32_t n_ranges, uint32_t nf) {
     hipStream_t s = ctx->stream;
-    const uint32_t FB = ctx->face_begin, FE = ctx->face_end, NF = FE - FB, V = ctx->n_views;
-    struct Restore { mvs_ctx* c; uint32_t b, e; bool done = false;
-                     ~Restore() { c->face_begin = b; c->face_end = e; c->dc_walk_resident = false;
-                                  if (!done) { c->dc_phase = 0; c->have_costs = false; }            // one range's fragment is no table
-                                  c->k_ptr.release(); c->k_view.release(); c->k_q.release(); } } restore{ctx, FB, FE};   // the kept arrays live for the call only
-    ctx->dc_n_ranges = plan.n; ctx->dc_range_faces = plan.first_faces();
-    ctx->dc_phase = 0; ctx->have_costs = false;   // (a walk that throws half way leaves no phase to continue from: see Restore)
-    DcKept kept;
-    mvs_dc_stats S; memset(&S, 0, sizeof(S));
-    unsigned long long hsum[16] = {0};
-    uint64_t deferred = 0;
-    ctx->k_max.ensure(4);
-    MVS_HIP(hipMemsetAsync(ctx->k_max.p, 0, 4 * sizeof(uint32_t), s));
-    keep_reserve(ctx, ctx->k_ptr, 0, (size_t)NF + plan.n + 1);
-    for (uint32_t r = 0; r < plan.n; ++r) {
-        const DcRange g = plan.range(r);
-        const uint32_t nf = g.end - g.begin;
-        ctx->face_begin = g.begin; ctx->face_end = g.end; ctx->dc_walk_resident = r > 0;
-        // the order can only be rebuilt where it is built: in the first range, before anything is kept -- the walk starts again, once
-        if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
-        const size_t nnz = (size_t)ctx->csr_nnz, at = (size_t)kept.total();
-        if (r == 0) { const size_t guess = nnz + nnz / 8; keep_reserve(ctx, ctx->k_view, 0, guess * plan.n + 1); keep_reserve(ctx, ctx->k_q, 0, guess * plan.n + 1); }
-        keep_reserve(ctx, ctx->k_view, at, at + nnz + 1); keep_reserve(ctx, ctx->k_q, at, at + nnz + 1);
-        MVS_HIP(hipMemcpyAsync(ctx->k_ptr.p + kept.ptr_base.back(), ctx->csr_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        if (nnz) {
-            MVS_HIP(hipMemcpyAsync(ctx->k_view.p + at, ctx->csr_view.p, nnz * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
-            MVS_HIP(hipMemcpyAsync(ctx->k_q.p + at, ctx->csr_q.p, nnz * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
-        hipLaunchKernelGGL(max_merge_kernel, dim3(1), dim3(1), 0, s, ctx->k_max.p, (const uint32_t*)ctx->max_q.p); MVS_LAUNCH_CHECK();
-        kept.push(nf, (uint32_t)nnz);
-        // every counter is a count per (face, view) pair or per ray of this range: summed on the host (the next range clears them)
-        unsigned long long hc[14];
-        read_words(ctx, ctx->counters.p, hc, (uint32_t)(sizeof(hc) / 4));
-        for (int k = 0; k < 14; ++k) hsum[k] += hc[k];
-        S.pairs += ctx->dc_stats.pairs; S.nnz_pre += ctx->dc_stats.nnz_pre; deferred += ctx->dc_stats_deferred;
+    const size_t nnz = (size_t)ctx->csr_nnz, at = (size_t)kept.total();
+    if (r == 0) { const size_t guess = nnz + nnz / 8; keep_reserve(ctx, ctx->k_view, 0, guess * n_ranges + 1); keep_reserve(ctx, ctx->k_q, 0, guess * n_ranges + 1); }
+    keep_reserve(ctx, ctx->k_view, at, at + nnz + 1); keep_reserve(ctx, ctx->k_q, at, at + nnz + 1);
+    MVS_HIP(hipMemcpyAsync(ctx->k_ptr.p + kept.ptr_base.back(), ctx->csr_ptr.p, ((size_t)nf + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (nnz) {
+        MVS_HIP(hipMemcpyAsync(ctx->k_view.p + at, ctx->csr_view.p, nnz * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+        MVS_HIP(hipMemcpyAsync(ctx->k_q.p + at, ctx->csr_q.p, nnz * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    ctx->face_begin = FB; ctx->face_end = FE; ctx->dc_walk_resident = false;
-    if (ctx->mesh_ordered && NF && V) {   // the table of the context's faces, as an unranged pass names it (nothing to evaluate: no order was built)
-        if (FB == 0 && NF == ctx->n_faces) { ctx->t_perm = ctx->f_perm.p; ctx->t_pos = ctx->f_pos.p; }
-        else { ctx->t_perm = ctx->f_perm.p + FB; ctx->t_pos = nullptr; }
-    }
-    // the histogram's "number of values" is one 32-bit word, here as in the reference (an int, histogram.cpp:21)
-    if (kept.total() >= DC_LIMIT_32)
-        throw StatusError(MVS_ERR_UNSUPPORTED, "the faces of this context keep " + std::to_string(kept.total()) + " qualities in all, the histogram of postprocess_face_infos counts its values in "
-                          "32 bits: give the context fewer faces (mvs_scene_set_face_range; the sharded path mvs_shard_* takes one part of the mesh per context)");
+    hipLaunchKernelGGL(max_merge_kernel, dim3(1), dim3(1), 0, s, ctx->k_max.p, (const uint32_t*)ctx->max_q.p); MVS_LAUNCH_CHECK();
+    kept.push(nf, (uint32_t)nnz);
+}
+
+// the merged maximum, one histogram of every kept quality against it, one percentile
+static void ranged_reductions(mvs_ctx* ctx, const DcKept& kept) {
+    hipStream_t s = ctx->stream;
     Prof pr_post(ctx, "dc_post");
-    ctx->max_q.ensure(4); ctx->hist.ensure(HIST_BINS + 8); ctx->pctl.ensure(4);
+    ctx->max_q.ensure(4); ctx->pctl.ensure(4);
     MVS_HIP(hipMemsetAsync(ctx->max_q.p, 0, 2 * sizeof(float), s));
     MVS_HIP(hipMemcpyAsync(ctx->max_q.p, ctx->k_max.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    MVS_HIP(hipMemsetAsync(ctx->hist.p, 0, (HIST_BINS + 8) * sizeof(uint32_t), s));
-    for (size_t r = 0; r < kept.ranges(); ++r) if (kept.entries(r)) {
-        hipLaunchKernelGGL(hist_kernel, dim3(512), dim3(1024), 0, s, ctx->k_q.p + kept.base[r], (size_t)kept.entries(r), ctx->max_q.p, ctx->hist.p);
-        MVS_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(set_count_kernel, dim3(1), dim3(1), 0, s, ctx->hist.p, (uint32_t)kept.total()); MVS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(percentile_kernel, dim3(1), dim3(1024), 0, s, ctx->hist.p, ctx->max_q.p, 0.995f, ctx->pctl.p, ctx->counters.p + 14);
-    MVS_LAUNCH_CHECK();
-    pr_post.end();
-    // the exact 64-bit size of the final table first: only IT has to fit 32-bit column pointers
-    const uint32_t kmax = ctx->max_labels > 0 ? (uint32_t)ctx->max_labels : 0u;
+    hist_clear(ctx);
+    for (size_t r = 0; r < kept.ranges(); ++r) hist_add(ctx, ctx->k_q.p + kept.base[r], (size_t)kept.entries(r));
+    hist_set_count(ctx, (uint32_t)kept.total());
+    percentile_of_hist(ctx);
+}
+
+// costs range by range into the one table, pruned to kmax labels per column (0: as they are); returns its entries, counted in 64 bits first: only IT has to fit 32-bit pointers
+static uint64_t ranged_append(mvs_ctx* ctx, const DcPlan& plan, const DcKept& kept, uint32_t kmax) {
+    hipStream_t s = ctx->stream;
+    const uint32_t FB = ctx->face_begin, NF = ctx->face_end - ctx->face_begin;
     uint64_t total = kept.total();
     Prof pr_app(ctx, "dc_append");
     ctx->csr_ptr.ensure((size_t)NF + 2);
@@ -1491,18 +1462,49 @@ static void dc_ranged(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats,
             if (n) { hipLaunchKernelGGL(cost_append_kernel, dim3(2048), dim3(256), 0, s, kv, kq, n, (const float*)ctx->pctl.p, ctx->csr_view.p + base, ctx->csr_q.p + base, ctx->csr_cost.p + base); MVS_LAUNCH_CHECK(); }
         }
     }
-    pr_app.end();
+    return total;
+}
+
+static void dc_ranged(mvs_ctx* ctx, const mvs_settings* st, mvs_dc_stats* stats, const DcPlan& plan) {
+    const uint32_t FB = ctx->face_begin, FE = ctx->face_end, NF = FE - FB, V = ctx->n_views;
+    struct Restore { mvs_ctx* c; uint32_t b, e; bool done = false;
+                     ~Restore() { c->face_begin = b; c->face_end = e; c->dc_walk_resident = false;
+                                  if (!done) { c->dc_phase = 0; c->have_costs = false; }            // one range's fragment is no table
+                                  c->k_ptr.release(); c->k_view.release(); c->k_q.release(); } } restore{ctx, FB, FE};   // the kept arrays live for the call only
+    ctx->dc_n_ranges = plan.n; ctx->dc_range_faces = plan.first_faces();
+    ctx->dc_phase = 0; ctx->have_costs = false;   // (a walk that throws half way leaves no phase to continue from: see Restore)
+    DcKept kept;
+    mvs_dc_stats S; memset(&S, 0, sizeof(S));
+    unsigned long long hsum[C_N_STATS] = {0};
+    uint64_t deferred = 0;
+    ctx->k_max.ensure(4);
+    MVS_HIP(hipMemsetAsync(ctx->k_max.p, 0, 4 * sizeof(uint32_t), ctx->stream));
+    keep_reserve(ctx, ctx->k_ptr, 0, (size_t)NF + plan.n + 1);
+    for (uint32_t r = 0; r < plan.n; ++r) {
+        const DcRange g = plan.range(r);
+        ctx->face_begin = g.begin; ctx->face_end = g.end; ctx->dc_walk_resident = r > 0;
+        // the order can only be rebuilt where it is built: in the first range, before anything is kept -- the walk starts again, once
+        if (dc_phase1_once(ctx, st)) (void)dc_phase1_once(ctx, st);
+        ranged_keep(ctx, kept, r, plan.n, g.end - g.begin);
+        // every counter is a count per (face, view) pair or per ray of this range: summed on the host (the next range clears them)
+        unsigned long long hc[C_N_SUMMED];
+        read_words(ctx, ctx->counters.p, hc, (uint32_t)(sizeof(hc) / 4));
+        dc_counters_add(hsum, hc);
+        S.pairs += ctx->dc_stats.pairs; S.nnz_pre += ctx->dc_stats.nnz_pre; deferred += ctx->dc_stats_deferred;
+    }
+    ctx->face_begin = FB; ctx->face_end = FE; ctx->dc_walk_resident = false;
+    if (NF && V) name_table_order(ctx, FB, NF);   // the table of the context's faces, as an unranged pass names it (nothing to evaluate: no order was built)
+    // the histogram's "number of values" is one 32-bit word, here as in the reference (an int, histogram.cpp:21)
+    if (kept.total() >= DC_LIMIT_32)
+        throw StatusError(MVS_ERR_UNSUPPORTED, "the faces of this context keep " + std::to_string(kept.total()) + " qualities in all, the histogram of postprocess_face_infos counts its values in "
+                          "32 bits: give the context fewer faces (mvs_scene_set_face_range; the sharded path mvs_shard_* takes one part of the mesh per context)");
+    ranged_reductions(ctx, kept);
+    const uint64_t total = ranged_append(ctx, plan, kept, ctx->max_labels > 0 ? (uint32_t)ctx->max_labels : 0u);
     ctx->csr_nnz = total; ctx->csr_faces = NF; ctx->csr_views = V;
-    unsigned long long rep[2];
-    read_words(ctx, ctx->counters.p + 14, rep, 4);
-    float mq, pc; { const uint32_t a = (uint32_t)rep[0], b = (uint32_t)rep[1]; memcpy(&mq, &a, 4); memcpy(&pc, &b, 4); }
-    S.cull_backface = hsum[C_BACK]; S.cull_angle = hsum[C_ANGLE]; S.cull_outside = hsum[C_OUTSIDE]; S.cull_occluded = hsum[C_OCCL];
-    S.cull_zero_quality = hsum[C_ZEROQ]; S.rays = hsum[C_RAYS]; S.ray_nodes = hsum[C_RNODES]; S.ray_tris = hsum[C_RTRIS] * 16ull; S.ray_leaf_rounds = hsum[13];
-    S.ray_packets = hsum[10]; S.ray_packets_generic = hsum[11]; S.footprints_lane_group = deferred; S.footprints_rewalked = hsum[C_REWALK];
-    S.nnz = total; S.max_quality = mq; S.percentile = pc;
+    read_words(ctx, ctx->counters.p + C_MAX_Q_BITS, hsum + C_MAX_Q_BITS, 4);   // the report of the one percentile
+    dc_stats_from_counters(hsum, deferred, total, &S);
     ctx->dc_stats = S;
-    ctx->r_ptr = ctx->csr_ptr.p; ctx->r_view = ctx->csr_view.p; ctx->r_cost = ctx->csr_cost.p; ctx->csr_q_valid = true; ctx->u_valid = false;
-    ctx->have_costs = true; ctx->dc_phase = 3; restore.done = true;
+    activate_own_table(ctx, true); ctx->dc_phase = 3; restore.done = true;
     if (stats) *stats = S;
 }
 

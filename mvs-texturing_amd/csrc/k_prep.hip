@@ -7,6 +7,7 @@
 // covers every view (grid.z = view).  Masks are bit-packed, rows padded to
 // 32-bit words, so that the flood fill and the erosion are word-parallel.
 #include "ctx.h"
+#include "dc_counters.h"
 
 namespace mvs {
 
@@ -395,7 +396,7 @@ void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const s
     uint32_t* zero = ctx->mask_zero.p;
     uint32_t* ra = ctx->mask_all.p;   // ping
     uint32_t* rb = ctx->mask_tmp.p;   // pong
-    uint32_t* d_changed = (uint32_t*)ctx->counters.p + 64;  // scratch words inside the counters block
+    uint32_t* d_changed = (uint32_t*)(ctx->counters.p + C_PREP);  // two words borrowed from the counters block (dc_counters.h)
     uint32_t* d_any_seed = d_changed + 1;
     MVS_HIP(hipMemsetAsync(d_changed, 0, 2 * sizeof(uint32_t), s));
     if (fast) {

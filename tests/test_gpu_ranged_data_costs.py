@@ -6,6 +6,7 @@ may exceed the unranged ones (a vertex shared by faces of two ranges is traced o
 import copy
 import ctypes as C
 import json
+import os
 
 import numpy as np
 import pytest
@@ -387,3 +388,113 @@ def test_nothing_to_evaluate_with_the_option_set():
         _same(_pass(c, s, 8 * 50), _pass(c, s, 0))
     finally:
         c.close()
+
+
+# How often one data_costs call records each dc_* stage (mvs_ctx_get_profile), per case: (context options, settings).  The dictionaries
+# were read off the build of the commit BEFORE the host code of csrc/k_dc.hip was split into a function per stage, with _stage_counts
+# below; a stage that moves between functions keeps its number of brackets.  "gmi_none" spells out what Settings() defaults to, so it
+# equals "defaults"; "area_damping" is one case more than were asked for (the area term's kernels, the lane group on colours alone).
+# The route of mvs_postprocess_face_infos has a test of its own below: the call itself runs on a temporary context whose profile no
+# call can read.
+STAGE_CASES = {
+    "defaults": (dict(), dict()),
+    "clamping": (dict(), dict(outlier_removal="gauss_clamping")),
+    "novis": (dict(), dict(geometric_visibility_test=False)),
+    "gmi_none": (dict(), dict(data_term="gmi", outlier_removal="none")),        # the WORDS kernels
+    "area_damping": (dict(), dict(data_term="area", outlier_removal="gauss_damping")),
+    "keep4": (dict(max_labels=4), dict()),
+    "three_ranges": (dict(dc_range_pairs=12 * 3227), dict()),
+}
+_ONE_RANGE = dict(dc_order=1, dc_bvh_build=1, dc_prep=1, dc_cull=1, dc_need=1, dc_rays=1, dc_rank_scan=1, dc_face_info=1, dc_csr=1, dc_post=3)   # dc_post: local maximum, histogram, percentile + costs
+STAGE_COUNTS = {
+    "defaults": _ONE_RANGE,
+    "clamping": _ONE_RANGE,
+    "novis": dict(dc_order=1, dc_prep=1, dc_cull=1, dc_rank_scan=1, dc_face_info=1, dc_csr=1, dc_post=3),
+    "gmi_none": _ONE_RANGE,
+    "area_damping": _ONE_RANGE,
+    "keep4": dict(_ONE_RANGE, dc_prune=1),
+    "three_ranges": dict(dc_order=1, dc_bvh_build=1, dc_prep=1, dc_cull=3, dc_need=3, dc_rays=3, dc_rank_scan=3, dc_face_info=3, dc_csr=3, dc_post=4, dc_append=1),
+}
+
+
+def _stage_counts(case):
+    """({stage: times recorded} of one data_costs call after a warm-up pass, its table, the table of the same call with stats = 1)"""
+    opts, kw = STAGE_CASES[case]
+    s = get_scene("bumpy")
+    c = M.Context(0)
+    try:
+        _load(c, s)
+        c.set_option("profile", 1)
+        for k, v in opts.items():
+            c.set_option(k, v)
+        c.data_costs(M.Settings(**kw)); c.get_profile()               # warm-up: allocations, the first order / BVH
+        if case == "three_ranges":
+            assert c.dc_ranges() == (3, 3227)
+        c.data_costs(M.Settings(**kw))
+        p = c.get_profile()
+        table = c.costs_download()
+        c.set_option("stats", 1)
+        c.data_costs(M.Settings(**kw))
+        return {k: v[1] for k, v in p.items() if k.startswith("dc_")}, table, c.costs_download()
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("case", list(STAGE_CASES))
+def test_every_stage_is_recorded_as_often_as_before_the_split(case):
+    counts, table, table_stats = _stage_counts(case)
+    assert counts == STAGE_COUNTS[case]
+    _same_table(table_stats, table)                                   # the STATS instantiation of every kernel computes the same table
+
+
+# the same for postprocess_face_infos on a caller's infos: dc_postprocess, dc_phase2, dc_phase3 as mvs_postprocess_face_infos runs them,
+# but on a context of the test's (tests/tools/dc_postprocess_ctx.hip).  Read off the same parent build.
+POSTPROCESS_STAGE_COUNTS = {"none": dict(dc_post=2), "gauss_clamping": dict(dc_post=2)}   # histogram, percentile + costs
+
+
+def _postprocess_on_context(mode_name, case_name="outlier_mix_lds"):
+    """({stage: times recorded} of one pass after a warm-up pass, its table and statistics, the table of the same pass with stats = 1)"""
+    import postprocess_model as PM
+    tool = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "libdc_postprocess_ctx.so"))
+    tool.test_dc_postprocess_on.restype = C.c_int
+    V, ptr, view, q, col = PM.get_case(case_name).args()
+    ptr = np.ascontiguousarray(ptr, np.uint32); n = int(ptr[-1])
+    face = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr.astype(np.int64)))
+    src = ptr[face].astype(np.int64) + ptr[face + 1] - 1 - np.arange(n)       # every face's list reversed
+    rv, rq, rc = np.ascontiguousarray(view[src], np.uint16), np.ascontiguousarray(q[src], np.float32), np.ascontiguousarray(col[src], np.float32)
+    st = M.Settings(outlier_removal=mode_name)
+    c = M.Context(0)
+
+    def run():
+        ds = M.viewsel.DcStats()
+        rcode = tool.test_dc_postprocess_on(c.h, C.c_uint32(len(ptr) - 1), C.c_uint32(V), C.c_void_p(ptr.ctypes.data),
+                                            C.c_void_p(rv.ctypes.data), C.c_void_p(rq.ctypes.data), C.c_void_p(rc.ctypes.data), C.byref(st), C.byref(ds))
+        assert rcode == 0, c.L.mvs_last_error()
+        return ds
+    try:
+        c.set_option("profile", 1)
+        run(); c.get_profile()
+        ds = run()
+        p = c.get_profile()
+        table = c.costs_download()
+        c.set_option("stats", 1)
+        run()
+        return {k: v[1] for k, v in p.items() if k.startswith("dc_")}, table, ds, c.costs_download()
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("mode", [0, 2], ids=["none", "gauss_clamping"])
+def test_postprocess_route_records_its_stages_as_before_the_split(mode):
+    """crafted infos (tests/tools/postprocess_model.py) through dc_postprocess + phases 2 and 3 on a context with the profile on: the
+    stage counts of the parent, the table of the plain reference bit for bit, the same table with stats = 1"""
+    import postprocess_model as PM
+    mode_name = dict(PM.MODES)[mode]
+    counts, got, ds, got_stats = _postprocess_on_context(mode_name)
+    assert counts == POSTPROCESS_STAGE_COUNTS[mode_name]
+    col_ptr, view, cost, q, rc, mx, pct, _ = PM.reference_of("outlier_mix_lds", mode)
+    assert got.nnz == len(view) == ds.nnz and np.array_equal(got.col_ptr, col_ptr) and np.array_equal(got.view_id, view)
+    assert np.array_equal(got.cost.view(np.uint32), cost.view(np.uint32))
+    assert np.float32(ds.max_quality).view(np.uint32) == np.float32(mx).view(np.uint32)
+    assert np.float32(ds.percentile).view(np.uint32) == np.float32(pct).view(np.uint32)
+    _same_table(got_stats, got)
