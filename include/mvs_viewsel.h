@@ -493,8 +493,8 @@ void mvs_gsl_system_free(mvs_gsl_system* s);
  *   validity[i] in {0, 255}, blending[i] in {0, 64, 255}.
  * params.max_pixels (0 = no cap): when the pixel total exceeds it the call fails with MVS_ERR_UNSUPPORTED before the pixel arrays
  * are allocated; stats (patches, merged, listed_faces, pixels) is filled all the same.  MVS_ERR_LABELING / MVS_ERR_STATE as row f5.
- * With out_on_device the arrays are device pointers owned by the context (valid until its next texture_patches call or its
- * destruction), otherwise malloc'ed host copies (mvs_patch_set_free). */
+ * With out_on_device the arrays are device pointers owned by the context (valid until its next texture_patches or debug_patches
+ * call or its destruction), otherwise malloc'ed host copies (mvs_patch_set_free). */
 typedef struct mvs_patch_params {
     uint64_t max_pixels;      /* refuse a result of more pixels than this (0: no cap) */
     uint64_t reserved;
@@ -668,6 +668,37 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
                               const char* prefix, const mvs_model_params* params, mvs_model_stats* stats);
 void mvs_model_text_free(mvs_model_text* t);
 mvs_status mvs_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height, int32_t level);
+
+/* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
+ * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
+ * the view list -- stamped all over with its three-digit id in cells of 13 x 6 pixels, and rows f6 (without adjust_colors), f8 and f9
+ * run on those images: a model whose faces show which view textures them.  The definition is DESIGN.md section 4 "Debug model"; every
+ * array is the same bits on any device and in every run.  view_ids: host array with one id per view, or NULL: the position (what
+ * from_images_and_camera_files assigns); an id above 999 is MVS_ERR_UNSUPPORTED (upstream asserts).  Upstream's debug pass would run
+ * hole filling on the faces of label 0; this library has none: faces of label 0 appear in no patch, as in rows f6 to f9.
+ *   mvs_debug_view_style: background and font colour of the view at `position` (host only, no device needed).
+ *   mvs_ctx_debug_embeddings: generate_debug_embeddings for n images of the caller's sizes (each side 0 .. 65535) at positions
+ *     first_position + i, packed back to back as RGB8 row-major into rgb_out (3 * sum of width * height bytes, host or device; no
+ *     alignment asked of a device pointer).  Needs neither mesh nor views.
+ *   mvs_ctx_debug_patches: the patch set of the debug path exactly as row f6 lays it out (rows f8 and f9 take it unchanged): label,
+ *     box, face_ptr, faces, texcoords and pix_ptr are row f6's for the same labels; image = byte / 255.0f of the view's debug image
+ *     inside the view, (1, 0, 1) outside; validity 255 and blending 0 for every pixel (no adjust_colors: what TexturePatch's
+ *     constructor leaves).  The context's real images are neither read nor written.  stats: valid_pixels = pixels, near_pixels =
+ *     degenerate_faces = 0, ms_mark = 0, ms_resolve = the pixel kernel.  params.max_pixels and the errors are row f6's.  With
+ *     out_on_device the arrays are the context's row-f6 buffers (valid until its next texture_patches or debug_patches call).
+ *   mvs_ctx_view_selection_model: debug patches, row f8, row f9's save_model with everything left on the device in between: writes
+ *     `<prefix>_view_selection.obj`, `.mtl` and `<prefix>_view_selection_material<a>_map_Kd.png`.  Any params / stats may be NULL. */
+mvs_status mvs_debug_view_style(uint32_t position, uint8_t bg[3], uint8_t fg[3]);
+mvs_status mvs_ctx_debug_embeddings(mvs_ctx* ctx, uint32_t n, const int32_t* width, const int32_t* height, const uint32_t* view_ids,
+                                    uint32_t first_position, uint8_t* rgb_out, int out_on_device);
+mvs_status mvs_ctx_debug_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const uint32_t* labels,
+                                 int labels_on_device, const uint32_t* view_ids, const mvs_patch_params* params, mvs_patch_set* out,
+                                 int out_on_device, mvs_patch_stats* stats);
+mvs_status mvs_ctx_view_selection_model(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const uint32_t* labels,
+                                        int labels_on_device, const uint32_t* view_ids, const float* vertex_normals, int normals_on_device,
+                                        const char* prefix, const mvs_patch_params* patch_params, const mvs_atlas_params* atlas_params,
+                                        const mvs_model_params* model_params, mvs_patch_stats* patch_stats, mvs_atlas_stats* atlas_stats,
+                                        mvs_model_stats* model_stats);
 
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is

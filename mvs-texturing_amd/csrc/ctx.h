@@ -137,6 +137,7 @@ struct TexPatchDev;   // row f6 (k_texpatch.hip)
 struct LslDev;   // row f7 (k_localseam.hip)
 struct AtlasDev; // row f8 (k_atlas.hip)
 struct ModelDev; // row f9 (k_model.hip)
+struct DebugDev; // row f10 (k_debug.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -264,6 +265,7 @@ struct mvs_ctx {
     mvs::DBuf<uint32_t> row_adj_ptr, row_adj, row_labels; mvs::HBuf<char> row_pin;
     mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
     mvs::ModelDev* model = nullptr;   // row f9 (k_model.hip)
+    mvs::DebugDev* debug = nullptr;   // row f10 (k_debug.hip)
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -394,6 +396,8 @@ void lsl_release(mvs_ctx* ctx);
 void atlas_release(mvs_ctx* ctx);
 // frees the buffers of row f9 (k_model.hip)
 void model_release(mvs_ctx* ctx);
+// frees the buffers of row f10 (k_debug.hip)
+void debug_release(mvs_ctx* ctx);
 // rows f5 / f6 (k_texpatch.hip): the views' parameters on the device and the checks on the caller's labels and faces -- throws MVS_ERR_LABELING
 // for a label above the number of views, MVS_ERR_INVALID for a vertex id >= n_verts; `who` starts the message
 void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, const char* who);

@@ -140,17 +140,11 @@ void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr,
     MVS_LAUNCH_CHECK();
 }
 
-// ---- row f6 ----
-// per-context buffers of row f6, allocated on first use, freed with the context (texpatch_release)
-struct TexPatchDev {
-    PatchTables pt;
-    DBuf<uint32_t> label, cnt, face_ptr, faces, epid, nchunk, chunk_ptr, win_in, win_near, big;
-    DBuf<int4> box; DBuf<float> texcoords, image, adjust; DBuf<unsigned long long> npix, pix_ptr, c64; DBuf<uint8_t> validity, blending;
-};
+// ---- row f6 (TexPatchDev: rows.h) ----
 void texpatch_release(mvs_ctx* ctx) { delete ctx->texpatch; ctx->texpatch = nullptr; }
 
 namespace {
-constexpr uint32_t CHUNK = 1024;          // pixels of one patch a resolve block handles (4 per thread, 256 apart: coalesced rows)
+constexpr uint32_t CHUNK = TEXPATCH_CHUNK;   // pixels of one patch a resolve block handles (4 per thread, 256 apart: coalesced rows)
 constexpr uint32_t GROUP = 8;             // lanes of mark_kernel per list entry
 constexpr uint32_t SMALL_MAX = 512;       // pixel ranges above this many pixels go to a block each (mark_big_kernel)
 constexpr uint32_t BIG_BLOCKS = 2048;     // grid of mark_big_kernel: blocks stride over the list of large entries
@@ -326,16 +320,20 @@ __global__ void __launch_bounds__(256) tp_resolve_kernel(uint32_t P, const uint3
     }
 }
 
-// the whole row on the context's stream; the pixel arrays are left in D
-void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const float* d_adjust,
-                  const mvs_patch_params& P, mvs_patch_stats& S, uint32_t& n_listed, uint64_t& n_pixels) {
+}  // namespace
+
+// the geometry half of row f6, which the debug model (k_debug.hip) runs as well: checks, patch tables, per-patch label / frame / sizes,
+// the three scans, the lists and texture coordinates, and room for the pixel arrays.  Marks tm three times (begin, tables, lists).
+// *n_chunks arrives with the next drain of the stream.
+void texpatch_geometry(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const mvs_patch_params& P,
+                       mvs_patch_stats& S, uint32_t& n_listed, uint64_t& n_pixels, uint32_t* n_chunks, StageTimer<5>& tm, const char* who) {
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces;
     PatchTables& T = D.pt;
-    StageTimer<5> tm(s);   // marks: begin, tables, lists, mark, resolve
+    const std::string w(who);
     tm.mark();
-    patch_check_inputs(ctx, T, d_labels, "texture_patches");
-    build_patch_tables(ctx, T, d_adj_ptr, d_adj, d_labels, "texture_patches");
+    patch_check_inputs(ctx, T, d_labels, who);
+    build_patch_tables(ctx, T, d_adj_ptr, d_adj, d_labels, who);
     tm.mark();
     // geometry, sizes, the three scans, the lists
     const uint32_t NP = T.n_patches, C = T.C;
@@ -357,20 +355,51 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
     n_listed = listed; n_pixels = total;
     S.patches = NP; S.merged = T.n_merged; S.listed_faces = listed; S.pixels = total;
     if (P.max_pixels && total > P.max_pixels)
-        throw StatusError(MVS_ERR_UNSUPPORTED, "texture_patches: " + std::to_string(total) + " pixels exceed params.max_pixels = " + std::to_string(P.max_pixels));
-    if (total / CHUNK + NP >= 0x7FFFFFFFull) throw StatusError(MVS_ERR_UNSUPPORTED, "texture_patches: too many pixels for one call");
+        throw StatusError(MVS_ERR_UNSUPPORTED, w + ": " + std::to_string(total) + " pixels exceed params.max_pixels = " + std::to_string(P.max_pixels));
+    if (total / CHUNK + NP >= 0x7FFFFFFFull) throw StatusError(MVS_ERR_UNSUPPORTED, w + ": too many pixels for one call");
     exclusive_scan_u32(ctx, D.nchunk.p, D.chunk_ptr.p, NP, D.chunk_ptr.p + NP);
     D.faces.ensure((size_t)listed + 1); D.epid.ensure((size_t)listed + 1); D.big.ensure((size_t)listed + 1); D.texcoords.ensure(6 * (size_t)listed + 6);
     hipLaunchKernelGGL(tp_entry_kernel, dim3(grid(F)), dim3(256), 0, s, d_labels, F, (const uint32_t*)T.fcand.p, (const uint32_t*)T.fpid.p,
                        (const uint32_t*)T.fpos.p, (const uint32_t*)T.parent.p, (const int4*)T.box.p, (const float2*)T.pc.p,
                        (const uint32_t*)D.face_ptr.p, D.faces.p, D.epid.p, D.texcoords.p);
     MVS_LAUNCH_CHECK();
-    uint32_t n_chunks = 0;
-    MVS_HIP(hipMemcpyAsync(&n_chunks, D.chunk_ptr.p + NP, sizeof(n_chunks), hipMemcpyDeviceToHost, s));
+    MVS_HIP(hipMemcpyAsync(n_chunks, D.chunk_ptr.p + NP, sizeof(*n_chunks), hipMemcpyDeviceToHost, s));
     tm.mark();
+    D.image.ensure(3 * (size_t)total + 3); D.validity.ensure((size_t)total + 1); D.blending.ensure((size_t)total + 1);
+}
+// the set as the caller receives it: the context's device arrays, or malloc'ed host copies
+void texpatch_output(mvs_ctx* ctx, TexPatchDev& D, uint32_t n_listed, uint64_t n_pixels, mvs_patch_set* out, int out_on_device) {
+    hipStream_t s = ctx->stream;
+    const uint32_t NP = D.pt.n_patches;
+    out->n_patches = NP; out->n_listed = n_listed; out->n_pixels = n_pixels;
+    if (out_on_device) {
+        out->label = D.label.p; out->box = (int32_t*)D.box.p; out->face_ptr = D.face_ptr.p; out->faces = D.faces.p; out->texcoords = D.texcoords.p;
+        out->pix_ptr = (uint64_t*)D.pix_ptr.p; out->image = D.image.p; out->validity = D.validity.p; out->blending = D.blending.p;
+    } else {
+        download(s, out, mvs_patch_set_free, [&] {
+            out->label = host_copy(D.label.p, NP, s); out->box = host_copy((const int32_t*)D.box.p, 4 * (size_t)NP, s);
+            out->face_ptr = host_copy(D.face_ptr.p, (size_t)NP + 1, s); out->faces = host_copy(D.faces.p, n_listed, s);
+            out->texcoords = host_copy(D.texcoords.p, 6 * (size_t)n_listed, s);
+            out->pix_ptr = host_copy((const uint64_t*)D.pix_ptr.p, (size_t)NP + 1, s);
+            out->image = host_copy(D.image.p, 3 * (size_t)n_pixels, s); out->validity = host_copy(D.validity.p, (size_t)n_pixels, s);
+            out->blending = host_copy(D.blending.p, (size_t)n_pixels, s);
+        });
+    }
+}
+
+namespace {
+// the whole row on the context's stream; the pixel arrays are left in D
+void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const float* d_adjust,
+                  const mvs_patch_params& P, mvs_patch_stats& S, uint32_t& n_listed, uint64_t& n_pixels) {
+    hipStream_t s = ctx->stream;
+    StageTimer<5> tm(s);   // marks: begin, tables, lists, mark, resolve
+    uint32_t n_chunks = 0;
+    texpatch_geometry(ctx, D, d_adj_ptr, d_adj, d_labels, P, S, n_listed, n_pixels, &n_chunks, tm, "texture_patches");
+    PatchTables& T = D.pt;
+    const uint32_t NP = T.n_patches, listed = n_listed;
+    const unsigned long long total = n_pixels;
     // mark
     D.win_in.ensure((size_t)total + 1); D.win_near.ensure((size_t)total + 1);
-    D.image.ensure(3 * (size_t)total + 3); D.validity.ensure((size_t)total + 1); D.blending.ensure((size_t)total + 1);
     MVS_HIP(hipMemsetAsync(D.win_in.p, 0, (size_t)total * sizeof(uint32_t), s));
     MVS_HIP(hipMemsetAsync(D.win_near.p, 0xFF, (size_t)total * sizeof(uint32_t), s));
     if (listed) {
@@ -435,21 +464,7 @@ mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const 
         if (F) MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
         uint32_t n_listed = 0; uint64_t n_pixels = 0;
         run_with_stats(s, stats, S, [&] { run_texpatch(ctx, D, g.adj_ptr, g.adj, g.labels, d_adjust, P, S, n_listed, n_pixels); });
-        const uint32_t NP = D.pt.n_patches;
-        out->n_patches = NP; out->n_listed = n_listed; out->n_pixels = n_pixels;
-        if (out_on_device) {
-            out->label = D.label.p; out->box = (int32_t*)D.box.p; out->face_ptr = D.face_ptr.p; out->faces = D.faces.p; out->texcoords = D.texcoords.p;
-            out->pix_ptr = (uint64_t*)D.pix_ptr.p; out->image = D.image.p; out->validity = D.validity.p; out->blending = D.blending.p;
-        } else {
-            download(s, out, mvs_patch_set_free, [&] {
-                out->label = host_copy(D.label.p, NP, s); out->box = host_copy((const int32_t*)D.box.p, 4 * (size_t)NP, s);
-                out->face_ptr = host_copy(D.face_ptr.p, (size_t)NP + 1, s); out->faces = host_copy(D.faces.p, n_listed, s);
-                out->texcoords = host_copy(D.texcoords.p, 6 * (size_t)n_listed, s);
-                out->pix_ptr = host_copy((const uint64_t*)D.pix_ptr.p, (size_t)NP + 1, s);
-                out->image = host_copy(D.image.p, 3 * (size_t)n_pixels, s); out->validity = host_copy(D.validity.p, (size_t)n_pixels, s);
-                out->blending = host_copy(D.blending.p, (size_t)n_pixels, s);
-            });
-        }
+        texpatch_output(ctx, D, n_listed, n_pixels, out, out_on_device);
     });
 }
 

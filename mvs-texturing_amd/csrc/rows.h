@@ -152,4 +152,21 @@ inline uint32_t upload_chunk_tables(mvs_ctx* ctx, const unsigned long long* pix_
     return h_ptr[NP];
 }
 
+// ---- row f6's buffers and its geometry half, which the debug model (row f10, k_debug.hip) shares ----
+// per-context buffers of row f6, allocated on first use, freed with the context (texpatch_release)
+struct TexPatchDev {
+    PatchTables pt;
+    DBuf<uint32_t> label, cnt, face_ptr, faces, epid, nchunk, chunk_ptr, win_in, win_near, big;
+    DBuf<int4> box; DBuf<float> texcoords, image, adjust; DBuf<unsigned long long> npix, pix_ptr, c64; DBuf<uint8_t> validity, blending;
+};
+constexpr uint32_t TEXPATCH_CHUNK = 1024;   // pixels of one patch per block of the kernels that run on chunk_ptr (resolve, debug_patch_kernel)
+// k_texpatch.hip: everything of row f6 before its pixels -- the input checks, build_patch_tables, label / box / face_ptr / faces /
+// texcoords / pix_ptr / chunk_ptr in D and room for image, validity and blending; fills S.patches, merged, listed_faces, pixels and
+// refuses max_pixels (`who` starts the messages).  Marks tm three times: begin, tables, lists.  *n_chunks (blocks of TEXPATCH_CHUNK
+// pixels, chunk_ptr[n_patches]) arrives with the next drain of the stream.
+void texpatch_geometry(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, const mvs_patch_params& P,
+                       mvs_patch_stats& S, uint32_t& n_listed, uint64_t& n_pixels, uint32_t* n_chunks, StageTimer<5>& tm, const char* who);
+// D as an mvs_patch_set: the context's device arrays, or malloc'ed host copies (mvs_patch_set_free)
+void texpatch_output(mvs_ctx* ctx, TexPatchDev& D, uint32_t n_listed, uint64_t n_pixels, mvs_patch_set* out, int out_on_device);
+
 }  // namespace mvs

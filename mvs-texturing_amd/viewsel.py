@@ -278,6 +278,10 @@ def load_library():
         "mvs_ctx_build_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelText), i32, C.POINTER(ModelStats)],
         "mvs_ctx_save_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelStats)],
         "mvs_write_png": [C.c_char_p, vp, u32, u32, C.c_int32],
+        "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
+        "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
+        "mvs_ctx_view_selection_model": [vp, vp, vp, i32, vp, i32, vp, vp, i32, C.c_char_p, C.POINTER(PatchParams), C.POINTER(AtlasParams), C.POINTER(ModelParams),
+                                         C.POINTER(PatchStats), C.POINTER(AtlasStats), C.POINTER(ModelStats)],
         "mvs_data_costs_stream": [C.POINTER(CMesh), C.POINTER(CView), u32, C.POINTER(Settings), vp, vp, C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_view_selection_cached": [u64, u32, u32, u64, vp, vp, C.POINTER(MrfParams), vp, C.POINTER(MrfStats)],
     }
@@ -667,6 +671,10 @@ class Context:
         res, st = PatchSet(), PatchStats()
         self._keep["patches"] = (adj_ptr, adj, labels, corner_adjust)
         rc = self.L.mvs_ctx_texture_patches(self.h, pa, pb, d0, pl, dl, pc, dc, C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        return self._patch_result(rc, res, st, on_device)
+
+    def _patch_result(self, rc, res, st, on_device):
+        """(arrays, stats) of a call that fills a PatchSet and PatchStats (texture_patches, debug_patches)"""
         stats = {k: int(getattr(st, k)) for k in PATCH_COUNTS}
         stats.update({k: float(getattr(st, k)) for k in PATCH_MS})
         _check_with_stats(self.L, rc, stats)
@@ -678,6 +686,59 @@ class Context:
             return out, stats
         out["box"] = out["box"].reshape(P, 4); out["texcoords"] = out["texcoords"].reshape(NL, 3, 2); out["image"] = out["image"].reshape(NP, 3)
         return out, stats
+
+    def debug_embeddings(self, sizes, view_ids=None, first_position=0, out=None):
+        """Row f10: generate_debug_embeddings (DESIGN.md section 4 "Debug model") for images of the given (width, height) sizes at
+        positions first_position + i of the view list: each a flat colour of its own stamped with its three-digit id (view_ids[i], or
+        the position).  Returns the images packed back to back as one flat uint8 array (RGB, row-major), or fills `out` -- a CUDA
+        tensor or DevArray of 3 * sum(w * h) bytes, any alignment -- and returns it.  An id above 999 raises MvsError (status 7)."""
+        sizes = np.ascontiguousarray(sizes, np.int32).reshape(-1, 2)
+        n = len(sizes)
+        w = np.ascontiguousarray(sizes[:, 0]); h = np.ascontiguousarray(sizes[:, 1])
+        ids = None if view_ids is None else np.ascontiguousarray(view_ids, np.uint32)
+        assert ids is None or ids.shape == (n,)
+        total = 3 * int((w.astype(np.int64) * h.astype(np.int64)).sum())
+        if out is None:
+            out = np.zeros(total, np.uint8)
+        po, dev = _ptr(out)
+        assert (int(out.numel()) if _is_torch(out) else int(out.shape[0])) >= total
+        _check(self.L, self.L.mvs_ctx_debug_embeddings(self.h, n, _ptr(w)[0], _ptr(h)[0], _ptr(ids)[0], int(first_position), po, dev))
+        return out
+
+    def debug_patches(self, adj_ptr, adj, labels, view_ids=None, params=None, on_device=False):
+        """Row f10: the patch set of the view-selection debug model -- texture_patches' geometry (label, box, face_ptr, faces, texcoords,
+        pix_ptr: the same bits) with the pixels of the views' debug images (debug_embeddings of the context's view sizes), validity 255
+        and blending 0 everywhere; the context's images are not touched.  view_ids: one id per view (host), None = the positions.
+        Returns (arrays, stats) as texture_patches does; with on_device=True DevArrays owned by the context (valid until the next
+        texture_patches or debug_patches call)."""
+        pa, d0 = _ptr(adj_ptr); pb, d1 = _ptr(adj); pl, dl = _ptr(labels)
+        assert d0 == d1
+        ids = None if view_ids is None else np.ascontiguousarray(view_ids, np.uint32)
+        p = params or default_patch_params()
+        res, st = PatchSet(), PatchStats()
+        self._keep["patches"] = (adj_ptr, adj, labels, ids)
+        rc = self.L.mvs_ctx_debug_patches(self.h, pa, pb, d0, pl, dl, _ptr(ids)[0], C.byref(p), C.byref(res), 1 if on_device else 0, C.byref(st))
+        return self._patch_result(rc, res, st, on_device)
+
+    def view_selection_model(self, adj_ptr, adj, labels, prefix, view_ids=None, vertex_normals=None, patch_params=None, atlas_params=None, model_params=None):
+        """Row f10 to files (`texrecon --view_selection_model`): debug_patches, texture_atlases and save_model with everything left on
+        the device in between: writes `<prefix>_view_selection.obj`, `.mtl` and the atlas PNGs.  Returns the stats of the three rows
+        as dict(patches=..., atlases=..., model=...)."""
+        pa, d0 = _ptr(adj_ptr); pb, d1 = _ptr(adj); pl, dl = _ptr(labels)
+        assert d0 == d1
+        ids = None if view_ids is None else np.ascontiguousarray(view_ids, np.uint32)
+        if vertex_normals is not None and not (_is_torch(vertex_normals) or isinstance(vertex_normals, DevArray)):
+            vertex_normals = np.ascontiguousarray(vertex_normals, np.float32).reshape(-1)
+        pn, dn = _ptr(vertex_normals)
+        pp, ap, mp = patch_params or default_patch_params(), atlas_params or default_atlas_params(), model_params or default_model_params()
+        ps, as_, ms = PatchStats(), AtlasStats(), ModelStats()
+        self._keep["debug_model"] = (adj_ptr, adj, labels, ids, vertex_normals)
+        rc = self.L.mvs_ctx_view_selection_model(self.h, pa, pb, d0, pl, dl, _ptr(ids)[0], pn, dn, os.fspath(prefix).encode(), C.byref(pp), C.byref(ap), C.byref(mp),
+                                                 C.byref(ps), C.byref(as_), C.byref(ms))
+        stats = dict(patches={k: (int if k in PATCH_COUNTS else float)(getattr(ps, k)) for k in PATCH_COUNTS + PATCH_MS},
+                     atlases={k: (int if k in ATLAS_COUNTS else float)(getattr(as_, k)) for k in ATLAS_COUNTS + ATLAS_MS}, model=_model_stats(ms))
+        _check_with_stats(self.L, rc, stats)
+        return stats
 
     def local_seam_leveling(self, adj_ptr, adj, labels, patches, params=None, on_device=False):
         """Row f7: tex::local_seam_leveling on a patch set (DESIGN.md section 4 "Local seam leveling"): `patches` is the dict of
@@ -939,10 +1000,28 @@ def texture_atlases(scene, labels, params=None, ctx=None):
         return c.texture_atlases(dev, params)
 
 
-def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None):
+def debug_view_style(position):
+    """background and font colour of the view at `position` of the view list in the debug model: ((r, g, b), (r, g, b)) bytes
+    (mvs_debug_view_style; needs no device)"""
+    L = load_library()
+    bg, fg = (C.c_uint8 * 3)(), (C.c_uint8 * 3)()
+    _check(L, L.mvs_debug_view_style(int(position), bg, fg))
+    return tuple(bg), tuple(fg)
+
+
+def view_selection_model(scene, labels, prefix, view_ids=None, vertex_normals=None, ctx=None):
+    """texrecon.cpp:216-236 for a synth.Scene-like object and its labels: writes the debug model `<prefix>_view_selection.obj`, `.mtl` and
+    PNGs, whose faces carry the colour and the id of the view that textures them.  Returns Context.view_selection_model's stats."""
+    with _scene_context(scene, ctx) as c:
+        return c.view_selection_model(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
+                                      np.ascontiguousarray(labels, dtype=np.uint32), prefix, view_ids, vertex_normals)
+
+
+def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None, view_selection_model=False):
     """texrecon.cpp:169-208 for a synth.Scene-like object and its labels: rows f5 to f8 as texture_atlases runs them, then the model
     output (row f9) with the atlases left on the device: writes `<prefix>.obj`, `<prefix>.mtl` and the atlas PNGs.  Returns row f9's
-    stats.  vertex_normals: (n_verts, 3) or None (no `vn` lines; vertex_normals(verts, faces) computes area-weighted ones)."""
+    stats.  vertex_normals: (n_verts, 3) or None (no `vn` lines; vertex_normals(verts, faces) computes area-weighted ones).
+    view_selection_model=True writes the debug model `<prefix>_view_selection.*` as well (Context.view_selection_model)."""
     with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
@@ -951,7 +1030,10 @@ def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=N
         lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
         dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
         atlases, _ = c.texture_atlases(dev, on_device=True)
-        return c.save_model(atlases, prefix, vertex_normals, params)
+        stats = c.save_model(atlases, prefix, vertex_normals, params)
+        if view_selection_model:   # texrecon.cpp:216-236: after the textured model, on the same context
+            c.view_selection_model(a, b, lab, prefix, None, vertex_normals, model_params=params)
+        return stats
 
 
 def global_seam_leveling(scene, labels, params=None, ctx=None):
