@@ -638,13 +638,17 @@ void mvs_atlas_set_free(mvs_atlas_set* a);
  * and the section arrays host arrays owned by the context (valid until its next build_model / save_model call or its destruction),
  * otherwise everything is malloc'ed (mvs_model_text_free).
  * mvs_ctx_save_model writes `<prefix>.obj`, `<prefix>.mtl` and per atlas `<prefix>_material<a>_map_Kd.png` (<a> zero-filled to four
- * characters): the text comes through a pinned buffer, the PNGs are encoded by up to 16 host threads.  PNG: 8-bit RGB, filter 0, one
- * IDAT; params.png_level 0 (default) = stored deflate blocks, no dependency; 1 .. 9 = libz.so.1 resolved at run time, MVS_ERR_UNSUPPORTED
- * where it is absent.  mvs_write_png is that encoder on a host image (rgb [height][width][3]). */
+ * characters): the text comes through a pinned buffer, the PNGs are written by up to 16 host threads.  PNG: 8-bit RGB, one IDAT.
+ *   params.png_device 0 (default): the pixels are copied to the host and encoded there with filter 0 on every row; params.png_level 0
+ *   (default) = stored deflate blocks, no dependency; 1 .. 9 = libz.so.1 resolved at run time, MVS_ERR_UNSUPPORTED where it is absent.
+ *   mvs_write_png is that encoder on a host image (rgb [height][width][3]).
+ *   params.png_device 1: the atlases are encoded on the device (mvs_ctx_encode_pngs below: per-row filters, run-length matches and a
+ *   dynamic Huffman block per 32 KiB chunk) and only the finished files are downloaded; needs no libz; png_level must be 0.  Any other
+ *   png_device, or png_device 1 with png_level != 0, is MVS_ERR_INVALID.  stats.ms_png covers whichever route ran. */
 typedef struct mvs_model_params {
     uint64_t max_bytes;       /* refuse an .obj of more bytes than this (0: no cap) */
     int32_t png_level;        /* 0 .. 9 */
-    int32_t reserved;
+    int32_t png_device;       /* 0: the PNGs are encoded on the host (png_level); 1: on the device */
 } mvs_model_params;
 void mvs_model_default_params(mvs_model_params* p);
 typedef struct mvs_model_text {
@@ -668,6 +672,39 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
                               const char* prefix, const mvs_model_params* params, mvs_model_stats* stats);
 void mvs_model_text_free(mvs_model_text* t);
 mvs_status mvs_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height, int32_t level);
+
+/* Row f9's compressed PNG route (DESIGN.md section 4 "Model output" item 7 defines the format; pixel parity with any PNG reader): every
+ * row takes the PNG filter 0 .. 4 whose residuals have the smallest sum of absolute values, the filtered stream is cut into independent
+ * chunks of 32768 bytes, and every chunk is one dynamic-Huffman block of literals and distance-1 matches (or a stored block where that
+ * is no shorter) behind an empty stored block.
+ * mvs_ctx_encode_pngs: the complete PNG files of n_images 8-bit RGB images in one call.  Image i is width[i] x height[i] pixels at
+ * image + 3 pix_ptr[i] (pix_ptr [n_images + 1] runs from 0, pix_ptr[i + 1] - pix_ptr[i] = width[i] height[i]); with on_device all four
+ * arrays are device pointers, otherwise host arrays.  out: file i is data[offsets[i] .. offsets[i + 1]) (host memory, malloc'ed:
+ * mvs_png_set_free).  MVS_ERR_INVALID for an empty frame, arrays that do not agree or a null image with pixels; MVS_ERR_UNSUPPORTED
+ * for an image whose raw or compressed stream reaches 0x7FF00000 bytes.
+ * mvs_ctx_deflate_rle: the chunk, gather and checksum passes alone on n bytes (host or device): one zlib stream, malloc'ed (mvs_png_free).
+ * mvs_encode_png_rle / mvs_deflate_rle: the same on the host, sequentially -- no GPU, no libz, the same bytes as the device gives. */
+typedef struct mvs_png_stats {
+    uint64_t raw_bytes, png_bytes;               /* filtered streams (height (3 width + 1) per image); the files */
+    uint64_t chunks, stored_chunks;              /* all chunks; those that went out as a stored block */
+    uint64_t filter_rows[5];                     /* rows per filter type */
+    float ms_filter, ms_chunk, ms_gather;        /* device time per pass */
+    float ms_download, ms_frame;                 /* host time: chunk table and streams to the host; checksums, CRCs and framing */
+    float reserved;
+} mvs_png_stats;
+typedef struct mvs_png_set {
+    uint32_t n_images, reserved;
+    uint64_t n_bytes;
+    uint8_t* data;                               /* [n_bytes] */
+    uint64_t* offsets;                           /* [n_images + 1] */
+} mvs_png_set;
+mvs_status mvs_ctx_encode_pngs(mvs_ctx* ctx, uint32_t n_images, const uint32_t* width, const uint32_t* height, const uint64_t* pix_ptr, const uint8_t* image,
+                               int on_device, mvs_png_set* out, mvs_png_stats* stats);
+void mvs_png_set_free(mvs_png_set* p);
+mvs_status mvs_ctx_deflate_rle(mvs_ctx* ctx, const uint8_t* bytes, uint64_t n, int on_device, uint8_t** out, uint64_t* out_bytes);
+mvs_status mvs_encode_png_rle(const uint8_t* rgb, uint32_t width, uint32_t height, uint8_t** out, uint64_t* out_bytes);
+mvs_status mvs_deflate_rle(const uint8_t* bytes, uint64_t n, uint8_t** out, uint64_t* out_bytes);
+void mvs_png_free(uint8_t* bytes);
 
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <functional>
@@ -138,6 +139,7 @@ struct LslDev;   // row f7 (k_localseam.hip)
 struct AtlasDev; // row f8 (k_atlas.hip)
 struct ModelDev; // row f9 (k_model.hip)
 struct DebugDev; // row f10 (k_debug.hip)
+struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -266,6 +268,7 @@ struct mvs_ctx {
     mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
     mvs::ModelDev* model = nullptr;   // row f9 (k_model.hip)
     mvs::DebugDev* debug = nullptr;   // row f10 (k_debug.hip)
+    mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -398,6 +401,18 @@ void atlas_release(mvs_ctx* ctx);
 void model_release(mvs_ctx* ctx);
 // frees the buffers of row f10 (k_debug.hip)
 void debug_release(mvs_ctx* ctx);
+// k_png.hip: frees its buffers; the PNG files of n images encoded on the device (mvs_ctx_encode_pngs after its checks: width, height [n] and
+// pix [n + 1] are host arrays that agree, image is 3 bytes per pixel on the host or the device) -- file i is data[offsets[i], offsets[i + 1])
+void png_release(mvs_ctx* ctx);
+struct PngFiles {
+    uint8_t* data = nullptr; std::vector<uint64_t> offsets;
+    PngFiles() = default;
+    PngFiles(const PngFiles&) = delete;
+    PngFiles& operator=(const PngFiles&) = delete;
+    ~PngFiles() { free(data); }
+};
+void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
+                       PngFiles& out, mvs_png_stats& st);
 // rows f5 / f6 (k_texpatch.hip): the views' parameters on the device and the checks on the caller's labels and faces -- throws MVS_ERR_LABELING
 // for a label above the number of views, MVS_ERR_INVALID for a vertex id >= n_verts; `who` starts the message
 void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, const char* who);

@@ -1,6 +1,6 @@
 // k_model.hip -- row f9: tex::build_model + ObjModel::save + MaterialLib::save_to_files (DESIGN.md section 4 "Model output"): the text of
-// the .obj and the .mtl formatted on the device, byte for byte what upstream's writers produce; the files and the atlas PNGs written on
-// the host (png_io.h).  Three phases on the context's stream:
+// the .obj and the .mtl formatted on the device, byte for byte what upstream's writers produce; the files written on the host, the atlas
+// PNGs encoded there too (png_io.h; params.png_device 0) or on the device (k_png.hip; params.png_device 1).  Three phases on the context's stream:
 //   measure  one thread per line computes its length (fmt6.h), checks its indices and counts the floats of the wide route
 //   scan     64-bit exclusive scan of the lengths (rocprim through rows.h); the section offsets are gathered from it
 //   write    a block's 256 lines are contiguous in the file: thread = line formats into an LDS staging buffer laid out like the file from
@@ -280,7 +280,7 @@ extern "C" {
 
 void mvs_model_default_params(mvs_model_params* p) {
     if (!p) return;
-    p->max_bytes = 0; p->png_level = 0; p->reserved = 0;
+    p->max_bytes = 0; p->png_level = 0; p->png_device = 0;
 }
 
 mvs_status mvs_ctx_build_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
@@ -333,6 +333,8 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
         const mvs_atlas_set& in = *atlases;
         const uint32_t A = in.n_atlases;
         if (P.png_level < 0 || P.png_level > 9) throw StatusError(MVS_ERR_INVALID, "save_model: png_level 0 .. 9");
+        if (P.png_device != 0 && P.png_device != 1) throw StatusError(MVS_ERR_INVALID, "save_model: png_device 0 or 1");
+        if (P.png_device == 1 && P.png_level != 0) throw StatusError(MVS_ERR_INVALID, "save_model: png_device 1 takes png_level 0");
         if (P.png_level > 0 && A && !png_zlib_available()) throw StatusError(MVS_ERR_UNSUPPORTED, "save_model: libz.so.1 not found (png_level 0 needs no library)");
         if (A && (!in.atlas_size || !in.atlas_pix_ptr || (in.n_pixels && !in.image))) throw StatusError(MVS_ERR_INVALID, "save_model: null array in the atlas set");
         const std::string pre(prefix), name = pre.substr(pre.find_last_of('/') == std::string::npos ? 0 : pre.find_last_of('/') + 1);
@@ -353,10 +355,12 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
                 if (atlases_on_device) {
                     MVS_HIP(hipMemcpyAsync(size.data(), in.atlas_size, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
                     MVS_HIP(hipMemcpyAsync(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                    own.resize(3 * (size_t)in.n_pixels + 1);
-                    if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
+                    if (!P.png_device) {
+                        own.resize(3 * (size_t)in.n_pixels + 1);
+                        if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
+                        image = own.data();
+                    }
                     MVS_HIP(hipStreamSynchronize(s));
-                    image = own.data();
                 } else {
                     memcpy(size.data(), in.atlas_size, A * sizeof(uint32_t)); memcpy(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t));
                 }
@@ -364,11 +368,15 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
             if (pix[0] != 0 || pix[A] != in.n_pixels) throw StatusError(MVS_ERR_INVALID, "save_model: atlas_pix_ptr does not run from 0 to n_pixels");
             for (uint32_t a = 0; a < A; ++a)
                 if (!size[a] || pix[a + 1] < pix[a] || pix[a + 1] - pix[a] != (uint64_t)size[a] * size[a]) throw StatusError(MVS_ERR_INVALID, "save_model: atlas " + std::to_string(a) + ": size and atlas_pix_ptr do not agree");
+            PngFiles files;   // png_device 1: the finished files, encoded on the device
+            if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
             std::atomic<uint32_t> next{0}; std::atomic<int> failed{MVS_OK};
             std::vector<std::string> errs(A);
             auto work = [&] {
                 for (uint32_t a = next.fetch_add(1); a < A; a = next.fetch_add(1)) {
-                    const mvs_status r = write_png((pre + "_material" + filled4(a) + "_map_Kd.png").c_str(), image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, errs[a]);
+                    const std::string path = pre + "_material" + filled4(a) + "_map_Kd.png";
+                    const mvs_status r = P.png_device ? write_file(path.c_str(), files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a])
+                                                      : write_png(path.c_str(), image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, errs[a]);
                     if (r != MVS_OK) failed.store(r);
                 }
             };

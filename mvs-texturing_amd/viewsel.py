@@ -154,7 +154,7 @@ class AtlasStats(C.Structure):
 
 
 class ModelParams(C.Structure):
-    _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("png_device", C.c_int32)]
 
 
 class ModelText(C.Structure):
@@ -175,6 +175,18 @@ class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
                [("max_quality", C.c_float), ("percentile", C.c_float), ("footprints_lane_group", C.c_uint64), ("footprints_rewalked", C.c_uint64), ("ray_leaf_rounds", C.c_uint64)]
+
+
+PNG_COUNTS = ("raw_bytes", "png_bytes", "chunks", "stored_chunks")
+PNG_MS = ("ms_filter", "ms_chunk", "ms_gather", "ms_download", "ms_frame")
+
+
+class PngStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in PNG_COUNTS] + [("filter_rows", C.c_uint64 * 5)] + [(k, C.c_float) for k in PNG_MS] + [("reserved", C.c_float)]
+
+
+class PngSet(C.Structure):
+    _fields_ = [("n_images", C.c_uint32), ("reserved", C.c_uint32), ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("offsets", C.c_void_p)]
 
 
 def _stats_dict(s):
@@ -278,6 +290,9 @@ def load_library():
         "mvs_ctx_build_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelText), i32, C.POINTER(ModelStats)],
         "mvs_ctx_save_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelStats)],
         "mvs_write_png": [C.c_char_p, vp, u32, u32, C.c_int32],
+        "mvs_ctx_encode_pngs": [vp, u32, vp, vp, vp, vp, i32, C.POINTER(PngSet), C.POINTER(PngStats)], "mvs_png_set_free": [C.POINTER(PngSet)],
+        "mvs_ctx_deflate_rle": [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)], "mvs_png_free": [vp],
+        "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
         "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
         "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
         "mvs_ctx_view_selection_model": [vp, vp, vp, i32, vp, i32, vp, vp, i32, C.c_char_p, C.POINTER(PatchParams), C.POINTER(AtlasParams), C.POINTER(ModelParams),
@@ -306,7 +321,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_png_set_free", "mvs_png_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -830,7 +845,8 @@ class Context:
 
     def save_model(self, atlases, prefix, vertex_normals=None, params=None):
         """Row f9 to files: `<prefix>.obj`, `<prefix>.mtl` and one `<prefix>_material<a>_map_Kd.png` per atlas (mvs_ctx_save_model; the
-        atlas set needs atlas_size, atlas_pix_ptr and image as well).  Returns the stats; params: default_model_params(png_level=...)."""
+        atlas set needs atlas_size, atlas_pix_ptr and image as well).  Returns the stats; params: default_model_params(png_level=...) for
+        the host encoder's level, default_model_params(png_device=1) for the PNGs compressed on the device (encode_pngs)."""
         ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
         st = ModelStats()
         self._keep["model"] = held
@@ -838,6 +854,54 @@ class Context:
         stats = _model_stats(st)
         _check_with_stats(self.L, rc, stats)
         return stats
+
+    def encode_pngs(self, images):
+        """The compressed PNG route of row f9 on its own (mvs_ctx_encode_pngs; DESIGN.md section 4 "Model output" item 7): `images` is a
+        list of (H, W, 3) uint8 arrays -- all numpy or all CUDA tensors -- or an atlas-set dict (atlas_size, atlas_pix_ptr, image: all
+        host or all device).  One call encodes them all.  Returns (list of bytes, one PNG file per image; stats)."""
+        if isinstance(images, dict):
+            held = _atlas_set_struct({k: images[k] for k in ("atlas_size", "atlas_pix_ptr", "image")})[1]
+            size, pix, img = held["atlas_size"], held["atlas_pix_ptr"], held["image"]
+            dev = 1 if (_is_torch(img) or isinstance(img, DevArray)) else 0
+            n = int(size.numel()) if _is_torch(size) else int(size.shape[0])
+            width = height = size
+        elif len(images) and _is_torch(images[0]):
+            import torch
+            assert all(_is_torch(a) and a.is_cuda and a.dtype == torch.uint8 and a.dim() == 3 and a.shape[2] == 3 for a in images)
+            n, dev = len(images), 1
+            d = images[0].device
+            width = torch.tensor([a.shape[1] for a in images], dtype=torch.int32, device=d)      # (the bits of a uint32 below 2^31)
+            height = torch.tensor([a.shape[0] for a in images], dtype=torch.int32, device=d)
+            pix = torch.tensor(np.concatenate([[0], np.cumsum([a.shape[0] * a.shape[1] for a in images])]).astype(np.int64), device=d)
+            img = torch.cat([a.contiguous().reshape(-1) for a in images])
+        else:
+            arrs = [np.ascontiguousarray(a, np.uint8) for a in images]
+            assert all(a.ndim == 3 and a.shape[2] == 3 for a in arrs)
+            n, dev = len(arrs), 0
+            width = np.array([a.shape[1] for a in arrs], np.uint32); height = np.array([a.shape[0] for a in arrs], np.uint32)
+            pix = np.concatenate([[0], np.cumsum([a.shape[0] * a.shape[1] for a in arrs])]).astype(np.uint64)
+            img = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.uint8)
+        res, st = PngSet(), PngStats()
+        self._keep["png"] = (width, height, pix, img)
+        n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
+        rc = self.L.mvs_ctx_encode_pngs(self.h, n, _ptr(width)[0], _ptr(height)[0], _ptr(pix)[0], _ptr(img)[0] if n_pix else None, dev, C.byref(res), C.byref(st))
+        stats = _png_stats(st)
+        _check_with_stats(self.L, rc, stats)
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        data = C.string_at(res.data, res.n_bytes)
+        self.L.mvs_png_set_free(C.byref(res))
+        return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
+
+    def deflate_rle(self, data):
+        """mvs_ctx_deflate_rle: the zlib stream (bytes) the chunk, gather and checksum passes of the compressed PNG route give the byte
+        stream `data` -- bytes, a uint8 numpy array or a CUDA uint8 tensor"""
+        if not (_is_torch(data) or isinstance(data, DevArray)):
+            data = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+        n = int(data.numel()) if _is_torch(data) else int(data.shape[0])
+        p, dev = _ptr(data)
+        out, nb = C.c_void_p(), C.c_uint64()
+        _check(self.L, self.L.mvs_ctx_deflate_rle(self.h, p if n else None, n, dev, C.byref(out), C.byref(nb)))
+        return _take_bytes(self.L, out, nb)
 
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
@@ -879,7 +943,7 @@ def default_atlas_params(**kw):
 
 
 def default_model_params(**kw):
-    """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks) with overrides"""
+    """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks, png_device 0 = PNGs encoded on the host) with overrides"""
     return _default_params(ModelParams, "mvs_model_default_params", kw)
 
 
@@ -913,6 +977,39 @@ def _model_stats(st):
     stats.update({k: int(getattr(st, k)) for k in MODEL_COUNTS})
     stats.update({k: float(getattr(st, k)) for k in MODEL_MS})
     return stats
+
+
+def _png_stats(st):
+    stats = {k: int(getattr(st, k)) for k in PNG_COUNTS}
+    stats["filter_rows"] = [int(x) for x in st.filter_rows]
+    stats.update({k: float(getattr(st, k)) for k in PNG_MS})
+    return stats
+
+
+def _take_bytes(L, out, nb):
+    z = C.string_at(out, nb.value)
+    L.mvs_png_free(out)
+    return z
+
+
+def encode_png_rle(img):
+    """mvs_encode_png_rle: the PNG file (bytes) of an (H, W, 3) uint8 host image by the host twin of the compressed route -- no GPU, no
+    libz; the same bytes as Context.encode_pngs gives"""
+    L = load_library()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3
+    out, nb = C.c_void_p(), C.c_uint64()
+    _check(L, L.mvs_encode_png_rle(img.ctypes.data, img.shape[1], img.shape[0], C.byref(out), C.byref(nb)))
+    return _take_bytes(L, out, nb)
+
+
+def deflate_rle(data):
+    """mvs_deflate_rle: the zlib stream (bytes) of a byte stream by the host twin; the same bytes as Context.deflate_rle gives"""
+    L = load_library()
+    data = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+    out, nb = C.c_void_p(), C.c_uint64()
+    _check(L, L.mvs_deflate_rle(data.ctypes.data if data.size else None, data.size, C.byref(out), C.byref(nb)))
+    return _take_bytes(L, out, nb)
 
 
 def write_png(path, rgb, level=0):

@@ -1,11 +1,14 @@
 """Row f9 (model output) at a BASELINE config, with labels from the library's own view selection and rows f5 - f8 left on the device:
-   model_output_time.py --config 3 [--runs 3] [--out profiles/model_c3.json] [--no-model] [--png-levels 0,1,6]
+   model_output_time.py --config 3 [--runs 3] [--out profiles/model_c3.json] [--no-model] [--png-levels 0,1,6] [--png-device]
 Records, as the median of the timed runs after one warm-up: the device time per phase of the text (mvs_model_stats ms_measure / ms_scan /
 ms_write, from events on the context's stream; inputs and the text stay on the device), a plain device-to-device copy of obj_bytes timed
 in the same run -- the bound the write kernel is compared against -- and their ratio; the host times of save_model per PNG level
 (ms_download: the text through the pinned buffer, ms_files: the two text files, ms_png: atlas pixels to the host, encoding on up to 16
 threads, writing); the lines and bytes per section and the wide-route / non-finite counters; and the single-thread time of the CPU model
-(tests/tools/obj_model.cpp: std::ostringstream << std::fixed) on the same inputs, with the .obj and .mtl files compared in full."""
+(tests/tools/obj_model.cpp: std::ostringstream << std::fixed) on the same inputs, with the .obj and .mtl files compared in full.
+--png-device adds a leg with params.png_device = 1 (the PNGs compressed on the device) under the same keys, and beside it the stats of
+Context.encode_pngs on the same atlases: the device time of the filter, chunk and gather passes, their GB/s on the raw bytes next to a
+device copy of that many bytes, the host time of the download and the framing, chunks and stored chunks, rows per filter type."""
 import argparse
 import json
 import os
@@ -27,6 +30,7 @@ ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-model", action="store_true")
 ap.add_argument("--png-levels", default="0", help="comma-separated png_level values to time save_model with")
+ap.add_argument("--png-device", action="store_true", help="also time save_model with png_device = 1 and Context.encode_pngs on the atlases")
 a = ap.parse_args()
 out_path = a.out or os.path.join(ROOT, "profiles", "model_c%d.json" % a.config)
 levels = [int(x) for x in a.png_levels.split(",")]
@@ -83,9 +87,10 @@ print(json.dumps({k: res[k] for k in ("ms_median", "lines", "bytes", "write", "w
 tmp = tempfile.mkdtemp(prefix="model_output_")
 try:
     res["save_model"] = {}
-    for level in levels:
-        p = M.default_model_params(png_level=level)
-        prefix = os.path.join(tmp, "l%d" % level, name)
+    legs = [("png_level_%d" % level, "l%d" % level, dict(png_level=level)) for level in levels] + ([("png_device", "dev", dict(png_device=1))] if a.png_device else [])
+    for leg, sub, kw in legs:
+        p = M.default_model_params(**kw)
+        prefix = os.path.join(tmp, sub, name)
         os.makedirs(os.path.dirname(prefix))
         c.save_model(atl, prefix, dn, p)                  # warm-up: the pinned buffer, the page cache
         sr = []
@@ -96,9 +101,34 @@ try:
             sr.append(st)
         keys = ("ms_download", "ms_files", "ms_png", "wall_ms")
         png_bytes = sum(os.path.getsize(os.path.join(os.path.dirname(prefix), f)) for f in os.listdir(os.path.dirname(prefix)) if f.endswith(".png"))
-        res["save_model"]["png_level_%d" % level] = {"ms_median": {k: float(np.median([r[k] for r in sr])) for k in keys}, "png_bytes": int(png_bytes),
-                                                     "threads": min(16, ast["atlases"])}
-        print("save_model png_level %d: %s, %d PNG bytes" % (level, json.dumps(res["save_model"]["png_level_%d" % level]["ms_median"]), png_bytes), flush=True)
+        res["save_model"][leg] = {"ms_median": {k: float(np.median([r[k] for r in sr])) for k in keys}, "png_bytes": int(png_bytes), "threads": min(16, ast["atlases"])}
+        print("save_model %s: %s, %d PNG bytes" % (leg, json.dumps(res["save_model"][leg]["ms_median"]), png_bytes), flush=True)
+    if a.png_device:
+        c.encode_pngs(atl)                                # warm-up
+        er = []
+        for _ in range(a.runs):
+            t = time.perf_counter()
+            _, st = c.encode_pngs(atl)
+            st["wall_ms"] = 1e3 * (time.perf_counter() - t)
+            er.append(st)
+        raw = er[-1]["raw_bytes"]
+        x = torch.empty(raw, dtype=torch.uint8, device="cuda"); y = torch.empty_like(x)
+        y.copy_(x); torch.cuda.synchronize()
+        copies = []
+        for _ in range(a.runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); y.copy_(x); e1.record(); torch.cuda.synchronize()
+            copies.append(float(e0.elapsed_time(e1)))
+        del x, y
+        keys = ("ms_filter", "ms_chunk", "ms_gather", "ms_download", "ms_frame", "wall_ms")
+        emed = {k: float(np.median([r[k] for r in er])) for k in keys}
+        raw_copy_ms = float(np.median(copies))
+        res["encode_pngs"] = {"ms_median": emed, "raw_bytes": raw, "png_bytes": er[-1]["png_bytes"], "chunks": er[-1]["chunks"], "stored_chunks": er[-1]["stored_chunks"],
+                              "filter_rows": er[-1]["filter_rows"], "device_copy_raw_bytes_ms": raw_copy_ms,
+                              "gb_per_s": {k: raw / (emed[k] * 1e-3) / 1e9 if emed[k] > 0 else None for k in ("ms_filter", "ms_chunk", "ms_gather")},
+                              "device_copy_gb_per_s": raw / (raw_copy_ms * 1e-3) / 1e9 if raw_copy_ms > 0 else None,
+                              "note": "Context.encode_pngs on the device-resident atlases; GB/s on raw_bytes = the filtered streams"}
+        print("encode_pngs: %s" % json.dumps(res["encode_pngs"]), flush=True)
     if not a.no_model:
         import obj_model as OM
         OM.build()
@@ -117,7 +147,7 @@ try:
         t = time.perf_counter()
         want_obj, want_mtl = OM.run(s.verts, s.faces, host, normals, name)
         res["model_single_thread_s"] = time.perf_counter() - t
-        prefix = os.path.join(tmp, "l%d" % levels[0], name)
+        prefix = os.path.join(tmp, legs[0][1], name)
         with open(prefix + ".obj", "rb") as f:
             obj_equal = f.read() == want_obj
         with open(prefix + ".mtl", "rb") as f:
