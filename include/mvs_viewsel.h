@@ -410,7 +410,7 @@ typedef struct mvs_mrf_progress {
 } mvs_mrf_progress;
 
 /* message element index of the first real run: elements [0, MVS_MRF_MSG_BASE) of the solver's message array are a reserved all-zero
- * run (k_mrf.hip): halo index lists start from here */
+ * run (k_mrf_setup.hip): halo index lists start from here */
 #define MVS_MRF_MSG_BASE 256u
 /* The sweep is colour-phased Gauss-Seidel: the adjacency graph is coloured at set-up (n_phases colours, each an independent set) and
  * one sweep = for phase in 0 .. n_phases - 1: the nodes of that colour recompute their outgoing messages in place. */

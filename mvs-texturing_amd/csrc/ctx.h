@@ -286,21 +286,21 @@ struct mvs_ctx {
     mvs::DBuf<uint32_t> m_sel, m_sel2, m_cand; mvs::DBuf<float> m_gain;
     mvs::DBuf<uint32_t> m_lab; mvs::DBuf<float> m_cost;
     uint32_t m_stride = 0;      // F + 1: offset of the second buffer
-    bool exact_valid = false; uint32_t exact_nb = 0, exact_ne = 0;   // b_sel / b_cost of nodes [exact_nb, exact_ne) are derived from b_lab (k_mrf.hip mrf_exact_costs)
+    bool exact_valid = false; uint32_t exact_nb = 0, exact_ne = 0;   // b_sel / b_cost of nodes [exact_nb, exact_ne) are derived from b_lab (k_mrf_polish.hip mrf_exact_costs)
     uint32_t* b_sel = nullptr; uint32_t* b_lab = nullptr; float* b_cost = nullptr; bool best_resolved = false;   // the best buffer, once the host knows which one it is (resolve_best)
     mvs::DBuf<unsigned long long> m_energy; mvs::SolverWords* words = nullptr /* allocated by mvs_ctx_create */; mvs::DBuf<uint32_t> m_alist; bool icm_dirty_valid = false;   // ICM active set: nodes whose gain the next pass re-evaluates
     uint32_t m_n_adj = 0;      // directed edges of the adjacency given to mrf_setup
     uint32_t m_energy_blocks = 0;   // per-block partial pairs the last mrf_energy left behind m_energy.p + 4
     bool m_energy_from_sweep = false;   // ... or the last sweep's own kernels did (fast path: the energy is accumulated while sweeping)
     uint64_t m_total = 0; uint32_t m_kmax = 0, m_degmax = 0;
-    // colour-phased schedule: colours of the adjacency graph and per-node classes (k_mrf.hip mrf_node_class); nodes in SCHEDULE order =
+    // colour-phased schedule: colours of the adjacency graph and per-node classes (k_mrf_setup.hip mrf_node_class); nodes in SCHEDULE order =
     // sorted by sub-class key (fast nodes by (colour, class, id), then generic nodes by (colour, id)); m_sub_begin[key] = first position
     // of a key >= `key` (host copy of m_sub); positions [0, m_n_fast) are the fast nodes
     mvs::DBuf<uint32_t> m_colour, m_perm, m_tmp_a, m_tmp_b, m_tmp_c, m_sub; mvs::DBuf<uint8_t> m_cls; uint32_t m_colours = 0, m_n_fast = 0; std::vector<uint32_t> m_sub_begin;
     const uint32_t* m_colour_in = nullptr;   // colours of all nodes kept by a sharded caller (null: mrf_setup colours the graph)
-    const uint8_t* m_bnd = nullptr;   // per node: 1 = boundary node of a sharded caller (own node with an edge into another rank's part) -> zone 0 of the schedule (k_mrf.hip); null: no marks
+    const uint8_t* m_bnd = nullptr;   // per node: 1 = boundary node of a sharded caller (own node with an edge into another rank's part) -> zone 0 of the schedule (mrf.h); null: no marks
     int mrf_force_generic = 0;   // test hook: every node takes the generic sweep kernel
-    // view-set bitmaps of the active table, F x ceil(csr_views / 64) words, rebuilt by every mrf_setup (k_mrf.hip mrf_bitmap_kernel); m_bitmaps:
+    // view-set bitmaps of the active table, F x ceil(csr_views / 64) words, rebuilt by every mrf_setup (k_mrf_setup.hip mrf_bitmap_kernel); m_bitmaps:
     // the last set-up took the bitmap route (not: more than 1024 views, a column that is not strictly ascending, the hook below)
     mvs::DBuf<unsigned long long> m_bits; bool m_bitmaps = false;
     int mrf_force_lists = 0;     // test hook: the set-up compares and searches the neighbours' view lists at any number of views
@@ -308,7 +308,7 @@ struct mvs_ctx {
     uint32_t m_sweep_no = 0;   // sweeps started since mrf_setup (1-based inside a sweep): sweeps 1, 5, 9, ... are damped
     uint32_t m_last_phase = 0xFFFFFFFFu;   // colour phase of the last mrf_sweep_phase since mrf_setup (none yet: 0xFFFFFFFF): a smaller phase number starts a sweep
     mvs_mrf_params m_params{};
-    // device-side stop rule (k_mrf.hip mrf_step): solver state in HBM, per-step reports through a pinned ring
+    // device-side stop rule (k_mrf_polish.hip mrf_step): solver state in HBM, per-step reports through a pinned ring
     static constexpr uint32_t RING = 16;
     static constexpr uint32_t ICM_RING = 8;
     uint32_t* h_icm = nullptr; uint32_t* d_icm = nullptr; uint32_t icm_seq = 0;   // pinned "moved" counts of the ICM rounds, read a few rounds late
@@ -360,16 +360,16 @@ struct RoctxRange { explicit RoctxRange(const char* name); ~RoctxRange(); bool o
 int default_device();
 // option "dc_range_pairs" as the environment sets it (MVS_DC_RANGE_PAIRS, 0 when unset): for a new context and for every one-shot call
 uint64_t env_dc_range_pairs();
-// which zone(s) of a colour phase mrf_sweep_phase sweeps (k_mrf.hip)
+// which zone(s) of a colour phase mrf_sweep_phase sweeps (k_mrf_sweep.hip)
 enum { MRF_PART_ALL = 0, MRF_PART_BOUNDARY = 1, MRF_PART_INTERIOR = 2 };
 // reports through pinned host memory (readback.hip)
 void ensure_report_ring(mvs_ctx* ctx);
 void report_u32(mvs_ctx* ctx, const uint32_t* d_src, uint32_t* d_dst, uint32_t seq_slot, uint32_t seq);
 void wait_report(mvs_ctx* ctx, uint32_t seq_slot, uint32_t seq);
-// ICM polish rounds until one moves nothing or max_rounds ran (k_mrf.hip): round(k) queues round k, which leaves its "moved" count in
+// ICM polish rounds until one moves nothing or max_rounds ran (k_mrf_polish.hip): round(k) queues round k, which leaves its "moved" count in
 // the device word d_moved.  Returns the index of the round that moved nothing (max_rounds if none did) -- the oracle's loop counter.
 int icm_rounds(mvs_ctx* ctx, int max_rounds, const uint32_t* d_moved, const std::function<void(int)>& round);
-constexpr uint32_t MRF_REC_BASE = 256;   // the first record starts at this word of m_rec (k_mrf.hip REC_BASE)
+constexpr uint32_t MRF_REC_BASE = 256;   // the first record starts at this word of m_rec (k_mrf_setup.hip REC_BASE)
 // damped sweeps: 1, 5, 9, ... -- part of the solver's definition, restated in oracle/oracle.cpp (MRF_DAMP_PERIOD)
 constexpr uint32_t MRF_DAMP_PERIOD = 4;
 // up to 64 words from device memory to the host between two launches of ctx->stream: a one-block kernel stores them into a pinned buffer and
@@ -458,10 +458,13 @@ void renumber_adjacency(mvs_ctx* ctx, uint32_t F, const uint32_t* perm, const ui
 uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* d_adj, const uint32_t* d_labels, uint32_t F, uint32_t n_labels);
 // k_region.hip
 uint32_t mrf_region_round(mvs_ctx* ctx);   // one round of region moves on the best labeling (needs mrf_exact_costs); returns the regions moved
-// k_mrf.hip -- node ranges [nb0, ne0) are positions of the active table
+// the MRF solver -- node ranges [nb0, ne0) are positions of the active table
+// k_mrf_setup.hip
 void mrf_setup(mvs_ctx* ctx, const mvs_mrf_params* params);   // the solver's tables for the active table and adjacency
+// k_mrf_sweep.hip
 void mrf_sweep(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0);     // one sweep = every colour phase in turn
 void mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, uint32_t ne0, int part = MRF_PART_ALL);   // one colour phase, both zones or one
+// k_mrf_polish.hip
 void mrf_sweep_energy_reduce(mvs_ctx* ctx, unsigned long long* out2 = nullptr);   // the last sweep's per-block energy partials -> ctx->m_energy (and out2)
 void mrf_energy(mvs_ctx* ctx, bool best, uint32_t nb0, uint32_t ne0, bool reduce = true);   // energy of the current decode or the best labeling -> ctx->m_energy
 void mrf_keep_best(mvs_ctx* ctx);                             // best labeling := the current decode
@@ -474,6 +477,9 @@ void mrf_icm_apply(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0); // ... the winners
 // labels of the best labeling into d_labels; out = {bad, unseen}; caller_order: the whole graph's labels at the caller's face ids
 void mrf_labels(mvs_ctx* ctx, uint32_t nb0, uint32_t ne0, uint32_t* d_labels, uint32_t out[2], bool caller_order = false);
 void resolve_best(mvs_ctx* ctx);                              // ctx->b_sel / b_lab / b_cost := the best labeling's buffers (one read-back)
+// The best labeling may have changed on the device (a bookkeeping step, keep_best, a replayed graph of sweeps): which buffer holds it,
+// the exact costs derived from it and the ICM's active list are stale until somebody asks again.
+inline void best_labeling_may_have_changed(mvs_ctx* ctx) { ctx->icm_dirty_valid = false; ctx->best_resolved = false; ctx->exact_valid = false; }
 
 // ---- around the body of an entry point: what it throws becomes the call's status and the message of mvs_last_error ----
 #define MVS_CATCH_TO_STATUS                                                                \

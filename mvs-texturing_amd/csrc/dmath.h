@@ -546,11 +546,11 @@ MVS_HD uint32_t hist_bin(float value, float maxv, uint32_t num_bins) {
     return (uint32_t)floorf(((clamped - 0.0f) / (maxv - 0.0f)) * (float)(num_bins - 1));
 }
 
-// ---- view-set bitmaps (k_mrf.hip set-up) ----
+// ---- view-set bitmaps (k_mrf_setup.hip) ----
 // A column's view ids are strictly ascending (calculate_data_costs.cpp:272), so a column IS a bitmap of W = ceil(V / 64) words, bit v of
 // word v / 64 = "view v is in the column".  Two columns are identical iff their bitmaps are equal; the position of view v in the column
 // is the number of set bits below bit v.  Neither identity holds for a column with a duplicate or a descending pair: such tables never
-// reach these helpers (k_mrf.hip mrf_bitmap_kernel flags them).
+// reach these helpers (k_mrf_setup.hip mrf_bitmap_kernel flags them).
 constexpr uint32_t BITMAP_NONE = 0xFFFFFFFFu;
 MVS_HD uint32_t bitmap_words(uint32_t n_views) { return (n_views + 63u) >> 6; }
 MVS_HD uint64_t bitmap_below(uint32_t p) { return (1ull << p) - 1ull; }                       // bits 0 .. p - 1 of a word, p in [0, 63]

@@ -16,7 +16,7 @@
 // ~6 faces): need bits -> ray kernel -> occluded bits, view-major bit matrices.
 #include "ctx.h"
 #include "dc_counters.h"
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 #ifndef MVS_LEAF_T
 #define MVS_LEAF_T 16
 #endif
@@ -621,10 +621,7 @@ __global__ void iota_kernel(uint32_t* __restrict__ v, uint32_t n) {
     if (i < n) v[i] = i;
 }
 void sort_by_key30(mvs_ctx* ctx, uint32_t* k_in, uint32_t* k_out, uint32_t* v_in, uint32_t* v_out, uint32_t n) {
-    size_t tmp_bytes = 0;
-    MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, n, 0, 30, ctx->stream));
-    ctx->sort_tmp.ensure(tmp_bytes + 16);
-    MVS_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp_bytes, k_in, k_out, v_in, v_out, n, 0, 30, ctx->stream));
+    dev_sort_pairs(ctx, k_in, k_out, v_in, v_out, n, 0, 30);
 }
 }  // namespace
 

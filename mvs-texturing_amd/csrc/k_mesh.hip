@@ -4,7 +4,7 @@
 // Both are integer / sorting work (HBM bound); results are exact (pinned to the reference's own two files through oracle/_ref,
 // tests/test_reference_pins.py, including meshes with repeated-vertex faces).
 #include "ctx.h"
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 
 namespace mvs {
 
@@ -197,10 +197,7 @@ uint64_t build_adjacency(mvs_ctx* ctx, const uint32_t* d_faces, uint32_t F, uint
         return total;
     }
     int vbits = 1; while ((1ull << vbits) < (unsigned long long)NV + 1 && vbits < 32) ++vbits;
-    size_t tmp_bytes = 0;
-    MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, ctx->g_keys.p, ctx->g_keys2.p, ctx->g_vals.p, ctx->g_vals2.p, n, 0, 32 + vbits, s));
-    ctx->sort_tmp.ensure(tmp_bytes + 16);
-    MVS_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp_bytes, ctx->g_keys.p, ctx->g_keys2.p, ctx->g_vals.p, ctx->g_vals2.p, n, 0, 32 + vbits, s));
+    dev_sort_pairs(ctx->sort_tmp, s, ctx->g_keys.p, ctx->g_keys2.p, ctx->g_vals.p, ctx->g_vals2.p, n, 0, 32 + vbits);
     hipLaunchKernelGGL(invert_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ctx->g_vals2.p, n, ctx->g_pos.p);
     MVS_LAUNCH_CHECK();
     hipLaunchKernelGGL(adjacency_kernel<false>, dim3((F + 127) / 128), dim3(128), 0, s, ctx->g_keys2.p, ctx->g_vals2.p, ctx->g_pos.p, F, ctx->g_cnt.p,

@@ -7,7 +7,7 @@
 // (k_bvh.hip build_scene_order).  This file holds what translates at the ABI:
 //   * the cost table back into the caller's order (mvs_ctx_costs_download / mvs_data_costs / tex::calculate_data_costs);
 //   * the adjacency lists (UniGraph, build_adjacency_graph.cpp:16-53) into the table's order, LIST ORDER KEPT -- the solver
-//     sums messages in list order, and the colouring is keyed on the caller's ids (k_mrf.hip), so labels do not depend on
+//     sums messages in list order, and the colouring is keyed on the caller's ids (k_mrf_setup.hip), so labels do not depend on
 //     the layout;
 //   * mvs_partition_faces / mvs_ctx_partition_faces: the order itself and its cut into `world` equal contiguous parts -- the
 //     partition of the sharded path (METIS is not available).

@@ -11,7 +11,7 @@
 //      block restores chunk by chunk with an atomicMin claim (earliest queue position wins) and a prefix sum.
 // Integer work only; the output equals the reference's vectors element for element.
 #include "ctx.h"
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 
 namespace mvs {
 
@@ -179,10 +179,7 @@ uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* 
     ctx->p_roots.ensure((size_t)C + 1); ctx->p_roots2.ensure((size_t)C + 1); ctx->p_rlab.ensure((size_t)C + 1); ctx->p_rlab2.ensure((size_t)C + 1);
     hipLaunchKernelGGL(cc_compact_roots_kernel, dim3(nb), dim3(256), 0, s, ctx->p_flag.p, ctx->p_pos.p, d_labels, F, ctx->p_roots.p, ctx->p_rlab.p); MVS_LAUNCH_CHECK();
     int lbits = 1; while ((1ull << lbits) < (unsigned long long)n_labels && lbits < 32) ++lbits;
-    size_t tmp_bytes = 0;
-    MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, ctx->p_rlab.p, ctx->p_rlab2.p, ctx->p_roots.p, ctx->p_roots2.p, C, 0, lbits, s));
-    ctx->sort_tmp.ensure(tmp_bytes + 16);
-    MVS_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp_bytes, ctx->p_rlab.p, ctx->p_rlab2.p, ctx->p_roots.p, ctx->p_roots2.p, C, 0, lbits, s));
+    dev_sort_pairs(ctx->sort_tmp, s, ctx->p_rlab.p, ctx->p_rlab2.p, ctx->p_roots.p, ctx->p_roots2.p, C, 0, lbits);
     const unsigned cb = (C + 255) / 256;
     uint32_t* rank_of = ctx->p_parent.p;   // the union-find forest is no longer needed
     hipLaunchKernelGGL(cc_rank_kernel, dim3(cb), dim3(256), 0, s, ctx->p_roots2.p, C, rank_of); MVS_LAUNCH_CHECK();
@@ -191,9 +188,7 @@ uint32_t get_subgraphs(mvs_ctx* ctx, const uint32_t* d_adj_ptr, const uint32_t* 
     uint32_t* key = ctx->p_flag.p; uint32_t* key_sorted = ctx->p_pos.p;
     hipLaunchKernelGGL(cc_face_key_kernel, dim3(nb), dim3(256), 0, s, ctx->p_root.p, rank_of, F, key); MVS_LAUNCH_CHECK();
     int cbits = 1; while ((1ull << cbits) < (unsigned long long)C && cbits < 32) ++cbits;
-    MVS_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, key, key_sorted, F, 0, cbits, s));
-    ctx->sort_tmp.ensure(tmp_bytes + 16);
-    MVS_HIP(rocprim::radix_sort_keys(ctx->sort_tmp.p, tmp_bytes, key, key_sorted, F, 0, cbits, s));
+    dev_sort_keys(ctx->sort_tmp, s, key, key_sorted, F, 0, cbits);
     ctx->p_comp_ptr.ensure((size_t)C + 2);
     hipLaunchKernelGGL(cc_comp_ptr_kernel, dim3(nb), dim3(256), 0, s, key_sorted, F, C, ctx->p_comp_ptr.p); MVS_LAUNCH_CHECK();
     hipLaunchKernelGGL(bfs_kernel<256>, dim3(C), dim3(256), 0, s, d_adj_ptr, d_adj, d_labels, ctx->p_roots2.p, ctx->p_comp_ptr.p, ctx->p_state.p, ctx->p_comp_faces.p, C);

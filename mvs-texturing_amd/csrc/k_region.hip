@@ -13,7 +13,7 @@
 // atomics only) -> best candidate per region (atomicMax on the gain, atomicMin on the label among the maxima) -> lose flags
 // over the cut edges -> apply.
 #include "ctx.h"
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 
 namespace mvs {
 
@@ -216,10 +216,7 @@ uint32_t mrf_region_round(mvs_ctx* ctx) {
     if (n_cut == 0) return 0;
     ctx->rg_key.ensure((size_t)n_cut + 2); ctx->rg_key2.ensure((size_t)n_cut + 2); ctx->rg_cut.ensure((size_t)n_cut + 2);
     hipLaunchKernelGGL(rg_cut_emit_kernel, dim3(nb), dim3(256), 0, s, ctx->r_adj_ptr, ctx->r_adj, ctx->b_lab, ctx->rg_root.p, ctx->rg_flag.p, ctx->rg_pos.p, F, ctx->rg_key.p, ctx->rg_cut.p); MVS_LAUNCH_CHECK();
-    size_t tmp = 0;
-    MVS_HIP(rocprim::radix_sort_keys(nullptr, tmp, ctx->rg_key.p, ctx->rg_key2.p, n_cut, 0, 48, s));
-    ctx->sort_tmp.ensure(tmp + 16);
-    MVS_HIP(rocprim::radix_sort_keys(ctx->sort_tmp.p, tmp, ctx->rg_key.p, ctx->rg_key2.p, n_cut, 0, 48, s));
+    dev_sort_keys(ctx->sort_tmp, s, ctx->rg_key.p, ctx->rg_key2.p, n_cut, 0, 48);
     // unique candidates
     ctx->rg_flag.ensure((size_t)n_cut + 2); ctx->rg_pos.ensure((size_t)n_cut + 2);
     hipLaunchKernelGGL(rg_first_kernel, dim3((n_cut + 256) / 256), dim3(256), 0, s, ctx->rg_key2.p, n_cut, ctx->rg_flag.p); MVS_LAUNCH_CHECK();

@@ -171,7 +171,7 @@ mvs_status mvs_ctx_mrf_sweep_phase(mvs_ctx* ctx, uint32_t phase, uint32_t nb0, u
     mrf_sweep_phase(ctx, phase, nb0, ne0);
     MVS_API_END
 }
-/* the set-up with BOUNDARY MARKS (marks_device[i] != 0: node i goes to the boundary zone of its colour class, see k_mrf.hip "zones") and one
+/* the set-up with BOUNDARY MARKS (marks_device[i] != 0: node i goes to the boundary zone of its colour class, see mrf.h "zones") and one
  * zone of a colour phase: what csrc/shard.hip does per rank, for drivers / measuring scripts one level below it */
 mvs_status mvs_ctx_mrf_setup_marked(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params, const uint8_t* marks_device) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");

@@ -1,9 +1,9 @@
 // rows.h -- the host plumbing the post-processing rows f5 - f8 share (k_seam.hip, k_texpatch.hip, k_localseam.hip, k_atlas.hip):
-//   launch and copy helpers, the rocprim two-call idiom, stage timers, the wrappers around an entry point's body, the staging of the
+//   launch and copy helpers, the rocprim two-call idiom (sort_scan.h), stage timers, the wrappers around an entry point's body, the staging of the
 //   caller's adjacency and labels, and the reader / checker of a patch set (DESIGN.md section 4 "Shared plumbing").  Internal, header-only.
 #pragma once
 #include "ctx.h"
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 
 namespace mvs {
 
@@ -32,26 +32,7 @@ void upload(DBuf<T>& buf, const T* h, size_t n, hipStream_t s) {
 template <class T>
 void upload(DBuf<T>& buf, const std::vector<T>& h, hipStream_t s) { upload(buf, h.data(), h.size(), s); }
 
-// ---- rocprim on the context's stream: size query, ctx->sort_tmp, run ----
-template <class Call>
-void with_sort_tmp(mvs_ctx* ctx, Call&& call) {   // call(temporary storage, its size)
-    size_t tmp = 0;
-    MVS_HIP(call(nullptr, tmp));
-    ctx->sort_tmp.ensure(tmp + 16);
-    MVS_HIP(call(ctx->sort_tmp.p, tmp));
-}
-template <class KeysIn, class KeysOut, class Size>
-void dev_sort_keys(mvs_ctx* ctx, KeysIn in, KeysOut out, Size n, unsigned begin_bit, unsigned end_bit) {
-    with_sort_tmp(ctx, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, in, out, n, begin_bit, end_bit, ctx->stream); });
-}
-template <class KeysIn, class KeysOut, class ValsIn, class ValsOut, class Size>
-void dev_sort_pairs(mvs_ctx* ctx, KeysIn kin, KeysOut kout, ValsIn vin, ValsOut vout, Size n, unsigned begin_bit, unsigned end_bit) {
-    with_sort_tmp(ctx, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, kin, kout, vin, vout, n, begin_bit, end_bit, ctx->stream); });
-}
-template <class In, class V>
-void dev_exclusive_scan(mvs_ctx* ctx, In in, V* out, size_t n) {   // out[i] = sum of in[0, i) as V
-    with_sort_tmp(ctx, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, in, out, V(0), n, rocprim::plus<V>(), ctx->stream); });
-}
+// (not a template, so it stays out of sort_scan.h: it would put its scan kernels into every file that includes that header)
 inline void dev_inclusive_max_scan(mvs_ctx* ctx, uint32_t* in, uint32_t* out, size_t n) {
     with_sort_tmp(ctx, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, in, out, n, rocprim::maximum<uint32_t>(), ctx->stream); });
 }

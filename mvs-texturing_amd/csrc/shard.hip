@@ -24,7 +24,7 @@
 
 #include <rccl/rccl.h>
 #include <dlfcn.h>
-#include <rocprim/rocprim.hpp>
+#include "sort_scan.h"
 
 #include <atomic>
 #include <chrono>
@@ -472,7 +472,7 @@ struct mvs_shard {
     const uint32_t* d_adj_ptr = nullptr; const uint32_t* d_adj = nullptr; uint32_t E = 0;   // the adjacency lists in the LIBRARY's face order (see mvs_shard_create)
     DBuf<uint32_t> own_adj_ptr, own_adj;
     // Boundary-first colour phases: bnd marks the own nodes with a cut edge (from adjacency + partition alone: made once, at creation).  The
-    // solver's schedule puts them in front of their colour class (k_mrf.hip "zones"), a phase sweeps them first, hands their runs and
+    // solver's schedule puts them in front of their colour class (mrf.h "zones"), a phase sweeps them first, hands their runs and
     // labels to the neighbours and sweeps the interior -- which reads nothing a peer writes -- while they travel.
     DBuf<uint8_t> bnd;
     DBuf<uint32_t> colours; bool colours_valid = false;   // the greedy colouring (a function of the pinned adjacency and the caller's ids): made by the first solve, kept
@@ -753,16 +753,11 @@ struct PeerPush : Transport {
 void sort_pairs(mvs_shard* S, DBuf<unsigned long long>& k, DBuf<unsigned long long>* v, uint32_t n, hipStream_t s) {
     if (n == 0) return;
     S->ks.ensure(n + 1); if (v) S->vs.ensure(n + 1);
-    size_t tmp = 0;
     if (v) {
-        MVS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, k.p, S->ks.p, v->p, S->vs.p, n, 0, 48, s));
-        S->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_pairs(S->sort_tmp.p, tmp, k.p, S->ks.p, v->p, S->vs.p, n, 0, 48, s));
+        dev_sort_pairs(S->sort_tmp, s, k.p, S->ks.p, v->p, S->vs.p, n, 0, 48);
         MVS_HIP(hipMemcpyAsync(v->p, S->vs.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     } else {
-        MVS_HIP(rocprim::radix_sort_keys(nullptr, tmp, k.p, S->ks.p, n, 0, 48, s));
-        S->sort_tmp.ensure(tmp + 16);
-        MVS_HIP(rocprim::radix_sort_keys(S->sort_tmp.p, tmp, k.p, S->ks.p, n, 0, 48, s));
+        dev_sort_keys(S->sort_tmp, s, k.p, S->ks.p, n, 0, 48);
     }
     MVS_HIP(hipMemcpyAsync(k.p, S->ks.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
 }

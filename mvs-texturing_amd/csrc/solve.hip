@@ -113,7 +113,7 @@ mvs_status mvs_ctx_view_selection(mvs_ctx* ctx, const uint32_t* adj_ptr, const u
         if (graphs && issued + GS <= P.max_sweeps) {
             MVS_HIP(hipGraphLaunch(ctx->sweep_exec, s));
             ctx->steps_issued += (uint32_t)GS; ctx->m_sweep_no += (uint32_t)GS; issued += GS; ++ctx->graph_launches;
-            ctx->icm_dirty_valid = false; ctx->best_resolved = false; ctx->exact_valid = false;
+            best_labeling_may_have_changed(ctx);
             // one whole graph stays queued behind the one whose reports are read
             while (issued - lag - GS > polled && !pg.stopped) report((uint32_t)++polled);
         } else {

@@ -1010,7 +1010,7 @@ int mrf_colour(const Mrf& g, std::vector<uint8_t>& colour) {
     return n_colours;
 }
 
-constexpr uint32_t MRF_DAMP_PERIOD = 4u;   // damped sweeps: 1, 5, 9, ... (csrc/k_mrf.hip sweep_alpha restates it)
+constexpr uint32_t MRF_DAMP_PERIOD = 4u;   // damped sweeps: 1, 5, 9, ... (csrc/k_mrf_sweep.hip sweep_alpha restates it)
 
 // One phase of a sweep: all nodes of colour `phase` (an independent set) recompute their outgoing messages IN PLACE
 // from the current messages -- colour-phased Gauss-Seidel.  Within a phase no node reads what another writes.

@@ -3,7 +3,7 @@ substitution, linked with the product's other objects.  usage: python scripts/bu
 -> mvs-texturing_amd/csrc/variants/libmvs_viewsel_NAME.so  (git-ignored, travels to the GPU box)
 --patch=FILE.patch:TARGET.hip applies a unified diff to the copy of TARGET first (the sweep kernel's access-pattern probes live in
 scripts/probe/sweep4_probes.patch, not in the product source):
-    python scripts/build_variant.py cachehot --patch=scripts/probe/sweep4_probes.patch:k_mrf.hip -DMVS_SWEEP_EXP=1 k_mrf.hip '' ''"""
+    python scripts/build_variant.py cachehot --patch=scripts/probe/sweep4_probes.patch:k_mrf_sweep.hip -DMVS_SWEEP_EXP=1 k_mrf_sweep.hip '' ''"""
 import os, subprocess, sys, tempfile, shutil
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mvs-texturing_amd"))

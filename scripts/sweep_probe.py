@@ -1,4 +1,4 @@
-"""Where does the sweep kernel's time go?  Variants of the library built with -DMVS_SWEEP_EXP=n (csrc/k_mrf.hip: 1 = every data access
+"""Where does the sweep kernel's time go?  Variants of the library built with -DMVS_SWEEP_EXP=n (csrc/k_mrf_sweep.hip: 1 = every data access
 inside a 64 KB window = the non-memory floor, 2 = loads and stores only = the memory floor, 3 / 4 = three / two waves per SIMD) against
 the product build: a fixed number of sweeps on the resident table of a BASELINE configuration, time per sweep from the stage profiler.
 Variants 1 and 2 compute garbage: only their time is looked at.

@@ -1,4 +1,4 @@
-"""The MRF solver (csrc/k_mrf.hip) against the CPU oracle on CRAFTED instances (util_cases "crafted MRF instances"): tied costs, columns
+"""The MRF solver (csrc/k_mrf_setup.hip, k_mrf_sweep.hip, k_mrf_polish.hip) against the CPU oracle on CRAFTED instances (util_cases "crafted MRF instances"): tied costs, columns
 exactly at the boundaries of the per-node routing, launches of one to three nodes, nodes without a neighbour in the model -- end to end
 under parameter sets that each pin one tie rule, through every route of the set-up and the sweep loop, sweep by sweep against the
 oracle's decode trace, and over three logical shards.  Every comparison is of integers or bit patterns: there is no tolerance.

@@ -391,7 +391,7 @@ def test_mrf_random_instances_all_kernel_paths(ctx, case):
 
 @pytest.mark.parametrize("seed", [11, 12])
 def test_mrf_mixed_node_classes_in_one_graph(seed):
-    """per-node routing of the sweep (k_mrf.hip mrf_node_class): short columns, columns of 100 / 200 / 300 labels and nodes of
+    """per-node routing of the sweep (k_mrf_setup.hip mrf_node_class): short columns, columns of 100 / 200 / 300 labels and nodes of
     degree up to 6 in ONE graph -- lane groups of 8, 16, 32 and 64 lanes and the generic kernel run side by side inside every
     colour phase, fast nodes exchange messages with generic neighbours.  Labels, energy and sweeps equal the oracle's, and the
     same solve with every node forced onto the generic kernel gives the same result (the split into launches is free: a colour

@@ -1,4 +1,4 @@
-"""The solver's set-up from per-face view bitmaps (k_mrf.hip mrf_bitmap_kernel, mrf_record_bits_kernel, mrf_map_bits_kernel; the
+"""The solver's set-up from per-face view bitmaps (k_mrf_setup.hip mrf_bitmap_kernel, mrf_record_bits_kernel, mrf_map_bits_kernel; the
 arithmetic in dmath.h "view-set bitmaps").
 
 A column's view ids are strictly ascending (calculate_data_costs.cpp:272), so a column is a bitmap: two columns are identical iff
@@ -94,7 +94,8 @@ def _solve(table, adj_ptr, adj, params, force_lists, prune=0, tables=True):
     n, V, col_ptr, view_id, cost = table
     c = M.Context(0)
     try:
-        c.set_option("mrf_force_lists", force_lists)
+        if force_lists is not None:                         # (None: no option set, the set-up decides)
+            c.set_option("mrf_force_lists", force_lists)
         c.costs_upload(M.viewsel.DataCosts(n, V, col_ptr, view_id, cost))
         if prune:
             c.prune_labels(prune)
@@ -196,6 +197,32 @@ def test_generic_senders_maps_from_bitmaps():
             c.close()
         assert np.array_equal(lo, lg)
         assert (so["energy_fixed"], so["sweeps"], so["icm_iters"]) == (sg["energy_fixed"], sg["sweeps"], sg["icm_iters"])
+
+
+@pytest.mark.gpu
+def test_route_decision_at_1024_views():
+    """the set-up's own choice of route on both sides of its boundary, W = ceil(V / 64) <= 16 words: bitmaps at V = 1024, lists at
+    V = 1025 with no option set (the 1025 instance has entries with id 1024, the seventeenth word); at both, the oracle's results, and
+    the same records, descriptors and identity flags whichever route is forced"""
+    n = 600
+    for V in (1024, 1025):
+        col_ptr, view_id, cost, adj_ptr, adj = random_mrf(n, V, 40, 3, 31, 0.05)
+        t = (n, V, col_ptr, view_id, cost)
+        if V == 1025:
+            assert int((np.asarray(view_id) == 1024).sum()) == 10
+        lo, so = O.view_selection(O.CsrNp(*t), adj_ptr, adj)
+        ld, sd, td = _solve(t, adj_ptr, adj, {}, None)
+        assert bool(td["bitmaps"]) == (V == 1024), V
+        l0, s0, t0 = _solve(t, adj_ptr, adj, {}, 0)
+        l1, s1, t1 = _solve(t, adj_ptr, adj, {}, 1)
+        assert bool(t0["bitmaps"]) == (V == 1024) and not t1["bitmaps"], V
+        print(V, "bitmaps", bool(td["bitmaps"]), "sweeps", sd["sweeps"], "fast nodes", td["desc"].shape[0], "record words", td["rec"].size)
+        for lg, sg in ((ld, sd), (l0, s0), (l1, s1)):
+            assert np.array_equal(lo, lg), V
+            assert (so["energy_fixed"], so["sweeps"], so["icm_iters"]) == (sg["energy_fixed"], sg["sweeps"], sg["icm_iters"]), V
+        for k in ("rec", "desc", "ident"):
+            assert t0[k].shape == t1[k].shape and t0[k].tobytes() == t1[k].tobytes(), (V, k)
+            assert td[k].tobytes() == t0[k].tobytes(), (V, k)
 
 
 def broken_tables():

@@ -147,7 +147,7 @@ class _FakeOps:
         self.arr[G.BEST_LAB][:] = self.arr[G.LAB]
 
     def step(self, e):
-        """host restatement of the device-side bookkeeping (k_mrf.hip mrf_step_kernel)"""
+        """host restatement of the device-side bookkeeping (k_mrf_polish.hip mrf_step_kernel)"""
         st = self.state
         if st["stopped"]:
             st["improved"] = 0

@@ -131,7 +131,7 @@ class HaloPlan:
         src = adj                                               # j
         valid = (K[dst] > 0) & (K[src] > 0)
         size = np.where(valid, K[dst], 0)                      # message elements per directed edge
-        padded = (size + 3) & ~3                               # runs are padded to a multiple of 4 elements in HBM (k_mrf.hip)
+        padded = (size + 3) & ~3                               # runs are padded to a multiple of 4 elements in HBM (k_mrf_setup.hip)
         if in_off is None:   # node-major layout (stand-in ops of the CPU tests)
             in_off = np.zeros(len(size) + 1, dtype=np.int64); in_off[1:] = np.cumsum(padded)
             in_off += MSG_BASE                                 # the library reserves [0, MSG_BASE) (zero / identity run)

@@ -32,7 +32,7 @@ def random_mrf(n_nodes, n_views, max_k, max_deg, seed, p_empty=0.1):
 def random_mrf_mixed(n_nodes, n_views, seed, base_k=6, p_long=0.03, long_k=(100, 200, 300), p_hub=0.01, hub_deg=6):
     """A mostly manifold-like instance (degree <= 3, columns of <= base_k labels) with a few LONG columns (long_k entries, some
     beyond the 255 a fast node holds) and a few HUB nodes of degree > 3 (non-manifold edges): every node class of the solver's
-    per-node routing (k_mrf.hip mrf_node_class) occurs in one colour phase, next to each other."""
+    per-node routing (k_mrf_setup.hip mrf_node_class) occurs in one colour phase, next to each other."""
     rng = np.random.default_rng(seed)
     lists = [[] for _ in range(n_nodes)]
     cap = np.where(rng.random(n_nodes) < p_hub, hub_deg, 3)
@@ -577,7 +577,7 @@ TIED_K = (1, 3, 4, 5, 31, 32, 33, 57, 63, 64, 65, 127, 128, 129, 254, 255, 256, 
 TIED_TIERS = ((1, 3, 4, 5, 31, 32), (33, 57, 63, 64), (65, 127, 128), (129, 254, 255), (256, 257))   # TIED_K by the class a neighbourhood of them gets
 # tier of each of the 40 segments of tied_mrf: 20, 10, 5, 3 and 2 segments of tiers 0 .. 4 (the long columns cost the oracle most), interleaved
 TIED_SEGMENT_TIER = tuple(([0] * 20 + [1] * 10 + [2] * 5 + [3] * 3 + [4] * 2)[(7 * k) % 40] for k in range(40))
-# nodes per 256-thread block of the five sweep launches (csrc/k_mrf.hip): launch_sweep4_g<G> hands launch_fast 256 / G with G = 8, 32, 64
+# nodes per 256-thread block of the five sweep launches (csrc/k_mrf_sweep.hip): launch_sweep4_g<G> hands launch_fast 256 / G with G = 8, 32, 64
 # for classes 0, 2, 3, launch_sweep8 256 / 8 for class 1, launch_sweep_generic one block per node
 MRF_NODES_PER_BLOCK = (256 // 8, 256 // 8, 256 // 32, 256 // 64, 1)
 MRF_CLASS_K = ((1, 32), (33, 64), (65, 128), (129, 255), (256, 257))      # kmx of classes 0 .. 3 (mrf_node_class); 4: a column past 255 labels
@@ -603,7 +603,7 @@ def rounding_pair(c):
 
 
 def mrf_hash32(x):
-    """the hash of the colouring's keys as csrc/k_mrf.hip and oracle.cpp give it"""
+    """the hash of the colouring's keys as csrc/k_mrf_setup.hip and oracle.cpp give it"""
     x = np.asarray(x, np.uint64).copy(); m = np.uint64(0xFFFFFFFF)
     x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & m
     x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & m
@@ -625,7 +625,7 @@ def colouring_numpy(adj_ptr, adj):
 
 
 def node_classes_numpy(col_ptr, adj_ptr, adj):
-    """mrf_node_class as csrc/k_mrf.hip documents it: kmx = the longest column among the node and its neighbours (0 for a node whose own
+    """mrf_node_class as csrc/k_mrf_setup.hip documents it: kmx = the longest column among the node and its neighbours (0 for a node whose own
     column is empty); degree > 3 (neighbours with empty columns count) or kmx > 255 -> 4 (generic), else 0 / 1 / 2 / 3 for
     kmx <= 32 / 64 / 128 / 255.  A table of fewer than four entries or a graph without an edge is generic throughout."""
     K = np.diff(np.asarray(col_ptr, np.int64)); F = len(K)
