@@ -31,6 +31,16 @@ mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts_device, uint16_t*
  * with the geometric visibility test, when the last pass covered a face range and not the whole mesh, or (which = 0, 1) when it walked
  * the mesh in more than one range (option "dc_range_pairs"): the matrices then hold the last range's rays only. */
 mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
+/* HARNESS ONLY (tests/test_gpu_mrf_regions.py): mvs_ctx_costs_upload of a HOST table whose columns stand in POSITION order, column p being
+ * the caller's face order_host[p] -- and the context left as a data-cost pass over the whole mesh leaves it (name_table_order, k_dc.hip): the
+ * active table lives in "the library's own order", mvs_ctx_table_order returns `order`, its inverse is known, both on the device and owned
+ * by the context (they take the place of the resident mesh's face order, which the next data-cost pass derives again; the next plain
+ * mvs_ctx_costs_upload ends the ordered state).  So crafted tables reach the branches of the solver that translate positions into the
+ * caller's ids -- colouring keys, the ICM winner rule, region names, the label scatter, the adjacency renumbering -- in ANY order, not
+ * only behind a scene's data costs.  To be followed by mvs_ctx_view_selection only (adjacency and labels in the CALLER's numbering, as
+ * always): the other consumers of an ordered table belong to a resident mesh.  MVS_ERR_INVALID, with the context untouched, when
+ * order_host is not a permutation of 0 .. n_faces - 1; MVS_ERR_STATE on a context whose face order a shard has pinned (mvs_shard_create). */
+mvs_status mvs_ctx_costs_upload_ordered(mvs_ctx* ctx, const mvs_csr* csr_in_position_order, const uint32_t* order_host);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----
  * Every rank holds the FULL cost table and adjacency (288 GB of HBM make the

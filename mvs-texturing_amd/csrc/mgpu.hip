@@ -146,6 +146,34 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
     MVS_API_END
 }
 
+// harness only: a host table in position order + the order itself -> the state name_table_order (k_dc.hip) leaves behind a pass over the
+// whole mesh.  f_perm / f_pos carry it: they no longer describe the resident mesh (mesh_ordered = false; every data-cost pass derives the
+// mesh's order again before it reads them), and a shard that pinned them keeps them.
+mvs_status mvs_ctx_costs_upload_ordered(mvs_ctx* ctx, const mvs_csr* csr, const uint32_t* order) {
+    if (!ctx || !csr || !csr->col_ptr || (!order && csr->n_faces)) return api_fail(MVS_ERR_INVALID, "null argument");
+    if (ctx->order_pinned) return api_fail(MVS_ERR_STATE, "ordered upload: a shard owns this context's face order");
+    const uint32_t F = csr->n_faces;
+    std::vector<uint32_t> pos(F, 0xFFFFFFFFu);
+    for (uint32_t p = 0; p < F; ++p) {
+        const uint32_t id = order[p];
+        if (id >= F) return api_fail(MVS_ERR_INVALID, "ordered upload: order[" + std::to_string(p) + "] = " + std::to_string(id) + " is no face id (n_faces = " + std::to_string(F) + ")");
+        if (pos[id] != 0xFFFFFFFFu) return api_fail(MVS_ERR_INVALID, "ordered upload: face " + std::to_string(id) + " stands at positions " + std::to_string(pos[id]) + " and " + std::to_string(p) + ": not a permutation");
+        pos[id] = p;
+    }
+    const mvs_status st = mvs_ctx_costs_upload(ctx, csr, 0);
+    if (st != MVS_OK) return st;
+    MVS_CTX_API_BEGIN
+    ctx->mesh_ordered = false;
+    ctx->f_perm.ensure((size_t)F + 1); ctx->f_pos.ensure((size_t)F + 1);
+    if (F) {
+        MVS_HIP(hipMemcpyAsync(ctx->f_perm.p, order, (size_t)F * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        MVS_HIP(hipMemcpyAsync(ctx->f_pos.p, pos.data(), (size_t)F * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->t_perm = ctx->f_perm.p; ctx->t_pos = ctx->f_pos.p;
+    MVS_API_END
+}
+
 mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");

@@ -206,7 +206,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_costs_upload_ordered"))
 
 
 _lib = None
@@ -265,6 +265,7 @@ def load_library():
         "mvs_ctx_mrf_labels": [vp, u32, u32, vp, C.POINTER(u32)],
         "mvs_ctx_mrf_setup_tables": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_ray_bits": [vp, i32, vp, u64, C.POINTER(u64)],
+        "mvs_ctx_costs_upload_ordered": [vp, C.POINTER(CCsr), vp],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_comm_unique_id": [vp], "mvs_comm_create_rccl": [i32, i32, i32, vp, C.POINTER(vp)], "mvs_comm_create_local": [i32, C.POINTER(vp)], "mvs_comm_create_local_devices": [i32, vp, C.POINTER(vp)],
@@ -528,7 +529,7 @@ class Context:
         """uint32[F]: the caller's face id of every column of the resident table as the library keeps it, or None (caller's order);
         after set_face_range(b, e) only the first e - b entries are meaningful (the columns of the range)"""
         import torch
-        F = self.n_faces
+        F = getattr(self, "n_faces", 0)       # (no mesh, no ordered upload: the table, if any, is in the caller's order and nothing is written)
         out = torch.zeros(max(F, 1), dtype=torch.int32, device="cuda:%d" % self.device)
         torch.cuda.synchronize(self.device)   # the library writes on the context's stream, torch filled on its own
         flag = C.c_int(0)
@@ -573,6 +574,26 @@ class Context:
         s, dev = dc._struct()
         self._keep["costs"] = dc
         _check(self.L, self.L.mvs_ctx_costs_upload(self.h, C.byref(s), dev))
+
+    def costs_upload_ordered(self, dc, order):
+        """mvs_ctx_costs_upload_ordered (building-blocks library; test harness only): the host table `dc`, given in the CALLER's numbering, is
+        uploaded with its columns in the order `order` (order[p] = the caller's id of column p) and the context left as after a data-cost
+        pass in the library's own face order: table_order() returns `order`.  Follow it with view_selection (adjacency and labels in the
+        caller's numbering, as always) only."""
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        cp = np.asarray(dc.col_ptr, np.int64)
+        assert len(order) == dc.n_faces == len(cp) - 1
+        idx = order.astype(np.int64)
+        ok = idx < dc.n_faces                                        # an id that is no face: an empty column; the library refuses the order
+        K = np.where(ok, np.diff(cp)[np.minimum(idx, max(dc.n_faces - 1, 0))], 0) if dc.n_faces else np.zeros(0, np.int64)
+        ptr = np.zeros(dc.n_faces + 1, np.uint32); ptr[1:] = np.cumsum(K)
+        take = (np.repeat(cp[:-1][np.where(ok, idx, 0)] - ptr[:-1].astype(np.int64), K) + np.arange(int(ptr[-1]))) if dc.n_faces else np.zeros(0, np.int64)
+        t = DataCosts(dc.n_faces, dc.n_views, ptr, np.ascontiguousarray(np.asarray(dc.view_id)[take]), np.ascontiguousarray(np.asarray(dc.cost)[take]))
+        s, dev = t._struct()
+        assert not dev, "a host table"
+        _check(self.L, self.L.mvs_ctx_costs_upload_ordered(self.h, C.byref(s), order.ctypes.data_as(C.c_void_p)))
+        self._keep["costs"] = t
+        self.n_faces = dc.n_faces
 
     def view_selection(self, adj_ptr, adj, params=None, labels_out=None):
         """tex::view_selection on the resident costs; returns (labels u32[F], stats)."""

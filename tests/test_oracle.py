@@ -703,3 +703,83 @@ def test_plateau_parameters_run_every_sweep():
         labels, st, tr = O.view_selection_traced(_mrf_csr(case), case.adj_ptr, case.adj, O.default_mrf_params(**U.CRAFTED_PARAMS["plateau"]), n_sweeps=40)
         best = np.minimum.accumulate(tr["energy"])
         assert st["sweeps"] == 40 and any(best[s] == best[s - 5] for s in range(6, 40)), name
+
+
+# ---- region moves on crafted instances (util_cases "region moves on crafted instances"): the oracle's rounds against a third statement
+# ---- written from the rule text (region_round_numpy), the instances' own properties, a witness per rule that the instances can tell the
+# ---- rule from its inversion, and the tie counts the GPU tests rely on; tests/test_gpu_mrf_regions.py runs the same instances on the GPU
+
+REGION_CASES = {**U.crafted_cases(), **U.region_cases()}
+REGION_START = U.CRAFTED_REGION_PARAMS["start"]
+
+
+@pytest.mark.parametrize("name", list(REGION_CASES))
+def test_region_rounds_agree_with_the_rule_text_round_by_round(name):
+    """from the argmin-unary labeling ("start": no sweep, a polish of zero iterations), for r = 1, 2, ..: the oracle's labels after r region
+    rounds are the model's, its move count the model's, and its energy has dropped by exactly the sum of the gains of the regions the
+    model moved; with region_rounds = 8 it runs as many rounds as the model finds moves in"""
+    case = REGION_CASES[name]()
+    csr = _mrf_csr(case)
+    start = U.argmin_labels(case)
+    l0, s0 = O.view_selection(csr, case.adj_ptr, case.adj, O.default_mrf_params(**{**REGION_START, "region_rounds": 0}))
+    assert np.array_equal(l0, start) and (s0["region_rounds"], s0["region_moves"]) == (0, 0)
+    assert energy_numpy(case.col_ptr, case.view_id, case.cost, case.adj_ptr, case.adj, start) == (s0["energy_fixed"], s0["cut_edges"])
+    rounds = U.region_rounds_numpy(case, start, REGION_START["region_rounds"])
+    energy, moves = s0["energy_fixed"], 0
+    for r, (lab, moved, _) in enumerate(rounds, 1):
+        lo, so = O.view_selection(csr, case.adj_ptr, case.adj, O.default_mrf_params(**{**REGION_START, "region_rounds": r}))
+        energy -= sum(g for _, g in moved.values()); moves += len(moved)
+        assert all(g > 0 for _, g in moved.values())
+        assert np.array_equal(lo, lab), "round %d: %d labels differ from the model's, first at node %d" % (r, int((lo != lab).sum()), int(np.nonzero(lo != lab)[0][0]))
+        assert (so["region_rounds"], so["region_moves"], so["energy_fixed"]) == (r, moves, energy), "round %d" % r
+        assert energy_numpy(case.col_ptr, case.view_id, case.cost, case.adj_ptr, case.adj, lab)[0] == energy
+    lo, so = O.view_selection(csr, case.adj_ptr, case.adj, O.default_mrf_params(**REGION_START))
+    assert so["region_rounds"] == len(rounds) and so["region_moves"] == moves and so["energy_fixed"] == energy
+    if rounds: assert np.array_equal(lo, rounds[-1][0])
+
+
+# rule -> (instance, the inversion): the model with that ONE rule inverted ends round 1 on other labels -- an implementation that has the
+# rule the other way round cannot pass on that instance
+REGION_WITNESSES = [
+    ("label_tie", "hub65_wnone_aligned", dict(label_tie="larger")), ("label_tie", "tied1", dict(label_tie="larger")),
+    ("name_tie", "chain", dict(name_tie="larger")), ("name_tie", "tied1", dict(name_tie="larger")),
+    ("name", "tied1", dict(name="position", order="reversed")), ("name", "chain", dict(name="position", order="reversed")),
+    ("name", "tied3", dict(name="position", order="random")),
+    ("zero_gain_moves", "large_zero", dict(zero_gain_moves=True)), ("zero_gain_moves", "tied1", dict(zero_gain_moves=True)),
+    ("ignore_lacking", "large_lacking", dict(ignore_lacking=True)), ("ignore_lacking", "tied1", dict(ignore_lacking=True)),
+]
+
+
+@pytest.mark.parametrize("rule,name,inverted", REGION_WITNESSES, ids=["%s-%s" % (r, n) for r, n, _ in REGION_WITNESSES])
+def test_region_rule_witnesses(rule, name, inverted):
+    case = REGION_CASES[name]()
+    start = U.argmin_labels(case)
+    rules = dict(inverted)
+    if "order" in rules: rules["order"] = U.table_orders(len(start))[rules["order"]]
+    good = U.region_round_numpy(case, start)[0]
+    bad = U.region_round_numpy(case, start, rules)[0]
+    assert int((good != bad).sum()) > 0, "inverting %s changes nothing on %s" % (rule, name)
+    if rule == "name":      # under the identity positions ARE names
+        assert np.array_equal(U.region_round_numpy(case, start, dict(name="position", order=U.table_orders(len(start))["identity"]))[0], good)
+
+
+def test_every_invertible_region_rule_has_a_witness():
+    assert {r for r, _, _ in REGION_WITNESSES} == set(U.REGION_RULES)
+
+
+def test_region_tie_material_of_the_crafted_instances():
+    """conditions the GPU tests rest on, on tied1 from the argmin start (measured: 404 / 35 / 739 / 2834 and 408 tied edges in all; tied3:
+    440 of 446 edges, 96 label ties): enough tied directed cut edges that positions in reversed order would decide differently from
+    names, enough label ties, zero-gain candidates and lacking candidates; the hubs have nc candidates, region_large 700 faces in a region"""
+    case = REGION_CASES["tied1"]()
+    F = len(case.col_ptr) - 1
+    cnt = U.region_round_numpy(case, U.argmin_labels(case), dict(order=U.table_orders(F)["reversed"]))[2]
+    assert cnt["tied_edges_flipped"] >= 100 and cnt["label_ties"] >= 20 and cnt["zero_gain"] >= 100 and cnt["lacking"] >= 1000, cnt
+    assert U.region_round_numpy(case, U.argmin_labels(case), dict(order=U.table_orders(F)["identity"]))[2]["tied_edges_flipped"] == 0
+    assert max(U.region_round_numpy(c, U.argmin_labels(c))[2]["max_candidates"] for c in (b() for n, b in U.crafted_cases().items())) < 64, "the existing instances never reach the second chunk"
+    for nc in U.REGION_HUB_NC:
+        case = U.region_hub(nc, 0, "aligned")
+        assert U.region_round_numpy(case, U.argmin_labels(case))[2]["max_candidates"] == nc
+    case = U.region_large("moves")
+    assert U.region_round_numpy(case, U.argmin_labels(case))[2]["max_region"] >= 700
+    assert sorted(len(o) for o in U.table_orders(7).values()) == [7, 7, 7] and all(sorted(o.tolist()) == list(range(7)) for o in U.table_orders(7).values())

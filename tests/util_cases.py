@@ -962,3 +962,316 @@ def crafted_cases():
         for n in small_range_counts(cls):
             out["range_c%d_n%d" % (cls, n)] = (lambda cls=cls, n=n: small_range_mrf(cls, n))
     return out
+
+
+# ---- region moves on crafted instances (tests/test_gpu_mrf_regions.py; the CPU half runs in tests/test_oracle.py): a THIRD statement of one
+# ---- region round, written from the rule text of DESIGN.md section 6 / the header of csrc/k_region.hip and from neither implementation's
+# ---- data layout, and instances for the paths the tied_* instances do not reach.  New costs are multiples of 1 / 64: every fixed-point
+# ---- sum is exact, every tie designed.
+
+CRAFTED_REGION_PARAMS = {
+    "start": dict(max_sweeps=0, icm_iters=0, region_rounds=8),          # region rounds alone, from the argmin-unary labeling (a polish of zero iterations)
+    "start_icm": dict(max_sweeps=0, icm_iters=100, region_rounds=8),
+    "defaults6": dict(region_rounds=6),
+}
+REGION_RULES = ("label_tie", "name_tie", "name", "zero_gain_moves", "ignore_lacking")      # what region_round_numpy can invert, one at a time
+
+
+def fix32_int(c):
+    """a cost in 32.32 fixed point as the solver's definition has it: the fp32 value, widened, times 2^32, truncated"""
+    return int(np.float64(np.float32(c)) * 4294967296.0)
+
+
+def argmin_labels(case):
+    """the labeling a solve without sweeps starts from: per node the FIRST label of smallest exact cost, 0 for an empty column"""
+    out = np.zeros(len(case.col_ptr) - 1, np.uint32)
+    for i in range(len(out)):
+        a, b = int(case.col_ptr[i]), int(case.col_ptr[i + 1])
+        if b > a: out[i] = int(case.view_id[a + int(np.argmin(case.cost[a:b]))]) + 1
+    return out
+
+
+def table_orders(F):
+    """name -> order (order[p] = the caller's id of the node at position p): the identity, the reversed order, one seeded random permutation"""
+    return {"identity": np.arange(F, dtype=np.uint32), "reversed": np.arange(F, dtype=np.uint32)[::-1].copy(),
+            "random": np.random.default_rng([F, 23]).permutation(F).astype(np.uint32)}
+
+
+def region_round_numpy(case, labels, rules=None):
+    """ONE round of region moves, from the rule text alone.  A region is a connected set of equally labelled faces over the model's edges
+    (both columns non-empty; an edge listed twice is two edges), named by its smallest face.  Its candidates are the labels of the faces
+    on the other side of its cut edges; a candidate that one face of the region lacks does not count; the gain of candidate l is
+    sum over the region's faces of (D(current) - D(l)) in 32.32 fixed point + 2^32 x the cut edges towards faces labelled l.  The best
+    candidate has the largest gain, among equal ones the smaller label.  The region moves iff that gain is positive and every neighbouring
+    region's best gain (0 without a positive one) is smaller, or equal with a larger name.
+    rules inverts exactly one rule: label_tie = "larger"; name_tie = "larger"; name = "position" with order = the table order (a region
+    is named by its smallest POSITION); zero_gain_moves = True (a gain of exactly 0 counts as positive); ignore_lacking = True (faces
+    that lack the candidate are left out of the sum, the candidate counts).  An `order` without name = "position" only feeds the counter.
+    Returns (labels after the round, {region name: (new label, gain)} of the regions that moved, counters): tied_edges = directed cut
+    edges whose two regions hold equal positive gains, tied_edges_flipped = those of them that the smallest positions under `order`
+    decide the other way round than the names, label_ties = candidates that reach their region's positive best gain beside the one that is taken,
+    zero_gain = counting candidates of gain exactly 0, lacking = candidates a face lacks, max_candidates, max_region, regions,
+    and candidates_before = {region name: candidates of all regions of smaller name}."""
+    rules = dict(rules or {})
+    assert set(rules) <= {"label_tie", "name_tie", "name", "order", "zero_gain_moves", "ignore_lacking"}
+    F = len(case.col_ptr) - 1
+    lab = [int(x) for x in labels]
+    cols = []
+    for i in range(F):
+        a, b = int(case.col_ptr[i]), int(case.col_ptr[i + 1])
+        cols.append({int(v) + 1: fix32_int(c) for v, c in zip(case.view_id[a:b], case.cost[a:b])})
+        assert (lab[i] in cols[i]) if cols[i] else lab[i] == 0
+    nbrs = [[int(j) for j in case.adj[case.adj_ptr[i]:case.adj_ptr[i + 1]] if cols[i] and cols[int(j)]] for i in range(F)]
+    region_of = [None] * F; members = {}
+    for i in range(F):                                   # ascending: the face a region is found from is its smallest
+        if region_of[i] is not None: continue
+        region_of[i] = i; members[i] = [i]; todo = [i]
+        while todo:
+            u = todo.pop()
+            for v in nbrs[u]:
+                if region_of[v] is None and lab[v] == lab[u]:
+                    region_of[v] = i; members[i].append(v); todo.append(v)
+    pos = None
+    if "order" in rules:
+        pos = np.zeros(F, np.int64); pos[np.asarray(rules["order"], np.int64)] = np.arange(F)
+    by_position = rules.get("name") == "position"
+    assert not by_position or pos is not None
+    key = {R: (min(int(pos[i]) for i in m) if by_position else R) for R, m in members.items()}
+    posname = {R: min(int(pos[i]) for i in m) for R, m in members.items()} if pos is not None else None
+    counters = dict(tied_edges=0, tied_edges_flipped=0, label_ties=0, zero_gain=0, lacking=0, max_candidates=0,
+                    max_region=max([len(m) for m in members.values()] + [0]), regions=len(members), candidates_before={})
+    best = {}; neighbours = {}; n_before = 0
+    for R in sorted(members):
+        m = members[R]
+        count = collections.Counter(lab[j] for i in m for j in nbrs[i] if lab[j] != lab[i])
+        neighbours[R] = {region_of[j] for i in m for j in nbrs[i] if lab[j] != lab[i]}
+        counters["candidates_before"][R] = n_before; n_before += len(count)
+        counters["max_candidates"] = max(counters["max_candidates"], len(count))
+        gains = {}
+        for l, n in count.items():
+            have = [i for i in m if l in cols[i]]
+            if len(have) < len(m):
+                counters["lacking"] += 1
+                if not rules.get("ignore_lacking"): continue
+            g = sum(cols[i][lab[i]] for i in m) - sum(cols[i][l] for i in have) + (n << 32)
+            if g == 0 and len(have) == len(m): counters["zero_gain"] += 1
+            gains[l] = g
+        ok = {l: g for l, g in gains.items() if g > 0 or (g == 0 and rules.get("zero_gain_moves"))}
+        if ok:
+            top = max(ok.values()); tied = [l for l, g in ok.items() if g == top]
+            if top > 0: counters["label_ties"] += len(tied) - 1
+            best[R] = (top, max(tied) if rules.get("label_tie") == "larger" else min(tied))
+    gain_of = lambda R: best[R][0] if R in best else 0
+    for i in range(F):
+        for j in nbrs[i]:
+            R, S = region_of[i], region_of[j]
+            if lab[i] != lab[j] and gain_of(R) == gain_of(S) > 0:
+                counters["tied_edges"] += 1
+                if posname is not None and (S < R) != (posname[S] < posname[R]): counters["tied_edges_flipped"] += 1
+    new = list(lab); moved = {}
+    for R, (g, l) in best.items():
+        beaten = False
+        for S in neighbours[R]:
+            gs = gain_of(S) if S in best else (0 if not rules.get("zero_gain_moves") else -1)
+            first = key[S] > key[R] if rules.get("name_tie") == "larger" else key[S] < key[R]
+            if gs > g or (gs == g and first): beaten = True
+        if beaten: continue
+        moved[R] = (l, g)
+        for i in members[R]: new[i] = l
+    return np.array(new, np.uint32), moved, counters
+
+
+def region_rounds_numpy(case, labels, rounds, rules=None):
+    """up to `rounds` rounds of region_round_numpy, ending with the first in which no region moves: [(labels, moved, counters)] of the
+    rounds that moved something (the solver's stats.region_rounds is its length)"""
+    out = []; lab = np.asarray(labels, np.uint32)
+    for _ in range(rounds):
+        lab, moved, counters = region_round_numpy(case, lab, rules)
+        if not moved: break
+        out.append((lab, moved, counters))
+    return out
+
+
+def _case64(lists, cols64, n_views=CRAFTED_VIEWS):
+    """MrfCase from adjacency lists and per node {label: cost in 64ths} (label = view id + 1)"""
+    cols = [(np.array([l - 1 for l in sorted(c)], np.uint16), np.array([c[l] / 64.0 for l in sorted(c)], np.float32)) for c in cols64]
+    assert all(0 <= x <= 64 for c in cols64 for x in c.values())
+    return _mrf_case(lists, cols, n_views)
+
+
+def _link(lists, a, b): lists[a].append(b); lists[b].append(a)
+
+
+REGION_HUB_NC = (63, 64, 65, 128, 129)
+REGION_HUB_PLACES = {"aligned": 64, "unaligned": 5, "aligned_last": None}
+
+
+@functools.lru_cache(maxsize=None)
+def region_hub(nc, winner, place):
+    """A hub region of three faces (a path, label 1, cost 16/64 each) whose columns hold the labels 1 .. nc + 1, every other one at 32/64,
+    and nc leaves -- one-face regions with the one-label columns {2}, .., {nc + 1} -- spread over the three faces: nc candidates of
+    the same gain 3 x (16 - 32) / 64 + 1 edge = 16/64, the hub's label lacking in every leaf.  `winner` = w makes candidate number w in
+    ascending label order better by 1/64 -- one hub face has it at 31/64 ((nc + w) even), or a second leaf of that label hangs on the
+    hub ((nc + w) odd: one edge more) --; None leaves them all tied: the smallest label.  Property (asserted with the model): the hub
+    moves in round 1, to label w + 2, it has nc candidates, and nobody else moves.  `place`: the candidates are kept sorted by (region
+    name, label) and every node in front of the hub's first face owns exactly one (leaves: the hub's label; padding: a path of
+    one-label faces, two labels in turn), so the hub's run of nc candidates starts at position 64 ("aligned": with nc = 64 and 128 it ends on a 64-key chunk of
+    rg_accumulate_kernel's loop; leaves follow it), at position 5 ("unaligned") or at a multiple of 64 with nothing behind
+    it ("aligned_last")."""
+    n_leaves = nc + (1 if winner is not None and (nc + winner) % 2 else 0)
+    before = REGION_HUB_PLACES[place]
+    if before is None:                                   # everything in front of the hub, as many as a multiple of 64
+        pad = (-n_leaves) % 64
+        if pad == 1: pad += 64
+    else:
+        pad = max(0, before - n_leaves)
+        if pad == 1 or n_leaves + pad == before: pad += 2          # a padding node needs a partner; something sorts behind the hub's run
+    F = n_leaves + pad + 3
+    hub = [F - 3, F - 2, F - 1] if before is None else [before, before + 1, F - 1]
+    rest = [i for i in range(F) if i not in hub]
+    pads, leaves = rest[:pad], rest[pad:]
+    lists = [[] for _ in range(F)]; cols = [None] * F
+    _link(lists, hub[0], hub[1]); _link(lists, hub[1], hub[2])
+    for h in hub: cols[h] = {1: 16, **{l: 32 for l in range(2, nc + 2)}}
+    for k, leaf in enumerate(leaves[:nc]):
+        cols[leaf] = {k + 2: 8}; _link(lists, hub[(k * 7) % 3], leaf)
+    if winner is not None:
+        if n_leaves > nc: cols[leaves[nc]] = {winner + 2: 8}; _link(lists, hub[winner % 3], leaves[nc])
+        else: cols[hub[winner % 3]][winner + 2] = 31
+    for k, a in enumerate(pads):                         # a path of one-label faces, labels alternating: one candidate each
+        cols[a] = {600 + k % 2: 8}
+        if k: _link(lists, pads[k - 1], a)
+    case = _case64(lists, cols)
+    start = argmin_labels(case)
+    assert np.all(start[hub] == 1)
+    lab, moved, cnt = region_round_numpy(case, start)
+    want = 2 if winner is None else winner + 2
+    assert moved == {hub[0]: (want, (16 << 26) + (0 if winner is None else (1 << 32) if n_leaves > nc else (1 << 26)))}, (moved, want)
+    assert cnt["max_candidates"] == nc and cnt["candidates_before"][hub[0]] == hub[0] and hub[0] % 64 == (5 if place == "unaligned" else 0)
+    assert (cnt["candidates_before"][hub[0]] == n_leaves + pad) == (place == "aligned_last")       # every other candidate in front: nothing sorts behind the hub's run
+    assert region_round_numpy(case, lab)[1] == {}
+    return case
+
+
+def region_hub_cases():
+    out = {}
+    for nc in REGION_HUB_NC:
+        winners = [w for w in (0, 63, 64, nc - 1) if w < nc] + ([None] if nc == 65 else [])
+        for w in dict.fromkeys(winners):
+            for place in ("aligned", "unaligned") + (("aligned_last",) if nc in (64, 128) and w == nc - 1 else ()):
+                out["hub%d_w%s_%s" % (nc, "none" if w is None else w, place)] = (lambda nc=nc, w=w, place=place: region_hub(nc, w, place))
+    return out
+
+
+REGION_LARGE_FACES = 700
+
+
+@functools.lru_cache(maxsize=None)
+def region_large(variant):
+    """Three regions A, B, C of 700 faces each, every one a path, their ids interleaved (node i belongs to region i % 3): every wave of 64
+    nodes holds faces of all three, and A's faces spread over nine blocks of 256 nodes.  B and C have one-label columns (labels 3 and 4); A
+    (label 2 at 8/64) has 11 edges to B and 22 to C, label 3 at 9/64 (x faces at 10/64) and label 4 at 10/64 (y faces at 11/64): the gains
+    are 11 - (700 + x) / 64 = (4 - x) / 64 and 22 - (1400 + y) / 64 = (8 - y) / 64.
+      "moves":   x = 2, y = 7: gains 2/64 and 1/64 -- A takes label 3;
+      "zero":    x = 4, y = 8: both gains exactly 0 -- nothing moves, no round is counted;
+      "lacking": as "moves", but ONE face of A (number 699 of its path) has no label 3: A takes its second best, label 4, at 1/64.
+    Asserted with the model."""
+    n = REGION_LARGE_FACES; F = 3 * n
+    x, y = (4, 8) if variant == "zero" else (2, 7)
+    lists = [[] for _ in range(F)]; cols = [None] * F
+    for k in range(n):
+        cols[3 * k] = {2: 8, 3: 10 if k % 100 == 50 and k // 100 < x else 9, 4: 11 if k % 80 == 40 and k // 80 < y else 10}
+        cols[3 * k + 1] = {3: 5}; cols[3 * k + 2] = {4: 6}
+        if k: [_link(lists, 3 * k - 3 + r, 3 * k + r) for r in range(3)]
+    for k in range(11): _link(lists, 3 * (60 * k + 7), 3 * (61 * k + 3) + 1)
+    for k in range(22): _link(lists, 3 * (31 * k + 2), 3 * (29 * k + 11) + 2)
+    if variant == "lacking": del cols[3 * (n - 1)][3]
+    case = _case64(lists, cols)
+    start = argmin_labels(case)
+    assert np.all(start[0::3] == 2) and np.all(start[1::3] == 3) and np.all(start[2::3] == 4)
+    lab, moved, cnt = region_round_numpy(case, start)
+    assert cnt["max_region"] == n and cnt["regions"] == 3
+    assert moved == {"moves": {0: (3, 2 << 26)}, "zero": {}, "lacking": {0: (4, 1 << 26)}}[variant], moved
+    assert cnt["zero_gain"] == (2 if variant == "zero" else 0) and cnt["lacking"] == (3 if variant == "lacking" else 2)
+    assert region_round_numpy(case, lab)[1] == {}
+    return case
+
+
+@functools.lru_cache(maxsize=None)
+def region_chain():
+    """Ten one-face regions on a path 0 - 1 - .. - 9, face i labelled i + 1, with planted gains (64ths; a gain is 1 edge - the label's extra cost):
+      0 and 1 want each other's label at 40 each: equal positive gains, the smaller name moves (0 takes label 2), 1 does not;
+      3 (20, towards 4), 4 (30, towards 5), 5 (50, towards 4): 5 beats 4 and moves; 4 beats 3 without moving itself, and 3 still stays;
+      7 (10, towards 8), 8 and 9 (33 each, towards each other): 8 moves, 9 loses the tie, 7 loses to 8;
+      2 and 6 have one-label columns.
+    Round 2: the merged region {0, 1} takes label 3 at (32 - 9) + (0 - 64) + 64 = 23 -- face 1 alone had that candidate at a gain of
+    exactly 0, face 0 alone did not have it at all: a move that exists only after the merge -- and 3 takes label 5 at 20, its neighbour
+    {4, 5} having no candidate left.  Round 3 finds nothing: a solve with region_rounds = 8 stops by itself after two rounds.
+    Asserted with the model."""
+    lists = [[] for _ in range(10)]
+    for i in range(9): _link(lists, i, i + 1)
+    cols = [{1: 8, 2: 32, 3: 9}, {1: 24, 2: 0, 3: 64}, {3: 7}, {4: 4, 5: 48}, {5: 10, 6: 44}, {5: 16, 6: 2}, {7: 3}, {8: 0, 9: 54}, {9: 5, 10: 36}, {9: 38, 10: 7}]
+    case = _case64(lists, cols)
+    start = argmin_labels(case)
+    assert start.tolist() == list(range(1, 11))
+    rounds = region_rounds_numpy(case, start, 8)
+    assert [r[1] for r in rounds] == [{0: (2, 40 << 26), 5: (5, 50 << 26), 8: (10, 33 << 26)}, {0: (3, 23 << 26), 3: (5, 20 << 26)}]
+    assert rounds[0][2]["tied_edges"] == 4 and rounds[0][2]["zero_gain"] == 1
+    assert rounds[1][0].tolist() == [3, 3, 3, 5, 5, 5, 7, 8, 10, 10]
+    return case
+
+
+REGION_EDGE_KINDS = ("no_cut", "single", "empties", "twice", "label65535")
+REGION_TOP_VIEWS = 65535       # label 65535 = view 65534: the largest label the candidate key (region << 16 | label) holds
+
+
+@functools.lru_cache(maxsize=None)
+def region_edges(kind):
+    """The edges of the definition, one tiny instance each:
+      "no_cut":     a path of five faces with the same one-label column -- no cut edge, no round;
+      "single":     F = 1, no adjacency;
+      "empties":    two adjacent faces with EMPTY columns, one of them next to a region of two faces that takes its other neighbour's
+                    label: the empty faces are in no region, give no candidate, and keep label 0;
+      "twice":      a face whose only edge is listed twice, the neighbour's label a whole 64/64 dearer than its own: the edge counts
+                    twice in the gain, 2 edges - 1 = 1 -- listed once the gain were exactly 0 and nothing moved;
+      "label65535": n_views = 65535; the last node is a region of its own (its root is the largest there is) whose one candidate is
+                    label 65535 -- the largest key the candidate sort sees."""
+    nv = CRAFTED_VIEWS
+    if kind == "no_cut":
+        lists = [[] for _ in range(5)]
+        for i in range(4): _link(lists, i, i + 1)
+        cols = [{9: 8 + i} for i in range(5)]; want = [{}]
+    elif kind == "single":
+        lists = [[]]; cols = [{3: 8, 5: 8}]; want = [{}]
+    elif kind == "empties":
+        lists = [[] for _ in range(5)]
+        for a, b in ((0, 1), (1, 2), (2, 3), (3, 4)): _link(lists, a, b)      # 0, 1 empty; {2, 3} label 7; 4 label 9
+        cols = [{}, {}, {7: 8, 9: 20}, {7: 8, 9: 30}, {9: 1}]; want = [{2: (9, (64 - 12 - 22) << 26)}, {}]
+    elif kind == "twice":
+        lists = [[1, 1], [0, 0, 2], [1]]
+        cols = [{4: 0, 6: 64}, {6: 3}, {6: 5}]; want = [{0: (6, 64 << 26)}, {}]
+    else:
+        assert kind == "label65535"
+        nv = REGION_TOP_VIEWS
+        lists = [[] for _ in range(4)]
+        for a, b in ((0, 1), (1, 3), (2, 3)): _link(lists, a, b)
+        cols = [{65535: 9}, {65535: 2}, {1: 4}, {1: 50, 70: 6, 65535: 40}]; want = [{3: (65535, (64 - 34) << 26)}, {}]
+    case = _case64(lists, cols, nv)
+    lab = argmin_labels(case)
+    for w in want:
+        lab, moved, cnt = region_round_numpy(case, lab)
+        assert moved == w, (kind, moved)
+    if kind == "empties": assert lab.tolist() == [0, 0, 9, 9, 9]
+    if kind == "twice":
+        once = _case64([[1], [0, 2], [1]], cols)
+        assert region_round_numpy(once, argmin_labels(once))[1] == {} and region_round_numpy(once, argmin_labels(once))[2]["zero_gain"] == 1
+    return case
+
+
+def region_cases():
+    """name -> builder of every crafted region-move instance (tests/test_oracle.py and tests/test_gpu_mrf_regions.py walk the same list)"""
+    out = region_hub_cases()
+    for v in ("moves", "zero", "lacking"): out["large_" + v] = (lambda v=v: region_large(v))
+    out["chain"] = region_chain
+    for k in REGION_EDGE_KINDS: out["edges_" + k] = (lambda k=k: region_edges(k))
+    return out
