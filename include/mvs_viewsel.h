@@ -431,7 +431,22 @@ mvs_status mvs_ctx_get_subgraphs(mvs_ctx* ctx, uint32_t n_faces, const uint32_t*
                                  const uint32_t* labels, int labels_on_device, uint32_t n_labels, mvs_subgraphs* out,
                                  int out_on_device);
 
-/* Row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp) with tone mapping `none`, from the caller's labels
+/* Tone mapping (tex::Settings::tone_mapping, settings.h): the field `tone_mapping` of mvs_gsl_params, mvs_patch_params and mvs_atlas_params.
+ * MVS_TONE_NONE (the default of every *_default_params) is `texrecon -t none`; MVS_TONE_GAMMA is `-t gamma`: a view's pixel value is
+ * gamma_pow(byte / 255.0f, 2.2f) wherever rows f5, f6 and f10 read one -- the crop's fill (255, 0, 255) included
+ * (generate_texture_patches.cpp:126-132: everything global and local seam leveling see is linearised) -- and row f8 applies
+ * gamma_pow(v, 1.0f / 2.2f) to every channel value in front of float_to_byte (generate_texture_atlases.cpp:102-104).  Any other
+ * value: MVS_ERR_INVALID, the context stays usable.  gamma_pow is csrc/tone.h -- one text for host and device, the same bits on both
+ * (DESIGN.md section 4 "Tone mapping").
+ * mvs_gamma_correct: values[i] = gamma_pow(values[i], power) on n host floats, in place; needs no GPU.  mvs_ctx_gamma_correct: the same
+ * by a kernel on the context's stream, values on the host or on the device -- the same bits.  power must be finite and > 0
+ * (MVS_ERR_INVALID otherwise).  mvs_tone_table: the 256 values of a view's bytes under `mode`. */
+enum { MVS_TONE_NONE = 0, MVS_TONE_GAMMA = 1 };
+mvs_status mvs_gamma_correct(float* values, uint64_t n, float power);
+mvs_status mvs_ctx_gamma_correct(mvs_ctx* ctx, float* values, uint64_t n, float power, int on_device);
+mvs_status mvs_tone_table(uint32_t mode, float out[256]);
+
+/* Row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp), tone mapping as params->tone_mapping says, from the caller's labels
  * (0 = unseen, L = view L - 1) on the context's mesh and views; no data-cost pass is needed.  adj_ptr / adj: the face adjacency
  * of mvs_ctx_get_subgraphs.  The definition -- the vertex rows, the patches generate_texture_patches would make, the seam samples,
  * the normal equations and their Jacobi-preconditioned CG -- is DESIGN.md section 4 "Global seam leveling"; every output is the
@@ -447,7 +462,7 @@ typedef struct mvs_gsl_params {
     float tolerance;          /* CG tolerance (1e-4) */
     uint32_t max_iterations;  /* per channel (1000) */
     float lambda;             /* weight of the smoothness rows Gamma (0.1) */
-    uint32_t reserved;
+    uint32_t tone_mapping;    /* MVS_TONE_NONE (default) or MVS_TONE_GAMMA: the seam samples read linearised texels */
 } mvs_gsl_params;
 void mvs_gsl_default_params(mvs_gsl_params* p);
 typedef struct mvs_gsl_result {
@@ -481,7 +496,7 @@ mvs_status mvs_ctx_gsl_system(mvs_ctx* ctx, mvs_gsl_system* out);
 void mvs_gsl_system_free(mvs_gsl_system* s);
 
 /* Row f6: generate_texture_patches for the labelled faces (generate_texture_patches.cpp:78-138, :484-508) followed by
- * TexturePatch::adjust_colors (texture_patch.cpp:41-122) on every patch, tone mapping `none`: from the caller's labels and the
+ * TexturePatch::adjust_colors (texture_patch.cpp:41-122) on every patch, tone mapping as params->tone_mapping says: from the caller's labels and the
  * per-corner adjustments of row f5 (corner_adjust[9 f + 3 k + c]; NULL = zeros, upstream's branch without global seam leveling,
  * texrecon.cpp:173-184) to the packed patch images and masks.  The definition is DESIGN.md section 4 "Texture patches"; every
  * array is the same bits on any device and in every run.  The call stands alone: it needs the mesh and the views, no data-cost
@@ -497,7 +512,8 @@ void mvs_gsl_system_free(mvs_gsl_system* s);
  * call or its destruction), otherwise malloc'ed host copies (mvs_patch_set_free). */
 typedef struct mvs_patch_params {
     uint64_t max_pixels;      /* refuse a result of more pixels than this (0: no cap) */
-    uint64_t reserved;
+    uint32_t tone_mapping;    /* MVS_TONE_NONE (default) or MVS_TONE_GAMMA: the crop is linearised before adjust_colors */
+    uint32_t reserved;
 } mvs_patch_params;
 void mvs_patch_default_params(mvs_patch_params* p);
 typedef struct mvs_patch_set {
@@ -525,8 +541,8 @@ mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const 
                                    const mvs_patch_params* params, mvs_patch_set* out, int out_on_device, mvs_patch_stats* stats);
 void mvs_patch_set_free(mvs_patch_set* s);
 
-/* Row f7: tex::local_seam_leveling (local_seam_leveling.cpp:105-204) on a patch set as mvs_patch_set describes it, tone mapping
- * `none`, labelled faces only: seam-edge and seam-vertex colours (the mean over the patches that meet there) are written into every
+/* Row f7: tex::local_seam_leveling (local_seam_leveling.cpp:105-204) on a patch set as mvs_patch_set describes it (the tone mapping
+ * is not read: the row works on the patch images it is given), labelled faces only: seam-edge and seam-vertex colours (the mean over the patches that meet there) are written into every
  * patch, prepare_blending_mask(strip_width) fixes everything but a strip along the patch border, and the strip is re-solved as a
  * Poisson problem that keeps the original image's Laplacian (poisson_blend with alpha 1); pixels of mask 64 lose their validity.
  * The definition is DESIGN.md section 4 "Local seam leveling"; upstream's direct solve is replaced by conjugate gradients per patch
@@ -572,7 +588,7 @@ void mvs_lsl_result_free(mvs_lsl_result* r);
 
 /* Row f8: tex::generate_texture_atlases (generate_texture_atlases.cpp:35-166, texture_atlas.cpp, rectangular_bin.cpp) on a patch set
  * as mvs_patch_set describes it (row f7's image and validity merged over row f6's set; `label` and `blending` are not read), tone
- * mapping `none`: the patches are ordered and packed into square atlases (256 .. 8192, padding = size >> 7), their pixels quantised
+ * mapping as params->tone_mapping says: the patches are ordered and packed into square atlases (256 .. 8192, padding = size >> 7), their pixels quantised
  * (float_to_byte_image) and copied with their validity, every atlas dilated by apply_edge_padding, the texture coordinates moved into
  * the atlas and merged.  The definition is DESIGN.md section 4 "Texture atlases"; every array is the same bits on any device and in
  * every run.  Needs neither mesh nor views; `patches` is all host arrays or all device pointers (patches_on_device) and is not
@@ -590,7 +606,8 @@ void mvs_lsl_result_free(mvs_lsl_result* r);
  * otherwise malloc'ed host copies (mvs_atlas_set_free). */
 typedef struct mvs_atlas_params {
     uint64_t max_pixels;      /* refuse a result of more atlas pixels than this (0: no cap) */
-    uint64_t reserved;
+    uint32_t tone_mapping;    /* MVS_TONE_NONE (default) or MVS_TONE_GAMMA: gamma_pow(v, 1.0f / 2.2f) in front of float_to_byte */
+    uint32_t reserved;
 } mvs_atlas_params;
 void mvs_atlas_default_params(mvs_atlas_params* p);
 typedef struct mvs_atlas_set {

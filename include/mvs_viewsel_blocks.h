@@ -41,6 +41,11 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
  * always): the other consumers of an ordered table belong to a resident mesh.  MVS_ERR_INVALID, with the context untouched, when
  * order_host is not a permutation of 0 .. n_faces - 1; MVS_ERR_STATE on a context whose face order a shard has pinned (mvs_shard_create). */
 mvs_status mvs_ctx_costs_upload_ordered(mvs_ctx* ctx, const mvs_csr* csr_in_position_order, const uint32_t* order_host);
+/* HARNESS ONLY (tests/test_gpu_tone_mapping.py): replaces the 256-entry texel table that tone_mapping = MVS_TONE_GAMMA reads in rows f5, f6
+ * and f10 (table256_host[b] = the value of byte b; the fill of the crop is entries 255, 0, 255) -- with a permuted byte / 255 table the
+ * gamma instantiations can be held to the CPU models of tone mapping `none` on permuted images: every texel read has to go through the
+ * table.  Null restores the gamma table (mvs_tone_table).  Row f8's correction is not affected. */
+mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256_host_or_null);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----
  * Every rank holds the FULL cost table and adjacency (288 GB of HBM make the

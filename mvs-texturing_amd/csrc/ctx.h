@@ -269,6 +269,7 @@ struct mvs_ctx {
     mvs::ModelDev* model = nullptr;   // row f9 (k_model.hip)
     mvs::DebugDev* debug = nullptr;   // row f10 (k_debug.hip)
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
+    mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
     mvs::DBuf<uint32_t> rg_parent, rg_root, rg_size, rg_bestl, rg_lose, rg_flag, rg_pos, rg_cstart, rg_have, rg_cfirst, rg_name;
@@ -413,6 +414,12 @@ struct PngFiles {
 };
 void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
                        PngFiles& out, mvs_png_stats& st);
+// k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
+// table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
+// (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)
+uint32_t tone_mode(uint32_t tone_mapping, const char* who);
+const float* tone_table_dev(mvs_ctx* ctx);
+void tone_table_set(mvs_ctx* ctx, const float* table256);
 // rows f5 / f6 (k_texpatch.hip): the views' parameters on the device and the checks on the caller's labels and faces -- throws MVS_ERR_LABELING
 // for a label above the number of views, MVS_ERR_INVALID for a vertex id >= n_verts; `who` starts the message
 void patch_check_inputs(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_labels, const char* who);

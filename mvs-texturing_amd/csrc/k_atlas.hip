@@ -1,5 +1,5 @@
 // k_atlas.hip -- row f8: tex::generate_texture_atlases (generate_texture_atlases.cpp:35-166, texture_atlas.cpp:19-253,
-//   rectangular_bin.cpp:19-70), tone mapping `none`.  The definition (DESIGN.md section 4 "Texture atlases") is shared with the CPU
+//   rectangular_bin.cpp:19-70), tone mapping `none` or `gamma` (compose is instantiated on the mode, tone.h).  The definition (DESIGN.md section 4 "Texture atlases") is shared with the CPU
 //   model of the tests (tests/tools/atlas_model.cpp): every output is bit-identical to it.  Phases (all but the first on the context's stream):
 //   pack      on the host, inside the call: upstream's loops over vectors (a one-workgroup device packer was built and measured slower than
 //             one host thread at config 3: profiles/EXPERIMENTS.md "Row f8: the packer", profiles/atlas_c3_device_packer.json, the kernel in
@@ -10,6 +10,7 @@
 //   texcoords one thread per list entry writes faces and coordinates; two stable radix sorts ((atlas, x) over y) group equal
 //             coordinates with their first occurrence in front; heads ranked by first index give upstream's ids.
 #include "rows.h"
+#include "tone.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -121,6 +122,7 @@ __device__ inline uint8_t float_to_byte(float x) {   // DEFINED HERE: mve::image
     return (uint8_t)(v + 0.5f);
 }
 
+template <int TONE>   // TONE_GAMMA: gamma_correct(image, 1.0f / 2.2f) of generate_texture_atlases.cpp:102-104 in front of the quantisation
 __global__ void __launch_bounds__(256) at_compose_kernel(Placement T, const uint32_t* __restrict__ chunk_ptr, const uint32_t* __restrict__ chunk_patch,
                                                          const float* __restrict__ image, const uint8_t* __restrict__ validity, uint8_t* __restrict__ out,
                                                          uint8_t* __restrict__ mask, uint8_t* __restrict__ lev, unsigned long long* __restrict__ c64) {
@@ -135,7 +137,10 @@ __global__ void __launch_bounds__(256) at_compose_kernel(Placement T, const uint
         const uint32_t sy = i / (uint32_t)wh.x, sx = i - sy * (uint32_t)wh.x;
         const unsigned long long s = src0 + i;
         const unsigned long long d = dst0 + (unsigned long long)(pl.y + (int)sy) * (unsigned long long)pl.z + (unsigned long long)(pl.x + (int)sx);
-        for (int c = 0; c < 3; ++c) out[3ull * d + c] = float_to_byte(image[3ull * s + c]);
+        for (int c = 0; c < 3; ++c) {
+            if (TONE == TONE_GAMMA) out[3ull * d + c] = float_to_byte(gamma_pow(image[3ull * s + c], TONE_INV_POWER));
+            else out[3ull * d + c] = float_to_byte(image[3ull * s + c]);
+        }
         const uint8_t v = validity[s];
         mask[d] = v;
         if (v == 255) { lev[d] = 0; ++valid; }
@@ -331,7 +336,8 @@ void run_atlas(mvs_ctx* ctx, AtlasDev& D, const Input& in, const int4* hb, const
     }
     if (NC) {
         Placement T{D.place.p, D.abase.p, D.ppix.p, D.wh.p};
-        hipLaunchKernelGGL(at_compose_kernel, dim3(NC), dim3(256), 0, s, T, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.chunk_patch.p, in.image, in.validity,
+        auto* compose = P.tone_mapping == TONE_GAMMA ? at_compose_kernel<TONE_GAMMA> : at_compose_kernel<TONE_NONE>;
+        hipLaunchKernelGGL(compose, dim3(NC), dim3(256), 0, s, T, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.chunk_patch.p, in.image, in.validity,
                            D.image.p, D.mask.p, D.lev.p, D.c64.p);
         MVS_LAUNCH_CHECK();
     }
@@ -397,7 +403,7 @@ extern "C" {
 
 void mvs_atlas_default_params(mvs_atlas_params* p) {
     if (!p) return;
-    p->max_pixels = 0; p->reserved = 0;
+    p->max_pixels = 0; p->tone_mapping = MVS_TONE_NONE; p->reserved = 0;
 }
 
 mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, int patches_on_device, const mvs_atlas_params* params, mvs_atlas_set* out,
@@ -413,6 +419,7 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
         AtlasDev& D = *ctx->atlas;
         mvs_atlas_params P;
         if (params) P = *params; else mvs_atlas_default_params(&P);
+        tone_mode(P.tone_mapping, "texture_atlases");
         const mvs_patch_set& in = *patches;
         const uint32_t NP = in.n_patches, L = in.n_listed;
         const uint64_t NPIX = in.n_pixels;

@@ -4,9 +4,12 @@
 //   debug_views_kernel materialises n images packed back to back (a pure store stream: 16 bytes per thread, one 16-byte store);
 //   debug_patch_kernel writes the patch pixels of the debug path straight from the rule -- the debug images never exist -- on the
 //   patch geometry and chunk tables of row f6 (texpatch_geometry, the same device functions): four pixels per thread, 48 bytes of
-//   image as three 16-byte stores, validity 255 and blending 0 as TexturePatch's constructor leaves them.
+//   image as three 16-byte stores, validity 255 and blending 0 as TexturePatch's constructor leaves them.  Instantiated on the tone
+//   mapping: under `gamma` the bytes of the rule (and the crop's fill) go through the context's texel table (tone.h), and row f8's
+//   correction brings every one of them back to its byte -- the files do not depend on the mode.
 #include "rows.h"
 #include "debug_embed.h"
+#include "tone.h"
 
 namespace mvs {
 
@@ -97,7 +100,8 @@ __global__ void __launch_bounds__(256) debug_views_kernel(uint8_t* __restrict__ 
 // by their GLOBAL index, so that a group's 48 bytes of image and 4 + 4 mask bytes are aligned; thread g of the block owns the g-th
 // group that overlaps the chunk (a chunk that does not start on a group boundary has a 257th, thread 0's), clipped to the chunk.  A
 // whole group is three 16-byte stores and two 4-byte ones, a clipped one goes element by element.
-__global__ void __launch_bounds__(256) debug_patch_kernel(uint32_t P, const uint32_t* __restrict__ chunk_ptr, const uint32_t* __restrict__ label,
+template <int TONE>
+__global__ void __launch_bounds__(256) debug_patch_kernel(const float* __restrict__ tone, uint32_t P, const uint32_t* __restrict__ chunk_ptr, const uint32_t* __restrict__ label,
                                                           const int4* __restrict__ box, const unsigned long long* __restrict__ pix_ptr,
                                                           const DebugView* __restrict__ views, const uint32_t* __restrict__ style,
                                                           float* __restrict__ image, uint8_t* __restrict__ validity, uint8_t* __restrict__ blending) {
@@ -112,8 +116,15 @@ __global__ void __launch_bounds__(256) debug_patch_kernel(uint32_t P, const uint
     const DebugView vw = views[label[p] - 1];
     const uint32_t st = style[vw.colour];
     const uint64_t glyphs = debug_id_glyphs(vw.id);
-    const float bg[3] = {(float)(st & 255u) / 255.0f, (float)((st >> 8) & 255u) / 255.0f, (float)((st >> 16) & 255u) / 255.0f};
-    const float font = (float)(st >> 24) / 255.0f;
+    float bg[3], font, fill1, fill0;   // the four values of the view, and the crop's fill (255, 0, 255)
+    if (TONE == TONE_GAMMA) {
+        bg[0] = tone[st & 255u]; bg[1] = tone[(st >> 8) & 255u]; bg[2] = tone[(st >> 16) & 255u]; font = tone[st >> 24];
+        fill1 = tone[255]; fill0 = tone[0];
+    } else {
+        bg[0] = (float)(st & 255u) / 255.0f; bg[1] = (float)((st >> 8) & 255u) / 255.0f; bg[2] = (float)((st >> 16) & 255u) / 255.0f;
+        font = (float)(st >> 24) / 255.0f;
+        fill1 = 1.0f; fill0 = 0.0f;
+    }
     for (unsigned long long i0 = g_base + 4ull * threadIdx.x; i0 < i_end; i0 += 1024ull) {
         const unsigned long long a = i0 > i_begin ? i0 : i_begin, e = i0 + 4ull < i_end ? i0 + 4ull : i_end;
         const unsigned long long j = a - base;
@@ -127,9 +138,9 @@ __global__ void __launch_bounds__(256) debug_patch_kernel(uint32_t P, const uint
                 const int vx = b.x + x, vy = b.y + y;
                 const bool in_view = vx >= 0 && vy >= 0 && vx < vw.width && vy < vw.height;
                 const bool on = in_view && debug_pixel_glyphs(vx, vy, vw.width, vw.height, glyphs);
-                px[3 * q] = in_view ? (on ? font : bg[0]) : 1.0f;      // outside: the crop's fill (255, 0, 255)
-                px[3 * q + 1] = in_view ? (on ? font : bg[1]) : 0.0f;
-                px[3 * q + 2] = in_view ? (on ? font : bg[2]) : 1.0f;
+                px[3 * q] = in_view ? (on ? font : bg[0]) : fill1;      // outside: the crop's fill (255, 0, 255)
+                px[3 * q + 1] = in_view ? (on ? font : bg[1]) : fill0;
+                px[3 * q + 2] = in_view ? (on ? font : bg[2]) : fill1;
                 if (++x == b.z) { x = 0; ++y; }
             } else {
                 px[3 * q] = 0.0f; px[3 * q + 1] = 0.0f; px[3 * q + 2] = 0.0f;
@@ -246,6 +257,8 @@ mvs_status mvs_ctx_debug_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const ui
         DebugDev& G = debug_dev(ctx);
         mvs_patch_params P;
         if (params) P = *params; else mvs_patch_default_params(&P);
+        const uint32_t tone = tone_mode(P.tone_mapping, "debug_patches");
+        const float* d_tone = tone == TONE_GAMMA ? tone_table_dev(ctx) : nullptr;
         const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device);
         upload(G.views, hv, s);
         MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only
@@ -256,7 +269,8 @@ mvs_status mvs_ctx_debug_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const ui
             texpatch_geometry(ctx, D, g.adj_ptr, g.adj, g.labels, P, S, n_listed, n_pixels, &n_chunks, tm, "debug_patches");
             MVS_HIP(hipStreamSynchronize(s));   // n_chunks
             if (n_chunks) {
-                hipLaunchKernelGGL(debug_patch_kernel, dim3(n_chunks), dim3(256), 0, s, D.pt.n_patches, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.label.p,
+                auto* pixels = tone == TONE_GAMMA ? debug_patch_kernel<TONE_GAMMA> : debug_patch_kernel<TONE_NONE>;
+                hipLaunchKernelGGL(pixels, dim3(n_chunks), dim3(256), 0, s, d_tone, D.pt.n_patches, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.label.p,
                                    (const int4*)D.box.p, (const unsigned long long*)D.pix_ptr.p, (const DebugView*)G.views.p, (const uint32_t*)G.style.p,
                                    D.image.p, D.validity.p, D.blending.p);
                 MVS_LAUNCH_CHECK();

@@ -1,5 +1,5 @@
 // k_localseam.hip -- row f7: tex::local_seam_leveling (local_seam_leveling.cpp:20-204, seam_leveling.cpp:16-91,
-//   texture_patch.cpp:118-297, poisson_blending.cpp:21-138), tone mapping `none`, labelled faces only.  The definition (DESIGN.md
+//   texture_patch.cpp:118-297, poisson_blending.cpp:21-138), labelled faces only; the tone mapping is not read here -- the row works on the patch images it is given.  The definition (DESIGN.md
 //   section 4 "Local seam leveling") is shared with the CPU model of the tests (tests/tools/blend_model.cpp): every output is
 //   bit-identical to it.  Phases, all on the context's stream:
 //   topology  sorted (vertex, 3 * list entry + corner) keys give every vertex's infos (patches ascending, first entry first); one

@@ -1,4 +1,5 @@
-// k_seam.hip -- row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp) with tone mapping `none`, together with the
+// k_seam.hip -- row f5: tex::global_seam_leveling (libs/tex/global_seam_leveling.cpp), tone mapping `none` or `gamma` (the b sampler is
+//   instantiated on the mode: under gamma a texel is the context's table at its byte, tone.h), together with the
 //   parts of generate_texture_patches it reads (candidate boxes and merges, generate_texture_patches.cpp:78-138 / :484-508 -- the
 //   tables of build_patch_tables, k_texpatch.hip, which row f6 builds with the same functions; the vertex projections
 //   merge_vertex_projection_infos keeps, :40-65).  The definition (DESIGN.md section 4 "Global seam leveling", items
@@ -11,6 +12,7 @@
 //   replayed as a linear captured graph of GSL_GRAPH_ITERS iterations; a device word says when every channel has stopped.
 //   Reductions follow the fixed two-level tree of item 8 (grid from x_rows only), so the bits do not depend on the device.
 #include "rows.h"
+#include "tone.h"
 #include <cfloat>
 #include <climits>
 
@@ -53,6 +55,7 @@ struct GslView {
     const uint32_t* vf_ptr; const uint32_t* vf; const uint32_t* x_ptr; const uint32_t* x_label; const uint32_t* ring_ptr; const uint32_t* ring;
     const int4* box; const float2* pc; const uint32_t* fcand; const uint32_t* parent; const uint32_t* fpid; const uint32_t* fpos;
     const ViewParams* views;
+    const float* tone;   // the 256 texel values of tone mapping `gamma` (null under `none`)
 };
 
 // ---- 1. (vertex, value) pairs -> CSR (the checks on labels and faces: patch_check_inputs, k_texpatch.hip) ----
@@ -138,12 +141,18 @@ __device__ float2 vproj(const GslView& g, uint32_t v, uint32_t P) {
     }
     return make_float2(x, y);
 }
-__device__ inline float texel(const ViewParams& vw, int x, int y, int ch) {
+template <int TONE>
+__device__ inline float texel(const ViewParams& vw, const float* __restrict__ tone, int x, int y, int ch) {
+    if (TONE == TONE_GAMMA) {   // the crop in bytes, fill included, through the table (generate_texture_patches.cpp:126-132)
+        if (x < 0 || y < 0 || x >= vw.width || y >= vw.height) return tone[ch == 1 ? 0 : 255];
+        return tone[vw.rgb[((size_t)y * vw.width + x) * 3 + ch]];
+    }
     if (x < 0 || y < 0 || x >= vw.width || y >= vw.height) return ch == 1 ? 0.0f : 1.0f;   // the crop's fill (255, 0, 255)
     return (float)vw.rgb[((size_t)y * vw.width + x) * 3 + ch] / 255.0f;
 }
 // sample_edge (global_seam_leveling.cpp:26-44) on the patch with frame bx of view vw; bilinear as item 6
-__device__ void sample_edge(const ViewParams& vw, int4 bx, float2 p1, float2 p2, float* out, unsigned long long& ns) {
+template <int TONE>
+__device__ void sample_edge(const ViewParams& vw, const float* __restrict__ tone, int4 bx, float2 p1, float2 p2, float* out, unsigned long long& ns) {
     const int pw = bx.z - bx.x + 2, ph = bx.w - bx.y + 2;
     const float W1 = (float)(pw - 1), H1 = (float)(ph - 1);
     const float dx = p2.x - p1.x, dy = p2.y - p1.y;
@@ -160,8 +169,8 @@ __device__ void sample_edge(const ViewParams& vw, int4 bx, float2 p1, float2 p2,
         const float w1 = x - (float)fx, w0 = 1.0f - w1, w3 = y - (float)fy, w2 = 1.0f - w3;
         const float w = 1.0f - fraction;
         for (int ch = 0; ch < 3; ++ch) {
-            const float v1 = texel(vw, fx + bx.x, fy + bx.y, ch), v2 = texel(vw, fx1 + bx.x, fy + bx.y, ch);
-            const float v3 = texel(vw, fx + bx.x, fy1 + bx.y, ch), v4 = texel(vw, fx1 + bx.x, fy1 + bx.y, ch);
+            const float v1 = texel<TONE>(vw, tone, fx + bx.x, fy + bx.y, ch), v2 = texel<TONE>(vw, tone, fx1 + bx.x, fy + bx.y, ch);
+            const float v3 = texel<TONE>(vw, tone, fx + bx.x, fy1 + bx.y, ch), v4 = texel<TONE>(vw, tone, fx1 + bx.x, fy1 + bx.y, ch);
             const float col = ((v1 * (w0 * w2) + v2 * (w1 * w2)) + v3 * (w0 * w3)) + v4 * (w1 * w3);
             acc[ch] = acc[ch] + col * w;
         }
@@ -193,6 +202,7 @@ __global__ void gsl_a_rows_kernel(GslView g, uint32_t NV, int fill, uint32_t* __
 }
 // b of one A row (calculate_difference, global_seam_leveling.cpp:76-138): seam-edge entries in ring order, per entry the edge's patches
 // of label l1 / l2 in ascending id, each sampled from p(v) to p(u) and accumulated with the edge's 3-D length
+template <int TONE>
 __global__ void gsl_b_kernel(GslView g, uint32_t AR, const uint32_t* __restrict__ a_col, const uint32_t* __restrict__ a_vert,
                              float* __restrict__ b, unsigned long long* __restrict__ c64) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -223,7 +233,7 @@ __global__ void gsl_b_kernel(GslView g, uint32_t AR, const uint32_t* __restrict_
                 uint32_t root = g.fcand[Pf];
                 while (g.parent[root] != NONE) root = g.parent[root];
                 float col[3];
-                sample_edge(g.views[PL - 1], g.box[root], vproj(g, v, P), vproj(g, u, P), col, ns);
+                sample_edge<TONE>(g.views[PL - 1], g.tone, g.box[root], vproj(g, v, P), vproj(g, u, P), col, ns);
                 if (PL == l1) { for (int ch = 0; ch < 3; ++ch) c1[ch] = c1[ch] + col[ch] * len; w1 = w1 + len; }
                 else { for (int ch = 0; ch < 3; ++ch) c2[ch] = c2[ch] + col[ch] * len; w2 = w2 + len; }
             }
@@ -531,6 +541,7 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     hipStream_t s = ctx->stream;
     const uint32_t F = ctx->n_faces, NV = ctx->n_verts;
     G.valid = false;
+    const uint32_t tone = tone_mode(P.tone_mapping, "global_seam_leveling");
     StageTimer<6> tm(s);   // marks: begin, rows, patches, system, solve, output
     tm.mark();
     G.flags.ensure(F_N); G.c64.ensure(C_N);
@@ -554,7 +565,7 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     tm.mark();
     // 4.-7. A rows, b, Lhs, Rhs
     const GslView gv{ctx->d_verts, ctx->d_faces, d_labels, G.vf_ptr.p, G.vf.p, G.x_ptr.p, G.x_label.p, G.ring_ptr.p, G.ring.p,
-                     T.box.p, T.pc.p, T.fcand.p, T.parent.p, T.fpid.p, T.fpos.p, T.views.p};
+                     T.box.p, T.pc.p, T.fcand.p, T.parent.p, T.fpid.p, T.fpos.p, T.views.p, tone == TONE_GAMMA ? tone_table_dev(ctx) : nullptr};
     G.cnt.ensure((size_t)std::max(NV, XR) + 1); G.a_ptr.ensure((size_t)NV + 2);
     hipLaunchKernelGGL(gsl_a_rows_kernel, dim3(grid(NV)), dim3(256), 0, s, gv, NV, 0, G.cnt.p, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
     MVS_LAUNCH_CHECK();
@@ -563,7 +574,9 @@ void run_gsl(mvs_ctx* ctx, GslDev& G, const uint32_t* d_adj_ptr, const uint32_t*
     G.a_col.ensure(2 * (size_t)AR + 2); G.a_vert.ensure((size_t)AR + 1); G.b.ensure(3 * (size_t)AR + 3);
     hipLaunchKernelGGL(gsl_a_rows_kernel, dim3(grid(NV)), dim3(256), 0, s, gv, NV, 1, (uint32_t*)nullptr, (const uint32_t*)G.a_ptr.p, G.a_col.p, G.a_vert.p);
     MVS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gsl_b_kernel, dim3(grid(AR)), dim3(256), 0, s, gv, AR, G.a_col.p, G.a_vert.p, G.b.p, G.c64.p); MVS_LAUNCH_CHECK();
+    if (tone == TONE_GAMMA) hipLaunchKernelGGL(gsl_b_kernel<TONE_GAMMA>, dim3(grid(AR)), dim3(256), 0, s, gv, AR, G.a_col.p, G.a_vert.p, G.b.p, G.c64.p);
+    else hipLaunchKernelGGL(gsl_b_kernel<TONE_NONE>, dim3(grid(AR)), dim3(256), 0, s, gv, AR, G.a_col.p, G.a_vert.p, G.b.p, G.c64.p);
+    MVS_LAUNCH_CHECK();
     G.lhs_ptr.ensure((size_t)XR + 2);
     hipLaunchKernelGGL(gsl_lhs_count_kernel, dim3(grid(XR)), dim3(256), 0, s, gv, XR, G.x_vert.p, G.a_ptr.p, G.a_col.p, G.cnt.p, G.c64.p); MVS_LAUNCH_CHECK();
     exclusive_scan_u32(ctx, G.cnt.p, G.lhs_ptr.p, XR, G.lhs_ptr.p + XR);
@@ -639,7 +652,7 @@ extern "C" {
 
 void mvs_gsl_default_params(mvs_gsl_params* p) {
     if (!p) return;
-    p->tolerance = 1e-4f; p->max_iterations = 1000; p->lambda = 0.1f; p->reserved = 0;
+    p->tolerance = 1e-4f; p->max_iterations = 1000; p->lambda = 0.1f; p->tone_mapping = MVS_TONE_NONE;
 }
 
 mvs_status mvs_ctx_global_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const uint32_t* labels,

@@ -1,5 +1,6 @@
 // k_texpatch.hip -- row f6: generate_texture_patches for the labelled faces (generate_texture_patches.cpp:78-138, :484-508) and
-//   TexturePatch::adjust_colors (texture_patch.cpp:41-122), tone mapping `none`.  The definition (DESIGN.md section 4 "Texture
+//   TexturePatch::adjust_colors (texture_patch.cpp:41-122), tone mapping `none` or `gamma` (resolve is instantiated on the mode: under
+//   gamma the crop is the context's table at its bytes, tone.h, so adjust_colors works on linearised values).  The definition (DESIGN.md section 4 "Texture
 //   patches") is shared with the CPU model of the tests (tests/tools/patch_model.cpp): every output is bit-identical to it.
 //   The first half of the file builds the tables rows f5 and f6 share (candidates, boxes, the merge, patch ids: build_patch_tables).
 //   Row f6 then runs: one thread per candidate (label, frame, sizes), three scans (face_ptr, the 64-bit pix_ptr, chunk_ptr), one
@@ -8,6 +9,7 @@
 //   same bits) and resolve (one thread per pixel in chunks of one patch: the winner's barycentrics again with the identical
 //   expression, crop + adjustment, the two masks).  No float atomics anywhere.
 #include "rows.h"
+#include "tone.h"
 #include <cfloat>
 #include <climits>
 
@@ -264,7 +266,8 @@ __global__ void __launch_bounds__(256) tp_mark_big_kernel(const uint32_t* __rest
     }
 }
 // one block per chunk of CHUNK pixels of one patch: the winner of every pixel, its adjustment, crop + adjustment, the masks
-__global__ void __launch_bounds__(256) tp_resolve_kernel(uint32_t P, const uint32_t* __restrict__ chunk_ptr, const uint32_t* __restrict__ label,
+template <int TONE>
+__global__ void __launch_bounds__(256) tp_resolve_kernel(const float* __restrict__ tone, uint32_t P, const uint32_t* __restrict__ chunk_ptr, const uint32_t* __restrict__ label,
                                                          const int4* __restrict__ box, const uint32_t* __restrict__ face_ptr,
                                                          const uint32_t* __restrict__ faces, const float* __restrict__ texcoords,
                                                          const unsigned long long* __restrict__ pix_ptr, const ViewParams* __restrict__ views,
@@ -305,7 +308,9 @@ __global__ void __launch_bounds__(256) tp_resolve_kernel(uint32_t P, const uint3
         for (int c = 0; c < 3; ++c) {
             const float v1 = av ? av[c] : 0.0f, v2 = av ? av[3 + c] : 0.0f, v3 = av ? av[6 + c] : 0.0f;
             const float adj = (v1 * w1 + v2 * w2) + v3 * w3;                                  // math::interpolate
-            const float crop = in_view ? (float)px[c] / 255.0f : (c == 1 ? 0.0f : 1.0f);      // the crop's fill (255, 0, 255)
+            float crop;
+            if (TONE == TONE_GAMMA) crop = tone[in_view ? px[c] : (c == 1 ? 0 : 255)];         // bytes, fill included, through the table
+            else crop = in_view ? (float)px[c] / 255.0f : (c == 1 ? 0.0f : 1.0f);              // the crop's fill (255, 0, 255)
             image[3 * i + c] = crop + adj;
         }
         validity[i] = 255; blending[i] = wi ? 255 : 64;
@@ -394,6 +399,8 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
     hipStream_t s = ctx->stream;
     StageTimer<5> tm(s);   // marks: begin, tables, lists, mark, resolve
     uint32_t n_chunks = 0;
+    const uint32_t tone = tone_mode(P.tone_mapping, "texture_patches");
+    const float* d_tone = tone == TONE_GAMMA ? tone_table_dev(ctx) : nullptr;
     texpatch_geometry(ctx, D, d_adj_ptr, d_adj, d_labels, P, S, n_listed, n_pixels, &n_chunks, tm, "texture_patches");
     PatchTables& T = D.pt;
     const uint32_t NP = T.n_patches, listed = n_listed;
@@ -415,7 +422,8 @@ void run_texpatch(mvs_ctx* ctx, TexPatchDev& D, const uint32_t* d_adj_ptr, const
     // resolve
     MVS_HIP(hipStreamSynchronize(s));   // n_chunks
     if (n_chunks) {
-        hipLaunchKernelGGL(tp_resolve_kernel, dim3(n_chunks), dim3(256), 0, s, NP, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.label.p,
+        auto* resolve = tone == TONE_GAMMA ? tp_resolve_kernel<TONE_GAMMA> : tp_resolve_kernel<TONE_NONE>;
+        hipLaunchKernelGGL(resolve, dim3(n_chunks), dim3(256), 0, s, d_tone, NP, (const uint32_t*)D.chunk_ptr.p, (const uint32_t*)D.label.p,
                            (const int4*)D.box.p, (const uint32_t*)D.face_ptr.p, (const uint32_t*)D.faces.p, (const float*)D.texcoords.p,
                            (const unsigned long long*)D.pix_ptr.p, (const ViewParams*)T.views.p, d_adjust, (const uint32_t*)D.win_in.p,
                            (const uint32_t*)D.win_near.p, D.image.p, D.validity.p, D.blending.p, D.c64.p);
@@ -439,7 +447,7 @@ extern "C" {
 
 void mvs_patch_default_params(mvs_patch_params* p) {
     if (!p) return;
-    p->max_pixels = 0; p->reserved = 0;
+    p->max_pixels = 0; p->tone_mapping = MVS_TONE_NONE; p->reserved = 0;
 }
 
 mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const uint32_t* labels,

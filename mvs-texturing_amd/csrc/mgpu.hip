@@ -174,6 +174,14 @@ mvs_status mvs_ctx_costs_upload_ordered(mvs_ctx* ctx, const mvs_csr* csr, const 
     MVS_API_END
 }
 
+// harness only: the texel table tone mapping `gamma` reads in rows f5, f6 and f10 (k_tone.hip); null = the gamma table of tone.h again
+mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256) {
+    if (!ctx) return api_fail(MVS_ERR_INVALID, "null argument");
+    MVS_CTX_API_BEGIN
+    tone_table_set(ctx, table256);
+    MVS_API_END
+}
+
 mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");

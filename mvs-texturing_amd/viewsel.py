@@ -74,7 +74,7 @@ class Subgraphs(C.Structure):
 
 
 class GslParams(C.Structure):
-    _fields_ = [("tolerance", C.c_float), ("max_iterations", C.c_uint32), ("lam", C.c_float), ("reserved", C.c_uint32)]
+    _fields_ = [("tolerance", C.c_float), ("max_iterations", C.c_uint32), ("lam", C.c_float), ("tone_mapping", C.c_uint32)]
 
 
 class GslResult(C.Structure):
@@ -96,7 +96,7 @@ class GslSystem(C.Structure):
 
 
 class PatchParams(C.Structure):
-    _fields_ = [("max_pixels", C.c_uint64), ("reserved", C.c_uint64)]
+    _fields_ = [("max_pixels", C.c_uint64), ("tone_mapping", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class PatchSet(C.Structure):
@@ -132,7 +132,7 @@ class LslStats(C.Structure):
 
 
 class AtlasParams(C.Structure):
-    _fields_ = [("max_pixels", C.c_uint64), ("reserved", C.c_uint64)]
+    _fields_ = [("max_pixels", C.c_uint64), ("tone_mapping", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 ATLAS_ARRAYS = ("atlas_size", "atlas_pix_ptr", "image", "patch_atlas", "patch_pos", "patch_order", "face_ptr", "faces", "texcoords", "tc_ptr",
@@ -206,7 +206,9 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_costs_upload_ordered"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table"))
+
+TONE_MAPPINGS = {"none": 0, "gamma": 1}                                       # tex::ToneMapping (settings.h); the *_params.tone_mapping field
 
 
 _lib = None
@@ -266,6 +268,8 @@ def load_library():
         "mvs_ctx_mrf_setup_tables": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_ray_bits": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_costs_upload_ordered": [vp, C.POINTER(CCsr), vp],
+        "mvs_ctx_tone_table": [vp, vp],
+        "mvs_gamma_correct": [vp, u64, C.c_float], "mvs_ctx_gamma_correct": [vp, vp, u64, C.c_float, i32], "mvs_tone_table": [u32, vp],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
         "mvs_comm_unique_id": [vp], "mvs_comm_create_rccl": [i32, i32, i32, vp, C.POINTER(vp)], "mvs_comm_create_local": [i32, C.POINTER(vp)], "mvs_comm_create_local_devices": [i32, vp, C.POINTER(vp)],
@@ -924,6 +928,26 @@ class Context:
         _check(self.L, self.L.mvs_ctx_deflate_rle(self.h, p if n else None, n, dev, C.byref(out), C.byref(nb)))
         return _take_bytes(self.L, out, nb)
 
+    def gamma_correct(self, values, power):
+        """mvs_ctx_gamma_correct: the tone mapping route on its own (csrc/tone.h gamma_pow on every value, by a kernel) -- a float32
+        numpy array (returns a new one of the same shape) or a CUDA float32 tensor / DevArray (corrected IN PLACE and returned).  The
+        same bits as the host twin gamma_correct gives."""
+        if _is_torch(values) or isinstance(values, DevArray):
+            n = int(values.numel()) if _is_torch(values) else int(values.shape[0])
+            _check(self.L, self.L.mvs_ctx_gamma_correct(self.h, _ptr(values)[0] if n else None, n, float(power), 1))
+            return values
+        out = np.array(values, dtype=np.float32, order="C")
+        _check(self.L, self.L.mvs_ctx_gamma_correct(self.h, out.ctypes.data if out.size else None, out.size, float(power), 0))
+        return out
+
+    def set_tone_table(self, table=None):
+        """mvs_ctx_tone_table (building-blocks library; test harness only): replaces the 256 texel values tone_mapping = 1 reads in rows
+        f5, f6 and f10 on this context; None restores the gamma table (tone_table("gamma"))"""
+        if table is not None:
+            table = np.ascontiguousarray(table, np.float32)
+            assert table.shape == (256,)
+        _check(self.L, self.L.mvs_ctx_tone_table(self.h, None if table is None else table.ctypes.data))
+
     def gsl_system(self):
         """host copies of the last global_seam_leveling's system: lower-triangle Lhs CSR (lhs_ptr, lhs_col, lhs_val), rhs (x_rows, 3),
         a_col (a_rows, 2), b (a_rows, 3), x_raw (x_rows, 3) = x before the mean"""
@@ -943,13 +967,48 @@ def _grab(ptr, n, ctype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), (n,)).copy()
 
 
+def _tone(tone_mapping):
+    """the value of the *_params.tone_mapping field: "none" | "gamma" or the number itself"""
+    return TONE_MAPPINGS[tone_mapping] if isinstance(tone_mapping, str) else int(tone_mapping)
+
+
+def _toned(params, default_fn, tone_mapping):
+    """the parameters of one row for a module-level call: the library's defaults, or a copy of the caller's, in the mode `tone_mapping`
+    ("none" leaves the caller's own field as it is)"""
+    t = _tone(tone_mapping)
+    if params is None:
+        return default_fn(tone_mapping=t)
+    p = type(params).from_buffer_copy(params)
+    if t:
+        p.tone_mapping = t
+    return p
+
+
+def gamma_correct(values, power):
+    """mvs_gamma_correct: csrc/tone.h gamma_pow(value, power) on every value of a float32 array, on the host (DEFINED HERE for
+    mve::image::gamma_correct; DESIGN.md section 4 "Tone mapping"); needs no GPU.  Returns a new array of the same shape."""
+    L = load_library()
+    out = np.array(values, dtype=np.float32, order="C")
+    _check(L, L.mvs_gamma_correct(out.ctypes.data if out.size else None, out.size, float(power)))
+    return out
+
+
+def tone_table(mode):
+    """mvs_tone_table: float32[256], the value of every byte of a view's image under tone mapping "none" (byte / 255) or "gamma"
+    (gamma_pow(byte / 255, 2.2f))"""
+    L = load_library()
+    out = np.zeros(256, np.float32)
+    _check(L, L.mvs_tone_table(_tone(mode), out.ctypes.data))
+    return out
+
+
 def default_gsl_params(**kw):
-    """mvs_gsl_default_params (tolerance 1e-4, max_iterations 1000, lam 0.1) with overrides"""
+    """mvs_gsl_default_params (tolerance 1e-4, max_iterations 1000, lam 0.1, tone_mapping 0 = none) with overrides"""
     return _default_params(GslParams, "mvs_gsl_default_params", kw)
 
 
 def default_patch_params(**kw):
-    """mvs_patch_default_params (max_pixels 0 = no cap) with overrides"""
+    """mvs_patch_default_params (max_pixels 0 = no cap, tone_mapping 0 = none) with overrides"""
     return _default_params(PatchParams, "mvs_patch_default_params", kw)
 
 
@@ -959,7 +1018,7 @@ def default_lsl_params(**kw):
 
 
 def default_atlas_params(**kw):
-    """mvs_atlas_default_params (max_pixels 0 = no cap) with overrides"""
+    """mvs_atlas_default_params (max_pixels 0 = no cap, tone_mapping 0 = none) with overrides"""
     return _default_params(AtlasParams, "mvs_atlas_default_params", kw)
 
 
@@ -1081,41 +1140,48 @@ def _scene_context(scene, ctx):
             ctx.close()
 
 
-def texture_patches(scene, labels, corner_adjust=None, ctx=None):
+def texture_patches(scene, labels, corner_adjust=None, ctx=None, tone_mapping="none"):
     """the texture patches (generate_texture_patches for the labelled faces + adjust_colors, texrecon.cpp:160-184) of a synth.Scene-like
-    object and its labels: returns (arrays, stats) of Context.texture_patches."""
+    object and its labels: returns (arrays, stats) of Context.texture_patches.  tone_mapping: "none" | "gamma"."""
     with _scene_context(scene, ctx) as c:
         return c.texture_patches(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
-                                 np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust)
+                                 np.ascontiguousarray(labels, dtype=np.uint32), corner_adjust, _toned(None, default_patch_params, tone_mapping))
 
 
-def local_seam_leveling(scene, labels, params=None, ctx=None):
+def local_seam_leveling(scene, labels, params=None, ctx=None, tone_mapping="none"):
     """texrecon.cpp:169-189 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with
     its adjustments (row f6) and local seam leveling (row f7), the patches staying on the device in between.  Returns (arrays, stats):
-    the patch set of Context.texture_patches with image, validity and blending replaced by row f7's, and row f7's stats."""
+    the patch set of Context.texture_patches with image, validity and blending replaced by row f7's, and row f7's stats.
+    tone_mapping: "none" | "gamma", passed to rows f5 and f6 (row f7 works on the patch images it is given)."""
     with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
-        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
-        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
+        gp, pp = _toned(None, default_gsl_params, tone_mapping), _toned(None, default_patch_params, tone_mapping)
+        gsl, _ = c.global_seam_leveling(a, b, lab, gp, on_device=True)
+        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], pp, on_device=True)
         out, stats = c.local_seam_leveling(a, b, lab, dev, params)
-        host, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"])
+        host, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], pp)
         host.update(out)
         return host, stats
 
 
-def texture_atlases(scene, labels, params=None, ctx=None):
+def texture_atlases(scene, labels, params=None, ctx=None, tone_mapping="none"):
     """texrecon.cpp:169-195 for a synth.Scene-like object and its labels: global seam leveling (row f5), the texture patches with its
     adjustments (row f6), local seam leveling (row f7) and the texture atlases (row f8), the patches staying on the device in
-    between.  Returns (arrays, stats) of Context.texture_atlases."""
+    between.  Returns (arrays, stats) of Context.texture_atlases.  tone_mapping: "none" | "gamma", passed to rows f5, f6 and f8."""
     with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
-        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
-        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
-        lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
-        dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
-        return c.texture_atlases(dev, params)
+        return c.texture_atlases(_leveled_patches(c, a, b, lab, tone_mapping), _toned(params, default_atlas_params, tone_mapping))
+
+
+def _leveled_patches(c, a, b, lab, tone_mapping):
+    """rows f5 to f7 in the mode `tone_mapping` on a context with its scene set: the device patch set row f8 reads"""
+    gsl, _ = c.global_seam_leveling(a, b, lab, _toned(None, default_gsl_params, tone_mapping), on_device=True)
+    dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], _toned(None, default_patch_params, tone_mapping), on_device=True)
+    lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
+    dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
+    return dev
 
 
 def debug_view_style(position):
@@ -1127,39 +1193,39 @@ def debug_view_style(position):
     return tuple(bg), tuple(fg)
 
 
-def view_selection_model(scene, labels, prefix, view_ids=None, vertex_normals=None, ctx=None):
+def view_selection_model(scene, labels, prefix, view_ids=None, vertex_normals=None, ctx=None, tone_mapping="none"):
     """texrecon.cpp:216-236 for a synth.Scene-like object and its labels: writes the debug model `<prefix>_view_selection.obj`, `.mtl` and
-    PNGs, whose faces carry the colour and the id of the view that textures them.  Returns Context.view_selection_model's stats."""
+    PNGs, whose faces carry the colour and the id of the view that textures them.  Returns Context.view_selection_model's stats.
+    tone_mapping: "none" | "gamma", passed to the patches and the atlases -- the files are the same bytes in either mode."""
     with _scene_context(scene, ctx) as c:
         return c.view_selection_model(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
-                                      np.ascontiguousarray(labels, dtype=np.uint32), prefix, view_ids, vertex_normals)
+                                      np.ascontiguousarray(labels, dtype=np.uint32), prefix, view_ids, vertex_normals,
+                                      _toned(None, default_patch_params, tone_mapping), _toned(None, default_atlas_params, tone_mapping))
 
 
-def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None, view_selection_model=False):
+def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None, view_selection_model=False, tone_mapping="none"):
     """texrecon.cpp:169-208 for a synth.Scene-like object and its labels: rows f5 to f8 as texture_atlases runs them, then the model
     output (row f9) with the atlases left on the device: writes `<prefix>.obj`, `<prefix>.mtl` and the atlas PNGs.  Returns row f9's
     stats.  vertex_normals: (n_verts, 3) or None (no `vn` lines; vertex_normals(verts, faces) computes area-weighted ones).
-    view_selection_model=True writes the debug model `<prefix>_view_selection.*` as well (Context.view_selection_model)."""
+    view_selection_model=True writes the debug model `<prefix>_view_selection.*` as well (Context.view_selection_model).
+    tone_mapping: "none" | "gamma", passed to every row that reads it (f5, f6, f8 and the debug model)."""
     with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
-        gsl, _ = c.global_seam_leveling(a, b, lab, on_device=True)
-        dev, _ = c.texture_patches(a, b, lab, gsl["corner_adjust"], on_device=True)
-        lsl, _ = c.local_seam_leveling(a, b, lab, dev, on_device=True)
-        dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
-        atlases, _ = c.texture_atlases(dev, on_device=True)
+        ap = _toned(None, default_atlas_params, tone_mapping)
+        atlases, _ = c.texture_atlases(_leveled_patches(c, a, b, lab, tone_mapping), ap, on_device=True)
         stats = c.save_model(atlases, prefix, vertex_normals, params)
         if view_selection_model:   # texrecon.cpp:216-236: after the textured model, on the same context
-            c.view_selection_model(a, b, lab, prefix, None, vertex_normals, model_params=params)
+            c.view_selection_model(a, b, lab, prefix, None, vertex_normals, _toned(None, default_patch_params, tone_mapping), ap, model_params=params)
         return stats
 
 
-def global_seam_leveling(scene, labels, params=None, ctx=None):
+def global_seam_leveling(scene, labels, params=None, ctx=None, tone_mapping="none"):
     """tex::global_seam_leveling for a synth.Scene-like object (verts, faces, normals, cams, images, adj_ptr, adj) and its labels
-    (texrecon.cpp:169-172): returns (arrays, stats) of Context.global_seam_leveling."""
+    (texrecon.cpp:169-172): returns (arrays, stats) of Context.global_seam_leveling.  tone_mapping: "none" | "gamma"."""
     with _scene_context(scene, ctx) as c:
         return c.global_seam_leveling(np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32), np.ascontiguousarray(scene.adj, dtype=np.uint32),
-                                      np.ascontiguousarray(labels, dtype=np.uint32), params)
+                                      np.ascontiguousarray(labels, dtype=np.uint32), _toned(params, default_gsl_params, tone_mapping))
 
 
 def _subgraphs_to_numpy(L, sg):

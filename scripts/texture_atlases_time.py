@@ -1,6 +1,6 @@
 """Row f8 (texture atlases) at a BASELINE config, with labels from the library's own view selection and the patches of its rows f5 - f7,
 which stay on the device:
-   texture_atlases_time.py --config 3 [--runs 3] [--out profiles/atlas_c3.json] [--no-model] [--lib other/libmvs_viewsel.so --packer device]
+   texture_atlases_time.py --config 3 [--runs 3] [--out profiles/atlas_c3.json] [--no-model] [--lib other/libmvs_viewsel.so --packer device] [--tone-mapping gamma]
 Records the time per phase (mvs_atlas_stats, median of the timed runs after one warm-up: ms_pack is HOST time -- ordering, packing, the
 per-patch tables and their uploads --, ms_compose / ms_pad / ms_texcoords are device time from events), the counters, the
 bytes the composition moves (12 B of colour and 1 B of validity read, 3 B of colour, 1 B of mask and at most 1 B of level written per
@@ -8,7 +8,9 @@ patch pixel, plus 5 B cleared per atlas pixel) and the rate that makes beside a 
 the single-thread time of the CPU model (tests/tools/atlas_model.cpp) -- its packing alone and the whole stage -- on the same input
 with a bit-for-bit comparison of every output array and every counter.  --lib runs another build of the library (the
 one-workgroup device packer of profiles/atlas_device_packer.patch: profiles/EXPERIMENTS.md "Row f8: the packer"); --packer names which packer
-that build has, for the record.  When profiles/atlas_c<config>_device_packer.json exists, its packing time is copied beside this run's."""
+that build has, for the record.  When profiles/atlas_c<config>_device_packer.json exists, its packing time is copied beside this run's.
+--tone-mapping gamma runs rows f5, f6 and f8 in that mode (the CPU model states `none` only: no comparison then; the default output becomes
+profiles/atlas_c<config>_gamma.json).  scripts/tone_mapping_time.py measures the two modes side by side."""
 import argparse
 import json
 import os
@@ -28,10 +30,14 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--no-model", action="store_true")
 ap.add_argument("--lib", default=None, help="another build of libmvs_viewsel.so (experiments)")
 ap.add_argument("--packer", default="host", choices=["host", "device"], help="the packer the library under test has (host: the committed code)")
+ap.add_argument("--tone-mapping", default="none", choices=["none", "gamma"])
 a = ap.parse_args()
+TONE = M.viewsel.TONE_MAPPINGS[a.tone_mapping]
+if TONE:
+    a.no_model = True
 if a.lib:
     M.viewsel._LIB_PATH = os.path.abspath(a.lib)
-out_path = a.out or os.path.join(ROOT, "profiles", "atlas_c%d.json" % a.config)
+out_path = a.out or os.path.join(ROOT, "profiles", "atlas_c%d%s.json" % (a.config, "_gamma" if TONE else ""))
 
 t0 = time.perf_counter()
 s = M.synth.make_scene(**M.synth.CONFIGS[a.config])
@@ -40,24 +46,25 @@ c.set_mesh(s.verts, s.faces, s.normals)
 c.set_views(s.cams, s.images)
 c.data_costs(M.Settings())
 labels, ms = c.view_selection(s.adj_ptr, s.adj)
-gsl, gst = c.global_seam_leveling(s.adj_ptr, s.adj, labels, on_device=True)
-dev, pst = c.texture_patches(s.adj_ptr, s.adj, labels, gsl["corner_adjust"], on_device=True)
+gsl, gst = c.global_seam_leveling(s.adj_ptr, s.adj, labels, M.default_gsl_params(tone_mapping=TONE), on_device=True)
+dev, pst = c.texture_patches(s.adj_ptr, s.adj, labels, gsl["corner_adjust"], M.default_patch_params(tone_mapping=TONE), on_device=True)
 lsl, lst = c.local_seam_leveling(s.adj_ptr, s.adj, labels, dev, on_device=True)
 dev = dict(dev); dev.update(image=lsl["image"], validity=lsl["validity"])
 print("scene + labels + rows f5 - f7: %.1f s, %d faces, %d views, %d patches, %d pixels" % (time.perf_counter() - t0, s.n_faces, s.n_views, pst["patches"], pst["pixels"]), flush=True)
 
-c.texture_atlases(dev, on_device=True)             # warm-up: buffers, code objects
+AP = M.default_atlas_params(tone_mapping=TONE)
+c.texture_atlases(dev, AP, on_device=True)         # warm-up: buffers, code objects
 runs = []
 for _ in range(a.runs):
     t = time.perf_counter()
-    got, st = c.texture_atlases(dev, on_device=True)
+    got, st = c.texture_atlases(dev, AP, on_device=True)
     st["wall_ms"] = 1e3 * (time.perf_counter() - t)
     runs.append(st)
 phases = ("ms_pack", "ms_compose", "ms_pad", "ms_texcoords", "ms_total", "wall_ms")
 med = {k: float(np.median([r[k] for r in runs])) for k in phases}
 last = runs[-1]
 compose_bytes = 17 * pst["pixels"] + 5 * last["pixels"]
-res = {"config": a.config, "workload": "BASELINE config %d: %s" % (a.config, M.synth.CONFIGS[a.config]), "faces": s.n_faces, "views": s.n_views,
+res = {"config": a.config, "tone_mapping": a.tone_mapping, "workload": "BASELINE config %d: %s" % (a.config, M.synth.CONFIGS[a.config]), "faces": s.n_faces, "views": s.n_views,
        "labels": "the library's view selection (sweeps %d)" % ms["sweeps"], "patches": pst["patches"], "patch_pixels": pst["pixels"],
        "listed_faces": pst["listed_faces"], "runs": a.runs, "ms_median": med, "ms_runs": [{k: r[k] for k in phases} for r in runs],
        **{k: last[k] for k in M.viewsel.ATLAS_COUNTS},

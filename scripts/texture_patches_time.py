@@ -1,11 +1,13 @@
 """Row f6 (texture patches + adjust_colors) at a BASELINE config, with labels from the library's own view selection and the
 adjustments of its own global seam leveling:
-   texture_patches_time.py --config 3 [--runs 3] [--out profiles/patches_c3.json] [--no-model] [--window 64]
+   texture_patches_time.py --config 3 [--runs 3] [--out profiles/patches_c3.json] [--no-model] [--window 64] [--tone-mapping gamma]
 Records pixels, the valid share, the device time per phase (mvs_patch_stats: median of the timed runs after one warm-up, device
 events), the bytes the two streaming phases must move and the bandwidth that implies beside a plain device-to-device copy of the same
 number of bytes on the same device (measured here with events), and the single-thread time of the CPU model
 (tests/tools/patch_model.cpp) on the same input with a bit-for-bit comparison.  The outputs stay on the device (out_on_device); with
---window N the comparison reads back only the first, the largest and N evenly spaced patches instead of a host copy of everything."""
+--window N the comparison reads back only the first, the largest and N evenly spaced patches instead of a host copy of everything.
+--tone-mapping gamma runs rows f5 and f6 in that mode (the CPU model states `none` only: no comparison then; the default output becomes
+profiles/patches_c<config>_gamma.json).  scripts/tone_mapping_time.py measures the two modes side by side."""
 import argparse
 import json
 import os
@@ -25,8 +27,12 @@ ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-model", action="store_true")
 ap.add_argument("--window", type=int, default=0, help="compare this many patches (plus the first and the largest) instead of all")
+ap.add_argument("--tone-mapping", default="none", choices=["none", "gamma"])
 a = ap.parse_args()
-out_path = a.out or os.path.join(ROOT, "profiles", "patches_c%d.json" % a.config)
+TONE = M.viewsel.TONE_MAPPINGS[a.tone_mapping]
+if TONE:
+    a.no_model = True
+out_path = a.out or os.path.join(ROOT, "profiles", "patches_c%d%s.json" % (a.config, "_gamma" if TONE else ""))
 
 
 def dev_bytes(dev, nbytes, offset=0):
@@ -59,23 +65,24 @@ c.set_mesh(s.verts, s.faces, s.normals)
 c.set_views(s.cams, s.images)
 c.data_costs(M.Settings())
 labels, ms = c.view_selection(s.adj_ptr, s.adj)
-gsl, gst = c.global_seam_leveling(s.adj_ptr, s.adj, labels)
+gsl, gst = c.global_seam_leveling(s.adj_ptr, s.adj, labels, M.default_gsl_params(tone_mapping=TONE))
 ca = gsl["corner_adjust"]
 print("scene + labels + seam leveling: %.1f s, %d faces, %d views, %d unseen" % (time.perf_counter() - t0, s.n_faces, s.n_views, int((labels == 0).sum())), flush=True)
 
 # the size first, without allocating the pixel arrays
 try:
-    c.texture_patches(s.adj_ptr, s.adj, labels, ca, params=M.default_patch_params(max_pixels=1), on_device=True)
+    c.texture_patches(s.adj_ptr, s.adj, labels, ca, params=M.default_patch_params(max_pixels=1, tone_mapping=TONE), on_device=True)
     sized = None
 except M.MvsError as e:
     sized = e.stats
 print("size:", json.dumps({k: sized[k] for k in ("patches", "merged", "listed_faces", "pixels")} if sized else None), flush=True)
 
-c.texture_patches(s.adj_ptr, s.adj, labels, ca, on_device=True)             # warm-up: buffers, code objects
+PP = M.default_patch_params(tone_mapping=TONE)
+c.texture_patches(s.adj_ptr, s.adj, labels, ca, PP, on_device=True)         # warm-up: buffers, code objects
 runs = []
 for _ in range(a.runs):
     t = time.perf_counter()
-    got, st = c.texture_patches(s.adj_ptr, s.adj, labels, ca, on_device=True)
+    got, st = c.texture_patches(s.adj_ptr, s.adj, labels, ca, PP, on_device=True)
     st["wall_ms"] = 1e3 * (time.perf_counter() - t)
     runs.append(st)
 phases = ("ms_tables", "ms_lists", "ms_mark", "ms_resolve", "ms_total", "wall_ms")
@@ -87,7 +94,7 @@ NP = last["pixels"]
 mark_clear_bytes = 8 * NP
 resolve_bytes = (8 + 3 + 12 + 2) * NP
 copy_resolve_gbs, copy_resolve_ms = copy_gbs(resolve_bytes)
-res = {"config": a.config, "workload": "BASELINE config %d: %s" % (a.config, M.synth.CONFIGS[a.config]), "faces": s.n_faces, "views": s.n_views,
+res = {"config": a.config, "tone_mapping": a.tone_mapping, "workload": "BASELINE config %d: %s" % (a.config, M.synth.CONFIGS[a.config]), "faces": s.n_faces, "views": s.n_views,
        "labels": "the library's view selection (sweeps %d)" % ms["sweeps"], "unseen_faces": int((labels == 0).sum()),
        "adjustments": "the library's global seam leveling (iterations %s)" % gst["iterations"],
        "runs": a.runs, "ms_median": med, "ms_runs": [{k: r[k] for k in phases} for r in runs],
