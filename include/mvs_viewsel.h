@@ -754,6 +754,41 @@ mvs_status mvs_ctx_view_selection_model(mvs_ctx* ctx, const uint32_t* adj_ptr, c
                                         const mvs_model_params* model_params, mvs_patch_stats* patch_stats, mvs_atlas_stats* atlas_stats,
                                         mvs_model_stats* model_stats);
 
+/* Row f11 (not in upstream; defined here): the textured model as ONE binary glTF 2.0 file (.glb) -- the same inputs as
+ * mvs_ctx_save_model, the definition is DESIGN.md section 4 "Model output" item 8, the buffers are built on the device (csrc/k_glb.hip)
+ * and every byte is the same on any device and in every run.  A glTF vertex carries one index for position and texture coordinate
+ * together, so the distinct pairs (global coordinate g, mesh vertex v) among the 3 n_listed corners are the vertices: they are numbered
+ * in ascending (g, v), which leaves every atlas one contiguous range, and atlas a with faces becomes one primitive (material a, its
+ * image the PNG that mvs_ctx_save_model writes for the same params, embedded) whose indices count from the start of its range.
+ * POSITION, TEXCOORD_0 (texcoords_merged as it is: its origin is glTF's) and NORMAL (when vertex_normals is given) are the inputs' bits,
+ * not rounded text.  Unlike the .obj the file holds only referenced vertices; faces of label 0 are in no atlas and so in no primitive.
+ * An atlas set without atlas_size or image gives a file without images, textures and samplers.
+ *   mvs_ctx_build_glb: the whole file in malloc'ed host memory (mvs_glb_free).  mvs_ctx_save_glb: the file at `path`, written once;
+ *   a refusal leaves `path` untouched (nothing is opened before the last check), a write error removes what was written.  Running out
+ *   of host memory is MVS_ERR_INVALID ("out of host memory"), as in every other row.
+ * Refusals: those of mvs_ctx_build_model (MVS_ERR_STATE without a mesh; MVS_ERR_INVALID for a bad face id, texcoord id, face_ptr or
+ * tc_ptr) and, for the PNGs, of mvs_ctx_save_model (png_level, png_device, libz); MVS_ERR_INVALID as well for a mesh face that names a
+ * vertex >= n_verts.  MVS_ERR_UNSUPPORTED for a position or normal of a referenced vertex that is not finite (JSON has no inf or nan;
+ * counted in stats.nonfinite_values per component of every glTF vertex) and for a file of 2^32 - 1 bytes or more or above
+ * params.max_bytes (0 = no cap): checked on headers + geometry after the numbering pass, before the attribute buffers are allocated,
+ * and on the whole file once the PNG sizes are known.  stats is filled either way (file_bytes: what was known at the refusal). */
+typedef struct mvs_glb {
+    uint64_t n_bytes;
+    uint8_t* data;                               /* [n_bytes] */
+} mvs_glb;
+typedef struct mvs_glb_stats {
+    uint64_t vertices, indices, primitives;      /* distinct (coordinate, vertex) pairs; 3 n_listed; atlases with faces */
+    uint64_t json_bytes, geometry_bytes, image_bytes, file_bytes;   /* the JSON chunk's data (padded); attributes + indices; the PNGs with their padding; all */
+    uint64_t nonfinite_values;                   /* inf / nan among the POSITION and NORMAL components of the glTF vertices */
+    float ms_keys, ms_sort, ms_number, ms_indices, ms_gather;      /* device time per phase */
+    float ms_png, ms_download, ms_file;          /* host time: the PNGs (copy, encode); geometry to the host; JSON and the file (or its assembly in memory) */
+} mvs_glb_stats;
+mvs_status mvs_ctx_build_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
+                             const mvs_model_params* params, mvs_glb* out, mvs_glb_stats* stats);
+mvs_status mvs_ctx_save_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
+                            const char* path, const mvs_model_params* params, mvs_glb_stats* stats);
+void mvs_glb_free(mvs_glb* g);
+
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
@@ -139,6 +140,7 @@ struct LslDev;   // row f7 (k_localseam.hip)
 struct AtlasDev; // row f8 (k_atlas.hip)
 struct ModelDev; // row f9 (k_model.hip)
 struct DebugDev; // row f10 (k_debug.hip)
+struct GlbDev;   // row f11 (k_glb.hip)
 struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
@@ -268,6 +270,7 @@ struct mvs_ctx {
     mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
     mvs::ModelDev* model = nullptr;   // row f9 (k_model.hip)
     mvs::DebugDev* debug = nullptr;   // row f10 (k_debug.hip)
+    mvs::GlbDev* glb = nullptr;       // row f11 (k_glb.hip)
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
@@ -400,6 +403,24 @@ void lsl_release(mvs_ctx* ctx);
 void atlas_release(mvs_ctx* ctx);
 // frees the buffers of row f9 (k_model.hip)
 void model_release(mvs_ctx* ctx);
+// k_model.hip, shared with row f11 (k_glb.hip); `who` starts every message:
+//   model_check_set: the host-side rules of "Model output" item 6 -- throws MVS_ERR_STATE without a mesh, MVS_ERR_INVALID for a null array or
+//     a face_ptr / tc_ptr that does not run from 0 to the totals or descends; leaves both arrays ([n_atlases + 1]) on the host
+//   model_refuse_bad_ids: MVS_ERR_INVALID for the counts the device pass made of model_corner.h's two id rules
+//   model_check_png_params: png_level / png_device and the arrays the PNGs need, as mvs_ctx_save_model refuses them
+//   model_for_each_png: the PNG file of every atlas by the route params chooses (png_io.h on up to 16 host threads, or k_png.hip), handed to
+//     `sink` (atlas, bytes, count, message) on the thread that holds it; the bytes are valid during the call only
+//   device_to_stream: a device range into an open file through the context's pinned buffer, 32 MB at a time (false: write error);
+//     ms_copy: the time spent waiting for the copies
+void model_check_set(mvs_ctx* ctx, const mvs_atlas_set& in, int on_device, const char* who, std::vector<uint32_t>& face_ptr, std::vector<uint32_t>& tc_ptr);
+void model_refuse_bad_ids(uint64_t bad_faces, uint64_t bad_ids, const char* who);
+void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who);
+typedef std::function<mvs_status(uint32_t, const uint8_t*, size_t, std::string&)> ModelPngSink;
+void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelPngSink& sink);
+bool device_to_stream(mvs_ctx* ctx, const char* d, uint64_t bytes, FILE* f, double& ms_copy);
+std::string model_filled4(uint32_t a);   // util::string::get_filled(a, 4)
+// frees the buffers of row f11 (k_glb.hip)
+void glb_release(mvs_ctx* ctx);
 // frees the buffers of row f10 (k_debug.hip)
 void debug_release(mvs_ctx* ctx);
 // k_png.hip: frees its buffers; the PNG files of n images encoded on the device (mvs_ctx_encode_pngs after its checks: width, height [n] and

@@ -11,6 +11,7 @@
 #include "rows.h"
 #include "fmt6.h"
 #include "png_io.h"
+#include "model_corner.h"
 
 #include <atomic>
 #include <chrono>
@@ -82,14 +83,14 @@ struct ObjSource {
         const uint32_t a = group_of(line), first = sec[4 + a];
         if (line == first) { k.str("usemtl material", 15); k.filled4(a); k.ch('\n'); return; }
         const uint32_t e = (first - sec[4] - a) + (line - first - 1u);   // face_ptr[a] + position in the group
-        const uint32_t f = faces[e], tc0 = tc_ptr[a], tcn = tc_ptr[a + 1] - tc0;
-        const bool f_ok = f < F;
-        if (!f_ok) bad[0] += 1u;
+        const uint32_t tc0 = tc_ptr[a], tcn = tc_ptr[a + 1] - tc0;
         k.ch('f');
         for (uint32_t c = 0; c < 3u; ++c) {
-            const uint32_t v = f_ok ? mesh_faces[3 * (size_t)f + c] + 1u : 0u, id = ids[3 * (size_t)e + c];
-            if (id >= tcn) bad[1] += 1u;
-            k.ch(' '); k.u32(v); k.ch('/'); k.u32(id < tcn ? tc0 + id + 1u : 0u);
+            const ModelCorner m = model_corner(mesh_faces, F, faces, ids, tc0, tcn, e, c);
+            if (!m.face_ok && c == 0u) bad[0] += 1u;
+            if (!m.id_ok) bad[1] += 1u;
+            const uint32_t v = m.face_ok ? m.v + 1u : 0u;
+            k.ch(' '); k.u32(v); k.ch('/'); k.u32(m.id_ok ? m.g + 1u : 0u);
             if (normals) { k.ch('/'); k.u32(v); }
         }
         k.ch('\n');
@@ -165,24 +166,9 @@ void run_model(mvs_ctx* ctx, ModelDev& D, const mvs_atlas_set& in, int on_device
                const mvs_model_params& P, mvs_model_stats& st) {
     hipStream_t s = ctx->stream;
     const uint32_t A = in.n_atlases, L = in.n_listed, NM = in.n_merged, NV = ctx->n_verts, F = ctx->n_faces;
-    if (!ctx->d_verts || !ctx->d_faces) throw StatusError(MVS_ERR_STATE, "build_model: no mesh (mvs_scene_set_mesh first)");
+    std::vector<uint32_t> hf, ht;
+    model_check_set(ctx, in, on_device, "build_model", hf, ht);
     if (name.size() > MAX_NAME) throw StatusError(MVS_ERR_INVALID, "build_model: name longer than 255 bytes");
-    if ((A && (!in.face_ptr || !in.tc_ptr)) || (L && (!in.faces || !in.texcoord_ids)) || (NM && !in.texcoords_merged))
-        throw StatusError(MVS_ERR_INVALID, "build_model: null array in the atlas set");
-    if ((L || NM) && !A) throw StatusError(MVS_ERR_INVALID, "build_model: faces or texture coordinates without an atlas");
-    // face_ptr and tc_ptr on the host: they must run from 0 to the totals
-    static const uint32_t zero = 0u;
-    const uint32_t* hf = &zero; const uint32_t* ht = &zero;
-    if (A) {
-        const size_t b = ((size_t)A + 1) * sizeof(uint32_t);
-        ctx->row_pin.ensure(2 * b);
-        hf = read_to_pin(ctx, ctx->row_pin.p, in.face_ptr, (size_t)A + 1, on_device);
-        ht = read_to_pin(ctx, ctx->row_pin.p + b, in.tc_ptr, (size_t)A + 1, on_device);
-        if (on_device) MVS_HIP(hipStreamSynchronize(s));
-    }
-    if (hf[0] != 0u || ht[0] != 0u || hf[A] != L || ht[A] != NM) throw StatusError(MVS_ERR_INVALID, "build_model: face_ptr / tc_ptr do not run from 0 to the totals");
-    for (uint32_t a = 0; a < A; ++a)
-        if (hf[a + 1] < hf[a] || ht[a + 1] < ht[a]) throw StatusError(MVS_ERR_INVALID, "build_model: face_ptr / tc_ptr of atlas " + std::to_string(a) + " descend");
     const uint64_t n64 = 1ull + NV + NM + (normals ? (uint64_t)NV : 0ull) + A + L;
     if (n64 >= 0xFFFFFE00ull) throw StatusError(MVS_ERR_UNSUPPORTED, "build_model: too many lines for one call");
     const uint32_t n = (uint32_t)n64, NS = A + 5u;
@@ -230,8 +216,7 @@ void run_model(mvs_ctx* ctx, ModelDev& D, const mvs_atlas_set& in, int on_device
     st.lines[4] = n - h_sec[4]; st.bytes[4] = obj_bytes - pin[4];
     st.mtl_bytes = mtl_bytes; st.wide_values = c64[K_WIDE]; st.nonfinite_values = c64[K_NONFINITE];
     st.ms_measure = tm.ms(0, 1); st.ms_scan = tm.ms(1, 2);
-    if (c64[K_BAD_FACE]) throw StatusError(MVS_ERR_INVALID, "build_model: " + std::to_string(c64[K_BAD_FACE]) + " face ids are not below the number of faces");
-    if (c64[K_BAD_ID]) throw StatusError(MVS_ERR_INVALID, "build_model: " + std::to_string(c64[K_BAD_ID]) + " texcoord ids lie outside their atlas's range");
+    model_refuse_bad_ids(c64[K_BAD_FACE], c64[K_BAD_ID], "build_model");
     if (P.max_bytes && obj_bytes > P.max_bytes)
         throw StatusError(MVS_ERR_UNSUPPORTED, "build_model: " + std::to_string(obj_bytes) + " bytes of .obj text exceed max_bytes = " + std::to_string(P.max_bytes));
     // ---- write ----
@@ -249,12 +234,22 @@ void run_model(mvs_ctx* ctx, ModelDev& D, const mvs_atlas_set& in, int on_device
     D.obj_bytes = obj_bytes; D.mtl_bytes = mtl_bytes;
 }
 
-// a device range into a file through the context's pinned buffer, 32 MB at a time; ms_copy: the time spent waiting for the copies
+// a device range into a file of its own
 mvs_status device_to_file(mvs_ctx* ctx, const char* d, uint64_t bytes, const std::string& path, double& ms_copy, std::string& msg) {
-    constexpr size_t CHUNK = 32u << 20;
     png_detail::File file(fopen(path.c_str(), "wb"));
-    FILE* f = file.get();
-    if (!f) return png_detail::fail(msg, MVS_ERR_INVALID, "cannot open " + path);
+    if (!file) return png_detail::fail(msg, MVS_ERR_INVALID, "cannot open " + path);
+    bool ok = device_to_stream(ctx, d, bytes, file.get(), ms_copy);
+    if (fclose(file.release()) != 0) ok = false;
+    return ok ? MVS_OK : png_detail::fail(msg, MVS_ERR_INVALID, "write error on " + path);
+}
+
+}  // namespace
+
+// ---- what rows f9 and f11 (k_glb.hip) share: declared in ctx.h ----
+std::string model_filled4(uint32_t a) { char b[16]; snprintf(b, sizeof(b), "%04u", a); return b; }
+
+bool device_to_stream(mvs_ctx* ctx, const char* d, uint64_t bytes, FILE* f, double& ms_copy) {
+    constexpr size_t CHUNK = 32u << 20;
     ctx->row_pin.ensure((size_t)std::min<uint64_t>(bytes, CHUNK) + 16);
     bool ok = true;
     for (uint64_t at = 0; ok && at < bytes; at += CHUNK) {
@@ -265,13 +260,94 @@ mvs_status device_to_file(mvs_ctx* ctx, const char* d, uint64_t bytes, const std
         ms_copy += now_ms_host() - t0;
         ok = fwrite(ctx->row_pin.p, 1, k, f) == k;
     }
-    if (fclose(file.release()) != 0) ok = false;
-    return ok ? MVS_OK : png_detail::fail(msg, MVS_ERR_INVALID, "write error on " + path);
+    return ok;
 }
 
-std::string filled4(uint32_t a) { char b[16]; snprintf(b, sizeof(b), "%04u", a); return b; }
+void model_check_set(mvs_ctx* ctx, const mvs_atlas_set& in, int on_device, const char* who, std::vector<uint32_t>& face_ptr, std::vector<uint32_t>& tc_ptr) {
+    const uint32_t A = in.n_atlases, L = in.n_listed, NM = in.n_merged;
+    const std::string w = std::string(who) + ": ";
+    if (!ctx->d_verts || !ctx->d_faces) throw StatusError(MVS_ERR_STATE, w + "no mesh (mvs_scene_set_mesh first)");
+    if ((A && (!in.face_ptr || !in.tc_ptr)) || (L && (!in.faces || !in.texcoord_ids)) || (NM && !in.texcoords_merged))
+        throw StatusError(MVS_ERR_INVALID, w + "null array in the atlas set");
+    if ((L || NM) && !A) throw StatusError(MVS_ERR_INVALID, w + "faces or texture coordinates without an atlas");
+    // face_ptr and tc_ptr on the host: they must run from 0 to the totals
+    face_ptr.assign((size_t)A + 1, 0u); tc_ptr.assign((size_t)A + 1, 0u);
+    if (A) {
+        const size_t b = ((size_t)A + 1) * sizeof(uint32_t);
+        ctx->row_pin.ensure(2 * b);
+        const uint32_t* hf = read_to_pin(ctx, ctx->row_pin.p, in.face_ptr, (size_t)A + 1, on_device);
+        const uint32_t* ht = read_to_pin(ctx, ctx->row_pin.p + b, in.tc_ptr, (size_t)A + 1, on_device);
+        if (on_device) MVS_HIP(hipStreamSynchronize(ctx->stream));
+        face_ptr.assign(hf, hf + A + 1); tc_ptr.assign(ht, ht + A + 1);
+    }
+    if (face_ptr[0] != 0u || tc_ptr[0] != 0u || face_ptr[A] != L || tc_ptr[A] != NM) throw StatusError(MVS_ERR_INVALID, w + "face_ptr / tc_ptr do not run from 0 to the totals");
+    for (uint32_t a = 0; a < A; ++a)
+        if (face_ptr[a + 1] < face_ptr[a] || tc_ptr[a + 1] < tc_ptr[a]) throw StatusError(MVS_ERR_INVALID, w + "face_ptr / tc_ptr of atlas " + std::to_string(a) + " descend");
+}
 
-}  // namespace
+void model_refuse_bad_ids(uint64_t bad_faces, uint64_t bad_ids, const char* who) {
+    if (bad_faces) throw StatusError(MVS_ERR_INVALID, std::string(who) + ": " + std::to_string(bad_faces) + " face ids are not below the number of faces");
+    if (bad_ids) throw StatusError(MVS_ERR_INVALID, std::string(who) + ": " + std::to_string(bad_ids) + " texcoord ids lie outside their atlas's range");
+}
+
+void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who) {
+    const std::string w = std::string(who) + ": ";
+    if (P.png_level < 0 || P.png_level > 9) throw StatusError(MVS_ERR_INVALID, w + "png_level 0 .. 9");
+    if (P.png_device != 0 && P.png_device != 1) throw StatusError(MVS_ERR_INVALID, w + "png_device 0 or 1");
+    if (P.png_device == 1 && P.png_level != 0) throw StatusError(MVS_ERR_INVALID, w + "png_device 1 takes png_level 0");
+    if (P.png_level > 0 && in.n_atlases && !png_zlib_available()) throw StatusError(MVS_ERR_UNSUPPORTED, w + "libz.so.1 not found (png_level 0 needs no library)");
+    if (in.n_atlases && (!in.atlas_size || !in.atlas_pix_ptr || (in.n_pixels && !in.image))) throw StatusError(MVS_ERR_INVALID, w + "null array in the atlas set");
+}
+
+void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelPngSink& sink) {
+    // sizes and offsets on the host, the pixels copied once, one atlas per thread at a time
+    hipStream_t s = ctx->stream;
+    const uint32_t A = in.n_atlases;
+    const std::string w = std::string(who) + ": ";
+    std::vector<uint32_t> size(A); std::vector<uint64_t> pix((size_t)A + 1, 0);
+    std::vector<uint8_t> own;
+    const uint8_t* image = in.image;
+    if (A) {
+        if (atlases_on_device) {
+            MVS_HIP(hipMemcpyAsync(size.data(), in.atlas_size, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            MVS_HIP(hipMemcpyAsync(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            if (!P.png_device) {
+                own.resize(3 * (size_t)in.n_pixels + 1);
+                if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
+                image = own.data();
+            }
+            MVS_HIP(hipStreamSynchronize(s));
+        } else {
+            memcpy(size.data(), in.atlas_size, A * sizeof(uint32_t)); memcpy(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t));
+        }
+    }
+    if (pix[0] != 0 || pix[A] != in.n_pixels) throw StatusError(MVS_ERR_INVALID, w + "atlas_pix_ptr does not run from 0 to n_pixels");
+    for (uint32_t a = 0; a < A; ++a)
+        if (!size[a] || pix[a + 1] < pix[a] || pix[a + 1] - pix[a] != (uint64_t)size[a] * size[a]) throw StatusError(MVS_ERR_INVALID, w + "atlas " + std::to_string(a) + ": size and atlas_pix_ptr do not agree");
+    PngFiles files;   // png_device 1: the finished files, encoded on the device
+    if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
+    std::atomic<uint32_t> next{0}; std::atomic<int> failed{MVS_OK};
+    std::vector<std::string> errs(A);
+    auto work = [&] {
+        for (uint32_t a = next.fetch_add(1); a < A; a = next.fetch_add(1)) {
+            mvs_status r;
+            if (P.png_device) r = sink(a, files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a]);
+            else {
+                std::vector<uint8_t> png;
+                r = encode_png(image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, png, errs[a]);
+                if (r == MVS_OK) r = sink(a, png.data(), png.size(), errs[a]);
+            }
+            if (r != MVS_OK) failed.store(r);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < std::min<uint32_t>(16u, A); ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (failed.load() != MVS_OK)
+        for (uint32_t a = 0; a < A; ++a) if (!errs[a].empty()) throw StatusError((mvs_status)failed.load(), w + errs[a]);
+}
+
 }  // namespace mvs
 
 using namespace mvs;
@@ -331,12 +407,7 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
         mvs_model_params P;
         if (params) P = *params; else mvs_model_default_params(&P);
         const mvs_atlas_set& in = *atlases;
-        const uint32_t A = in.n_atlases;
-        if (P.png_level < 0 || P.png_level > 9) throw StatusError(MVS_ERR_INVALID, "save_model: png_level 0 .. 9");
-        if (P.png_device != 0 && P.png_device != 1) throw StatusError(MVS_ERR_INVALID, "save_model: png_device 0 or 1");
-        if (P.png_device == 1 && P.png_level != 0) throw StatusError(MVS_ERR_INVALID, "save_model: png_device 1 takes png_level 0");
-        if (P.png_level > 0 && A && !png_zlib_available()) throw StatusError(MVS_ERR_UNSUPPORTED, "save_model: libz.so.1 not found (png_level 0 needs no library)");
-        if (A && (!in.atlas_size || !in.atlas_pix_ptr || (in.n_pixels && !in.image))) throw StatusError(MVS_ERR_INVALID, "save_model: null array in the atlas set");
+        model_check_png_params(P, in, "save_model");
         const std::string pre(prefix), name = pre.substr(pre.find_last_of('/') == std::string::npos ? 0 : pre.find_last_of('/') + 1);
         run_with_stats(s, stats, st, [&] {
             run_model(ctx, D, in, atlases_on_device, vertex_normals, normals_on_device, name, P, st);
@@ -346,47 +417,14 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
             if (rc == MVS_OK) rc = device_to_file(ctx, D.mtl.p, D.mtl_bytes, pre + ".mtl", ms_copy, msg);
             st.ms_download = (float)ms_copy; st.ms_files = (float)(now_ms_host() - t0 - ms_copy);
             if (rc != MVS_OK) throw StatusError(rc, "save_model: " + msg);
-            // ---- the PNGs: sizes and offsets on the host, the pixels copied once, one atlas per thread at a time ----
+            // ---- the PNGs: one file per atlas, written by the thread that holds its bytes ----
             const double t1 = now_ms_host();
-            std::vector<uint32_t> size(A); std::vector<uint64_t> pix((size_t)A + 1, 0);
-            std::vector<uint8_t> own;
-            const uint8_t* image = in.image;
-            if (A) {
-                if (atlases_on_device) {
-                    MVS_HIP(hipMemcpyAsync(size.data(), in.atlas_size, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    MVS_HIP(hipMemcpyAsync(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-                    if (!P.png_device) {
-                        own.resize(3 * (size_t)in.n_pixels + 1);
-                        if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
-                        image = own.data();
-                    }
-                    MVS_HIP(hipStreamSynchronize(s));
-                } else {
-                    memcpy(size.data(), in.atlas_size, A * sizeof(uint32_t)); memcpy(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t));
-                }
-            }
-            if (pix[0] != 0 || pix[A] != in.n_pixels) throw StatusError(MVS_ERR_INVALID, "save_model: atlas_pix_ptr does not run from 0 to n_pixels");
-            for (uint32_t a = 0; a < A; ++a)
-                if (!size[a] || pix[a + 1] < pix[a] || pix[a + 1] - pix[a] != (uint64_t)size[a] * size[a]) throw StatusError(MVS_ERR_INVALID, "save_model: atlas " + std::to_string(a) + ": size and atlas_pix_ptr do not agree");
-            PngFiles files;   // png_device 1: the finished files, encoded on the device
-            if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
-            std::atomic<uint32_t> next{0}; std::atomic<int> failed{MVS_OK};
-            std::vector<std::string> errs(A);
-            auto work = [&] {
-                for (uint32_t a = next.fetch_add(1); a < A; a = next.fetch_add(1)) {
-                    const std::string path = pre + "_material" + filled4(a) + "_map_Kd.png";
-                    const mvs_status r = P.png_device ? write_file(path.c_str(), files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a])
-                                                      : write_png(path.c_str(), image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, errs[a]);
-                    if (r != MVS_OK) failed.store(r);
-                }
-            };
-            std::vector<std::thread> pool;
-            for (uint32_t t = 1; t < std::min<uint32_t>(16u, A); ++t) pool.emplace_back(work);
-            work();
-            for (auto& t : pool) t.join();
+            try {
+                model_for_each_png(ctx, in, atlases_on_device, P, "save_model", [&](uint32_t a, const uint8_t* bytes, size_t n, std::string& err) {
+                    return write_file((pre + "_material" + model_filled4(a) + "_map_Kd.png").c_str(), bytes, n, err);
+                });
+            } catch (...) { st.ms_png = (float)(now_ms_host() - t1); throw; }
             st.ms_png = (float)(now_ms_host() - t1);
-            if (failed.load() != MVS_OK)
-                for (uint32_t a = 0; a < A; ++a) if (!errs[a].empty()) throw StatusError((mvs_status)failed.load(), "save_model: " + errs[a]);
         });
     });
 }

@@ -171,6 +171,18 @@ class ModelStats(C.Structure):
     _fields_ = [("lines", C.c_uint64 * 5), ("bytes", C.c_uint64 * 5)] + [(k, C.c_uint64) for k in MODEL_COUNTS] + [(k, C.c_float) for k in MODEL_MS]
 
 
+GLB_COUNTS = ("vertices", "indices", "primitives", "json_bytes", "geometry_bytes", "image_bytes", "file_bytes", "nonfinite_values")
+GLB_MS = ("ms_keys", "ms_sort", "ms_number", "ms_indices", "ms_gather", "ms_png", "ms_download", "ms_file")
+
+
+class GlbStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in GLB_COUNTS] + [(k, C.c_float) for k in GLB_MS]
+
+
+class Glb(C.Structure):
+    _fields_ = [("n_bytes", C.c_uint64), ("data", C.c_void_p)]
+
+
 class DcStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("pairs", "cull_backface", "cull_angle", "cull_outside", "cull_occluded",
                                            "cull_zero_quality", "nnz_pre", "nnz", "rays", "ray_nodes", "ray_tris", "ray_packets", "ray_packets_generic")] + \
@@ -295,6 +307,8 @@ def load_library():
         "mvs_ctx_build_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelText), i32, C.POINTER(ModelStats)],
         "mvs_ctx_save_model": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(ModelStats)],
         "mvs_write_png": [C.c_char_p, vp, u32, u32, C.c_int32],
+        "mvs_ctx_build_glb": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.POINTER(ModelParams), C.POINTER(Glb), C.POINTER(GlbStats)],
+        "mvs_ctx_save_glb": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(GlbStats)], "mvs_glb_free": [C.POINTER(Glb)],
         "mvs_ctx_encode_pngs": [vp, u32, vp, vp, vp, vp, i32, C.POINTER(PngSet), C.POINTER(PngStats)], "mvs_png_set_free": [C.POINTER(PngSet)],
         "mvs_ctx_deflate_rle": [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)], "mvs_png_free": [vp],
         "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
@@ -326,7 +340,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_png_set_free", "mvs_png_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_glb_free", "mvs_png_set_free", "mvs_png_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -880,6 +894,32 @@ class Context:
         _check_with_stats(self.L, rc, stats)
         return stats
 
+    def build_glb(self, atlases, vertex_normals=None, params=None):
+        """Row f11: the textured model as one binary glTF 2.0 file (mvs_ctx_build_glb; DESIGN.md section 4 "Model output" item 8) on the
+        context's mesh and an atlas set -- the dict of texture_atlases, all host arrays or all DevArrays / CUDA tensors; without
+        atlas_size or image the file carries no images.  vertex_normals: (n_verts, 3) host or device array, or None: no NORMAL attribute.
+        Returns (bytes, stats).  params: default_model_params(...) as save_model reads it -- the embedded PNGs are the files it would
+        write; max_bytes caps the file.  A refusal raises MvsError with `.stats` holding the counts."""
+        ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
+        res, st = Glb(), GlbStats()
+        self._keep["glb"] = held
+        rc = self.L.mvs_ctx_build_glb(self.h, C.byref(ps), dev, pn, dn, C.byref(p), C.byref(res), C.byref(st))
+        stats = _glb_stats(st)
+        _check_with_stats(self.L, rc, stats)
+        data = C.string_at(res.data, res.n_bytes)
+        self.L.mvs_glb_free(C.byref(res))
+        return data, stats
+
+    def save_glb(self, atlases, path, vertex_normals=None, params=None):
+        """Row f11 to a file: build_glb's bytes at `path`, written once (mvs_ctx_save_glb).  Returns the stats."""
+        ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
+        st = GlbStats()
+        self._keep["glb"] = held
+        rc = self.L.mvs_ctx_save_glb(self.h, C.byref(ps), dev, pn, dn, os.fspath(path).encode(), C.byref(p), C.byref(st))
+        stats = _glb_stats(st)
+        _check_with_stats(self.L, rc, stats)
+        return stats
+
     def encode_pngs(self, images):
         """The compressed PNG route of row f9 on its own (mvs_ctx_encode_pngs; DESIGN.md section 4 "Model output" item 7): `images` is a
         list of (H, W, 3) uint8 arrays -- all numpy or all CUDA tensors -- or an atlas-set dict (atlas_size, atlas_pix_ptr, image: all
@@ -1059,6 +1099,12 @@ def _model_stats(st):
     return stats
 
 
+def _glb_stats(st):
+    stats = {k: int(getattr(st, k)) for k in GLB_COUNTS}
+    stats.update({k: float(getattr(st, k)) for k in GLB_MS})
+    return stats
+
+
 def _png_stats(st):
     stats = {k: int(getattr(st, k)) for k in PNG_COUNTS}
     stats["filter_rows"] = [int(x) for x in st.filter_rows]
@@ -1203,18 +1249,26 @@ def view_selection_model(scene, labels, prefix, view_ids=None, vertex_normals=No
                                       _toned(None, default_patch_params, tone_mapping), _toned(None, default_atlas_params, tone_mapping))
 
 
-def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None, view_selection_model=False, tone_mapping="none"):
+def texture_model(scene, labels, prefix, vertex_normals=None, params=None, ctx=None, view_selection_model=False, tone_mapping="none", format="obj"):
     """texrecon.cpp:169-208 for a synth.Scene-like object and its labels: rows f5 to f8 as texture_atlases runs them, then the model
     output (row f9) with the atlases left on the device: writes `<prefix>.obj`, `<prefix>.mtl` and the atlas PNGs.  Returns row f9's
     stats.  vertex_normals: (n_verts, 3) or None (no `vn` lines; vertex_normals(verts, faces) computes area-weighted ones).
     view_selection_model=True writes the debug model `<prefix>_view_selection.*` as well (Context.view_selection_model).
-    tone_mapping: "none" | "gamma", passed to every row that reads it (f5, f6, f8 and the debug model)."""
+    tone_mapping: "none" | "gamma", passed to every row that reads it (f5, f6, f8 and the debug model).
+    format: "obj" (default) | "glb" | "both".  "glb" writes `<prefix>.glb` alone (row f11, Context.save_glb) and returns its stats;
+    "both" writes the OBJ route's files as "obj" does, then `<prefix>.glb`, and returns (row f9's stats, row f11's stats).  The debug
+    model is an OBJ in every format."""
+    if format not in ("obj", "glb", "both"):
+        raise ValueError("texture_model: format must be \"obj\", \"glb\" or \"both\", not %r" % (format,))
     with _scene_context(scene, ctx) as c:
         a = np.ascontiguousarray(scene.adj_ptr, dtype=np.uint32); b = np.ascontiguousarray(scene.adj, dtype=np.uint32)
         lab = np.ascontiguousarray(labels, dtype=np.uint32)
         ap = _toned(None, default_atlas_params, tone_mapping)
         atlases, _ = c.texture_atlases(_leveled_patches(c, a, b, lab, tone_mapping), ap, on_device=True)
-        stats = c.save_model(atlases, prefix, vertex_normals, params)
+        stats = c.save_model(atlases, prefix, vertex_normals, params) if format != "glb" else None
+        if format != "obj":
+            glb_stats = c.save_glb(atlases, os.fspath(prefix) + ".glb", vertex_normals, params)
+            stats = glb_stats if format == "glb" else (stats, glb_stats)
         if view_selection_model:   # texrecon.cpp:216-236: after the textured model, on the same context
             c.view_selection_model(a, b, lab, prefix, None, vertex_normals, _toned(None, default_patch_params, tone_mapping), ap, model_params=params)
         return stats
