@@ -31,6 +31,21 @@ mvs_status mvs_ctx_costs_export(mvs_ctx* ctx, uint32_t* counts_device, uint16_t*
  * with the geometric visibility test, when the last pass covered a face range and not the whole mesh, or (which = 0, 1) when it walked
  * the mesh in more than one range (option "dc_range_pairs"): the matrices then hold the last range's rays only. */
 mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
+/* HARNESS ONLY (tests/test_gpu_image_prep.py): what the image preparation (csrc/k_prep.hip prepare_views) of the context's last data-cost
+ * pass left on the device, copied to the host as it lies -- the entry launches nothing and no pass does any work for it.
+ *   which = 0  the view's gradient-magnitude image, width * height bytes (MVS_ERR_STATE when the last pass ran the area term: there is none);
+ *   which = 1  the view's validity mask, height * mask_stride 32-bit words, mask_stride = (width + 31) / 32, bit (x & 31) of word
+ *              (y, x >> 5) = pixel (x, y) -- eroded when the last pass ran the gradient term, plain with the area term;
+ *   which = 2  the view's tile summary, (height + 31) / 32 rows of msum_stride = 2 * ((mask_stride + 63) / 64) words, bit (tx & 31) of word
+ *              (ty, tx >> 5) = 32 x 32 tile (tx, ty).  Meaningful, like the mask, only for a view whose flag (which = 3) is 1: the shortcut for
+ *              a scene without a black corner pixel skips the flood fill, the mask and the summary;
+ *   which = 3  one byte per view of the context (`view` ignored): 1 = the DEVICE copy of the view table still carries the view's mask
+ *              pointer, 0 = a shortcut nulled it (no view has a black corner pixel, or this view's summary came out all ones).
+ * *n_bytes = the size; out_host == null: the size only; a buffer smaller than that, or view >= n_views: MVS_ERR_INVALID.  MVS_ERR_STATE before
+ * a data-cost pass that evaluated (face, view) pairs of the scene (mvs_postprocess_face_infos and a pass over no faces prepare nothing).
+ * Ranged passes (option "dc_range_pairs") and the ranks of the sharded driver ARE served: a ranged pass prepares the views in its first
+ * range and every later range reads the same resident products; a rank runs the whole preparation on its own context. */
+mvs_status mvs_ctx_prep_products(mvs_ctx* ctx, int which, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 /* HARNESS ONLY (tests/test_gpu_mrf_regions.py): mvs_ctx_costs_upload of a HOST table whose columns stand in POSITION order, column p being
  * the caller's face order_host[p] -- and the context left as a data-cost pass over the whole mesh leaves it (name_table_order, k_dc.hip): the
  * active table lives in "the library's own order", mvs_ctx_table_order returns `order`, its inverse is known, both on the device and owned

@@ -17,6 +17,12 @@ struct dmh_view {
     const uint8_t* gmi;
     const uint32_t* mask;  // bit-packed, rows padded to 32-bit words, may be null
 };
+// dmh_view keeps its layout (callers build it field by field); the view WITH the mask's tile summary is a struct of its own
+struct dmh_view_sum {
+    dmh_view view;
+    const uint32_t* msum;  // tile summary of the mask (dmath.h ViewParams::msum), may be null: every mask bit is then read
+    int32_t msum_stride;   // 32-bit words per row of the summary
+};
 
 static ViewParams to_vp(const dmh_view* v) {
     ViewParams p;
@@ -57,6 +63,16 @@ void dmh_cull_pairs(const dmh_view* base, uint32_t n, const float* pos, const fl
         const V3 centre = ((v1 + v2) + v3) / 3.0f;
         out[2 * i] = (int8_t)cull_pair(vp, v1, v2, v3, nr, cos_limit);
         out[2 * i + 1] = (int8_t)cull_pair_prefiltered(vp, v1, v2, v3, nr, centre, cos_limit);
+    }
+}
+
+// the last cull (dmath.h valid_pixels3) at n triples of 2-D pixel positions: xy = n x 3 x (x, y), out[i] = 0 / 1
+void dmh_valid_pixels3(const dmh_view_sum* view, const float* xy, uint32_t n, uint8_t* out) {
+    ViewParams vp = to_vp(&view->view);
+    if (view->msum) { vp.msum = view->msum; vp.msum_stride = view->msum_stride; }
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* p = xy + 6 * (size_t)i;
+        out[i] = valid_pixels3(vp, V2{p[0], p[1]}, V2{p[2], p[3]}, V2{p[4], p[5]}) ? 1 : 0;
     }
 }
 

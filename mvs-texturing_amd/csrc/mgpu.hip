@@ -146,6 +146,40 @@ mvs_status mvs_ctx_ray_bits(mvs_ctx* ctx, int which, void* out_host, uint64_t ca
     MVS_API_END
 }
 
+// harness only: what the image preparation of the last data-cost pass (k_prep.hip prepare_views) left on the device, copied out as it lies:
+// nothing is launched.  The pass that ran the preparation is the last one that evaluated (face, view) pairs -- a ranged pass prepares in its
+// first range and keeps the products resident for the others, a rank of the sharded driver prepares for itself -- so every such state is served.
+mvs_status mvs_ctx_prep_products(mvs_ctx* ctx, int which, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
+    if (!ctx || !n_bytes || which < 0 || which > 3) return api_fail(MVS_ERR_INVALID, "bad argument");
+    const uint32_t V = ctx->n_views;
+    // dc_stats.pairs: set by a pass over the scene, zero after mvs_postprocess_face_infos and for a pass with nothing to evaluate (no preparation either)
+    if (ctx->dc_phase < 1 || V == 0 || ctx->dc_stats.pairs == 0 || ctx->h_views.size() != V || ctx->mask_off.size() != (size_t)V + 1 ||
+        ctx->gmi_off.size() != (size_t)V + 1 || ctx->msum_off.size() != (size_t)V + 1 || !ctx->d_views.p || !ctx->mask_all.p || !ctx->msum_all.p)
+        return api_fail(MVS_ERR_STATE, "prep products: needs a data-cost pass that evaluated the scene's views");
+    const bool have_gmi = ctx->dc_settings.data_term == MVS_DATA_TERM_GMI;
+    if (which == 0 && !have_gmi) return api_fail(MVS_ERR_STATE, "prep products: the last data-cost pass ran the area term: there is no gradient-magnitude image");
+    if (which != 3 && view >= V) return api_fail(MVS_ERR_INVALID, "prep products: view " + std::to_string(view) + " of " + std::to_string(V));
+    MVS_CTX_API_BEGIN
+    const ViewParams& hv = ctx->h_views[which == 3 ? 0 : view];
+    const void* src = nullptr; uint64_t n = 0;
+    if (which == 0) { src = ctx->gmi_all.p + ctx->gmi_off[view]; n = (uint64_t)hv.width * hv.height; }
+    else if (which == 1) { src = ctx->mask_all.p + ctx->mask_off[view]; n = (uint64_t)hv.height * hv.mask_stride * sizeof(uint32_t); }
+    else if (which == 2) { src = ctx->msum_all.p + ctx->msum_off[view]; n = (uint64_t)((hv.height + 31) / 32) * hv.msum_stride * sizeof(uint32_t); }
+    else n = V;
+    *n_bytes = n;
+    if (out_host && cap_bytes < n) throw StatusError(MVS_ERR_INVALID, "prep products: buffer too small");
+    if (out_host && which == 3) {   // the DEVICE copy of the view table: the host copy keeps every mask pointer
+        std::vector<ViewParams> dv(V);
+        MVS_HIP(hipMemcpyAsync(dv.data(), ctx->d_views.p, (size_t)V * sizeof(ViewParams), hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint32_t j = 0; j < V; ++j) ((uint8_t*)out_host)[j] = dv[j].mask ? 1 : 0;
+    } else if (out_host) {
+        MVS_HIP(hipMemcpyAsync(out_host, src, n, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    MVS_API_END
+}
+
 // harness only: a host table in position order + the order itself -> the state name_table_order (k_dc.hip) leaves behind a pass over the
 // whole mesh.  f_perm / f_pos carry it: they no longer describe the resident mesh (mesh_ordered = false; every data-cost pass derives the
 // mesh's order again before it reads them), and a shard that pinned them keeps them.

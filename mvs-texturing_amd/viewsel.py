@@ -218,7 +218,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_prep_products", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table"))
 
 TONE_MAPPINGS = {"none": 0, "gamma": 1}                                       # tex::ToneMapping (settings.h); the *_params.tone_mapping field
 
@@ -279,6 +279,7 @@ def load_library():
         "mvs_ctx_mrf_labels": [vp, u32, u32, vp, C.POINTER(u32)],
         "mvs_ctx_mrf_setup_tables": [vp, i32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_ray_bits": [vp, i32, vp, u64, C.POINTER(u64)],
+        "mvs_ctx_prep_products": [vp, i32, u32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_costs_upload_ordered": [vp, C.POINTER(CCsr), vp],
         "mvs_ctx_tone_table": [vp, vp],
         "mvs_gamma_correct": [vp, u64, C.c_float], "mvs_ctx_gamma_correct": [vp, vp, u64, C.c_float, i32], "mvs_tone_table": [u32, vp],
@@ -466,6 +467,25 @@ class DataCosts:
         _check(L, L.mvs_write_spt(C.byref(s), path.encode()))
 
 
+class PrepProducts:
+    """One view's image-preparation products as read back by Context.prep_products: gmi (uint8 (h, w) or None), mask_words and summary_words
+    (uint32, rows as the device pads them)."""
+
+    def __init__(self, width, height, gmi, mask_words, summary_words):
+        self.width, self.height, self.gmi, self.mask_words, self.summary_words = width, height, gmi, mask_words, summary_words
+
+    def mask_bits(self):
+        """(valid bool (h, w), padding bool (h, 32 * mask_stride - w)): bit x & 31 of word (y, x >> 5) is pixel (x, y)"""
+        bits = np.unpackbits(np.ascontiguousarray(self.mask_words).view(np.uint8).reshape(self.height, -1), axis=1, bitorder="little").astype(bool)
+        return bits[:, :self.width], bits[:, self.width:]
+
+    def summary_bits(self):
+        """(tiles bool (ceil(h / 32), mask_stride), padding bool: the bits of tile columns >= mask_stride)"""
+        bits = np.unpackbits(np.ascontiguousarray(self.summary_words).view(np.uint8).reshape(self.summary_words.shape[0], -1), axis=1, bitorder="little").astype(bool)
+        ms = self.mask_words.shape[1]
+        return bits[:, :ms], bits[:, ms:]
+
+
 class Context:
     """Resident scene + results on one GPU (mvs_ctx)."""
 
@@ -525,6 +545,7 @@ class Context:
             assert dev is None or dev == d
             dev = d
         self._keep["views"] = images
+        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)]
         self.n_views = V
         _check(self.L, self.L.mvs_scene_set_views(self.h, arr, V, dev or 0))
 
@@ -666,6 +687,34 @@ class Context:
         buf = np.zeros(n.value // 4, dtype=np.uint32)
         _check(self.L, self.L.mvs_ctx_ray_bits(self.h, 2, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return buf
+
+    def _prep_read(self, which, view, dtype):
+        n = C.c_uint64(0)
+        _check(self.L, self.L.mvs_ctx_prep_products(self.h, which, view, None, 0, C.byref(n)))
+        buf = np.zeros(n.value // np.dtype(dtype).itemsize, dtype=dtype)
+        _check(self.L, self.L.mvs_ctx_prep_products(self.h, which, view, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return buf
+
+    def prep_products(self, view):
+        """what the image preparation of the last data-cost pass left on the device for one view (mvs_ctx_prep_products, building-blocks
+        library; test harness only): a PrepProducts with gmi (uint8 (h, w), None after an area-term pass), mask_words (uint32 (h, mask_stride))
+        and summary_words (uint32 (ceil(h / 32), msum_stride)) exactly as the device holds them"""
+        mask = self._prep_read(1, view, np.uint32)                         # (raises what the entry refuses: no pass yet, no such view)
+        w, h = self._view_sizes[view]
+        mask = mask.reshape(h, -1)
+        summary = self._prep_read(2, view, np.uint32).reshape((h + 31) // 32, -1)
+        try:
+            gmi = self._prep_read(0, view, np.uint8).reshape(h, w)
+        except MvsError as e:
+            if e.status != 6:                                              # MVS_ERR_STATE here: the last pass ran the area term
+                raise
+            gmi = None
+        return PrepProducts(w, h, gmi, mask, summary)
+
+    def prep_mask_flags(self):
+        """uint8[n_views]: 1 = the DEVICE copy of the view table still carries the view's mask pointer after the last data-cost pass, 0 = a
+        shortcut of the image preparation nulled it (mvs_ctx_prep_products, which = 3)"""
+        return self._prep_read(3, 0, np.uint8)
 
     def mrf_diagnostics(self):
         """{graph_launches, graph_updates, graph_instantiations, generic_nodes} of this context's view selections"""

@@ -1275,3 +1275,270 @@ def region_cases():
     out["chain"] = region_chain
     for k in REGION_EDGE_KINDS: out["edges_" + k] = (lambda k=k: region_edges(k))
     return out
+
+
+# ---- image preparation (csrc/k_prep.hip): crafted images, the scene around them and the references of tests/test_gpu_image_prep.py and
+# ---- tests/test_image_prep_host.py.  Everything here is exact: bytes, bits, words.
+
+def prep_scene(images):
+    """a synth.Scene (no adjacency) with ONE triangle in front of one camera per image; camera j carries the width and height of images[j].
+    Image preparation does not depend on the mesh: the triangle makes data_costs a legal call and gives the culls one face to decide."""
+    verts = np.float32([[-0.5, -0.5, 0.0], [0.5, -0.5, 0.0], [0.0, 0.5, 0.0]])
+    n = len(images)
+    s = lookat_scene(verts, np.uint32([[0, 1, 2]]), np.float32([[0.0, 0.0, 1.0]]), [(0.0, 0.0, 3.0)] * n, [(0.0, 0.0, 0.0)] * n,
+                     [(int(i.shape[1]), int(i.shape[0])) for i in images])
+    s.images = [np.ascontiguousarray(i, dtype=np.uint8) for i in images]
+    for i in s.images: assert i.ndim == 3 and i.shape[2] == 3 and i.shape[0] >= 2 and i.shape[1] >= 2
+    return s
+
+
+def noise_blob(rng, w, h, bw, bh, lo=0):
+    """noise over the byte range [lo, 255] with a black bw x bh blob in the corner (0, 0)"""
+    img = rng.integers(lo, 256, (h, w, 3)).astype(np.uint8)
+    img[:bh, :bw] = 0
+    return np.ascontiguousarray(img)
+
+
+SMALL_HOSTILE = ("all_black", "corner_pixel", "first_row", "last_col", "frame1", "frame2", "hline", "hline_break32", "hline_break31",
+                 "vline31", "vline32", "blob_rim", "island")
+
+
+def small_hostile_images(rng, w, h):
+    """the patterns that matter at small sizes: name -> (h, w, 3) u8, everything not mentioned noise >= 1.  A pattern the size cannot hold is
+    left out (the tests assert which).  Needs: frame1 / blob_rim / island an interior pixel (w, h >= 3); frame2 a pixel behind the eroded
+    third ring (w, h >= 7); the lines an interior row 1 (h >= 3) and a pixel beyond the break / a neighbouring interior column."""
+    def noise():
+        return rng.integers(1, 255, (h, w, 3)).astype(np.uint8)
+    out = {}
+    out["all_black"] = np.zeros((h, w, 3), np.uint8)
+    img = noise(); img[0, 0] = 0; out["corner_pixel"] = img
+    img = noise(); img[0, :] = 0; out["first_row"] = img
+    img = noise(); img[:, w - 1] = 0; out["last_col"] = img
+    if w >= 3 and h >= 3:
+        img = noise(); img[0] = 0; img[-1] = 0; img[:, 0] = 0; img[:, -1] = 0        # every invalid pixel is a border pixel: erosion changes nothing
+        out["frame1"] = img
+        img = noise(); img[:h - 1, :w - 1] = 0                                       # rim at x = w - 2 and y = h - 2: erosion reaches the border pixels
+        out["blob_rim"] = img
+        r = min(w, h) // 6
+        img = noise(); img[h // 2 - r:h // 2 + r + 1, w // 2 - r:w // 2 + r + 1] = 0  # black, unreachable: stays valid
+        out["island"] = img
+    if w >= 7 and h >= 7:
+        img = noise(); img[:2] = 0; img[-2:] = 0; img[:, :2] = 0; img[:, -2:] = 0     # erosion eats a third ring
+        out["frame2"] = img
+    if h >= 3:
+        def hline():
+            img = noise(); img[0, 0] = 0; img[1, :] = 0                              # corner (0, 0), then row 1 from x = 0 to w - 1: one word per Jacobi step
+            return img
+        out["hline"] = hline()
+        if w >= 34:
+            img = hline(); img[1, 32] = (0, 1, 0); out["hline_break32"] = img        # nothing beyond the break may be filled
+        if w >= 33:
+            img = hline(); img[1, 31] = (0, 0, 1); out["hline_break31"] = img
+        for col in (31, 32):
+            if w >= col + 2:                                                         # column `col` is interior
+                img = noise(); img[0, :col + 1] = 0; img[:h - 1, col] = 0            # along the top border from the corner, then down column `col`
+                out["vline%d" % col] = img
+    return {k: np.ascontiguousarray(v) for k, v in out.items()}
+
+
+def erosion_bites(name, w, h):
+    """does erode_validity_mask change the mask of this pattern (hostile_images / small_hostile_images) at this size?  From the patterns'
+    definitions alone: erosion acts only through INTERIOR invalid pixels."""
+    if name in ("all_black", "corner_pixel", "first_row", "last_col", "frame1", "island", "checker", "corners"):
+        return False                                                                 # nothing invalid off the border (all_black: nothing left to clear)
+    if name == "hline": return w >= 3
+    return True
+
+
+def rim_blob(rng, w, h, bx, by, corner="tl"):
+    """a flooded black blob in noise >= 1, clipped to the image, anchored at a corner: "tl" [0, bx) x [0, by) -- its eroded rim ends at column bx
+    and row by; "tr" [bx, w) x [0, by) -- the plain rim STARTS at column bx, the eroded one at bx - 1: with bx = 32 or 33 the only invalid pixels
+    of tile column 0 are in pixel column 32, the one it shares with its neighbour; "bl" [0, bx) x [by, h) likewise for rows; "br" both"""
+    img = rng.integers(1, 255, (h, w, 3)).astype(np.uint8)
+    ys = slice(0, by) if corner[0] == "t" else slice(by, h)
+    xs = slice(0, bx) if corner[1] == "l" else slice(bx, w)
+    img[ys, xs] = 0
+    return np.ascontiguousarray(img)
+
+
+def luminance_numpy(rgb):
+    """the oracle's luminance plane (oracle.cpp orc_gradient_magnitude: T(0.30 * r + 0.59f * g + 0.11f * b), the first product in double, the
+    other two in float, the sum in double, truncated)"""
+    r, g, b = (rgb[..., k] for k in range(3))
+    v = np.float64(0.30) * r.astype(np.float64) + (np.float32(0.59) * g.astype(np.float32)).astype(np.float64) + (np.float32(0.11) * b.astype(np.float32)).astype(np.float64)
+    return v.astype(np.uint8)
+
+
+def sobel_sums_numpy(lum):
+    """(sx, sy) int32 (h - 2, w - 2): the 3 x 3 Sobel sums at the interior pixels of a luminance plane"""
+    l = lum.astype(np.int32)
+    a, b, c = l[:-2, :-2], l[:-2, 1:-1], l[:-2, 2:]
+    d, f = l[1:-1, :-2], l[1:-1, 2:]
+    g, hh, i = l[2:, :-2], l[2:, 1:-1], l[2:, 2:]
+    return (c - a) + 2 * (f - d) + (i - g), (g - a) + 2 * (hh - b) + (i - c)
+
+
+def gradient_magnitude_numpy(rgb):
+    """floor(min(255, sqrt(sx^2 + sy^2))) in integers, border 0: what orc_gradient_magnitude computes in double (exact: n < 2^53)"""
+    h, w = rgb.shape[:2]
+    out = np.zeros((h, w), np.uint8)
+    if h >= 3 and w >= 3:
+        sx, sy = sobel_sums_numpy(luminance_numpy(rgb))
+        n = (sx.astype(np.int64) ** 2 + sy.astype(np.int64) ** 2)
+        k = np.floor(np.sqrt(n.astype(np.float64))).astype(np.int64)
+        k -= (k * k > n); k += ((k + 1) * (k + 1) <= n)                              # integer-exact whatever the libm
+        out[1:-1, 1:-1] = np.minimum(k, 255).astype(np.uint8)
+    return out
+
+
+LUM_MAX = 254          # the luminance of (255, 255, 255): 0.30 * 255 + 0.59f * 255 + 0.11f * 255 falls short of 255 and is truncated
+
+
+def luminance_triples():
+    """uint8 (255, 3): for every luminance L <= LUM_MAX an RGB triple whose oracle luminance is L and whose channel sum is not 0 (a black pixel
+    would seed or feed the validity flood fill).  Grey (v, v, v) is not always v after truncation, so the neighbours of grey are searched.
+    Luminance is monotone in every channel, so white's 254 is the largest there is: 255 has no triple."""
+    assert int(luminance_numpy(np.uint8([255, 255, 255]))) == LUM_MAX
+    out = np.zeros((LUM_MAX + 1, 3), np.uint8)
+    for L in range(LUM_MAX + 1):
+        found = None
+        for dr in (0, 1, -1, 2):
+            for dg in (0, 1, -1):
+                for db in (0, 1, -1, 2):
+                    t = np.array([L + dr, L + dg, L + db])
+                    if found is None and t.min() >= 0 and t.max() <= 255 and t.sum() > 0 and int(luminance_numpy(t.astype(np.uint8))) == L:
+                        found = t
+        assert found is not None, L
+        out[L] = found
+    return out
+
+
+def _block(sx, sy):
+    """3 x 3 luminances with Sobel sums (sx, sy) at the centre, 0 <= sx, sy <= 510 of equal parity: a = b = c = d = g = 0, f = sx div 2,
+    h = sy div 2, i = sx mod 2 -- sx = 2 f + i, sy = 2 h + i"""
+    assert (sx - sy) % 2 == 0
+    return np.array([[0, 0, 0], [0, 0, sx // 2], [0, sy // 2, sx % 2]], np.int32)
+
+
+SOBEL_EXTREME = 4 * LUM_MAX
+
+
+def _extreme(b, h):
+    """sx = SOBEL_EXTREME (the largest: c = f = i = LUM_MAX, a = d = g = 0), sy = 2 (h - b).  |sx| at its extreme fixes a, c, g and i, so
+    |sy| <= SOBEL_EXTREME / 2 beside it: the two sums are never extreme together."""
+    return np.array([[0, b, LUM_MAX], [0, 128, LUM_MAX], [0, h, LUM_MAX]], np.int32)
+
+
+SOBEL_SIGNED = ((1, 1), (7, 3), (256, 256), (255, 1), (0, 256), (256, 0), (181, 181))     # these magnitudes also with every combination of signs
+
+
+def sobel_pairs_image(width):
+    """an image that holds, as the 3 x 3 neighbourhood of some interior pixel, every pair of Sobel sums (sx, sy) with 0 <= sx, sy <= 256 and
+    sx = sy (mod 2) -- the two sums always have the same parity -- i.e. every even square k^2 + 0^2 as an argument of the square root (an odd one is never
+    an argument: n = sx^2 + sy^2 is 0 or 2 mod 4) and arguments on both sides of all 255 thresholds; the SOBEL_SIGNED pairs under all four sign combinations; and the extremes sx = +-1016 with sy in {0, +-508} and
+    sy = +-1016 with sx in {0, +-508} (luminance ends at LUM_MAX = 254).  Blocks of 3 x 3 pixels, width // 3 per row; no pixel is black (r + g + b > 0)."""
+    per_row = width // 3
+    assert per_row >= 1
+    blocks = [_block(sx, sy) for sx in range(257) for sy in range(sx % 2, 257, 2)]
+    for sx, sy in SOBEL_SIGNED:
+        b = _block(sx, sy)
+        blocks += [b[:, ::-1], b[::-1, :], b[::-1, ::-1]]
+    for b, h in ((0, 0), (0, LUM_MAX), (LUM_MAX, 0)):
+        e = _extreme(b, h)
+        blocks += [e, e[:, ::-1], e.T, e.T[::-1, :]]
+    rows = (len(blocks) + per_row - 1) // per_row
+    lum = np.zeros((3 * rows, width), np.int32)
+    for k, b in enumerate(blocks):
+        r, c = divmod(k, per_row)
+        lum[3 * r:3 * r + 3, 3 * c:3 * c + 3] = b
+    return np.ascontiguousarray(luminance_triples()[lum])
+
+
+def sobel_pairs_seen(img):
+    """bool (2041, 2041): [sx + 1020, sy + 1020] = the pair occurs at an interior pixel of img -- from the REFERENCE side (luminance_numpy)"""
+    sx, sy = sobel_sums_numpy(luminance_numpy(img))
+    seen = np.zeros((2041, 2041), bool)
+    seen[sx.ravel() + 1020, sy.ravel() + 1020] = True
+    return seen
+
+
+def assert_sobel_pairs_coverage(img):
+    """what sobel_pairs_image promises, asserted on the image itself"""
+    seen = sobel_pairs_seen(img)
+    sx, sy = np.meshgrid(np.arange(257), np.arange(257), indexing="ij")
+    want = (sx - sy) % 2 == 0
+    assert int(want.sum()) == 129 * 129 + 128 * 128
+    got = seen[1020:1020 + 257, 1020:1020 + 257]
+    assert got[want].all(), "missing pairs: %s" % np.argwhere(want & ~got)[:8].tolist()
+    assert not got[~want].any()                                                      # the parity rule itself
+    for x, y in SOBEL_SIGNED:
+        for s, t in ((1, 1), (-1, 1), (1, -1), (-1, -1)):
+            assert seen[1020 + s * x, 1020 + t * y], (s * x, t * y)
+    for e in (SOBEL_EXTREME, -SOBEL_EXTREME):
+        for o in (0, SOBEL_EXTREME // 2, -SOBEL_EXTREME // 2):
+            assert seen[1020 + e, 1020 + o] and seen[1020 + o, 1020 + e], (e, o)
+    assert not (img.astype(np.int32).sum(axis=2) == 0).any()
+    # among the arguments n = sx^2 + sy^2 of the square root.  Equal parity makes n = 0 or 2 (mod 4): an ODD square is never an argument, the
+    # even ones all are, as k^2 + 0^2; every result 0 .. 255 occurs, so both sides of every threshold k^2 do
+    sxs, sys_ = np.nonzero(seen)
+    n = np.unique((sxs - 1020).astype(np.int64) ** 2 + (sys_ - 1020).astype(np.int64) ** 2)
+    assert np.isin(n % 4, (0, 2)).all()
+    for k in range(1, 256):
+        assert (k % 2 == 1 or k * k in n) and ((n >= (k - 1) * (k - 1)) & (n < k * k)).any(), k
+    assert n.max() > 255 * 255                                                       # the clamp
+
+
+def tile_summary_numpy(mask):
+    """the definition of dmath.h ViewParams::msum restated: bool (ceil(h / 32), ceil(w / 32)), [ty, tx] = every mask bit of the pixels
+    [32 tx, 32 tx + 32] x [32 ty, 32 ty + 32] -- 33 x 33 of them, clipped to the image -- is set"""
+    h, w = mask.shape
+    out = np.zeros(((h + 31) // 32, (w + 31) // 32), bool)
+    for ty in range(out.shape[0]):
+        for tx in range(out.shape[1]):
+            out[ty, tx] = bool(np.all(mask[32 * ty:min(32 * ty + 33, h), 32 * tx:min(32 * tx + 33, w)]))
+    return out
+
+
+def pack_mask_words(mask):
+    """bool (h, w) -> uint32 (h, ceil(w / 32)): bit x & 31 of word (y, x >> 5), padding bits zero (the device's layout)"""
+    h, w = mask.shape
+    wpr = (w + 31) // 32
+    bits = np.zeros((h, wpr * 32), np.uint8); bits[:, :w] = mask
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view(np.uint32).reshape(h, wpr)
+
+
+def pack_summary_words(tiles):
+    """bool (th, tw) -> uint32 (th, msum_stride), msum_stride = 2 * ceil(tw / 64): rows padded to a wave's ballot"""
+    th, tw = tiles.shape
+    ms = ((tw + 63) // 64) * 2
+    bits = np.zeros((th, ms * 32), np.uint8); bits[:, :tw] = tiles
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view(np.uint32).reshape(th, ms)
+
+
+def jacobi_flood_steps(rgb, stop_after=None):
+    """(reach bool (h, w), steps): the corner flood fill as WORD-parallel Jacobi steps -- per step a 32-pixel word takes its upper and lower
+    neighbour words, one bit from the word to its left and right, and fills along its own runs of black pixels -- and the number of steps that
+    changed something (stop_after: give up once more than that many did, reach = None).  A restatement in numpy of the schedule, not of the
+    kernel's code: the reach set must equal the oracle's queue fill."""
+    h, w = rgb.shape[:2]
+    wpr = (w + 31) // 32
+    z = np.zeros((h, wpr * 32), bool); z[:, :w] = rgb.astype(np.int32).sum(axis=2) == 0
+    r = np.zeros_like(z)
+    for y, x in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1)): r[y, x] = z[y, x]
+    steps = 0
+    while True:
+        n = r.copy()
+        n[1:] |= r[:-1]; n[:-1] |= r[1:]
+        n[:, 32::32] |= r[:, 31:-1:32]                                               # bit 31 of the word to the left -> bit 0
+        n[:, 31:-1:32] |= r[:, 32::32]                                               # bit 0 of the word to the right -> bit 31
+        n &= z
+        n3 = n.reshape(h, wpr, 32); z3 = z.reshape(h, wpr, 32)
+        for _ in range(31):                                                          # along the runs inside a word, both ways, to the end
+            n3[:, :, 1:] |= n3[:, :, :-1] & z3[:, :, 1:]
+            n3[:, :, :-1] |= n3[:, :, 1:] & z3[:, :, :-1]
+        n = n3.reshape(h, wpr * 32)
+        if np.array_equal(n, r):
+            return r[:, :w], steps
+        r = n; steps += 1
+        if stop_after is not None and steps > stop_after:
+            return None, steps
