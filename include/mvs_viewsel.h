@@ -661,11 +661,22 @@ void mvs_atlas_set_free(mvs_atlas_set* a);
  *   mvs_write_png is that encoder on a host image (rgb [height][width][3]).
  *   params.png_device 1: the atlases are encoded on the device (mvs_ctx_encode_pngs below: per-row filters, run-length matches and a
  *   dynamic Huffman block per 32 KiB chunk) and only the finished files are downloaded; needs no libz; png_level must be 0.  Any other
- *   png_device, or png_device 1 with png_level != 0, is MVS_ERR_INVALID.  stats.ms_png covers whichever route ran. */
+ *   png_device, or png_device 1 with png_level != 0, is MVS_ERR_INVALID.  stats.ms_png covers whichever route ran.
+ *   params.image_format 1: the atlases become baseline JPEGs, encoded on the device (mvs_ctx_encode_jpegs below) with jpeg_quality
+ *   1 .. 100 and jpeg_subsampling 0 (4:4:4) / 1 (4:2:0): the files are `<prefix>_material<a>_map_Kd.jpg` and the `map_Kd` lines of the
+ *   .mtl name them (the one change in the text); png_level and png_device must be 0.  MVS_ERR_INVALID for any other image_format, a
+ *   quality or subsampling outside those values, or a non-zero png_level / png_device beside image_format 1; MVS_ERR_UNSUPPORTED for an
+ *   atlas side above 65535.  With image_format 0 jpeg_quality, jpeg_subsampling and reserved are not read: a zeroed struct is the PNG
+ *   route with stored blocks, as before.  stats.ms_png stays the one field for whichever encoder ran.
+ *   The struct grew from 16 to 32 bytes with image_format: callers compiled against the 16-byte struct must be recompiled. */
 typedef struct mvs_model_params {
     uint64_t max_bytes;       /* refuse an .obj of more bytes than this (0: no cap) */
     int32_t png_level;        /* 0 .. 9 */
     int32_t png_device;       /* 0: the PNGs are encoded on the host (png_level); 1: on the device */
+    int32_t image_format;     /* 0: PNG (default); 1: JPEG */
+    int32_t jpeg_quality;     /* 1 .. 100 (default 90); read under image_format 1 only */
+    int32_t jpeg_subsampling; /* 0: 4:4:4; 1: 4:2:0 (default); read under image_format 1 only */
+    int32_t reserved;
 } mvs_model_params;
 void mvs_model_default_params(mvs_model_params* p);
 typedef struct mvs_model_text {
@@ -723,6 +734,30 @@ mvs_status mvs_encode_png_rle(const uint8_t* rgb, uint32_t width, uint32_t heigh
 mvs_status mvs_deflate_rle(const uint8_t* bytes, uint64_t n, uint8_t** out, uint64_t* out_bytes);
 void mvs_png_free(uint8_t* bytes);
 
+/* The JPEG route of rows f9 and f11 (DESIGN.md section 4 "Model output" item 9 and csrc/jpeg_base.h define the format bit for bit; any
+ * JPEG decoder reads it): baseline sequential, 8 bit, JFIF, YCbCr 4:4:4 (subsampling 0) or 4:2:0 (subsampling 1), Annex K's quantiser
+ * tables scaled by `quality` 1 .. 100, Annex K's Huffman tables, a restart interval of 8 MCUs.  Integer arithmetic throughout: the host
+ * and the device give the same bytes.
+ * mvs_ctx_encode_jpegs: the complete JPEG files of n_images 8-bit RGB images in one call; the arrays, on_device and `out` are those of
+ * mvs_ctx_encode_pngs (mvs_jpeg_set_free releases out).  Every restart segment is coded by one workgroup (csrc/k_jpeg.hip), a second
+ * pass gathers the segments, the host adds the headers.  MVS_ERR_INVALID for an empty frame, arrays that do not agree, a null image with
+ * pixels, a quality outside 1 .. 100 or a subsampling other than 0 / 1; MVS_ERR_UNSUPPORTED for a side above 65535.
+ * mvs_encode_jpeg: the same file on the host, sequentially (rgb [height][width][3]) -- no GPU, no library; malloc'ed (mvs_jpeg_free). */
+typedef struct mvs_jpeg_stats {
+    uint64_t raw_bytes, jpeg_bytes;              /* 3 bytes per pixel; the files */
+    uint64_t segments;                           /* restart segments of all images */
+    uint64_t stuffed_bytes;                      /* 0x00 bytes behind a 0xFF of entropy data */
+    uint64_t marker_bytes;                       /* everything that is not entropy data: SOI .. SOS, the RST markers, EOI */
+    float ms_segment, ms_gather;                 /* device time per pass */
+    float ms_download, ms_frame;                 /* host time: segment table and entropy data to the host; headers and assembly */
+} mvs_jpeg_stats;
+typedef mvs_png_set mvs_jpeg_set;
+mvs_status mvs_ctx_encode_jpegs(mvs_ctx* ctx, uint32_t n_images, const uint32_t* width, const uint32_t* height, const uint64_t* pix_ptr, const uint8_t* image,
+                                int on_device, int32_t quality, int32_t subsampling, mvs_jpeg_set* out, mvs_jpeg_stats* stats);
+void mvs_jpeg_set_free(mvs_jpeg_set* p);
+mvs_status mvs_encode_jpeg(const uint8_t* rgb, uint32_t width, uint32_t height, int32_t quality, int32_t subsampling, uint8_t** out, uint64_t* out_bytes);
+void mvs_jpeg_free(uint8_t* bytes);
+
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
  * the view list -- stamped all over with its three-digit id in cells of 13 x 6 pixels, and rows f6 (without adjust_colors), f8 and f9
@@ -741,7 +776,8 @@ void mvs_png_free(uint8_t* bytes);
  *     degenerate_faces = 0, ms_mark = 0, ms_resolve = the pixel kernel.  params.max_pixels and the errors are row f6's.  With
  *     out_on_device the arrays are the context's row-f6 buffers (valid until its next texture_patches or debug_patches call).
  *   mvs_ctx_view_selection_model: debug patches, row f8, row f9's save_model with everything left on the device in between: writes
- *     `<prefix>_view_selection.obj`, `.mtl` and `<prefix>_view_selection_material<a>_map_Kd.png`.  Any params / stats may be NULL. */
+ *     `<prefix>_view_selection.obj`, `.mtl` and `<prefix>_view_selection_material<a>_map_Kd.png` (`.jpg` under model_params.image_format 1: the parameters reach
+ *     mvs_ctx_save_model unchanged).  Any params / stats may be NULL. */
 mvs_status mvs_debug_view_style(uint32_t position, uint8_t bg[3], uint8_t fg[3]);
 mvs_status mvs_ctx_debug_embeddings(mvs_ctx* ctx, uint32_t n, const int32_t* width, const int32_t* height, const uint32_t* view_ids,
                                     uint32_t first_position, uint8_t* rgb_out, int out_on_device);
@@ -759,7 +795,8 @@ mvs_status mvs_ctx_view_selection_model(mvs_ctx* ctx, const uint32_t* adj_ptr, c
  * and every byte is the same on any device and in every run.  A glTF vertex carries one index for position and texture coordinate
  * together, so the distinct pairs (global coordinate g, mesh vertex v) among the 3 n_listed corners are the vertices: they are numbered
  * in ascending (g, v), which leaves every atlas one contiguous range, and atlas a with faces becomes one primitive (material a, its
- * image the PNG that mvs_ctx_save_model writes for the same params, embedded) whose indices count from the start of its range.
+ * image the PNG -- or, under params.image_format 1, the JPEG with "mimeType": "image/jpeg" -- that mvs_ctx_save_model writes for the
+ * same params, embedded) whose indices count from the start of its range.
  * POSITION, TEXCOORD_0 (texcoords_merged as it is: its origin is glTF's) and NORMAL (when vertex_normals is given) are the inputs' bits,
  * not rounded text.  Unlike the .obj the file holds only referenced vertices; faces of label 0 are in no atlas and so in no primitive.
  * An atlas set without atlas_size or image gives a file without images, textures and samplers.
@@ -767,7 +804,7 @@ mvs_status mvs_ctx_view_selection_model(mvs_ctx* ctx, const uint32_t* adj_ptr, c
  *   a refusal leaves `path` untouched (nothing is opened before the last check), a write error removes what was written.  Running out
  *   of host memory is MVS_ERR_INVALID ("out of host memory"), as in every other row.
  * Refusals: those of mvs_ctx_build_model (MVS_ERR_STATE without a mesh; MVS_ERR_INVALID for a bad face id, texcoord id, face_ptr or
- * tc_ptr) and, for the PNGs, of mvs_ctx_save_model (png_level, png_device, libz); MVS_ERR_INVALID as well for a mesh face that names a
+ * tc_ptr) and, for the images, of mvs_ctx_save_model (png_level, png_device, libz, image_format and the JPEG parameters); MVS_ERR_INVALID as well for a mesh face that names a
  * vertex >= n_verts.  MVS_ERR_UNSUPPORTED for a position or normal of a referenced vertex that is not finite (JSON has no inf or nan;
  * counted in stats.nonfinite_values per component of every glTF vertex) and for a file of 2^32 - 1 bytes or more or above
  * params.max_bytes (0 = no cap): checked on headers + geometry after the numbering pass, before the attribute buffers are allocated,

@@ -142,6 +142,7 @@ struct ModelDev; // row f9 (k_model.hip)
 struct DebugDev; // row f10 (k_debug.hip)
 struct GlbDev;   // row f11 (k_glb.hip)
 struct PngDev;   // row f9's compressed PNGs (k_png.hip)
+struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -272,6 +273,7 @@ struct mvs_ctx {
     mvs::DebugDev* debug = nullptr;   // row f10 (k_debug.hip)
     mvs::GlbDev* glb = nullptr;       // row f11 (k_glb.hip)
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
+    mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -407,8 +409,9 @@ void model_release(mvs_ctx* ctx);
 //   model_check_set: the host-side rules of "Model output" item 6 -- throws MVS_ERR_STATE without a mesh, MVS_ERR_INVALID for a null array or
 //     a face_ptr / tc_ptr that does not run from 0 to the totals or descends; leaves both arrays ([n_atlases + 1]) on the host
 //   model_refuse_bad_ids: MVS_ERR_INVALID for the counts the device pass made of model_corner.h's two id rules
-//   model_check_png_params: png_level / png_device and the arrays the PNGs need, as mvs_ctx_save_model refuses them
-//   model_for_each_png: the PNG file of every atlas by the route params chooses (png_io.h on up to 16 host threads, or k_png.hip), handed to
+//   model_check_png_params: image_format, png_level / png_device or jpeg_quality / jpeg_subsampling and the arrays the images need, as
+//     mvs_ctx_save_model refuses them
+//   model_for_each_png: the image file of every atlas by the route params chooses (png_io.h on up to 16 host threads, k_png.hip or k_jpeg.hip), handed to
 //     `sink` (atlas, bytes, count, message) on the thread that holds it; the bytes are valid during the call only
 //   device_to_stream: a device range into an open file through the context's pinned buffer, 32 MB at a time (false: write error);
 //     ms_copy: the time spent waiting for the copies
@@ -435,6 +438,11 @@ struct PngFiles {
 };
 void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
                        PngFiles& out, mvs_png_stats& st);
+// k_jpeg.hip: the same for the JPEG route (mvs_ctx_encode_jpegs after its checks; quality and subsampling already checked by
+// jpeg_base.h's check_params); a side above 65535 throws MVS_ERR_UNSUPPORTED
+void jpeg_release(mvs_ctx* ctx);
+void jpeg_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
+                        int quality, int subsampling, PngFiles& out, mvs_jpeg_stats& st);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

@@ -332,7 +332,7 @@ void run_glb(mvs_ctx* ctx, GlbDev& D, const mvs_atlas_set& in, int on_device, co
         j += "\"textures\":[";
         for (uint32_t a = 0; a < A; ++a) j += std::string(a ? "," : "") + "{\"sampler\":0,\"source\":" + num(a) + "}";
         j += "],\"images\":[";
-        for (uint32_t a = 0; a < A; ++a) j += std::string(a ? "," : "") + "{\"bufferView\":" + num(v0 + a) + ",\"mimeType\":\"image/png\"}";
+        for (uint32_t a = 0; a < A; ++a) j += std::string(a ? "," : "") + "{\"bufferView\":" + num(v0 + a) + (P.image_format == 1 ? ",\"mimeType\":\"image/jpeg\"}" : ",\"mimeType\":\"image/png\"}");
         j += "],\"samplers\":[{\"magFilter\":9729,\"minFilter\":9729,\"wrapS\":33071,\"wrapT\":33071}],";
     }
     if (G.bin_bytes) {

@@ -1,6 +1,7 @@
 // k_model.hip -- row f9: tex::build_model + ObjModel::save + MaterialLib::save_to_files (DESIGN.md section 4 "Model output"): the text of
 // the .obj and the .mtl formatted on the device, byte for byte what upstream's writers produce; the files written on the host, the atlas
-// PNGs encoded there too (png_io.h; params.png_device 0) or on the device (k_png.hip; params.png_device 1).  Three phases on the context's stream:
+// PNGs encoded there too (png_io.h; params.png_device 0) or on the device (k_png.hip; params.png_device 1), or JPEGs from the device (k_jpeg.hip;
+// params.image_format 1: the `.jpg` in the .mtl's map_Kd lines is the one change in the text).  Three phases on the context's stream:
 //   measure  one thread per line computes its length (fmt6.h), checks its indices and counts the floats of the wide route
 //   scan     64-bit exclusive scan of the lengths (rocprim through rows.h); the section offsets are gathered from it
 //   write    a block's 256 lines are contiguous in the file: thread = line formats into an LDS staging buffer laid out like the file from
@@ -11,6 +12,7 @@
 #include "rows.h"
 #include "fmt6.h"
 #include "png_io.h"
+#include "jpeg_base.h"
 #include "model_corner.h"
 
 #include <atomic>
@@ -99,12 +101,12 @@ struct ObjSource {
 
 // ---- the "lines" of the .mtl: material a's record (material_lib.cpp:31-38) ----
 struct MtlSource {
-    const char* name; uint32_t name_len;
+    const char* name; uint32_t name_len; uint32_t jpeg;   // jpeg: params.image_format 1, the one thing that changes the text
     template <class Sink>
     __device__ void emit(uint32_t a, Sink& k, uint32_t*) const {
         k.str("newmtl material", 15); k.filled4(a);
         k.str("\nKa 1.000000 1.000000 1.000000\nKd 1.000000 1.000000 1.000000\nKs 0.000000 0.000000 0.000000\nTr 0.000000\nillum 1\nNs 1.000000\nmap_Kd ", 130);
-        k.str(name, name_len); k.str("_material", 9); k.filled4(a); k.str("_map_Kd.png\n", 12);
+        k.str(name, name_len); k.str("_material", 9); k.filled4(a); k.str(jpeg ? "_map_Kd.jpg\n" : "_map_Kd.png\n", 12);
     }
 };
 
@@ -184,7 +186,7 @@ void run_model(mvs_ctx* ctx, ModelDev& D, const mvs_atlas_set& in, int on_device
     S.merged = stage(D.in_merged, (const float*)in.texcoords_merged, 2 * (size_t)NM, on_device, s);
     S.tc_ptr = A ? stage(D.in_tc_ptr, (const uint32_t*)in.tc_ptr, (size_t)A + 1, on_device, s) : nullptr;
     S.normals = normals ? stage(D.in_normals, normals, 3 * (size_t)NV, normals_on_device, s) : nullptr;
-    MtlSource M{D.name.p, (uint32_t)name.size()};
+    MtlSource M{D.name.p, (uint32_t)name.size(), P.image_format == 1 ? 1u : 0u};
     MVS_HIP(hipStreamSynchronize(s));   // host buffers are borrowed for the call only (h_sec and name are this function's)
     D.len.ensure((size_t)n + 1); D.off.ensure((size_t)n + 1); D.mlen.ensure((size_t)A + 1); D.moff.ensure((size_t)A + 1); D.sec_bytes.ensure(NS); D.c64.ensure(K_N);
     StageTimer<5> tm(s);
@@ -292,6 +294,12 @@ void model_refuse_bad_ids(uint64_t bad_faces, uint64_t bad_ids, const char* who)
 
 void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who) {
     const std::string w = std::string(who) + ": ";
+    if (P.image_format != 0 && P.image_format != 1) throw StatusError(MVS_ERR_INVALID, w + "image_format 0 (PNG) or 1 (JPEG)");
+    if (P.image_format == 1) {
+        std::string msg;
+        if (P.png_level != 0 || P.png_device != 0) throw StatusError(MVS_ERR_INVALID, w + "image_format 1 takes png_level 0 and png_device 0");
+        if (jpeg_base::check_params(P.jpeg_quality, P.jpeg_subsampling, msg) != MVS_OK) throw StatusError(MVS_ERR_INVALID, w + msg);
+    }
     if (P.png_level < 0 || P.png_level > 9) throw StatusError(MVS_ERR_INVALID, w + "png_level 0 .. 9");
     if (P.png_device != 0 && P.png_device != 1) throw StatusError(MVS_ERR_INVALID, w + "png_device 0 or 1");
     if (P.png_device == 1 && P.png_level != 0) throw StatusError(MVS_ERR_INVALID, w + "png_device 1 takes png_level 0");
@@ -311,7 +319,7 @@ void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_de
         if (atlases_on_device) {
             MVS_HIP(hipMemcpyAsync(size.data(), in.atlas_size, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             MVS_HIP(hipMemcpyAsync(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            if (!P.png_device) {
+            if (!P.png_device && P.image_format != 1) {
                 own.resize(3 * (size_t)in.n_pixels + 1);
                 if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
                 image = own.data();
@@ -324,14 +332,16 @@ void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_de
     if (pix[0] != 0 || pix[A] != in.n_pixels) throw StatusError(MVS_ERR_INVALID, w + "atlas_pix_ptr does not run from 0 to n_pixels");
     for (uint32_t a = 0; a < A; ++a)
         if (!size[a] || pix[a + 1] < pix[a] || pix[a + 1] - pix[a] != (uint64_t)size[a] * size[a]) throw StatusError(MVS_ERR_INVALID, w + "atlas " + std::to_string(a) + ": size and atlas_pix_ptr do not agree");
-    PngFiles files;   // png_device 1: the finished files, encoded on the device
-    if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
+    PngFiles files;   // png_device 1 or image_format 1: the finished files, encoded on the device
+    const bool on_dev = P.png_device || P.image_format == 1;
+    if (P.image_format == 1 && A) { mvs_jpeg_stats jst{}; jpeg_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, P.jpeg_quality, P.jpeg_subsampling, files, jst); }
+    else if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
     std::atomic<uint32_t> next{0}; std::atomic<int> failed{MVS_OK};
     std::vector<std::string> errs(A);
     auto work = [&] {
         for (uint32_t a = next.fetch_add(1); a < A; a = next.fetch_add(1)) {
             mvs_status r;
-            if (P.png_device) r = sink(a, files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a]);
+            if (on_dev) r = sink(a, files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a]);
             else {
                 std::vector<uint8_t> png;
                 r = encode_png(image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, png, errs[a]);
@@ -357,6 +367,7 @@ extern "C" {
 void mvs_model_default_params(mvs_model_params* p) {
     if (!p) return;
     p->max_bytes = 0; p->png_level = 0; p->png_device = 0;
+    p->image_format = 0; p->jpeg_quality = 90; p->jpeg_subsampling = 1; p->reserved = 0;
 }
 
 mvs_status mvs_ctx_build_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
@@ -421,7 +432,7 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
             const double t1 = now_ms_host();
             try {
                 model_for_each_png(ctx, in, atlases_on_device, P, "save_model", [&](uint32_t a, const uint8_t* bytes, size_t n, std::string& err) {
-                    return write_file((pre + "_material" + model_filled4(a) + "_map_Kd.png").c_str(), bytes, n, err);
+                    return write_file((pre + "_material" + model_filled4(a) + (P.image_format == 1 ? "_map_Kd.jpg" : "_map_Kd.png")).c_str(), bytes, n, err);
                 });
             } catch (...) { st.ms_png = (float)(now_ms_host() - t1); throw; }
             st.ms_png = (float)(now_ms_host() - t1);

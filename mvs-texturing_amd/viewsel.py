@@ -154,7 +154,8 @@ class AtlasStats(C.Structure):
 
 
 class ModelParams(C.Structure):
-    _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("png_device", C.c_int32)]
+    _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("png_device", C.c_int32),
+                ("image_format", C.c_int32), ("jpeg_quality", C.c_int32), ("jpeg_subsampling", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ModelText(C.Structure):
@@ -195,6 +196,15 @@ PNG_MS = ("ms_filter", "ms_chunk", "ms_gather", "ms_download", "ms_frame")
 
 class PngStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PNG_COUNTS] + [("filter_rows", C.c_uint64 * 5)] + [(k, C.c_float) for k in PNG_MS] + [("reserved", C.c_float)]
+
+
+JPEG_COUNTS = ("raw_bytes", "jpeg_bytes", "segments", "stuffed_bytes", "marker_bytes")
+JPEG_MS = ("ms_segment", "ms_gather", "ms_download", "ms_frame")
+IMAGE_FORMATS = {"png": 0, "jpeg": 1}
+
+
+class JpegStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in JPEG_COUNTS] + [(k, C.c_float) for k in JPEG_MS]
 
 
 class PngSet(C.Structure):
@@ -312,6 +322,8 @@ def load_library():
         "mvs_ctx_save_glb": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(GlbStats)], "mvs_glb_free": [C.POINTER(Glb)],
         "mvs_ctx_encode_pngs": [vp, u32, vp, vp, vp, vp, i32, C.POINTER(PngSet), C.POINTER(PngStats)], "mvs_png_set_free": [C.POINTER(PngSet)],
         "mvs_ctx_deflate_rle": [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)], "mvs_png_free": [vp],
+        "mvs_ctx_encode_jpegs": [vp, u32, vp, vp, vp, vp, i32, C.c_int32, C.c_int32, C.POINTER(PngSet), C.POINTER(JpegStats)], "mvs_jpeg_set_free": [C.POINTER(PngSet)],
+        "mvs_encode_jpeg": [vp, u32, u32, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(u64)], "mvs_jpeg_free": [vp],
         "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
         "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
         "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
@@ -341,7 +353,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_glb_free", "mvs_png_set_free", "mvs_png_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_glb_free", "mvs_png_set_free", "mvs_png_free", "mvs_jpeg_set_free", "mvs_jpeg_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -934,7 +946,8 @@ class Context:
     def save_model(self, atlases, prefix, vertex_normals=None, params=None):
         """Row f9 to files: `<prefix>.obj`, `<prefix>.mtl` and one `<prefix>_material<a>_map_Kd.png` per atlas (mvs_ctx_save_model; the
         atlas set needs atlas_size, atlas_pix_ptr and image as well).  Returns the stats; params: default_model_params(png_level=...) for
-        the host encoder's level, default_model_params(png_device=1) for the PNGs compressed on the device (encode_pngs)."""
+        the host encoder's level, default_model_params(png_device=1) for the PNGs compressed on the device (encode_pngs),
+        default_model_params(image_format="jpeg", jpeg_quality=..., jpeg_subsampling=...) for `.jpg` files from the device (encode_jpegs)."""
         ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
         st = ModelStats()
         self._keep["model"] = held
@@ -969,10 +982,9 @@ class Context:
         _check_with_stats(self.L, rc, stats)
         return stats
 
-    def encode_pngs(self, images):
-        """The compressed PNG route of row f9 on its own (mvs_ctx_encode_pngs; DESIGN.md section 4 "Model output" item 7): `images` is a
-        list of (H, W, 3) uint8 arrays -- all numpy or all CUDA tensors -- or an atlas-set dict (atlas_size, atlas_pix_ptr, image: all
-        host or all device).  One call encodes them all.  Returns (list of bytes, one PNG file per image; stats)."""
+    @staticmethod
+    def _image_set(images):
+        """the arrays encode_pngs and encode_jpegs share: (n, width, height, pix, img, on_device)"""
         if isinstance(images, dict):
             held = _atlas_set_struct({k: images[k] for k in ("atlas_size", "atlas_pix_ptr", "image")})[1]
             size, pix, img = held["atlas_size"], held["atlas_pix_ptr"], held["image"]
@@ -995,6 +1007,13 @@ class Context:
             width = np.array([a.shape[1] for a in arrs], np.uint32); height = np.array([a.shape[0] for a in arrs], np.uint32)
             pix = np.concatenate([[0], np.cumsum([a.shape[0] * a.shape[1] for a in arrs])]).astype(np.uint64)
             img = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.uint8)
+        return n, width, height, pix, img, dev
+
+    def encode_pngs(self, images):
+        """The compressed PNG route of row f9 on its own (mvs_ctx_encode_pngs; DESIGN.md section 4 "Model output" item 7): `images` is a
+        list of (H, W, 3) uint8 arrays -- all numpy or all CUDA tensors -- or an atlas-set dict (atlas_size, atlas_pix_ptr, image: all
+        host or all device).  One call encodes them all.  Returns (list of bytes, one PNG file per image; stats)."""
+        n, width, height, pix, img, dev = self._image_set(images)
         res, st = PngSet(), PngStats()
         self._keep["png"] = (width, height, pix, img)
         n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
@@ -1004,6 +1023,24 @@ class Context:
         off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
         data = C.string_at(res.data, res.n_bytes)
         self.L.mvs_png_set_free(C.byref(res))
+        return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
+
+    def encode_jpegs(self, images, quality=90, subsampling=1):
+        """The JPEG route of rows f9 / f11 on its own (mvs_ctx_encode_jpegs; DESIGN.md section 4 "Model output" item 9): `images` as
+        encode_pngs takes them, quality 1 .. 100, subsampling 0 (4:4:4) or 1 (4:2:0).  One call encodes them all.  Returns (list of
+        bytes, one baseline JPEG file per image; stats).  The same bytes as the host twin encode_jpeg gives."""
+        n, width, height, pix, img, dev = self._image_set(images)
+        res, st = PngSet(), JpegStats()
+        self._keep["jpeg"] = (width, height, pix, img)
+        n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
+        rc = self.L.mvs_ctx_encode_jpegs(self.h, n, _ptr(width)[0], _ptr(height)[0], _ptr(pix)[0], _ptr(img)[0] if n_pix else None, dev, int(quality), int(subsampling),
+                                         C.byref(res), C.byref(st))
+        stats = {k: int(getattr(st, k)) for k in JPEG_COUNTS}
+        stats.update({k: float(getattr(st, k)) for k in JPEG_MS})
+        _check_with_stats(self.L, rc, stats)
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        data = C.string_at(res.data, res.n_bytes)
+        self.L.mvs_jpeg_set_free(C.byref(res))
         return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
 
     def deflate_rle(self, data):
@@ -1112,7 +1149,12 @@ def default_atlas_params(**kw):
 
 
 def default_model_params(**kw):
-    """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks, png_device 0 = PNGs encoded on the host) with overrides"""
+    """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks, png_device 0 = PNGs encoded on the host,
+    image_format 0 = PNG, jpeg_quality 90, jpeg_subsampling 1 = 4:2:0) with overrides; image_format: "png" | "jpeg" | 0 | 1"""
+    if isinstance(kw.get("image_format"), str):
+        if kw["image_format"] not in IMAGE_FORMATS:
+            raise ValueError("default_model_params: image_format must be \"png\" or \"jpeg\", not %r" % (kw["image_format"],))
+        kw = dict(kw, image_format=IMAGE_FORMATS[kw["image_format"]])
     return _default_params(ModelParams, "mvs_model_default_params", kw)
 
 
@@ -1176,6 +1218,19 @@ def encode_png_rle(img):
     out, nb = C.c_void_p(), C.c_uint64()
     _check(L, L.mvs_encode_png_rle(img.ctypes.data, img.shape[1], img.shape[0], C.byref(out), C.byref(nb)))
     return _take_bytes(L, out, nb)
+
+
+def encode_jpeg(img, quality=90, subsampling=1):
+    """mvs_encode_jpeg: the baseline JPEG file (bytes) of an (H, W, 3) uint8 host image by the host twin of the JPEG route -- no GPU, no
+    library; the same bytes as Context.encode_jpegs gives"""
+    L = load_library()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3
+    out, nb = C.c_void_p(), C.c_uint64()
+    _check(L, L.mvs_encode_jpeg(img.ctypes.data, img.shape[1], img.shape[0], int(quality), int(subsampling), C.byref(out), C.byref(nb)))
+    z = C.string_at(out, nb.value)
+    L.mvs_jpeg_free(out)
+    return z
 
 
 def deflate_rle(data):
