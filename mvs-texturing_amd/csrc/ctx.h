@@ -265,8 +265,9 @@ struct mvs_ctx {
     // ---- row f3: patch components (k_patch.hip) ----
     mvs::DBuf<uint32_t> p_label_ptr, p_comp_ptr, p_comp_faces, p_parent, p_root, p_state, p_flag, p_pos, p_roots, p_roots2, p_rlab, p_rlab2, p_adj_ptr, p_adj, p_labels;
 
-    // ---- rows f5 - f8 (k_seam.hip, k_texpatch.hip, k_localseam.hip, k_atlas.hip): per-row buffers allocated on first use; the caller's adjacency
-    // and labels where they arrive as host arrays and the pinned read-back of a patch set's frames are shared (rows.h stage_graph, read_patch_set) ----
+    // ---- rows f5 - f11 and the image routes: per-row buffers allocated on first use (rows.h row_dev); the caller's adjacency and labels where they
+    // arrive as host arrays and the pinned read-back of a patch set's frames and of an image route's bytes are shared (rows.h stage_graph,
+    // read_patch_set; image_routes.h pack_slots) ----
     mvs::DBuf<uint32_t> row_adj_ptr, row_adj, row_labels; mvs::HBuf<char> row_pin;
     mvs::GslDev* gsl = nullptr; mvs::TexPatchDev* texpatch = nullptr; mvs::LslDev* lsl = nullptr; mvs::AtlasDev* atlas = nullptr;
     mvs::ModelDev* model = nullptr;   // row f9 (k_model.hip)
@@ -409,40 +410,26 @@ void model_release(mvs_ctx* ctx);
 //   model_check_set: the host-side rules of "Model output" item 6 -- throws MVS_ERR_STATE without a mesh, MVS_ERR_INVALID for a null array or
 //     a face_ptr / tc_ptr that does not run from 0 to the totals or descends; leaves both arrays ([n_atlases + 1]) on the host
 //   model_refuse_bad_ids: MVS_ERR_INVALID for the counts the device pass made of model_corner.h's two id rules
-//   model_check_png_params: image_format, png_level / png_device or jpeg_quality / jpeg_subsampling and the arrays the images need, as
+//   model_check_image_params: image_format, png_level / png_device or jpeg_quality / jpeg_subsampling and the arrays the images need, as
 //     mvs_ctx_save_model refuses them
-//   model_for_each_png: the image file of every atlas by the route params chooses (png_io.h on up to 16 host threads, k_png.hip or k_jpeg.hip), handed to
-//     `sink` (atlas, bytes, count, message) on the thread that holds it; the bytes are valid during the call only
+//   model_for_each_image: the image file (PNG or JPEG) of every atlas by the route params chooses (png_io.h on up to 16 host threads, k_png.hip or
+//     k_jpeg.hip), handed to `sink` (atlas, bytes, count, message) on the thread that holds it; the bytes are valid during the call only
 //   device_to_stream: a device range into an open file through the context's pinned buffer, 32 MB at a time (false: write error);
 //     ms_copy: the time spent waiting for the copies
 void model_check_set(mvs_ctx* ctx, const mvs_atlas_set& in, int on_device, const char* who, std::vector<uint32_t>& face_ptr, std::vector<uint32_t>& tc_ptr);
 void model_refuse_bad_ids(uint64_t bad_faces, uint64_t bad_ids, const char* who);
-void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who);
-typedef std::function<mvs_status(uint32_t, const uint8_t*, size_t, std::string&)> ModelPngSink;
-void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelPngSink& sink);
+void model_check_image_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who);
+typedef std::function<mvs_status(uint32_t, const uint8_t*, size_t, std::string&)> ModelImageSink;
+void model_for_each_image(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelImageSink& sink);
 bool device_to_stream(mvs_ctx* ctx, const char* d, uint64_t bytes, FILE* f, double& ms_copy);
 std::string model_filled4(uint32_t a);   // util::string::get_filled(a, 4)
 // frees the buffers of row f11 (k_glb.hip)
 void glb_release(mvs_ctx* ctx);
 // frees the buffers of row f10 (k_debug.hip)
 void debug_release(mvs_ctx* ctx);
-// k_png.hip: frees its buffers; the PNG files of n images encoded on the device (mvs_ctx_encode_pngs after its checks: width, height [n] and
-// pix [n + 1] are host arrays that agree, image is 3 bytes per pixel on the host or the device) -- file i is data[offsets[i], offsets[i + 1])
+// k_png.hip, k_jpeg.hip: free their buffers (the routes themselves: image_routes.h)
 void png_release(mvs_ctx* ctx);
-struct PngFiles {
-    uint8_t* data = nullptr; std::vector<uint64_t> offsets;
-    PngFiles() = default;
-    PngFiles(const PngFiles&) = delete;
-    PngFiles& operator=(const PngFiles&) = delete;
-    ~PngFiles() { free(data); }
-};
-void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
-                       PngFiles& out, mvs_png_stats& st);
-// k_jpeg.hip: the same for the JPEG route (mvs_ctx_encode_jpegs after its checks; quality and subsampling already checked by
-// jpeg_base.h's check_params); a side above 65535 throws MVS_ERR_UNSUPPORTED
 void jpeg_release(mvs_ctx* ctx);
-void jpeg_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
-                        int quality, int subsampling, PngFiles& out, mvs_jpeg_stats& st);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

@@ -12,7 +12,6 @@
 #include "rows.h"
 #include "tone.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <numeric>
 
@@ -38,7 +37,6 @@ namespace {
 constexpr uint32_t MAX_SIZE = 8192, PREF_SIZE = 4096, MIN_SIZE = 256;
 constexpr uint32_t CHUNK = 1024;          // pixels of one patch a compose block handles
 enum { K_VALID = 0, K_PADDED, K_BAD_TC, K_N };           // 64-bit counters
-inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- pack (on the host: profiles/EXPERIMENTS.md "Row f8: the packer") ----
 struct HostPack { std::vector<uint32_t> atlas, seq, size; std::vector<int2> pos; uint32_t peak = 0; };
@@ -415,8 +413,7 @@ mvs_status mvs_ctx_texture_atlases(mvs_ctx* ctx, const mvs_patch_set* patches, i
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->atlas) ctx->atlas = new AtlasDev();
-        AtlasDev& D = *ctx->atlas;
+        AtlasDev& D = row_dev(ctx->atlas);
         mvs_atlas_params P;
         if (params) P = *params; else mvs_atlas_default_params(&P);
         tone_mode(P.tone_mapping, "texture_atlases");

@@ -164,8 +164,7 @@ __global__ void __launch_bounds__(256) debug_patch_kernel(const float* __restric
 }
 
 DebugDev& debug_dev(mvs_ctx* ctx) {
-    if (!ctx->debug) ctx->debug = new DebugDev();
-    DebugDev& G = *ctx->debug;
+    DebugDev& G = row_dev(ctx->debug);
     if (!G.style_set) {   // the table is data: built on the host (debug_embed.h), uploaded once per context
         uint32_t h_style[DEBUG_COLOURS];
         debug_style_table(h_style);
@@ -252,8 +251,7 @@ mvs_status mvs_ctx_debug_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const ui
         std::vector<int32_t> w(V), h(V);
         for (uint32_t v = 0; v < V; ++v) { w[v] = ctx->h_views[v].width; h[v] = ctx->h_views[v].height; }
         const std::vector<DebugView> hv = debug_headers(V, w.data(), h.data(), view_ids, 0, "debug_patches");
-        if (!ctx->texpatch) ctx->texpatch = new TexPatchDev();
-        TexPatchDev& D = *ctx->texpatch;
+        TexPatchDev& D = row_dev(ctx->texpatch);
         DebugDev& G = debug_dev(ctx);
         mvs_patch_params P;
         if (params) P = *params; else mvs_patch_default_params(&P);

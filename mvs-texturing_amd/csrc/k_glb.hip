@@ -10,12 +10,10 @@
 //            stores (the at most 3 dwords in front of and behind a block's aligned part go out singly); POSITION's bounds per atlas on the
 //            order-preserving integer image of the floats: wave shuffles, LDS across the waves, then integer atomicMin / atomicMax --
 //            6 per block whose pairs share an atlas, per lane in the few blocks that straddle a range's end.  No float atomics anywhere.
-// The JSON chunk (O(n_atlases)) is formatted on the host; the PNGs are save_model's (k_model.hip model_for_each_png).
+// The JSON chunk (O(n_atlases)) is formatted on the host; the PNGs are save_model's (k_model.hip model_for_each_image).
 #include "rows.h"
 #include "png_io.h"
 #include "model_corner.h"
-
-#include <chrono>
 
 namespace mvs {
 
@@ -30,7 +28,6 @@ void glb_release(mvs_ctx* ctx) { delete ctx->glb; ctx->glb = nullptr; }
 namespace {
 typedef unsigned long long u64;
 enum { K_BAD_FACE = 0, K_BAD_ID, K_BAD_VERT, K_NONFINITE, K_N };   // 64-bit counters
-inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // the order-preserving integer image of a float's bits: -nan < -inf < ... < -0 < +0 < ... < +inf < +nan as unsigned integers
 __host__ __device__ inline uint32_t order_image(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
@@ -186,7 +183,7 @@ void run_glb(mvs_ctx* ctx, GlbDev& D, const mvs_atlas_set& in, int on_device, co
     std::vector<uint32_t> hf, ht;
     model_check_set(ctx, in, on_device, who, hf, ht);
     const bool images = A && in.atlas_size && in.image;   // a text-only set has neither
-    if (images) model_check_png_params(P, in, who);
+    if (images) model_check_image_params(P, in, who);
     st.indices = 3ull * L;
     for (uint32_t a = 0; a < A; ++a) st.primitives += hf[a + 1] > hf[a] ? 1u : 0u;
     refuse_size(28ull + 12ull * L, mvs_model_params{0, 0, 0}, who);   // the format's own limit on the indices alone (so 3 L < 2^30 below); max_bytes waits for the numbering
@@ -272,7 +269,7 @@ void run_glb(mvs_ctx* ctx, GlbDev& D, const mvs_atlas_set& in, int on_device, co
     G.png_at.clear(); G.png.clear();
     if (images) {
         G.png.resize(A);
-        model_for_each_png(ctx, in, on_device, P, who, [&](uint32_t a, const uint8_t* bytes, size_t n, std::string&) { G.png[a].assign(bytes, bytes + n); return MVS_OK; });
+        model_for_each_image(ctx, in, on_device, P, who, [&](uint32_t a, const uint8_t* bytes, size_t n, std::string&) { G.png[a].assign(bytes, bytes + n); return MVS_OK; });
     }
     st.ms_png = (float)(now_ms_host() - t_png);
     uint64_t at = G.geometry_bytes;
@@ -373,12 +370,6 @@ std::vector<uint8_t> glb_front(const GlbParts& G) {
     return h;
 }
 
-mvs_model_params params_or_default(const mvs_model_params* params) {
-    mvs_model_params P;
-    if (params) P = *params; else mvs_model_default_params(&P);
-    return P;
-}
-
 }  // namespace
 }  // namespace mvs
 
@@ -395,8 +386,7 @@ mvs_status mvs_ctx_build_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atl
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->glb) ctx->glb = new GlbDev();
-        GlbDev& D = *ctx->glb;
+        GlbDev& D = row_dev(ctx->glb);
         const mvs_model_params P = params_or_default(params);
         run_with_stats(s, stats, st, [&] {
             GlbParts G;
@@ -431,8 +421,7 @@ mvs_status mvs_ctx_save_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atla
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->glb) ctx->glb = new GlbDev();
-        GlbDev& D = *ctx->glb;
+        GlbDev& D = row_dev(ctx->glb);
         const mvs_model_params P = params_or_default(params);
         run_with_stats(s, stats, st, [&] {
             GlbParts G;

@@ -13,10 +13,8 @@
 //            back.  SOI .. SOS and EOI are written on the host (jpeg_base.h's header()).
 // Slots are sized by the worst case of R (segment_worst_bytes: 19 970 bytes at 4:2:0, 9 986 at 4:4:4, rounded up to 16): config 3's 88
 // atlases are 15 968 segments at 4:2:0, 319 MB of slots for 98 MB of pixels (4:4:4: 63 872 segments, 639 MB) -- a measuring launch would run the whole transform twice.
-#include "rows.h"
+#include "image_routes.h"
 #include "jpeg_base.h"
-
-#include <chrono>
 
 namespace mvs {
 
@@ -42,7 +40,6 @@ constexpr uint32_t STUFFED_MAX = MAX_BLOCKS * BLOCK_BYTES * 2 + 2;        // 199
 static_assert((STUFFED_MAX + 15) / 16 * 16 <= WORK_BYTES, "the stuffed bytes reuse the pixels' and coefficients' LDS");
 static_assert(STUFFED_MAX == R * MAX_MCU_BLOCKS * BLOCK_BYTES * 2 + 2, "segment_worst_bytes(1)");
 inline uint32_t slot_bytes(uint32_t sub) { return (segment_worst_bytes(sub) + 15u) / 16u * 16u; }
-inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct SegLds {
     alignas(16) uint8_t work[WORK_BYTES];   // pixels | samples | pass 1 | coefficients; later the stuffed bytes
@@ -54,13 +51,6 @@ struct SegLds {
     uint32_t total_bits;
 };
 static_assert(sizeof(SegLds) <= 40 * 1024, "four workgroups per CU in 160 KiB of LDS");
-
-// ptr [K + 1] ascending from 0: the k with ptr[k] <= i < ptr[k + 1]
-__device__ uint32_t owner_of(const uint32_t* __restrict__ ptr, uint32_t K, uint32_t i) {
-    uint32_t lo = 0, hi = K;
-    while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (ptr[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
 
 struct Segs { const uint32_t* seg_ptr; const uint32_t* width; const uint32_t* height; const u64* pix; uint32_t K, sub, slot; };   // seg_ptr [K + 1]; pix: first pixel
 
@@ -209,34 +199,13 @@ __global__ void __launch_bounds__(THREADS) jpeg_segment_kernel(Segs S, const uin
     if (tid == 0u) { sizes[c] = bytes; if (all_ff) atomicAdd(stuffed, (u64)all_ff); }
 }
 
-// ---- gather pass: off [segments + 1] = the scan of the sizes ----
-__global__ void __launch_bounds__(THREADS) jpeg_gather_kernel(uint32_t slot, const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes, const u64* __restrict__ off,
-                                                              uint8_t* __restrict__ out) {
-    const uint32_t c = blockIdx.x, nb = sizes[c];
-    const uint8_t* src = slots + (u64)c * slot;
-    uint8_t* dst = out + off[c];
-    const uint32_t lead = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u), head = lead < nb ? lead : nb;   // bytes up to dst's first 16-byte boundary
-    for (uint32_t i = threadIdx.x; i < head; i += THREADS) dst[i] = src[i];
-    const uint32_t words = (nb - head) / 16u;
-    for (uint32_t i = threadIdx.x; i < words; i += THREADS) {
-        uint4 v;
-        uint8_t* b = reinterpret_cast<uint8_t*>(&v);
-        const uint8_t* s = src + head + 16u * i;
-        for (int j = 0; j < 16; ++j) b[j] = s[j];
-        reinterpret_cast<uint4*>(dst + head)[i] = v;
-    }
-    for (uint32_t i = head + 16u * words + threadIdx.x; i < nb; i += THREADS) dst[i] = src[i];
-}
-
-JpegDev& jpeg_dev(mvs_ctx* ctx) { if (!ctx->jpeg) ctx->jpeg = new JpegDev(); return *ctx->jpeg; }
-
 }  // namespace
 
 // width, height [n], pix [n + 1]: host arrays, already checked against each other; image: 3 bytes per pixel, host or device
 void jpeg_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
-                        int quality, int subsampling, PngFiles& out, mvs_jpeg_stats& st) {
+                        int quality, int subsampling, EncodedFiles& out, mvs_jpeg_stats& st) {
     hipStream_t s = ctx->stream;
-    JpegDev& D = jpeg_dev(ctx);
+    JpegDev& D = row_dev(ctx->jpeg);
     std::string msg;
     mvs_status rc = check_params(quality, subsampling, msg);
     for (uint32_t k = 0; rc == MVS_OK && k < n; ++k) rc = check_frame(width[k], height[k], msg);
@@ -271,36 +240,15 @@ void jpeg_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const u
         MVS_LAUNCH_CHECK();
     }
     tm.mark();
-    MVS_HIP(hipMemsetAsync(D.sizes.p + NC, 0, sizeof(uint32_t), s));
-    dev_exclusive_scan(ctx, (const uint32_t*)D.sizes.p, D.off.p, (size_t)NC + 1);
-    if (NC) {
-        hipLaunchKernelGGL(jpeg_gather_kernel, dim3(NC), dim3(THREADS), 0, s, slot, (const uint8_t*)D.slots.p, (const uint32_t*)D.sizes.p, (const u64*)D.off.p, D.out.p);
-        MVS_LAUNCH_CHECK();
-    }
-    tm.mark();
-    // ---- the segments' offsets, then the entropy data ----
-    MVS_HIP(hipStreamSynchronize(s));   // (so that ms_download is the copies' time, not the passes')
-    st.ms_segment = tm.ms(0, 1); st.ms_gather = tm.ms(1, 2);
-    const double t0 = now_ms_host();
-    const size_t b_off = ((size_t)NC + 1) * sizeof(u64);
-    ctx->row_pin.ensure(b_off + sizeof(u64) + 16);
-    MVS_HIP(hipMemcpyAsync(ctx->row_pin.p, D.off.p, b_off, hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipMemcpyAsync(ctx->row_pin.p + b_off, D.stuffed.p, sizeof(u64), hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipStreamSynchronize(s));
-    std::vector<u64> h_off((const u64*)ctx->row_pin.p, (const u64*)ctx->row_pin.p + NC + 1);
-    st.stuffed_bytes = *(const u64*)(ctx->row_pin.p + b_off);
-    const uint64_t total = h_off[NC];
-    ctx->row_pin.ensure((size_t)total + 16);
-    if (total) MVS_HIP(hipMemcpyAsync(ctx->row_pin.p, D.out.p, (size_t)total, hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipStreamSynchronize(s));
-    st.ms_download = (float)(now_ms_host() - t0);
+    // ---- gather: the entropy data of all images, back to back ----
+    double ms_copy = 0.0;
+    const std::vector<u64> h_off = pack_slots<0, 0>(ctx, nullptr, n, NC, slot, D.slots.p, D.sizes.p, D.off, D.out.p, D.stuffed.p, &st.stuffed_bytes, sizeof(u64), tm, ms_copy);
+    st.ms_segment = tm.ms(0, 1); st.ms_gather = tm.ms(1, 2); st.ms_download = (float)ms_copy;
     // ---- the files: SOI .. SOS, the image's entropy data, EOI ----
     const double t1 = now_ms_host();
     out.offsets.assign((size_t)n + 1, 0);
     for (uint32_t k = 0; k < n; ++k) out.offsets[k + 1] = out.offsets[k] + HEADER_BYTES + (h_off[h32[k + 1]] - h_off[h32[k]]) + 2u;
-    free(out.data);
-    out.data = (uint8_t*)malloc(std::max<size_t>((size_t)out.offsets[n], 1));
-    if (!out.data) throw StatusError(MVS_ERR_INVALID, "out of host memory");
+    out.resize_data();
     std::vector<uint8_t> head;
     for (uint32_t k = 0; k < n; ++k) {
         head.clear();
@@ -326,34 +274,8 @@ extern "C" {
 mvs_status mvs_ctx_encode_jpegs(mvs_ctx* ctx, uint32_t n_images, const uint32_t* width, const uint32_t* height, const uint64_t* pix_ptr, const uint8_t* image, int on_device,
                                 int32_t quality, int32_t subsampling, mvs_jpeg_set* out, mvs_jpeg_stats* stats) {
     if (!ctx || !out || (n_images && (!width || !height)) || !pix_ptr) return api_fail(MVS_ERR_INVALID, "null argument");
-    *out = mvs_jpeg_set{};
-    mvs_jpeg_stats st{};
-    if (stats) *stats = st;
-    return api_guard([&] {
-        MVS_HIP(hipSetDevice(ctx->device));
-        hipStream_t s = ctx->stream;
-        const uint32_t n = n_images;
-        std::vector<uint32_t> w(n), h(n); std::vector<uint64_t> pix((size_t)n + 1);
-        if (on_device) {
-            if (n) { MVS_HIP(hipMemcpyAsync(w.data(), width, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s)); MVS_HIP(hipMemcpyAsync(h.data(), height, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s)); }
-            MVS_HIP(hipMemcpyAsync(pix.data(), pix_ptr, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            MVS_HIP(hipStreamSynchronize(s));
-        } else {
-            if (n) { memcpy(w.data(), width, n * sizeof(uint32_t)); memcpy(h.data(), height, n * sizeof(uint32_t)); }
-            memcpy(pix.data(), pix_ptr, ((size_t)n + 1) * sizeof(uint64_t));
-        }
-        if (pix[0] != 0) throw StatusError(MVS_ERR_INVALID, "encode_jpegs: pix_ptr does not start at 0");
-        for (uint32_t k = 0; k < n; ++k)
-            if (!w[k] || !h[k] || pix[k + 1] < pix[k] || pix[k + 1] - pix[k] != (uint64_t)w[k] * h[k]) throw StatusError(MVS_ERR_INVALID, "encode_jpegs: image " + std::to_string(k) + ": width, height and pix_ptr do not agree");
-        if (pix[n] && !image) throw StatusError(MVS_ERR_INVALID, "encode_jpegs: null image");
-        run_with_stats(s, stats, st, [&] {
-            PngFiles F;
-            jpeg_encode_images(ctx, n, w.data(), h.data(), pix.data(), image, on_device, quality, subsampling, F, st);
-            out->offsets = (uint64_t*)malloc(((size_t)n + 1) * sizeof(uint64_t));
-            if (!out->offsets) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-            memcpy(out->offsets, F.offsets.data(), ((size_t)n + 1) * sizeof(uint64_t));
-            out->n_images = n; out->n_bytes = F.offsets[n]; out->data = F.data; F.data = nullptr;
-        });
+    return encode_entry(ctx, n_images, width, height, pix_ptr, image, on_device, out, stats, "encode_jpegs", [&](const ImageSet& S, EncodedFiles& F, mvs_jpeg_stats& st) {
+        jpeg_encode_images(ctx, n_images, S.w.data(), S.h.data(), S.pix.data(), image, on_device, quality, subsampling, F, st);
     });
 }
 
@@ -365,13 +287,7 @@ mvs_status mvs_encode_jpeg(const uint8_t* rgb, uint32_t width, uint32_t height, 
     if (!out || !out_bytes) return api_fail(MVS_ERR_INVALID, "null argument");
     *out = nullptr; *out_bytes = 0;
     std::vector<uint8_t> v; std::string msg;
-    const mvs_status st = encode_jpeg(rgb, width, height, quality, subsampling, v, msg);
-    if (st != MVS_OK) return api_fail(st, msg);
-    uint8_t* p = (uint8_t*)malloc(std::max<size_t>(v.size(), 1));
-    if (!p) return api_fail(MVS_ERR_INVALID, "out of host memory");
-    memcpy(p, v.data(), v.size());
-    *out = p; *out_bytes = v.size();
-    return MVS_OK;
+    return twin_out(encode_jpeg(rgb, width, height, quality, subsampling, v, msg), msg, v, out, out_bytes);
 }
 
 }  // extern "C"

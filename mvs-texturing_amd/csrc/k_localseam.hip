@@ -718,8 +718,7 @@ mvs_status mvs_ctx_local_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, co
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->lsl) ctx->lsl = new LslDev();
-        LslDev& D = *ctx->lsl;
+        LslDev& D = row_dev(ctx->lsl);
         mvs_lsl_params P;
         if (params) P = *params; else mvs_lsl_default_params(&P);
         if (P.strip_width > 250) throw StatusError(MVS_ERR_INVALID, "local_seam_leveling: strip_width above 250");

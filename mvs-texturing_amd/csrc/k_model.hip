@@ -9,15 +9,11 @@
 //            first and behind the last full chunk belong to chunks shared with the neighbours and go out as bytes).  A block whose
 //            text exceeds the buffer takes as many passes as it needs, each over the longest run of whole lines that fits.
 // The .mtl goes through the same three kernels with one "line" per material (its eight lines).
-#include "rows.h"
+#include "image_routes.h"
 #include "fmt6.h"
 #include "png_io.h"
 #include "jpeg_base.h"
 #include "model_corner.h"
-
-#include <atomic>
-#include <chrono>
-#include <thread>
 
 namespace mvs {
 
@@ -38,7 +34,6 @@ constexpr uint32_t LINES = 256;        // lines of a block
 constexpr uint32_t STAGE = 16384;      // bytes of the LDS staging buffer: a typical block (256 lines of ~30 bytes) in one pass, 9 blocks per CU
 constexpr uint32_t MAX_NAME = 255;     // longest line: a material's record = 166 + 255 + 2 x 10 bytes, far below STAGE - 15
 enum { K_WIDE = 0, K_NONFINITE, K_BAD_FACE, K_BAD_ID, K_N };   // 64-bit counters
-inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- sinks: one emit() per source serves the measuring and the writing pass ----
 struct CountSink {
@@ -292,7 +287,7 @@ void model_refuse_bad_ids(uint64_t bad_faces, uint64_t bad_ids, const char* who)
     if (bad_ids) throw StatusError(MVS_ERR_INVALID, std::string(who) + ": " + std::to_string(bad_ids) + " texcoord ids lie outside their atlas's range");
 }
 
-void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who) {
+void model_check_image_params(const mvs_model_params& P, const mvs_atlas_set& in, const char* who) {
     const std::string w = std::string(who) + ": ";
     if (P.image_format != 0 && P.image_format != 1) throw StatusError(MVS_ERR_INVALID, w + "image_format 0 (PNG) or 1 (JPEG)");
     if (P.image_format == 1) {
@@ -307,53 +302,41 @@ void model_check_png_params(const mvs_model_params& P, const mvs_atlas_set& in, 
     if (in.n_atlases && (!in.atlas_size || !in.atlas_pix_ptr || (in.n_pixels && !in.image))) throw StatusError(MVS_ERR_INVALID, w + "null array in the atlas set");
 }
 
-void model_for_each_png(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelPngSink& sink) {
+void model_for_each_image(mvs_ctx* ctx, const mvs_atlas_set& in, int atlases_on_device, const mvs_model_params& P, const char* who, const ModelImageSink& sink) {
     // sizes and offsets on the host, the pixels copied once, one atlas per thread at a time
     hipStream_t s = ctx->stream;
     const uint32_t A = in.n_atlases;
     const std::string w = std::string(who) + ": ";
-    std::vector<uint32_t> size(A); std::vector<uint64_t> pix((size_t)A + 1, 0);
-    std::vector<uint8_t> own;
-    const uint8_t* image = in.image;
-    if (A) {
-        if (atlases_on_device) {
-            MVS_HIP(hipMemcpyAsync(size.data(), in.atlas_size, A * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            MVS_HIP(hipMemcpyAsync(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            if (!P.png_device && P.image_format != 1) {
-                own.resize(3 * (size_t)in.n_pixels + 1);
-                if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
-                image = own.data();
-            }
-            MVS_HIP(hipStreamSynchronize(s));
-        } else {
-            memcpy(size.data(), in.atlas_size, A * sizeof(uint32_t)); memcpy(pix.data(), in.atlas_pix_ptr, ((size_t)A + 1) * sizeof(uint64_t));
-        }
-    }
+    ImageSet S{{}, {}, {0}};
+    if (A) S = read_image_arrays(ctx, A, in.atlas_size, in.atlas_size, in.atlas_pix_ptr, atlases_on_device);
+    const std::vector<uint32_t>& size = S.w; const std::vector<uint64_t>& pix = S.pix;
     if (pix[0] != 0 || pix[A] != in.n_pixels) throw StatusError(MVS_ERR_INVALID, w + "atlas_pix_ptr does not run from 0 to n_pixels");
     for (uint32_t a = 0; a < A; ++a)
         if (!size[a] || pix[a + 1] < pix[a] || pix[a + 1] - pix[a] != (uint64_t)size[a] * size[a]) throw StatusError(MVS_ERR_INVALID, w + "atlas " + std::to_string(a) + ": size and atlas_pix_ptr do not agree");
-    PngFiles files;   // png_device 1 or image_format 1: the finished files, encoded on the device
+    EncodedFiles files;   // png_device 1 or image_format 1: the finished files, encoded on the device
     const bool on_dev = P.png_device || P.image_format == 1;
+    std::vector<uint8_t> own;   // the host route's pixels of a device-resident set
+    const uint8_t* image = in.image;
+    if (A && atlases_on_device && !on_dev) {
+        own.resize(3 * (size_t)in.n_pixels + 1);
+        if (in.n_pixels) MVS_HIP(hipMemcpyAsync(own.data(), in.image, 3 * (size_t)in.n_pixels, hipMemcpyDeviceToHost, s));
+        MVS_HIP(hipStreamSynchronize(s));
+        image = own.data();
+    }
     if (P.image_format == 1 && A) { mvs_jpeg_stats jst{}; jpeg_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, P.jpeg_quality, P.jpeg_subsampling, files, jst); }
     else if (P.png_device && A) { mvs_png_stats pst{}; png_encode_images(ctx, A, size.data(), size.data(), pix.data(), in.image, atlases_on_device, files, pst); }
-    std::atomic<uint32_t> next{0}; std::atomic<int> failed{MVS_OK};
+    std::atomic<int> failed{MVS_OK};
     std::vector<std::string> errs(A);
-    auto work = [&] {
-        for (uint32_t a = next.fetch_add(1); a < A; a = next.fetch_add(1)) {
-            mvs_status r;
-            if (on_dev) r = sink(a, files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a]);
-            else {
-                std::vector<uint8_t> png;
-                r = encode_png(image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, png, errs[a]);
-                if (r == MVS_OK) r = sink(a, png.data(), png.size(), errs[a]);
-            }
-            if (r != MVS_OK) failed.store(r);
+    for_each_on_threads(A, [&](uint32_t a) {
+        mvs_status r;
+        if (on_dev) r = sink(a, files.data + files.offsets[a], (size_t)(files.offsets[a + 1] - files.offsets[a]), errs[a]);
+        else {
+            std::vector<uint8_t> png;
+            r = encode_png(image + 3 * (size_t)pix[a], size[a], size[a], P.png_level, png, errs[a]);
+            if (r == MVS_OK) r = sink(a, png.data(), png.size(), errs[a]);
         }
-    };
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < std::min<uint32_t>(16u, A); ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+        if (r != MVS_OK) failed.store(r);
+    });
     if (failed.load() != MVS_OK)
         for (uint32_t a = 0; a < A; ++a) if (!errs[a].empty()) throw StatusError((mvs_status)failed.load(), w + errs[a]);
 }
@@ -379,10 +362,8 @@ mvs_status mvs_ctx_build_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int a
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->model) ctx->model = new ModelDev();
-        ModelDev& D = *ctx->model;
-        mvs_model_params P;
-        if (params) P = *params; else mvs_model_default_params(&P);
+        ModelDev& D = row_dev(ctx->model);
+        const mvs_model_params P = params_or_default(params);
         run_with_stats(s, stats, st, [&] { run_model(ctx, D, *atlases, atlases_on_device, vertex_normals, normals_on_device, name, P, st); });
         const size_t NS = (size_t)atlases->n_atlases + 5;
         out->n_atlases = atlases->n_atlases; out->obj_bytes = D.obj_bytes; out->mtl_bytes = D.mtl_bytes;
@@ -413,12 +394,10 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->model) ctx->model = new ModelDev();
-        ModelDev& D = *ctx->model;
-        mvs_model_params P;
-        if (params) P = *params; else mvs_model_default_params(&P);
+        ModelDev& D = row_dev(ctx->model);
+        const mvs_model_params P = params_or_default(params);
         const mvs_atlas_set& in = *atlases;
-        model_check_png_params(P, in, "save_model");
+        model_check_image_params(P, in, "save_model");
         const std::string pre(prefix), name = pre.substr(pre.find_last_of('/') == std::string::npos ? 0 : pre.find_last_of('/') + 1);
         run_with_stats(s, stats, st, [&] {
             run_model(ctx, D, in, atlases_on_device, vertex_normals, normals_on_device, name, P, st);
@@ -428,10 +407,10 @@ mvs_status mvs_ctx_save_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int at
             if (rc == MVS_OK) rc = device_to_file(ctx, D.mtl.p, D.mtl_bytes, pre + ".mtl", ms_copy, msg);
             st.ms_download = (float)ms_copy; st.ms_files = (float)(now_ms_host() - t0 - ms_copy);
             if (rc != MVS_OK) throw StatusError(rc, "save_model: " + msg);
-            // ---- the PNGs: one file per atlas, written by the thread that holds its bytes ----
+            // ---- the images: one file per atlas, written by the thread that holds its bytes ----
             const double t1 = now_ms_host();
             try {
-                model_for_each_png(ctx, in, atlases_on_device, P, "save_model", [&](uint32_t a, const uint8_t* bytes, size_t n, std::string& err) {
+                model_for_each_image(ctx, in, atlases_on_device, P, "save_model", [&](uint32_t a, const uint8_t* bytes, size_t n, std::string& err) {
                     return write_file((pre + "_material" + model_filled4(a) + (P.image_format == 1 ? "_map_Kd.jpg" : "_map_Kd.png")).c_str(), bytes, n, err);
                 });
             } catch (...) { st.ms_png = (float)(now_ms_host() - t1); throw; }

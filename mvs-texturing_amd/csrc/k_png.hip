@@ -12,12 +12,8 @@
 //   gather   a 64-bit scan of the chunks' byte counts, then every chunk is copied behind its predecessors: one contiguous zlib stream per
 //            image.  The two header bytes and the Adler-32 (combined from the chunks' sums) are written on the host, which also frames
 //            the PNGs (signature, IHDR, IDAT with its CRC, IEND: png_io.h's routines on the compressed bytes).
-#include "rows.h"
+#include "image_routes.h"
 #include "png_rle.h"
-
-#include <atomic>
-#include <chrono>
-#include <thread>
 
 namespace mvs {
 
@@ -37,14 +33,6 @@ constexpr uint32_t SEG_PITCH = SEG + 4;            // ... and their distance in 
 constexpr uint32_t SLOT = CHUNK + 16;              // bytes of a chunk's output slot: at most n + 10 are used
 constexpr uint64_t STREAM_ALIGN = 256;             // streams start at multiples of this in the filtered buffer
 static_assert(SEG * THREADS == CHUNK && SEG % 16 == 0 && SLOT % 16 == 0, "segments and slots are whole 16-byte pieces");
-inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// ptr [K + 1] ascending from 0: the k with ptr[k] <= i < ptr[k + 1]
-__device__ uint32_t owner_of(const uint32_t* __restrict__ ptr, uint32_t K, uint32_t i) {
-    uint32_t lo = 0, hi = K;
-    while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (ptr[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
 
 // ---- filter pass ----
 struct Images { const uint32_t* row_ptr; const uint32_t* width; const u64* pix; const u64* off; uint32_t K; };   // row_ptr [K + 1]; pix: first pixel; off: first byte of the stream
@@ -197,31 +185,12 @@ __global__ void __launch_bounds__(THREADS) png_chunk_kernel(Streams S, const uin
     if (tid == 0u) { sizes[c] = bytes; meta[c] = make_uint4(bytes, L.adler_a % ADLER_MOD, L.adler_b % ADLER_MOD, dynamic ? 0u : 1u); }
 }
 
-// ---- gather pass: off [chunks + 1] = the scan of the sizes; stream k starts 16 k bytes behind its chunks' offset, its first chunk 2 further ----
-__global__ void __launch_bounds__(THREADS) png_gather_kernel(Streams S, const uint8_t* __restrict__ slots, const uint32_t* __restrict__ sizes, const u64* __restrict__ off,
-                                                             uint8_t* __restrict__ zout) {
-    const uint32_t c = blockIdx.x, k = owner_of(S.chunk_ptr, S.K, c), nb = sizes[c];
-    const uint8_t* src = slots + (u64)c * SLOT;
-    uint8_t* dst = zout + off[c] + 16ull * k + 2ull;
-    const uint32_t lead = (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u), head = lead < nb ? lead : nb;   // bytes up to dst's first 16-byte boundary
-    for (uint32_t i = threadIdx.x; i < head; i += THREADS) dst[i] = src[i];
-    const uint32_t words = (nb - head) / 16u;
-    for (uint32_t i = threadIdx.x; i < words; i += THREADS) {
-        uint4 v;
-        uint8_t* b = reinterpret_cast<uint8_t*>(&v);
-        const uint8_t* s = src + head + 16u * i;
-        for (int j = 0; j < 16; ++j) b[j] = s[j];
-        reinterpret_cast<uint4*>(dst + head)[i] = v;
-    }
-    for (uint32_t i = head + 16u * words + threadIdx.x; i < nb; i += THREADS) dst[i] = src[i];
-}
-
 // the zlib streams of a call on the host: stream k is z[k] bytes at base + begin[k] of the context's pinned buffer
 struct ZStreams { std::vector<uint64_t> begin, bytes; uint8_t* base = nullptr; uint64_t chunks = 0, stored = 0; };
 
 // the chunk and gather passes over K streams of D.filt (off: multiples of STREAM_ALIGN, the buffer ends at least 16 bytes behind the last
-// stream), the download and the streams' header and checksum.  Marks tm twice (behind the chunk pass, behind the gather pass); ms_copy +=
-// the host time of the downloads.
+// stream), the download and the streams' header and checksum.  Marks tm twice (behind the chunk pass, behind the gather pass: stream k
+// starts 16 k bytes behind its chunks' offset, its first chunk 2 further); ms_copy += the host time of the downloads.
 void run_streams(mvs_ctx* ctx, PngDev& D, const std::vector<uint64_t>& off, const std::vector<uint64_t>& len, ZStreams& Z, StageTimer<4>& tm, double& ms_copy) {
     hipStream_t s = ctx->stream;
     const uint32_t K = (uint32_t)off.size();
@@ -247,28 +216,8 @@ void run_streams(mvs_ctx* ctx, PngDev& D, const std::vector<uint64_t>& off, cons
         MVS_LAUNCH_CHECK();
     }
     tm.mark();
-    MVS_HIP(hipMemsetAsync(D.sizes.p + NC, 0, sizeof(uint32_t), s));
-    dev_exclusive_scan(ctx, (const uint32_t*)D.sizes.p, D.off.p, (size_t)NC + 1);
-    if (NC) {
-        hipLaunchKernelGGL(png_gather_kernel, dim3(NC), dim3(THREADS), 0, s, S, (const uint8_t*)D.slots.p, (const uint32_t*)D.sizes.p, (const u64*)D.off.p, D.zout.p);
-        MVS_LAUNCH_CHECK();
-    }
-    tm.mark();
-    // ---- the chunks' offsets and sums, then the streams ----
-    MVS_HIP(hipStreamSynchronize(s));   // (so that ms_copy is the copies' time, not the passes')
-    const double t0 = now_ms_host();
-    const size_t b_off = ((size_t)NC + 1) * sizeof(u64), b_meta = (size_t)NC * sizeof(uint4);
-    ctx->row_pin.ensure(b_off + b_meta + 16);
-    MVS_HIP(hipMemcpyAsync(ctx->row_pin.p, D.off.p, b_off, hipMemcpyDeviceToHost, s));
-    if (NC) MVS_HIP(hipMemcpyAsync(ctx->row_pin.p + b_off, D.meta.p, b_meta, hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipStreamSynchronize(s));
-    std::vector<u64> h_off((const u64*)ctx->row_pin.p, (const u64*)ctx->row_pin.p + NC + 1);
-    std::vector<uint4> h_meta((const uint4*)(ctx->row_pin.p + b_off), (const uint4*)(ctx->row_pin.p + b_off) + NC);
-    const uint64_t total = h_off[NC] + 16ull * K;
-    ctx->row_pin.ensure((size_t)total + 16);
-    if (total) MVS_HIP(hipMemcpyAsync(ctx->row_pin.p, D.zout.p, (size_t)total, hipMemcpyDeviceToHost, s));
-    MVS_HIP(hipStreamSynchronize(s));
-    ms_copy += now_ms_host() - t0;
+    std::vector<uint4> h_meta(NC);   // the chunks' sizes and sums
+    const std::vector<u64> h_off = pack_slots<16, 2>(ctx, D.t32.p, K, NC, SLOT, D.slots.p, D.sizes.p, D.off, D.zout.p, D.meta.p, h_meta.data(), (size_t)NC * sizeof(uint4), tm, ms_copy);
     Z.base = (uint8_t*)ctx->row_pin.p; Z.begin.resize(K); Z.bytes.resize(K); Z.chunks = NC; Z.stored = 0;
     for (uint32_t k = 0; k < K; ++k) {
         uint8_t* z = Z.base + h_off[cptr[k]] + 16ull * k;
@@ -287,15 +236,13 @@ void run_streams(mvs_ctx* ctx, PngDev& D, const std::vector<uint64_t>& off, cons
     }
 }
 
-PngDev& png_dev(mvs_ctx* ctx) { if (!ctx->png) ctx->png = new PngDev(); return *ctx->png; }
-
 }  // namespace
 
 // width, height [n], pix [n + 1]: host arrays, already checked against each other; image: 3 bytes per pixel, host or device
 void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const uint32_t* height, const uint64_t* pix, const uint8_t* image, int image_on_device,
-                       PngFiles& out, mvs_png_stats& st) {
+                       EncodedFiles& out, mvs_png_stats& st) {
     hipStream_t s = ctx->stream;
-    PngDev& D = png_dev(ctx);
+    PngDev& D = row_dev(ctx->png);
     std::string msg;
     std::vector<uint32_t> h32(2 * (size_t)n + 1, 0u);   // row_ptr [n + 1], width [n]
     std::vector<u64> h64(2 * (size_t)n);               // pix [n], off [n]
@@ -336,15 +283,8 @@ void png_encode_images(mvs_ctx* ctx, uint32_t n, const uint32_t* width, const ui
     const double t0 = now_ms_host();
     out.offsets.assign((size_t)n + 1, 0);
     for (uint32_t k = 0; k < n; ++k) out.offsets[k + 1] = out.offsets[k] + Z.bytes[k] + PNG_FRAME;
-    free(out.data);
-    out.data = (uint8_t*)malloc(std::max<size_t>((size_t)out.offsets[n], 1));
-    if (!out.data) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-    std::atomic<uint32_t> next{0};   // one image per thread at a time: the CRC of its compressed bytes is the work
-    auto work = [&] { for (uint32_t k = next.fetch_add(1); k < n; k = next.fetch_add(1)) frame_png(out.data + out.offsets[k], width[k], height[k], Z.base + Z.begin[k], (size_t)Z.bytes[k]); };
-    std::vector<std::thread> pool;
-    for (uint32_t t = 1; t < std::min<uint32_t>(16u, n); ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    out.resize_data();
+    for_each_on_threads(n, [&](uint32_t k) { frame_png(out.data + out.offsets[k], width[k], height[k], Z.base + Z.begin[k], (size_t)Z.bytes[k]); });   // the CRC of the compressed bytes is the work
     st.png_bytes = out.offsets[n];
     st.ms_frame = (float)(now_ms_host() - t0);
 }
@@ -358,34 +298,8 @@ extern "C" {
 mvs_status mvs_ctx_encode_pngs(mvs_ctx* ctx, uint32_t n_images, const uint32_t* width, const uint32_t* height, const uint64_t* pix_ptr, const uint8_t* image, int on_device,
                                mvs_png_set* out, mvs_png_stats* stats) {
     if (!ctx || !out || (n_images && (!width || !height)) || !pix_ptr) return api_fail(MVS_ERR_INVALID, "null argument");
-    *out = mvs_png_set{};
-    mvs_png_stats st{};
-    if (stats) *stats = st;
-    return api_guard([&] {
-        MVS_HIP(hipSetDevice(ctx->device));
-        hipStream_t s = ctx->stream;
-        const uint32_t n = n_images;
-        std::vector<uint32_t> w(n), h(n); std::vector<uint64_t> pix((size_t)n + 1);
-        if (on_device) {
-            if (n) { MVS_HIP(hipMemcpyAsync(w.data(), width, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s)); MVS_HIP(hipMemcpyAsync(h.data(), height, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s)); }
-            MVS_HIP(hipMemcpyAsync(pix.data(), pix_ptr, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-            MVS_HIP(hipStreamSynchronize(s));
-        } else {
-            if (n) { memcpy(w.data(), width, n * sizeof(uint32_t)); memcpy(h.data(), height, n * sizeof(uint32_t)); }
-            memcpy(pix.data(), pix_ptr, ((size_t)n + 1) * sizeof(uint64_t));
-        }
-        if (pix[0] != 0) throw StatusError(MVS_ERR_INVALID, "encode_pngs: pix_ptr does not start at 0");
-        for (uint32_t k = 0; k < n; ++k)
-            if (!w[k] || !h[k] || pix[k + 1] < pix[k] || pix[k + 1] - pix[k] != (uint64_t)w[k] * h[k]) throw StatusError(MVS_ERR_INVALID, "encode_pngs: image " + std::to_string(k) + ": width, height and pix_ptr do not agree");
-        if (pix[n] && !image) throw StatusError(MVS_ERR_INVALID, "encode_pngs: null image");
-        run_with_stats(s, stats, st, [&] {
-            PngFiles F;
-            png_encode_images(ctx, n, w.data(), h.data(), pix.data(), image, on_device, F, st);
-            out->offsets = (uint64_t*)malloc(((size_t)n + 1) * sizeof(uint64_t));
-            if (!out->offsets) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-            memcpy(out->offsets, F.offsets.data(), ((size_t)n + 1) * sizeof(uint64_t));
-            out->n_images = n; out->n_bytes = F.offsets[n]; out->data = F.data; F.data = nullptr;
-        });
+    return encode_entry(ctx, n_images, width, height, pix_ptr, image, on_device, out, stats, "encode_pngs", [&](const ImageSet& S, EncodedFiles& F, mvs_png_stats& st) {
+        png_encode_images(ctx, n_images, S.w.data(), S.h.data(), S.pix.data(), image, on_device, F, st);
     });
 }
 
@@ -404,7 +318,7 @@ mvs_status mvs_ctx_deflate_rle(mvs_ctx* ctx, const uint8_t* bytes, uint64_t n, i
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         if (n >= MAX_STREAM) throw StatusError(MVS_ERR_UNSUPPORTED, "deflate_rle: stream too large for one IDAT chunk");
-        PngDev& D = png_dev(ctx);
+        PngDev& D = row_dev(ctx->png);
         D.filt.ensure((size_t)n + STREAM_ALIGN);
         if (n) MVS_HIP(hipMemcpyAsync(D.filt.p, bytes, (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         StageTimer<4> tm(s);
@@ -415,15 +329,6 @@ mvs_status mvs_ctx_deflate_rle(mvs_ctx* ctx, const uint8_t* bytes, uint64_t n, i
         memcpy(z, Z.base + Z.begin[0], (size_t)Z.bytes[0]);
         *out = z; *out_bytes = Z.bytes[0];
     });
-}
-
-static mvs_status twin_out(mvs_status st, const std::string& msg, const std::vector<uint8_t>& v, uint8_t** out, uint64_t* out_bytes) {
-    if (st != MVS_OK) return api_fail(st, msg);
-    uint8_t* p = (uint8_t*)malloc(std::max<size_t>(v.size(), 1));
-    if (!p) return api_fail(MVS_ERR_INVALID, "out of host memory");
-    memcpy(p, v.data(), v.size());
-    *out = p; *out_bytes = v.size();
-    return MVS_OK;
 }
 
 mvs_status mvs_encode_png_rle(const uint8_t* rgb, uint32_t width, uint32_t height, uint8_t** out, uint64_t* out_bytes) {

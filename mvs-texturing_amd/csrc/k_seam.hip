@@ -667,8 +667,7 @@ mvs_status mvs_ctx_global_seam_leveling(mvs_ctx* ctx, const uint32_t* adj_ptr, c
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->gsl) ctx->gsl = new GslDev();
-        GslDev& G = *ctx->gsl;
+        GslDev& G = row_dev(ctx->gsl);
         mvs_gsl_params P;
         if (params) P = *params; else mvs_gsl_default_params(&P);
         const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device);

@@ -463,8 +463,7 @@ mvs_status mvs_ctx_texture_patches(mvs_ctx* ctx, const uint32_t* adj_ptr, const 
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
-        if (!ctx->texpatch) ctx->texpatch = new TexPatchDev();
-        TexPatchDev& D = *ctx->texpatch;
+        TexPatchDev& D = row_dev(ctx->texpatch);
         mvs_patch_params P;
         if (params) P = *params; else mvs_patch_default_params(&P);
         const RowGraph g = stage_graph(ctx, adj_ptr, adj, adj_on_device, labels, labels_on_device);

@@ -1,13 +1,38 @@
 // rows.h -- the host plumbing the post-processing rows f5 - f8 share (k_seam.hip, k_texpatch.hip, k_localseam.hip, k_atlas.hip):
 //   launch and copy helpers, the rocprim two-call idiom (sort_scan.h), stage timers, the wrappers around an entry point's body, the staging of the
-//   caller's adjacency and labels, and the reader / checker of a patch set (DESIGN.md section 4 "Shared plumbing").  Internal, header-only.
+//   caller's adjacency and labels, and the reader / checker of a patch set; and what rows f9 - f11 and the image encoders need beside them: the host
+//   clock, a row's buffers on first use, the model parameters' defaults, a loop on host threads (DESIGN.md section 4 "Shared plumbing").  Internal, header-only.
 #pragma once
 #include "ctx.h"
 #include "sort_scan.h"
 
+#include <atomic>
+#include <chrono>
+#include <thread>
+
 namespace mvs {
 
 inline unsigned grid(size_t n) { return (unsigned)std::max<size_t>(1, (n + 255) / 256); }   // blocks of 256 threads, at least one
+inline double now_ms_host() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// a row's per-context buffers (ctx->gsl, ctx->atlas, ...): allocated on first use, freed by the row's *_release
+template <class Dev>
+Dev& row_dev(Dev*& slot) { if (!slot) slot = new Dev(); return *slot; }
+// the caller's model parameters, or the library's defaults (rows f9 and f11)
+inline mvs_model_params params_or_default(const mvs_model_params* params) {
+    mvs_model_params P;
+    if (params) P = *params; else mvs_model_default_params(&P);
+    return P;
+}
+// fn(i) for every i < n, one item per thread at a time on min(16, n) host threads, the calling one included; fn does not throw
+template <class Fn>
+void for_each_on_threads(uint32_t n, Fn&& fn) {
+    std::atomic<uint32_t> next{0};
+    auto work = [&] { for (uint32_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i); };
+    std::vector<std::thread> pool;
+    for (uint32_t t = 1; t < std::min<uint32_t>(16u, n); ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+}
 
 // ---- copies (all asynchronous on `s`: the caller drains the stream before the host side goes away) ----
 template <class T>

@@ -966,7 +966,7 @@ class Context:
         res, st = Glb(), GlbStats()
         self._keep["glb"] = held
         rc = self.L.mvs_ctx_build_glb(self.h, C.byref(ps), dev, pn, dn, C.byref(p), C.byref(res), C.byref(st))
-        stats = _glb_stats(st)
+        stats = _stats_dict(st)
         _check_with_stats(self.L, rc, stats)
         data = C.string_at(res.data, res.n_bytes)
         self.L.mvs_glb_free(C.byref(res))
@@ -978,7 +978,7 @@ class Context:
         st = GlbStats()
         self._keep["glb"] = held
         rc = self.L.mvs_ctx_save_glb(self.h, C.byref(ps), dev, pn, dn, os.fspath(path).encode(), C.byref(p), C.byref(st))
-        stats = _glb_stats(st)
+        stats = _stats_dict(st)
         _check_with_stats(self.L, rc, stats)
         return stats
 
@@ -1009,39 +1009,32 @@ class Context:
             img = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.uint8)
         return n, width, height, pix, img, dev
 
+    def _encode_images(self, images, key, fn, stats_cls, stats_dict, free, *extra):
+        """encode_pngs / encode_jpegs: one call of `fn` on the image set (`extra`: the arguments between on_device and the result), the
+        files cut out of the set, the set released by `free`"""
+        n, width, height, pix, img, dev = self._image_set(images)
+        res, st = PngSet(), stats_cls()
+        self._keep[key] = (width, height, pix, img)
+        n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
+        rc = fn(self.h, n, _ptr(width)[0], _ptr(height)[0], _ptr(pix)[0], _ptr(img)[0] if n_pix else None, dev, *extra, C.byref(res), C.byref(st))
+        stats = stats_dict(st)
+        _check_with_stats(self.L, rc, stats)
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        data = C.string_at(res.data, res.n_bytes)
+        free(C.byref(res))
+        return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
+
     def encode_pngs(self, images):
         """The compressed PNG route of row f9 on its own (mvs_ctx_encode_pngs; DESIGN.md section 4 "Model output" item 7): `images` is a
         list of (H, W, 3) uint8 arrays -- all numpy or all CUDA tensors -- or an atlas-set dict (atlas_size, atlas_pix_ptr, image: all
         host or all device).  One call encodes them all.  Returns (list of bytes, one PNG file per image; stats)."""
-        n, width, height, pix, img, dev = self._image_set(images)
-        res, st = PngSet(), PngStats()
-        self._keep["png"] = (width, height, pix, img)
-        n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
-        rc = self.L.mvs_ctx_encode_pngs(self.h, n, _ptr(width)[0], _ptr(height)[0], _ptr(pix)[0], _ptr(img)[0] if n_pix else None, dev, C.byref(res), C.byref(st))
-        stats = _png_stats(st)
-        _check_with_stats(self.L, rc, stats)
-        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
-        data = C.string_at(res.data, res.n_bytes)
-        self.L.mvs_png_set_free(C.byref(res))
-        return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
+        return self._encode_images(images, "png", self.L.mvs_ctx_encode_pngs, PngStats, _png_stats, self.L.mvs_png_set_free)
 
     def encode_jpegs(self, images, quality=90, subsampling=1):
         """The JPEG route of rows f9 / f11 on its own (mvs_ctx_encode_jpegs; DESIGN.md section 4 "Model output" item 9): `images` as
         encode_pngs takes them, quality 1 .. 100, subsampling 0 (4:4:4) or 1 (4:2:0).  One call encodes them all.  Returns (list of
         bytes, one baseline JPEG file per image; stats).  The same bytes as the host twin encode_jpeg gives."""
-        n, width, height, pix, img, dev = self._image_set(images)
-        res, st = PngSet(), JpegStats()
-        self._keep["jpeg"] = (width, height, pix, img)
-        n_pix = int(img.numel()) if _is_torch(img) else int(img.shape[0])
-        rc = self.L.mvs_ctx_encode_jpegs(self.h, n, _ptr(width)[0], _ptr(height)[0], _ptr(pix)[0], _ptr(img)[0] if n_pix else None, dev, int(quality), int(subsampling),
-                                         C.byref(res), C.byref(st))
-        stats = {k: int(getattr(st, k)) for k in JPEG_COUNTS}
-        stats.update({k: float(getattr(st, k)) for k in JPEG_MS})
-        _check_with_stats(self.L, rc, stats)
-        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
-        data = C.string_at(res.data, res.n_bytes)
-        self.L.mvs_jpeg_set_free(C.byref(res))
-        return [data[int(off[i]):int(off[i + 1])] for i in range(n)], stats
+        return self._encode_images(images, "jpeg", self.L.mvs_ctx_encode_jpegs, JpegStats, _stats_dict, self.L.mvs_jpeg_set_free, int(quality), int(subsampling))
 
     def deflate_rle(self, data):
         """mvs_ctx_deflate_rle: the zlib stream (bytes) the chunk, gather and checksum passes of the compressed PNG route give the byte
@@ -1190,13 +1183,8 @@ def _model_stats(st):
     return stats
 
 
-def _glb_stats(st):
-    stats = {k: int(getattr(st, k)) for k in GLB_COUNTS}
-    stats.update({k: float(getattr(st, k)) for k in GLB_MS})
-    return stats
-
-
 def _png_stats(st):
+    # (not _stats_dict: filter_rows is an array, which goes out as a list, and the struct's reserved word stays out)
     stats = {k: int(getattr(st, k)) for k in PNG_COUNTS}
     stats["filter_rows"] = [int(x) for x in st.filter_rows]
     stats.update({k: float(getattr(st, k)) for k in PNG_MS})

@@ -89,6 +89,27 @@ def test_encode_jpegs_of_an_atlas_set(ctx, twin):
     assert dev == host
 
 
+def test_gather_at_every_alignment(ctx):
+    """PD.alignment_images() in one call, from host arrays and from device tensors.  At 4:2:0 every image is one segment (at most 3 x 2
+    MCUs), which lands behind the entropy data of the images in front of it: a file without its header and EOI.  The sizes, not luck,
+    spread those destinations over the residues modulo 16 and make segments shorter than their way to the next boundary; at 4:4:4 the
+    larger images have two segments."""
+    import torch
+    imgs = PD.alignment_images()
+    want = [M.encode_jpeg(a, 90, 1) for a in imgs]
+    seg = np.array([len(f) - JD.HEADER_BYTES - 2 for f in want])
+    start = np.concatenate([[0], np.cumsum(seg)[:-1]])
+    assert len(set(int(x) % 16 for x in start)) >= 12
+    assert any(n < (-s) % 16 for n, s in zip(seg, start))
+    host, stats = ctx.encode_jpegs(imgs, 90, 1)
+    for k, (got, exp) in enumerate(zip(host, want)):
+        assert got == exp, PD.ALIGN_SIZES[k]
+    assert stats["segments"] == len(imgs)
+    dev, _ = ctx.encode_jpegs([torch.from_numpy(a).cuda() for a in imgs], 90, 1)
+    assert dev == want
+    assert ctx.encode_jpegs(imgs, 90, 0)[0] == [M.encode_jpeg(a, 90, 0) for a in imgs]
+
+
 def _files(d):
     return {n: open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d))}
 

@@ -92,6 +92,65 @@ def test_encode_pngs_of_an_atlas_set(ctx, twin_pngs):
     assert dev == host
 
 
+def test_gather_at_every_alignment(ctx):
+    """PD.alignment_images() in one call, from host arrays and from device tensors.  Every image is one chunk; chunk k lands 2 + 16 k
+    bytes behind the chunks in front of it, each of which is its zlib stream without the 2 header bytes and the 4 of the Adler-32.  The
+    sizes, not luck, spread those destinations over the residues modulo 16 and make a chunk shorter than its way to the next boundary."""
+    import torch
+    imgs = PD.alignment_images()
+    want = [M.encode_png_rle(a) for a in imgs]
+    chunk = np.array([len(p) - 57 - 6 for p in want])                  # 57: signature, IHDR, the IDAT chunk's frame, IEND
+    start = 2 + 16 * np.arange(len(imgs)) + np.concatenate([[0], np.cumsum(chunk)[:-1]])
+    assert len(set(int(x) % 16 for x in start)) >= 12
+    assert any(n < (-s) % 16 for n, s in zip(chunk, start))
+    host, stats = ctx.encode_pngs(imgs)
+    for k, (got, exp) in enumerate(zip(host, want)):
+        assert got == exp, PD.ALIGN_SIZES[k]
+    assert stats["chunks"] == len(imgs)
+    dev, _ = ctx.encode_pngs([torch.from_numpy(a).cuda() for a in imgs])
+    assert dev == want
+
+
+# (caller, start at 1, total not n_pixels, size against range): the messages as the library words them
+_SET_REFUSALS = (
+    ("encode_pngs", "encode_pngs: pix_ptr does not start at 0", "encode_pngs: image 0: width, height and pix_ptr do not agree", "encode_pngs: image 0: width, height and pix_ptr do not agree"),
+    ("encode_jpegs", "encode_jpegs: pix_ptr does not start at 0", "encode_jpegs: image 0: width, height and pix_ptr do not agree", "encode_jpegs: image 0: width, height and pix_ptr do not agree"),
+    ("save_model", "save_model: atlas_pix_ptr does not run from 0 to n_pixels", "save_model: atlas_pix_ptr does not run from 0 to n_pixels", "save_model: atlas 0: size and atlas_pix_ptr do not agree"),
+    ("build_glb", "build_glb: atlas_pix_ptr does not run from 0 to n_pixels", "build_glb: atlas_pix_ptr does not run from 0 to n_pixels", "build_glb: atlas 0: size and atlas_pix_ptr do not agree"),
+)
+
+
+def test_image_set_refusals_per_caller(tmp_path):
+    """an atlas_pix_ptr / pix_ptr that starts at 1, one whose total is not n_pixels and a size that disagrees with its range, through both
+    encoders and through save_model and build_glb on both device routes: MVS_ERR_INVALID with the caller's own message, then a good call"""
+    verts, faces, atlases = PD.tiny_model()
+    c = M.Context(0)
+    c.set_mesh(verts, faces, np.zeros((1, 3), np.float32))
+    img = atlases["image"].reshape(16, 16, 3)
+    png, jpg = M.encode_png_rle(img), M.encode_jpeg(img, 90, 1)
+    cases = (dict(atlas_pix_ptr=np.array([1, 257], np.uint64)), dict(atlas_pix_ptr=np.array([0, 255], np.uint64)), dict(atlas_size=np.array([15], np.uint32)))
+    routes = ((M.default_model_params(png_device=1), png, ".png"), (M.default_model_params(image_format=1), jpg, ".jpg"))
+    calls = []                                                       # (message row, call on an atlas set -> the image's bytes)
+    image_set = lambda a: {k: a[k] for k in ("atlas_size", "atlas_pix_ptr", "image")}
+    calls.append((_SET_REFUSALS[0], lambda a: c.encode_pngs(image_set(a))[0][0], png))
+    calls.append((_SET_REFUSALS[1], lambda a: c.encode_jpegs(image_set(a))[0][0], jpg))
+    for p, want, ext in routes:
+        def save(a, p=p, ext=ext):
+            c.save_model(a, str(tmp_path / "m"), params=p)
+            return open(str(tmp_path / ("m_material0000_map_Kd" + ext)), "rb").read()
+        calls.append((_SET_REFUSALS[2], save, want))
+        calls.append((_SET_REFUSALS[3], lambda a, p=p: c.build_glb(a, params=p)[0], want))
+    for row, call, want in calls:
+        for bad, message in zip(cases, row[1:]):
+            with pytest.raises(M.MvsError) as e:
+                call(dict(atlases, **bad))
+            assert e.value.status == 1, (row[0], bad)                  # MVS_ERR_INVALID
+            assert str(e.value) == message + " (status 1)", (row[0], bad)
+            good = call(atlases)
+            assert good == want or (row[0] == "build_glb" and good.count(want) == 1), (row[0], bad)
+    c.close()
+
+
 def _pngs_of(d):
     return {n: open(os.path.join(d, n), "rb").read() for n in sorted(os.listdir(d)) if n.endswith(".png")}
 

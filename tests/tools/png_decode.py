@@ -174,6 +174,16 @@ def images():
     return out
 
 
+ALIGN_SIZES = [(1 + k, 1 + (7 * k) % 23) for k in range(40)] + [(2, 1)] + [(1, 1)] * 8
+
+
+def alignment_images():
+    """49 small images (ALIGN_SIZES: width, height) of two, sixteen and 256 values in turn: encoded in one call, their packed units start at
+    15 or 16 of the 16 residues modulo 16, and the tiny ones at the end are shorter than the bytes up to their first 16-byte boundary"""
+    rng = np.random.default_rng(11)
+    return [rng.integers(0, (2, 16, 256)[k % 3], (h, w, 3)).astype(np.uint8) for k, (w, h) in enumerate(ALIGN_SIZES)]
+
+
 def tiny_model():
     """(verts, faces, atlas set) of the smallest model save_model writes: one face, one 16 x 16 atlas of four colours"""
     verts = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32)
