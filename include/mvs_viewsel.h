@@ -666,7 +666,7 @@ void mvs_atlas_set_free(mvs_atlas_set* a);
  *   1 .. 100 and jpeg_subsampling 0 (4:4:4) / 1 (4:2:0): the files are `<prefix>_material<a>_map_Kd.jpg` and the `map_Kd` lines of the
  *   .mtl name them (the one change in the text); png_level and png_device must be 0.  MVS_ERR_INVALID for any other image_format, a
  *   quality or subsampling outside those values, or a non-zero png_level / png_device beside image_format 1; MVS_ERR_UNSUPPORTED for an
- *   atlas side above 65535.  With image_format 0 jpeg_quality, jpeg_subsampling and reserved are not read: a zeroed struct is the PNG
+ *   atlas side above 65535.  With image_format 0 jpeg_quality and jpeg_subsampling are not read, and glb_quantize is read by row f11 alone: a zeroed struct is the PNG
  *   route with stored blocks, as before.  stats.ms_png stays the one field for whichever encoder ran.
  *   The struct grew from 16 to 32 bytes with image_format: callers compiled against the 16-byte struct must be recompiled. */
 typedef struct mvs_model_params {
@@ -676,7 +676,7 @@ typedef struct mvs_model_params {
     int32_t image_format;     /* 0: PNG (default); 1: JPEG */
     int32_t jpeg_quality;     /* 1 .. 100 (default 90); read under image_format 1 only */
     int32_t jpeg_subsampling; /* 0: 4:4:4; 1: 4:2:0 (default); read under image_format 1 only */
-    int32_t reserved;
+    int32_t glb_quantize;     /* row f11 only: 0 (default): float32 attributes, 32-bit indices; 1: KHR_mesh_quantization (below) */
 } mvs_model_params;
 void mvs_model_default_params(mvs_model_params* p);
 typedef struct mvs_model_text {
@@ -808,7 +808,19 @@ mvs_status mvs_ctx_view_selection_model(mvs_ctx* ctx, const uint32_t* adj_ptr, c
  * vertex >= n_verts.  MVS_ERR_UNSUPPORTED for a position or normal of a referenced vertex that is not finite (JSON has no inf or nan;
  * counted in stats.nonfinite_values per component of every glTF vertex) and for a file of 2^32 - 1 bytes or more or above
  * params.max_bytes (0 = no cap): checked on headers + geometry after the numbering pass, before the attribute buffers are allocated,
- * and on the whole file once the PNG sizes are known.  stats is filled either way (file_bytes: what was known at the refusal). */
+ * and on the whole file once the PNG sizes are known.  stats is filled either way (file_bytes: what was known at the refusal).
+ *   params.glb_quantize 1 (DESIGN.md section 4 "Model output" item 10): the same pairs, numbering, primitives and images, with the
+ *   geometry quantised under the extension KHR_mesh_quantization, which the file then requires: POSITION as UNSIGNED_SHORT on ONE grid
+ *   for the whole file (step S = the largest extent of the three axes / 65535; the node's translation is the lower corner, its
+ *   scale [S, S, S]; 8 bytes per vertex), TEXCOORD_0 as normalised UNSIGNED_SHORT (4 bytes), NORMAL as the unit normal in normalised
+ *   BYTEs (4 bytes), and 16-bit indices for every primitive of at most 65 535 vertices -- 16 instead of 32 bytes per vertex, 2 instead
+ *   of 4 per index.  A position is off by at most half a step, a texture coordinate by 0.5 / 65535, a unit normal's component by
+ *   0.5 / 127.  A texture coordinate of a glTF vertex that is NaN or outside [0, 1] cannot be stored: MVS_ERR_UNSUPPORTED, counted
+ *   in texcoords_out_of_range per component; a normal of length 0 is stored as (0, 0, 0) and counted in zero_normals (both below).
+ *   The size checks run on the quantised sizes.  Any glb_quantize other than 0 / 1 is MVS_ERR_INVALID; mvs_ctx_save_model and
+ *   mvs_ctx_build_model do not read the field.  mvs_glb_stats keeps its 96 bytes: what this route adds to the stats is
+ *   mvs_glb_quant_stats, which mvs_ctx_glb_quant_stats copies out for the context's LAST build_glb / save_glb call, refused or not
+ *   (all zero after a call with glb_quantize 0 and before the first call; MVS_ERR_INVALID for a null argument). */
 typedef struct mvs_glb {
     uint64_t n_bytes;
     uint8_t* data;                               /* [n_bytes] */
@@ -825,6 +837,13 @@ mvs_status mvs_ctx_build_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atl
 mvs_status mvs_ctx_save_glb(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,
                             const char* path, const mvs_model_params* params, mvs_glb_stats* stats);
 void mvs_glb_free(mvs_glb* g);
+typedef struct mvs_glb_quant_stats {
+    uint64_t zero_normals;                       /* glTF vertices whose normal has length 0: stored as (0, 0, 0) */
+    uint64_t texcoords_out_of_range;             /* TEXCOORD_0 components of glTF vertices that are NaN or outside [0, 1]: the call was refused */
+    uint64_t index16_primitives;                 /* primitives with 16-bit indices */
+    float ms_bounds, reserved;                   /* device time of the file-wide bounds pass (between ms_indices and ms_gather) */
+} mvs_glb_quant_stats;
+mvs_status mvs_ctx_glb_quant_stats(mvs_ctx* ctx, mvs_glb_quant_stats* out);
 
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is

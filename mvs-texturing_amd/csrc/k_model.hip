@@ -350,7 +350,7 @@ extern "C" {
 void mvs_model_default_params(mvs_model_params* p) {
     if (!p) return;
     p->max_bytes = 0; p->png_level = 0; p->png_device = 0;
-    p->image_format = 0; p->jpeg_quality = 90; p->jpeg_subsampling = 1; p->reserved = 0;
+    p->image_format = 0; p->jpeg_quality = 90; p->jpeg_subsampling = 1; p->glb_quantize = 0;
 }
 
 mvs_status mvs_ctx_build_model(mvs_ctx* ctx, const mvs_atlas_set* atlases, int atlases_on_device, const float* vertex_normals, int normals_on_device,

@@ -155,7 +155,7 @@ class AtlasStats(C.Structure):
 
 class ModelParams(C.Structure):
     _fields_ = [("max_bytes", C.c_uint64), ("png_level", C.c_int32), ("png_device", C.c_int32),
-                ("image_format", C.c_int32), ("jpeg_quality", C.c_int32), ("jpeg_subsampling", C.c_int32), ("reserved", C.c_int32)]
+                ("image_format", C.c_int32), ("jpeg_quality", C.c_int32), ("jpeg_subsampling", C.c_int32), ("glb_quantize", C.c_int32)]
 
 
 class ModelText(C.Structure):
@@ -178,6 +178,14 @@ GLB_MS = ("ms_keys", "ms_sort", "ms_number", "ms_indices", "ms_gather", "ms_png"
 
 class GlbStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in GLB_COUNTS] + [(k, C.c_float) for k in GLB_MS]
+
+
+GLB_QUANT_COUNTS = ("zero_normals", "texcoords_out_of_range", "index16_primitives")
+GLB_QUANT_MS = ("ms_bounds",)
+
+
+class GlbQuantStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in GLB_QUANT_COUNTS] + [(k, C.c_float) for k in GLB_QUANT_MS] + [("reserved", C.c_float)]
 
 
 class Glb(C.Structure):
@@ -320,6 +328,7 @@ def load_library():
         "mvs_write_png": [C.c_char_p, vp, u32, u32, C.c_int32],
         "mvs_ctx_build_glb": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.POINTER(ModelParams), C.POINTER(Glb), C.POINTER(GlbStats)],
         "mvs_ctx_save_glb": [vp, C.POINTER(AtlasSet), i32, vp, i32, C.c_char_p, C.POINTER(ModelParams), C.POINTER(GlbStats)], "mvs_glb_free": [C.POINTER(Glb)],
+        "mvs_ctx_glb_quant_stats": [vp, C.POINTER(GlbQuantStats)],
         "mvs_ctx_encode_pngs": [vp, u32, vp, vp, vp, vp, i32, C.POINTER(PngSet), C.POINTER(PngStats)], "mvs_png_set_free": [C.POINTER(PngSet)],
         "mvs_ctx_deflate_rle": [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)], "mvs_png_free": [vp],
         "mvs_ctx_encode_jpegs": [vp, u32, vp, vp, vp, vp, i32, C.c_int32, C.c_int32, C.POINTER(PngSet), C.POINTER(JpegStats)], "mvs_jpeg_set_free": [C.POINTER(PngSet)],
@@ -956,17 +965,28 @@ class Context:
         _check_with_stats(self.L, rc, stats)
         return stats
 
+    def _glb_stats(self, st):
+        """mvs_glb_stats as a dict, with the last call's mvs_glb_quant_stats (ms_bounds, zero_normals, texcoords_out_of_range,
+        index16_primitives: all zero under glb_quantize 0) beside it"""
+        qs = GlbQuantStats()
+        _check(self.L, self.L.mvs_ctx_glb_quant_stats(self.h, C.byref(qs)))
+        stats = _stats_dict(st)
+        stats.update((k, getattr(qs, k)) for k in GLB_QUANT_COUNTS + GLB_QUANT_MS)
+        return stats
+
     def build_glb(self, atlases, vertex_normals=None, params=None):
         """Row f11: the textured model as one binary glTF 2.0 file (mvs_ctx_build_glb; DESIGN.md section 4 "Model output" item 8) on the
         context's mesh and an atlas set -- the dict of texture_atlases, all host arrays or all DevArrays / CUDA tensors; without
         atlas_size or image the file carries no images.  vertex_normals: (n_verts, 3) host or device array, or None: no NORMAL attribute.
         Returns (bytes, stats).  params: default_model_params(...) as save_model reads it -- the embedded PNGs are the files it would
-        write; max_bytes caps the file.  A refusal raises MvsError with `.stats` holding the counts."""
+        write; max_bytes caps the file; glb_quantize=1 stores the geometry under KHR_mesh_quantization (item 10: 16-bit positions on
+        one grid for the file, 16-bit texture coordinates, 8-bit unit normals, 16-bit indices per primitive where they fit).  A refusal
+        raises MvsError with `.stats` holding the counts."""
         ps, dev, pn, dn, p, held = self._model_call(atlases, vertex_normals, params)
         res, st = Glb(), GlbStats()
         self._keep["glb"] = held
         rc = self.L.mvs_ctx_build_glb(self.h, C.byref(ps), dev, pn, dn, C.byref(p), C.byref(res), C.byref(st))
-        stats = _stats_dict(st)
+        stats = self._glb_stats(st)
         _check_with_stats(self.L, rc, stats)
         data = C.string_at(res.data, res.n_bytes)
         self.L.mvs_glb_free(C.byref(res))
@@ -978,7 +998,7 @@ class Context:
         st = GlbStats()
         self._keep["glb"] = held
         rc = self.L.mvs_ctx_save_glb(self.h, C.byref(ps), dev, pn, dn, os.fspath(path).encode(), C.byref(p), C.byref(st))
-        stats = _stats_dict(st)
+        stats = self._glb_stats(st)
         _check_with_stats(self.L, rc, stats)
         return stats
 
@@ -1143,7 +1163,9 @@ def default_atlas_params(**kw):
 
 def default_model_params(**kw):
     """mvs_model_default_params (max_bytes 0 = no cap, png_level 0 = stored deflate blocks, png_device 0 = PNGs encoded on the host,
-    image_format 0 = PNG, jpeg_quality 90, jpeg_subsampling 1 = 4:2:0) with overrides; image_format: "png" | "jpeg" | 0 | 1"""
+    image_format 0 = PNG, jpeg_quality 90, jpeg_subsampling 1 = 4:2:0, glb_quantize 0 = float32 geometry in the .glb) with overrides;
+    image_format: "png" | "jpeg" | 0 | 1; glb_quantize=1: build_glb / save_glb / texture_model(format="glb" | "both") write the geometry
+    under KHR_mesh_quantization (DESIGN.md section 4 "Model output" item 10); the OBJ route does not read it"""
     if isinstance(kw.get("image_format"), str):
         if kw["image_format"] not in IMAGE_FORMATS:
             raise ValueError("default_model_params: image_format must be \"png\" or \"jpeg\", not %r" % (kw["image_format"],))

@@ -6,7 +6,13 @@ number, indices, gather; events on the context's stream), its host times (PNGs, 
 number of glTF vertices NP; the .glb's bytes beside the .obj + .mtl bytes and beside everything save_model writes; and the gather pass's
 bytes per second (the attribute bytes it writes) beside a device-to-device copy of that many bytes timed in the same run.  Unless
 --no-check, the file is parsed (tests/tools/glb_model.py), its BIN chunk and JSON are compared with the numpy restatement, and its
-embedded PNGs with the files save_model wrote."""
+embedded PNGs with the files save_model wrote.
+   glb_output_time.py --config 3 --quantize [--out profiles/glb_quant_c3.json]
+runs the leg of glb_quantize = 1 (DESIGN.md section 4 "Model output" item 10) instead: save_glb with glb_quantize 1 and with 0 alternate in
+one process with the same image parameters (JPEG at the defaults), and the medians of the timed runs are recorded for both: the file's and
+the geometry's bytes, the device phases (ms_bounds among them), the gather's bytes per second beside a device copy of as many bytes, and
+the ratio of the two gathers.  Unless --no-check the quantised file is parsed (tests/tools/glb_quant_model.py) and compared with the
+restatement."""
 import argparse
 import json
 import os
@@ -27,8 +33,9 @@ ap.add_argument("--config", type=int, default=3)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--out", default=None)
 ap.add_argument("--no-check", action="store_true")
+ap.add_argument("--quantize", action="store_true", help="the glb_quantize = 1 leg beside the float route (profiles/glb_quant_c<config>.json)")
 a = ap.parse_args()
-out_path = a.out or os.path.join(ROOT, "profiles", "glb_c%d.json" % a.config)
+out_path = a.out or os.path.join(ROOT, "profiles", ("glb_quant_c%d.json" if a.quantize else "glb_c%d.json") % a.config)
 
 t0 = time.perf_counter()
 s = M.synth.make_scene(**M.synth.CONFIGS[a.config])
@@ -48,14 +55,95 @@ torch.cuda.synchronize()
 print("scene + labels + rows f5 - f8: %.1f s, %d faces, %d vertices, %d atlases, %d atlas pixels" % (time.perf_counter() - t0, s.n_faces, len(s.verts), ast["atlases"], ast["pixels"]), flush=True)
 
 name = "glb_c%d" % a.config
-GLB_KEYS = M.viewsel.GLB_MS + ("wall_ms",)
+GLB_KEYS = M.viewsel.GLB_MS + M.viewsel.GLB_QUANT_MS + ("wall_ms",)
 OBJ_KEYS = M.viewsel.MODEL_MS + ("wall_ms",)
 res = {"config": a.config, "workload": "BASELINE config %d: %s" % (a.config, M.synth.CONFIGS[a.config]), "faces": s.n_faces, "vertices": int(len(s.verts)), "views": s.n_views,
        "labels": "the library's view selection (sweeps %d)" % ms["sweeps"], "atlases": ast["atlases"], "atlas_pixels": ast["pixels"], "runs": a.runs, "legs": {},
        "note": "save_glb and save_model alternate in one process, same mvs_model_params per leg, vertex normals given, atlases and normals on the device; medians "
                "of the timed runs after one warm-up of each.  ms_keys .. ms_gather: device time from events on the context's stream; ms_png / ms_download / ms_file "
                "(ms_files): host time; wall_ms: host clock around the call"}
+
+
+def device_copy_ms(n_bytes):
+    """median device time of a device-to-device copy of n_bytes"""
+    x = torch.empty(n_bytes, dtype=torch.uint8, device="cuda"); y = torch.empty_like(x)
+    y.copy_(x); torch.cuda.synchronize()
+    copies = []
+    for _ in range(a.runs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); y.copy_(x); e1.record(); torch.cuda.synchronize()
+        copies.append(float(e0.elapsed_time(e1)))
+    return float(np.median(copies))
+
+
+def host_atlases():
+    def dev_host(darr, dtype):
+        dt = np.dtype(dtype); n = darr.shape[0]
+        if n == 0:
+            return np.zeros(0, dt)
+
+        class _Dev:
+            __cuda_array_interface__ = {"shape": (n * dt.itemsize,), "typestr": "|u1", "data": (darr.data_ptr(), False), "version": 2}
+        return torch.as_tensor(_Dev(), device="cuda").cpu().numpy().view(dt)
+    return {k: dev_host(atl[k], dt) for k, dt in (("face_ptr", np.uint32), ("faces", np.uint32), ("tc_ptr", np.uint32), ("texcoords_merged", np.float32), ("texcoord_ids", np.uint32))}
+
+
+def quantize_leg(d):
+    """save_glb with glb_quantize 1 and 0 alternately, the same JPEG parameters: the medians of both and the quantised file's check"""
+    kw = dict(image_format=1)
+    params = {"quantized": M.default_model_params(glb_quantize=1, **kw), "float": M.default_model_params(glb_quantize=0, **kw)}
+    path = {k: os.path.join(d, "%s_%s.glb" % (name, k)) for k in params}
+    for k in params:
+        c.save_glb(atl, path[k], dn, params[k])                     # warm-up
+    runs = {k: [] for k in params}
+    for _ in range(a.runs):
+        for k in params:
+            t = time.perf_counter(); st = c.save_glb(atl, path[k], dn, params[k]); st["wall_ms"] = 1e3 * (time.perf_counter() - t); runs[k].append(st)
+    leg = {"params": kw}
+    for k in params:
+        last = runs[k][-1]
+        med = {m: float(np.median([r[m] for r in runs[k]])) for m in GLB_KEYS}
+        idx_bytes = 4 * last["indices"] if k == "float" else last["geometry_bytes"] - (16 if normals is not None else 12) * last["vertices"]
+        attr_bytes = last["geometry_bytes"] - idx_bytes
+        copy_ms = device_copy_ms(attr_bytes)
+        leg[k] = {"save_glb_ms_median": med, "save_glb_ms_runs": [{m: r[m] for m in GLB_KEYS} for r in runs[k]], "NP": last["vertices"], "indices": last["indices"],
+                  "primitives": last["primitives"], "index16_primitives": last["index16_primitives"], "zero_normals": last["zero_normals"],
+                  "glb": {m: last[m] for m in ("json_bytes", "geometry_bytes", "image_bytes", "file_bytes")}, "index_bytes": idx_bytes, "file_on_disk": os.path.getsize(path[k]),
+                  "gather": {"attribute_bytes": attr_bytes, "gb_per_s": attr_bytes / (med["ms_gather"] * 1e-3) / 1e9 if med["ms_gather"] > 0 else None, "device_copy_ms": copy_ms,
+                             "device_copy_gb_per_s": attr_bytes / (copy_ms * 1e-3) / 1e9 if copy_ms > 0 else None, "gather_over_copy": med["ms_gather"] / copy_ms if copy_ms > 0 else None}}
+    q, f = leg["quantized"], leg["float"]
+    leg["quantized_over_float"] = {"file_bytes": q["glb"]["file_bytes"] / f["glb"]["file_bytes"], "geometry_bytes": q["glb"]["geometry_bytes"] / f["glb"]["geometry_bytes"],
+                                   "ms_gather": q["save_glb_ms_median"]["ms_gather"] / f["save_glb_ms_median"]["ms_gather"],
+                                   "ms_bounds_plus_gather_over_float_gather": (q["save_glb_ms_median"]["ms_bounds"] + q["save_glb_ms_median"]["ms_gather"]) / f["save_glb_ms_median"]["ms_gather"],
+                                   "ms_indices": q["save_glb_ms_median"]["ms_indices"] / f["save_glb_ms_median"]["ms_indices"], "wall_ms": q["save_glb_ms_median"]["wall_ms"] / f["save_glb_ms_median"]["wall_ms"]}
+    print("quantize", json.dumps({k: leg[k] for k in ("quantized_over_float",)}), json.dumps({k: {m: leg[k][m] for m in ("save_glb_ms_median", "glb", "gather")} for k in params}), flush=True)
+    if not a.no_check:
+        import glb_quant_model as QM
+        t = time.perf_counter()
+        with open(path["quantized"], "rb") as fh:
+            got = QM.parse_glb(fh.read())
+        want = QM.restate(s.verts, s.faces, host_atlases(), normals, got["images"], "image/jpeg")
+        leg["file_equals_restatement"] = bool(got["bin"] == want["bin"] and QM.json_equal(got["json"], want["json"]))
+        print("quantize: parsed and compared with the numpy restatement in %.1f s: %s" % (time.perf_counter() - t, leg["file_equals_restatement"]), flush=True)
+    return leg
+
+
+def write_result():
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out_path)
+
+
 tmp = tempfile.mkdtemp(prefix="glb_output_")
+if a.quantize:
+    try:
+        res["legs"]["quantize"] = quantize_leg(tmp)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    c.close()
+    write_result()
+    sys.exit(0)
 try:
     for leg, kw in (("png_level_0", dict()), ("png_device", dict(png_device=1))):
         p = M.default_model_params(**kw)
@@ -72,15 +160,7 @@ try:
         gmed = {k: float(np.median([r[k] for r in gr])) for k in GLB_KEYS}
         omed = {k: float(np.median([r[k] for r in orr])) for k in OBJ_KEYS}
         attr_bytes = last["geometry_bytes"] - 4 * last["indices"]
-        x = torch.empty(attr_bytes, dtype=torch.uint8, device="cuda"); y = torch.empty_like(x)
-        y.copy_(x); torch.cuda.synchronize()
-        copies = []
-        for _ in range(a.runs):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); y.copy_(x); e1.record(); torch.cuda.synchronize()
-            copies.append(float(e0.elapsed_time(e1)))
-        del x, y
-        copy_ms = float(np.median(copies))
+        copy_ms = device_copy_ms(attr_bytes)
         text_bytes = size[name + ".obj"] + size[name + ".mtl"]
         res["legs"][leg] = {
             "params": kw, "save_glb_ms_median": gmed, "save_model_ms_median": omed, "save_glb_ms_runs": [{k: r[k] for k in GLB_KEYS} for r in gr],
@@ -97,17 +177,7 @@ try:
         print(leg, json.dumps({k: res["legs"][leg][k] for k in ("save_glb_ms_median", "save_model_ms_median", "NP", "glb", "obj_plus_mtl_bytes", "gather")}), flush=True)
         if not a.no_check:
             import glb_model as GM
-
-            def dev_host(darr, dtype):
-                dt = np.dtype(dtype); n = darr.shape[0]
-                if n == 0:
-                    return np.zeros(0, dt)
-
-                class _Dev:
-                    __cuda_array_interface__ = {"shape": (n * dt.itemsize,), "typestr": "|u1", "data": (darr.data_ptr(), False), "version": 2}
-                return torch.as_tensor(_Dev(), device="cuda").cpu().numpy().view(dt)
-            host = {k: dev_host(atl[k], dt) for k, dt in (("face_ptr", np.uint32), ("faces", np.uint32), ("tc_ptr", np.uint32), ("texcoords_merged", np.float32),
-                                                           ("texcoord_ids", np.uint32))}
+            host = host_atlases()
             t = time.perf_counter()
             with open(prefix + ".glb", "rb") as f:
                 got = GM.parse_glb(f.read())
@@ -123,7 +193,4 @@ try:
 finally:
     shutil.rmtree(tmp, ignore_errors=True)
 c.close()
-os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-with open(out_path, "w") as f:
-    json.dump(res, f, indent=1)
-print("wrote", out_path)
+write_result()
