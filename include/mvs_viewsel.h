@@ -758,6 +758,57 @@ void mvs_jpeg_set_free(mvs_jpeg_set* p);
 mvs_status mvs_encode_jpeg(const uint8_t* rgb, uint32_t width, uint32_t height, int32_t quality, int32_t subsampling, uint8_t** out, uint64_t* out_bytes);
 void mvs_jpeg_free(uint8_t* bytes);
 
+/* View input: baseline JPEG files decoded on the device (DESIGN.md section 4 "View input" and csrc/jpeg_dec.h define the format accepted
+ * and the arithmetic; the pixels are libjpeg-turbo's, bit for bit).  Accepted: one SOF0 frame of 8-bit samples, 1 component (written as
+ * R = G = B) or 3 (Y, Cb, Cr; luma sampled 1x1, 2x1 or 2x2, chroma 1x1), one interleaved sequential scan, DQT of 8 bits, DHT classes and
+ * ids 0 / 1, any restart interval or none.  Everything else is MVS_ERR_INVALID with a message that names the file and the reason.
+ * The host reads the markers up to SOS; the entropy data goes to the device as it lies in the file and is unstuffed, cut into
+ * subsequences of option "jpegdec_subseq_bytes" bytes that synchronise themselves, decoded, transformed and converted there
+ * (csrc/k_jpegdec.hip).
+ * mvs_ctx_decode_jpegs: the n files files[i][0, sizes[i]) -> their RGB images, back to back: image i is data[offsets[i], offsets[i + 1])
+ *   = [height[i]][width[i]][3].  out_on_device 0: data is a malloc'ed host copy; 1: data is the context's device buffer, valid until the
+ *   context's next decode.  width, height and offsets are host arrays either way; mvs_rgb_set_free releases what the library allocated.
+ * mvs_scene_set_views_jpeg: mvs_scene_set_views with the images taken from files: view j's file is decoded straight into the context's
+ *   image buffer of view j.  The frame's size must be views[j].width x height; views[j].rgb is not read.  Afterwards the context is
+ *   exactly as mvs_scene_set_views on the decoded pixels leaves it.  A refusal leaves the context without views.  A view whose file
+ *   pointer is null (a PNG, a progressive file, an image that had to be undistorted first) brings its decoded host pixels in views[j].rgb,
+ *   which are uploaded as mvs_scene_set_views uploads them.
+ * mvs_jpeg_probe: MVS_OK and the frame's size when the file's headers are in the accepted format (the entropy data is not read).
+ * params (null: the defaults): max_scratch_bytes bounds the device scratch of one batch (the entropy bytes, the states, 128 bytes of
+ *   coefficients per block and the planes); the files are decoded in batches that fit, and a file that does not fit alone is refused.
+ * stats are filled on refusals too.
+ * mvs_decode_jpeg: the same image on the host, sequentially -- no GPU, no library; *rgb is malloc'ed (mvs_jpeg_free).  coefs (may be
+ *   null): the quantised coefficients int16 [*n_blocks][64] in coding order, index v * 8 + u, malloc'ed (free()). */
+typedef struct mvs_jpegdec_params {
+    uint64_t max_scratch_bytes;                  /* default 1 GiB */
+    uint64_t reserved;
+} mvs_jpegdec_params;
+typedef struct mvs_jpegdec_stats {
+    uint64_t files, file_bytes, entropy_bytes;   /* entropy_bytes: SOS's end .. EOI as it lies in the files */
+    uint64_t stuffed_bytes;                      /* 0x00 bytes behind a 0xFF of entropy data */
+    uint64_t restart_segments, subsequences, windows;
+    uint64_t sync_rounds_max, sync_launches;     /* most rounds one workgroup ran in one launch; launches of the synchronising kernel */
+    uint64_t subseq_exact_after_pass1;           /* subsequences whose first guess already left the exact state */
+    uint64_t blocks, batches;
+    float ms_upload, ms_unstuff, ms_sync, ms_decode, ms_idct, ms_colour;
+} mvs_jpegdec_stats;
+typedef struct mvs_rgb_set {
+    uint32_t n_images, on_device;
+    uint64_t n_bytes;
+    uint8_t* data;                               /* [n_bytes] */
+    uint64_t* offsets;                           /* [n_images + 1] */
+    uint32_t* width;                             /* [n_images] */
+    uint32_t* height;                            /* [n_images] */
+} mvs_rgb_set;
+void mvs_jpegdec_default_params(mvs_jpegdec_params* p);
+mvs_status mvs_ctx_decode_jpegs(mvs_ctx* ctx, const uint8_t* const* files, const uint64_t* sizes, uint32_t n, const mvs_jpegdec_params* params,
+                                int out_on_device, mvs_rgb_set* out_set, mvs_jpegdec_stats* stats);
+void mvs_rgb_set_free(mvs_rgb_set* p);
+mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes,
+                                    const mvs_jpegdec_params* params, mvs_jpegdec_stats* stats);
+mvs_status mvs_jpeg_probe(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height);
+mvs_status mvs_decode_jpeg(const uint8_t* data, uint64_t size, uint8_t** rgb, uint32_t* width, uint32_t* height, int16_t** coefs, uint64_t* n_blocks);
+
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
  * the view list -- stamped all over with its three-digit id in cells of 13 x 6 pixels, and rows f6 (without adjust_colors), f8 and f9

@@ -170,6 +170,13 @@ void upload_through_ring(mvs_ctx* ctx, const std::vector<UploadPiece>& pieces) {
     if (failed.load()) throw HipError("image upload: " + error);
 }
 }  // namespace
+namespace mvs {
+void upload_pieces_through_ring(mvs_ctx* ctx, const uint8_t* const* src, uint8_t* const* dst, const size_t* bytes, size_t n) {
+    std::vector<UploadPiece> pieces;
+    for (size_t k = 0; k < n; ++k) if (bytes[k]) pieces.push_back(UploadPiece{src[k], dst[k], bytes[k]});
+    if (!pieces.empty()) upload_through_ring(ctx, pieces);
+}
+}  // namespace mvs
 
 extern "C" {
 
@@ -228,7 +235,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto* b : ctx->own_rgb) delete b;
-    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx);
+    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx);
     mvs::sweep_graph_release(ctx);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -284,6 +291,7 @@ mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value) {
     else if (n == "mrf_blocks_per_cu") ctx->mrf_blocks_per_cu = std::max(0, (int)value);
     else if (n == "bvh_upper_min_faces") { ctx->kd_disabled = false; ctx->bvh_upper_min_faces = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 0xFFFFFFFFll)); ctx->order_pinned = false; }
     else if (n == "bvh_window") { ctx->kd_disabled = false; ctx->bvh_window = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 0x40000000)); ctx->order_pinned = false; }   // 0 = whole mesh, 1 = no upper-level cuts; otherwise rounded up to a power of two by the builder
+    else if (n == "jpegdec_subseq_bytes") { if (value < 16 || value > 128 || value % 4) return api_fail(MVS_ERR_INVALID, "jpegdec_subseq_bytes: a multiple of 4 in 16 .. 128"); ctx->jpegdec_subseq = (uint32_t)value; }
     else if (n == "face_order") { ctx->face_order = value != 0 ? 1 : 0; ctx->order_pinned = false; }   // takes effect with the next data-cost pass (the active table keeps the order it was made in)
     else return api_fail(MVS_ERR_INVALID, "unknown option " + n);
     return MVS_OK;

@@ -143,6 +143,7 @@ struct DebugDev; // row f10 (k_debug.hip)
 struct GlbDev;   // row f11 (k_glb.hip)
 struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
+struct JpegDecDev;   // view input: JPEG files decoded on the device (k_jpegdec.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -275,6 +276,7 @@ struct mvs_ctx {
     mvs::GlbDev* glb = nullptr;       // row f11 (k_glb.hip)
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
     mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
+    mvs::JpegDecDev* jpegdec = nullptr; uint32_t jpegdec_subseq = 128;   // view input (k_jpegdec.hip); option "jpegdec_subseq_bytes": bytes of entropy data one lane owns
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -430,6 +432,7 @@ void debug_release(mvs_ctx* ctx);
 // k_png.hip, k_jpeg.hip: free their buffers (the routes themselves: image_routes.h)
 void png_release(mvs_ctx* ctx);
 void jpeg_release(mvs_ctx* ctx);
+void jpegdec_release(mvs_ctx* ctx);   // k_jpegdec.hip
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)
@@ -448,6 +451,8 @@ void build_patch_tables(mvs_ctx* ctx, PatchTables& T, const uint32_t* d_adj_ptr,
 mvs_status api_fail(mvs_status st, const std::string& msg);   // records the message of mvs_last_error, returns st
 // the caller's adjacency lists (host or device) as ctx->r_adj_ptr / r_adj in the order of the active table; table_order: they already are
 void set_adjacency(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int on_device, bool table_order);
+// host ranges src[k][0, bytes[k]) -> device dst[k] through the device's pinned upload ring; returns with the stream drained
+void upload_pieces_through_ring(mvs_ctx* ctx, const uint8_t* const* src, uint8_t* const* dst, const size_t* bytes, size_t n);
 void release_upload_rings();   // frees the pinned upload ring of every device (mvs_release_cached; the next host-image upload allocates again)
 // solve.hip
 void sweep_graph_release(mvs_ctx* ctx);   // destroys the sweep loop's executable graph and capture stream

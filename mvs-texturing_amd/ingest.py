@@ -8,13 +8,15 @@
   * mesh: PLY (ascii or binary_little_endian) with vertex x/y/z and face vertex lists, the subset of
     mve::geom::load_ply_mesh the texturing needs (apps/texrecon/texrecon.cpp:52-60).
   * image decode stays on the host (PIL), exactly as in the reference it is outside the timed window.
+    With `device_jpeg` (CLI --device-jpeg) the views that are baseline JPEG files without distortion coefficients are decoded
+    on the GPU instead (viewsel.Context.set_views_jpeg; DESIGN.md section 4 "View input"): the same pixels, bit for bit.
 
 Lens undistortion (generate_texture_views.cpp:153-165, MVE image_undistort_k2k4 / _vsfm; row f4) runs on the GPU
 (mvs_undistort_image) when a `.cam` carries a non-zero first distortion coefficient.
 
 This is harness code (plumbing around the C ABI); the compute runs in libmvs_viewsel.so.
 
-CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area]
+CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg]
 """
 import os
 import struct
@@ -195,14 +197,32 @@ def write_ply(path, verts, faces):
         f.write(rec.tobytes())
 
 
-def load_scene(scene_dir, mesh_path=None):
+def load_scene(scene_dir, mesh_path=None, keep_jpeg=False):
     """A synth.Scene-like object from a folder of .cam + image pairs (and optionally a PLY mesh, prepared as
-    texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given)."""
+    texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given).
+    keep_jpeg: a view without distortion coefficients whose file is a baseline JPEG in the format the device route accepts
+    (viewsel.jpeg_probe) is not decoded: its bytes go to s.jpeg_files[j] and s.images[j] is None, for Context.set_views_jpeg.  Every
+    other view is decoded here as without the flag, and its s.jpeg_files[j] is None."""
     from .synth import Scene
     s = Scene()
+    s.jpeg_files = []
     cams = {"pos": [], "viewdir": [], "K": [], "w2c": [], "width": [], "height": []}
     for cam_path, img_path in list_scene_folder(scene_dir):
         cam = read_cam_file(cam_path)
+        if keep_jpeg and cam.dist[0] == 0.0:
+            from .viewsel import jpeg_probe
+            with open(img_path, "rb") as f:
+                data = f.read()
+            size = jpeg_probe(data) if data[:2] == b"\xff\xd8" else None
+            if size is not None:
+                w, h = size
+                arr = camera_arrays(cam, w, h)
+                for k in ("pos", "viewdir", "K", "w2c"):
+                    cams[k].append(arr[k])
+                cams["width"].append(w); cams["height"].append(h)
+                s.images.append(None); s.jpeg_files.append(data)
+                continue
+        s.jpeg_files.append(None)
         img = load_image_rgb8(img_path)
         if cam.dist[0] != 0.0:   # generate_texture_views.cpp:153-165: k2k4 when both coefficients are set, else the VisualSFM model
             from .viewsel import undistort_image
@@ -250,17 +270,21 @@ def save_scene_folder(scene, scene_dir, mesh_path=None):
         write_ply(mesh_path, scene.verts, scene.faces)
 
 
-def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none"):
-    """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec"""
+def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False):
+    """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec.
+    device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)"""
     from . import viewsel as V
-    s = load_scene(scene_dir, mesh_path)
+    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg)
     st = V.Settings()
     st.data_term = {"area": 0, "gmi": 1}[data_term]
     st.outlier_removal = {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier_removal]
     ctx = V.Context()
     try:
         ctx.set_mesh(s.verts, s.faces, s.normals)
-        ctx.set_views(s.cams, s.images)
+        if device_jpeg:
+            ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images)
+        else:
+            ctx.set_views(s.cams, s.images)
         dstats = ctx.data_costs(st)
         dc = ctx.costs_download()
         labels, mstats = ctx.view_selection(s.adj_ptr, s.adj)
@@ -278,6 +302,7 @@ if __name__ == "__main__":
     ap.add_argument("scene_dir"); ap.add_argument("mesh"); ap.add_argument("out_prefix")
     ap.add_argument("--data-term", default="gmi", choices=["gmi", "area"])
     ap.add_argument("--outlier-removal", default="none", choices=["none", "gauss_damping", "gauss_clamping"])
+    ap.add_argument("--device-jpeg", action="store_true", help="decode baseline JPEG views on the device")
     a = ap.parse_args()
-    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal)
+    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg)
     print("data costs: nnz=%d  labeling: energy=%.3f sweeps=%d unseen=%d" % (d["nnz"], m["energy"], m["sweeps"], m["unseen"]))

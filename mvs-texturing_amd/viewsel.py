@@ -215,6 +215,23 @@ class JpegStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in JPEG_COUNTS] + [(k, C.c_float) for k in JPEG_MS]
 
 
+JPEGDEC_COUNTS = ("files", "file_bytes", "entropy_bytes", "stuffed_bytes", "restart_segments", "subsequences", "windows", "sync_rounds_max", "sync_launches",
+                  "subseq_exact_after_pass1", "blocks", "batches")
+JPEGDEC_MS = ("ms_upload", "ms_unstuff", "ms_sync", "ms_decode", "ms_idct", "ms_colour")
+
+
+class JpegDecParams(C.Structure):
+    _fields_ = [("max_scratch_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class JpegDecStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in JPEGDEC_COUNTS] + [(k, C.c_float) for k in JPEGDEC_MS]
+
+
+class RgbSet(C.Structure):
+    _fields_ = [("n_images", C.c_uint32), ("on_device", C.c_uint32), ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("offsets", C.c_void_p), ("width", C.c_void_p), ("height", C.c_void_p)]
+
+
 class PngSet(C.Structure):
     _fields_ = [("n_images", C.c_uint32), ("reserved", C.c_uint32), ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("offsets", C.c_void_p)]
 
@@ -333,6 +350,11 @@ def load_library():
         "mvs_ctx_deflate_rle": [vp, vp, u64, i32, C.POINTER(vp), C.POINTER(u64)], "mvs_png_free": [vp],
         "mvs_ctx_encode_jpegs": [vp, u32, vp, vp, vp, vp, i32, C.c_int32, C.c_int32, C.POINTER(PngSet), C.POINTER(JpegStats)], "mvs_jpeg_set_free": [C.POINTER(PngSet)],
         "mvs_encode_jpeg": [vp, u32, u32, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(u64)], "mvs_jpeg_free": [vp],
+        "mvs_jpegdec_default_params": [C.POINTER(JpegDecParams)], "mvs_rgb_set_free": [C.POINTER(RgbSet)],
+        "mvs_ctx_decode_jpegs": [vp, vp, vp, u32, C.POINTER(JpegDecParams), i32, C.POINTER(RgbSet), C.POINTER(JpegDecStats)],
+        "mvs_scene_set_views_jpeg": [vp, C.POINTER(CView), u32, vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats)],
+        "mvs_jpeg_probe": [vp, u64, C.POINTER(u32), C.POINTER(u32)],
+        "mvs_decode_jpeg": [vp, u64, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(u64)],
         "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
         "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
         "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
@@ -362,7 +384,7 @@ def load_library():
             fn = getattr(L, name)
         fn.argtypes = argtypes
         if name not in ("mvs_mrf_default_params", "mvs_default_settings", "mvs_csr_free", "mvs_subgraphs_free", "mvs_gsl_default_params",
-                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_glb_free", "mvs_png_set_free", "mvs_png_free", "mvs_jpeg_set_free", "mvs_jpeg_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
+                        "mvs_gsl_result_free", "mvs_gsl_system_free", "mvs_patch_default_params", "mvs_patch_set_free", "mvs_lsl_default_params", "mvs_lsl_result_free", "mvs_atlas_default_params", "mvs_atlas_set_free", "mvs_model_default_params", "mvs_model_text_free", "mvs_glb_free", "mvs_png_set_free", "mvs_png_free", "mvs_jpeg_set_free", "mvs_jpeg_free", "mvs_jpegdec_default_params", "mvs_rgb_set_free", "mvs_ctx_destroy", "mvs_comm_destroy", "mvs_comm_abort", "mvs_shard_destroy"):
             fn.restype = C.c_int
     L._declared = sorted([k for k in sig.keys() if k not in BLOCK_SYMBOLS] + ["mvs_last_error", "mvs_status_string"])
     L._blocks = blocks
@@ -569,6 +591,68 @@ class Context:
         self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)]
         self.n_views = V
         _check(self.L, self.L.mvs_scene_set_views(self.h, arr, V, dev or 0))
+
+    def _view_array(self, cams, V):
+        arr = (CView * V)()
+        for j in range(V):
+            v = arr[j]
+            v.pos[:] = np.asarray(cams["pos"][j], dtype=np.float32).tolist()
+            v.viewdir[:] = np.asarray(cams["viewdir"][j], dtype=np.float32).tolist()
+            v.K[:] = np.asarray(cams["K"][j], dtype=np.float32).ravel().tolist()
+            v.w2c[:] = np.asarray(cams["w2c"][j], dtype=np.float32).ravel().tolist()
+            v.width, v.height = int(cams["width"][j]), int(cams["height"][j])
+        return arr
+
+    @staticmethod
+    def _file_arrays(files):
+        """a list of JPEG files (bytes) as the arrays of pointers and sizes the ABI takes; `held` keeps the bytes alive"""
+        held = [None if f is None else bytes(f) for f in files]
+        n = len(held)
+        ptrs = (C.c_char_p * max(n, 1))(*held)
+        sizes = (C.c_uint64 * max(n, 1))(*[0 if f is None else len(f) for f in held])
+        return held, ptrs, sizes
+
+    def set_views_jpeg(self, cams, files, params=None, images=None):
+        """mvs_scene_set_views_jpeg: set_views with the images taken from baseline JPEG files (a list of bytes), decoded on the device
+        straight into the context's image buffers (DESIGN.md section 4 "View input").  The frames' sizes must be cams' width / height.
+        A view whose entry in `files` is None brings its pixels as images[j], an (H, W, 3) uint8 host array.
+        Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views."""
+        V = len(files)
+        arr = self._view_array(cams, V)
+        held, ptrs, sizes = self._file_arrays(files)
+        pixels = [None if files[j] is not None else np.ascontiguousarray(images[j], np.uint8) for j in range(V)]
+        for j in range(V):
+            if pixels[j] is not None:
+                assert pixels[j].shape == (arr[j].height, arr[j].width, 3)
+                arr[j].rgb = pixels[j].ctypes.data_as(C.c_void_p)
+        st = JpegDecStats()
+        rc = self.L.mvs_scene_set_views_jpeg(self.h, arr, V, ptrs, sizes, C.byref(params) if params is not None else None, C.byref(st))
+        _check_with_stats(self.L, rc, _stats_dict(st))
+        self._keep["views"] = None
+        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)]
+        self.n_views = V
+        return _stats_dict(st)
+
+    def decode_jpegs(self, files, params=None, on_device=False):
+        """mvs_ctx_decode_jpegs: the view input route on its own -- `files` (a list of bytes, baseline JPEG) decoded in one call.  Returns
+        (images, stats): a list of (H, W, 3) uint8 arrays, or with on_device a list of (DevArray, H, W) into the context's buffer, valid
+        until the context's next decode.  The same bytes as the host twin decode_jpeg gives."""
+        n = len(files)
+        held, ptrs, sizes = self._file_arrays(files)
+        res, st = RgbSet(), JpegDecStats()
+        rc = self.L.mvs_ctx_decode_jpegs(self.h, ptrs, sizes, n, C.byref(params) if params is not None else None, 1 if on_device else 0, C.byref(res), C.byref(st))
+        stats = _stats_dict(st)
+        _check_with_stats(self.L, rc, stats)
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        w = np.frombuffer(C.string_at(res.width, 4 * n), np.uint32) if n else np.zeros(0, np.uint32)
+        h = np.frombuffer(C.string_at(res.height, 4 * n), np.uint32) if n else np.zeros(0, np.uint32)
+        if on_device:
+            out = [(DevArray(res.data + int(off[i]), int(off[i + 1] - off[i])), int(h[i]), int(w[i])) for i in range(n)]
+        else:
+            data = np.frombuffer(C.string_at(res.data, res.n_bytes), np.uint8)
+            out = [data[int(off[i]):int(off[i + 1])].reshape(int(h[i]), int(w[i]), 3).copy() for i in range(n)]
+        self.L.mvs_rgb_set_free(C.byref(res))
+        return out, stats
 
     def set_face_range(self, begin, end):
         """positions [begin, end) of the library's face order (the caller's ids with option face_order = 0)"""
@@ -1241,6 +1325,36 @@ def encode_jpeg(img, quality=90, subsampling=1):
     z = C.string_at(out, nb.value)
     L.mvs_jpeg_free(out)
     return z
+
+
+def default_jpegdec_params(**kw):
+    return _default_params(JpegDecParams, "mvs_jpegdec_default_params", kw)
+
+
+def jpeg_probe(data):
+    """mvs_jpeg_probe: (width, height) when the headers of the file `data` (bytes) are a baseline JPEG in the format the device route
+    accepts, else None"""
+    L = load_library()
+    data = bytes(data)
+    w, h = C.c_uint32(), C.c_uint32()
+    return (w.value, h.value) if L.mvs_jpeg_probe(data, len(data), C.byref(w), C.byref(h)) == 0 else None
+
+
+def decode_jpeg(data, coefficients=False):
+    """mvs_decode_jpeg: the (H, W, 3) uint8 image of a baseline JPEG file (bytes) by the host twin of the view input route -- no GPU, no
+    library; the same bytes as Context.decode_jpegs gives and as libjpeg-turbo decodes.  coefficients=True: (image, int16 [blocks, 64]),
+    the quantised coefficients in coding order, index v * 8 + u."""
+    L = load_library()
+    data = bytes(data)
+    out, w, h, co, nb = C.c_void_p(), C.c_uint32(), C.c_uint32(), C.c_void_p(), C.c_uint64()
+    _check(L, L.mvs_decode_jpeg(data, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(co) if coefficients else None, C.byref(nb) if coefficients else None))
+    img = np.frombuffer(C.string_at(out, 3 * w.value * h.value), np.uint8).reshape(h.value, w.value, 3).copy()
+    L.mvs_jpeg_free(out)
+    if not coefficients:
+        return img
+    c = np.frombuffer(C.string_at(co, 128 * nb.value), np.int16).reshape(-1, 64).copy()
+    C.CDLL(None).free(co)
+    return img, c
 
 
 def deflate_rle(data):
