@@ -771,8 +771,9 @@ void mvs_jpeg_free(uint8_t* bytes);
  * mvs_scene_set_views_jpeg: mvs_scene_set_views with the images taken from files: view j's file is decoded straight into the context's
  *   image buffer of view j.  The frame's size must be views[j].width x height; views[j].rgb is not read.  Afterwards the context is
  *   exactly as mvs_scene_set_views on the decoded pixels leaves it.  A refusal leaves the context without views.  A view whose file
- *   pointer is null (a PNG, a progressive file, an image that had to be undistorted first) brings its decoded host pixels in views[j].rgb,
- *   which are uploaded as mvs_scene_set_views uploads them.
+ *   pointer is null (a PNG, a progressive file) brings its decoded host pixels in views[j].rgb, which are uploaded as
+ *   mvs_scene_set_views uploads them.  An image that needs lens undistortion no longer has to come as undistorted host pixels: with
+ *   mvs_scene_set_views_lens (below) it stays a file, or the pixels it was decoded to, and is undistorted on the device.
  * mvs_jpeg_probe: MVS_OK and the frame's size when the file's headers are in the accepted format (the entropy data is not read).
  * params (null: the defaults): max_scratch_bytes bounds the device scratch of one batch (the entropy bytes, the states, 128 bytes of
  *   coefficients per block and the planes); the files are decoded in batches that fit, and a file that does not fit alone is refused.
@@ -808,6 +809,38 @@ mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_
                                     const mvs_jpegdec_params* params, mvs_jpegdec_stats* stats);
 mvs_status mvs_jpeg_probe(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height);
 mvs_status mvs_decode_jpeg(const uint8_t* data, uint64_t size, uint8_t** rgb, uint32_t* width, uint32_t* height, int16_t** coefs, uint64_t* n_blocks);
+
+/* View input: lens undistortion on the device (row f4's arithmetic -- csrc/lens.h states it once for undistort_kernel, the batched kernel
+ * and the host twin; DESIGN.md section 4 "View input").  A view comes as pixels or as a baseline JPEG file together with its lens, is
+ * uploaded and / or decoded once into a staging buffer of the context, and ONE launch per batch (csrc/k_lens.hip) writes the
+ * undistorted pixels of all the batch's views into the context's image buffers: the bytes of mvs_undistort_image on every image.
+ * mvs_lens: the .cam file's focal length and distortion coefficients.  dist0 == 0: the image is taken as it is
+ *   (generate_texture_views.cpp:153); dist1 != 0: the k2k4 model; dist1 == 0: the VisualSFM model.
+ * mvs_scene_set_views_lens: lens[j] belongs to view j.  files == null: every view brings host pixels in views[j].rgb (sizes is not read, jpeg_stats
+ *   stays zero, jpeg_params gives max_scratch_bytes only); otherwise the files[j] / views[j].rgb rule of every view is that of mvs_scene_set_views_jpeg.
+ *   A view with dist0 != 0 goes through staging: the 3 * width * height bytes count towards its scratch in the batch cut of the files
+ *   (jpeg_params->max_scratch_bytes), and pixel views are staged in groups of at most max_scratch_bytes; a view that does not fit alone is
+ *   refused with its number and both sizes.  Views with dist0 == 0 take the path of mvs_scene_set_views_jpeg: no staging, no extra pass.
+ *   Afterwards the context is exactly as mvs_scene_set_views on the undistorted pixels leaves it.  A refusal leaves the context without views:
+ *   until another view input follows, mvs_ctx_data_costs is MVS_ERR_STATE (not the empty table of a scene of zero views).
+ * mvs_ctx_undistort_images: the route on its own -- n host images [heights[i]][widths[i]][3] -> their undistorted images back to back in
+ *   an mvs_rgb_set as mvs_ctx_decode_jpegs returns one (out_on_device 1: the context's buffer, valid until its next call of this entry).
+ *   Image starts are deliberately not aligned.  dist0 == 0 copies.
+ * Refusals are MVS_ERR_INVALID and name the view and the reason: dist0 != 0 with flen not positive, a non-finite field, reserved != 0.
+ * lens_stats (may be null) are filled on refusals too.
+ * mvs_undistort_image_host: the same image on the host, sequentially -- no GPU. */
+typedef struct mvs_lens { float flen, dist0, dist1; uint32_t reserved; } mvs_lens;
+typedef struct mvs_lens_stats {
+    uint64_t views_undistorted, views_copied;    /* by the batched kernel: dist0 != 0 / dist0 == 0 (mvs_ctx_undistort_images only) */
+    uint64_t pixels, pixels_no_source;           /* of the undistorted views; pixels left black because they have no source */
+    uint64_t staging_bytes, batches;             /* the most bytes staged at one time; launches of the batched kernel */
+    float ms_upload, ms_undistort;               /* host time of the pixel uploads into staging; device time of the launches */
+} mvs_lens_stats;
+mvs_status mvs_scene_set_views_lens(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
+                                    const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats);
+mvs_status mvs_ctx_undistort_images(mvs_ctx* ctx, const uint8_t* const* images, const uint32_t* widths, const uint32_t* heights, const mvs_lens* lens, uint32_t n,
+                                    int out_on_device, mvs_rgb_set* out_set, mvs_lens_stats* stats);
+mvs_status mvs_undistort_image_host(const uint8_t* rgb, int32_t width, int32_t height, float flen, float dist0, float dist1, uint8_t* out);
 
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
@@ -899,7 +932,7 @@ mvs_status mvs_ctx_glb_quant_stats(mvs_ctx* ctx, mvs_glb_quant_stats* out);
 /* Row f4: the undistortion step of from_images_and_camera_files (generate_texture_views.cpp:153-165): dist0 == 0 copies the
  * image; dist0 != 0 and dist1 != 0 is mve::image::image_undistort_k2k4(image, flen, dist0, dist1); dist0 != 0 and dist1 == 0 is
  * image_undistort_vsfm(image, flen, dist0).  rgb / out: host arrays of width * height * 3 bytes.  MVE is absent: the two
- * models are DEFINED in csrc/k_prep.hip (and restated in the oracle) from recollection of mve/image_tools.h. */
+ * models are DEFINED in csrc/lens.h (and restated in the oracle) from recollection of mve/image_tools.h. */
 mvs_status mvs_undistort_image(const uint8_t* rgb, int32_t width, int32_t height, float flen, float dist0, float dist1, uint8_t* out);
 
 /* Label-space compression for scenes with hundreds of candidate views per face (BASELINE config 5): keeps, per face, the

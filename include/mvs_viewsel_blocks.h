@@ -61,6 +61,10 @@ mvs_status mvs_ctx_costs_upload_ordered(mvs_ctx* ctx, const mvs_csr* csr_in_posi
  * gamma instantiations can be held to the CPU models of tone mapping `none` on permuted images: every texel read has to go through the
  * table.  Null restores the gamma table (mvs_tone_table).  Row f8's correction is not affected. */
 mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256_host_or_null);
+/* HARNESS ONLY (tests/test_gpu_lens.py): the context's image of one view, width * height * 3 bytes, copied to the host as it lies -- whatever
+ * mvs_scene_set_views, _jpeg or _lens left there; nothing is launched.  *n_bytes = the size; out_host == null: the size only; a smaller
+ * buffer or view >= n_views: MVS_ERR_INVALID; MVS_ERR_STATE on a context without views. */
+mvs_status mvs_ctx_view_image(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----
  * Every rank holds the FULL cost table and adjacency (288 GB of HBM make the

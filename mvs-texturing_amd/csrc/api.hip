@@ -235,7 +235,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto* b : ctx->own_rgb) delete b;
-    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx);
+    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx); mvs::lens_release(ctx);
     mvs::sweep_graph_release(ctx);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -357,6 +357,7 @@ mvs_status mvs_scene_set_views_from(mvs_ctx* ctx, const mvs_view* views, uint32_
 static mvs_status set_views_impl(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, int rgb_on_device, const mvs_image_source* src) {
     if (!ctx || (!views && n_views)) return api_fail(MVS_ERR_INVALID, "null argument");
     MVS_CTX_API_BEGIN
+    ctx->views_refused = false;
     // image buffers of an earlier call are reused (a context that serves one scene after another allocates once)
     if (rgb_on_device) { for (auto* b : ctx->own_rgb) delete b; ctx->own_rgb.clear(); }
     else { while (ctx->own_rgb.size() > n_views) { delete ctx->own_rgb.back(); ctx->own_rgb.pop_back(); } }
@@ -405,9 +406,7 @@ static mvs_status set_views_impl(mvs_ctx* ctx, const mvs_view* views, uint32_t n
         }
         if (v.width < 2 || v.height < 2 || !v.rgb) throw StatusError(MVS_ERR_INVALID, "view " + std::to_string(j) + ": bad image");
         ViewParams& p = ctx->h_views[j];
-        memcpy(p.pos, v.pos, sizeof(p.pos)); memcpy(p.viewdir, v.viewdir, sizeof(p.viewdir));
-        memcpy(p.K, v.K, sizeof(p.K)); memcpy(p.w2c, v.w2c, sizeof(p.w2c));
-        p.width = v.width; p.height = v.height;
+        p = view_params_of(v);
         if (rgb_on_device) p.rgb = v.rgb;
         else {
             if (ctx->own_rgb.size() <= j) ctx->own_rgb.push_back(new DBuf<uint8_t>());

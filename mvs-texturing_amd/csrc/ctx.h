@@ -144,6 +144,7 @@ struct GlbDev;   // row f11 (k_glb.hip)
 struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
 struct JpegDecDev;   // view input: JPEG files decoded on the device (k_jpegdec.hip)
+struct LensDev;      // view input: lens undistortion on the device (k_lens.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -202,6 +203,7 @@ struct mvs_ctx {
     std::vector<size_t> gmi_off, mask_off, msum_off;
     mvs::DBuf<size_t> view_off;
     bool mesh_dirty = true, views_dirty = true;
+    bool views_refused = false;      // mvs_scene_set_views_lens refused its views and no other view input followed: a data-cost pass is MVS_ERR_STATE
 
     // ---- the library's own mesh layout (k_bvh.hip build_scene_order; DESIGN.md "Face order") ----
     // The caller's mesh arrives in file order (calculate_data_costs.cpp:136-138); nothing about it is assumed.  Every data-cost pass
@@ -277,6 +279,7 @@ struct mvs_ctx {
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
     mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
     mvs::JpegDecDev* jpegdec = nullptr; uint32_t jpegdec_subseq = 128;   // view input (k_jpegdec.hip); option "jpegdec_subseq_bytes": bytes of entropy data one lane owns
+    mvs::LensDev* lens = nullptr;     // view input: the staging buffer, the per-view table and the output of the lens route (k_lens.hip)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -332,6 +335,14 @@ struct mvs_ctx {
 };
 
 namespace mvs {
+// a caller's view as the kernels read it: the camera and the size (every view input fills in rgb itself)
+inline ViewParams view_params_of(const mvs_view& v) {
+    ViewParams p{};
+    memcpy(p.pos, v.pos, sizeof(p.pos)); memcpy(p.viewdir, v.viewdir, sizeof(p.viewdir));
+    memcpy(p.K, v.K, sizeof(p.K)); memcpy(p.w2c, v.w2c, sizeof(p.w2c));
+    p.width = v.width; p.height = v.height;
+    return p;
+}
 // RAII stage marker; no-op unless ctx->profile
 struct Prof {
     mvs_ctx* c; size_t idx; bool on;
@@ -433,6 +444,16 @@ void debug_release(mvs_ctx* ctx);
 void png_release(mvs_ctx* ctx);
 void jpeg_release(mvs_ctx* ctx);
 void jpegdec_release(mvs_ctx* ctx);   // k_jpegdec.hip
+void lens_release(mvs_ctx* ctx);      // k_lens.hip
+// k_lens.hip: the context's staging buffer with room for `bytes` (16-byte aligned; growing it loses what it held)
+uint8_t* lens_staging(mvs_ctx* ctx, uint64_t bytes);
+// k_jpegdec.hip: the views whose files[j] is not null, decoded in batches whose scratch fits params->max_scratch_bytes (null: the default) --
+// view j into dst[j], or, where staged[j] is not 0, into the context's lens staging (lens_staging), whose 3 * width * height bytes count
+// towards the view's scratch.  After every batch that staged views, after_batch(views, pixels) gets their numbers and where their decoded
+// pixels lie (valid until it returns).  `who` starts the messages; throws as mvs_scene_set_views_jpeg refuses.
+typedef std::function<void(const std::vector<uint32_t>& views, const std::vector<const uint8_t*>& pixels)> StagedBatchFn;
+void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
+                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

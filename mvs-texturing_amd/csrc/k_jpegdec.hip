@@ -505,22 +505,61 @@ std::vector<HostFile> read_headers(mvs_ctx* ctx, const uint8_t* const* files, co
     }
     return H;
 }
-// all files in batches whose scratch fits
-void decode_files(mvs_ctx* ctx, const uint8_t* const* files, const std::vector<HostFile>& H, uint8_t* const* dst, const mvs_jpegdec_params& P, const char* who, mvs_jpegdec_stats& st) {
-    JpegDecDev& D = row_dev(ctx->jpegdec);
+// the batch cut: files [cut[k], cut[k + 1]) are batch k, the longest run whose scratch fits; a file that does not fit alone is refused
+std::vector<uint32_t> cut_batches(const std::vector<HostFile>& H, const mvs_jpegdec_params& P, const char* who) {
     const uint32_t n = (uint32_t)H.size();
     for (uint32_t k = 0; k < n; ++k)
         if (H[k].scratch > P.max_scratch_bytes)
             throw StatusError(MVS_ERR_INVALID, std::string(who) + ": view " + std::to_string(H[k].view) + " needs " + std::to_string(H[k].scratch) + " bytes of scratch, max_scratch_bytes is " + std::to_string(P.max_scratch_bytes));
+    std::vector<uint32_t> cut{0u};
     for (uint32_t a = 0; a < n;) {
         uint32_t b = a; uint64_t sum = 0;
         while (b < n && b - a < 32768u && (b == a || sum + H[b].scratch <= P.max_scratch_bytes)) sum += H[b++].scratch;   // (an image per grid row: at most 65535)
-        decode_batch(ctx, D, files, H, a, b, dst, who, st);
+        cut.push_back(b);
         a = b;
     }
+    return cut;
+}
+// all files in batches whose scratch fits
+void decode_files(mvs_ctx* ctx, const uint8_t* const* files, const std::vector<HostFile>& H, uint8_t* const* dst, const mvs_jpegdec_params& P, const char* who, mvs_jpegdec_stats& st) {
+    JpegDecDev& D = row_dev(ctx->jpegdec);
+    const std::vector<uint32_t> cut = cut_batches(H, P, who);
+    for (size_t k = 0; k + 1 < cut.size(); ++k) decode_batch(ctx, D, files, H, cut[k], cut[k + 1], dst, who, st);
 }
 
 }  // namespace
+
+// the file views of a scene, some of them through the lens staging (ctx.h)
+void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
+                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch) {
+    const mvs_jpegdec_params P = jpegdec_params(params);
+    std::vector<const uint8_t*> jf; std::vector<uint64_t> js; std::vector<uint32_t> jv;   // the views that come as files
+    for (uint32_t j = 0; j < n_views; ++j) if (files[j]) { jf.push_back(files[j]); js.push_back(sizes[j]); jv.push_back(j); }
+    std::vector<HostFile> H = read_headers(ctx, jf.data(), js.data(), (uint32_t)jf.size(), jv.data(), views, who, st);
+    const uint32_t n = (uint32_t)H.size();
+    auto stage_bytes = [&](uint32_t k) -> uint64_t { return staged[H[k].view] ? align16(3ull * H[k].F.width * H[k].F.height) : 0ull; };
+    for (uint32_t k = 0; k < n; ++k) H[k].scratch += stage_bytes(k);
+    const std::vector<uint32_t> cut = cut_batches(H, P, who);
+    // every batch stages from the buffer's start: it is as large as the largest batch needs
+    uint64_t most = 0;
+    std::vector<uint64_t> off(n, 0);
+    for (size_t b = 0; b + 1 < cut.size(); ++b) {
+        uint64_t sum = 0;
+        for (uint32_t k = cut[b]; k < cut[b + 1]; ++k) { off[k] = sum; sum += stage_bytes(k); }
+        most = std::max(most, sum);
+    }
+    uint8_t* staging = most ? lens_staging(ctx, most) : nullptr;
+    std::vector<uint8_t*> to(n);
+    for (uint32_t k = 0; k < n; ++k) to[k] = staged[H[k].view] ? staging + off[k] : dst[H[k].view];
+    JpegDecDev& D = row_dev(ctx->jpegdec);
+    for (size_t b = 0; b + 1 < cut.size(); ++b) {
+        decode_batch(ctx, D, jf.data(), H, cut[b], cut[b + 1], to.data(), who, st);
+        std::vector<uint32_t> bv; std::vector<const uint8_t*> bp;
+        for (uint32_t k = cut[b]; k < cut[b + 1]; ++k) if (staged[H[k].view]) { bv.push_back(H[k].view); bp.push_back(to[k]); }
+        if (!bv.empty()) after_batch(bv, bp);
+    }
+}
+
 }  // namespace mvs
 
 using namespace mvs;
@@ -576,7 +615,7 @@ mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_
         MVS_HIP(hipSetDevice(ctx->device));
         const mvs_jpegdec_params P = jpegdec_params(params);
         // a refusal leaves the context without views
-        ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0;
+        ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0; ctx->views_refused = false;
         run_with_stats(ctx->stream, stats, st, [&] {
             for (uint32_t j = 0; j < n_views; ++j)
                 if (views[j].width < 2 || views[j].height < 2) throw StatusError(MVS_ERR_INVALID, "view " + std::to_string(j) + ": bad image");
@@ -589,9 +628,7 @@ mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_
             for (uint32_t j = 0; j < n_views; ++j) {
                 const mvs_view& v = views[j];
                 ViewParams& p = hv[j];
-                memcpy(p.pos, v.pos, sizeof(p.pos)); memcpy(p.viewdir, v.viewdir, sizeof(p.viewdir));
-                memcpy(p.K, v.K, sizeof(p.K)); memcpy(p.w2c, v.w2c, sizeof(p.w2c));
-                p.width = v.width; p.height = v.height;
+                p = view_params_of(v);
                 if (ctx->own_rgb.size() <= j) ctx->own_rgb.push_back(new DBuf<uint8_t>());
                 ctx->own_rgb[j]->ensure((size_t)v.width * v.height * 3 + 16);
                 p.rgb = ctx->own_rgb[j]->p;

@@ -216,6 +216,23 @@ mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256) {
     MVS_API_END
 }
 
+// harness only: the context's image of one view as it lies on the device
+mvs_status mvs_ctx_view_image(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
+    if (!ctx || !n_bytes) return api_fail(MVS_ERR_INVALID, "null argument");
+    if (ctx->n_views == 0 || ctx->h_views.size() != ctx->n_views) return api_fail(MVS_ERR_STATE, "view image: the context has no views");
+    if (view >= ctx->n_views) return api_fail(MVS_ERR_INVALID, "view image: view " + std::to_string(view) + " of " + std::to_string(ctx->n_views));
+    MVS_CTX_API_BEGIN
+    const ViewParams& hv = ctx->h_views[view];
+    const uint64_t n = (uint64_t)hv.width * hv.height * 3;
+    *n_bytes = n;
+    if (out_host && cap_bytes < n) throw StatusError(MVS_ERR_INVALID, "view image: buffer too small");
+    if (out_host) {
+        MVS_HIP(hipMemcpyAsync(out_host, hv.rgb, n, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    MVS_API_END
+}
+
 mvs_status mvs_ctx_mrf_setup(mvs_ctx* ctx, const uint32_t* adj_ptr, const uint32_t* adj, int adj_on_device, const mvs_mrf_params* params) {
     if (!ctx || !adj_ptr || !adj) return api_fail(MVS_ERR_INVALID, "null argument");
     if (!ctx->have_costs) return api_fail(MVS_ERR_STATE, "mrf setup needs data costs");

@@ -12,11 +12,14 @@
     on the GPU instead (viewsel.Context.set_views_jpeg; DESIGN.md section 4 "View input"): the same pixels, bit for bit.
 
 Lens undistortion (generate_texture_views.cpp:153-165, MVE image_undistort_k2k4 / _vsfm; row f4) runs on the GPU
-(mvs_undistort_image) when a `.cam` carries a non-zero first distortion coefficient.
+(mvs_undistort_image) when a `.cam` carries a non-zero first distortion coefficient.  With `device_undistort` (CLI
+--device-undistort) such a view is not undistorted here: it goes to the context as the camera took it, together with its lens, and
+is undistorted on the device on its way into the image buffers (viewsel.Context.set_views(lens=) / set_views_jpeg(lens=)): the same
+pixels, bit for bit.  Together with `device_jpeg` a distorted baseline JPEG stays a file.
 
 This is harness code (plumbing around the C ABI); the compute runs in libmvs_viewsel.so.
 
-CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg]
+CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-undistort]
 """
 import os
 import struct
@@ -197,19 +200,33 @@ def write_ply(path, verts, faces):
         f.write(rec.tobytes())
 
 
-def load_scene(scene_dir, mesh_path=None, keep_jpeg=False):
+def _note_restated_models(img_path, cam):
+    # MVE's own routines are not available to compare with: the models are restated from recollection (csrc/lens.h), the VisualSFM
+    # one inverted by guarded Newton steps -- an approximation of upstream, said so here
+    import sys
+    print("[mvs ingest] %s: undistorting with the %s model as restated in this library (approximates MVE's image_undistort_*)"
+          % (os.path.basename(img_path), "k2k4" if cam.dist[1] != 0.0 else "VisualSFM"), file=sys.stderr)
+
+
+def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False):
     """A synth.Scene-like object from a folder of .cam + image pairs (and optionally a PLY mesh, prepared as
     texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given).
     keep_jpeg: a view without distortion coefficients whose file is a baseline JPEG in the format the device route accepts
     (viewsel.jpeg_probe) is not decoded: its bytes go to s.jpeg_files[j] and s.images[j] is None, for Context.set_views_jpeg.  Every
-    other view is decoded here as without the flag, and its s.jpeg_files[j] is None."""
+    other view is decoded here as without the flag, and its s.jpeg_files[j] is None.
+    device_undistort: a view with dist[0] != 0 is not undistorted here; s.lens[j] = (flen, dist0, dist1) carries its coefficients for
+    Context.set_views(lens=) / set_views_jpeg(lens=), and with keep_jpeg such a view stays a file when jpeg_probe accepts it.  The rows of
+    views without distortion are (flen, 0, 0).  Without the flag s.lens is None."""
     from .synth import Scene
     s = Scene()
     s.jpeg_files = []
+    lens = []
     cams = {"pos": [], "viewdir": [], "K": [], "w2c": [], "width": [], "height": []}
     for cam_path, img_path in list_scene_folder(scene_dir):
         cam = read_cam_file(cam_path)
-        if keep_jpeg and cam.dist[0] == 0.0:
+        distorted = cam.dist[0] != 0.0
+        lens.append((cam.flen, cam.dist[0], cam.dist[1]) if distorted and device_undistort else (cam.flen, 0.0, 0.0))
+        if keep_jpeg and (not distorted or device_undistort):
             from .viewsel import jpeg_probe
             with open(img_path, "rb") as f:
                 data = f.read()
@@ -221,17 +238,16 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False):
                     cams[k].append(arr[k])
                 cams["width"].append(w); cams["height"].append(h)
                 s.images.append(None); s.jpeg_files.append(data)
+                if distorted:
+                    _note_restated_models(img_path, cam)
                 continue
         s.jpeg_files.append(None)
         img = load_image_rgb8(img_path)
-        if cam.dist[0] != 0.0:   # generate_texture_views.cpp:153-165: k2k4 when both coefficients are set, else the VisualSFM model
-            from .viewsel import undistort_image
-            import sys
-            # MVE's own routines are not available to compare with: the models are restated from recollection (k_prep.hip
-            # undistort_kernel), the VisualSFM one inverted by guarded Newton steps -- an approximation of upstream, said so here
-            print("[mvs ingest] %s: undistorting with the %s model as restated in this library (approximates MVE's image_undistort_*)"
-                  % (os.path.basename(img_path), "k2k4" if cam.dist[1] != 0.0 else "VisualSFM"), file=sys.stderr)
-            img = undistort_image(img, cam.flen, cam.dist[0], cam.dist[1])
+        if distorted:   # generate_texture_views.cpp:153-165: k2k4 when both coefficients are set, else the VisualSFM model
+            _note_restated_models(img_path, cam)
+            if not device_undistort:
+                from .viewsel import undistort_image
+                img = undistort_image(img, cam.flen, cam.dist[0], cam.dist[1])
         h, w = img.shape[:2]
         arr = camera_arrays(cam, w, h)
         for k in ("pos", "viewdir", "K", "w2c"):
@@ -239,6 +255,7 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False):
         cams["width"].append(w); cams["height"].append(h)
         s.images.append(img)
     n = len(s.images)
+    s.lens = np.array(lens, np.float32).reshape(n, 3) if device_undistort else None
     s.cams = {"pos": np.array(cams["pos"], np.float32).reshape(n, 3), "viewdir": np.array(cams["viewdir"], np.float32).reshape(n, 3),
               "K": np.array(cams["K"], np.float32).reshape(n, 9), "w2c": np.array(cams["w2c"], np.float32).reshape(n, 16),
               "width": np.array(cams["width"], np.int32), "height": np.array(cams["height"], np.int32)}
@@ -270,11 +287,13 @@ def save_scene_folder(scene, scene_dir, mesh_path=None):
         write_ply(mesh_path, scene.verts, scene.faces)
 
 
-def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False):
+def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False):
     """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec.
-    device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)"""
+    device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)
+    device_undistort: the views with distortion coefficients are undistorted on the device on their way in (load_scene's
+    device_undistort, the `lens` of Context.set_views / set_views_jpeg)"""
     from . import viewsel as V
-    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg)
+    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort)
     st = V.Settings()
     st.data_term = {"area": 0, "gmi": 1}[data_term]
     st.outlier_removal = {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier_removal]
@@ -282,9 +301,9 @@ def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none
     try:
         ctx.set_mesh(s.verts, s.faces, s.normals)
         if device_jpeg:
-            ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images)
+            ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images, lens=s.lens)
         else:
-            ctx.set_views(s.cams, s.images)
+            ctx.set_views(s.cams, s.images, lens=s.lens)
         dstats = ctx.data_costs(st)
         dc = ctx.costs_download()
         labels, mstats = ctx.view_selection(s.adj_ptr, s.adj)
@@ -303,6 +322,7 @@ if __name__ == "__main__":
     ap.add_argument("--data-term", default="gmi", choices=["gmi", "area"])
     ap.add_argument("--outlier-removal", default="none", choices=["none", "gauss_damping", "gauss_clamping"])
     ap.add_argument("--device-jpeg", action="store_true", help="decode baseline JPEG views on the device")
+    ap.add_argument("--device-undistort", action="store_true", help="undistort the views with distortion coefficients on the device, on their way in")
     a = ap.parse_args()
-    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg)
+    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort)
     print("data costs: nnz=%d  labeling: energy=%.3f sweeps=%d unseen=%d" % (d["nnz"], m["energy"], m["sweeps"], m["unseen"]))

@@ -228,6 +228,29 @@ class JpegDecStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in JPEGDEC_COUNTS] + [(k, C.c_float) for k in JPEGDEC_MS]
 
 
+LENS_COUNTS = ("views_undistorted", "views_copied", "pixels", "pixels_no_source", "staging_bytes", "batches")
+LENS_MS = ("ms_upload", "ms_undistort")
+
+
+class Lens(C.Structure):
+    _fields_ = [("flen", C.c_float), ("dist0", C.c_float), ("dist1", C.c_float), ("reserved", C.c_uint32)]
+
+
+class LensStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in LENS_COUNTS] + [(k, C.c_float) for k in LENS_MS]
+
+
+def _lens_array(lens, n):
+    """an (n, 3) array of (flen, dist0, dist1) -- or (n, 4) with the reserved word, which must be 0 -- as the ABI's mvs_lens [n]"""
+    a = np.asarray(lens, dtype=np.float32).reshape(n, -1)
+    assert a.shape[1] in (3, 4)
+    arr = (Lens * max(n, 1))()
+    for j in range(n):
+        arr[j].flen, arr[j].dist0, arr[j].dist1 = float(a[j, 0]), float(a[j, 1]), float(a[j, 2])
+        arr[j].reserved = int(a[j, 3]) if a.shape[1] == 4 else 0
+    return arr
+
+
 class RgbSet(C.Structure):
     _fields_ = [("n_images", C.c_uint32), ("on_device", C.c_uint32), ("n_bytes", C.c_uint64), ("data", C.c_void_p), ("offsets", C.c_void_p), ("width", C.c_void_p), ("height", C.c_void_p)]
 
@@ -253,7 +276,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_prep_products", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_prep_products", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table", "mvs_ctx_view_image"))
 
 TONE_MAPPINGS = {"none": 0, "gamma": 1}                                       # tex::ToneMapping (settings.h); the *_params.tone_mapping field
 
@@ -317,6 +340,7 @@ def load_library():
         "mvs_ctx_prep_products": [vp, i32, u32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_costs_upload_ordered": [vp, C.POINTER(CCsr), vp],
         "mvs_ctx_tone_table": [vp, vp],
+        "mvs_ctx_view_image": [vp, u32, vp, u64, C.POINTER(u64)],
         "mvs_gamma_correct": [vp, u64, C.c_float], "mvs_ctx_gamma_correct": [vp, vp, u64, C.c_float, i32], "mvs_tone_table": [u32, vp],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
@@ -355,6 +379,9 @@ def load_library():
         "mvs_scene_set_views_jpeg": [vp, C.POINTER(CView), u32, vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats)],
         "mvs_jpeg_probe": [vp, u64, C.POINTER(u32), C.POINTER(u32)],
         "mvs_decode_jpeg": [vp, u64, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(u64)],
+        "mvs_scene_set_views_lens": [vp, C.POINTER(CView), u32, C.POINTER(Lens), vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats), C.POINTER(LensStats)],
+        "mvs_ctx_undistort_images": [vp, vp, vp, vp, C.POINTER(Lens), u32, i32, C.POINTER(RgbSet), C.POINTER(LensStats)],
+        "mvs_undistort_image_host": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
         "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
         "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
@@ -571,9 +598,13 @@ class Context:
         self.n_faces = int(faces.shape[0])
         _check(self.L, self.L.mvs_scene_set_mesh(self.h, C.byref(m), d0))
 
-    def set_views(self, cams, images):
-        """cams: dict of arrays pos, viewdir, K, w2c, width, height; images: list of (H,W,3) u8 numpy / torch cuda"""
+    def set_views(self, cams, images, lens=None):
+        """cams: dict of arrays pos, viewdir, K, w2c, width, height; images: list of (H,W,3) u8 numpy / torch cuda.
+        lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the images are then host arrays as the camera took them, and the
+        views with dist0 != 0 are undistorted on the device (mvs_scene_set_views_lens; returns the lens stats)"""
         V = len(images)
+        if lens is not None:
+            return self._set_views_lens(cams, [None] * V, images, lens, None)["lens"]
         arr = (CView * V)()
         dev = None
         for j in range(V):
@@ -612,12 +643,70 @@ class Context:
         sizes = (C.c_uint64 * max(n, 1))(*[0 if f is None else len(f) for f in held])
         return held, ptrs, sizes
 
-    def set_views_jpeg(self, cams, files, params=None, images=None):
+    def _set_views_lens(self, cams, files, images, lens, params):
+        """mvs_scene_set_views_lens: the jpeg stats with the lens stats under "lens"; a refusal raises MvsError with them as `.stats`"""
+        V = len(files)
+        arr = self._view_array(cams, V)
+        any_file = any(f is not None for f in files)
+        held, ptrs, sizes = self._file_arrays(files)
+        pixels = [None if files[j] is not None else np.ascontiguousarray(images[j], np.uint8) for j in range(V)]
+        for j in range(V):
+            if pixels[j] is not None:
+                assert pixels[j].shape == (arr[j].height, arr[j].width, 3)
+                arr[j].rgb = pixels[j].ctypes.data_as(C.c_void_p)
+        st, ls = JpegDecStats(), LensStats()
+        rc = self.L.mvs_scene_set_views_lens(self.h, arr, V, _lens_array(lens, V), ptrs if any_file else None, sizes if any_file else None,
+                                             C.byref(params) if params is not None else None, C.byref(st), C.byref(ls))
+        stats = _stats_dict(st)
+        stats["lens"] = _stats_dict(ls)
+        self._keep["views"] = None
+        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)] if rc == 0 else []
+        self.n_views = V if rc == 0 else 0
+        _check_with_stats(self.L, rc, stats)
+        return stats
+
+    def undistort_images(self, images, lens, on_device=False):
+        """mvs_ctx_undistort_images: the lens route on its own -- `images` (a list of (H, W, 3) uint8 host arrays) with lens[i] = (flen, dist0,
+        dist1), undistorted in one call.  Returns (images, stats): a list of (H, W, 3) uint8 arrays, or with on_device a list of
+        (DevArray, H, W) into the context's buffer, valid until the context's next call.  The same bytes as undistort_image gives."""
+        n = len(images)
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in images]
+        assert all(i.ndim == 3 and i.shape[2] == 3 for i in imgs)
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        w = (C.c_uint32 * max(n, 1))(*[i.shape[1] for i in imgs]); h = (C.c_uint32 * max(n, 1))(*[i.shape[0] for i in imgs])
+        res, st = RgbSet(), LensStats()
+        rc = self.L.mvs_ctx_undistort_images(self.h, ptrs, w, h, _lens_array(lens, n), n, 1 if on_device else 0, C.byref(res), C.byref(st))
+        stats = _stats_dict(st)
+        _check_with_stats(self.L, rc, stats)
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        if on_device:
+            out = [(DevArray(res.data + int(off[i]), int(off[i + 1] - off[i])), imgs[i].shape[0], imgs[i].shape[1]) for i in range(n)]
+        else:
+            data = np.frombuffer(C.string_at(res.data, res.n_bytes), np.uint8)
+            out = [data[int(off[i]):int(off[i + 1])].reshape(imgs[i].shape).copy() for i in range(n)]
+        self.L.mvs_rgb_set_free(C.byref(res))
+        return out, stats
+
+    def view_image(self, j):
+        """the context's image of view j as it lies on the device, (H, W, 3) uint8 (mvs_ctx_view_image, building-blocks library; test
+        harness only)"""
+        n = C.c_uint64()
+        _check(self.L, self.L.mvs_ctx_view_image(self.h, j, None, 0, C.byref(n)))
+        buf = np.empty(n.value, np.uint8)
+        _check(self.L, self.L.mvs_ctx_view_image(self.h, j, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        w, h = self._view_sizes[j]
+        return buf.reshape(h, w, 3)
+
+    def set_views_jpeg(self, cams, files, params=None, images=None, lens=None):
         """mvs_scene_set_views_jpeg: set_views with the images taken from baseline JPEG files (a list of bytes), decoded on the device
         straight into the context's image buffers (DESIGN.md section 4 "View input").  The frames' sizes must be cams' width / height.
         A view whose entry in `files` is None brings its pixels as images[j], an (H, W, 3) uint8 host array.
-        Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views."""
+        Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views.
+        lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the views with dist0 != 0, files and pixels alike, are undistorted
+        on the device (mvs_scene_set_views_lens); the stats then carry the lens stats under "lens"."""
         V = len(files)
+        if lens is not None:
+            return self._set_views_lens(cams, files, images if images is not None else [None] * V, lens, params)
         arr = self._view_array(cams, V)
         held, ptrs, sizes = self._file_arrays(files)
         pixels = [None if files[j] is not None else np.ascontiguousarray(images[j], np.uint8) for j in range(V)]
@@ -1576,6 +1665,16 @@ def undistort_image(rgb, flen, dist0, dist1):
     assert rgb.ndim == 3 and rgb.shape[2] == 3
     out = np.empty_like(rgb)
     _check(L, L.mvs_undistort_image(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], float(flen), float(dist0), float(dist1), out.ctypes.data))
+    return out
+
+
+def undistort_host(rgb, flen, dist0, dist1):
+    """mvs_undistort_image_host: undistort_image by the sequential host twin of csrc/lens.h -- no GPU; the same bytes"""
+    L = load_library()
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    out = np.empty_like(rgb)
+    _check(L, L.mvs_undistort_image_host(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], float(flen), float(dist0), float(dist1), out.ctypes.data))
     return out
 
 
