@@ -842,6 +842,33 @@ mvs_status mvs_ctx_undistort_images(mvs_ctx* ctx, const uint8_t* const* images, 
                                     int out_on_device, mvs_rgb_set* out_set, mvs_lens_stats* stats);
 mvs_status mvs_undistort_image_host(const uint8_t* rgb, int32_t width, int32_t height, float flen, float dist0, float dist1, uint8_t* out);
 
+/* View input: view masks (DESIGN.md section 4 "View input" item 10).  ONE rule: a masked pixel is an invalid pixel, and nothing else changes.
+ * A view may carry a mask, one byte per pixel, [height][width] of the view, 0 = leave out, anything else = keep.  The view's validity
+ * before the erosion is (flood-fill validity AND keep); under the gradient term erode_validity_mask runs on that.  The image, the gradient
+ * magnitude and the footprint sampling are untouched: a (face, view) pair is dropped exactly when valid_pixel fails at one of its three
+ * projected vertices, so a masked blob strictly inside one large projected triangle does not exclude that pair -- dilate the mask for a margin.
+ * Rows f5 to f11 do not see masks.  Upstream has none.
+ * mvs_scene_set_view_masks: masks[j] belongs to view j (null: view j has no mask); host arrays, or with on_device device arrays that stay
+ *   valid during the call only.  Called after any view input (mvs_scene_set_views, _from, _jpeg, _lens) and before mvs_ctx_data_costs.  All
+ *   null, n_views == 0 with masks == null, or a later view input clears the masks.  A scene without masks runs exactly as before.
+ *   lens (null: none): lens[j].dist0 != 0 says that masks[j] is in the frame the camera took, as the photographs a user paints on are; it is
+ *   then undistorted on the device with row f4's arithmetic, read as a one-channel image of 0 / 255: destination pixel (x, y) is kept iff
+ *   it has a source and linear_at there gives the byte 255.  Views with dist0 == 0 use the mask as it is.
+ *   Host masks travel through the pinned upload ring into the context's staging buffer in batches of at most max_scratch_bytes -- that of
+ *   the view input the views came by (mvs_jpegdec_params; 1 GiB for mvs_scene_set_views) -- and one launch per batch packs them into keep
+ *   words in the layout of the validity mask (csrc/k_viewmask.hip; under a lens csrc/k_lens.hip), kept for masked views only
+ *   (4 * ceil(width / 32) * height bytes each).  A host mask that does not fit alone is refused with the view's number.
+ *   Refusals name the reason and, where there is one, the view: n_views is not the context's (MVS_ERR_INVALID), no views
+ *   (MVS_ERR_STATE), a non-finite lens field, reserved != 0, dist0 != 0 with flen not positive (MVS_ERR_INVALID).  A refusal leaves the
+ *   context without masks.  stats (may be null) are filled on refusals too. */
+typedef struct mvs_mask_stats {
+    uint64_t views_masked, views_undistorted;    /* views that carry a mask; those of them whose mask went through the lens */
+    uint64_t pixels, pixels_masked_out;          /* of the masked views; pixels left out, after undistortion */
+    uint64_t device_bytes, staging_bytes, batches;   /* keep words held by the context; the most mask bytes staged at one time; batches */
+    float ms_upload, ms_pack, ms_undistort;      /* host time of the uploads into staging; device time of the pack / the lens launches */
+} mvs_mask_stats;
+mvs_status mvs_scene_set_view_masks(mvs_ctx* ctx, const uint8_t* const* masks, uint32_t n_views, int on_device, const mvs_lens* lens, mvs_mask_stats* stats);
+
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
  * the view list -- stamped all over with its three-digit id in cells of 13 x 6 pixels, and rows f6 (without adjust_colors), f8 and f9

@@ -65,6 +65,10 @@ mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256_host_or_null);
  * mvs_scene_set_views, _jpeg or _lens left there; nothing is launched.  *n_bytes = the size; out_host == null: the size only; a smaller
  * buffer or view >= n_views: MVS_ERR_INVALID; MVS_ERR_STATE on a context without views. */
 mvs_status mvs_ctx_view_image(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
+/* HARNESS ONLY (tests/test_gpu_view_masks.py): the keep words of one view as mvs_scene_set_view_masks left them, height * ceil(width / 32)
+ * 32-bit words (bit b of word wx of a row = pixel 32 wx + b), copied to the host; nothing is launched.  *n_bytes = the size, 0 for a view
+ * without a mask; the other rules are mvs_ctx_view_image's. */
+mvs_status mvs_ctx_view_keep_words(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes);
 
 /* ---- multi-GPU MRF building blocks (one context per rank; DESIGN.md "Multi-GPU") ----
  * Every rank holds the FULL cost table and adjacency (288 GB of HBM make the

@@ -235,7 +235,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto* b : ctx->own_rgb) delete b;
-    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx); mvs::lens_release(ctx);
+    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx); mvs::lens_release(ctx); mvs::viewmask_release(ctx);
     mvs::sweep_graph_release(ctx);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -358,6 +358,7 @@ static mvs_status set_views_impl(mvs_ctx* ctx, const mvs_view* views, uint32_t n
     if (!ctx || (!views && n_views)) return api_fail(MVS_ERR_INVALID, "null argument");
     MVS_CTX_API_BEGIN
     ctx->views_refused = false;
+    view_masks_clear(ctx); ctx->view_scratch_cap = 1ull << 30;   // (a view input clears the masks; mvs_jpegdec_default_params' max_scratch_bytes)
     // image buffers of an earlier call are reused (a context that serves one scene after another allocates once)
     if (rgb_on_device) { for (auto* b : ctx->own_rgb) delete b; ctx->own_rgb.clear(); }
     else { while (ctx->own_rgb.size() > n_views) { delete ctx->own_rgb.back(); ctx->own_rgb.pop_back(); } }

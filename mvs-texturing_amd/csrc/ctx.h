@@ -145,6 +145,7 @@ struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
 struct JpegDecDev;   // view input: JPEG files decoded on the device (k_jpegdec.hip)
 struct LensDev;      // view input: lens undistortion on the device (k_lens.hip)
+struct ViewMaskDev;  // view input: the keep words of the views that carry a mask (k_viewmask.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
 // build_patch_tables): per candidate (component of a label, label-major) its frame box = (min_x - 1, min_y - 1, max_x, max_y), the
@@ -280,6 +281,7 @@ struct mvs_ctx {
     mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
     mvs::JpegDecDev* jpegdec = nullptr; uint32_t jpegdec_subseq = 128;   // view input (k_jpegdec.hip); option "jpegdec_subseq_bytes": bytes of entropy data one lane owns
     mvs::LensDev* lens = nullptr;     // view input: the staging buffer, the per-view table and the output of the lens route (k_lens.hip)
+    mvs::ViewMaskDev* viewmask = nullptr; uint64_t view_scratch_cap = 1ull << 30;   // view masks (k_viewmask.hip): the keep words; max_scratch_bytes of the last view input (mask staging is cut by it)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -447,6 +449,19 @@ void jpegdec_release(mvs_ctx* ctx);   // k_jpegdec.hip
 void lens_release(mvs_ctx* ctx);      // k_lens.hip
 // k_lens.hip: the context's staging buffer with room for `bytes` (16-byte aligned; growing it loses what it held)
 uint8_t* lens_staging(mvs_ctx* ctx, uint64_t bytes);
+// k_lens.hip: byte masks in the camera's frame -> keep words in the undistorted frame, one launch for the n views of T (DESIGN.md section 4
+// "View input" item 10); adds the launch's device time to ms.  Returns with the stream drained.
+struct LensMaskView { const uint8_t* src; uint32_t* keep; int32_t width, height; float flen, d0, d1; uint32_t pad_; };
+void lens_mask_run(mvs_ctx* ctx, const std::vector<LensMaskView>& T, float& ms);
+// k_viewmask.hip: what prepare_views hands to its kernels -- the device table of every view's keep words (null entries: views without a
+// mask) and the device list of the n_masked views that carry one; table == null: the scene has no masks.  view_keep_words: one view's
+// keep words on the device (null: none; the harness read-back of mgpu.hip).  view_masks_clear forgets the masks (every view input calls
+// it), viewmask_release frees them.
+struct ViewKeep { const uint32_t* const* table; const uint32_t* list; uint32_t n_masked; };
+ViewKeep view_keep(mvs_ctx* ctx);
+const uint32_t* view_keep_words(mvs_ctx* ctx, uint32_t view, std::vector<const uint32_t*>& host_table);
+void view_masks_clear(mvs_ctx* ctx);
+void viewmask_release(mvs_ctx* ctx);
 // k_jpegdec.hip: the views whose files[j] is not null, decoded in batches whose scratch fits params->max_scratch_bytes (null: the default) --
 // view j into dst[j], or, where staged[j] is not 0, into the context's lens staging (lens_staging), whose 3 * width * height bytes count
 // towards the view's scratch.  After every batch that staged views, after_batch(views, pixels) gets their numbers and where their decoded

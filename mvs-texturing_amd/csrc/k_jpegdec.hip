@@ -616,6 +616,7 @@ mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_
         const mvs_jpegdec_params P = jpegdec_params(params);
         // a refusal leaves the context without views
         ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0; ctx->views_refused = false;
+        view_masks_clear(ctx); ctx->view_scratch_cap = P.max_scratch_bytes;   // (a view input clears the masks; the masks of these views are staged under the same cap)
         run_with_stats(ctx->stream, stats, st, [&] {
             for (uint32_t j = 0; j < n_views; ++j)
                 if (views[j].width < 2 || views[j].height < 2) throw StatusError(MVS_ERR_INVALID, "view " + std::to_string(j) + ": bad image");

@@ -73,17 +73,70 @@ __global__ void __launch_bounds__(THREADS) lens_kernel(const LensView* __restric
     if (none && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(no_source, (u64)none);
 }
 
+// View masks under a lens: keep words (mask_stride words per row, bit b of word wx = pixel 32 wx + b, bits beyond the width zero) from the
+// staged byte mask in the camera's frame.  A lane evaluates lens.h lens_keep for ONE destination pixel; 32 consecutive lanes are the 32
+// bit positions of one word (positions beyond the width evaluate nothing), so a wave's ballot is two finished words.  The batch's words
+// are numbered through all views (word_ptr, a prefix array), as lens_kernel numbers its chunks.
+__global__ void __launch_bounds__(THREADS) lens_mask_kernel(const LensMaskView* __restrict__ views, uint32_t n, const u64* __restrict__ word_ptr, u64 n_words) {
+    const u64 g = ((u64)blockIdx.x * THREADS + threadIdx.x) >> 5;   // the word; THREADS and the wave are multiples of 32
+    const int b = (int)(threadIdx.x & 31u);
+    bool keep = false;
+    uint32_t* dst = nullptr;
+    __shared__ uint32_t s_lo;   // the view of the block's first word, searched once per block (k_viewmask.hip mask_pack_kernel)
+    if (threadIdx.x == 0) {
+        const u64 g0 = ((u64)blockIdx.x * THREADS) >> 5;   // < n_words: the grid has no empty block
+        uint32_t lo = 0, hi = n;
+        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (word_ptr[mid] <= g0) lo = mid; else hi = mid; }
+        s_lo = lo;
+    }
+    __syncthreads();
+    if (g < n_words) {
+        uint32_t lo = s_lo;
+        while (word_ptr[lo + 1] <= g) ++lo;                // g < n_words = word_ptr[n]: ends at lo <= n - 1
+        const LensMaskView V = views[lo];
+        const u64 q = g - word_ptr[lo];
+        const uint32_t wpr = ((uint32_t)V.width + 31u) / 32u;
+        const uint32_t yq = (q >> 32) ? (uint32_t)(q / wpr) : (uint32_t)q / wpr;
+        const int y = (int)yq, x = 32 * (int)(uint32_t)(q - (u64)yq * wpr) + b;
+        if (x < V.width) keep = lens_keep(V.src, V.width, V.height, x, y, (double)V.flen, (double)V.d0, (double)V.d1);
+        dst = V.keep + q;
+    }
+    const u64 kept = __ballot(keep);
+    if (dst && b == 0) *dst = (uint32_t)(kept >> (threadIdx.x & 32u));
+}
+
 uint64_t align16(uint64_t v) { return (v + 15u) & ~15ull; }
 
 }  // namespace
 
 // per-context buffers of the route, allocated on first use
-struct LensDev { DBuf<uint8_t> staging, out; DBuf<LensView> table; DBuf<u64> chunk_ptr, words; };
+struct LensDev { DBuf<uint8_t> staging, out; DBuf<LensView> table; DBuf<u64> chunk_ptr, words; DBuf<LensMaskView> mask_table; DBuf<u64> mask_word_ptr; };
 void lens_release(mvs_ctx* ctx) { delete ctx->lens; ctx->lens = nullptr; }
 uint8_t* lens_staging(mvs_ctx* ctx, uint64_t bytes) {
     LensDev& D = row_dev(ctx->lens);
     D.staging.ensure((size_t)bytes + 16);
     return D.staging.p;
+}
+
+void lens_mask_run(mvs_ctx* ctx, const std::vector<LensMaskView>& T, float& ms) {
+    if (T.empty()) return;
+    LensDev& D = row_dev(ctx->lens);
+    hipStream_t s = ctx->stream;
+    const uint32_t n = (uint32_t)T.size();
+    std::vector<u64> word_ptr((size_t)n + 1, 0);
+    for (uint32_t k = 0; k < n; ++k) word_ptr[k + 1] = word_ptr[k] + (u64)(((uint32_t)T[k].width + 31u) / 32u) * (u64)T[k].height;
+    const u64 n_words = word_ptr[n], blocks = (n_words * 32u + THREADS - 1u) / THREADS;
+    if (blocks >= 0x7FFFFFFFull) throw StatusError(MVS_ERR_UNSUPPORTED, "set_view_masks: too many pixels in one batch (lower max_scratch_bytes)");
+    upload(D.mask_table, T, s); upload(D.mask_word_ptr, word_ptr, s);
+    StageTimer<2> tm(s);
+    tm.mark();
+    if (blocks) {
+        hipLaunchKernelGGL(lens_mask_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, s, (const LensMaskView*)D.mask_table.p, n, (const u64*)D.mask_word_ptr.p, n_words);
+        MVS_LAUNCH_CHECK();
+    }
+    tm.mark();
+    MVS_HIP(hipStreamSynchronize(s));   // (T and word_ptr were read by asynchronous copies)
+    ms += tm.ms(0, 1);
 }
 
 namespace {
@@ -224,6 +277,7 @@ mvs_status mvs_scene_set_views_lens(mvs_ctx* ctx, const mvs_view* views, uint32_
         const uint64_t cap = jpeg_params ? jpeg_params->max_scratch_bytes : DEFAULT_MAX_SCRATCH;
         // a refusal leaves the context without views, and says so to the next data-cost pass
         ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0; ctx->views_refused = true;
+        view_masks_clear(ctx); ctx->view_scratch_cap = cap;   // (a view input clears the masks; the masks of these views are staged under the same cap)
         run_with_stats(ctx->stream, jpeg_stats, jst, [&] { run_with_stats(ctx->stream, lens_stats, st, [&] {
             for (uint32_t j = 0; j < n_views; ++j)
                 if (views[j].width < 2 || views[j].height < 2) throw StatusError(MVS_ERR_INVALID, std::string(who) + ": view " + std::to_string(j) + ": bad image");

@@ -128,26 +128,33 @@ __global__ void mask_flood_kernel(const ViewParams* __restrict__ views, const ui
 // mask = ~reach; with ERODE the literal semantics of erode_validity_mask:
 // every INTERIOR invalid pixel clears its 3x3 neighbourhood, border pixels keep
 // their own value otherwise (the reference clears them only in the discarded copy).
-template <bool ERODE>
-__global__ void mask_final_kernel(const ViewParams* __restrict__ views, const uint32_t* __restrict__ reach_all,
-                                  uint32_t* __restrict__ mask_all, const size_t* __restrict__ mask_off) {
-    const ViewParams& vp = views[blockIdx.z];
+// KEEP (view masks, k_viewmask.hip): the view's keep words -- `keep`, in the mask's own layout, null for a view without a mask -- are one
+// more source of invalid pixels IN FRONT of the erosion: a pixel is invalid when the flood reached it or its keep bit is 0, and the
+// interior-invalid term of the erosion sees both.  reach_all == null (KEEP only): no flood ran, nothing was reached.
+template <bool ERODE, bool KEEP>
+__device__ __forceinline__ void mask_final_word(const ViewParams& vp, const uint32_t* __restrict__ reach_all, uint32_t* __restrict__ mask_all, size_t base,
+                                                const uint32_t* __restrict__ keep) {
     const int w = vp.width, h = vp.height, wpr = vp.mask_stride;
     const int wx = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;   // blocks of 64 words x 4 rows (one-wave blocks of one row each were launch bound: 307 k blocks per pass at 200 views)
     if (wx >= wpr || y >= h) return;
-    const size_t base = mask_off[blockIdx.z];
     auto inbounds = [&](int ww) -> uint32_t {  // bits of word ww that are real pixels
         const int rem = w - ww * 32;
         return rem >= 32 ? 0xFFFFFFFFu : (rem <= 0 ? 0u : ((1u << rem) - 1u));
     };
+    auto invalid = [&](int ww, int yy) -> uint32_t {   // before the erosion; bits beyond the width are not meaningful
+        if (!KEEP) return reach_all[base + (size_t)yy * wpr + ww];
+        uint32_t inv = reach_all ? reach_all[base + (size_t)yy * wpr + ww] : 0u;
+        if (keep) inv |= ~keep[(size_t)yy * wpr + ww];
+        return inv;
+    };
     auto invalid_interior = [&](int ww, int yy) -> uint32_t {
         if (ww < 0 || ww >= wpr || yy <= 0 || yy >= h - 1) return 0u;
-        uint32_t inv = reach_all[base + (size_t)yy * wpr + ww] & inbounds(ww);
+        uint32_t inv = invalid(ww, yy) & inbounds(ww);
         if (ww == 0) inv &= ~1u;                                    // x == 0 is border
         if (ww == (w - 1) / 32) inv &= ~(1u << ((w - 1) & 31));     // x == w-1 is border
         return inv;
     };
-    uint32_t valid = ~reach_all[base + (size_t)y * wpr + wx] & inbounds(wx);
+    uint32_t valid = ~invalid(wx, y) & inbounds(wx);
     if (ERODE) {
         uint32_t kill = 0;
         for (int dy = -1; dy <= 1; ++dy) {
@@ -160,19 +167,39 @@ __global__ void mask_final_kernel(const ViewParams* __restrict__ views, const ui
     }
     mask_all[base + (size_t)y * wpr + wx] = valid;
 }
+template <bool ERODE>
+__global__ void mask_final_kernel(const ViewParams* __restrict__ views, const uint32_t* __restrict__ reach_all,
+                                  uint32_t* __restrict__ mask_all, const size_t* __restrict__ mask_off) {
+    mask_final_word<ERODE, false>(views[blockIdx.z], reach_all, mask_all, mask_off[blockIdx.z], nullptr);
+}
+// the scene has masks: grid.z runs over all views (list == null), or over the views of `list`, the masked ones, when no flood ran
+template <bool ERODE>
+__global__ void mask_final_keep_kernel(const ViewParams* __restrict__ views, const uint32_t* __restrict__ reach_all, uint32_t* __restrict__ mask_all,
+                                       const size_t* __restrict__ mask_off, const uint32_t* const* __restrict__ keep, const uint32_t* __restrict__ list) {
+    const uint32_t v = list ? list[blockIdx.z] : blockIdx.z;
+    mask_final_word<ERODE, true>(views[v], reach_all, mask_all, mask_off[v], keep[v]);
+}
 
 // ---- tile summary of the final mask (dmath.h ViewParams::msum / valid_pixels3) ----
 // One thread per 32 x 32 tile: bit (tx, ty) = every mask bit of the pixels [32 tx, 32 tx + 32] x [32 ty, 32 ty + 32] clipped to
 // the image is set, i.e. the four bits valid_pixel (texture_view.cpp:253-281) reads around any position whose integer part lies in
 // the tile.  A wave holds 64 consecutive tiles of one tile row: its ballot is two words of the summary.
+__device__ __forceinline__ void mask_summary_view(const ViewParams& vp, const uint32_t* __restrict__ m);
 __global__ void __launch_bounds__(64) mask_summary_kernel(const ViewParams* __restrict__ views, const uint32_t* __restrict__ mask_all, const size_t* __restrict__ mask_off) {
-    const ViewParams& vp = views[blockIdx.z];
+    mask_summary_view(views[blockIdx.z], mask_all + mask_off[blockIdx.z]);
+}
+// ... of the views of `list` only (view masks without a flood: prepare_views)
+__global__ void __launch_bounds__(64) mask_summary_list_kernel(const ViewParams* __restrict__ views, const uint32_t* __restrict__ mask_all, const size_t* __restrict__ mask_off,
+                                                               const uint32_t* __restrict__ list) {
+    const uint32_t v = list[blockIdx.z];
+    mask_summary_view(views[v], mask_all + mask_off[v]);
+}
+__device__ __forceinline__ void mask_summary_view(const ViewParams& vp, const uint32_t* __restrict__ m) {
     const int w = vp.width, h = vp.height, wpr = vp.mask_stride;
     const int tx = blockIdx.x * 64 + threadIdx.x, ty = blockIdx.y;
     if (blockIdx.x * 64 >= wpr || ty * 32 >= h) return;           // wave-uniform: no tile of this view here
     bool all = false;
     if (tx < wpr) {
-        const uint32_t* __restrict__ m = mask_all + mask_off[blockIdx.z];
         const int rem = w - tx * 32;
         const uint32_t inb = rem >= 32 ? 0xFFFFFFFFu : ((1u << rem) - 1u);      // bits of the tile's word that are real pixels (rem >= 1)
         const bool next = (tx + 1) * 32 <= w - 1;                               // pixel column 32 tx + 32 exists
@@ -192,8 +219,10 @@ __global__ void __launch_bounds__(64) mask_summary_kernel(const ViewParams* __re
 }
 // A view whose summary is all ones has an all-ones mask: its device-side ViewParams drops the mask pointer and the last cull
 // (calculate_data_costs.cpp:191) becomes pure arithmetic for it.  One block per view.
-__global__ void __launch_bounds__(256) mask_trivial_kernel(ViewParams* __restrict__ views) {
-    ViewParams& vp = views[blockIdx.x];
+__device__ __forceinline__ void mask_trivial_view(ViewParams& vp);
+__global__ void __launch_bounds__(256) mask_trivial_kernel(ViewParams* __restrict__ views) { mask_trivial_view(views[blockIdx.x]); }
+__global__ void __launch_bounds__(256) mask_trivial_list_kernel(ViewParams* __restrict__ views, const uint32_t* __restrict__ list) { mask_trivial_view(views[list[blockIdx.x]]); }
+__device__ __forceinline__ void mask_trivial_view(ViewParams& vp) {
     const int wpr = vp.mask_stride, th = (vp.height + 31) / 32, ms = vp.msum_stride;
     bool ok = true;
     for (int k = threadIdx.x; k < th * ms; k += 256) {
@@ -210,6 +239,11 @@ __global__ void __launch_bounds__(256) mask_trivial_kernel(ViewParams* __restric
 __global__ void mask_all_valid_kernel(ViewParams* __restrict__ views, uint32_t n_views) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v < n_views) views[v].mask = nullptr;
+}
+// ... the same for the views without a view mask, when other views of the scene carry one (those went through mask_final and the summary)
+__global__ void mask_unmasked_valid_kernel(ViewParams* __restrict__ views, uint32_t n_views, const uint32_t* const* __restrict__ keep) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < n_views && !keep[v]) views[v].mask = nullptr;
 }
 
 // ---- vectorised fast path (image width a multiple of 32, 4-byte aligned rows) ----
@@ -428,9 +462,26 @@ void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const s
     // No view with a black corner pixel = no seed anywhere: every mask is all ones, the views drop their mask pointers (what
     // mask_trivial_kernel would find after three passes over 307 k one-wave blocks: 0.3 ms at 200 views) -- one read-back, which the
     // first flood step needed anyway.
+    // View masks (k_viewmask.hip): a view that carries one needs mask_final and the summary even without a seed -- nothing was reached,
+    // its keep words alone are its mask -- so those views, and only those, go round the shortcut; a scene without masks takes it as ever.
+    const ViewKeep vk = view_keep(ctx);
     { uint32_t seeded = 0;
       read_words(ctx, d_any_seed, &seeded, 1);
-      if (!seeded) { hipLaunchKernelGGL(mask_all_valid_kernel, dim3((V + 255) / 256), dim3(256), 0, s, ctx->d_views.p, V); MVS_LAUNCH_CHECK(); return; } }
+      if (!seeded && !vk.table) { hipLaunchKernelGGL(mask_all_valid_kernel, dim3((V + 255) / 256), dim3(256), 0, s, ctx->d_views.p, V); MVS_LAUNCH_CHECK(); return; }
+      if (!seeded) {
+          const uint32_t M = vk.n_masked;
+          dim3 lgrid(mgrid.x, mgrid.y, M);
+          if (need_gmi) hipLaunchKernelGGL(mask_final_keep_kernel<true>, lgrid, mblock, 0, s, ctx->d_views.p, (const uint32_t*)nullptr, ctx->mask_all.p, d_mask_off, vk.table, vk.list);
+          else hipLaunchKernelGGL(mask_final_keep_kernel<false>, lgrid, mblock, 0, s, ctx->d_views.p, (const uint32_t*)nullptr, ctx->mask_all.p, d_mask_off, vk.table, vk.list);
+          MVS_LAUNCH_CHECK();
+          hipLaunchKernelGGL(mask_summary_list_kernel, dim3((maxwpr + 63) / 64, (maxh + 31) / 32, M), dim3(64), 0, s, ctx->d_views.p, (const uint32_t*)ctx->mask_all.p, d_mask_off, vk.list);
+          MVS_LAUNCH_CHECK();
+          hipLaunchKernelGGL(mask_trivial_list_kernel, dim3(M), dim3(256), 0, s, ctx->d_views.p, vk.list);
+          MVS_LAUNCH_CHECK();
+          hipLaunchKernelGGL(mask_unmasked_valid_kernel, dim3((V + 255) / 256), dim3(256), 0, s, ctx->d_views.p, V, vk.table);
+          MVS_LAUNCH_CHECK();
+          return;
+      } }
     // flood fill until a whole batch of steps changes nothing
     for (int iter = 0;; ++iter) {
         MVS_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), s));
@@ -448,7 +499,10 @@ void prepare_views(mvs_ctx* ctx, bool need_gmi, const size_t* d_gmi_off, const s
     // ra holds the converged reach set; the final mask must land in mask_all
     uint32_t* reach = ra;
     uint32_t* out = (ra == ctx->mask_all.p) ? ctx->mask_tmp.p : ctx->mask_all.p;
-    if (need_gmi) hipLaunchKernelGGL(mask_final_kernel<true>, mgrid, mblock, 0, s, ctx->d_views.p, reach, out, d_mask_off);
+    if (vk.table) {   // the scene has masks: the instantiation that ANDs the keep words in, for every view (a null entry: no mask)
+        if (need_gmi) hipLaunchKernelGGL(mask_final_keep_kernel<true>, mgrid, mblock, 0, s, ctx->d_views.p, (const uint32_t*)reach, out, d_mask_off, vk.table, (const uint32_t*)nullptr);
+        else hipLaunchKernelGGL(mask_final_keep_kernel<false>, mgrid, mblock, 0, s, ctx->d_views.p, (const uint32_t*)reach, out, d_mask_off, vk.table, (const uint32_t*)nullptr);
+    } else if (need_gmi) hipLaunchKernelGGL(mask_final_kernel<true>, mgrid, mblock, 0, s, ctx->d_views.p, reach, out, d_mask_off);
     else hipLaunchKernelGGL(mask_final_kernel<false>, mgrid, mblock, 0, s, ctx->d_views.p, reach, out, d_mask_off);
     MVS_LAUNCH_CHECK();
     if (out != ctx->mask_all.p)

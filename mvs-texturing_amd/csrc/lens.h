@@ -58,6 +58,24 @@ MVS_HD bool lens_pixel(const uint8_t* src, int w, int h, int x, int y, double fl
     return true;
 }
 
+// A view's MASK under a lens (DESIGN.md section 4 "View input" item 10): `mask` is a [h][w] byte image in the camera's frame, 0 = leave out,
+// anything else = keep.  It is read as the one-channel image of 0 / 255 and undistorted as a colour channel is: output pixel (x, y) is
+// kept iff it has a source and linear_at there gives the byte 255.  The expression is linear_at's (dmath.h), restated on the two
+// values a tap can take, so that this equals undistorting the 0 / 255 replica and comparing with 255, bit for bit.
+MVS_HD bool lens_keep(const uint8_t* mask, int w, int h, int x, int y, double flen, double d0, double d1) {
+    double sx, sy;
+    if (!lens_source(x, y, w, h, flen, d0, d1, sx, sy)) return false;
+    const float fx = smax(0.0f, smin((float)(w - 1), (float)sx)), fy = smax(0.0f, smin((float)(h - 1), (float)sy));
+    const int floor_x = (int)fx, floor_y = (int)fy;
+    const int floor_xp1 = imin(floor_x + 1, w - 1), floor_yp1 = imin(floor_y + 1, h - 1);
+    const float w1 = fx - (float)floor_x, w0 = 1.0f - w1;
+    const float w3 = fy - (float)floor_y, w2 = 1.0f - w3;
+    const size_t row1 = (size_t)floor_y * w, row2 = (size_t)floor_yp1 * w;
+    const float v1 = mask[row1 + floor_x] ? 255.0f : 0.0f, v2 = mask[row1 + floor_xp1] ? 255.0f : 0.0f;
+    const float v3 = mask[row2 + floor_x] ? 255.0f : 0.0f, v4 = mask[row2 + floor_xp1] ? 255.0f : 0.0f;
+    return (uint8_t)(((v1 * (w0 * w2) + v2 * (w1 * w2)) + v3 * (w0 * w3)) + v4 * (w1 * w3) + 0.5f) == 255;
+}
+
 // what is wrong with a view's lens (empty: nothing).  dist0 == 0 is a plain copy whatever flen and dist1 say, as long as they are numbers.
 inline std::string lens_refusal(const mvs_lens& L) {
     if (!isfinite(L.flen) || !isfinite(L.dist0) || !isfinite(L.dist1)) return "lens: flen, dist0 and dist1 must be finite";

@@ -217,6 +217,25 @@ mvs_status mvs_ctx_tone_table(mvs_ctx* ctx, const float* table256) {
 }
 
 // harness only: the context's image of one view as it lies on the device
+// harness only: the keep words of view `view` as mvs_scene_set_view_masks left them (height * mask_stride words); *n_bytes == 0: the view has no mask
+mvs_status mvs_ctx_view_keep_words(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
+    if (!ctx || !n_bytes) return api_fail(MVS_ERR_INVALID, "null argument");
+    if (ctx->n_views == 0 || ctx->h_views.size() != ctx->n_views) return api_fail(MVS_ERR_STATE, "view keep words: the context has no views");
+    if (view >= ctx->n_views) return api_fail(MVS_ERR_INVALID, "view keep words: view " + std::to_string(view) + " of " + std::to_string(ctx->n_views));
+    MVS_CTX_API_BEGIN
+    std::vector<const uint32_t*> table;
+    const uint32_t* src = view_keep_words(ctx, view, table);
+    const ViewParams& hv = ctx->h_views[view];
+    const uint64_t n = src ? (uint64_t)hv.height * (uint64_t)((hv.width + 31) / 32) * sizeof(uint32_t) : 0;
+    *n_bytes = n;
+    if (out_host && cap_bytes < n) throw StatusError(MVS_ERR_INVALID, "view keep words: buffer too small");
+    if (out_host && n) {
+        MVS_HIP(hipMemcpyAsync(out_host, src, n, hipMemcpyDeviceToHost, ctx->stream));
+        MVS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    MVS_API_END
+}
+
 mvs_status mvs_ctx_view_image(mvs_ctx* ctx, uint32_t view, void* out_host, uint64_t cap_bytes, uint64_t* n_bytes) {
     if (!ctx || !n_bytes) return api_fail(MVS_ERR_INVALID, "null argument");
     if (ctx->n_views == 0 || ctx->h_views.size() != ctx->n_views) return api_fail(MVS_ERR_STATE, "view image: the context has no views");

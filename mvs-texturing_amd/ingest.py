@@ -17,9 +17,12 @@ Lens undistortion (generate_texture_views.cpp:153-165, MVE image_undistort_k2k4 
 is undistorted on the device on its way into the image buffers (viewsel.Context.set_views(lens=) / set_views_jpeg(lens=)): the same
 pixels, bit for bit.  Together with `device_jpeg` a distorted baseline JPEG stays a file.
 
+View masks: with `masks` (CLI --masks) a file `<name>.mask.png` beside `<name>.cam` leaves its zero pixels out of that view
+(viewsel.Context.set_view_masks; DESIGN.md section 4 "View input" item 10).  Such a file is never a view's image, flag or no flag.
+
 This is harness code (plumbing around the C ABI); the compute runs in libmvs_viewsel.so.
 
-CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-undistort]
+CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-undistort] [--masks]
 """
 import os
 import struct
@@ -100,9 +103,43 @@ def camera_arrays(cam, width, height):
     return {"pos": pos, "viewdir": R[2].copy(), "K": K, "w2c": w2c}
 
 
+MASK_SUFFIX = ".mask.png"
+
+
+def is_mask_file(name):
+    return name.lower().endswith(MASK_SUFFIX)
+
+
+def mask_path_of(cam_path):
+    """NAME.mask.png beside NAME.cam, or None when there is no such file"""
+    p = cam_path[:-4] + MASK_SUFFIX
+    return p if os.path.isfile(p) else None
+
+
+def load_mask(path, width, height):
+    """a view's mask file as an (H, W) uint8 array of 0 (leave out) / 255 (keep): any Pillow mode through convert("L"), non-zero = keep"""
+    from PIL import Image
+    with Image.open(path) as im:
+        m = np.asarray(im.convert("L"), dtype=np.uint8)
+    if m.shape != (height, width):
+        raise ValueError("%s: the mask is %d x %d, its view %d x %d" % (path, m.shape[1], m.shape[0], width, height))
+    return np.ascontiguousarray(np.where(m != 0, 255, 0).astype(np.uint8))
+
+
+def undistort_mask_host(mask, flen, dist0, dist1):
+    """a mask in the camera's frame -> the undistorted frame, on the host, by the rule of the device route (DESIGN.md section 4 "View
+    input"): the 0 / 255 replica goes through undistort_host, a pixel is kept iff the result is 255"""
+    from .viewsel import undistort_host
+    rep = np.ascontiguousarray(np.repeat(np.where(np.asarray(mask) != 0, 255, 0).astype(np.uint8)[:, :, None], 3, axis=2))
+    out = undistort_host(rep, flen, dist0, dist1)
+    return np.ascontiguousarray(np.where(out[:, :, 0] == 255, 255, 0).astype(np.uint8))
+
+
 def list_scene_folder(path):
     """(cam_file, image_file) pairs in the order of generate_texture_views.cpp:71-111: sorted directory, every .cam
-    takes the nearest following -- else preceding -- file with the same prefix and an image extension"""
+    takes the nearest following -- else preceding -- file with the same prefix and an image extension.  A file named *.mask.png is a
+    view's MASK (load_scene's `masks`), never its image: the search steps over it, with or without the flag -- the one place where a
+    folder pairs differently from upstream, which would take NAME.mask.png for NAME.cam's photograph"""
     names = sorted(n for n in os.listdir(path))
     is_dir = [os.path.isdir(os.path.join(path, n)) for n in names]
     pairs = []
@@ -119,7 +156,7 @@ def list_scene_folder(path):
                     j, step = i - 1, -1
                     continue
                 break
-            if names[j][-4:].upper() in IMAGE_EXTS:
+            if names[j][-4:].upper() in IMAGE_EXTS and not is_mask_file(names[j]):
                 pairs.append((os.path.join(path, name), os.path.join(path, names[j])))
                 break
             j += step
@@ -208,7 +245,7 @@ def _note_restated_models(img_path, cam):
           % (os.path.basename(img_path), "k2k4" if cam.dist[1] != 0.0 else "VisualSFM"), file=sys.stderr)
 
 
-def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False):
+def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False, masks=False):
     """A synth.Scene-like object from a folder of .cam + image pairs (and optionally a PLY mesh, prepared as
     texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given).
     keep_jpeg: a view without distortion coefficients whose file is a baseline JPEG in the format the device route accepts
@@ -216,10 +253,25 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
     other view is decoded here as without the flag, and its s.jpeg_files[j] is None.
     device_undistort: a view with dist[0] != 0 is not undistorted here; s.lens[j] = (flen, dist0, dist1) carries its coefficients for
     Context.set_views(lens=) / set_views_jpeg(lens=), and with keep_jpeg such a view stays a file when jpeg_probe accepts it.  The rows of
-    views without distortion are (flen, 0, 0).  Without the flag s.lens is None."""
+    views without distortion are (flen, 0, 0).  Without the flag s.lens is None.
+    masks: for a view NAME.cam + NAME.<ext>, a file NAME.mask.png beside them is its mask (load_mask: non-zero = keep; a size other than
+    the view's is refused with the file's name): s.masks[j] is the (H, W) uint8 mask or None, for Context.set_view_masks.  With
+    device_undistort the mask of a distorted view stays in the camera's frame, to go in with the view's lens; without it the mask is
+    undistorted here by the same rule (undistort_mask_host), so both routes give the same bits.  Without the flag mask files are
+    ignored and s.masks is None."""
     from .synth import Scene
     s = Scene()
     s.jpeg_files = []
+    s.masks = [] if masks else None
+
+    def take_mask(cam_path, cam, w, h, distorted):
+        if not masks:
+            return
+        mp = mask_path_of(cam_path)
+        m = load_mask(mp, w, h) if mp else None
+        if m is not None and distorted and not device_undistort:
+            m = undistort_mask_host(m, cam.flen, cam.dist[0], cam.dist[1])
+        s.masks.append(m)
     lens = []
     cams = {"pos": [], "viewdir": [], "K": [], "w2c": [], "width": [], "height": []}
     for cam_path, img_path in list_scene_folder(scene_dir):
@@ -238,6 +290,7 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
                     cams[k].append(arr[k])
                 cams["width"].append(w); cams["height"].append(h)
                 s.images.append(None); s.jpeg_files.append(data)
+                take_mask(cam_path, cam, w, h, distorted)
                 if distorted:
                     _note_restated_models(img_path, cam)
                 continue
@@ -254,6 +307,7 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
             cams[k].append(arr[k])
         cams["width"].append(w); cams["height"].append(h)
         s.images.append(img)
+        take_mask(cam_path, cam, w, h, distorted)
     n = len(s.images)
     s.lens = np.array(lens, np.float32).reshape(n, 3) if device_undistort else None
     s.cams = {"pos": np.array(cams["pos"], np.float32).reshape(n, 3), "viewdir": np.array(cams["viewdir"], np.float32).reshape(n, 3),
@@ -287,13 +341,14 @@ def save_scene_folder(scene, scene_dir, mesh_path=None):
         write_ply(mesh_path, scene.verts, scene.faces)
 
 
-def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False):
+def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False, masks=False):
     """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec.
     device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)
     device_undistort: the views with distortion coefficients are undistorted on the device on their way in (load_scene's
-    device_undistort, the `lens` of Context.set_views / set_views_jpeg)"""
+    device_undistort, the `lens` of Context.set_views / set_views_jpeg)
+    masks: every view's NAME.mask.png, where there is one, leaves its zero pixels out of the view (load_scene's masks, Context.set_view_masks)"""
     from . import viewsel as V
-    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort)
+    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort, masks=masks)
     st = V.Settings()
     st.data_term = {"area": 0, "gmi": 1}[data_term]
     st.outlier_removal = {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier_removal]
@@ -301,9 +356,9 @@ def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none
     try:
         ctx.set_mesh(s.verts, s.faces, s.normals)
         if device_jpeg:
-            ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images, lens=s.lens)
+            ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images, lens=s.lens, masks=s.masks)
         else:
-            ctx.set_views(s.cams, s.images, lens=s.lens)
+            ctx.set_views(s.cams, s.images, lens=s.lens, masks=s.masks)
         dstats = ctx.data_costs(st)
         dc = ctx.costs_download()
         labels, mstats = ctx.view_selection(s.adj_ptr, s.adj)
@@ -323,6 +378,7 @@ if __name__ == "__main__":
     ap.add_argument("--outlier-removal", default="none", choices=["none", "gauss_damping", "gauss_clamping"])
     ap.add_argument("--device-jpeg", action="store_true", help="decode baseline JPEG views on the device")
     ap.add_argument("--device-undistort", action="store_true", help="undistort the views with distortion coefficients on the device, on their way in")
+    ap.add_argument("--masks", action="store_true", help="NAME.mask.png beside NAME.cam leaves its zero pixels out of that view")
     a = ap.parse_args()
-    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort)
+    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort, masks=a.masks)
     print("data costs: nnz=%d  labeling: energy=%.3f sweeps=%d unseen=%d" % (d["nnz"], m["energy"], m["sweeps"], m["unseen"]))

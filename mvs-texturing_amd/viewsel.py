@@ -240,6 +240,14 @@ class LensStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in LENS_COUNTS] + [(k, C.c_float) for k in LENS_MS]
 
 
+MASK_COUNTS = ("views_masked", "views_undistorted", "pixels", "pixels_masked_out", "device_bytes", "staging_bytes", "batches")
+MASK_MS = ("ms_upload", "ms_pack", "ms_undistort")
+
+
+class MaskStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in MASK_COUNTS] + [(k, C.c_float) for k in MASK_MS]
+
+
 def _lens_array(lens, n):
     """an (n, 3) array of (flen, dist0, dist1) -- or (n, 4) with the reserved word, which must be 0 -- as the ABI's mvs_lens [n]"""
     a = np.asarray(lens, dtype=np.float32).reshape(n, -1)
@@ -276,7 +284,7 @@ BLOCK_SYMBOLS = frozenset((
     "mvs_ctx_dc_get_max", "mvs_ctx_dc_set_max", "mvs_ctx_dc_get_histogram", "mvs_ctx_dc_set_histogram", "mvs_ctx_costs_export",
     "mvs_ctx_mrf_setup", "mvs_ctx_mrf_setup_marked", "mvs_ctx_mrf_sweep", "mvs_ctx_mrf_sweep_phase", "mvs_ctx_mrf_sweep_phase_part", "mvs_ctx_mrf_layout", "mvs_ctx_mrf_gather", "mvs_ctx_mrf_scatter",
     "mvs_ctx_mrf_energy", "mvs_ctx_mrf_keep_best", "mvs_ctx_mrf_step", "mvs_ctx_mrf_poll", "mvs_ctx_mrf_icm_gain", "mvs_ctx_mrf_icm_apply",
-    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_prep_products", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table", "mvs_ctx_view_image"))
+    "mvs_ctx_mrf_labels", "mvs_ctx_mrf_setup_tables", "mvs_ctx_ray_bits", "mvs_ctx_prep_products", "mvs_ctx_costs_upload_ordered", "mvs_ctx_tone_table", "mvs_ctx_view_image", "mvs_ctx_view_keep_words"))
 
 TONE_MAPPINGS = {"none": 0, "gamma": 1}                                       # tex::ToneMapping (settings.h); the *_params.tone_mapping field
 
@@ -340,7 +348,8 @@ def load_library():
         "mvs_ctx_prep_products": [vp, i32, u32, vp, u64, C.POINTER(u64)],
         "mvs_ctx_costs_upload_ordered": [vp, C.POINTER(CCsr), vp],
         "mvs_ctx_tone_table": [vp, vp],
-        "mvs_ctx_view_image": [vp, u32, vp, u64, C.POINTER(u64)],
+        "mvs_ctx_view_image": [vp, u32, vp, u64, C.POINTER(u64)], "mvs_ctx_view_keep_words": [vp, u32, vp, u64, C.POINTER(u64)],
+        "mvs_scene_set_view_masks": [vp, vp, u32, i32, C.POINTER(Lens), C.POINTER(MaskStats)],
         "mvs_gamma_correct": [vp, u64, C.c_float], "mvs_ctx_gamma_correct": [vp, vp, u64, C.c_float, i32], "mvs_tone_table": [u32, vp],
         "mvs_ctx_prune_labels": [vp, u32], "mvs_undistort_image": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
         "mvs_postprocess_face_infos": [u32, u32, vp, vp, vp, vp, C.POINTER(Settings), C.POINTER(CCsr), C.POINTER(DcStats)],
@@ -598,13 +607,23 @@ class Context:
         self.n_faces = int(faces.shape[0])
         _check(self.L, self.L.mvs_scene_set_mesh(self.h, C.byref(m), d0))
 
-    def set_views(self, cams, images, lens=None):
+    def set_views(self, cams, images, lens=None, masks=None):
         """cams: dict of arrays pos, viewdir, K, w2c, width, height; images: list of (H,W,3) u8 numpy / torch cuda.
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the images are then host arrays as the camera took them, and the
-        views with dist0 != 0 are undistorted on the device (mvs_scene_set_views_lens; returns the lens stats)"""
+        views with dist0 != 0 are undistorted on the device (mvs_scene_set_views_lens; returns the lens stats).
+        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats)"""
         V = len(images)
         if lens is not None:
-            return self._set_views_lens(cams, [None] * V, images, lens, None)["lens"]
+            st = self._set_views_lens(cams, [None] * V, images, lens, None)["lens"]
+            if masks is not None:
+                self.set_view_masks(masks, lens=lens)
+            return st
+        self._set_views_plain(cams, images)
+        if masks is not None:
+            self.set_view_masks(masks)
+
+    def _set_views_plain(self, cams, images):
+        V = len(images)
         arr = (CView * V)()
         dev = None
         for j in range(V):
@@ -665,6 +684,56 @@ class Context:
         _check_with_stats(self.L, rc, stats)
         return stats
 
+    def set_view_masks(self, masks, lens=None):
+        """mvs_scene_set_view_masks: masks[j] is view j's mask -- an (H, W) uint8 host array or torch cuda tensor of the view's size, 0 = leave
+        the pixel out, anything else = keep -- or None for a view without one (all of them host arrays or all of them device tensors).  A
+        masked pixel is an invalid pixel and nothing else changes (DESIGN.md section 4 "View input").  After any set_views*, before
+        data_costs; None or all None clears the masks, and so does every later set_views*.  lens: the (n, 3) array of set_views(lens=) --
+        the masks of views with dist0 != 0 are then in the frame the camera took and are undistorted on the device.  Returns the stats
+        (also self.mask_stats); a refusal raises MvsError with them as `.stats` and leaves the context without masks."""
+        V = getattr(self, "n_views", 0)
+        masks = [None] * V if masks is None else list(masks)
+        n = len(masks)
+        held, dev = [], None
+        for j, m in enumerate(masks):
+            if m is None:
+                held.append(None)
+                continue
+            if _is_torch(m):
+                assert m.is_cuda and m.is_contiguous() and str(m.dtype) == "torch.uint8"
+                d = 1
+            else:
+                m = np.ascontiguousarray(m, np.uint8)
+                d = 0
+            assert dev is None or dev == d, "host and device masks in one call"
+            dev = d
+            if j < len(getattr(self, "_view_sizes", [])):
+                w, h = self._view_sizes[j]
+                assert tuple(m.shape) == (h, w), "view %d: the mask is %s, the view %d x %d" % (j, tuple(m.shape), w, h)
+            held.append(m)
+        ptrs = (C.c_void_p * max(n, 1))(*[None if m is None else (m.data_ptr() if dev else m.ctypes.data) for m in held])
+        if dev:
+            import torch
+            torch.cuda.synchronize(self.device)   # the library reads on the context's stream, torch wrote on its own
+        st = MaskStats()
+        rc = self.L.mvs_scene_set_view_masks(self.h, ptrs, n, dev or 0, _lens_array(lens, n) if lens is not None else None, C.byref(st))
+        self.mask_stats = _stats_dict(st)
+        _check_with_stats(self.L, rc, self.mask_stats)
+        return self.mask_stats
+
+    def view_keep_bits(self, j):
+        """view j's keep bits as set_view_masks left them on the device, bool (H, W), and the padding bits of its words -- or None for a
+        view without a mask (mvs_ctx_view_keep_words, building-blocks library; test harness only)"""
+        n = C.c_uint64()
+        _check(self.L, self.L.mvs_ctx_view_keep_words(self.h, j, None, 0, C.byref(n)))
+        if not n.value:
+            return None
+        buf = np.empty(n.value // 4, np.uint32)
+        _check(self.L, self.L.mvs_ctx_view_keep_words(self.h, j, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        w, h = self._view_sizes[j]
+        bits = np.unpackbits(buf.view(np.uint8).reshape(h, -1), axis=1, bitorder="little").astype(bool)
+        return bits[:, :w], bits[:, w:]
+
     def undistort_images(self, images, lens, on_device=False):
         """mvs_ctx_undistort_images: the lens route on its own -- `images` (a list of (H, W, 3) uint8 host arrays) with lens[i] = (flen, dist0,
         dist1), undistorted in one call.  Returns (images, stats): a list of (H, W, 3) uint8 arrays, or with on_device a list of
@@ -697,13 +766,20 @@ class Context:
         w, h = self._view_sizes[j]
         return buf.reshape(h, w, 3)
 
-    def set_views_jpeg(self, cams, files, params=None, images=None, lens=None):
+    def set_views_jpeg(self, cams, files, params=None, images=None, lens=None, masks=None):
         """mvs_scene_set_views_jpeg: set_views with the images taken from baseline JPEG files (a list of bytes), decoded on the device
         straight into the context's image buffers (DESIGN.md section 4 "View input").  The frames' sizes must be cams' width / height.
         A view whose entry in `files` is None brings its pixels as images[j], an (H, W, 3) uint8 host array.
         Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views.
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the views with dist0 != 0, files and pixels alike, are undistorted
-        on the device (mvs_scene_set_views_lens); the stats then carry the lens stats under "lens"."""
+        on the device (mvs_scene_set_views_lens); the stats then carry the lens stats under "lens".
+        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats)."""
+        st = self._set_views_jpeg(cams, files, params, images, lens)
+        if masks is not None:
+            self.set_view_masks(masks, lens=lens)
+        return st
+
+    def _set_views_jpeg(self, cams, files, params, images, lens):
         V = len(files)
         if lens is not None:
             return self._set_views_lens(cams, files, images if images is not None else [None] * V, lens, params)
@@ -1496,7 +1572,7 @@ def _scene_context(scene, ctx):
     ctx = ctx or Context()
     try:
         ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images)
+        ctx.set_views(scene.cams, scene.images, masks=getattr(scene, "masks", None))
         yield ctx
     finally:
         if own:
