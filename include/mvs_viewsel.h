@@ -320,7 +320,10 @@ mvs_status mvs_set_option(mvs_ctx* ctx, const char* name, int64_t value);
 mvs_status mvs_ctx_get_profile(mvs_ctx* ctx, char* buf, size_t buf_size);
 
 mvs_status mvs_scene_set_mesh(mvs_ctx* ctx, const mvs_mesh* mesh, int on_device);
-/* views: HOST array of n structs; their rgb pointers are device pointers iff rgb_on_device */
+/* views: HOST array of n structs; their rgb pointers are device pointers iff rgb_on_device.
+ * ONE rule for every view input (mvs_scene_set_views, _from, _jpeg, _lens): a refused call leaves the context WITHOUT views, whatever it
+ * held before and however many views the call brought -- until a view input succeeds mvs_ctx_data_costs is MVS_ERR_STATE (not the empty
+ * table of a successful call with zero views), and so are mvs_scene_set_view_masks and the read-back of a view's image. */
 mvs_status mvs_scene_set_views(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, int rgb_on_device);
 /* host images supplied view by view -- an mvs_image_source; mvs_view.rgb is ignored */
 mvs_status mvs_scene_set_views_from(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_image_source* images);
@@ -770,7 +773,8 @@ void mvs_jpeg_free(uint8_t* bytes);
  *   context's next decode.  width, height and offsets are host arrays either way; mvs_rgb_set_free releases what the library allocated.
  * mvs_scene_set_views_jpeg: mvs_scene_set_views with the images taken from files: view j's file is decoded straight into the context's
  *   image buffer of view j.  The frame's size must be views[j].width x height; views[j].rgb is not read.  Afterwards the context is
- *   exactly as mvs_scene_set_views on the decoded pixels leaves it.  A refusal leaves the context without views.  A view whose file
+ *   exactly as mvs_scene_set_views on the decoded pixels leaves it.  A refusal leaves the context without views (the rule at mvs_scene_set_views:
+ *   a data-cost pass is then MVS_ERR_STATE, no longer an empty table).  A view whose file
  *   pointer is null (a PNG, a progressive file) brings its decoded host pixels in views[j].rgb, which are uploaded as
  *   mvs_scene_set_views uploads them.  An image that needs lens undistortion no longer has to come as undistorted host pixels: with
  *   mvs_scene_set_views_lens (below) it stays a file, or the pixels it was decoded to, and is undistorted on the device.
@@ -821,8 +825,8 @@ mvs_status mvs_decode_jpeg(const uint8_t* data, uint64_t size, uint8_t** rgb, ui
  *   A view with dist0 != 0 goes through staging: the 3 * width * height bytes count towards its scratch in the batch cut of the files
  *   (jpeg_params->max_scratch_bytes), and pixel views are staged in groups of at most max_scratch_bytes; a view that does not fit alone is
  *   refused with its number and both sizes.  Views with dist0 == 0 take the path of mvs_scene_set_views_jpeg: no staging, no extra pass.
- *   Afterwards the context is exactly as mvs_scene_set_views on the undistorted pixels leaves it.  A refusal leaves the context without views:
- *   until another view input follows, mvs_ctx_data_costs is MVS_ERR_STATE (not the empty table of a scene of zero views).
+ *   Afterwards the context is exactly as mvs_scene_set_views on the undistorted pixels leaves it.  A refusal leaves the context without views
+ *   (the rule at mvs_scene_set_views).
  * mvs_ctx_undistort_images: the route on its own -- n host images [heights[i]][widths[i]][3] -> their undistorted images back to back in
  *   an mvs_rgb_set as mvs_ctx_decode_jpegs returns one (out_on_device 1: the context's buffer, valid until its next call of this entry).
  *   Image starts are deliberately not aligned.  dist0 == 0 copies.

@@ -2,7 +2,7 @@
 // options / profile, mesh and views (host images through the pinned upload ring), the data-cost phases, table download / upload, the
 // adjacency hand-over and the wrappers of the .spt / .vec files (spt_io.h).  The solver's host loop is solve.hip; the calls that bring
 // their own context -- the host-pointer drop-ins for tex::calculate_data_costs / tex::view_selection -- are oneshot.hip.
-#include "ctx.h"
+#include "view_input.h"
 #include "spt_io.h"
 
 #include <atomic>
@@ -357,12 +357,9 @@ mvs_status mvs_scene_set_views_from(mvs_ctx* ctx, const mvs_view* views, uint32_
 static mvs_status set_views_impl(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, int rgb_on_device, const mvs_image_source* src) {
     if (!ctx || (!views && n_views)) return api_fail(MVS_ERR_INVALID, "null argument");
     MVS_CTX_API_BEGIN
-    ctx->views_refused = false;
-    view_masks_clear(ctx); ctx->view_scratch_cap = 1ull << 30;   // (a view input clears the masks; mvs_jpegdec_default_params' max_scratch_bytes)
-    // image buffers of an earlier call are reused (a context that serves one scene after another allocates once)
-    if (rgb_on_device) { for (auto* b : ctx->own_rgb) delete b; ctx->own_rgb.clear(); }
-    else { while (ctx->own_rgb.size() > n_views) { delete ctx->own_rgb.back(); ctx->own_rgb.pop_back(); } }
-    ctx->h_views.assign(n_views, ViewParams{});
+    view_input_begin(ctx, VIEW_SCRATCH_DEFAULT);   // (a refusal leaves the context without views: view_input.h)
+    own_images_keep(ctx, rgb_on_device ? 0u : n_views);
+    std::vector<ViewParams> hv(n_views, ViewParams{});
     // Host images.  The caller's buffers are pageable, and a pageable hipMemcpyAsync is staged through the driver's bounce buffer at
     // ~13 GB/s (1.9 GB of BASELINE config 3: 146 ms).  Three routes (environment MVS_HOST_UPLOAD; DESIGN.md "Boundary"):
     //   ring      (default) host threads copy the images, cut into 16 MB pieces, into a ring of LIBRARY-OWNED pinned buffers
@@ -406,27 +403,24 @@ static mvs_status set_views_impl(mvs_ctx* ctx, const mvs_view* views, uint32_t n
             held.views.push_back(j);
         }
         if (v.width < 2 || v.height < 2 || !v.rgb) throw StatusError(MVS_ERR_INVALID, "view " + std::to_string(j) + ": bad image");
-        ViewParams& p = ctx->h_views[j];
+        ViewParams& p = hv[j];
         p = view_params_of(v);
         if (rgb_on_device) p.rgb = v.rgb;
         else {
-            if (ctx->own_rgb.size() <= j) ctx->own_rgb.push_back(new DBuf<uint8_t>());
-            auto* b = ctx->own_rgb[j];
+            uint8_t* image = own_image(ctx, j, v);
             const size_t bytes = (size_t)v.width * v.height * 3;
-            b->ensure(bytes + 16);
-            p.rgb = b->p;
-            if (route == UploadRoute::Ring && bytes >= (1u << 18)) { pieces.push_back(UploadPiece{v.rgb, b->p, bytes}); if (src && held.views.size() >= in_flight) flush_batch(); continue; }
+            p.rgb = image;
+            if (route == UploadRoute::Ring && bytes >= (1u << 18)) { pieces.push_back(UploadPiece{v.rgb, image, bytes}); if (src && held.views.size() >= in_flight) flush_batch(); continue; }
             if (route == UploadRoute::Register && bytes >= (1u << 20) && hipHostRegister(const_cast<uint8_t*>(v.rgb), bytes, hipHostRegisterDefault) == hipSuccess) pinned.ptrs.push_back(const_cast<uint8_t*>(v.rgb));
             else (void)hipGetLastError();   // not registered: clear the sticky error, copy from pageable memory
-            MVS_HIP(hipMemcpyAsync(b->p, v.rgb, bytes, hipMemcpyHostToDevice, ctx->stream));
+            MVS_HIP(hipMemcpyAsync(image, v.rgb, bytes, hipMemcpyHostToDevice, ctx->stream));
             if (src && held.views.size() >= in_flight) flush_batch();
         }
     }
     if (src) flush_batch();
     if (!pieces.empty()) upload_through_ring(ctx, pieces);
     MVS_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->n_views = n_views;
-    ctx->have_costs = false; ctx->dc_phase = 0;
+    view_input_commit(ctx, hv, n_views);
     MVS_API_END
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/mvs_viewsel.h"
 #include "dmath.h"
+#include "view_batches.h"
 
 namespace mvs {
 
@@ -204,7 +205,7 @@ struct mvs_ctx {
     std::vector<size_t> gmi_off, mask_off, msum_off;
     mvs::DBuf<size_t> view_off;
     bool mesh_dirty = true, views_dirty = true;
-    bool views_refused = false;      // mvs_scene_set_views_lens refused its views and no other view input followed: a data-cost pass is MVS_ERR_STATE
+    bool views_refused = false;      // the last view input was refused (view_input.h view_input_begin): a data-cost pass is MVS_ERR_STATE
 
     // ---- the library's own mesh layout (k_bvh.hip build_scene_order; DESIGN.md "Face order") ----
     // The caller's mesh arrives in file order (calculate_data_costs.cpp:136-138); nothing about it is assumed.  Every data-cost pass
@@ -280,8 +281,9 @@ struct mvs_ctx {
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
     mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
     mvs::JpegDecDev* jpegdec = nullptr; uint32_t jpegdec_subseq = 128;   // view input (k_jpegdec.hip); option "jpegdec_subseq_bytes": bytes of entropy data one lane owns
-    mvs::LensDev* lens = nullptr;     // view input: the staging buffer, the per-view table and the output of the lens route (k_lens.hip)
-    mvs::ViewMaskDev* viewmask = nullptr; uint64_t view_scratch_cap = 1ull << 30;   // view masks (k_viewmask.hip): the keep words; max_scratch_bytes of the last view input (mask staging is cut by it)
+    mvs::LensDev* lens = nullptr;     // view input: the per-view tables and the output of the lens route (k_lens.hip)
+    mvs::ViewMaskDev* viewmask = nullptr; uint64_t view_scratch_cap = mvs::VIEW_SCRATCH_DEFAULT;   // view masks (k_viewmask.hip): the keep words; max_scratch_bytes of the last view input (mask staging is cut by it)
+    mvs::DBuf<uint8_t> view_staging;  // view input: the staging buffer of all routes (view_input.h view_staging)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -447,10 +449,8 @@ void png_release(mvs_ctx* ctx);
 void jpeg_release(mvs_ctx* ctx);
 void jpegdec_release(mvs_ctx* ctx);   // k_jpegdec.hip
 void lens_release(mvs_ctx* ctx);      // k_lens.hip
-// k_lens.hip: the context's staging buffer with room for `bytes` (16-byte aligned; growing it loses what it held)
-uint8_t* lens_staging(mvs_ctx* ctx, uint64_t bytes);
-// k_lens.hip: byte masks in the camera's frame -> keep words in the undistorted frame, one launch for the n views of T (DESIGN.md section 4
-// "View input" item 10); adds the launch's device time to ms.  Returns with the stream drained.
+// k_lens.hip: byte masks in the camera's frame -> keep words in the undistorted frame, one span launch (view_input.h) for the n views of T
+// (DESIGN.md section 4 "View input" item 10); adds the launch's device time to ms.  Returns with the stream drained.
 struct LensMaskView { const uint8_t* src; uint32_t* keep; int32_t width, height; float flen, d0, d1; uint32_t pad_; };
 void lens_mask_run(mvs_ctx* ctx, const std::vector<LensMaskView>& T, float& ms);
 // k_viewmask.hip: what prepare_views hands to its kernels -- the device table of every view's keep words (null entries: views without a
@@ -463,12 +463,15 @@ const uint32_t* view_keep_words(mvs_ctx* ctx, uint32_t view, std::vector<const u
 void view_masks_clear(mvs_ctx* ctx);
 void viewmask_release(mvs_ctx* ctx);
 // k_jpegdec.hip: the views whose files[j] is not null, decoded in batches whose scratch fits params->max_scratch_bytes (null: the default) --
-// view j into dst[j], or, where staged[j] is not 0, into the context's lens staging (lens_staging), whose 3 * width * height bytes count
-// towards the view's scratch.  After every batch that staged views, after_batch(views, pixels) gets their numbers and where their decoded
+// view j into dst[j], or, where staged[j] is not 0, into the context's staging (view_input.h view_staging), whose 3 * width * height bytes
+// count towards the view's scratch.  After every batch that staged views, after_batch(views, pixels) gets their numbers and where their decoded
 // pixels lie (valid until it returns).  `who` starts the messages; throws as mvs_scene_set_views_jpeg refuses.
 typedef std::function<void(const std::vector<uint32_t>& views, const std::vector<const uint8_t*>& pixels)> StagedBatchFn;
 void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
                        const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch);
+// k_lens.hip: the body of mvs_scene_set_views_jpeg (lens == null) and mvs_scene_set_views_lens behind their argument checks
+mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
+                           const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

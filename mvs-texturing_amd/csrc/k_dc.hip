@@ -1247,7 +1247,7 @@ static void dc_local_max(mvs_ctx* ctx, const DcPass& P) {
 // phase 1: everything up to the per-face sorted infos + local max quality.  true: the face order was rebuilt on the way, nothing is left
 static bool dc_phase1_once(mvs_ctx* ctx, const mvs_settings* st) {
     if (!ctx->d_verts) throw StatusError(MVS_ERR_STATE, "scene not set (mesh + views)");
-    if (ctx->views_refused) throw StatusError(MVS_ERR_STATE, "the context has no views: mvs_scene_set_views_lens refused the last ones");
+    if (ctx->views_refused) throw StatusError(MVS_ERR_STATE, "the context has no views: the last view input was refused");
     /* calculate_data_costs.cpp:315-318 -- F is a uint32 here, so only the view guard can fire */
     if (ctx->n_views > 65535u) throw StatusError(MVS_ERR_TOO_MANY_VIEWS, "Exeeded maximal number of views");
     if (st->data_term != MVS_DATA_TERM_AREA && st->data_term != MVS_DATA_TERM_GMI) throw StatusError(MVS_ERR_INVALID, "bad data_term");

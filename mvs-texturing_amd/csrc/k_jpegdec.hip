@@ -14,8 +14,8 @@
 //                 a segmented scan over MCUs makes the differences values (dc_kernel);
 //     IDCT        idct_kernel, eight lanes per block, one column then one row each, the transpose through LDS;
 //     colour      colour_kernel upsamples the chroma planes and writes interleaved RGB in 16-byte stores into the destination image.
-//   Scratch is bounded by mvs_jpegdec_params.max_scratch_bytes: the files are decoded in batches that fit.
-#include "rows.h"
+//   Scratch is bounded by mvs_jpegdec_params.max_scratch_bytes: the files are decoded in batches that fit (view_batches.h cut_batches).
+#include "view_input.h"
 #include "image_routes.h"
 #include "jpeg_dec.h"
 
@@ -303,9 +303,7 @@ __global__ void __launch_bounds__(THREADS) idct_kernel(Batch B, const uint32_t* 
 __global__ void __launch_bounds__(THREADS) colour_kernel(Batch B, const u64* __restrict__ chunk_ptr, u64 n_chunks, const uint8_t* __restrict__ planes) {
     const u64 g = (u64)blockIdx.x * THREADS + threadIdx.x;
     if (g >= n_chunks) return;
-    uint32_t lo = 0, hi = B.n;
-    while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (chunk_ptr[mid] <= g) lo = mid; else hi = mid; }
-    const uint32_t i = lo;
+    const uint32_t i = span_of(chunk_ptr, B.n, g);
     const Frame& F = B.frame[i];
     const ImgDev& I = B.img[i];
     const u64 bytes = 3ull * F.width * F.height, lead = (u64)((uintptr_t)I.dst & 15u), q = g - chunk_ptr[i];
@@ -341,7 +339,6 @@ void jpegdec_release(mvs_ctx* ctx) { delete ctx->jpegdec; ctx->jpegdec = nullptr
 namespace {
 
 struct HostFile { Frame F; size_t begin = 0, raw_len = 0; uint64_t scratch = 0; uint32_t view = 0; };   // view: its number in the caller's list
-uint64_t align16(uint64_t v) { return (v + 15u) & ~15ull; }
 
 // the scratch one file needs: raw, keep, mark, clean (1 each) and two scans (4 each) per entropy byte, 16 bytes per subsequence,
 // 128 bytes of coefficients per block, 32 per MCU, the planes
@@ -359,7 +356,7 @@ void decode_batch(mvs_ctx* ctx, JpegDecDev& D, const uint8_t* const* files, cons
     std::vector<ImgDev> img(n); std::vector<Frame> frame(n);
     std::vector<uint32_t> t32(4 * ((size_t)n + 1));   // seg_ptr, mcu_ptr, blk_ptr, win_ptr: [n + 1] each
     uint32_t* seg_ptr = t32.data(); uint32_t* mcu_ptr = seg_ptr + n + 1; uint32_t* blk_ptr = mcu_ptr + n + 1; uint32_t* win_ptr = blk_ptr + n + 1;
-    std::vector<u64> chunk_ptr((size_t)n + 1, 0);
+    std::vector<uint64_t> chunks(n);
     uint64_t raw_total = 0, plane_total = 0, seg = 0, mcu = 0, blk = 0; uint32_t raw_max = 0;
     seg_ptr[0] = mcu_ptr[0] = blk_ptr[0] = win_ptr[0] = 0;
     for (uint32_t k = 0; k < n; ++k) {
@@ -372,7 +369,7 @@ void decode_batch(mvs_ctx* ctx, JpegDecDev& D, const uint8_t* const* files, cons
         for (uint32_t c = 0; c < 3u; ++c) { I.plane[c] = plane_total; if (c < f.F.ncomp) plane_total += align16((uint64_t)plane_pitch(f.F, c) * plane_rows(f.F, c)); }
         I.dst = dst[a + k];
         const uint64_t bytes = 3ull * f.F.width * f.F.height;
-        chunk_ptr[k + 1] = chunk_ptr[k] + (((uintptr_t)I.dst & 15u) + bytes + 15u) / 16u;
+        chunks[k] = (((uintptr_t)I.dst & 15u) + bytes + 15u) / 16u;
         seg_ptr[k + 1] = (uint32_t)seg; mcu_ptr[k + 1] = (uint32_t)mcu; blk_ptr[k + 1] = (uint32_t)blk;
         if (raw_total >= 0x7FFFFFF0ull || blk * 64u >= 0xFFFFFFFFFFull || blk >= 0x7FFFFFFFull || seg + n >= 0x7FFFFFFFull)
             throw StatusError(MVS_ERR_UNSUPPORTED, std::string(who) + ": a batch too large for 32-bit positions (lower max_scratch_bytes)");
@@ -472,10 +469,12 @@ void decode_batch(mvs_ctx* ctx, JpegDecDev& D, const uint8_t* const* files, cons
     MVS_LAUNCH_CHECK();
     tm.mark();
     // ---- upsampling and colour ----
+    const std::vector<u64> chunk_ptr = span_prefix(chunks);
     upload(D.t64, chunk_ptr, s);
     const u64 n_chunks = chunk_ptr[n];
-    if (n_chunks >= 0x7FFFFFFFull * THREADS) throw StatusError(MVS_ERR_UNSUPPORTED, std::string(who) + ": too many pixels in one batch");
-    hipLaunchKernelGGL(colour_kernel, dim3((unsigned)((n_chunks + THREADS - 1u) / THREADS)), dim3(THREADS), 0, s, B, (const u64*)D.t64.p, n_chunks, (const uint8_t*)D.planes.p);
+    uint64_t colour_blocks = 0;
+    if (!span_blocks(n_chunks, THREADS, true, colour_blocks)) throw StatusError(MVS_ERR_UNSUPPORTED, std::string(who) + ": too many pixels in one batch");
+    hipLaunchKernelGGL(colour_kernel, dim3((unsigned)colour_blocks), dim3(THREADS), 0, s, B, (const u64*)D.t64.p, n_chunks, (const uint8_t*)D.planes.p);
     MVS_LAUNCH_CHECK();
     tm.mark();
     uint32_t hw[4];
@@ -506,56 +505,34 @@ std::vector<HostFile> read_headers(mvs_ctx* ctx, const uint8_t* const* files, co
     return H;
 }
 // the batch cut: files [cut[k], cut[k + 1]) are batch k, the longest run whose scratch fits; a file that does not fit alone is refused
-std::vector<uint32_t> cut_batches(const std::vector<HostFile>& H, const mvs_jpegdec_params& P, const char* who) {
-    const uint32_t n = (uint32_t)H.size();
-    for (uint32_t k = 0; k < n; ++k)
-        if (H[k].scratch > P.max_scratch_bytes)
-            throw StatusError(MVS_ERR_INVALID, std::string(who) + ": view " + std::to_string(H[k].view) + " needs " + std::to_string(H[k].scratch) + " bytes of scratch, max_scratch_bytes is " + std::to_string(P.max_scratch_bytes));
-    std::vector<uint32_t> cut{0u};
-    for (uint32_t a = 0; a < n;) {
-        uint32_t b = a; uint64_t sum = 0;
-        while (b < n && b - a < 32768u && (b == a || sum + H[b].scratch <= P.max_scratch_bytes)) sum += H[b++].scratch;   // (an image per grid row: at most 65535)
-        cut.push_back(b);
-        a = b;
-    }
-    return cut;
-}
-// all files in batches whose scratch fits
-void decode_files(mvs_ctx* ctx, const uint8_t* const* files, const std::vector<HostFile>& H, uint8_t* const* dst, const mvs_jpegdec_params& P, const char* who, mvs_jpegdec_stats& st) {
-    JpegDecDev& D = row_dev(ctx->jpegdec);
-    const std::vector<uint32_t> cut = cut_batches(H, P, who);
-    for (size_t k = 0; k + 1 < cut.size(); ++k) decode_batch(ctx, D, files, H, cut[k], cut[k + 1], dst, who, st);
+std::vector<size_t> cut_files(const std::vector<HostFile>& H, const mvs_jpegdec_params& P, const char* who) {
+    std::vector<uint64_t> need(H.size()); std::vector<uint32_t> view(H.size());
+    for (size_t k = 0; k < H.size(); ++k) { need[k] = H[k].scratch; view[k] = H[k].view; }
+    refuse_over_cap(need, P.max_scratch_bytes, view.data(), who, "scratch");
+    return cut_batches(need.data(), need.size(), P.max_scratch_bytes, VIEW_FILES_PER_BATCH);
 }
 
 }  // namespace
 
-// the file views of a scene, some of them through the lens staging (ctx.h)
+// the file views of a scene, some of them through the staging (ctx.h)
 void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
                        const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch) {
     const mvs_jpegdec_params P = jpegdec_params(params);
-    std::vector<const uint8_t*> jf; std::vector<uint64_t> js; std::vector<uint32_t> jv;   // the views that come as files
-    for (uint32_t j = 0; j < n_views; ++j) if (files[j]) { jf.push_back(files[j]); js.push_back(sizes[j]); jv.push_back(j); }
-    std::vector<HostFile> H = read_headers(ctx, jf.data(), js.data(), (uint32_t)jf.size(), jv.data(), views, who, st);
-    const uint32_t n = (uint32_t)H.size();
-    auto stage_bytes = [&](uint32_t k) -> uint64_t { return staged[H[k].view] ? align16(3ull * H[k].F.width * H[k].F.height) : 0ull; };
-    for (uint32_t k = 0; k < n; ++k) H[k].scratch += stage_bytes(k);
-    const std::vector<uint32_t> cut = cut_batches(H, P, who);
-    // every batch stages from the buffer's start: it is as large as the largest batch needs
-    uint64_t most = 0;
-    std::vector<uint64_t> off(n, 0);
-    for (size_t b = 0; b + 1 < cut.size(); ++b) {
-        uint64_t sum = 0;
-        for (uint32_t k = cut[b]; k < cut[b + 1]; ++k) { off[k] = sum; sum += stage_bytes(k); }
-        most = std::max(most, sum);
-    }
-    uint8_t* staging = most ? lens_staging(ctx, most) : nullptr;
+    const FileViews fv = file_views(files, sizes, n_views);
+    std::vector<HostFile> H = read_headers(ctx, fv.files.data(), fv.sizes.data(), (uint32_t)fv.files.size(), fv.view.data(), views, who, st);
+    const size_t n = H.size();
+    std::vector<uint64_t> stage_bytes(n);   // a staged file's decoded pixels count towards its scratch
+    for (size_t k = 0; k < n; ++k) { stage_bytes[k] = staged[H[k].view] ? 3ull * H[k].F.width * H[k].F.height : 0ull; H[k].scratch += align16(stage_bytes[k]); }
+    const std::vector<size_t> cut = cut_files(H, P, who);
+    const BatchLayout L = batch_layout(stage_bytes.data(), n, cut);   // every batch stages from the buffer's start: it is as large as the largest batch needs
+    uint8_t* staging = L.most ? view_staging(ctx, L.most) : nullptr;
     std::vector<uint8_t*> to(n);
-    for (uint32_t k = 0; k < n; ++k) to[k] = staged[H[k].view] ? staging + off[k] : dst[H[k].view];
+    for (size_t k = 0; k < n; ++k) to[k] = staged[H[k].view] ? staging + L.off[k] : dst[H[k].view];
     JpegDecDev& D = row_dev(ctx->jpegdec);
     for (size_t b = 0; b + 1 < cut.size(); ++b) {
-        decode_batch(ctx, D, jf.data(), H, cut[b], cut[b + 1], to.data(), who, st);
+        decode_batch(ctx, D, fv.files.data(), H, (uint32_t)cut[b], (uint32_t)cut[b + 1], to.data(), who, st);
         std::vector<uint32_t> bv; std::vector<const uint8_t*> bp;
-        for (uint32_t k = cut[b]; k < cut[b + 1]; ++k) if (staged[H[k].view]) { bv.push_back(H[k].view); bp.push_back(to[k]); }
+        for (size_t k = cut[b]; k < cut[b + 1]; ++k) if (staged[H[k].view]) { bv.push_back(H[k].view); bp.push_back(to[k]); }
         if (!bv.empty()) after_batch(bv, bp);
     }
 }
@@ -566,7 +543,7 @@ using namespace mvs;
 
 extern "C" {
 
-void mvs_jpegdec_default_params(mvs_jpegdec_params* p) { if (p) { p->max_scratch_bytes = 1ull << 30; p->reserved = 0; } }
+void mvs_jpegdec_default_params(mvs_jpegdec_params* p) { if (p) { p->max_scratch_bytes = VIEW_SCRATCH_DEFAULT; p->reserved = 0; } }
 
 mvs_status mvs_ctx_decode_jpegs(mvs_ctx* ctx, const uint8_t* const* files, const uint64_t* sizes, uint32_t n, const mvs_jpegdec_params* params, int out_on_device,
                                 mvs_rgb_set* out, mvs_jpegdec_stats* stats) {
@@ -580,20 +557,12 @@ mvs_status mvs_ctx_decode_jpegs(mvs_ctx* ctx, const uint8_t* const* files, const
         run_with_stats(ctx->stream, stats, st, [&] {
             const std::vector<HostFile> H = read_headers(ctx, files, sizes, n, nullptr, nullptr, "decode_jpegs", st);
             JpegDecDev& D = row_dev(ctx->jpegdec);
-            std::vector<uint64_t> off((size_t)n + 1, 0);
-            for (uint32_t k = 0; k < n; ++k) off[k + 1] = off[k] + 3ull * H[k].F.width * H[k].F.height;
-            D.out.ensure((size_t)off[n] + 16);
-            std::vector<uint8_t*> dst(n);
-            for (uint32_t k = 0; k < n; ++k) dst[k] = D.out.p + off[k];
-            decode_files(ctx, files, H, dst.data(), P, "decode_jpegs", st);
-            download<mvs_rgb_set>(ctx->stream, out, mvs_rgb_set_free, [&] {
-                out->n_images = n; out->on_device = out_on_device ? 1u : 0u; out->n_bytes = off[n];
-                out->offsets = (uint64_t*)malloc(((size_t)n + 1) * sizeof(uint64_t)); out->width = (uint32_t*)malloc(std::max<size_t>(n, 1) * sizeof(uint32_t)); out->height = (uint32_t*)malloc(std::max<size_t>(n, 1) * sizeof(uint32_t));
-                if (!out->offsets || !out->width || !out->height) throw StatusError(MVS_ERR_INVALID, "out of host memory");
-                memcpy(out->offsets, off.data(), ((size_t)n + 1) * sizeof(uint64_t));
-                for (uint32_t k = 0; k < n; ++k) { out->width[k] = H[k].F.width; out->height[k] = H[k].F.height; }
-                out->data = out_on_device ? D.out.p : host_copy(D.out.p, (size_t)off[n], ctx->stream);
-            });
+            std::vector<uint32_t> w(n), h(n);
+            for (uint32_t k = 0; k < n; ++k) { w[k] = H[k].F.width; h[k] = H[k].F.height; }
+            const RgbRoom R = rgb_set_room(D.out, w, h);
+            const std::vector<size_t> cut = cut_files(H, P, "decode_jpegs");   // all files in batches whose scratch fits
+            for (size_t k = 0; k + 1 < cut.size(); ++k) decode_batch(ctx, D, files, H, (uint32_t)cut[k], (uint32_t)cut[k + 1], R.dst.data(), "decode_jpegs", st);
+            rgb_set_out(ctx, D.out, R, w, h, out_on_device, out);
         });
     });
 }
@@ -608,41 +577,7 @@ void mvs_rgb_set_free(mvs_rgb_set* p) {
 mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, const mvs_jpegdec_params* params,
                                     mvs_jpegdec_stats* stats) {
     if (!ctx || (n_views && (!views || !files || !sizes))) return api_fail(MVS_ERR_INVALID, "null argument");
-    for (uint32_t j = 0; j < n_views; ++j) if (!files[j] && !views[j].rgb) return api_fail(MVS_ERR_INVALID, "view " + std::to_string(j) + ": neither a file nor pixels");
-    mvs_jpegdec_stats st{};
-    if (stats) *stats = st;
-    return api_guard([&] {
-        MVS_HIP(hipSetDevice(ctx->device));
-        const mvs_jpegdec_params P = jpegdec_params(params);
-        // a refusal leaves the context without views
-        ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0; ctx->views_refused = false;
-        view_masks_clear(ctx); ctx->view_scratch_cap = P.max_scratch_bytes;   // (a view input clears the masks; the masks of these views are staged under the same cap)
-        run_with_stats(ctx->stream, stats, st, [&] {
-            for (uint32_t j = 0; j < n_views; ++j)
-                if (views[j].width < 2 || views[j].height < 2) throw StatusError(MVS_ERR_INVALID, "view " + std::to_string(j) + ": bad image");
-            std::vector<const uint8_t*> jf; std::vector<uint64_t> js; std::vector<uint32_t> jv;   // the views that come as files
-            for (uint32_t j = 0; j < n_views; ++j) if (files[j]) { jf.push_back(files[j]); js.push_back(sizes[j]); jv.push_back(j); }
-            const std::vector<HostFile> H = read_headers(ctx, jf.data(), js.data(), (uint32_t)jf.size(), jv.data(), views, "set_views_jpeg", st);
-            while (ctx->own_rgb.size() > n_views) { delete ctx->own_rgb.back(); ctx->own_rgb.pop_back(); }
-            std::vector<ViewParams> hv(n_views, ViewParams{});
-            std::vector<uint8_t*> dst; std::vector<const uint8_t*> psrc; std::vector<uint8_t*> pdst; std::vector<size_t> pbytes;   // decoded into / pixels uploaded
-            for (uint32_t j = 0; j < n_views; ++j) {
-                const mvs_view& v = views[j];
-                ViewParams& p = hv[j];
-                p = view_params_of(v);
-                if (ctx->own_rgb.size() <= j) ctx->own_rgb.push_back(new DBuf<uint8_t>());
-                ctx->own_rgb[j]->ensure((size_t)v.width * v.height * 3 + 16);
-                p.rgb = ctx->own_rgb[j]->p;
-                if (files[j]) dst.push_back(ctx->own_rgb[j]->p);
-                else { psrc.push_back(v.rgb); pdst.push_back(ctx->own_rgb[j]->p); pbytes.push_back((size_t)v.width * v.height * 3); }
-            }
-            upload_pieces_through_ring(ctx, psrc.data(), pdst.data(), pbytes.data(), psrc.size());
-            decode_files(ctx, jf.data(), H, dst.data(), P, "set_views_jpeg", st);
-            MVS_HIP(hipStreamSynchronize(ctx->stream));
-            ctx->h_views.swap(hv);
-            ctx->n_views = n_views;
-        });
-    });
+    return set_views_files(ctx, views, n_views, nullptr, files, sizes, params, stats, nullptr, "", "set_views_jpeg");
 }
 
 mvs_status mvs_jpeg_probe(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height) {

@@ -250,7 +250,7 @@ class MaskStats(C.Structure):
 
 def _lens_array(lens, n):
     """an (n, 3) array of (flen, dist0, dist1) -- or (n, 4) with the reserved word, which must be 0 -- as the ABI's mvs_lens [n]"""
-    a = np.asarray(lens, dtype=np.float32).reshape(n, -1)
+    a = np.asarray(lens, dtype=np.float32).reshape(n, -1) if n else np.zeros((0, 3), np.float32)
     assert a.shape[1] in (3, 4)
     arr = (Lens * max(n, 1))()
     for j in range(n):
@@ -611,10 +611,12 @@ class Context:
         """cams: dict of arrays pos, viewdir, K, w2c, width, height; images: list of (H,W,3) u8 numpy / torch cuda.
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the images are then host arrays as the camera took them, and the
         views with dist0 != 0 are undistorted on the device (mvs_scene_set_views_lens; returns the lens stats).
-        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats)"""
+        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats).
+        A refused call raises MvsError and leaves the context without views (n_views == 0): data_costs then raises status 6 until a
+        set_views* succeeds."""
         V = len(images)
         if lens is not None:
-            st = self._set_views_lens(cams, [None] * V, images, lens, None)["lens"]
+            st = self._set_views_files(cams, [None] * V, images, lens, None)["lens"]
             if masks is not None:
                 self.set_view_masks(masks, lens=lens)
             return st
@@ -624,23 +626,15 @@ class Context:
 
     def _set_views_plain(self, cams, images):
         V = len(images)
-        arr = (CView * V)()
+        arr = self._view_array(cams, V)
         dev = None
         for j in range(V):
-            v = arr[j]
-            v.pos[:] = np.asarray(cams["pos"][j], dtype=np.float32).tolist()
-            v.viewdir[:] = np.asarray(cams["viewdir"][j], dtype=np.float32).tolist()
-            v.K[:] = np.asarray(cams["K"][j], dtype=np.float32).ravel().tolist()
-            v.w2c[:] = np.asarray(cams["w2c"][j], dtype=np.float32).ravel().tolist()
-            v.width, v.height = int(cams["width"][j]), int(cams["height"][j])
-            p, d = _ptr(images[j])
-            v.rgb = p
+            arr[j].rgb, d = _ptr(images[j])
             assert dev is None or dev == d
             dev = d
-        self._keep["views"] = images
-        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)]
-        self.n_views = V
-        _check(self.L, self.L.mvs_scene_set_views(self.h, arr, V, dev or 0))
+        rc = self.L.mvs_scene_set_views(self.h, arr, V, dev or 0)
+        self._views_set(V, cams, rc, images)
+        _check(self.L, rc)
 
     def _view_array(self, cams, V):
         arr = (CView * V)()
@@ -653,6 +647,36 @@ class Context:
             v.width, v.height = int(cams["width"][j]), int(cams["height"][j])
         return arr
 
+    def _views_set(self, V, cams, rc, held=None):
+        """the bookkeeping behind every set_views*: the V views of cams (`held` keeps their images alive), or none after a refusal (rc != 0)"""
+        ok = rc == 0
+        self._keep["views"] = held if ok else None
+        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)] if ok else []
+        self.n_views = V if ok else 0
+
+    @staticmethod
+    def _pixel_views(arr, files, images):
+        """the views without a file bring host pixels: arr[j].rgb points into the returned arrays, which the caller holds during the call"""
+        pixels = [None if f is not None else np.ascontiguousarray(images[j], np.uint8) for j, f in enumerate(files)]
+        for j, px in enumerate(pixels):
+            if px is not None:
+                assert px.shape == (arr[j].height, arr[j].width, 3)
+                arr[j].rgb = px.ctypes.data_as(C.c_void_p)
+        return pixels
+
+    def _rgb_set_images(self, res, n, shapes, on_device):
+        """an RgbSet as a list of (H, W, 3) uint8 arrays, or with on_device of (DevArray, H, W); shapes: every image's (H, W), None: the set's own"""
+        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
+        if shapes is None:
+            shapes = list(zip(np.frombuffer(C.string_at(res.height, 4 * n), np.uint32).tolist(), np.frombuffer(C.string_at(res.width, 4 * n), np.uint32).tolist())) if n else []
+        if on_device:
+            out = [(DevArray(res.data + int(off[i]), int(off[i + 1] - off[i])), int(h), int(w)) for i, (h, w) in enumerate(shapes)]
+        else:
+            data = np.frombuffer(C.string_at(res.data, res.n_bytes), np.uint8)
+            out = [data[int(off[i]):int(off[i + 1])].reshape(int(h), int(w), 3).copy() for i, (h, w) in enumerate(shapes)]
+        self.L.mvs_rgb_set_free(C.byref(res))
+        return out
+
     @staticmethod
     def _file_arrays(files):
         """a list of JPEG files (bytes) as the arrays of pointers and sizes the ABI takes; `held` keeps the bytes alive"""
@@ -662,25 +686,23 @@ class Context:
         sizes = (C.c_uint64 * max(n, 1))(*[0 if f is None else len(f) for f in held])
         return held, ptrs, sizes
 
-    def _set_views_lens(self, cams, files, images, lens, params):
-        """mvs_scene_set_views_lens: the jpeg stats with the lens stats under "lens"; a refusal raises MvsError with them as `.stats`"""
+    def _set_views_files(self, cams, files, images, lens, params):
+        """mvs_scene_set_views_jpeg, or with lens mvs_scene_set_views_lens: the jpeg stats, with a lens the lens stats under "lens"; a refusal
+        raises MvsError with them as `.stats`"""
         V = len(files)
         arr = self._view_array(cams, V)
-        any_file = any(f is not None for f in files)
         held, ptrs, sizes = self._file_arrays(files)
-        pixels = [None if files[j] is not None else np.ascontiguousarray(images[j], np.uint8) for j in range(V)]
-        for j in range(V):
-            if pixels[j] is not None:
-                assert pixels[j].shape == (arr[j].height, arr[j].width, 3)
-                arr[j].rgb = pixels[j].ctypes.data_as(C.c_void_p)
-        st, ls = JpegDecStats(), LensStats()
-        rc = self.L.mvs_scene_set_views_lens(self.h, arr, V, _lens_array(lens, V), ptrs if any_file else None, sizes if any_file else None,
-                                             C.byref(params) if params is not None else None, C.byref(st), C.byref(ls))
+        pixels = self._pixel_views(arr, files, images)   # (held during the call)
+        st, ls, pp = JpegDecStats(), LensStats(), C.byref(params) if params is not None else None
+        if lens is None:
+            rc = self.L.mvs_scene_set_views_jpeg(self.h, arr, V, ptrs, sizes, pp, C.byref(st))
+        else:
+            any_file = any(f is not None for f in files)
+            rc = self.L.mvs_scene_set_views_lens(self.h, arr, V, _lens_array(lens, V), ptrs if any_file else None, sizes if any_file else None, pp, C.byref(st), C.byref(ls))
         stats = _stats_dict(st)
-        stats["lens"] = _stats_dict(ls)
-        self._keep["views"] = None
-        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)] if rc == 0 else []
-        self.n_views = V if rc == 0 else 0
+        if lens is not None:
+            stats["lens"] = _stats_dict(ls)
+        self._views_set(V, cams, rc)
         _check_with_stats(self.L, rc, stats)
         return stats
 
@@ -747,14 +769,7 @@ class Context:
         rc = self.L.mvs_ctx_undistort_images(self.h, ptrs, w, h, _lens_array(lens, n), n, 1 if on_device else 0, C.byref(res), C.byref(st))
         stats = _stats_dict(st)
         _check_with_stats(self.L, rc, stats)
-        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
-        if on_device:
-            out = [(DevArray(res.data + int(off[i]), int(off[i + 1] - off[i])), imgs[i].shape[0], imgs[i].shape[1]) for i in range(n)]
-        else:
-            data = np.frombuffer(C.string_at(res.data, res.n_bytes), np.uint8)
-            out = [data[int(off[i]):int(off[i + 1])].reshape(imgs[i].shape).copy() for i in range(n)]
-        self.L.mvs_rgb_set_free(C.byref(res))
-        return out, stats
+        return self._rgb_set_images(res, n, [i.shape[:2] for i in imgs], on_device), stats
 
     def view_image(self, j):
         """the context's image of view j as it lies on the device, (H, W, 3) uint8 (mvs_ctx_view_image, building-blocks library; test
@@ -770,33 +785,15 @@ class Context:
         """mvs_scene_set_views_jpeg: set_views with the images taken from baseline JPEG files (a list of bytes), decoded on the device
         straight into the context's image buffers (DESIGN.md section 4 "View input").  The frames' sizes must be cams' width / height.
         A view whose entry in `files` is None brings its pixels as images[j], an (H, W, 3) uint8 host array.
-        Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views.
+        Returns the stats; a refusal raises MvsError with them as `.stats` and leaves the context without views (n_views == 0): data_costs
+        then raises status 6 until a set_views* succeeds.
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the views with dist0 != 0, files and pixels alike, are undistorted
         on the device (mvs_scene_set_views_lens); the stats then carry the lens stats under "lens".
         masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats)."""
-        st = self._set_views_jpeg(cams, files, params, images, lens)
+        st = self._set_views_files(cams, files, images, lens, params)
         if masks is not None:
             self.set_view_masks(masks, lens=lens)
         return st
-
-    def _set_views_jpeg(self, cams, files, params, images, lens):
-        V = len(files)
-        if lens is not None:
-            return self._set_views_lens(cams, files, images if images is not None else [None] * V, lens, params)
-        arr = self._view_array(cams, V)
-        held, ptrs, sizes = self._file_arrays(files)
-        pixels = [None if files[j] is not None else np.ascontiguousarray(images[j], np.uint8) for j in range(V)]
-        for j in range(V):
-            if pixels[j] is not None:
-                assert pixels[j].shape == (arr[j].height, arr[j].width, 3)
-                arr[j].rgb = pixels[j].ctypes.data_as(C.c_void_p)
-        st = JpegDecStats()
-        rc = self.L.mvs_scene_set_views_jpeg(self.h, arr, V, ptrs, sizes, C.byref(params) if params is not None else None, C.byref(st))
-        _check_with_stats(self.L, rc, _stats_dict(st))
-        self._keep["views"] = None
-        self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)]
-        self.n_views = V
-        return _stats_dict(st)
 
     def decode_jpegs(self, files, params=None, on_device=False):
         """mvs_ctx_decode_jpegs: the view input route on its own -- `files` (a list of bytes, baseline JPEG) decoded in one call.  Returns
@@ -808,16 +805,7 @@ class Context:
         rc = self.L.mvs_ctx_decode_jpegs(self.h, ptrs, sizes, n, C.byref(params) if params is not None else None, 1 if on_device else 0, C.byref(res), C.byref(st))
         stats = _stats_dict(st)
         _check_with_stats(self.L, rc, stats)
-        off = np.frombuffer(C.string_at(res.offsets, 8 * (n + 1)), np.uint64)
-        w = np.frombuffer(C.string_at(res.width, 4 * n), np.uint32) if n else np.zeros(0, np.uint32)
-        h = np.frombuffer(C.string_at(res.height, 4 * n), np.uint32) if n else np.zeros(0, np.uint32)
-        if on_device:
-            out = [(DevArray(res.data + int(off[i]), int(off[i + 1] - off[i])), int(h[i]), int(w[i])) for i in range(n)]
-        else:
-            data = np.frombuffer(C.string_at(res.data, res.n_bytes), np.uint8)
-            out = [data[int(off[i]):int(off[i + 1])].reshape(int(h[i]), int(w[i]), 3).copy() for i in range(n)]
-        self.L.mvs_rgb_set_free(C.byref(res))
-        return out, stats
+        return self._rgb_set_images(res, n, None, on_device), stats
 
     def set_face_range(self, begin, end):
         """positions [begin, end) of the library's face order (the caller's ids with option face_order = 0)"""
