@@ -814,6 +814,46 @@ mvs_status mvs_scene_set_views_jpeg(mvs_ctx* ctx, const mvs_view* views, uint32_
 mvs_status mvs_jpeg_probe(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height);
 mvs_status mvs_decode_jpeg(const uint8_t* data, uint64_t size, uint8_t** rgb, uint32_t* width, uint32_t* height, int16_t** coefs, uint64_t* n_blocks);
 
+/* View input: PNG files inflated and unfiltered on the device (DESIGN.md section 4 "View input" and csrc/png_dec.h define the format
+ * accepted and the arithmetic; PNG is lossless: the pixels are those of any PNG reader's 8-bit RGB, Pillow's convert("RGB"), bit for bit).
+ * Accepted: bit depth 8, colour type 0, 2, 3, 4 or 6 (grey is written as R = G = B, alpha of any kind is dropped, tRNS is not read, a
+ * palette index becomes its PLTE entry), compression 0, filter method 0, no interlace; IHDR first, PLTE (a multiple of 3 bytes, at most
+ * 768; required for colour type 3) in front of the IDATs, one or more consecutive IDAT chunks; IEND is not required.  The host walks every
+ * chunk by its length and checks the CRC of IHDR and PLTE.  IDAT CRCs are NOT checked: the zlib stream's Adler-32 is, and it covers every
+ * byte that becomes a pixel.  zlib: CM 8, CINFO <= 7, FCHECK, no FDICT; stored, fixed and dynamic blocks.  Inflated bytes beyond
+ * height * (1 + width * bytes per pixel) are ignored (the stream is still read to its end; its Adler-32, which covers them, is then not
+ * checked).  Everything else is MVS_ERR_INVALID with a message that names the file and the reason: the other bit depths, Adam7, a missing
+ * PLTE, IDATs that are not consecutive, a chunk running past the file, no IDAT, an unknown critical chunk; block type 3, LEN != ~NLEN, HLIT
+ * above 286 or HDIST above 30, a used length symbol 286 / 287 or distance code 30 / 31, a repeat code 16 with no previous length, a repeat
+ * past HLIT + HDIST, an over-subscribed code, an incomplete code (other than no distance code at all and zlib's single distance code of one
+ * bit), no end-of-block code, a distance further back than the bytes produced, a stream that ends inside a symbol or before the final
+ * block's end, an Adler-32 mismatch, fewer inflated bytes than the image needs, a filter type above 4 (with its row), palette indices at or
+ * past PLTE's entries (with the count of such pixels).
+ * Only the IDAT payloads cross the bus, through the pinned upload ring; one wave64 per stream inflates, the Adler-32 is summed in pieces,
+ * and one wave per file unfilters bands of 64 rows, a lane per row, each one pixel behind the row above (csrc/k_pngdec.hip).
+ * mvs_ctx_decode_pngs: the route on its own; arguments and result as mvs_ctx_decode_jpegs (params gives max_scratch_bytes: the zlib
+ *   bytes, the inflated stream and, under a lens, the staged pixels of a batch; a file that does not fit alone is refused).
+ * mvs_scene_set_views_files: the rule of mvs_scene_set_views_lens with one addition: a file that starts with the PNG signature takes the PNG
+ *   route, any other file the JPEG route; a null file brings pixels in views[j].rgb.  lens == null: no view is undistorted.  The frame's size
+ *   must be the view's.  Afterwards the context is exactly as mvs_scene_set_views on the decoded, undistorted pixels leaves it; a refusal
+ *   leaves the context without views.  mvs_scene_set_views_jpeg and mvs_scene_set_views_lens refuse a PNG as before.
+ * mvs_png_probe: MVS_OK and the frame's size when the file's chunks are in the accepted format (the zlib stream is not read).
+ * stats are filled on refusals too.
+ * mvs_decode_png: the same image on the host, sequentially -- no GPU, no library; *rgb is malloc'ed (mvs_png_free).  raw (may be null): the
+ *   inflated, still filtered stream, height * (1 + width * bytes per pixel) bytes, malloc'ed (mvs_png_free). */
+typedef struct mvs_pngdec_stats {
+    uint64_t files, file_bytes, idat_chunks;
+    uint64_t zlib_bytes, raw_bytes;              /* the IDAT payloads; the inflated streams as the images need them */
+    uint64_t stored_blocks, fixed_blocks, dynamic_blocks;
+    uint64_t filter_rows[5];                     /* rows per filter type */
+    uint64_t batches;
+    float ms_upload, ms_inflate, ms_adler, ms_unfilter;
+} mvs_pngdec_stats;
+mvs_status mvs_ctx_decode_pngs(mvs_ctx* ctx, const uint8_t* const* files, const uint64_t* sizes, uint32_t n, const mvs_jpegdec_params* params,
+                               int out_on_device, mvs_rgb_set* out_set, mvs_pngdec_stats* stats);
+mvs_status mvs_png_probe(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height);
+mvs_status mvs_decode_png(const uint8_t* data, uint64_t size, uint8_t** rgb, uint32_t* width, uint32_t* height, uint8_t** raw);
+
 /* View input: lens undistortion on the device (row f4's arithmetic -- csrc/lens.h states it once for undistort_kernel, the batched kernel
  * and the host twin; DESIGN.md section 4 "View input").  A view comes as pixels or as a baseline JPEG file together with its lens, is
  * uploaded and / or decoded once into a staging buffer of the context, and ONE launch per batch (csrc/k_lens.hip) writes the
@@ -842,6 +882,9 @@ typedef struct mvs_lens_stats {
 } mvs_lens_stats;
 mvs_status mvs_scene_set_views_lens(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
                                     const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats);
+/* (the PNG view input above: files may be PNGs or baseline JPEGs; lens may be null) */
+mvs_status mvs_scene_set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
+                                     const mvs_jpegdec_params* params, mvs_jpegdec_stats* jpeg_stats, mvs_pngdec_stats* png_stats, mvs_lens_stats* lens_stats);
 mvs_status mvs_ctx_undistort_images(mvs_ctx* ctx, const uint8_t* const* images, const uint32_t* widths, const uint32_t* heights, const mvs_lens* lens, uint32_t n,
                                     int out_on_device, mvs_rgb_set* out_set, mvs_lens_stats* stats);
 mvs_status mvs_undistort_image_host(const uint8_t* rgb, int32_t width, int32_t height, float flen, float dist0, float dist1, uint8_t* out);

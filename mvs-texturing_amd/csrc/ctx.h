@@ -146,6 +146,7 @@ struct PngDev;   // row f9's compressed PNGs (k_png.hip)
 struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
 struct JpegDecDev;   // view input: JPEG files decoded on the device (k_jpegdec.hip)
 struct LensDev;      // view input: lens undistortion on the device (k_lens.hip)
+struct PngDecDev;    // view input: PNG files inflated and unfiltered on the device (k_pngdec.hip)
 struct ViewMaskDev;  // view input: the keep words of the views that carry a mask (k_viewmask.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
@@ -281,6 +282,7 @@ struct mvs_ctx {
     mvs::PngDev* png = nullptr;       // row f9's compressed PNGs (k_png.hip)
     mvs::JpegDev* jpeg = nullptr;     // rows f9 / f11: JPEG images (k_jpeg.hip)
     mvs::JpegDecDev* jpegdec = nullptr; uint32_t jpegdec_subseq = 128;   // view input (k_jpegdec.hip); option "jpegdec_subseq_bytes": bytes of entropy data one lane owns
+    mvs::PngDecDev* pngdec = nullptr; // view input: the PNG route's buffers (k_pngdec.hip)
     mvs::LensDev* lens = nullptr;     // view input: the per-view tables and the output of the lens route (k_lens.hip)
     mvs::ViewMaskDev* viewmask = nullptr; uint64_t view_scratch_cap = mvs::VIEW_SCRATCH_DEFAULT;   // view masks (k_viewmask.hip): the keep words; max_scratch_bytes of the last view input (mask staging is cut by it)
     mvs::DBuf<uint8_t> view_staging;  // view input: the staging buffer of all routes (view_input.h view_staging)
@@ -448,6 +450,7 @@ void debug_release(mvs_ctx* ctx);
 void png_release(mvs_ctx* ctx);
 void jpeg_release(mvs_ctx* ctx);
 void jpegdec_release(mvs_ctx* ctx);   // k_jpegdec.hip
+void pngdec_release(mvs_ctx* ctx);    // k_pngdec.hip
 void lens_release(mvs_ctx* ctx);      // k_lens.hip
 // k_lens.hip: byte masks in the camera's frame -> keep words in the undistorted frame, one span launch (view_input.h) for the n views of T
 // (DESIGN.md section 4 "View input" item 10); adds the launch's device time to ms.  Returns with the stream drained.
@@ -467,11 +470,18 @@ void viewmask_release(mvs_ctx* ctx);
 // count towards the view's scratch.  After every batch that staged views, after_batch(views, pixels) gets their numbers and where their decoded
 // pixels lie (valid until it returns).  `who` starts the messages; throws as mvs_scene_set_views_jpeg refuses.
 typedef std::function<void(const std::vector<uint32_t>& views, const std::vector<const uint8_t*>& pixels)> StagedBatchFn;
+// png_stats (null: the entries that refuse a PNG as any file that is no baseline JPEG): a file that starts with the PNG signature takes the
+// PNG route (decode_view_pngs) under the same rules, its batches cut on their own.
 void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
-                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch);
-// k_lens.hip: the body of mvs_scene_set_views_jpeg (lens == null) and mvs_scene_set_views_lens behind their argument checks
+                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch, mvs_pngdec_stats* png_stats = nullptr);
+// k_pngdec.hip: decode_view_files for the PNG files fv of a scene (view_input.h FileViews; dst and staged are indexed by the view)
+struct FileViews;
+void decode_view_pngs(mvs_ctx* ctx, const mvs_view* views, const FileViews& fv, uint8_t* const* dst, const uint8_t* staged, const mvs_jpegdec_params* params, const char* who,
+                      mvs_pngdec_stats& st, const StagedBatchFn& after_batch);
+// k_lens.hip: the body of mvs_scene_set_views_jpeg (lens == null), mvs_scene_set_views_lens and mvs_scene_set_views_files (accept_png) behind their argument checks
 mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
-                           const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who);
+                           const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who,
+                           bool accept_png = false, mvs_pngdec_stats* png_stats = nullptr);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

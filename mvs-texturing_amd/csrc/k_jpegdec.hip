@@ -18,6 +18,7 @@
 #include "view_input.h"
 #include "image_routes.h"
 #include "jpeg_dec.h"
+#include "png_dec.h"
 
 namespace mvs {
 
@@ -516,9 +517,19 @@ std::vector<size_t> cut_files(const std::vector<HostFile>& H, const mvs_jpegdec_
 
 // the file views of a scene, some of them through the staging (ctx.h)
 void decode_view_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const uint8_t* const* files, const uint64_t* sizes, uint8_t* const* dst, const uint8_t* staged,
-                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch) {
+                       const mvs_jpegdec_params* params, const char* who, mvs_jpegdec_stats& st, const StagedBatchFn& after_batch, mvs_pngdec_stats* png_stats) {
     const mvs_jpegdec_params P = jpegdec_params(params);
-    const FileViews fv = file_views(files, sizes, n_views);
+    FileViews fv = file_views(files, sizes, n_views);
+    if (png_stats) {   // the files with the PNG signature leave the list for their own route
+        FileViews jpegs, pngs;
+        for (size_t k = 0; k < fv.files.size(); ++k) {
+            FileViews& to = png_dec::has_signature(fv.files[k], (size_t)fv.sizes[k]) ? pngs : jpegs;
+            to.files.push_back(fv.files[k]); to.sizes.push_back(fv.sizes[k]); to.view.push_back(fv.view[k]);
+        }
+        if (!pngs.files.empty()) decode_view_pngs(ctx, views, pngs, dst, staged, params, who, *png_stats, after_batch);
+        fv = jpegs;
+        if (fv.files.empty()) return;
+    }
     std::vector<HostFile> H = read_headers(ctx, fv.files.data(), fv.sizes.data(), (uint32_t)fv.files.size(), fv.view.data(), views, who, st);
     const size_t n = H.size();
     std::vector<uint64_t> stage_bytes(n);   // a staged file's decoded pixels count towards its scratch

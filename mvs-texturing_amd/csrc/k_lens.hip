@@ -140,20 +140,23 @@ void stage_pixels(mvs_ctx* ctx, const std::vector<const uint8_t*>& src, const st
 
 }  // namespace
 
-// mvs_scene_set_views_jpeg (lens == null: no view is undistorted) and mvs_scene_set_views_lens behind their argument checks: who_view starts
-// the messages about a view's size and source ("" for the JPEG entry), `who` all others
+// mvs_scene_set_views_jpeg (lens == null: no view is undistorted), mvs_scene_set_views_lens and mvs_scene_set_views_files (accept_png: a file
+// with the PNG signature takes the route of k_pngdec.hip) behind their argument checks: who_view starts the messages about a view's size
+// and source ("" for the JPEG entry), `who` all others
 mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
-                           const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who) {
+                           const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who,
+                           bool accept_png, mvs_pngdec_stats* png_stats) {
     for (uint32_t j = 0; j < n_views; ++j)
         if (!(files && files[j]) && !views[j].rgb) return api_fail(MVS_ERR_INVALID, view_msg(who_view, j) + "neither a file nor pixels");
-    mvs_jpegdec_stats jst{}; mvs_lens_stats st{};
+    mvs_jpegdec_stats jst{}; mvs_lens_stats st{}; mvs_pngdec_stats pst{};
     if (jpeg_stats) *jpeg_stats = jst;
     if (lens_stats) *lens_stats = st;
+    if (png_stats) *png_stats = pst;
     return api_guard([&] {
         MVS_HIP(hipSetDevice(ctx->device));
         const uint64_t cap = jpeg_params ? jpeg_params->max_scratch_bytes : VIEW_SCRATCH_DEFAULT;
         view_input_begin(ctx, cap);
-        run_with_stats(ctx->stream, jpeg_stats, jst, [&] { run_with_stats(ctx->stream, lens_stats, st, [&] {
+        run_with_stats(ctx->stream, png_stats, pst, [&] { run_with_stats(ctx->stream, jpeg_stats, jst, [&] { run_with_stats(ctx->stream, lens_stats, st, [&] {
             check_view_sizes(views, n_views, who_view);
             if (lens) check_lenses(lens, n_views, who);
             std::vector<ViewParams> hv;
@@ -181,10 +184,10 @@ mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views
                     }
                     st.staging_bytes = std::max<uint64_t>(st.staging_bytes, sum);
                     lens_run(ctx, T, who, st);
-                });
+                }, accept_png ? &pst : nullptr);
             MVS_HIP(hipStreamSynchronize(ctx->stream));
             view_input_commit(ctx, hv, n_views);
-        }); });
+        }); }); });
     });
 }
 

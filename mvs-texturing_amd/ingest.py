@@ -10,6 +10,8 @@
   * image decode stays on the host (PIL), exactly as in the reference it is outside the timed window.
     With `device_jpeg` (CLI --device-jpeg) the views that are baseline JPEG files without distortion coefficients are decoded
     on the GPU instead (viewsel.Context.set_views_jpeg; DESIGN.md section 4 "View input"): the same pixels, bit for bit.
+    With `device_png` (CLI --device-png) the views that are 8-bit, non-interlaced PNG files are inflated and unfiltered on the GPU
+    (viewsel.Context.set_views_files): the same pixels, bit for bit.  With both flags one set_views_files call takes all files.
 
 Lens undistortion (generate_texture_views.cpp:153-165, MVE image_undistort_k2k4 / _vsfm; row f4) runs on the GPU
 (mvs_undistort_image) when a `.cam` carries a non-zero first distortion coefficient.  With `device_undistort` (CLI
@@ -22,7 +24,7 @@ View masks: with `masks` (CLI --masks) a file `<name>.mask.png` beside `<name>.c
 
 This is harness code (plumbing around the C ABI); the compute runs in libmvs_viewsel.so.
 
-CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-undistort] [--masks]
+CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-png] [--device-undistort] [--masks]
 """
 import os
 import struct
@@ -245,12 +247,15 @@ def _note_restated_models(img_path, cam):
           % (os.path.basename(img_path), "k2k4" if cam.dist[1] != 0.0 else "VisualSFM"), file=sys.stderr)
 
 
-def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False, masks=False):
+def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False, masks=False, keep_png=False):
     """A synth.Scene-like object from a folder of .cam + image pairs (and optionally a PLY mesh, prepared as
     texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given).
     keep_jpeg: a view without distortion coefficients whose file is a baseline JPEG in the format the device route accepts
     (viewsel.jpeg_probe) is not decoded: its bytes go to s.jpeg_files[j] and s.images[j] is None, for Context.set_views_jpeg.  Every
     other view is decoded here as without the flag, and its s.jpeg_files[j] is None.
+    keep_png: the same for a view whose file is a PNG in the format the device route accepts (viewsel.png_probe): its bytes go to
+    s.png_files[j], for Context.set_views_files; with distortion coefficients it stays a file only together with device_undistort.
+    s.view_files[j] is the view's file of either kind, or None.
     device_undistort: a view with dist[0] != 0 is not undistorted here; s.lens[j] = (flen, dist0, dist1) carries its coefficients for
     Context.set_views(lens=) / set_views_jpeg(lens=), and with keep_jpeg such a view stays a file when jpeg_probe accepts it.  The rows of
     views without distortion are (flen, 0, 0).  Without the flag s.lens is None.
@@ -262,6 +267,7 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
     from .synth import Scene
     s = Scene()
     s.jpeg_files = []
+    s.png_files = []
     s.masks = [] if masks else None
 
     def take_mask(cam_path, cam, w, h, distorted):
@@ -278,23 +284,28 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
         cam = read_cam_file(cam_path)
         distorted = cam.dist[0] != 0.0
         lens.append((cam.flen, cam.dist[0], cam.dist[1]) if distorted and device_undistort else (cam.flen, 0.0, 0.0))
-        if keep_jpeg and (not distorted or device_undistort):
-            from .viewsel import jpeg_probe
+        if (keep_jpeg or keep_png) and (not distorted or device_undistort):
+            from .viewsel import jpeg_probe, png_probe
             with open(img_path, "rb") as f:
                 data = f.read()
-            size = jpeg_probe(data) if data[:2] == b"\xff\xd8" else None
+            is_png = data[:8] == b"\x89PNG\r\n\x1a\n"
+            size = None
+            if keep_png and is_png:
+                size = png_probe(data)
+            elif keep_jpeg and data[:2] == b"\xff\xd8":
+                size = jpeg_probe(data)
             if size is not None:
                 w, h = size
                 arr = camera_arrays(cam, w, h)
                 for k in ("pos", "viewdir", "K", "w2c"):
                     cams[k].append(arr[k])
                 cams["width"].append(w); cams["height"].append(h)
-                s.images.append(None); s.jpeg_files.append(data)
+                s.images.append(None); s.jpeg_files.append(None if is_png else data); s.png_files.append(data if is_png else None)
                 take_mask(cam_path, cam, w, h, distorted)
                 if distorted:
                     _note_restated_models(img_path, cam)
                 continue
-        s.jpeg_files.append(None)
+        s.jpeg_files.append(None); s.png_files.append(None)
         img = load_image_rgb8(img_path)
         if distorted:   # generate_texture_views.cpp:153-165: k2k4 when both coefficients are set, else the VisualSFM model
             _note_restated_models(img_path, cam)
@@ -309,6 +320,7 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
         s.images.append(img)
         take_mask(cam_path, cam, w, h, distorted)
     n = len(s.images)
+    s.view_files = [j if j is not None else p for j, p in zip(s.jpeg_files, s.png_files)]
     s.lens = np.array(lens, np.float32).reshape(n, 3) if device_undistort else None
     s.cams = {"pos": np.array(cams["pos"], np.float32).reshape(n, 3), "viewdir": np.array(cams["viewdir"], np.float32).reshape(n, 3),
               "K": np.array(cams["K"], np.float32).reshape(n, 9), "w2c": np.array(cams["w2c"], np.float32).reshape(n, 16),
@@ -341,21 +353,25 @@ def save_scene_folder(scene, scene_dir, mesh_path=None):
         write_ply(mesh_path, scene.verts, scene.faces)
 
 
-def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False, masks=False):
+def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False, masks=False, device_png=False):
     """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec.
     device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)
+    device_png: the views that are 8-bit PNG files are decoded on the device (load_scene's keep_png, Context.set_views_files); together
+    with device_jpeg one set_views_files call takes the files of both kinds
     device_undistort: the views with distortion coefficients are undistorted on the device on their way in (load_scene's
-    device_undistort, the `lens` of Context.set_views / set_views_jpeg)
+    device_undistort, the `lens` of Context.set_views / set_views_jpeg / set_views_files)
     masks: every view's NAME.mask.png, where there is one, leaves its zero pixels out of the view (load_scene's masks, Context.set_view_masks)"""
     from . import viewsel as V
-    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort, masks=masks)
+    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort, masks=masks, keep_png=device_png)
     st = V.Settings()
     st.data_term = {"area": 0, "gmi": 1}[data_term]
     st.outlier_removal = {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier_removal]
     ctx = V.Context()
     try:
         ctx.set_mesh(s.verts, s.faces, s.normals)
-        if device_jpeg:
+        if device_png:
+            ctx.set_views_files(s.cams, s.view_files, images=s.images, lens=s.lens, masks=s.masks)
+        elif device_jpeg:
             ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images, lens=s.lens, masks=s.masks)
         else:
             ctx.set_views(s.cams, s.images, lens=s.lens, masks=s.masks)
@@ -377,8 +393,9 @@ if __name__ == "__main__":
     ap.add_argument("--data-term", default="gmi", choices=["gmi", "area"])
     ap.add_argument("--outlier-removal", default="none", choices=["none", "gauss_damping", "gauss_clamping"])
     ap.add_argument("--device-jpeg", action="store_true", help="decode baseline JPEG views on the device")
+    ap.add_argument("--device-png", action="store_true", help="inflate and unfilter 8-bit PNG views on the device")
     ap.add_argument("--device-undistort", action="store_true", help="undistort the views with distortion coefficients on the device, on their way in")
     ap.add_argument("--masks", action="store_true", help="NAME.mask.png beside NAME.cam leaves its zero pixels out of that view")
     a = ap.parse_args()
-    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort, masks=a.masks)
+    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort, masks=a.masks, device_png=a.device_png)
     print("data costs: nnz=%d  labeling: energy=%.3f sweeps=%d unseen=%d" % (d["nnz"], m["energy"], m["sweeps"], m["unseen"]))

@@ -228,6 +228,22 @@ class JpegDecStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in JPEGDEC_COUNTS] + [(k, C.c_float) for k in JPEGDEC_MS]
 
 
+PNGDEC_COUNTS = ("files", "file_bytes", "idat_chunks", "zlib_bytes", "raw_bytes", "stored_blocks", "fixed_blocks", "dynamic_blocks")
+PNGDEC_MS = ("ms_upload", "ms_inflate", "ms_adler", "ms_unfilter")
+PNGDEC_UNFILTER_BAND = 64      # rows of one band of png_unfilter_kernel (csrc/png_dec.h UNFILTER_BAND)
+PNGDEC_UNFILTER_SEGMENT = 64   # pixels of a row it stages in LDS at a time (UNFILTER_SEGMENT)
+
+
+class PngDecStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in PNGDEC_COUNTS] + [("filter_rows", C.c_uint64 * 5), ("batches", C.c_uint64)] + [(k, C.c_float) for k in PNGDEC_MS]
+
+
+def _png_stats_dict(s):
+    d = _stats_dict(s)
+    d["filter_rows"] = list(s.filter_rows)
+    return d
+
+
 LENS_COUNTS = ("views_undistorted", "views_copied", "pixels", "pixels_no_source", "staging_bytes", "batches")
 LENS_MS = ("ms_upload", "ms_undistort")
 
@@ -388,6 +404,10 @@ def load_library():
         "mvs_scene_set_views_jpeg": [vp, C.POINTER(CView), u32, vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats)],
         "mvs_jpeg_probe": [vp, u64, C.POINTER(u32), C.POINTER(u32)],
         "mvs_decode_jpeg": [vp, u64, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(u64)],
+        "mvs_ctx_decode_pngs": [vp, vp, vp, u32, C.POINTER(JpegDecParams), i32, C.POINTER(RgbSet), C.POINTER(PngDecStats)],
+        "mvs_png_probe": [vp, u64, C.POINTER(u32), C.POINTER(u32)],
+        "mvs_decode_png": [vp, u64, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32), C.POINTER(vp)],
+        "mvs_scene_set_views_files": [vp, C.POINTER(CView), u32, C.POINTER(Lens), vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats), C.POINTER(PngDecStats), C.POINTER(LensStats)],
         "mvs_scene_set_views_lens": [vp, C.POINTER(CView), u32, C.POINTER(Lens), vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats), C.POINTER(LensStats)],
         "mvs_ctx_undistort_images": [vp, vp, vp, vp, C.POINTER(Lens), u32, i32, C.POINTER(RgbSet), C.POINTER(LensStats)],
         "mvs_undistort_image_host": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
@@ -806,6 +826,38 @@ class Context:
         stats = _stats_dict(st)
         _check_with_stats(self.L, rc, stats)
         return self._rgb_set_images(res, n, None, on_device), stats
+
+    def decode_pngs(self, files, params=None, on_device=False):
+        """mvs_ctx_decode_pngs: the PNG view input route on its own -- `files` (a list of bytes: 8-bit PNGs, not interlaced) inflated and
+        unfiltered on the device in one call.  Returns (images, stats) as decode_jpegs does (params: default_jpegdec_params, for its
+        max_scratch_bytes).  The same bytes as the host twin decode_png gives; a refusal raises MvsError with the stats as `.stats`."""
+        n = len(files)
+        held, ptrs, sizes = self._file_arrays(files)
+        res, st = RgbSet(), PngDecStats()
+        rc = self.L.mvs_ctx_decode_pngs(self.h, ptrs, sizes, n, C.byref(params) if params is not None else None, 1 if on_device else 0, C.byref(res), C.byref(st))
+        stats = _png_stats_dict(st)
+        _check_with_stats(self.L, rc, stats)
+        return self._rgb_set_images(res, n, None, on_device), stats
+
+    def set_views_files(self, cams, files, params=None, images=None, lens=None, masks=None):
+        """mvs_scene_set_views_files: set_views_jpeg whose files may also be PNGs -- a file that starts with the PNG signature is inflated and
+        unfiltered on the device, any other file takes the JPEG route, an entry None brings its pixels as images[j].  lens and masks as
+        set_views_jpeg.  Returns {"png": ..., "jpeg": ..., "lens": ...}, the three routes' stats; a refusal raises MvsError with them as
+        `.stats` and leaves the context without views."""
+        V = len(files)
+        arr = self._view_array(cams, V)
+        held, ptrs, sizes = self._file_arrays(files)
+        pixels = self._pixel_views(arr, files, images)   # (held during the call)
+        jst, pst, ls = JpegDecStats(), PngDecStats(), LensStats()
+        any_file = any(f is not None for f in files)
+        rc = self.L.mvs_scene_set_views_files(self.h, arr, V, _lens_array(lens, V) if lens is not None else None, ptrs if any_file else None, sizes if any_file else None,
+                                              C.byref(params) if params is not None else None, C.byref(jst), C.byref(pst), C.byref(ls))
+        stats = {"png": _png_stats_dict(pst), "jpeg": _stats_dict(jst), "lens": _stats_dict(ls)}
+        self._views_set(V, cams, rc)
+        _check_with_stats(self.L, rc, stats)
+        if masks is not None:
+            self.set_view_masks(masks, lens=lens)
+        return stats
 
     def set_face_range(self, begin, end):
         """positions [begin, end) of the library's face order (the caller's ids with option face_order = 0)"""
@@ -1508,6 +1560,33 @@ def decode_jpeg(data, coefficients=False):
     c = np.frombuffer(C.string_at(co, 128 * nb.value), np.int16).reshape(-1, 64).copy()
     C.CDLL(None).free(co)
     return img, c
+
+
+def png_probe(data):
+    """mvs_png_probe: (width, height) when the chunks of the file `data` (bytes) are a PNG in the format the device route accepts (8 bit,
+    colour type 0, 2, 3, 4 or 6, not interlaced), else None"""
+    L = load_library()
+    data = bytes(data)
+    w, h = C.c_uint32(), C.c_uint32()
+    return (w.value, h.value) if L.mvs_png_probe(data, len(data), C.byref(w), C.byref(h)) == 0 else None
+
+
+def decode_png(data, raw=False):
+    """mvs_decode_png: the (H, W, 3) uint8 image of a PNG file (bytes) by the host twin of the PNG view input route -- no GPU, no library;
+    the same bytes as Context.decode_pngs gives and as Pillow's convert("RGB").  raw=True: (image, bytes), the inflated, still filtered
+    stream of H * (1 + W * bytes per pixel) bytes."""
+    L = load_library()
+    data = bytes(data)
+    out, w, h, rw = C.c_void_p(), C.c_uint32(), C.c_uint32(), C.c_void_p()
+    _check(L, L.mvs_decode_png(data, len(data), C.byref(out), C.byref(w), C.byref(h), C.byref(rw) if raw else None))
+    img = np.frombuffer(C.string_at(out, 3 * w.value * h.value), np.uint8).reshape(h.value, w.value, 3).copy()
+    L.mvs_png_free(out)
+    if not raw:
+        return img
+    bpp = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[data[25]]
+    stream = C.string_at(rw, h.value * (1 + w.value * bpp))
+    L.mvs_png_free(rw)
+    return img, stream
 
 
 def deflate_rle(data):
