@@ -1,4 +1,4 @@
-// call_barrier.h -- the rendezvous of the in-process communicator's ranks (shard.hip LocalHub), free of any device code so that its
+// call_barrier.h -- the rendezvous of the in-process communicator's ranks (comm.hip LocalHub), free of any device code so that its
 // failure semantics are unit-tested on the CPU (tests/cpp/test_call_barrier.cpp, tests/test_host.py).
 //
 // Every sharded entry point is a CALL that all ranks make in the same order; a rank numbers its calls 1, 2, ... (begin).  A call is

@@ -20,7 +20,7 @@ typedef uint8_t msg_t;
 constexpr uint32_t N_SUB = 320;            // sub-classes 0 .. 319 (64 colours x 4 fast classes, 64 generic colour classes)
 constexpr uint32_t SUB_GENERIC = 256;
 // Every sub-class has two ZONES (sort key = 2 * sub-class + zone): zone 0 = the nodes a sharded caller marked as its BOUNDARY nodes
-// (own nodes with an edge into another rank's part: ctx->m_bnd, shard.hip), zone 1 = everybody else.  A sharded rank sweeps the
+// (own nodes with an edge into another rank's part: ctx->m_bnd, shard.hip setup_with_marks), zone 1 = everybody else.  A sharded rank sweeps the
 // boundary zone of a colour first, hands its runs to the neighbours, and sweeps the interior while they travel; a colour class is an
 // independent set, so the split changes no value.  Without marks (single context, building blocks) zone 0 is empty and the order is
 // the plain (colour, class, id) order.

@@ -1,6 +1,6 @@
 // solve.hip -- the solver's host loop on one context (mvs_ctx_view_selection): sweeps with the device-side stop rule, replayed from a
 // hipGraph after the first damping period, exact costs, ICM polish, region moves, labels; and the solver's diagnostics.  (The sharded
-// loop is shard.hip: it differs in transport, lag and graph use.)
+// loop is shard.hip sweep_loop: it differs in transport, lag and graph use.)
 #include "ctx.h"
 
 #include <algorithm>

@@ -1,8 +1,8 @@
 // fake_rccl.hip -- TEST DOUBLE for librccl.so (not part of the product; built into tests/tools/librccl_fake.so).
 //
-// A 1-GPU test box cannot host two RCCL ranks, so the RCCL communicator of csrc/shard.hip (RcclComm: ncclCommInitRank, grouped ncclSend /
+// A 1-GPU test box cannot host two RCCL ranks, so the RCCL communicator of csrc/comm.hip (RcclComm: ncclCommInitRank, grouped ncclSend /
 // ncclRecv per colour phase, ncclAllReduce / ncclAllGather) would only ever run at world size 1, where its peer loops are empty.  The
-// product resolves RCCL BY NAME at run time (dlopen + dlsym, shard.hip rccl()); with MVS_RCCL_LIB=<this library> it binds the ten entry
+// product resolves RCCL BY NAME at run time (dlopen + dlsym, comm.hip rccl()); with MVS_RCCL_LIB=<this library> it binds the ten entry
 // points below instead: the ranks are host THREADS of one process sharing the device, matching of sends and receives, group semantics and
 // stream ordering follow NCCL's contract, the wire is hipMemcpyAsync:
 //
