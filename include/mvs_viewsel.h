@@ -916,6 +916,43 @@ typedef struct mvs_mask_stats {
 } mvs_mask_stats;
 mvs_status mvs_scene_set_view_masks(mvs_ctx* ctx, const uint8_t* const* masks, uint32_t n_views, int on_device, const mvs_lens* lens, mvs_mask_stats* stats);
 
+/* View input: pyramid levels -- views halved on the device on their way in (DESIGN.md section 4 "View input" item 14; csrc/level.h states
+ * the arithmetic once for csrc/k_level.hip and the host twin).  What `scene::undist-L<k>` is to texrecon: the photograph crosses the bus
+ * once, as the file or as its pixels, is decoded, undistorted in the frame the camera took and halved `level` times on the device, and
+ * only the level image stays resident.  half(I) of a w x h image is (w + 1) / 2 x (h + 1) / 2 with
+ *   half(I)(x, y, c) = (I(2x, y0, c) + I(x1, y0, c) + I(2x, y1, c) + I(x1, y1, c) + 2) >> 2,  x1 = min(2x + 1, w - 1), y1 = min(2y + 1, h - 1), y0 = 2y,
+ * a box filter (DEFINED HERE from recollection of MVE's rescale_half_size<uint8_t>); level k is half applied k times, the bytes rounded
+ * at every level.  Pixels without a source under a lens are black before they are averaged.
+ * mvs_view_level: view j's level, 0 .. 4, and the size of its source.  views[j] (width, height, K) describes the view AT ITS LEVEL, which
+ *   is what the kernels read; files[j] or views[j].rgb bring src_width x src_height pixels.  Level 0: the view is taken as it is.
+ * mvs_scene_set_views_levels: mvs_scene_set_views_files with levels -- the same begin / commit rule, the same batches, PNG accepted.  A view
+ *   with level > 0 is a staged view exactly as one with dist0 != 0: its 3 * src_width * src_height bytes count towards its scratch in the
+ *   batch cut of the files, pixel views are staged in groups of at most max_scratch_bytes, and a view that does not fit alone is refused.
+ *   A view with a lens and a level needs no second buffer: the kernel's source fetch is the lens'.  lens_stats->pixels_no_source counts
+ *   full-size pixels.  Refusals (MVS_ERR_INVALID, with the view and the reason; the context is left without views): level > 4,
+ *   reserved != 0, a source whose level size is not views[j]'s, a file whose frame is not src_width x src_height, a level image below
+ *   2 x 2, and everything the file and lens entries refuse.
+ *   Masks: mvs_scene_set_view_masks keeps its signature.  The context remembers every view's level and source size from this entry (every
+ *   other view input resets them to level 0); the mask of a view with level > 0 has the SOURCE's size, and the level's keep bit is the AND
+ *   of the source keep bits (after the lens, where there is one) over the clamped 2^k x 2^k block: a level pixel is kept iff everything
+ *   that went into it is kept.  The full-size keep words of such a view (1 / 8 of its mask bytes) live in a scratch buffer per batch.
+ * mvs_ctx_halve_images: the route on its own, shaped as mvs_ctx_undistort_images (lens may be null; level 0 copies or undistorts only).
+ * mvs_halve_image_host / mvs_level_size: the host twin (out: exactly the level image's bytes) and the size of a level.  No GPU. */
+typedef struct mvs_view_level { uint32_t level; int32_t src_width, src_height; uint32_t reserved; } mvs_view_level;
+typedef struct mvs_level_stats {
+    uint64_t views_halved, pixels_in, pixels_out;   /* views with level > 0; their source pixels and their level pixels */
+    uint64_t pixels_no_source;                      /* of the halved views under a lens: full-size pixels left black (mvs_ctx_halve_images: of all images) */
+    uint64_t batches, staging_bytes;                /* launches of the level kernel; the most bytes staged at one time, by the lens and the level route together */
+    float ms_upload, ms_halve;                      /* host time of the pixel uploads into staging (both routes); device time of the level launches */
+} mvs_level_stats;
+mvs_status mvs_scene_set_views_levels(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_view_level* levels, const mvs_lens* lens, const uint8_t* const* files,
+                                      const uint64_t* sizes, const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, mvs_pngdec_stats* png_stats,
+                                      mvs_level_stats* level_stats);
+mvs_status mvs_ctx_halve_images(mvs_ctx* ctx, const uint8_t* const* images, const uint32_t* widths, const uint32_t* heights, const uint32_t* levels, const mvs_lens* lens, uint32_t n,
+                                int out_on_device, mvs_rgb_set* out_set, mvs_level_stats* stats);
+mvs_status mvs_halve_image_host(const uint8_t* rgb, int32_t width, int32_t height, uint32_t level, uint8_t* out);
+mvs_status mvs_level_size(int32_t width, int32_t height, uint32_t level, int32_t* level_width, int32_t* level_height);
+
 /* Row f10: the view-selection debug model, `texrecon --view_selection_model` (texrecon.cpp:216-236, generate_debug_embeddings.cpp):
  * every view's image is replaced by a flat colour of its own -- colour (position % 144) of an HSV sweep, position = the view's place in
  * the view list -- stamped all over with its three-digit id in cells of 13 x 6 pixels, and rows f6 (without adjust_colors), f8 and f9

@@ -20,4 +20,4 @@ from .viewsel import (Context, Settings, MrfParams, MvsError, calculate_data_cos
                       global_seam_leveling, default_gsl_params, texture_patches, default_patch_params, patch_view,
                       local_seam_leveling, default_lsl_params, texture_atlases, default_atlas_params, atlas_view,
                       texture_model, default_model_params, vertex_normals, write_png, encode_png_rle, encode_jpeg, deflate_rle, decode_jpeg, jpeg_probe, default_jpegdec_params, decode_png, png_probe,
-                      view_selection_model, debug_view_style, gamma_correct, tone_table, undistort_host)
+                      view_selection_model, debug_view_style, gamma_correct, tone_table, undistort_host, halve_host, halve_mask_host, level_size)

@@ -7,7 +7,7 @@
                                                   mrf.h (what the MRF solver's k_mrf_setup / k_mrf_sweep / k_mrf_polish.hip share) and
                                                   sort_scan.h (the rocprim two-call idiom), comm.h / shard.h (the communicator interface / what the sharded driver's sources share), rows.h / image_routes.h / view_input.h (the host plumbing of rows f5 - f11 / of the PNG and JPEG routes / of the view inputs) and model_corner.h (a face-list corner as k_model.hip and k_glb.hip read it) are internal headers;
                                                   stash.h / spt_io.h / dc_ranges.h / view_batches.h / shard_lists.h / call_barrier.h / png_io.h are plain host headers, fmt6.h,
-                                                  png_rle.h, jpeg_base.h, jpeg_dec.h (the view input route of k_jpegdec.hip), png_dec.h (that of k_pngdec.hip: container, inflate, filters and the host twin), lens.h (row f4's arithmetic: k_prep.hip, k_lens.hip and the host twin); k_viewmask.hip packs the view masks into keep words for k_prep.hip, dc_counters.h, debug_embed.h and tone.h host-and-device ones, that tests/cpp compiles on their own)
+                                                  png_rle.h, jpeg_base.h, jpeg_dec.h (the view input route of k_jpegdec.hip), png_dec.h (that of k_pngdec.hip: container, inflate, filters and the host twin), lens.h (row f4's arithmetic: k_prep.hip, k_lens.hip and the host twin), level.h (the pyramid levels of the view input: k_level.hip and the host twin); k_viewmask.hip packs the view masks into keep words for k_prep.hip, dc_counters.h, debug_embed.h and tone.h host-and-device ones, that tests/cpp compiles on their own)
   csrc/mgpu.hip       -> csrc/libmvs_blocks.so    (building blocks of include/mvs_viewsel_blocks.h: the test harness's library, links the product)
   csrc/scene_synth.cpp-> csrc/libmvs_synth.so     (g++; synthetic input producer)
   csrc/dmath_host.cpp -> csrc/libmvs_dmath_host.so(g++; CPU build of dmath.h for the arithmetic unit test)
@@ -22,7 +22,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-HIP_SOURCES = ["scan.hip", "k_prep.hip", "k_bvh.hip", "k_kdorder.hip", "k_dc.hip", "k_mrf_setup.hip", "k_mrf_sweep.hip", "k_mrf_polish.hip", "readback.hip", "k_region.hip", "k_mesh.hip", "k_patch.hip", "k_seam.hip", "k_texpatch.hip", "k_localseam.hip", "k_atlas.hip", "k_model.hip", "k_glb.hip", "k_png.hip", "k_jpeg.hip", "k_jpegdec.hip", "k_pngdec.hip", "k_lens.hip", "k_viewmask.hip", "k_debug.hip", "k_tone.hip", "k_order.hip", "comm.hip", "shard_plan.hip", "shard_table.hip", "shard_transport.hip", "shard.hip", "api.hip", "solve.hip", "oneshot.hip"]
+HIP_SOURCES = ["scan.hip", "k_prep.hip", "k_bvh.hip", "k_kdorder.hip", "k_dc.hip", "k_mrf_setup.hip", "k_mrf_sweep.hip", "k_mrf_polish.hip", "readback.hip", "k_region.hip", "k_mesh.hip", "k_patch.hip", "k_seam.hip", "k_texpatch.hip", "k_localseam.hip", "k_atlas.hip", "k_model.hip", "k_glb.hip", "k_png.hip", "k_jpeg.hip", "k_jpegdec.hip", "k_pngdec.hip", "k_lens.hip", "k_level.hip", "k_viewmask.hip", "k_debug.hip", "k_tone.hip", "k_order.hip", "comm.hip", "shard_plan.hip", "shard_table.hip", "shard_transport.hip", "shard.hip", "api.hip", "solve.hip", "oneshot.hip"]
 BLOCKS_SOURCES = ["mgpu.hip"]                       # NOT in the product library
 BLOCKS_LIB = os.path.join(CSRC, "libmvs_blocks.so")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
@@ -47,7 +47,7 @@ def _hipcc():
 
 
 def build_hip(force=False, verbose=False):
-    headers = [os.path.join(CSRC, h) for h in ("ctx.h", "rows.h", "image_routes.h", "view_input.h", "view_batches.h", "sort_scan.h", "mrf.h", "comm.h", "shard.h", "shard_lists.h", "dmath.h", "call_barrier.h", "dc_ranges.h", "dc_counters.h", "stash.h", "spt_io.h", "fmt6.h", "png_io.h", "png_rle.h", "jpeg_base.h", "jpeg_dec.h", "png_dec.h", "lens.h", "debug_embed.h", "tone.h", "model_corner.h")] + [os.path.join(HERE, "..", "include", h) for h in ("mvs_viewsel.h", "mvs_viewsel_blocks.h")]
+    headers = [os.path.join(CSRC, h) for h in ("ctx.h", "rows.h", "image_routes.h", "view_input.h", "view_batches.h", "sort_scan.h", "mrf.h", "comm.h", "shard.h", "shard_lists.h", "dmath.h", "call_barrier.h", "dc_ranges.h", "dc_counters.h", "stash.h", "spt_io.h", "fmt6.h", "png_io.h", "png_rle.h", "jpeg_base.h", "jpeg_dec.h", "png_dec.h", "lens.h", "level.h", "debug_embed.h", "tone.h", "model_corner.h")] + [os.path.join(HERE, "..", "include", h) for h in ("mvs_viewsel.h", "mvs_viewsel_blocks.h")]
     objs, bobjs, jobs = [], [], []
     for src in HIP_SOURCES + BLOCKS_SOURCES:
         s = os.path.join(CSRC, src)

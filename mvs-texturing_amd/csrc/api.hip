@@ -235,7 +235,7 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto* b : ctx->own_rgb) delete b;
-    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx); mvs::pngdec_release(ctx); mvs::lens_release(ctx); mvs::viewmask_release(ctx);
+    mvs::gsl_release(ctx); mvs::texpatch_release(ctx); mvs::lsl_release(ctx); mvs::atlas_release(ctx); mvs::model_release(ctx); mvs::debug_release(ctx); mvs::glb_release(ctx); mvs::png_release(ctx); mvs::jpeg_release(ctx); mvs::jpegdec_release(ctx); mvs::pngdec_release(ctx); mvs::lens_release(ctx); mvs::level_release(ctx); mvs::viewmask_release(ctx);
     mvs::sweep_graph_release(ctx);
     if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);

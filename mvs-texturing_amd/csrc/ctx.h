@@ -147,6 +147,7 @@ struct JpegDev;  // rows f9 / f11: JPEG images (k_jpeg.hip)
 struct JpegDecDev;   // view input: JPEG files decoded on the device (k_jpegdec.hip)
 struct LensDev;      // view input: lens undistortion on the device (k_lens.hip)
 struct PngDecDev;    // view input: PNG files inflated and unfiltered on the device (k_pngdec.hip)
+struct LevelDev;     // view input: the tables and the output of the level route (k_level.hip)
 struct ViewMaskDev;  // view input: the keep words of the views that carry a mask (k_viewmask.hip)
 
 // The tables of generate_texture_patches both rows build (DESIGN.md section 4 "Global seam leveling" items 3-4; k_texpatch.hip
@@ -286,6 +287,7 @@ struct mvs_ctx {
     mvs::LensDev* lens = nullptr;     // view input: the per-view tables and the output of the lens route (k_lens.hip)
     mvs::ViewMaskDev* viewmask = nullptr; uint64_t view_scratch_cap = mvs::VIEW_SCRATCH_DEFAULT;   // view masks (k_viewmask.hip): the keep words; max_scratch_bytes of the last view input (mask staging is cut by it)
     mvs::DBuf<uint8_t> view_staging;  // view input: the staging buffer of all routes (view_input.h view_staging)
+    mvs::LevelDev* level = nullptr; std::vector<mvs_view_level> view_levels;   // view input: pyramid levels (k_level.hip); every view's level and source size as the last view input left them (empty: all at level 0)
     mvs::DBuf<float> tone_table; bool tone_table_valid = false;   // the 256 texel values tone mapping `gamma` reads (k_tone.hip tone_table_dev), uploaded on first use
 
     // ---- region moves (k_region.hip) ----
@@ -481,7 +483,22 @@ void decode_view_pngs(mvs_ctx* ctx, const mvs_view* views, const FileViews& fv, 
 // k_lens.hip: the body of mvs_scene_set_views_jpeg (lens == null), mvs_scene_set_views_lens and mvs_scene_set_views_files (accept_png) behind their argument checks
 mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
                            const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who,
-                           bool accept_png = false, mvs_pngdec_stats* png_stats = nullptr);
+                           bool accept_png = false, mvs_pngdec_stats* png_stats = nullptr, const mvs_view_level* levels = nullptr, mvs_level_stats* level_stats = nullptr);
+// k_level.hip (DESIGN.md section 4 "View input" item 14): ONE span launch halves the images of T `level` times (1 .. 4) from the staging
+// into dst; d0 != 0: the source fetch is lens.h lens_pixel, and the pixels without a source are counted into lens_st as lens_kernel counts
+// them (full-size pixels).  Returns with the stream drained.  keep_level_run: full-size keep words (`src`, the layout of the validity
+// mask) -> the level's keep words, one launch.  check_levels: the refusals of an mvs_view_level list against the views at their level.
+struct LevelItem { const uint8_t* src; uint8_t* dst; int32_t width, height; uint32_t level; float flen, d0, d1; };
+struct KeepLevelItem { const uint32_t* src; uint32_t* keep; int32_t width, height; uint32_t level, pad_; };
+void level_run(mvs_ctx* ctx, const std::vector<LevelItem>& T, const char* who, mvs_level_stats& st, mvs_lens_stats& lens_st);
+void keep_level_run(mvs_ctx* ctx, const std::vector<KeepLevelItem>& T, float& ms);
+void check_levels(const mvs_view* views, const mvs_view_level* levels, uint32_t n, const char* who);
+void level_release(mvs_ctx* ctx);
+// k_lens.hip: host images through staging in groups of at most `cap` bytes: image k (src[k], w[k] x h[k], lens[k], level[k]) -> dst[k]; `view`
+// names image k in a refusal.  Level 0: lens_kernel (dist0 == 0 copies), above: level_run.  level_st may be null where every level is 0.
+void stage_pixels(mvs_ctx* ctx, const std::vector<const uint8_t*>& src, const std::vector<uint8_t*>& dst, const std::vector<uint32_t>& w, const std::vector<uint32_t>& h,
+                  const std::vector<mvs_lens>& lens, const std::vector<uint32_t>& level, const std::vector<uint32_t>& view, uint64_t cap, const char* who, mvs_lens_stats& st,
+                  mvs_level_stats* level_st);
 // k_tone.hip: the mode of a parameter struct checked (throws MVS_ERR_INVALID, `who` in front, for anything but none / gamma); the device
 // table of the context for tone mapping `gamma` -- built from tone.h and uploaded on first use, or what tone_table_set put there
 // (256 host floats; null: the gamma table again; the harness entry mvs_ctx_tone_table)

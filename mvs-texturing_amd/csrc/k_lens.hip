@@ -125,18 +125,27 @@ void lens_run(mvs_ctx* ctx, const std::vector<LensView>& T, const char* who, mvs
     st.pixels_no_source += none; st.batches += 1;
 }
 
-// Host images through staging in groups of at most `cap` bytes: image k (src[k], w[k] x h[k], lens[k]) -> dst[k].  `view` names image k in
-// a refusal.  An image with dist0 == 0 is copied by the same launch (mvs_ctx_undistort_images; mvs_scene_set_views_lens sends none).
+}  // namespace
+
+// host images through staging in groups (ctx.h): level 0 by lens_kernel (an image with dist0 == 0 is copied by the same launch:
+// mvs_ctx_undistort_images and mvs_ctx_halve_images; the view entries send none), a level above by level_run of k_level.hip
 void stage_pixels(mvs_ctx* ctx, const std::vector<const uint8_t*>& src, const std::vector<uint8_t*>& dst, const std::vector<uint32_t>& w, const std::vector<uint32_t>& h,
-                  const std::vector<mvs_lens>& lens, const std::vector<uint32_t>& view, uint64_t cap, const char* who, mvs_lens_stats& st) {
+                  const std::vector<mvs_lens>& lens, const std::vector<uint32_t>& level, const std::vector<uint32_t>& view, uint64_t cap, const char* who, mvs_lens_stats& st,
+                  mvs_level_stats* level_st) {
     std::vector<uint64_t> bytes(src.size());
     for (size_t k = 0; k < src.size(); ++k) bytes[k] = 3ull * w[k] * h[k];
     stage_in_groups(ctx, src, bytes, view, cap, who, st.ms_upload, st.staging_bytes, [&](size_t first, size_t last, const std::vector<uint8_t*>& at) {
-        std::vector<LensView> T;
-        for (size_t k = first; k < last; ++k) T.push_back(LensView{at[k - first], dst[k], (int32_t)w[k], (int32_t)h[k], lens[k].flen, lens[k].dist0, lens[k].dist1, 0u});
+        std::vector<LensView> T; std::vector<LevelItem> U;
+        for (size_t k = first; k < last; ++k) {
+            if (level[k]) U.push_back(LevelItem{at[k - first], dst[k], (int32_t)w[k], (int32_t)h[k], level[k], lens[k].flen, lens[k].dist0, lens[k].dist1});
+            else T.push_back(LensView{at[k - first], dst[k], (int32_t)w[k], (int32_t)h[k], lens[k].flen, lens[k].dist0, lens[k].dist1, 0u});
+        }
         lens_run(ctx, T, who, st);
+        if (!U.empty()) level_run(ctx, U, who, *level_st, st);
     });
 }
+
+namespace {
 
 }  // namespace
 
@@ -145,10 +154,11 @@ void stage_pixels(mvs_ctx* ctx, const std::vector<const uint8_t*>& src, const st
 // and source ("" for the JPEG entry), `who` all others
 mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views, const mvs_lens* lens, const uint8_t* const* files, const uint64_t* sizes,
                            const mvs_jpegdec_params* jpeg_params, mvs_jpegdec_stats* jpeg_stats, mvs_lens_stats* lens_stats, const char* who_view, const char* who,
-                           bool accept_png, mvs_pngdec_stats* png_stats) {
+                           bool accept_png, mvs_pngdec_stats* png_stats, const mvs_view_level* levels, mvs_level_stats* level_stats) {
     for (uint32_t j = 0; j < n_views; ++j)
         if (!(files && files[j]) && !views[j].rgb) return api_fail(MVS_ERR_INVALID, view_msg(who_view, j) + "neither a file nor pixels");
-    mvs_jpegdec_stats jst{}; mvs_lens_stats st{}; mvs_pngdec_stats pst{};
+    mvs_jpegdec_stats jst{}; mvs_lens_stats st{}; mvs_pngdec_stats pst{}; mvs_level_stats vst{};
+    if (level_stats) *level_stats = vst;
     if (jpeg_stats) *jpeg_stats = jst;
     if (lens_stats) *lens_stats = st;
     if (png_stats) *png_stats = pst;
@@ -156,38 +166,53 @@ mvs_status set_views_files(mvs_ctx* ctx, const mvs_view* views, uint32_t n_views
         MVS_HIP(hipSetDevice(ctx->device));
         const uint64_t cap = jpeg_params ? jpeg_params->max_scratch_bytes : VIEW_SCRATCH_DEFAULT;
         view_input_begin(ctx, cap);
-        run_with_stats(ctx->stream, png_stats, pst, [&] { run_with_stats(ctx->stream, jpeg_stats, jst, [&] { run_with_stats(ctx->stream, lens_stats, st, [&] {
+        run_with_stats(ctx->stream, level_stats, vst, [&] { run_with_stats(ctx->stream, png_stats, pst, [&] { run_with_stats(ctx->stream, jpeg_stats, jst, [&] { run_with_stats(ctx->stream, lens_stats, st, [&] {
+            if (levels) check_levels(views, levels, n_views, who);
             check_view_sizes(views, n_views, who_view);
             if (lens) check_lenses(lens, n_views, who);
+            // a view with a level comes at its source's size: the files' frames are checked against it, and the staging holds it
+            auto level_of = [&](uint32_t j) { return levels ? levels[j].level : 0u; };
+            std::vector<mvs_view> src_views(views, views + n_views);
+            for (uint32_t j = 0; levels && j < n_views; ++j) { src_views[j].width = levels[j].src_width; src_views[j].height = levels[j].src_height; }
+            const mvs_lens no_lens{0.0f, 0.0f, 0.0f, 0u};
             std::vector<ViewParams> hv;
             const std::vector<uint8_t*> image = own_images(ctx, views, n_views, hv);
             std::vector<uint8_t> staged(n_views, 0);
             std::vector<const uint8_t*> psrc; std::vector<uint8_t*> pdst; std::vector<size_t> pbytes;   // pixels uploaded as they are
-            std::vector<const uint8_t*> ssrc; std::vector<uint8_t*> sdst; std::vector<uint32_t> sw, sh, sview; std::vector<mvs_lens> slens;   // pixels through staging
+            std::vector<const uint8_t*> ssrc; std::vector<uint8_t*> sdst; std::vector<uint32_t> sw, sh, sview, slevel; std::vector<mvs_lens> slens;   // pixels through staging
             bool any_file = false;
             for (uint32_t j = 0; j < n_views; ++j) {
                 const mvs_view& v = views[j];
-                staged[j] = lens && lens[j].dist0 != 0.0f ? 1 : 0;
+                staged[j] = (lens && lens[j].dist0 != 0.0f) || level_of(j) ? 1 : 0;
                 if (files && files[j]) any_file = true;
-                else if (staged[j]) { ssrc.push_back(v.rgb); sdst.push_back(image[j]); sw.push_back((uint32_t)v.width); sh.push_back((uint32_t)v.height); sview.push_back(j); slens.push_back(lens[j]); }
+                else if (staged[j]) {
+                    ssrc.push_back(v.rgb); sdst.push_back(image[j]); sw.push_back((uint32_t)src_views[j].width); sh.push_back((uint32_t)src_views[j].height); sview.push_back(j);
+                    slens.push_back(lens ? lens[j] : no_lens); slevel.push_back(level_of(j));
+                }
                 else { psrc.push_back(v.rgb); pdst.push_back(image[j]); pbytes.push_back((size_t)v.width * v.height * 3); }
             }
             upload_pieces_through_ring(ctx, psrc.data(), pdst.data(), pbytes.data(), psrc.size());
-            stage_pixels(ctx, ssrc, sdst, sw, sh, slens, sview, cap, who, st);
+            stage_pixels(ctx, ssrc, sdst, sw, sh, slens, slevel, sview, cap, who, st, &vst);
             if (any_file)
-                decode_view_files(ctx, views, n_views, files, sizes, image.data(), staged.data(), jpeg_params, who, jst, [&](const std::vector<uint32_t>& bv, const std::vector<const uint8_t*>& bp) {
-                    std::vector<LensView> T; uint64_t sum = 0;
+                decode_view_files(ctx, src_views.data(), n_views, files, sizes, image.data(), staged.data(), jpeg_params, who, jst, [&](const std::vector<uint32_t>& bv, const std::vector<const uint8_t*>& bp) {
+                    std::vector<LensView> T; std::vector<LevelItem> U; uint64_t sum = 0;
                     for (size_t k = 0; k < bv.size(); ++k) {
                         const uint32_t j = bv[k];
-                        T.push_back(LensView{bp[k], image[j], views[j].width, views[j].height, lens[j].flen, lens[j].dist0, lens[j].dist1, 0u});
-                        sum += align16(3ull * views[j].width * views[j].height);
+                        const mvs_view& sv = src_views[j];
+                        const mvs_lens& L = lens ? lens[j] : no_lens;
+                        if (level_of(j)) U.push_back(LevelItem{bp[k], image[j], sv.width, sv.height, level_of(j), L.flen, L.dist0, L.dist1});
+                        else T.push_back(LensView{bp[k], image[j], sv.width, sv.height, L.flen, L.dist0, L.dist1, 0u});
+                        sum += align16(3ull * sv.width * sv.height);
                     }
                     st.staging_bytes = std::max<uint64_t>(st.staging_bytes, sum);
                     lens_run(ctx, T, who, st);
+                    level_run(ctx, U, who, vst, st);
                 }, accept_png ? &pst : nullptr);
             MVS_HIP(hipStreamSynchronize(ctx->stream));
+            vst.staging_bytes = st.staging_bytes; vst.ms_upload = st.ms_upload;
             view_input_commit(ctx, hv, n_views);
-        }); }); });
+            if (levels) ctx->view_levels.assign(levels, levels + n_views);
+        }); }); }); });
     });
 }
 
@@ -223,7 +248,7 @@ mvs_status mvs_ctx_undistort_images(mvs_ctx* ctx, const uint8_t* const* images, 
             const RgbRoom R = rgb_set_room(D.out, w, h);
             std::vector<uint32_t> view(n);
             for (uint32_t k = 0; k < n; ++k) view[k] = k;
-            stage_pixels(ctx, std::vector<const uint8_t*>(images, images + n), R.dst, w, h, std::vector<mvs_lens>(lens, lens + n), view, VIEW_SCRATCH_DEFAULT, who, st);
+            stage_pixels(ctx, std::vector<const uint8_t*>(images, images + n), R.dst, w, h, std::vector<mvs_lens>(lens, lens + n), std::vector<uint32_t>(n, 0u), view, VIEW_SCRATCH_DEFAULT, who, st, nullptr);
             rgb_set_out(ctx, D.out, R, w, h, out_on_device, out);
         });
     });

@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(THREADS) keep_count_kernel(const uint32_t* __r
 // per-context state of the masks: the keep words of the masked views back to back, the table of every view's keep pointer (null: no
 // mask) and the list of the masked views as prepare_views hands them to its kernels, and the launch tables of the pack kernel
 struct ViewMaskDev {
-    DBuf<uint32_t> keep, list; DBuf<const uint32_t*> table; DBuf<PackView> pack_table; DBuf<u64> word_ptr, counter;
+    DBuf<uint32_t> keep, list, full; DBuf<const uint32_t*> table; DBuf<PackView> pack_table; DBuf<u64> word_ptr, counter;
     uint32_t n_masked = 0;
 };
 void viewmask_release(mvs_ctx* ctx) { delete ctx->viewmask; ctx->viewmask = nullptr; }
@@ -138,32 +138,41 @@ mvs_status mvs_scene_set_view_masks(mvs_ctx* ctx, const uint8_t* const* masks, u
             if (mv.empty()) return;
             const size_t n = mv.size();
             const uint64_t cap = ctx->view_scratch_cap;
-            std::vector<uint64_t> off(n + 1, 0), bytes(n), need(n);
+            // a view with a pyramid level (k_level.hip) brings its mask at the SOURCE's size: sw x sh, level lv (0: the view's own size)
+            std::vector<uint64_t> off(n + 1, 0), bytes(n), need(n), px(n);
             std::vector<const uint8_t*> src(n);
+            std::vector<int32_t> sw(n), sh(n); std::vector<uint32_t> lv(n, 0u);
             for (size_t k = 0; k < n; ++k) {
                 const ViewParams& v = ctx->h_views[mv[k]];
                 src[k] = masks[mv[k]];
-                bytes[k] = (uint64_t)v.width * (uint64_t)v.height; need[k] = align16(bytes[k]);
+                sw[k] = v.width; sh[k] = v.height;
+                if (!ctx->view_levels.empty() && ctx->view_levels[mv[k]].level) { const mvs_view_level& L = ctx->view_levels[mv[k]]; lv[k] = L.level; sw[k] = L.src_width; sh[k] = L.src_height; }
+                bytes[k] = (uint64_t)sw[k] * (uint64_t)sh[k]; need[k] = align16(bytes[k]); px[k] = (uint64_t)v.width * (uint64_t)v.height;
                 off[k + 1] = off[k] + keep_words(v.width, v.height);
             }
             const size_t counted = on_device ? n : std::min(n, first_over_cap(need.data(), n, cap) + 1);   // (a refusal reports the pixels up to the refused view)
-            for (size_t k = 0; k < counted; ++k) st.pixels += bytes[k];
+            for (size_t k = 0; k < counted; ++k) st.pixels += px[k];
             if (!on_device) refuse_over_cap(need, cap, mv.data(), who, "staging");
             ViewMaskDev& D = row_dev(ctx->viewmask);
             D.keep.ensure((size_t)off[n] + 4); D.counter.ensure(2);
             MVS_HIP(hipMemsetAsync(D.counter.p, 0, sizeof(u64), ctx->stream));
             // items [first, last) of mv with their bytes at at[k - first]: one launch packs the masks that are used as they are, one undistorts the others
             auto batch = [&](size_t first, size_t last, const auto& at) {
-                std::vector<PackView> P; std::vector<LensMaskView> Q;
+                std::vector<PackView> P; std::vector<LensMaskView> Q; std::vector<KeepLevelItem> R;
+                uint64_t full = 0;   // the full-size keep words of the batch's views with a level: a scratch of this batch
+                for (size_t k = first; k < last; ++k) if (lv[k]) full += keep_words(sw[k], sh[k]);
+                D.full.ensure((size_t)full + 4);
+                full = 0;
                 for (size_t k = first; k < last; ++k) {
                     const uint32_t j = mv[k];
-                    const ViewParams& v = ctx->h_views[j];
                     uint32_t* keep = D.keep.p + off[k];
-                    if (lens && lens[j].dist0 != 0.0f) Q.push_back(LensMaskView{at[k - first], keep, v.width, v.height, lens[j].flen, lens[j].dist0, lens[j].dist1, 0u});
-                    else P.push_back(PackView{at[k - first], keep, v.width, v.height});
+                    if (lv[k]) { R.push_back(KeepLevelItem{D.full.p + full, keep, sw[k], sh[k], lv[k], 0u}); keep = D.full.p + full; full += keep_words(sw[k], sh[k]); }
+                    if (lens && lens[j].dist0 != 0.0f) Q.push_back(LensMaskView{at[k - first], keep, sw[k], sh[k], lens[j].flen, lens[j].dist0, lens[j].dist1, 0u});
+                    else P.push_back(PackView{at[k - first], keep, sw[k], sh[k]});
                 }
-                pack_run(ctx, D, P, st.ms_pack);                      // (both return with the stream drained: the staging is free for the next batch)
+                pack_run(ctx, D, P, st.ms_pack);                      // (all three return with the stream drained: the staging is free for the next batch)
                 lens_mask_run(ctx, Q, st.ms_undistort);
+                keep_level_run(ctx, R, st.ms_pack);
                 st.batches += 1; st.views_undistorted += Q.size();
             };
             // device masks are read where they lie, all in one batch; host masks in groups whose staged bytes fit the cap

@@ -14,7 +14,7 @@ namespace mvs {
 // staged under its cap); commit() hands over the finished views.  Nothing of the context's views is written in between.
 inline void view_input_begin(mvs_ctx* ctx, uint64_t cap) {
     ctx->n_views = 0; ctx->h_views.clear(); ctx->have_costs = false; ctx->dc_phase = 0; ctx->views_refused = true;
-    view_masks_clear(ctx); ctx->view_scratch_cap = cap;
+    view_masks_clear(ctx); ctx->view_scratch_cap = cap; ctx->view_levels.clear();
 }
 inline void view_input_commit(mvs_ctx* ctx, std::vector<ViewParams>& hv, uint32_t n_views) { ctx->h_views.swap(hv); ctx->n_views = n_views; ctx->views_refused = false; }
 

@@ -22,9 +22,15 @@ pixels, bit for bit.  Together with `device_jpeg` a distorted baseline JPEG stay
 View masks: with `masks` (CLI --masks) a file `<name>.mask.png` beside `<name>.cam` leaves its zero pixels out of that view
 (viewsel.Context.set_view_masks; DESIGN.md section 4 "View input" item 10).  Such a file is never a view's image, flag or no flag.
 
+Pyramid levels: with `level` K (CLI --level K, 0 .. 4) every view is textured from its photograph halved K times, what `scene::undist-L<K>`
+is to texrecon (DESIGN.md section 4 "View input" item 14): cameras are built from the level's size (texture_view.cpp:36).  A view that
+stays a file, or that goes in with its lens, is halved on the device on its way in (Context.set_views_files(levels=)); a view decoded
+here is undistorted and then halved here by the host twin (viewsel.halve_host), its mask by the same AND rule (viewsel.halve_mask_host):
+every combination of flags writes the same files.
+
 This is harness code (plumbing around the C ABI); the compute runs in libmvs_viewsel.so.
 
-CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-png] [--device-undistort] [--masks]
+CLI:  python -m mvs_texturing_amd.ingest <scene_dir> <mesh.ply> <out_prefix> [--data-term gmi|area] [--device-jpeg] [--device-png] [--device-undistort] [--masks] [--level K]
 """
 import os
 import struct
@@ -247,7 +253,7 @@ def _note_restated_models(img_path, cam):
           % (os.path.basename(img_path), "k2k4" if cam.dist[1] != 0.0 else "VisualSFM"), file=sys.stderr)
 
 
-def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False, masks=False, keep_png=False):
+def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=False, masks=False, keep_png=False, level=0):
     """A synth.Scene-like object from a folder of .cam + image pairs (and optionally a PLY mesh, prepared as
     texrecon does: tex::prepare_mesh then tex::build_adjacency_graph, both on the GPU when a mesh is given).
     keep_jpeg: a view without distortion coefficients whose file is a baseline JPEG in the format the device route accepts
@@ -263,20 +269,31 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
     the view's is refused with the file's name): s.masks[j] is the (H, W) uint8 mask or None, for Context.set_view_masks.  With
     device_undistort the mask of a distorted view stays in the camera's frame, to go in with the view's lens; without it the mask is
     undistorted here by the same rule (undistort_mask_host), so both routes give the same bits.  Without the flag mask files are
-    ignored and s.masks is None."""
+    ignored and s.masks is None.
+    level: the pyramid level, 0 .. 4.  Above 0 the cameras (s.cams) are those of the level's size, and s.levels[j] says what is left to
+    the device: `level` for a view that stays a file or goes in with its lens -- its file, pixels and mask keep the SOURCE's size
+    (s.src_sizes[j]), for Context.set_views_files(levels=) -- and 0 for a view decoded here, whose pixels are undistorted and then halved
+    here (viewsel.halve_host) and whose mask follows by the AND rule (viewsel.halve_mask_host).  With level 0 s.levels is None and
+    nothing changes."""
     from .synth import Scene
+    from .viewsel import level_size
     s = Scene()
     s.jpeg_files = []
     s.png_files = []
     s.masks = [] if masks else None
+    s.levels = [] if level else None
+    s.src_sizes = []
 
-    def take_mask(cam_path, cam, w, h, distorted):
+    def take_mask(cam_path, cam, w, h, distorted, halve_here=False):
         if not masks:
             return
         mp = mask_path_of(cam_path)
         m = load_mask(mp, w, h) if mp else None
         if m is not None and distorted and not device_undistort:
             m = undistort_mask_host(m, cam.flen, cam.dist[0], cam.dist[1])
+        if m is not None and halve_here:
+            from .viewsel import halve_mask_host
+            m = halve_mask_host(m, level)
         s.masks.append(m)
     lens = []
     cams = {"pos": [], "viewdir": [], "K": [], "w2c": [], "width": [], "height": []}
@@ -296,10 +313,14 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
                 size = jpeg_probe(data)
             if size is not None:
                 w, h = size
-                arr = camera_arrays(cam, w, h)
+                wl, hl = level_size(w, h, level)
+                arr = camera_arrays(cam, wl, hl)
                 for k in ("pos", "viewdir", "K", "w2c"):
                     cams[k].append(arr[k])
-                cams["width"].append(w); cams["height"].append(h)
+                cams["width"].append(wl); cams["height"].append(hl)
+                s.src_sizes.append((w, h))
+                if level:
+                    s.levels.append(level)
                 s.images.append(None); s.jpeg_files.append(None if is_png else data); s.png_files.append(data if is_png else None)
                 take_mask(cam_path, cam, w, h, distorted)
                 if distorted:
@@ -313,12 +334,20 @@ def load_scene(scene_dir, mesh_path=None, keep_jpeg=False, device_undistort=Fals
                 from .viewsel import undistort_image
                 img = undistort_image(img, cam.flen, cam.dist[0], cam.dist[1])
         h, w = img.shape[:2]
-        arr = camera_arrays(cam, w, h)
+        on_device = level and distorted and device_undistort   # the lens comes first: such a view is halved where it is undistorted
+        if level and not on_device:
+            from .viewsel import halve_host
+            img = halve_host(img, level)
+        wl, hl = level_size(w, h, level)
+        arr = camera_arrays(cam, wl, hl)
         for k in ("pos", "viewdir", "K", "w2c"):
             cams[k].append(arr[k])
-        cams["width"].append(w); cams["height"].append(h)
+        cams["width"].append(wl); cams["height"].append(hl)
+        s.src_sizes.append((w, h) if on_device else (wl, hl))
+        if level:
+            s.levels.append(level if on_device else 0)
         s.images.append(img)
-        take_mask(cam_path, cam, w, h, distorted)
+        take_mask(cam_path, cam, w, h, distorted, halve_here=bool(level) and not on_device)
     n = len(s.images)
     s.view_files = [j if j is not None else p for j, p in zip(s.jpeg_files, s.png_files)]
     s.lens = np.array(lens, np.float32).reshape(n, 3) if device_undistort else None
@@ -353,23 +382,26 @@ def save_scene_folder(scene, scene_dir, mesh_path=None):
         write_ply(mesh_path, scene.verts, scene.faces)
 
 
-def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False, masks=False, device_png=False):
+def run(scene_dir, mesh_path, out_prefix, data_term="gmi", outlier_removal="none", device_jpeg=False, device_undistort=False, masks=False, device_png=False, level=0):
     """texrecon.cpp:88-136 with the GPU path: writes <prefix>_data_costs.spt and <prefix>_labeling.vec.
     device_jpeg: the views that are baseline JPEG files are decoded on the device (load_scene's keep_jpeg, Context.set_views_jpeg)
     device_png: the views that are 8-bit PNG files are decoded on the device (load_scene's keep_png, Context.set_views_files); together
     with device_jpeg one set_views_files call takes the files of both kinds
     device_undistort: the views with distortion coefficients are undistorted on the device on their way in (load_scene's
     device_undistort, the `lens` of Context.set_views / set_views_jpeg / set_views_files)
-    masks: every view's NAME.mask.png, where there is one, leaves its zero pixels out of the view (load_scene's masks, Context.set_view_masks)"""
+    masks: every view's NAME.mask.png, where there is one, leaves its zero pixels out of the view (load_scene's masks, Context.set_view_masks)
+    level: the pyramid level 0 .. 4 of every view (load_scene's level; the views left to the device go through Context.set_views_files(levels=))"""
     from . import viewsel as V
-    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort, masks=masks, keep_png=device_png)
+    s = load_scene(scene_dir, mesh_path, keep_jpeg=device_jpeg, device_undistort=device_undistort, masks=masks, keep_png=device_png, level=level)
     st = V.Settings()
     st.data_term = {"area": 0, "gmi": 1}[data_term]
     st.outlier_removal = {"none": 0, "gauss_damping": 1, "gauss_clamping": 2}[outlier_removal]
     ctx = V.Context()
     try:
         ctx.set_mesh(s.verts, s.faces, s.normals)
-        if device_png:
+        if level:
+            ctx.set_views_files(s.cams, s.view_files, images=s.images, lens=s.lens, masks=s.masks, levels=s.levels, src_sizes=s.src_sizes)
+        elif device_png:
             ctx.set_views_files(s.cams, s.view_files, images=s.images, lens=s.lens, masks=s.masks)
         elif device_jpeg:
             ctx.set_views_jpeg(s.cams, s.jpeg_files, images=s.images, lens=s.lens, masks=s.masks)
@@ -396,6 +428,8 @@ if __name__ == "__main__":
     ap.add_argument("--device-png", action="store_true", help="inflate and unfilter 8-bit PNG views on the device")
     ap.add_argument("--device-undistort", action="store_true", help="undistort the views with distortion coefficients on the device, on their way in")
     ap.add_argument("--masks", action="store_true", help="NAME.mask.png beside NAME.cam leaves its zero pixels out of that view")
+    ap.add_argument("--level", type=int, default=0, choices=range(5), help="texture from every photograph halved K times (what scene::undist-L<K> is to texrecon)")
     a = ap.parse_args()
-    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort, masks=a.masks, device_png=a.device_png)
+    d, m = run(a.scene_dir, a.mesh, a.out_prefix, a.data_term, a.outlier_removal, device_jpeg=a.device_jpeg, device_undistort=a.device_undistort, masks=a.masks, device_png=a.device_png,
+               level=a.level)
     print("data costs: nnz=%d  labeling: energy=%.3f sweeps=%d unseen=%d" % (d["nnz"], m["energy"], m["sweeps"], m["unseen"]))

@@ -256,6 +256,29 @@ class LensStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in LENS_COUNTS] + [(k, C.c_float) for k in LENS_MS]
 
 
+LEVEL_COUNTS = ("views_halved", "pixels_in", "pixels_out", "pixels_no_source", "batches", "staging_bytes")
+LEVEL_MS = ("ms_upload", "ms_halve")
+LEVEL_MAX = 4
+
+
+class ViewLevel(C.Structure):
+    _fields_ = [("level", C.c_uint32), ("src_width", C.c_int32), ("src_height", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class LevelStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in LEVEL_COUNTS] + [(k, C.c_float) for k in LEVEL_MS]
+
+
+def _levels_list(levels, n):
+    """`levels` of the set_views* calls -- an int or one int per view, or (n, 2) rows with the reserved word, which must be 0 -- as two
+    lists of n ints: the levels and the reserved words"""
+    if np.ndim(levels) == 0:
+        return [int(levels)] * n, [0] * n
+    a = np.asarray(levels, dtype=np.int64).reshape(len(levels), -1)
+    assert a.shape[0] == n and a.shape[1] in (1, 2), "levels: %s for %d views" % (a.shape, n)
+    return a[:, 0].tolist(), (a[:, 1].tolist() if a.shape[1] == 2 else [0] * n)
+
+
 MASK_COUNTS = ("views_masked", "views_undistorted", "pixels", "pixels_masked_out", "device_bytes", "staging_bytes", "batches")
 MASK_MS = ("ms_upload", "ms_pack", "ms_undistort")
 
@@ -411,6 +434,10 @@ def load_library():
         "mvs_scene_set_views_lens": [vp, C.POINTER(CView), u32, C.POINTER(Lens), vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats), C.POINTER(LensStats)],
         "mvs_ctx_undistort_images": [vp, vp, vp, vp, C.POINTER(Lens), u32, i32, C.POINTER(RgbSet), C.POINTER(LensStats)],
         "mvs_undistort_image_host": [vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, vp],
+        "mvs_scene_set_views_levels": [vp, C.POINTER(CView), u32, C.POINTER(ViewLevel), C.POINTER(Lens), vp, vp, C.POINTER(JpegDecParams), C.POINTER(JpegDecStats), C.POINTER(LensStats),
+                                       C.POINTER(PngDecStats), C.POINTER(LevelStats)],
+        "mvs_ctx_halve_images": [vp, vp, vp, vp, vp, C.POINTER(Lens), u32, i32, C.POINTER(RgbSet), C.POINTER(LevelStats)],
+        "mvs_halve_image_host": [vp, C.c_int32, C.c_int32, u32, vp], "mvs_level_size": [C.c_int32, C.c_int32, u32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
         "mvs_encode_png_rle": [vp, u32, u32, C.POINTER(vp), C.POINTER(u64)], "mvs_deflate_rle": [vp, u64, C.POINTER(vp), C.POINTER(u64)],
         "mvs_debug_view_style": [u32, vp, vp], "mvs_ctx_debug_embeddings": [vp, u32, vp, vp, vp, u32, vp, i32],
         "mvs_ctx_debug_patches": [vp, vp, vp, i32, vp, i32, vp, C.POINTER(PatchParams), C.POINTER(PatchSet), i32, C.POINTER(PatchStats)],
@@ -627,14 +654,18 @@ class Context:
         self.n_faces = int(faces.shape[0])
         _check(self.L, self.L.mvs_scene_set_mesh(self.h, C.byref(m), d0))
 
-    def set_views(self, cams, images, lens=None, masks=None):
+    def set_views(self, cams, images, lens=None, masks=None, levels=None):
         """cams: dict of arrays pos, viewdir, K, w2c, width, height; images: list of (H,W,3) u8 numpy / torch cuda.
+        levels: an int or one int per view, 0 .. 4 -- set_views_files(cams, [None] * V, images=images, ..., levels=levels): the images are host
+        arrays at the SOURCE's size, cams describe the views at their level (mvs_scene_set_views_levels; returns its stats dict).
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the images are then host arrays as the camera took them, and the
         views with dist0 != 0 are undistorted on the device (mvs_scene_set_views_lens; returns the lens stats).
         masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats).
         A refused call raises MvsError and leaves the context without views (n_views == 0): data_costs then raises status 6 until a
         set_views* succeeds."""
         V = len(images)
+        if levels is not None:
+            return self.set_views_files(cams, [None] * V, images=images, lens=lens, masks=masks, levels=levels)
         if lens is not None:
             st = self._set_views_files(cams, [None] * V, images, lens, None)["lens"]
             if masks is not None:
@@ -672,15 +703,16 @@ class Context:
         ok = rc == 0
         self._keep["views"] = held if ok else None
         self._view_sizes = [(int(cams["width"][j]), int(cams["height"][j])) for j in range(V)] if ok else []
+        self._mask_sizes = list(self._view_sizes)   # (set_views_files(levels=) puts the sources' sizes here)
         self.n_views = V if ok else 0
 
     @staticmethod
-    def _pixel_views(arr, files, images):
+    def _pixel_views(arr, files, images, levels=None):
         """the views without a file bring host pixels: arr[j].rgb points into the returned arrays, which the caller holds during the call"""
         pixels = [None if f is not None else np.ascontiguousarray(images[j], np.uint8) for j, f in enumerate(files)]
         for j, px in enumerate(pixels):
             if px is not None:
-                assert px.shape == (arr[j].height, arr[j].width, 3)
+                assert px.ndim == 3 and px.shape[2] == 3 and (levels is not None or px.shape == (arr[j].height, arr[j].width, 3))
                 arr[j].rgb = px.ctypes.data_as(C.c_void_p)
         return pixels
 
@@ -731,7 +763,9 @@ class Context:
         the pixel out, anything else = keep -- or None for a view without one (all of them host arrays or all of them device tensors).  A
         masked pixel is an invalid pixel and nothing else changes (DESIGN.md section 4 "View input").  After any set_views*, before
         data_costs; None or all None clears the masks, and so does every later set_views*.  lens: the (n, 3) array of set_views(lens=) --
-        the masks of views with dist0 != 0 are then in the frame the camera took and are undistorted on the device.  Returns the stats
+        the masks of views with dist0 != 0 are then in the frame the camera took and are undistorted on the device.  The mask of a view that
+        came with a pyramid level > 0 (set_views*(levels=)) has the SOURCE's size; the level keeps a pixel iff everything that went into it
+        is kept.  Returns the stats
         (also self.mask_stats); a refusal raises MvsError with them as `.stats` and leaves the context without masks."""
         V = getattr(self, "n_views", 0)
         masks = [None] * V if masks is None else list(masks)
@@ -749,9 +783,9 @@ class Context:
                 d = 0
             assert dev is None or dev == d, "host and device masks in one call"
             dev = d
-            if j < len(getattr(self, "_view_sizes", [])):
-                w, h = self._view_sizes[j]
-                assert tuple(m.shape) == (h, w), "view %d: the mask is %s, the view %d x %d" % (j, tuple(m.shape), w, h)
+            if j < len(getattr(self, "_mask_sizes", [])):
+                w, h = self._mask_sizes[j]
+                assert tuple(m.shape) == (h, w), "view %d: the mask is %s, the view (at its source's size) %d x %d" % (j, tuple(m.shape), w, h)
             held.append(m)
         ptrs = (C.c_void_p * max(n, 1))(*[None if m is None else (m.data_ptr() if dev else m.ctypes.data) for m in held])
         if dev:
@@ -801,7 +835,7 @@ class Context:
         w, h = self._view_sizes[j]
         return buf.reshape(h, w, 3)
 
-    def set_views_jpeg(self, cams, files, params=None, images=None, lens=None, masks=None):
+    def set_views_jpeg(self, cams, files, params=None, images=None, lens=None, masks=None, levels=None):
         """mvs_scene_set_views_jpeg: set_views with the images taken from baseline JPEG files (a list of bytes), decoded on the device
         straight into the context's image buffers (DESIGN.md section 4 "View input").  The frames' sizes must be cams' width / height.
         A view whose entry in `files` is None brings its pixels as images[j], an (H, W, 3) uint8 host array.
@@ -809,7 +843,10 @@ class Context:
         then raises status 6 until a set_views* succeeds.
         lens: an (n, 3) float32 array of (flen, dist0, dist1) per view -- the views with dist0 != 0, files and pixels alike, are undistorted
         on the device (mvs_scene_set_views_lens); the stats then carry the lens stats under "lens".
-        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats)."""
+        masks: set_view_masks(masks, lens=lens) behind the views (its stats: self.mask_stats).
+        levels: set_views_files(..., levels=levels), which see (its stats dict comes back)."""
+        if levels is not None:
+            return self.set_views_files(cams, files, params=params, images=images, lens=lens, masks=masks, levels=levels)
         st = self._set_views_files(cams, files, images, lens, params)
         if masks is not None:
             self.set_view_masks(masks, lens=lens)
@@ -839,25 +876,67 @@ class Context:
         _check_with_stats(self.L, rc, stats)
         return self._rgb_set_images(res, n, None, on_device), stats
 
-    def set_views_files(self, cams, files, params=None, images=None, lens=None, masks=None):
+    def set_views_files(self, cams, files, params=None, images=None, lens=None, masks=None, levels=None, src_sizes=None):
         """mvs_scene_set_views_files: set_views_jpeg whose files may also be PNGs -- a file that starts with the PNG signature is inflated and
         unfiltered on the device, any other file takes the JPEG route, an entry None brings its pixels as images[j].  lens and masks as
         set_views_jpeg.  Returns {"png": ..., "jpeg": ..., "lens": ...}, the three routes' stats; a refusal raises MvsError with them as
-        `.stats` and leaves the context without views."""
+        `.stats` and leaves the context without views.
+        levels: an int or one int per view, 0 .. 4 -- pyramid levels (mvs_scene_set_views_levels; DESIGN.md section 4 "View input" item 14):
+        files and images come at the SOURCE's size and are decoded, undistorted and halved `level` times on the device, cams describe the
+        views AT THEIR LEVEL (level_size of the source), masks have the source's size.  The stats then carry "level".  src_sizes: every
+        view's source (width, height) where the caller knows better than the files' headers and the images' shapes.  None: this call
+        without levels, untouched."""
         V = len(files)
         arr = self._view_array(cams, V)
         held, ptrs, sizes = self._file_arrays(files)
-        pixels = self._pixel_views(arr, files, images)   # (held during the call)
-        jst, pst, ls = JpegDecStats(), PngDecStats(), LensStats()
+        pixels = self._pixel_views(arr, files, images, levels)   # (held during the call)
+        jst, pst, ls, vs = JpegDecStats(), PngDecStats(), LensStats(), LevelStats()
         any_file = any(f is not None for f in files)
-        rc = self.L.mvs_scene_set_views_files(self.h, arr, V, _lens_array(lens, V) if lens is not None else None, ptrs if any_file else None, sizes if any_file else None,
-                                              C.byref(params) if params is not None else None, C.byref(jst), C.byref(pst), C.byref(ls))
-        stats = {"png": _png_stats_dict(pst), "jpeg": _stats_dict(jst), "lens": _stats_dict(ls)}
+        la = _lens_array(lens, V) if lens is not None else None
+        pp = C.byref(params) if params is not None else None
+        if levels is None:
+            rc = self.L.mvs_scene_set_views_files(self.h, arr, V, la, ptrs if any_file else None, sizes if any_file else None, pp, C.byref(jst), C.byref(pst), C.byref(ls))
+            stats = {"png": _png_stats_dict(pst), "jpeg": _stats_dict(jst), "lens": _stats_dict(ls)}
+        else:
+            lv, reserved = _levels_list(levels, V)
+            src = [self._source_size(held[j], pixels[j], arr[j], lv[j]) for j in range(V)] if src_sizes is None else [tuple(int(v) for v in s) for s in src_sizes]
+            va = (ViewLevel * max(V, 1))()
+            for j in range(V):
+                va[j].level, va[j].src_width, va[j].src_height, va[j].reserved = lv[j], src[j][0], src[j][1], reserved[j]
+            rc = self.L.mvs_scene_set_views_levels(self.h, arr, V, va, la, ptrs if any_file else None, sizes if any_file else None, pp, C.byref(jst), C.byref(ls), C.byref(pst), C.byref(vs))
+            stats = {"png": _png_stats_dict(pst), "jpeg": _stats_dict(jst), "lens": _stats_dict(ls), "level": _stats_dict(vs)}
         self._views_set(V, cams, rc)
+        if levels is not None and rc == 0:
+            self._mask_sizes = src
         _check_with_stats(self.L, rc, stats)
         if masks is not None:
             self.set_view_masks(masks, lens=lens)
         return stats
+
+    @staticmethod
+    def _source_size(file, pixels, view, level):
+        """(width, height) of a view's source: its pixels' shape, its file's header -- or, for a file no probe reads, the size the level
+        implies, so that the library refuses the file in its own words"""
+        if pixels is not None:
+            return int(pixels.shape[1]), int(pixels.shape[0])
+        return png_probe(file) or jpeg_probe(file) or (int(view.width) << level, int(view.height) << level)
+
+    def halve_images(self, images, levels, lens=None, on_device=False):
+        """mvs_ctx_halve_images: the level route on its own -- `images` (a list of (H, W, 3) uint8 host arrays) halved levels[i] times (an int:
+        all alike), under lens[i] = (flen, dist0, dist1) undistorted first, in one call.  Returns (images, stats) as undistort_images does.
+        The same bytes as halve_host (of undistort_host) gives."""
+        n = len(images)
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in images]
+        assert all(i.ndim == 3 and i.shape[2] == 3 for i in imgs)
+        lv, _ = _levels_list(levels, n)
+        ptrs = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in imgs])
+        w = (C.c_uint32 * max(n, 1))(*[i.shape[1] for i in imgs]); h = (C.c_uint32 * max(n, 1))(*[i.shape[0] for i in imgs])
+        la = (C.c_uint32 * max(n, 1))(*lv)
+        res, st = RgbSet(), LevelStats()
+        rc = self.L.mvs_ctx_halve_images(self.h, ptrs, w, h, la, _lens_array(lens, n) if lens is not None else None, n, 1 if on_device else 0, C.byref(res), C.byref(st))
+        stats = _stats_dict(st)
+        _check_with_stats(self.L, rc, stats)
+        return self._rgb_set_images(res, n, None, on_device), stats
 
     def set_face_range(self, begin, end):
         """positions [begin, end) of the library's face order (the caller's ids with option face_order = 0)"""
@@ -1639,7 +1718,7 @@ def _scene_context(scene, ctx):
     ctx = ctx or Context()
     try:
         ctx.set_mesh(scene.verts, scene.faces, scene.normals)
-        ctx.set_views(scene.cams, scene.images, masks=getattr(scene, "masks", None))
+        ctx.set_views(scene.cams, scene.images, masks=getattr(scene, "masks", None), levels=getattr(scene, "levels", None))
         yield ctx
     finally:
         if own:
@@ -1819,6 +1898,37 @@ def undistort_host(rgb, flen, dist0, dist1):
     out = np.empty_like(rgb)
     _check(L, L.mvs_undistort_image_host(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], float(flen), float(dist0), float(dist1), out.ctypes.data))
     return out
+
+
+def level_size(width, height, level):
+    """mvs_level_size: (width, height) of a width x height image at pyramid level `level` (0 .. 4): halved `level` times, rounding up"""
+    L = load_library()
+    wl, hl = C.c_int32(), C.c_int32()
+    _check(L, L.mvs_level_size(int(width), int(height), int(level), C.byref(wl), C.byref(hl)))
+    return wl.value, hl.value
+
+
+def halve_host(rgb, level):
+    """mvs_halve_image_host: an (H, W, 3) uint8 image at pyramid level `level` by the sequential host twin of csrc/level.h -- no GPU; the
+    bytes the device route leaves (DESIGN.md section 4 "View input" item 14)"""
+    L = load_library()
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    wl, hl = level_size(rgb.shape[1], rgb.shape[0], level)
+    out = np.empty((hl, wl, 3), np.uint8)
+    _check(L, L.mvs_halve_image_host(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], int(level), out.ctypes.data))
+    return out
+
+
+def halve_mask_host(mask, level):
+    """the keep rule of a pyramid level on the host: an (H, W) mask (0 = leave out) -> the level's (0 / 255): a level pixel is kept iff
+    every source pixel of its clamped 2^level x 2^level block is kept"""
+    m = (np.ascontiguousarray(mask) != 0)
+    for _ in range(int(level)):
+        h, w = m.shape
+        ys, xs = np.minimum(np.arange(0, h + (h & 1), 2) + 1, h - 1), np.minimum(np.arange(0, w + (w & 1), 2) + 1, w - 1)
+        m = m[0::2][:, 0::2] & m[0::2][:, xs] & m[ys][:, 0::2] & m[ys][:, xs]
+    return m.astype(np.uint8) * 255
 
 
 def partition_faces(verts, faces, world=1):
